@@ -10,7 +10,8 @@ Default workload = BASELINE.json configs[1]: one synthetic HDL-64E pair of 64 x 
 (laser_slam/src/laser_track.cpp:496) = lsgpu_icp_compute: reference filter (SamplingSurfaceNormal), centring + voxel
 grid, reading filter, then {transform, exact 1-NN, trimmed weights, point-to-plane 6x6} until the (tightened, 1e-4 m /
 1e-5 rad) differential checker stops it -- on RAW clouds that are resident in HBM when the timed region starts.
-`value` = scans/s of that step.  Reported beside it in the same line:
+`value` = scans/s of that step.  A plain run sets up, warms up, times the steps and prints the headline; with --full the
+same line also carries:
   value_loop  the resident loop alone (set_reference + align on already filtered clouds: the north-star kernels)
   value_e2e   the same compute handed HOST buffers (H2D + D2H inclusive; pageable / pinned) -- never `value`
 With N > 1 every rank registers its own pair (embarrassingly parallel, no data-path collective; "weak" scaling).
@@ -21,6 +22,11 @@ With N > 1 every rank registers its own pair (embarrassingly parallel, no data-p
 --split  BASELINE configs[3]: ONE 8.4 M-point local map (8 scans in one frame) vs ONE 1 M-point scan per step, the
          reading sharded over the ranks, RCCL all-reduce of the select tables + 29 f64 per iteration; value = scans/s
          ("strong").  --split-pair uses the configs[1] pair instead (what round 2 measured on one rank).
+
+--full          also the side figures: value_loop, value_e2e, compute_variants, the rooflines (extra profiled steps), the
+                CPU baseline, value_track, and --split's yaml_checker / split_exchange.  Off by default.
+--dump-outputs DIR  after the timed steps, what the last timed step returned (rank 0) as DIR/<name>.npy: the transform(s)
+                and the result fields of the statistics; the inputs are seeded, so two builds compare output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -96,6 +102,18 @@ def _free_port() -> int:
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def dump_outputs(out_dir: str, T, stats, extra=None) -> None:
+    """--dump-outputs: what the last timed step returned -- the transform(s) as the caller receives them (float32) and the
+    result fields of IcpStats, one entry per alignment (float64; the clocks are left out, they differ from run to run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"transform": np.asarray(T, np.float32)}
+    for k in ("iterations", "converged", "final_limit", "final_n_used"):
+        arrays[k] = np.array([getattr(s, k) for s in stats], np.float64)
+    arrays.update(extra or {})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def track_section(n_az: int, n_scans: int, cpu_threads: int):
@@ -293,7 +311,14 @@ def main():
                     help="no GPU: the launch / rendezvous / sharding / handshake / reduction plumbing of the chosen mode on the gloo\n"
                          "backend with a small host workload, so that a multi-GPU lease is not spent finding a typo in it")
     ap.add_argument("--dry-run-dead-rank", type=int, default=-1, help="(with --dry-run) this rank leaves before the first exchange: the others must give up, not hang")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side figures (loop / host-buffer / variant timings, rooflines, CPU baseline, value_track,\n"
+                         "--split's yaml_checker and split_exchange); without it a run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if needs_relaunch(args.gpus, os.environ):
         # `python bench.py --gpus 8` (no launcher): become N ranks of this node, default / --batch / --split alike
@@ -379,6 +404,8 @@ def main():
             T, st, rc = step_batch()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, T, st, {"return_code": rc.astype(np.float64)})
         err = max((synth.pose_error(T[i].astype(np.float64), Tts[i])[0] for i in range(len(pairs))), default=0.0)
         out = dict(base, metric="scan_pairs_per_sec", value=args.batch_pairs * args.steps / elapsed, unit="pairs/s",
                    ms_per_step=elapsed / args.steps * 1e3, scaling="strong",
@@ -436,14 +463,14 @@ def main():
     nq, nr = rd.shape[0], int(d_ref.shape[0])
 
     h = icp.IcpHandle(cfg, local_rank)
-    # second handle, identical but with a HIP-event pair around every kNN launch: used for a few extra
+    # second handle (--full), identical but with a HIP-event pair around every kNN launch: used for a few extra
     # steps right after the timed region (event records inside the timed region cost ~5 % throughput)
     cfg_p = IcpConfig()
     C.memmove(C.byref(cfg_p), C.byref(cfg), C.sizeof(cfg))
     cfg_p.profile_kernels = 1
-    hp = icp.IcpHandle(cfg_p, local_rank)
+    hp = icp.IcpHandle(cfg_p, local_rank) if args.full else None
     if args.split:
-        for hh in (h, hp):
+        for hh in (h, hp) if hp else (h,):
             sharding.init_split_comm(hh, device="cuda")
 
     def step_loop(hh=h):       # the resident loop: steps 2-7 of ICP::compute on filtered clouds
@@ -472,12 +499,14 @@ def main():
         n_converged += int(st.converged)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, T, [st])
 
-    # ---- the resident loop alone (value_loop), then the profiled steps for the rooflines
+    # ---- (--full) the resident loop alone (value_loop), then the profiled steps for the rooflines
     loop_steps = max(1, min(args.steps, 10))
     value_loop = None
     align_ms, loop_iters = 0.0, 0
-    if not args.split and not args.no_compute_e2e:
+    if args.full and not args.split and not args.no_compute_e2e:
         step_loop(); step_loop()
         torch.cuda.synchronize()
         per_step = []
@@ -497,27 +526,28 @@ def main():
     prof_steps = max(1, min(args.steps, 3))
     sel_ms = ne_ms = knn_ms = knn_main_ms = knn_fb_ms = comm_ms = 0.0
     knn_launches = strag = comm_calls = 0
-    step_loop(hp)
-    for _ in range(prof_steps):
-        Tp, stp = step_loop(hp)
-        knn_ms += stp.t_knn_ms
-        knn_main_ms += stp.t_knn_main_ms
-        knn_fb_ms += stp.t_knn_fallback_ms
-        knn_launches += stp.knn_launches
-        strag += stp.stragglers
-        sel_ms += stp.t_select_ms
-        ne_ms += stp.t_ne_ms
-        comm_ms += stp.t_comm_ms
-        comm_calls += stp.comm_calls
-    # the last profiled step's searches one by one (search kernel + hand-over pass, us): the first launches and the settled
-    # ones are different kernels with different costs, the average alone hides which is which
-    knn_per_iter = [round(float(t["knn_main_us"] + t["knn_fallback_us"]), 1) for t in hp.trace()]
-    loop_equals_compute = bool(np.array_equal(Tp, T))   # (chain F keeps every point: the loop on filtered clouds is the same alignment)
+    if args.full:
+        step_loop(hp)
+        for _ in range(prof_steps):
+            Tp, stp = step_loop(hp)
+            knn_ms += stp.t_knn_ms
+            knn_main_ms += stp.t_knn_main_ms
+            knn_fb_ms += stp.t_knn_fallback_ms
+            knn_launches += stp.knn_launches
+            strag += stp.stragglers
+            sel_ms += stp.t_select_ms
+            ne_ms += stp.t_ne_ms
+            comm_ms += stp.t_comm_ms
+            comm_calls += stp.comm_calls
+        # the last profiled step's searches one by one (search kernel + hand-over pass, us): the first launches and the settled
+        # ones are different kernels with different costs, the average alone hides which is which
+        knn_per_iter = [round(float(t["knn_main_us"] + t["knn_fallback_us"]), 1) for t in hp.trace()]
+        loop_equals_compute = bool(np.array_equal(Tp, T))   # (chain F keeps every point: the loop on filtered clouds is the same alignment)
 
-    # ---- the same compute handed HOST buffers (H2D + D2H inclusive), chains F and P, pageable and pinned
+    # ---- (--full) the same compute handed HOST buffers (H2D + D2H inclusive), chains F and P, pageable and pinned
     value_e2e = None
     variants = None
-    if not args.split and not args.no_compute_e2e and world == 1:   # (the PCIe-inclusive side figures: one rank only)
+    if args.full and not args.split and not args.no_compute_e2e and world == 1:   # (the PCIe-inclusive side figures: one rank only)
         variants = {}
         for name, prob, ratio in (("P_yaml_chain", 0.5, 0.5),):
             ts = []
@@ -563,26 +593,6 @@ def main():
             value_e2e["host_to_device_copy_of_one_raw_cloud"] = {"error": str(e)}
         h.set_reference(d_ref, d_nrm)
 
-    info = h.info()
-    ncell = int(info.cells[0])
-    # algorithmic bytes of one kNN launch: 24 Nq + 16 Nr + 8 Ncell
-    b_knn = 24 * nq + 16 * nr + 8 * ncell
-    t_knn = knn_ms / max(knn_launches, 1) * 1e-3
-    achieved = b_knn / t_knn / 1e9 if t_knn > 0 else 0.0
-    # HBM traffic of the kernel: PMC counters cannot be read from inside the process, so the figure comes from the
-    # artifact of the separate rocprofv3 --pmc passes (devtools/gpu_check.sh pmc) -- only if it was measured on THESE
-    # kernel sources (csrc_sha) and this workload; otherwise null
-    traffic, traffic_note = None, "no PMC artifact for these kernel sources (profiles/knn_traffic.json csrc_sha mismatch or absent)"
-    tpath = os.path.join(ROOT, "profiles", "knn_traffic.json")
-    if os.path.exists(tpath) and not args.split:
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("n_az") == args.n_az and tj.get("csrc_sha") == base["csrc_sha"]:
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_note = "profiles/knn_traffic.json (separate --pmc FETCH_SIZE / WRITE_SIZE passes on these kernel sources)"
-        except Exception:
-            traffic = None
-
     et, er = synth.pose_error(T.astype(np.float64), T_true)
     units = 1 if args.split else world
     out = dict(base, metric="scans_per_sec", value=units * args.steps / elapsed, unit="scans/s",
@@ -600,9 +610,9 @@ def main():
         out["filters_and_grid_ms_per_step"] = filt_ms / args.steps
         out["ms_per_icp_iteration"] = (elapsed / args.steps * 1e3 - filt_ms / args.steps) / max(iters / args.steps, 1)
         out["value_is"] = ("the whole ICP::compute (lsgpu_icp_compute: reference filter + grid + reading filter + loop) on RAW clouds "
-                           "resident in HBM; value_loop = the loop alone on filtered clouds; value_e2e = the same compute from host "
-                           "buffers (PCIe inclusive)")
-    if args.split:
+                           "resident in HBM; with --full, value_loop = the loop alone on filtered clouds; value_e2e = the same compute "
+                           "from host buffers (PCIe inclusive)")
+    if args.split and args.full:
         # The differential checker at 1e-4 m / 1e-5 rad (configs[1]'s tolerance) does not stop this registration before
         # max_iterations: against an 8-scan map -- eight noisy samples of every surface -- the trimmed point-to-plane steps
         # shrink to ~1e-4 m and stay there for dozens of iterations, whatever the guess (3 cm: 35 iterations at 0.5 M points
@@ -657,45 +667,65 @@ def main():
     out["config"] = {"workload": workload, "n_reading": nq, "n_reference": nr, "pairs_per_gpu_per_step": 1,
                      "sharding": ("one scan pair per step, reading sharded over ranks, RCCL all-reduce of the select tables + 29 f64 "
                                   "per iteration" if args.split else "one scan pair per rank, no collective")}
-    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                       "kernel": "k_knn_cone (direction-indexed search, iterations >= 2) / k_knn_tile + k_knn_fallback (voxel-grid search, iterations 0-1) -- exact 1-NN correspondence search",
-                       "per_iteration_us": knn_per_iter,
-                       "algorithmic_bytes_per_launch": b_knn,
-                       "avg_launch_us": t_knn * 1e6,
-                       "avg_main_us": knn_main_ms / max(knn_launches, 1) * 1e3,
-                       "avg_fallback_us": knn_fb_ms / max(knn_launches, 1) * 1e3,
-                       "launches": knn_launches, "timed_in": "%d extra profiled steps of the resident loop after the timed region (HIP events on the handle's stream)" % prof_steps,
-                       "occupied_cells": ncell,
-                       "stragglers_per_launch": strag / max(knn_launches, 1)}
-    if traffic and t_knn > 0:   # SURVEY.md 8d "roofline.measured": the literal rocprof HBM GB/s of the launch
-        out["roofline"]["measured"] = traffic / t_knn / 1e9
-        out["roofline"]["measured_frac"] = traffic / t_knn / 1e9 / HBM_PEAK_GBS
-        out["roofline"]["traffic_over_algorithmic"] = traffic / b_knn
-    # second yardstick for a kernel that is vector-issue bound, not byte bound: the distance evaluations an ideal
-    # per-query search would need (a libnabo kd-tree with bucket size 8 visits 20-30 points per query) x the
-    # 7.75 vector operations one evaluation costs (6 for the defined arithmetic, 1.75 for minimum / runner-up / index),
-    # against what the chip's vector units could issue during the launch (256 CUs x 4 SIMDs x 16 lanes at 2.4 GHz)
-    if t_knn > 0:
-        ideal_ops = nq * 25 * 7.75
-        peak_lane_ops = 256 * 4 * 16 * 2.4e9
-        out["roofline"]["valu_frac"] = ideal_ops / (t_knn * peak_lane_ops)
-        out["roofline"]["valu_frac_is"] = ("(Nq x 25 kd-tree-equivalent distance evaluations x 7.75 lane-ops) / (launch time x 256 CUs x 4 SIMDs x "
-                                           "16 lanes x 2.4 GHz): the share of the launch's vector issue slots an ideal search would need")
     out["final_error_vs_truth"] = {"trans_m": et, "rot_rad": er}
-    out["profiled_loop_transform_equals_timed_compute"] = loop_equals_compute
-    # the other two per-iteration kernel groups against the same HBM roofline (B_trim = 4 Nq, B_ne = 52 Nq)
-    n_it = max(knn_launches, 1)
-    t_sel, t_ne = sel_ms / n_it * 1e-3, ne_ms / n_it * 1e-3
-    if t_sel > 0 and t_ne > 0:
-        out["roofline_select"] = {"bound": "hbm", "kernel": "k_hist1 + k_hist_refine<2> + k_hist_refine<3> (exact radix select of the trim limit)",
-                                  "algorithmic_bytes_per_iteration": 4 * nq, "avg_us": t_sel * 1e6,
-                                  "achieved": 4 * nq / t_sel / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": 4 * nq / t_sel / 1e9 / HBM_PEAK_GBS}
-        out["roofline_ne"] = {"bound": "hbm", "kernel": "k_normal_eq_loop (point-to-plane normal equations + solve + checkers)",
-                              "algorithmic_bytes_per_iteration": 52 * nq, "avg_us": t_ne * 1e6,
-                              "achieved": 52 * nq / t_ne / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": 52 * nq / t_ne / 1e9 / HBM_PEAK_GBS}
+    if args.full:
+        info = h.info()
+        ncell = int(info.cells[0])
+        # algorithmic bytes of one kNN launch: 24 Nq + 16 Nr + 8 Ncell
+        b_knn = 24 * nq + 16 * nr + 8 * ncell
+        t_knn = knn_ms / max(knn_launches, 1) * 1e-3
+        achieved = b_knn / t_knn / 1e9 if t_knn > 0 else 0.0
+        # HBM traffic of the kernel: PMC counters cannot be read from inside the process, so the figure comes from the
+        # artifact of the separate rocprofv3 --pmc passes (devtools/gpu_check.sh pmc) -- only if it was measured on THESE
+        # kernel sources (csrc_sha) and this workload; otherwise null
+        traffic, traffic_note = None, "no PMC artifact for these kernel sources (profiles/knn_traffic.json csrc_sha mismatch or absent)"
+        tpath = os.path.join(ROOT, "profiles", "knn_traffic.json")
+        if os.path.exists(tpath) and not args.split:
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("n_az") == args.n_az and tj.get("csrc_sha") == base["csrc_sha"]:
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_note = "profiles/knn_traffic.json (separate --pmc FETCH_SIZE / WRITE_SIZE passes on these kernel sources)"
+            except Exception:
+                traffic = None
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+                           "kernel": "k_knn_cone (direction-indexed search, iterations >= 2) / k_knn_tile + k_knn_fallback (voxel-grid search, iterations 0-1) -- exact 1-NN correspondence search",
+                           "per_iteration_us": knn_per_iter,
+                           "algorithmic_bytes_per_launch": b_knn,
+                           "avg_launch_us": t_knn * 1e6,
+                           "avg_main_us": knn_main_ms / max(knn_launches, 1) * 1e3,
+                           "avg_fallback_us": knn_fb_ms / max(knn_launches, 1) * 1e3,
+                           "launches": knn_launches, "timed_in": "%d extra profiled steps of the resident loop after the timed region (HIP events on the handle's stream)" % prof_steps,
+                           "occupied_cells": ncell,
+                           "stragglers_per_launch": strag / max(knn_launches, 1)}
+        if traffic and t_knn > 0:   # SURVEY.md 8d "roofline.measured": the literal rocprof HBM GB/s of the launch
+            out["roofline"]["measured"] = traffic / t_knn / 1e9
+            out["roofline"]["measured_frac"] = traffic / t_knn / 1e9 / HBM_PEAK_GBS
+            out["roofline"]["traffic_over_algorithmic"] = traffic / b_knn
+        # second yardstick for a kernel that is vector-issue bound, not byte bound: the distance evaluations an ideal
+        # per-query search would need (a libnabo kd-tree with bucket size 8 visits 20-30 points per query) x the
+        # 7.75 vector operations one evaluation costs (6 for the defined arithmetic, 1.75 for minimum / runner-up / index),
+        # against what the chip's vector units could issue during the launch (256 CUs x 4 SIMDs x 16 lanes at 2.4 GHz)
+        if t_knn > 0:
+            ideal_ops = nq * 25 * 7.75
+            peak_lane_ops = 256 * 4 * 16 * 2.4e9
+            out["roofline"]["valu_frac"] = ideal_ops / (t_knn * peak_lane_ops)
+            out["roofline"]["valu_frac_is"] = ("(Nq x 25 kd-tree-equivalent distance evaluations x 7.75 lane-ops) / (launch time x 256 CUs x 4 SIMDs x "
+                                               "16 lanes x 2.4 GHz): the share of the launch's vector issue slots an ideal search would need")
+        out["profiled_loop_transform_equals_timed_compute"] = loop_equals_compute
+        # the other two per-iteration kernel groups against the same HBM roofline (B_trim = 4 Nq, B_ne = 52 Nq)
+        n_it = max(knn_launches, 1)
+        t_sel, t_ne = sel_ms / n_it * 1e-3, ne_ms / n_it * 1e-3
+        if t_sel > 0 and t_ne > 0:
+            out["roofline_select"] = {"bound": "hbm", "kernel": "k_hist1 + k_hist_refine<2> + k_hist_refine<3> (exact radix select of the trim limit)",
+                                      "algorithmic_bytes_per_iteration": 4 * nq, "avg_us": t_sel * 1e6,
+                                      "achieved": 4 * nq / t_sel / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": 4 * nq / t_sel / 1e9 / HBM_PEAK_GBS}
+            out["roofline_ne"] = {"bound": "hbm", "kernel": "k_normal_eq_loop (point-to-plane normal equations + solve + checkers)",
+                                  "algorithmic_bytes_per_iteration": 52 * nq, "avg_us": t_ne * 1e6,
+                                  "achieved": 52 * nq / t_ne / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": 52 * nq / t_ne / 1e9 / HBM_PEAK_GBS}
     if value_loop is not None:
         out["value_loop"] = value_loop
     if value_e2e is not None:
@@ -709,9 +739,9 @@ def main():
     if variants is not None:
         out["compute_variants"] = variants
 
-    # ---- CPU baseline: the oracle (port) on this box's host cores, same workload and SAME region as `value`
+    # ---- (--full) CPU baseline: the oracle (port) on this box's host cores, same workload and SAME region as `value`
     # (both filters + kd-tree build + loop), rank 0, N=1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.split:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.split:
         from oracle import oracle_py as O
         ocfg = O.config_yaml(accum_double=0, min_diff_rot=1e-5, min_diff_trans=1e-4, num_threads=args.cpu_threads,
                              reading_sampling_prob=1.0, surface_normal_knn=10, surface_normal_ratio=1.0)
@@ -746,9 +776,9 @@ def main():
             best = max(tried.values(), key=lambda r: r["value"])
             out["cpu_baseline"]["all_threads"] = dict(best, tried={str(k): round(v["value"], 4) for k, v in tried.items()},
                                                       host_threads=os.cpu_count())
-    # ---- the reference's own timed region (value_track) and the real call shape of localScanToSubMap: a reference of
+    # ---- (--full) the reference's own timed region (value_track) and the real call shape of localScanToSubMap: a reference of
     # three scans (compute_variants.F_submap3 / P_submap3)
-    if rank == 0 and world == 1 and not args.no_track and not args.no_compute_e2e and not args.split:
+    if args.full and rank == 0 and world == 1 and not args.no_track and not args.no_compute_e2e and not args.split:
         try:
             trk, scans, poses = track_section(args.n_az, args.track_scans, args.cpu_threads)
             out["value_track"] = trk
@@ -781,7 +811,8 @@ def main():
     if rank == 0:
         print(json.dumps(out))
     h.close()
-    hp.close()
+    if hp is not None:
+        hp.close()
     if world > 1:
         dist.destroy_process_group()
 
