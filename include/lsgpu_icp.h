@@ -56,8 +56,20 @@ typedef struct lsgpu_icp_config {
   int   smooth_length;    /* Differential... smoothLength              yaml:27  (4)     */
   float cell_size;        /* finest voxel edge [m]; <= 0: automatic                      */
   int   profile_kernels;  /* 1: HIP-event time every kNN launch (see lsgpu_icp_stats)    */
-  int   reserved[8];      /* reserved[0] = 1 disables the trimmed-radius cap (debug)       */
+  int   reserved[1];      /* reserved[0] = 1 disables the trimmed-radius cap (debug)       */
+  int   error_minimizer;  /* LSGPU_MINIMIZER_* (0, the default: point-to-plane); any other value: LSGPU_BAD_CONFIG */
+  int   reserved_[6];
 } lsgpu_icp_config;
+
+/* errorMinimizer modules (lsgpu_icp_config.error_minimizer).  Point-to-plane (yaml:18-19) solves the 6x6 normal
+ * equations of J = [p x n; n] and needs the reference normals.  Point-to-point (libpointmatcher's
+ * PointToPointErrorMinimizer) needs none: with the trimmed pairs' centroids p_, q_ and M = sum (q - q_)(p - p_)^T
+ * = U S V^T, R = U V^T (U diag(1,1,-1) V^T if det < 0), t = q_ - R p_, and T_iter <- [R t] T_iter.  Sums in double,
+ * the 3x3 solve in double (Horn's quaternion, Jacobi eigen-solver with an exact stopping rule), R and t rounded to
+ * float.  A point-to-point handle never reads reference normals: set_reference / align_batch accept NULL normals, and
+ * lsgpu_chain_config.ssn_knn = 0 (no reference filter module) is accepted. */
+#define LSGPU_MINIMIZER_POINT_TO_PLANE 0
+#define LSGPU_MINIMIZER_POINT_TO_POINT 1
 
 /* icp_default.yaml values / ICP::setDefault() values (laser_track.cpp:17,20). */
 void lsgpu_icp_config_yaml(lsgpu_icp_config* c);
@@ -101,7 +113,8 @@ typedef struct lsgpu_iter_trace {
   int64_t n_used;
   double  A[36];
   double  b[6];
-  double  x[6];
+  double  x[6];             /* point-to-point handles: A[0..8] = the centred M (row major, rest 0), b = {p_, q_},
+                             * x = {rotation vector of R, t} */
   float   knn_main_us;      /* k_knn_tile duration (HIP events; 0 unless profile_kernels) */
   float   knn_fallback_us;  /* k_knn_fallback duration                                    */
   uint32_t stragglers;      /* queries resolved by the fallback in this iteration         */
@@ -113,7 +126,8 @@ int  lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out);
 void lsgpu_icp_destroy(lsgpu_icp* h);
 
 /* Steps 2-3 of ICP::compute: centre the (already filtered) reference on its mean, build the voxel
- * grid.  `normals` = the descriptor SamplingSurfaceNormalDataPointsFilter attached (yaml:5-7). */
+ * grid.  `normals` = the descriptor SamplingSurfaceNormalDataPointsFilter attached (yaml:5-7); may be NULL (a
+ * point-to-point handle reads no normals). */
 int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* ref_normals, int64_t nr);
 
 /* Steps 5-7 of ICP::compute on the (already filtered) reading.  T_out = T_init on failure.  A T_init that is not rigid
@@ -132,6 +146,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
  * T_out[i] = T_init[i], like lsgpu_icp_align); the function returns the first non-OK, non-NO_CONVERGENCE
  * code, else LSGPU_NO_CONVERGENCE if any pair failed to converge, else LSGPU_OK.
  * T_init / T_out: 16 floats per pair, column major.  stats and rc may be NULL.
+ * reference_normals[i] may be NULL for point-to-point handles (LSGPU_MINIMIZER_POINT_TO_POINT).
  * Reference reuse: a pair whose reference_xyz1[i], reference_normals[i] and n_reference[i] equal those of the previous
  * pair of the same handle (pair i - n_handles) skips set_reference -- the sorted reference, chunks and cell tables depend
  * on the reference alone (stats[i].reference_reused = 1 for such a pair).  Results are bit-identical either way. */
@@ -198,6 +213,14 @@ int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, floa
  * order a<=c), 6 of -sum J r, sum w, sum w r^2  -> double[29]. */
 int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
                     const int32_t* ids, const float* d2, float limit, double out[29]);
+/* PointToPointErrorMinimizer accumulation, same inputs as lsgpu_normal_eq: out[0..2] = sum p, [3..5] = sum q,
+ * [6..14] = sum q p^T (row major), [15..26] = 0, [27] = sum w, [28] = sum w |p - q|^2 (p - q in float) -> double[29]. */
+int lsgpu_point_to_point(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
+                         const int32_t* ids, const float* d2, float limit, double out[29]);
+/* The point-to-point step from those 29 sums: T_out = dT (4x4 float, column major).  Host only (no GPU, no handle);
+ * the same function the device loop runs, bit for bit.  LSGPU_NO_CONVERGENCE for sum w = 0 ("no point to minimize")
+ * or a non-finite result. */
+int lsgpu_point_to_point_solve(const double sums[29], float T_out[16]);
 /* RigidTransformation::compute on features (laser_track.cpp:265,485): out = T * xyz1. */
 int lsgpu_transform_points(lsgpu_icp* h, const float T[16], const float* xyz1, int64_t n, float* out);
 /* RigidTransformation::compute on a 3-row descriptor of the cloud (`normals`, `observationDirections`: the descriptors
@@ -216,7 +239,8 @@ int lsgpu_rotate_descriptors(lsgpu_icp* h, const float T[16], const float* desc3
 typedef struct lsgpu_chain_config {
   float   reading_prob;     /* RandomSamplingDataPointsFilter.prob            yaml:2-3 (0.5); < 0: NO reading filter
                              * module (a yaml without readingDataPointsFilters): every point, no draw consumed */
-  int     ssn_knn;          /* SamplingSurfaceNormalDataPointsFilter.knn      yaml:6-7 (10)   */
+  int     ssn_knn;          /* SamplingSurfaceNormalDataPointsFilter.knn      yaml:6-7 (10); 0: NO reference filter
+                             * module -- the reference as given, no normals, no draw (point-to-point handles only) */
   float   ssn_ratio;        /* SamplingSurfaceNormalDataPointsFilter.ratio    yaml:6-7 (0.5)  */
   int     pad_;
   int64_t seed;             /* >= 0: reseed before the reference filter; < 0: continue        */

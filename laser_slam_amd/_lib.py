@@ -14,6 +14,9 @@ SO_PATH = os.environ.get("LSGPU_SO") or os.path.join(_HERE, "liblsgpu_icp.so")  
 
 OK, NO_CONVERGENCE, BAD_CONFIG, HIP_ERROR, BAD_ARG = 0, 1, 2, 3, 4
 
+# lsgpu_icp_config.error_minimizer (LSGPU_MINIMIZER_*)
+MINIMIZER_POINT_TO_PLANE, MINIMIZER_POINT_TO_POINT = 0, 1
+
 # every symbol include/lsgpu_icp.h declares (tests/test_abi.py checks the export table against this)
 ABI_SYMBOLS = [
     "lsgpu_icp_config_yaml", "lsgpu_icp_config_default", "lsgpu_icp_create", "lsgpu_icp_destroy",
@@ -22,6 +25,7 @@ ABI_SYMBOLS = [
     "lsgpu_icp_filter_reading", "lsgpu_icp_compute", "lsgpu_cloud_upload", "lsgpu_cloud_release",
     "lsgpu_cloud_size", "lsgpu_icp_compute_clouds", "lsgpu_icp_compute_clouds_upload", "lsgpu_filter_cylinder", "lsgpu_filter_voxel_grid",
     "lsgpu_icp_get_reference_mean", "lsgpu_icp_get_info", "lsgpu_icp_get_policy_info", "lsgpu_comm_get_unique_id", "lsgpu_icp_comm_init", "lsgpu_knn", "lsgpu_trim_limit", "lsgpu_normal_eq",
+    "lsgpu_point_to_point", "lsgpu_point_to_point_solve",
     "lsgpu_transform_points", "lsgpu_rotate_descriptors", "lsgpu_filter_random_sampling",
     "lsgpu_filter_sampling_surface_normal", "lsgpu_check_rigid", "lsgpu_correct_rigid", "lsgpu_rotation_distance",
     "lsgpu_strerror", "lsgpu_last_error", "lsgpu_abi_version", "lsgpu_apply_point_filters",
@@ -48,7 +52,9 @@ class IcpConfig(C.Structure):
         ("smooth_length", C.c_int),
         ("cell_size", C.c_float),
         ("profile_kernels", C.c_int),
-        ("reserved", C.c_int * 8),
+        ("reserved", C.c_int * 1),          # reserved[0] = 1 disables the trimmed-radius cap (debug)
+        ("error_minimizer", C.c_int),       # MINIMIZER_*
+        ("reserved_", C.c_int * 6),
     ]
 
 
@@ -194,6 +200,9 @@ def lib() -> C.CDLL:
     L.lsgpu_trim_limit.argtypes = [vp, fp, i64, C.c_float, C.POINTER(C.c_float)]
     L.lsgpu_normal_eq.argtypes = [vp, fp, i64, C.POINTER(C.c_float), fp, fp, C.c_float,
                                   C.POINTER(C.c_double)]
+    L.lsgpu_point_to_point.argtypes = [vp, fp, i64, C.POINTER(C.c_float), fp, fp, C.c_float,
+                                       C.POINTER(C.c_double)]
+    L.lsgpu_point_to_point_solve.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_float)]
     L.lsgpu_transform_points.argtypes = [vp, C.POINTER(C.c_float), fp, i64, fp]
     L.lsgpu_rotate_descriptors.argtypes = [vp, C.POINTER(C.c_float), fp, i64, fp]
     L.lsgpu_filter_random_sampling.argtypes = [i64, C.c_float, i64, C.POINTER(C.c_int64)]

@@ -252,8 +252,9 @@ class ICP {
     release();
   }
 
-  // Accepts the module chain of laser_slam/configurations/icp_default.yaml; any other module is a
-  // configuration error (PointMatcher's registrar throws on unknown names as well).
+  // Accepts the module chain of laser_slam/configurations/icp_default.yaml, with PointToPlaneErrorMinimizer or
+  // PointToPointErrorMinimizer; any other module is a configuration error (PointMatcher's registrar throws on unknown
+  // names as well).
   void loadFromYaml(std::istream& in) {
     lsgpu_icp_config c;
     lsgpu_icp_config_default(&c);
@@ -289,7 +290,11 @@ class ICP {
       } else if (sec == "outlierFilters" && name == "TrimmedDistOutlierFilter") {
         if (has_outlier) throw ConfigError("outlierFilters: one TrimmedDistOutlierFilter at most");
         has_outlier = true; c.trim_ratio = (float)num("ratio", 0.85);
-      } else if (sec == "errorMinimizer" && name == "PointToPlaneErrorMinimizer") { has_minimizer = true; }
+      } else if (sec == "errorMinimizer" && (name == "PointToPlaneErrorMinimizer" || name == "PointToPointErrorMinimizer")) {
+        if (has_minimizer) throw ConfigError("errorMinimizer: one module at most");
+        has_minimizer = true;
+        c.error_minimizer = name == "PointToPointErrorMinimizer" ? LSGPU_MINIMIZER_POINT_TO_POINT : LSGPU_MINIMIZER_POINT_TO_PLANE;
+      }
       else if (sec == "transformationCheckers" && name == "CounterTransformationChecker") {
         has_counter = true; c.max_iterations = (int)num("maxIterationCount", 40);
       } else if (sec == "transformationCheckers" && name == "DifferentialTransformationChecker") {
@@ -301,10 +306,13 @@ class ICP {
       else throw ConfigError(sec + ": module " + name + " is not implemented on the HIP path");
     }
     // what the device loop needs: normals for the point-to-plane minimiser, the 1-NN matcher, the minimiser itself
-    // and a stopping rule.  (Absent reading filter: every point; absent outlier filter: every pair, ratio 1.)
-    if (!has_reference) throw ConfigError("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter is required (it provides the normals)");
+    // and a stopping rule.  (Absent reading filter: every point; absent outlier filter: every pair, ratio 1; absent
+    // reference filter with the point-to-point minimiser, which reads no normals: the reference as given, knn 0.)
     if (!has_matcher) throw ConfigError("matcher: KDTreeMatcher is required");
-    if (!has_minimizer) throw ConfigError("errorMinimizer: PointToPlaneErrorMinimizer is required");
+    if (!has_minimizer) throw ConfigError("errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer is required");
+    if (!has_reference && c.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
+      throw ConfigError("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter is required (it provides the normals of PointToPlaneErrorMinimizer)");
+    if (!has_reference) knn = 0;
     if (!has_counter) throw ConfigError("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
     if (!has_differential) { c.min_diff_rot = -1.f; c.min_diff_trans = -1.f; c.smooth_length = 1; }  // never satisfied: the counter stops
     cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio;

@@ -6,6 +6,7 @@
 //   lsgpu_knn.hip.h    k_knn_seed / k_knn_tile / k_knn_fallback  ...::findClosests (knn 1, eps 0)
 //   lsgpu_solve.hip.h  k_hist* / find_bin                TrimmedDistOutlierFilter     (yaml:14-16)
 //                      k_normal_eq / k_ne_final          PointToPlaneErrorMinimizer   (yaml:18-19)
+//                                                        / PointToPointErrorMinimizer (template parameter)
 //   lsgpu_grid.hip.h   k_transform                       RigidTransformation::compute
 //
 // Shared arithmetic definitions (the CPU oracle uses the same, so ids / d2 / weights are
@@ -87,7 +88,7 @@ struct IcpState {
   int iter;           // completed iterations
   int done;
   int status;         // 0 ok; 1 no convergence; 100 = cap prediction failed, host repeats uncapped
-  int err_code;       // 1 no point to minimize, 2 normal matrix not positive definite, 3 NaN in checker
+  int err_code;       // 1 no point to minimize, 2 normal matrix not positive definite, 3 NaN in checker, 4 non-finite point-to-point step
   int converged;      // stopped by the differential checker
   int counter, n_hist;  // checker state
   int cap_enabled;
@@ -131,9 +132,12 @@ struct IcpState {
   // the last completed iteration's trim limit and inlier count (the alignment's statistics; the per-iteration trace stays on
   // the device until somebody asks for it)
   float last_limit;
-  uint32_t pad2_;
+  int minimizer;      // LSGPU_MINIMIZER_* of the handle (the host launches the matching instantiation of the loop's kernels)
   long long last_used;
 };
+// the errorMinimizer a kernel is instantiated for (= LSGPU_MINIMIZER_*, include/lsgpu_icp.h)
+constexpr int kPointToPlane = 0;
+constexpr int kPointToPoint = 1;
 constexpr int kSelBelowSlots = 64;   // counters of "distance below the predicted bin", hashed by tile ...
 constexpr int kSelBelowStride = 32;  // ... one per 128-byte line (atomics on one line serialise in L2)
 constexpr int kSelFailFlag = kSelBelowSlots * kSelBelowStride;  // word index of the failure flag

@@ -152,6 +152,16 @@ void lsgpu_correct_rigid(const float T[16], float out[16]) {
   for (int r = 0; r < 3; ++r) { out[r] = c0[r]; out[4 + r] = c1[r]; out[8 + r] = c[2][r]; }
 }
 
+int lsgpu_point_to_point_solve(const double sums[29], float T_out[16]) {
+  if (!sums || !T_out) return LSGPU_BAD_ARG;
+  double Mc[9], pq[6], x[6];
+  if (!lsgpu::hostmath::point_to_point_delta(sums, T_out, Mc, pq, x)) {
+    lsgpu::hostmath::identity4(T_out);
+    return LSGPU_NO_CONVERGENCE;
+  }
+  return LSGPU_OK;
+}
+
 float lsgpu_rotation_distance(const float Ta[16], const float Tb[16]) {
   float qa[4], qb[4];
   lsgpu::hostmath::quat_from_rotation(Ta, qa);

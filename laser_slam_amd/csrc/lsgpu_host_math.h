@@ -84,6 +84,100 @@ LSGPU_HD bool llt_solve6(const double A[36], const double b[6], float x[6]) {
   return true;
 }
 
+// ---- PointToPointErrorMinimizer.  Device accumulator layout (the same 29 slots as the normal equations):
+// [0..2] sum p, [3..5] sum q, [6..14] sum q p^T (row major), [15..26] 0, [27] count, [28] sum |p - q|^2.
+// M = sum (q - q_)(p - p_)^T;  R = argmax over SO(3) of tr(R^T M) -- what U V^T with the reflection fix
+// (U diag(1,1,-1) V^T if det < 0) computes -- by Horn's quaternion: the eigenvector of the largest eigenvalue of
+// a symmetric 4x4 built from M.  Cyclic Jacobi with an exact stopping rule: a rotation whose off-diagonal element is
+// below 1e-18 of its two diagonal elements is skipped, the sweeps end with the first one that rotates nothing (at most
+// kP2pSweeps; quadratic convergence: 4-5 reach double precision).  Same IEEE operations on both sides, so host and
+// device give the same bits.  A rank-deficient M (collinear or coincident matches) still yields a unit quaternion,
+// i.e. a proper rotation.  (The update lane runs this on ONE lane, a dependent chain of double divisions and square
+// roots: every sweep saved is time off each iteration.)
+constexpr int kP2pSweeps = 12;
+
+LSGPU_HD void jacobi_eig4(double a[16], double v[16]) {
+  for (int i = 0; i < 16; ++i) v[i] = (i % 5 == 0) ? 1.0 : 0.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int sweep = 0; sweep < kP2pSweeps; ++sweep) {
+    bool rotated = false;
+    for (int p = 0; p < 3; ++p)
+      for (int q = p + 1; q < 4; ++q) {
+        const double apq = a[p * 4 + q];
+        if (!(fabs(apq) > 1e-18 * (fabs(a[p * 4 + p]) + fabs(a[q * 4 + q])))) continue;
+        rotated = true;
+        const double theta = (a[q * 4 + q] - a[p * 4 + p]) / (2.0 * apq);
+        const double at = fabs(theta);
+        double t = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(theta * theta + 1.0));
+        if (theta < 0.0) t = -t;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 4; ++k) {   // A <- A J (columns p, q)
+          const double akp = a[k * 4 + p], akq = a[k * 4 + q];
+          a[k * 4 + p] = c * akp - s * akq;
+          a[k * 4 + q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 4; ++k) {   // A <- J^T A (rows p, q)
+          const double apk = a[p * 4 + k], aqk = a[q * 4 + k];
+          a[p * 4 + k] = c * apk - s * aqk;
+          a[q * 4 + k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < 4; ++k) {   // V <- V J
+          const double vkp = v[k * 4 + p], vkq = v[k * 4 + q];
+          v[k * 4 + p] = c * vkp - s * vkq;
+          v[k * 4 + q] = s * vkp + c * vkq;
+        }
+      }
+    if (!rotated) break;
+  }
+}
+
+// dT (column major float) from the 29 sums; Mc = the centred M (row major), pq = {p_, q_}, x = {rotation vector, t}.
+// false: no pair (count 0, "no point to minimize") or a non-finite result.
+LSGPU_HD bool point_to_point_delta(const double* ne, float dT[16], double Mc[9], double pq[6], double x[6]) {
+  const double W = ne[27];
+  if (!(W > 0.0)) return false;
+  for (int d = 0; d < 3; ++d) { pq[d] = ne[d] / W; pq[3 + d] = ne[3 + d] / W; }
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Mc[r * 3 + c] = ne[6 + r * 3 + c] - ne[3 + r] * pq[c];
+  // Horn: S_ab = sum p'_a q'_b = M[b][a]
+  const double Sxx = Mc[0], Syx = Mc[1], Szx = Mc[2], Sxy = Mc[3], Syy = Mc[4], Szy = Mc[5], Sxz = Mc[6], Syz = Mc[7], Szz = Mc[8];
+  double N[16] = {Sxx + Syy + Szz, Syz - Szy,        Szx - Sxz,        Sxy - Syx,
+                  Syz - Szy,       Sxx - Syy - Szz,  Sxy + Syx,        Szx + Sxz,
+                  Szx - Sxz,       Sxy + Syx,        Syy - Sxx - Szz,  Syz + Szy,
+                  Sxy - Syx,       Szx + Sxz,        Syz + Szy,        Szz - Sxx - Syy};
+  double V[16];
+  jacobi_eig4(N, V);
+  // the column of the largest eigenvalue (the first of equal ones); selected without indexing by a variable
+  double lam = N[0], w = V[0], qx = V[4], qy = V[8], qz = V[12];
+  for (int i = 1; i < 4; ++i) {
+    const bool better = N[i * 4 + i] > lam;
+    lam = better ? N[i * 4 + i] : lam;
+    w = better ? V[i] : w; qx = better ? V[4 + i] : qx; qy = better ? V[8 + i] : qy; qz = better ? V[12 + i] : qz;
+  }
+  const double nn = sqrt(w * w + qx * qx + qy * qy + qz * qz);
+  if (!(nn > 0.0)) return false;
+  if (w < 0.0) { w = -w; qx = -qx; qy = -qy; qz = -qz; }
+  w = w / nn; qx = qx / nn; qy = qy / nn; qz = qz / nn;
+  const double R[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - w * qz),         2.0 * (qx * qz + w * qy),
+                       2.0 * (qx * qy + w * qz),         1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - w * qx),
+                       2.0 * (qx * qz - w * qy),         2.0 * (qy * qz + w * qx),         1.0 - 2.0 * (qx * qx + qy * qy)};
+  identity4(dT);
+  bool finite = true;
+  for (int r = 0; r < 3; ++r) {
+    const double t = pq[3 + r] - ((R[r * 3] * pq[0] + R[r * 3 + 1] * pq[1]) + R[r * 3 + 2] * pq[2]);
+    x[3 + r] = t;
+    set(dT, r, 3, (float)t);
+    for (int c = 0; c < 3; ++c) set(dT, r, c, (float)R[r * 3 + c]);
+    finite = finite && t - t == 0.0;
+  }
+  const double s = sqrt(qx * qx + qy * qy + qz * qz);
+  const double ang = s > 0.0 ? 2.0 * atan2(s, w) / s : 0.0;
+  x[0] = qx * ang; x[1] = qy * ang; x[2] = qz * ang;
+  return finite;
+}
+
 LSGPU_HD float sin_f32(float a) { return (float)sin((double)a); }
 LSGPU_HD float cos_f32(float a) { return (float)cos((double)a); }
 LSGPU_HD float atan2_f32(float y, float x) { return (float)atan2((double)y, (double)x); }

@@ -425,7 +425,8 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
   if (!cfg || !out) return LSGPU_BAD_ARG;
   *out = nullptr;
   if (!(cfg->trim_ratio > 0.f && cfg->trim_ratio <= 1.f) || cfg->max_iterations < 1 ||
-      cfg->smooth_length < 1)
+      cfg->smooth_length < 1 ||
+      (cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_PLANE && cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT))
     return LSGPU_BAD_CONFIG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
@@ -1192,11 +1193,14 @@ int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, floa
   return LSGPU_OK;
 }
 
-int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
-                    const int32_t* ids, const float* d2, float limit, double out[29]) {
+// the stand-alone accumulation of either minimizer (lsgpu_normal_eq / lsgpu_point_to_point): 29 sums of the pairs with
+// d2 <= limit, ids indexing the reference as given to set_reference
+extern "C++" template <int MIN>
+static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_xyz1, int64_t nq, const float T[16],
+                            const int32_t* ids, const float* d2, float limit, double out[29]) {
   if (!h || !out) return LSGPU_BAD_ARG;
   h->err.clear();
-  if (h->nr <= 0) { h->err = "normal_eq: no reference set"; return LSGPU_BAD_ARG; }
+  if (h->nr <= 0) { h->err = std::string(what) + ": no reference set"; return LSGPU_BAD_ARG; }
   if (nq <= 0 || !query_xyz1 || !ids || !d2 || nq > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
   HIPC(hipSetDevice(h->device));
   int rc = ensure_loop_buffers(h, nq);
@@ -1218,15 +1222,25 @@ int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const flo
   float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const Mat34 Tm = to_mat34(T ? T : I);
   const int nb = std::min(kNeBlocks, nblk(nq));
-  hipLaunchKernelGGL((k_normal_eq<true, false>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm,
-                     idp, dp, h->pts.p, h->nrm.p, h->ref_inv.p, (const uint32_t*)nullptr,
-                     (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p);
+  hipLaunchKernelGGL((k_normal_eq<true, false, MIN>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm,
+                     idp, dp, h->pts.p, MIN == kPointToPoint ? (const float4*)nullptr : h->nrm.p, h->ref_inv.p,
+                     (const uint32_t*)nullptr, (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p);
   hipLaunchKernelGGL(k_ne_final, dim3(1), dim3(1024), 0, h->stream, h->ne_partials.p, nb, h->ne_out.p);
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h->h_pinned, h->ne_out.p, kNe * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPC(hipStreamSynchronize(h->stream));
   std::memcpy(out, h->h_pinned, kNe * sizeof(double));
   return LSGPU_OK;
+}
+
+int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
+                    const int32_t* ids, const float* d2, float limit, double out[29]) {
+  return stand_alone_sums<kPointToPlane>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
+}
+
+int lsgpu_point_to_point(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
+                         const int32_t* ids, const float* d2, float limit, double out[29]) {
+  return stand_alone_sums<kPointToPoint>(h, "point_to_point", query_xyz1, nq, T, ids, d2, limit, out);
 }
 
 int lsgpu_transform_points(lsgpu_icp* h, const float T[16], const float* xyz1, int64_t n,
@@ -1806,6 +1820,12 @@ int lsgpu_icp_filter_reading(lsgpu_icp* h, const float* xyz1, int64_t n, float p
   return LSGPU_OK;
 }
 
+// ssn_knn in [3, kSsnMaxKnn]; or 0 (no reference filter module) on a point-to-point handle, which needs no normals
+static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain) {
+  if (chain->ssn_knn == 0) return h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
+  return chain->ssn_knn >= 3 && chain->ssn_knn <= kSsnMaxKnn;
+}
+
 int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1,
                       int64_t nr, const float T_init[16], const lsgpu_chain_config* chain,
                       float T_out[16], lsgpu_icp_stats* stats) {
@@ -1813,7 +1833,11 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   h->err.clear();
   std::memcpy(T_out, T_init, 16 * sizeof(float));
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (chain->ssn_knn < 3 || chain->ssn_knn > kSsnMaxKnn) { h->err = "compute: ssn_knn must be in [3, 32]"; return LSGPU_BAD_CONFIG; }
+  if (!chain_ok(h, chain)) {
+    h->err = "compute: ssn_knn must be in [3, 32] (0, no reference filter, only with the point-to-point minimizer)";
+    return LSGPU_BAD_CONFIG;
+  }
+  const bool ref_filter = chain->ssn_knn != 0;
   if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
   if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
   if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
@@ -1823,7 +1847,8 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   // reading point
   DrawAhead draws;
   {
-    const int rc0 = draws.begin(h, -1, (size_t)nr + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq), (size_t)nr);   // (the reference filter's share first)
+    const size_t ref_draws = ref_filter ? (size_t)nr : (size_t)0;
+    const int rc0 = draws.begin(h, -1, ref_draws + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq), ref_draws);   // (the reference filter's share first)
     if (rc0) return rc0;
   }
   // step 1: reference filter (yaml:5-7)
@@ -1872,12 +1897,19 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
       if (started && h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     }
   } joiner{uploader, h, overlap_upload};
-  HIPC(h->flt_ref.reserve(nr));
-  HIPC(h->flt_nrm.reserve(3 * nr));
   int64_t nrf = 0, nqf = 0;
-  rc = ssn_device(h, src, nr, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
-  if (rc) return rc;
-  if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+  const float4* ref_pts = src;          // (no reference filter module: the reference as given, no normals, no draw)
+  const float* ref_nrm = nullptr;
+  if (ref_filter) {
+    HIPC(h->flt_ref.reserve(nr));
+    HIPC(h->flt_nrm.reserve(3 * nr));
+    rc = ssn_device(h, src, nr, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
+    if (rc) return rc;
+    if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+    ref_pts = h->flt_ref.p; ref_nrm = h->flt_nrm.p;
+  } else {
+    nrf = nr;
+  }
   // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
   draws.commit_now(draws.used + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq));
   // steps 2-4.  The grid build (steps 2-3, h->stream) and the reading's side -- its filter (step 4) and the ordering of
@@ -1966,7 +1998,7 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
     };
   }
   h->defer_cone = side;
-  rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(h->flt_ref.p), h->flt_nrm.p, nrf);
+  rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(ref_pts), ref_nrm, nrf);
   h->hook_before_ref_sync = nullptr; h->hook_after_grid = nullptr;
   h->defer_cone = false;
   if (rc) return rc;
@@ -2330,7 +2362,7 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
     fused = have(ref_slots[i]) && ref_slots[i] != reading_slot;
     if (fused) total += h->cloud_n[ref_slots[i]];
   }
-  fused = fused && total > 0 && total <= 0x7FFFFFF0ll && chain->ssn_knn >= 3 && chain->ssn_knn <= kSsnMaxKnn;
+  fused = fused && total > 0 && total <= 0x7FFFFFF0ll && chain_ok(h, chain);   // (ssn_knn 0: point-to-point without a reference filter)
   if (!fused) {   // nothing to overlap (or nothing to match against): the two calls, one after the other
     const int rcu = lsgpu_cloud_upload(h, reading_slot, reading_xyz1, nq);
     if (rcu) return rcu;
@@ -2452,6 +2484,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     for (int c = 0; c < 4; ++c) hst->T_rows[r * 4 + c] = hst->T_iter[c * 4 + r];
   hst->prev_limit = INFINITY; hst->cap2 = INFINITY;
   hst->cap_enabled = h->cfg.reserved[0] == 0 ? 1 : 0;
+  hst->minimizer = h->cfg.error_minimizer;
   hst->max_iter = max_it; hst->smooth = h->cfg.smooth_length;
   hst->lim_rot = h->cfg.min_diff_rot; hst->lim_trans = h->cfg.min_diff_trans;
   AlignInitArgs ia{};
@@ -2482,6 +2515,10 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   const Mat34 Tdummy = to_mat34(hst->T_iter);
   std::vector<size_t> ev_of_launch;  // event index of every enqueued iteration
   const bool split_update = tuning().split_update;  // (profiling: the update as its own launch)
+  // the minimizer's instantiations of the accumulation and of the update (point-to-point reads no normals)
+  const bool p2p = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
+  const auto ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
+  const auto update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
   // The launch policy (lsgpu_policy.h) decides what every iteration is made of and when the host looks at the loop
   // state; this function executes its decisions.  (tests/cpp/policy_check.cpp drives the same state machine on the CPU.)
   policy::Config& pc = h->pol_cfg;
@@ -2532,8 +2569,8 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     }
     lsgpu_icp::KnnEv* ev = (timed && itn.knn && h->knn_events_used) ? &h->knn_events[h->knn_events_used - 1] : nullptr;
     if (ev) HIPC(hipEventRecord(ev->d, h->stream));
-    hipLaunchKernelGGL(k_normal_eq_loop, dim3(nb), dim3(256), 0, h->stream, h->rdq.p, (int)nq,
-                       h->state.p, h->prev.p, h->d2.p, h->nrm.p, h->hist.p, h->sel.p + 2,
+    hipLaunchKernelGGL(ne_loop, dim3(nb), dim3(256), 0, h->stream, h->rdq.p, (int)nq,
+                       h->state.p, h->prev.p, h->d2.p, p2p ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
                        h->counters.p + 32, h->ne_tickets.p, h->ne_partials.p, h->ne_gpartials.p, h->ne_out.p,
                        h->chk_hist.p, h->trace_dev.p, max_it, itn.capped ? 1 : 0, (h->comm || split_update) ? 0 : 1,
                        h->sel_aux.p, (h->comm || !tuning().fused_select) ? h->sel_win.p : nullptr, itn.committed ? 1 : 0, h->spread_cnt.p,
@@ -2546,7 +2583,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
         return LSGPU_HIP_ERROR;
       }
       if (h->comm) comm_mark(h, false);
-      hipLaunchKernelGGL(k_icp_update, dim3(1), dim3(64), 0, h->stream, h->state.p, h->ne_out.p,
+      hipLaunchKernelGGL(update, dim3(1), dim3(64), 0, h->stream, h->state.p, h->ne_out.p,
                          h->chk_hist.p, h->trace_dev.p, max_it, itn.capped ? 1 : 0, h->sel_aux.p);           // 6d+6e
     }
     if (ev) HIPC(hipEventRecord(ev->e, h->stream));
@@ -2659,7 +2696,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   rc = hst->status;
   if (rc == LSGPU_NO_CONVERGENCE)
     h->err = hst->err_code == 1 ? "no point to minimize" : hst->err_code == 2 ? "normal matrix not positive definite"
-                                                                          : "NaN in transformation checker";
+           : hst->err_code == 4 ? "non-finite point-to-point solution" : "NaN in transformation checker";
   st.iterations = it;
   st.converged = hst->converged;
   st.stragglers = (int64_t)hst->stragglers;

@@ -208,10 +208,30 @@ __global__ __launch_bounds__(256) void k_align_init(AlignInitArgs a) {
 // Per pair with weight 1: J = [p x n ; n] (float, as libpointmatcher), r = (p - q).n ;
 // accumulate 21 upper-tri J J^T, 6 of -J r, count, r^2 in double.  Per-block partials, then a
 // single-block fixed-order reduction => bitwise reproducible.
+// Point-to-point instantiation (MIN == kPointToPoint): the same 29 slots hold sum p, sum q, sum q p^T, zeros, count,
+// sum |p - q|^2 (lsgpu_host_math.h, point_to_point_delta); no normal is read.
 constexpr int kNe = 29;
 constexpr int kNeGroup = 16;   // k_normal_eq_loop: blocks per first-level reduction group
 
-template <bool IDS_ORIG, bool LIMIT_DEV>
+// slots a point-to-point kernel leaves at zero (they are still reduced and stored: the layout is the same)
+template <int MIN>
+__device__ constexpr bool ne_slot_unused(int k) { return MIN == kPointToPoint && k >= 15 && k < 27; }
+
+// one point-to-point pair: sum p, sum q, sum q p^T, count, |p - q|^2 (the difference in float, as r of point-to-plane)
+__device__ __forceinline__ void p2p_terms(const float3 p, const float4 q, double* v) {
+  const float e0 = p.x - q.x, e1 = p.y - q.y, e2 = p.z - q.z;
+  const double pd[3] = {(double)p.x, (double)p.y, (double)p.z}, qd[3] = {(double)q.x, (double)q.y, (double)q.z};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { v[a] = pd[a]; v[3 + a] = qd[a]; }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[6 + 3 * a + c] = qd[a] * pd[c];
+  }
+  v[15] = ((double)e0 * (double)e0 + (double)e1 * (double)e1) + (double)e2 * (double)e2;
+}
+
+template <bool IDS_ORIG, bool LIMIT_DEV, int MIN = kPointToPlane>
 __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rdq, int nq, Mat34 T,
                                                    const int* __restrict__ ids,
                                                    const float* __restrict__ d2,
@@ -240,6 +260,15 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
     const float4 r = rdq[j];
     const float3 p = xform(T, r.x, r.y, r.z);
     const float4 q = pts[id];
+    if constexpr (MIN == kPointToPoint) {
+      double v[16];
+      p2p_terms(p, q, v);
+#pragma unroll
+      for (int k = 0; k < 15; ++k) acc[k] += v[k];
+      acc[27] += 1.0;
+      acc[28] += v[15];
+      continue;
+    }
     const float4 n = nrm[id];
     float J[6];
     J[0] = p.y * n.z - p.z * n.y;
@@ -259,7 +288,7 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
     acc[28] += (double)res * (double)res;
   }
 #pragma unroll
-  for (int k = 0; k < kNe; ++k) acc[k] = wave_sum(acc[k]);
+  for (int k = 0; k < kNe; ++k) acc[k] = ne_slot_unused<MIN>(k) ? 0.0 : wave_sum(acc[k]);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -283,7 +312,9 @@ __device__ unsigned long long g_ne_tail[4];   // (wall clock at points of the la
 #endif
 // ---------------------------------------------------------------- per-iteration update (device side)
 // One lane: 6x6 float LLT solve, AngleAxis update, T_iter <- dT * T_iter, Counter + Differential
-// checkers, trace record, next cap.  Same code as the host (lsgpu_host_math.h).
+// checkers, trace record, next cap.  Same code as the host (lsgpu_host_math.h).  MIN: the handle's minimizer
+// (point-to-point: point_to_point_delta instead of the LLT solve; the trace keeps its layout, see lsgpu_iter_trace).
+template <int MIN>
 __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float* chk_hist,
                                        lsgpu_iter_trace* trace, int trace_cap, int capped_launch,
                                        uint32_t* sel_aux, int sel_failed = -1 /* -1: read (and clear) the flag in sel_aux */) {
@@ -314,13 +345,19 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
   const long long used = (long long)ne_out[27];
   if (used <= 0) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 1; st->done = 1; return; }
   double A[36], b[6];
-  hostmath::unpack_normal_eq(ne_out, A, b);
   float x[6], dT[16], Tn[16];
+  double xd[6];
+  if constexpr (MIN == kPointToPoint) {
+    for (int i = 0; i < 36; ++i) A[i] = 0.0;
+    if (!hostmath::point_to_point_delta(ne_out, dT, A, b, xd)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 4; st->done = 1; return; }
+  } else {
+  hostmath::unpack_normal_eq(ne_out, A, b);
   if (!hostmath::llt_solve6(A, b, x)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 2; st->done = 1; return; }
+  }
 #ifdef LSGPU_KNN_STATS
   const long long u1 = clock64();
 #endif
-  hostmath::delta_from_x(x, dT);
+  if constexpr (MIN != kPointToPoint) hostmath::delta_from_x(x, dT);
   hostmath::mul4(dT, st->T_iter, Tn);
   for (int i = 0; i < 16; ++i) st->T_iter[i] = Tn[i];
   for (int i = 0; i < 12; ++i) st->T_rows_prev[i] = st->T_rows[i];
@@ -336,7 +373,11 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
     for (int i = 0; i < 16; ++i) tr.T_iter[i] = Tn[i];
     tr.limit = limit; tr.n_used = used;
     for (int i = 0; i < 36; ++i) tr.A[i] = A[i];
+    if constexpr (MIN == kPointToPoint) {
+      for (int i = 0; i < 6; ++i) { tr.b[i] = b[i]; tr.x[i] = xd[i]; }
+    } else {
     for (int i = 0; i < 6; ++i) { tr.b[i] = b[i]; tr.x[i] = x[i]; }
+    }
     tr.knn_main_us = 0.f; tr.knn_fallback_us = 0.f; tr.stragglers = (uint32_t)nstrag; tr.reserved = (uint32_t)ne_out[31];
   }
 #ifdef LSGPU_KNN_STATS
@@ -392,17 +433,19 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
 
 // stand-alone launch: used when something sits between the normal equations and the update (the RCCL
 // all-reduce of the split-scan mode); otherwise the last block of k_normal_eq_loop runs the update itself
+template <int MIN>
 __global__ __launch_bounds__(64) void k_icp_update(IcpState* __restrict__ st,
                                                    const double* __restrict__ ne_out,
                                                    float* __restrict__ chk_hist,
                                                    lsgpu_iter_trace* __restrict__ trace, int trace_cap,
                                                    int capped_launch, uint32_t* __restrict__ sel_aux) {
-  if (threadIdx.x == 0) icp_update_lane(st, ne_out, chk_hist, trace, trace_cap, capped_launch, sel_aux);
+  if (threadIdx.x == 0) icp_update_lane<MIN>(st, ne_out, chk_hist, trace, trace_cap, capped_launch, sel_aux);
 }
 
 
 // The align loop's variant: the matched point comes coalesced from the warm-start array (xyz + sorted
-// index of every query's neighbour, written by the kNN kernels), only the normal is gathered.  The
+// index of every query's neighbour, written by the kNN kernels), only the normal is gathered (point-to-point:
+// nothing is gathered, `nrm` may be null -- 36 instead of 52 bytes per query, 17 running sums instead of 29).  The
 // LAST block to finish (ticket; partial sums exchanged with agent-scope accesses) reduces the block
 // partials in a fixed order, publishes {29 sums, limit, straggler count} and re-arms the per-iteration
 // scratch (histograms, straggler counter, ticket) so the next iteration needs no memset launches.
@@ -410,6 +453,7 @@ __global__ __launch_bounds__(64) void k_icp_update(IcpState* __restrict__ st,
 #define LSGPU_NE_UNROLL 8
 #endif
 constexpr int kNeUnroll = LSGPU_NE_UNROLL;  // points whose loads are in flight together, per lane
+template <int MIN>
 __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict__ rdq, int nq,
                                                         IcpState* __restrict__ ist,
                                                         const float4* __restrict__ match,
@@ -600,13 +644,38 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     // (the normal is gathered: the 16 MB normal array stays in the L2s / Infinity Cache over an alignment, and a copy of
     // the match's normal kept next to the match -- coalesced 16 B per query, written by the search kernels -- measured
     // SLOWER: 31.5 -> 34.6 us per launch, profiles/r03b_bench.json; it adds 16 MB of HBM stream to save cache hits)
-    for (int u = 0; u < kNeUnroll; ++u) nn[u] = use[u] ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int u = 0; u < kNeUnroll; ++u) {
+      if constexpr (MIN != kPointToPoint) nn[u] = use[u] ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
 #pragma unroll
     for (int u = 0; u < kNeUnroll; ++u) {
     if (!use[u]) continue;
     const float4 q = qq[u];
     const float4 r = rr[u];
     const float3 p = xform(T, r.x, r.y, r.z);
+    if constexpr (MIN == kPointToPoint) {
+      double v[16];
+      p2p_terms(p, q, v);
+      if (amb[u]) {   // (as below: the same 32-double record, the unused slots written 0)
+        const uint32_t slot = __hip_atomic_fetch_add(amb_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (slot < (uint32_t)kSelAmbCap) {
+          double* av = amb_val + (size_t)slot * 32;
+          for (int k = 0; k < 15; ++k) __hip_atomic_store(&av[k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          for (int k = 15; k < 27; ++k) __hip_atomic_store(&av[k], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(&av[27], 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(&av[28], v[15], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_store(reinterpret_cast<unsigned long long*>(&amb_key[slot]),
+                             ((unsigned long long)__float_as_uint(dd[u]) << 32) | (unsigned long long)(uint32_t)(j0 + u * stride),
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        continue;
+      }
+#pragma unroll
+      for (int k = 0; k < 15; ++k) acc[k] += v[k];
+      acc[27] += 1.0;
+      acc[28] += v[15];
+      continue;
+    }
     const float4 n = nn[u];
     float J[6];
     J[0] = p.y * n.z - p.z * n.y;
@@ -648,7 +717,7 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   if (threadIdx.x == 0) atomicMax(&g_ne_dbg[6], (unsigned long long)wall_clock64());
 #endif
 #pragma unroll
-  for (int k = 0; k < kNe; ++k) acc[k] = wave_sum(acc[k]);
+  for (int k = 0; k < kNe; ++k) acc[k] = ne_slot_unused<MIN>(k) ? 0.0 : wave_sum(acc[k]);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -873,7 +942,7 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   // wave 0's first lane advances the loop state; the other waves re-arm the iteration's scratch meanwhile (every
   // block has read hist3 / the window table by now)
   if (threadIdx.x == 0) {
-    if (fuse_update) icp_update_lane(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh);
+    if (fuse_update) icp_update_lane<MIN>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh);
     else if (sel_aux && fail_sh) sel_aux[kSelFailFlag] = 1u;   // the stand-alone update kernel reads it there
   } else if (threadIdx.x >= 64) {
     const int t = (int)threadIdx.x - 64;

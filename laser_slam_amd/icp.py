@@ -78,11 +78,16 @@ def _raise(code: int, what: str, h=None):
 class IcpHandle:
     """One lsgpu_icp handle == one reference ``icp_`` member: one device, one HIP stream."""
 
-    def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0):
+    def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None):
+        """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
+        or an _lib.MINIMIZER_* value."""
         L = _lib.lib()
         if cfg is None:
             cfg = IcpConfig()
             L.lsgpu_icp_config_yaml(C.byref(cfg))
+        if error_minimizer is not None:
+            cfg = IcpConfig.from_buffer_copy(cfg)       # (the caller's config stays as it is)
+            cfg.error_minimizer = _MINIMIZERS.get(error_minimizer, error_minimizer)
         self.cfg = cfg
         self.device = device
         self._h = C.c_void_p()
@@ -105,9 +110,10 @@ class IcpHandle:
         self.close()
 
     # ---- ICP::compute steps 2-3
-    def set_reference(self, ref_xyz1, ref_normals):
+    def set_reference(self, ref_xyz1, ref_normals=None):
+        """ref_normals None: no normals (a point-to-point handle reads none)."""
         p, _k1, n = _as_f32(ref_xyz1, 4)
-        q, _k2, m = _as_f32(ref_normals, 3)
+        q, _k2, m = _as_f32(ref_normals, 3) if ref_normals is not None else (None, None, n)
         if m != n:
             raise ValueError("normals must have one row per reference point")
         rc = _lib.lib().lsgpu_icp_set_reference(self._h, p, q, n)
@@ -392,6 +398,20 @@ class IcpHandle:
                 k += 1
         return A, out[21:27].copy(), int(out[27]), float(out[28])
 
+    def point_to_point(self, query_xyz1, T, ids, d2, limit: float) -> np.ndarray:
+        """lsgpu_point_to_point: the 29 point-to-point sums (sum p, sum q, sum q p^T row major, 12 zeros, count,
+        sum |p - q|^2) of the pairs with d2 <= limit, double."""
+        p, _k, n = _as_f32(query_xyz1, 4)
+        ids = np.ascontiguousarray(ids, np.int32)
+        d2 = np.ascontiguousarray(d2, np.float32)
+        out = np.zeros(29)
+        tp = _fp(_t16(T)) if T is not None else None
+        rc = _lib.lib().lsgpu_point_to_point(self._h, p, n, tp, ids.ctypes.data, d2.ctypes.data, limit,
+                                             out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_point_to_point", self._h)
+        return out
+
     def transform_points(self, T, xyz1):
         p, _k, n = _as_f32(xyz1, 4)
         out = np.empty((n, 4), np.float32)
@@ -428,7 +448,7 @@ def align_batch(handles, references, normals, readings, T_inits):
     nr, nq = (C.c_int64 * B)(), (C.c_int64 * B)()
     for i in range(B):
         p, k1, n = _as_f32(references[i], 4)
-        q, k2, m = _as_f32(normals[i], 3)
+        q, k2, m = _as_f32(normals[i], 3) if normals[i] is not None else (None, None, n)   # (None: point-to-point handles)
         r, k3, l = _as_f32(readings[i], 4)
         if m != n:
             raise ValueError("normals must have one row per reference point")
@@ -479,6 +499,20 @@ def sampling_surface_normal(xyz1, knn: int = 10, ratio: float = 0.5, seed: int =
     return o[:m].copy(), nr[:m].copy()
 
 
+def point_to_point_solve(sums) -> np.ndarray:
+    """lsgpu_point_to_point_solve: the point-to-point step dT (4x4 float32) from the 29 sums of
+    IcpHandle.point_to_point -- host only, the same function the device loop runs.  Raises ConvergenceError for
+    count 0."""
+    s = np.ascontiguousarray(sums, np.float64)
+    if s.shape != (29,):
+        raise ValueError("expected 29 sums")
+    out = np.empty(16, np.float32)
+    rc = _lib.lib().lsgpu_point_to_point_solve(s.ctypes.data_as(C.POINTER(C.c_double)), _fp(out))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_point_to_point_solve")
+    return out.reshape(4, 4).T.copy()
+
+
 def check_rigid(T) -> bool:
     return bool(_lib.lib().lsgpu_check_rigid(_fp(_t16(T))))
 
@@ -501,16 +535,19 @@ _SUPPORTED = {
     "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter"},
     "matcher": {"KDTreeMatcher"},
     "outlierFilters": {"TrimmedDistOutlierFilter"},
-    "errorMinimizer": {"PointToPlaneErrorMinimizer"},
+    "errorMinimizer": {"PointToPlaneErrorMinimizer", "PointToPointErrorMinimizer"},
     "transformationCheckers": {"CounterTransformationChecker", "DifferentialTransformationChecker"},
 }
+
+_MINIMIZERS = {"PointToPlaneErrorMinimizer": _lib.MINIMIZER_POINT_TO_PLANE,
+               "PointToPointErrorMinimizer": _lib.MINIMIZER_POINT_TO_POINT}
 
 
 @dataclass
 class ChainConfig:
     """The module chain of laser_slam/configurations/icp_default.yaml, as parameters."""
     reading_sampling_prob: float = 0.5      # yaml:3   (module default 0.75)
-    surface_normal_knn: int = 10            # yaml:7   (module default 7)
+    surface_normal_knn: int = 10            # yaml:7   (module default 7); 0: no reference filter (point-to-point only)
     surface_normal_ratio: float = 0.5       # module default
     trim_ratio: float = 0.75                # yaml:16  (module default 0.85)
     max_iterations: int = 40                # yaml:23
@@ -518,6 +555,7 @@ class ChainConfig:
     min_diff_trans: float = 0.01            # yaml:26  (module default 0.001)
     smooth_length: int = 4                  # yaml:27  (module default 3)
     seed: int = -1                          # >= 0: srand(seed) before the filters
+    error_minimizer: str = "PointToPlaneErrorMinimizer"   # yaml:18-19, or "PointToPointErrorMinimizer"
     extra: dict = field(default_factory=dict)
 
 
@@ -594,6 +632,11 @@ class ICP:
                                          "only knn 1 / epsilon 0 is implemented")
                 elif name == "TrimmedDistOutlierFilter":
                     ch.trim_ratio = float(params.get("ratio", 0.85))
+                elif name in _MINIMIZERS:
+                    if "minimizer" in seen:
+                        raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "errorMinimizer: one module at most")
+                    seen.add("minimizer")
+                    ch.error_minimizer = name
                 elif name == "CounterTransformationChecker":
                     ch.max_iterations = int(params.get("maxIterationCount", 40))
                 elif name == "DifferentialTransformationChecker":
@@ -602,10 +645,14 @@ class ICP:
                     ch.smooth_length = int(params.get("smoothLength", 3))
         if modules("readingStepDataPointsFilters"):
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "readingStepDataPointsFilters")
-        for need, why in (("SamplingSurfaceNormalDataPointsFilter", "it provides the normals"),
-                          ("KDTreeMatcher", "the matcher"), ("PointToPlaneErrorMinimizer", "the error minimizer"),
+        # the point-to-point minimizer reads no normals: without a reference filter module the reference is used as given
+        p2p = ch.error_minimizer == "PointToPointErrorMinimizer"
+        if p2p and "SamplingSurfaceNormalDataPointsFilter" not in seen:
+            ch.surface_normal_knn = 0
+        for need, why in (("SamplingSurfaceNormalDataPointsFilter", "it provides the normals of the point-to-plane minimizer"),
+                          ("KDTreeMatcher", "the matcher"), ("minimizer", "the error minimizer"),
                           ("CounterTransformationChecker", "the loop would not stop")):
-            if need not in seen:
+            if need not in seen and not (p2p and need == "SamplingSurfaceNormalDataPointsFilter"):
                 raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{need} is required ({why})")
         # inspector / logger (yaml:32-44) only produce debug dumps: accepted and ignored
         self.chain = ch
@@ -620,7 +667,7 @@ class ICP:
             cfg.min_diff_rot = self.chain.min_diff_rot
             cfg.min_diff_trans = self.chain.min_diff_trans
             cfg.smooth_length = self.chain.smooth_length
-            self._handle = IcpHandle(cfg, self.device)
+            self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer)
         return self._handle
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
