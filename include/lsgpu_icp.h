@@ -23,6 +23,9 @@
  * the caller's stream has to be synchronised first (hipStreamSynchronize / an event wait on the producing stream).
  * The Python twin (laser_slam_amd/icp.py) synchronises torch's current stream before every call that passes a
  * device tensor.
+ *
+ * Modules: the chain of icp_default.yaml, PointToPointErrorMinimizer in place of PointToPlaneErrorMinimizer
+ * (lsgpu_icp_config.error_minimizer), and KDTreeMatcher with knn 1..LSGPU_MATCHER_KNN_MAX (lsgpu_icp_config.matcher_knn).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -58,8 +61,18 @@ typedef struct lsgpu_icp_config {
   int   profile_kernels;  /* 1: HIP-event time every kNN launch (see lsgpu_icp_stats)    */
   int   reserved[1];      /* reserved[0] = 1 disables the trimmed-radius cap (debug)       */
   int   error_minimizer;  /* LSGPU_MINIMIZER_* (0, the default: point-to-plane); any other value: LSGPU_BAD_CONFIG */
-  int   reserved_[6];
+  int   matcher_knn;      /* KDTreeMatcher knn: 0 or 1 one neighbour; 2..LSGPU_MATCHER_KNN_MAX k nearest matches; other: BAD_CONFIG */
+  int   reserved_[5];
 } lsgpu_icp_config;
+
+/* KDTreeMatcher knn (lsgpu_icp_config.matcher_knn), epsilon 0.  With knn = k >= 2 every reading point is paired with its k
+ * nearest reference points (Matches: k x N dists / ids): TrimmedDistOutlierFilter ranks all k N distances (limit =
+ * sorted(d2)[floor(float(k N) * ratio)]), the error minimizer adds every pair with weight 1 (the reading point once per
+ * kept match; point-to-plane with the matched point's normal), lsgpu_icp_stats.final_n_used and the trace's n_used count
+ * pairs.  Checkers, the update and the composition of T are those of knn 1.  The k matches of a point are in ascending
+ * d2, ties to the smaller index of the handle's Morton-sorted reference (csrc/lsgpu_knn_k.hip.h).  A reference with fewer
+ * than k points is LSGPU_BAD_ARG; the split-scan mode (lsgpu_icp_comm_init) refuses a k-match handle (LSGPU_BAD_CONFIG). */
+#define LSGPU_MATCHER_KNN_MAX 8
 
 /* errorMinimizer modules (lsgpu_icp_config.error_minimizer).  Point-to-plane (yaml:18-19) solves the 6x6 normal
  * equations of J = [p x n; n] and needs the reference normals.  Point-to-point (libpointmatcher's
@@ -207,6 +220,11 @@ int lsgpu_icp_get_reference_mean(lsgpu_icp* h, float mean[3]);
  * set_reference, d2 = squared distance.  T (may be NULL = identity) is applied to each query on load. */
 int lsgpu_knn(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16], int32_t* ids,
               float* d2);
+/* KDTreeMatcher::findClosests knn=k eps=0, 1 <= k <= LSGPU_MATCHER_KNN_MAX: ids / d2 hold k entries per query, query
+ * major (query i at [i k, i k + k) -- the k x N column-major Matches), each query's in ascending d2 (ties: see
+ * matcher_knn), ids indexing the reference as given to set_reference.  LSGPU_BAD_ARG if the reference has fewer than k
+ * points or k nq does not fit the loop's 32-bit counts. */
+int lsgpu_knn_k(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16], int k, int32_t* ids, float* d2);
 /* TrimmedDistOutlierFilter (yaml:14-16): limit = sorted(d2)[floor(n*ratio)]. */
 int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, float* limit);
 /* PointToPlaneErrorMinimizer accumulation (yaml:18-19): out = 21 upper-tri of sum J J^T (row major

@@ -17,6 +17,9 @@ OK, NO_CONVERGENCE, BAD_CONFIG, HIP_ERROR, BAD_ARG = 0, 1, 2, 3, 4
 # lsgpu_icp_config.error_minimizer (LSGPU_MINIMIZER_*)
 MINIMIZER_POINT_TO_PLANE, MINIMIZER_POINT_TO_POINT = 0, 1
 
+# lsgpu_icp_config.matcher_knn: the largest k of KDTreeMatcher (LSGPU_MATCHER_KNN_MAX)
+MATCHER_KNN_MAX = 8
+
 # every symbol include/lsgpu_icp.h declares (tests/test_abi.py checks the export table against this)
 ABI_SYMBOLS = [
     "lsgpu_icp_config_yaml", "lsgpu_icp_config_default", "lsgpu_icp_create", "lsgpu_icp_destroy",
@@ -24,7 +27,7 @@ ABI_SYMBOLS = [
     "lsgpu_chain_config_yaml", "lsgpu_chain_config_default", "lsgpu_icp_filter_reference",
     "lsgpu_icp_filter_reading", "lsgpu_icp_compute", "lsgpu_cloud_upload", "lsgpu_cloud_release",
     "lsgpu_cloud_size", "lsgpu_icp_compute_clouds", "lsgpu_icp_compute_clouds_upload", "lsgpu_filter_cylinder", "lsgpu_filter_voxel_grid",
-    "lsgpu_icp_get_reference_mean", "lsgpu_icp_get_info", "lsgpu_icp_get_policy_info", "lsgpu_comm_get_unique_id", "lsgpu_icp_comm_init", "lsgpu_knn", "lsgpu_trim_limit", "lsgpu_normal_eq",
+    "lsgpu_icp_get_reference_mean", "lsgpu_icp_get_info", "lsgpu_icp_get_policy_info", "lsgpu_comm_get_unique_id", "lsgpu_icp_comm_init", "lsgpu_knn", "lsgpu_knn_k", "lsgpu_trim_limit", "lsgpu_normal_eq",
     "lsgpu_point_to_point", "lsgpu_point_to_point_solve",
     "lsgpu_transform_points", "lsgpu_rotate_descriptors", "lsgpu_filter_random_sampling",
     "lsgpu_filter_sampling_surface_normal", "lsgpu_check_rigid", "lsgpu_correct_rigid", "lsgpu_rotation_distance",
@@ -54,7 +57,8 @@ class IcpConfig(C.Structure):
         ("profile_kernels", C.c_int),
         ("reserved", C.c_int * 1),          # reserved[0] = 1 disables the trimmed-radius cap (debug)
         ("error_minimizer", C.c_int),       # MINIMIZER_*
-        ("reserved_", C.c_int * 6),
+        ("matcher_knn", C.c_int),           # KDTreeMatcher knn: 0 / 1 one neighbour, 2..MATCHER_KNN_MAX k nearest matches
+        ("reserved_", C.c_int * 5),
     ]
 
 
@@ -197,6 +201,7 @@ def lib() -> C.CDLL:
     L.lsgpu_comm_get_unique_id.argtypes = [C.c_char_p]
     L.lsgpu_icp_comm_init.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
     L.lsgpu_knn.argtypes = [vp, fp, i64, C.POINTER(C.c_float), fp, fp]
+    L.lsgpu_knn_k.argtypes = [vp, fp, i64, C.POINTER(C.c_float), C.c_int, fp, fp]
     L.lsgpu_trim_limit.argtypes = [vp, fp, i64, C.c_float, C.POINTER(C.c_float)]
     L.lsgpu_normal_eq.argtypes = [vp, fp, i64, C.POINTER(C.c_float), fp, fp, C.c_float,
                                   C.POINTER(C.c_double)]

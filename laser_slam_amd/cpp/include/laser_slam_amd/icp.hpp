@@ -253,7 +253,7 @@ class ICP {
   }
 
   // Accepts the module chain of laser_slam/configurations/icp_default.yaml, with PointToPlaneErrorMinimizer or
-  // PointToPointErrorMinimizer; any other module is a configuration error (PointMatcher's registrar throws on unknown
+  // PointToPointErrorMinimizer and KDTreeMatcher knn 1..LSGPU_MATCHER_KNN_MAX (epsilon 0); any other module is a configuration error (PointMatcher's registrar throws on unknown
   // names as well).
   void loadFromYaml(std::istream& in) {
     lsgpu_icp_config c;
@@ -286,7 +286,11 @@ class ICP {
         if ((int)num("samplingMethod", 0) != 0) throw ConfigError("samplingMethod != 0 is not implemented");
       } else if (sec == "matcher" && name == "KDTreeMatcher") {
         has_matcher = true;
-        if ((int)num("knn", 1) != 1 || num("epsilon", 0) != 0.0) throw ConfigError("only knn 1 / epsilon 0");
+        // knn 1..LSGPU_MATCHER_KNN_MAX, exact search only; its other parameters (maxDist, searchType, ...) are not read
+        const double k = num("knn", 1);
+        if (!(k >= 1 && k <= LSGPU_MATCHER_KNN_MAX) || k != (double)(int)k || num("epsilon", 0) != 0.0)
+          throw ConfigError("KDTreeMatcher: knn 1.." + std::to_string(LSGPU_MATCHER_KNN_MAX) + " with epsilon 0 is implemented");
+        c.matcher_knn = (int)k;
       } else if (sec == "outlierFilters" && name == "TrimmedDistOutlierFilter") {
         if (has_outlier) throw ConfigError("outlierFilters: one TrimmedDistOutlierFilter at most");
         has_outlier = true; c.trim_ratio = (float)num("ratio", 0.85);

@@ -4,6 +4,7 @@
 // PointMatcher::ICP::compute at laser_slam/src/laser_track.cpp:496):
 //   lsgpu_grid.hip.h   k_ref_* / k_chunk_* / k_cells_*   KDTreeMatcher::init          (yaml:9-12)
 //   lsgpu_knn.hip.h    k_knn_seed / k_knn_tile / k_knn_fallback  ...::findClosests (knn 1, eps 0)
+//   lsgpu_knn_k.hip.h  k_knnk_seed / k_knnk_tile / k_knnk_fallback  ...::findClosests (knn 2..8, eps 0)
 //   lsgpu_solve.hip.h  k_hist* / find_bin                TrimmedDistOutlierFilter     (yaml:14-16)
 //                      k_normal_eq / k_ne_final          PointToPlaneErrorMinimizer   (yaml:18-19)
 //                                                        / PointToPointErrorMinimizer (template parameter)

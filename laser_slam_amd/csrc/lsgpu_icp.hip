@@ -29,6 +29,7 @@
 #include "lsgpu_tuning.h"
 #include "lsgpu_policy.h"
 #include "lsgpu_knn.hip.h"
+#include "lsgpu_knn_k.hip.h"
 #include "lsgpu_cone.hip.h"
 #ifdef LSGPU_EXPERIMENTS
 #include "lsgpu_knn_rows.hip.h"   // measured-slower variants, kept as the record of what was tried
@@ -298,6 +299,8 @@ struct lsgpu_icp {
   DevBuf<int> ids;   DevBuf<float> d2;
   DevBuf<int> ids_io; DevBuf<float> d2_io;
   DevBuf<uint32_t> strag;
+  // k-match loop (lsgpu_icp_config.matcher_knn >= 2) and lsgpu_knn_k: k entries per sorted query (lsgpu_knn_k.hip.h)
+  DevBuf<float4> kmatch; DevBuf<float> kd2;
   DevBuf<uint32_t> hist;      // 3 * kHistBins
   DevBuf<SelState> sel;       // [0] input rank, [1] after pass 2, [2] after pass 3
   DevBuf<double> ne_partials; // kNeBlocks * 32
@@ -426,7 +429,8 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
   *out = nullptr;
   if (!(cfg->trim_ratio > 0.f && cfg->trim_ratio <= 1.f) || cfg->max_iterations < 1 ||
       cfg->smooth_length < 1 ||
-      (cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_PLANE && cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT))
+      (cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_PLANE && cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT) ||
+      cfg->matcher_knn < 0 || cfg->matcher_knn > LSGPU_MATCHER_KNN_MAX)
     return LSGPU_BAD_CONFIG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
@@ -466,7 +470,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
   h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
-  h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->hist.release();
+  h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->sel.release(); h->ne_partials.release(); h->ne_gpartials.release(); h->ne_tickets.release(); h->ne_out.release(); h->limit_dev.release();
   for (auto& e : h->comm_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : h->knn_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); (void)hipEventDestroy(e.d); (void)hipEventDestroy(e.e); }
@@ -846,6 +850,54 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
   return LSGPU_OK;
 }
 
+// ---- k nearest matches (lsgpu_knn_k.hip.h): the k-best search of the queries in h->rdq into h->kmatch / h->kd2.
+//   st    : loop state (T from it, `done` exits) or nullptr (T from the argument: kernel-level API)
+//   seed  : the queries have no warm start yet (first iteration of an align, kernel-level API)
+template <int K>
+static void launch_knn_k(lsgpu_icp* h, const KnnKArgs& a, bool seed) {
+  const int nq = a.nq;
+  if (seed) hipLaunchKernelGGL(k_knnk_seed<K>, dim3(nblk(nq)), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL(k_knnk_tile<K>, dim3((nq + 63) / 64), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL(k_knnk_fallback<K>, dim3(kFallbackBlocks), dim3(256), 0, h->stream, a);
+}
+
+static int run_knn_k(lsgpu_icp* h, int k, const Mat34& T, const IcpState* st, bool seed, bool timed) {
+  const int64_t nq = h->nq;
+  HIPC(h->kmatch.reserve((size_t)k * nq)); HIPC(h->kd2.reserve((size_t)k * nq));
+  KnnKArgs a;
+  a.rdq = h->rdq.p; a.nq = (int)nq; a.T = T; a.st = st; a.g = h->grid; a.pts = h->pts.p; a.chunks = h->chunks.p;
+  a.kmatch = h->kmatch.p; a.kd2 = h->kd2.p; a.strag = h->strag.p; a.strag_count = h->counters.p + 32;
+  a.r_cap = kKnnKRCap;
+  if (!st) HIPC(hipMemsetAsync(a.strag_count, 0, sizeof(uint32_t), h->stream));  // (align: k_align_init, then the normal equations re-arm it)
+  lsgpu_icp::KnnEv* ev = nullptr;
+  if (timed) {   // (the same event record as run_knn: main launches a..b, fallback b..c)
+    if (h->knn_events_used == h->knn_events.size()) {
+      lsgpu_icp::KnnEv n{};
+      HIPC(hipEventCreate(&n.a)); HIPC(hipEventCreate(&n.b)); HIPC(hipEventCreate(&n.c));
+      HIPC(hipEventCreate(&n.d)); HIPC(hipEventCreate(&n.e));
+      h->knn_events.push_back(n);
+    }
+    ev = &h->knn_events[h->knn_events_used++];
+    ev->second = false;
+    HIPC(hipEventRecord(ev->a, h->stream));
+  }
+  switch (k) {
+    case 1: launch_knn_k<1>(h, a, seed); break;
+    case 2: launch_knn_k<2>(h, a, seed); break;
+    case 3: launch_knn_k<3>(h, a, seed); break;
+    case 4: launch_knn_k<4>(h, a, seed); break;
+    case 5: launch_knn_k<5>(h, a, seed); break;
+    case 6: launch_knn_k<6>(h, a, seed); break;
+    case 7: launch_knn_k<7>(h, a, seed); break;
+    case 8: launch_knn_k<8>(h, a, seed); break;
+    default: h->err = "knn_k: k out of range"; return LSGPU_BAD_ARG;
+  }
+  static_assert(kKnnKMax == 8, "one instantiation per k");
+  if (timed) { HIPC(hipEventRecord(ev->b, h->stream)); }
+  HIPC(hipGetLastError());
+  return LSGPU_OK;
+}
+
 #define RCCLC(expr)                                                                     \
   do {                                                                                  \
     ncclResult_t r__ = (expr);                                                          \
@@ -885,6 +937,7 @@ static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zer
 // is a direction index built for the current reference at all?  (host-side facts only)
 static bool cone_wanted(const lsgpu_icp* h) {
   const int64_t nr = h->nr;
+  if (h->cfg.matcher_knn >= 2) return false;   // (the k-match loop searches the voxel grid only)
   if (!(tuning().cone && h->cone_origin_inside && nr >= 1024)) return false;
   // a reference with more points than 0.6 x the occupancy limit x the number of bins cannot come out below the limit
   // (measured: 4.3 / 6.3 / 8.5 points per occupied bin at 3.0 / 4.0 / 5.0 per bin): spare it the build (1.8 ms at 8 M points)
@@ -1107,6 +1160,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
   if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return LSGPU_BAD_ARG;
   h->err.clear();
   RcclApi* api = rccl_api();
+  if (h->cfg.matcher_knn >= 2) {
+    h->err = "comm_init: the split-scan mode runs knn 1 only (matcher_knn >= 2 is not supported there)";
+    return LSGPU_BAD_CONFIG;
+  }
   if (!api) { h->err = "librccl.so.1 could not be loaded"; return LSGPU_HIP_ERROR; }
   HIPC(hipSetDevice(h->device));
   if (h->comm) { (void)api->CommDestroy(h->comm); h->comm = nullptr; }
@@ -1163,6 +1220,42 @@ int lsgpu_knn(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[1
   if (!dev_out) {
     HIPC(hipMemcpyAsync(ids, ids_o, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
     HIPC(hipMemcpyAsync(d2, d2_o, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPC(hipStreamSynchronize(h->stream));
+  return LSGPU_OK;
+}
+
+int lsgpu_knn_k(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16], int k, int32_t* ids, float* d2) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (h->nr <= 0) { h->err = "knn_k: no reference set"; return LSGPU_BAD_ARG; }
+  if (k < 1 || k > LSGPU_MATCHER_KNN_MAX) { h->err = "knn_k: k must be in [1, 8]"; return LSGPU_BAD_ARG; }
+  if (h->nr < k) { h->err = "knn_k: the reference has fewer points than k"; return LSGPU_BAD_ARG; }
+  if (nq == 0) return LSGPU_OK;
+  if (!query_xyz1 || !ids || !d2 || nq < 0 || nq > 0x7FFFFFF0ll / k) {
+    if (nq > 0x7FFFFFF0ll / k) h->err = "knn_k: k x nq exceeds the 32-bit pair count";
+    return LSGPU_BAD_ARG;
+  }
+  HIPC(hipSetDevice(h->device));
+  float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const Mat34 Tm = to_mat34(T ? T : I);
+  int rc = prepare_queries(h, query_xyz1, nq, to_mat34(I));   // (the transform is applied inside the search kernels)
+  if (rc) return rc;
+  rc = run_knn_k(h, k, Tm, nullptr, true, false);
+  if (rc) return rc;
+  const int64_t np = (int64_t)k * nq;
+  const bool dev_out = is_device_ptr(ids);
+  int* ids_o = ids; float* d2_o = d2;
+  if (!dev_out) {
+    HIPC(h->ids_io.reserve(np)); HIPC(h->d2_io.reserve(np));
+    ids_o = h->ids_io.p; d2_o = h->d2_io.p;
+  }
+  hipLaunchKernelGGL(k_knnk_unpermute, dim3(nblk(np)), dim3(256), 0, h->stream, h->rdq.p, (int)np, k, h->kmatch.p,
+                     h->kd2.p, h->pts.p, ids_o, d2_o);
+  HIPC(hipGetLastError());
+  if (!dev_out) {
+    HIPC(hipMemcpyAsync(ids, ids_o, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipMemcpyAsync(d2, d2_o, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
   }
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
@@ -2399,6 +2492,19 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
   return rc;
 }
 
+// the pair-indexed instantiations of the loop's normal-equation kernel (k-match loop, k = 2..LSGPU_MATCHER_KNN_MAX)
+using NeLoopFn = decltype(&k_normal_eq_loop<kPointToPlane>);
+static NeLoopFn ne_loop_pairs(bool p2p, int k) {
+  static const NeLoopFn tab[2][kKnnKMax + 1] = {
+      {nullptr, nullptr, k_normal_eq_loop<kPointToPlane, 2>, k_normal_eq_loop<kPointToPlane, 3>, k_normal_eq_loop<kPointToPlane, 4>,
+       k_normal_eq_loop<kPointToPlane, 5>, k_normal_eq_loop<kPointToPlane, 6>, k_normal_eq_loop<kPointToPlane, 7>,
+       k_normal_eq_loop<kPointToPlane, 8>},
+      {nullptr, nullptr, k_normal_eq_loop<kPointToPoint, 2>, k_normal_eq_loop<kPointToPoint, 3>, k_normal_eq_loop<kPointToPoint, 4>,
+       k_normal_eq_loop<kPointToPoint, 5>, k_normal_eq_loop<kPointToPoint, 6>, k_normal_eq_loop<kPointToPoint, 7>,
+       k_normal_eq_loop<kPointToPoint, 8>}};
+  return tab[p2p ? 1 : 0][k];
+}
+
 int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
                     float T_out[16], lsgpu_icp_stats* stats) {
   if (!h || !T_init || !T_out) return LSGPU_BAD_ARG;
@@ -2417,10 +2523,19 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   // Local reasons not to start.  In the split-scan mode they are NOT returned yet: a rank that left here would
   // leave its peers blocked in the first collective, so every rank first takes part in the entry handshake below.
   int local_rc = LSGPU_OK;
+  // KDTreeMatcher knn: 1, or k >= 2 nearest matches per reading point (k N pairs; the split-scan mode refuses such handles)
+  const int kk = h->cfg.matcher_knn >= 2 ? h->cfg.matcher_knn : 1;
+  const bool kmatch = kk > 1;
   if (h->nr <= 0 || nq <= 0 || !reading_xyz1) {  // empty cloud: ConvergenceError upstream
     h->err = "align: empty reading or no reference";
     local_rc = LSGPU_NO_CONVERGENCE;
   } else if (nq > 0x7FFFFFF0ll) {
+    local_rc = LSGPU_BAD_ARG;
+  } else if (kmatch && h->nr < kk) {
+    h->err = "align: the reference has fewer points than the matcher's knn";
+    local_rc = LSGPU_BAD_ARG;
+  } else if (kmatch && nq > 0x7FFFFFF0ll / kk) {
+    h->err = "align: knn x reading points exceeds the 32-bit pair count";
     local_rc = LSGPU_BAD_ARG;
   } else if (!lsgpu_check_rigid(T_init)) {
     // step 5 moves the reading with RigidTransformation::compute, which throws TransformationError for such a matrix
@@ -2483,7 +2598,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 4; ++c) hst->T_rows[r * 4 + c] = hst->T_iter[c * 4 + r];
   hst->prev_limit = INFINITY; hst->cap2 = INFINITY;
-  hst->cap_enabled = h->cfg.reserved[0] == 0 ? 1 : 0;
+  hst->cap_enabled = (h->cfg.reserved[0] == 0 && !kmatch) ? 1 : 0;   // (no radius cap in the k-match loop)
   hst->minimizer = h->cfg.error_minimizer;
   hst->max_iter = max_it; hst->smooth = h->cfg.smooth_length;
   hst->lim_rot = h->cfg.min_diff_rot; hst->lim_trans = h->cfg.min_diff_trans;
@@ -2493,12 +2608,12 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     hostmath::checker_push(&cs, ia.chk0, hst->T_iter);
     hst->counter = cs.counter; hst->n_hist = cs.n_hist;
   }
-  const uint32_t k = trim_rank(nq_total, h->cfg.trim_ratio);
+  const uint32_t k = trim_rank((int64_t)kk * nq_total, h->cfg.trim_ratio);   // (TrimmedDist ranks all k N distances)
   HIPC(h->sel_aux.reserve(kSelFailFlag + 4));
   HIPC(h->spread_flag.reserve((size_t)((nq + 63) / 64))); HIPC(h->spread_list.reserve(kFrontMax)); HIPC(h->spread_cnt.reserve(2));
   HIPC(h->sel_win.reserve((size_t)kSelWinRows * 512));
   HIPC(h->amb_key.reserve((size_t)kSelAmbCap)); HIPC(h->amb_val.reserve((size_t)kSelAmbCap * 32));
-  hst->sel_wide = (!h->comm && tuning().fused_select) ? 1 : 0;
+  hst->sel_wide = (!h->comm && tuning().fused_select && !kmatch) ? 1 : 0;
   h->n_spread_host = 0; h->n_spread_known = false;
   ia.state = *hst;
   ia.sel0 = SelState{0u, k};   // sel[0] = {0, rank}: constant during an align
@@ -2510,7 +2625,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   hipLaunchKernelGGL(k_align_init, dim3(64), dim3(256), 0, h->stream, ia);
   HIPC(hipGetLastError());
 
-  const int nb = std::min(kNeBlocks, nblk(nq));
+  const int nb = std::min(kNeBlocks, nblk((int64_t)kk * nq));
   const bool timed = h->cfg.profile_kernels != 0;
   const Mat34 Tdummy = to_mat34(hst->T_iter);
   std::vector<size_t> ev_of_launch;  // event index of every enqueued iteration
@@ -2519,6 +2634,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   const bool p2p = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
   const auto ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
   const auto update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
+  const NeLoopFn ne_loop_k = kmatch ? ne_loop_pairs(p2p, kk) : nullptr;
   // The launch policy (lsgpu_policy.h) decides what every iteration is made of and when the host looks at the loop
   // state; this function executes its decisions.  (tests/cpp/policy_check.cpp drives the same state machine on the CPU.)
   policy::Config& pc = h->pol_cfg;
@@ -2530,6 +2646,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   pc.seed_cap = tuning().seed_cap; pc.cap_enabled = h->cfg.reserved[0] == 0;
   pc.two_pass_select = !h->comm && tuning().fused_select && tuning().two_pass_select;
   pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
+  pc.kmatch = kmatch;
   policy::State& pol = h->pol;
   if (h->cone_build_in_align) { h->cone_ok = cone_wanted(h); h->cone_decided = false; }   // (its build follows the first iteration, below)
   // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
@@ -2547,6 +2664,27 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     // all-reduce (the host knows beforehand that no select kernel will run: sel_streak comes from the global limit,
     // so every rank takes the same decision); un-committed iterations there run the plain three-pass select.
     int r = LSGPU_OK;
+    if (kmatch) {   // the k-match plan (lsgpu_policy.h): k-best search, three-pass select on the k N distances, pair-indexed sums
+      const int np = (int)(kk * nq);
+      r = run_knn_k(h, kk, Tdummy, h->state.p, itn.seed, timed);                                     // 6a+6b
+      if (r) return r;
+      ev_of_launch.push_back(h->knn_events_used ? h->knn_events_used - 1 : 0);
+      r = run_select(h, h->kd2.p, np, k, false /* armed by k_align_init / the previous k_normal_eq_loop */, h->state.p, true, false);  // 6c
+      if (r) return r;
+      lsgpu_icp::KnnEv* evk = (timed && h->knn_events_used) ? &h->knn_events[h->knn_events_used - 1] : nullptr;
+      if (evk) HIPC(hipEventRecord(evk->d, h->stream));
+      hipLaunchKernelGGL(ne_loop_k, dim3(nb), dim3(256), 0, h->stream, h->rdq.p, np,
+                         h->state.p, h->kmatch.p, h->kd2.p, p2p ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
+                         h->counters.p + 32, h->ne_tickets.p, h->ne_partials.p, h->ne_gpartials.p, h->ne_out.p,
+                         h->chk_hist.p, h->trace_dev.p, max_it, 0, split_update ? 0 : 1,
+                         h->sel_aux.p, (uint32_t*)nullptr, 0, (uint32_t*)nullptr,
+                         0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0);   // 6d (+6e)
+      if (split_update)
+        hipLaunchKernelGGL(update, dim3(1), dim3(64), 0, h->stream, h->state.p, h->ne_out.p,
+                           h->chk_hist.p, h->trace_dev.p, max_it, 0, h->sel_aux.p);                       // 6d+6e
+      if (evk) HIPC(hipEventRecord(evk->e, h->stream));
+      return hipGetLastError() == hipSuccess ? LSGPU_OK : LSGPU_HIP_ERROR;
+    }
     if (itn.knn) {
       r = run_knn(h, Tdummy, h->state.p, itn, timed, itn.seed && itn.capped ? k : 0xFFFFFFFFu);  // 6a+6b
       if (r) return r;

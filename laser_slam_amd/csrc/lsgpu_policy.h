@@ -32,6 +32,7 @@ struct Config {               // constant during an alignment (from Tuning and t
   float cone_heavy_share = 0.07f;    // >= 2: the index is never priced
   float cone_max_occupancy = 7.f;
   double straggler_share = 0.02;     // lanes the index could not serve, per settled iteration, above which it is dropped
+  bool kmatch = false;        // k nearest matches (lsgpu_icp_config.matcher_knn >= 2): see State::plan
 };
 
 struct Iteration {            // one enqueued iteration: what the search, the select and the normal equations are told
@@ -103,6 +104,7 @@ struct State {
 
   // ---- what the next iteration is made of
   Iteration plan(const Config& c, bool seed, bool capped, bool wide, bool knn, bool price_next) {
+    if (c.kmatch) return plan_kmatch(seed, knn);
     Iteration it;
     it.knn = knn; it.seed = seed; it.capped = capped; it.wide = wide;
     // capped launches without a wave-per-query pass may fold the first half of the select into the search kernel; in the
@@ -116,6 +118,18 @@ struct State {
     it.price = knn && (enq == c.cone_from - 1 || price_next);
     it.ordinal = enq;
     if (!it.committed) first_select = false; else ++committed_iterations;
+    return it;
+  }
+
+  // The k-match plan: a k-best search on the voxel grid every iteration, seeded in the first one and warm-started from
+  // the previous matches after it; no direction index, no predicted / committed select, no radius cap (the select runs
+  // its three passes on the k N distances).  So no look can ask for a repeat: Continue, Done or GiveUp.
+  Iteration plan_kmatch(bool seed, bool knn) {
+    Iteration it;
+    it.knn = knn; it.seed = seed; it.capped = false; it.wide = false;
+    it.predicted = false; it.committed = false; it.full_select = true;
+    it.cone_iter = false; it.dense_wait = false; it.price = false;
+    it.ordinal = enq;
     return it;
   }
 

@@ -453,7 +453,10 @@ __global__ __launch_bounds__(64) void k_icp_update(IcpState* __restrict__ st,
 #define LSGPU_NE_UNROLL 8
 #endif
 constexpr int kNeUnroll = LSGPU_NE_UNROLL;  // points whose loads are in flight together, per lane
-template <int MIN>
+// KP > 1: the pair-indexed instantiation of the k-match loop (KDTreeMatcher knn = KP, lsgpu_knn_k.hip.h): `nq` counts
+// pairs, `match` / `d2` hold KP entries per query and pair j reads query j / KP.  The select, the sums, their order and
+// the update are those of the 1-NN loop; its launches pass no fused / predicted / committed select.
+template <int MIN, int KP = 1>
 __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict__ rdq, int nq,
                                                         IcpState* __restrict__ ist,
                                                         const float4* __restrict__ match,
@@ -637,7 +640,8 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
         use[u] = use[u] && inl;
       }
       qq[u] = use[u] ? match[j] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-      rr[u] = use[u] ? rdq[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (KP > 1) rr[u] = use[u] ? rdq[j / KP] : make_float4(0.f, 0.f, 0.f, 0.f);
+      else rr[u] = use[u] ? rdq[j] : make_float4(0.f, 0.f, 0.f, 0.f);
       use[u] = use[u] && __float_as_int(qq[u].w) >= 0;
     }
 #pragma unroll

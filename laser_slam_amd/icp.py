@@ -78,16 +78,20 @@ def _raise(code: int, what: str, h=None):
 class IcpHandle:
     """One lsgpu_icp handle == one reference ``icp_`` member: one device, one HIP stream."""
 
-    def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None):
+    def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
-        or an _lib.MINIMIZER_* value."""
+        or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
+        every reading point is paired with its k nearest reference points)."""
         L = _lib.lib()
         if cfg is None:
             cfg = IcpConfig()
             L.lsgpu_icp_config_yaml(C.byref(cfg))
-        if error_minimizer is not None:
+        if error_minimizer is not None or matcher_knn is not None:
             cfg = IcpConfig.from_buffer_copy(cfg)       # (the caller's config stays as it is)
-            cfg.error_minimizer = _MINIMIZERS.get(error_minimizer, error_minimizer)
+            if error_minimizer is not None:
+                cfg.error_minimizer = _MINIMIZERS.get(error_minimizer, error_minimizer)
+            if matcher_knn is not None:
+                cfg.matcher_knn = int(matcher_knn)
         self.cfg = cfg
         self.device = device
         self._h = C.c_void_p()
@@ -370,6 +374,19 @@ class IcpHandle:
             _raise(rc, "lsgpu_knn", self._h)
         return ids, d2
 
+    def knn_k(self, query_xyz1, k: int, T=None):
+        """KDTreeMatcher::findClosests with knn = k: (ids, d2), each of shape (n, k) -- row i holds query i's k nearest
+        reference points (indices as given to set_reference) in ascending squared distance."""
+        p, _k, n = _as_f32(query_xyz1, 4)
+        ids = np.empty((n, k), np.int32)
+        d2 = np.empty((n, k), np.float32)
+        tp = _fp(_t16(T)) if T is not None else None
+        rc = _lib.lib().lsgpu_knn_k(self._h, p, n, tp, int(k), ids.ctypes.data if n else None,
+                                    d2.ctypes.data if n else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_knn_k", self._h)
+        return ids, d2
+
     def trim_limit(self, d2, ratio: float) -> float:
         a = np.ascontiguousarray(d2, np.float32)
         lim = C.c_float()
@@ -556,6 +573,7 @@ class ChainConfig:
     smooth_length: int = 4                  # yaml:27  (module default 3)
     seed: int = -1                          # >= 0: srand(seed) before the filters
     error_minimizer: str = "PointToPlaneErrorMinimizer"   # yaml:18-19, or "PointToPointErrorMinimizer"
+    matcher_knn: int = 1                    # yaml:11  KDTreeMatcher knn (1.._lib.MATCHER_KNN_MAX), epsilon 0
     extra: dict = field(default_factory=dict)
 
 
@@ -627,9 +645,12 @@ class ICP:
                     if int(params.get("samplingMethod", 0)) != 0:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "samplingMethod != 0")
                 elif name == "KDTreeMatcher":
-                    if int(params.get("knn", 1)) != 1 or float(params.get("epsilon", 0)) != 0.0:
+                    # (its other parameters -- maxDist, searchType, ... -- are not read: a finite maxDist is ignored)
+                    knn = int(params.get("knn", 1))
+                    if not 1 <= knn <= _lib.MATCHER_KNN_MAX or float(params.get("epsilon", 0)) != 0.0:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml",
-                                         "only knn 1 / epsilon 0 is implemented")
+                                         f"KDTreeMatcher: knn 1..{_lib.MATCHER_KNN_MAX} with epsilon 0 is implemented")
+                    ch.matcher_knn = knn
                 elif name == "TrimmedDistOutlierFilter":
                     ch.trim_ratio = float(params.get("ratio", 0.85))
                 elif name in _MINIMIZERS:
@@ -667,7 +688,7 @@ class ICP:
             cfg.min_diff_rot = self.chain.min_diff_rot
             cfg.min_diff_trans = self.chain.min_diff_trans
             cfg.smooth_length = self.chain.smooth_length
-            self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer)
+            self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer, self.chain.matcher_knn)
         return self._handle
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
