@@ -1,6 +1,6 @@
 #!/bin/bash
 # dev helper, run ON the GPU box through gpurun:  bash devtools/gpu_check.sh <tag> [steps...]
-# steps: tests bench bench0 prof pmc sq batch cfg3 rows2 (default: tests bench prof)
+# steps: tests bench bench0 prof pmc sq batch split cfg3 (default: tests bench prof)
 # Everything lands under $OUT_DIR/<tag>_* (default bench_out/); every step has its own timeout so a hung kernel cannot eat the box.
 tag=${1:-chk}; shift
 steps=${@:-tests bench prof}
@@ -11,7 +11,6 @@ export TMPDIR=/tmp
 for s in $steps; do
   case $s in
     tests)   timeout 600 python -m pytest tests -m gpu -x -q > $out/${tag}_tests.log 2>&1; echo "tests rc=$?"; tail -3 $out/${tag}_tests.log ;;
-    rows2)   LSGPU_SO=$PWD/devtools/liblsgpu_exp.so LSGPU_KNN_ROWS=2 timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q > $out/${tag}_rows2.log 2>&1; echo "rows2 rc=$?"; tail -3 $out/${tag}_rows2.log ;;
     bench)   timeout 600 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"; cut -c1-1500 $out/${tag}_bench.json ;;
     bench0)  timeout 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-compute-e2e > $out/${tag}_bench0.json 2> $out/${tag}_bench0.err; echo "bench0 rc=$?"; cut -c1-600 $out/${tag}_bench0.json ;;
     prof)    rm -rf $out/prof_${tag}

@@ -10,7 +10,7 @@ def mean_counter(path, name):
     per_kernel = per_kernel_all.setdefault(name, {})
     for r in csv.DictReader(open(path)):
         k = r["Kernel_Name"]
-        if r["Counter_Name"] == name and ("k_knn_tile" in k or "k_knn_cone" in k or "k_knn_fallback" in k or "k_knn_rowq" in k):
+        if r["Counter_Name"] == name and ("k_knn_tile" in k or "k_knn_cone" in k or "k_knn_fallback" in k):
             # launches enqueued behind the end of an alignment exit at once (a few microseconds, no traffic): not launches
             # of the search, left out of the mean like bench.py leaves them out of the launch time
             main = "k_knn_tile" in k or "k_knn_cone" in k
@@ -31,7 +31,7 @@ out = {"n_az": 16384, "csrc_sha": csrc_digest(), "kernel": "one kNN launch = k_k
                          "k_knn_tile": {"fetch": pk.get("FETCH_SIZE", {}).get("tile"), "write": pk.get("WRITE_SIZE", {}).get("tile")}},
        "fetch_size_kb_per_launch": f, "write_size_kb_per_launch": w,
        "hbm_bytes_per_launch": (2 * f + w) * 1024,
-       "dispatches": {"k_knn_cone + k_knn_tile": nt, "k_knn_fallback + k_knn_rowq": nf, "launches that exited at once (left out)": skipped[0] // 2},
+       "dispatches": {"k_knn_cone + k_knn_tile": nt, "k_knn_fallback": nf, "launches that exited at once (left out)": skipped[0] // 2},
        "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes with --kernel-trace, mean over the "
                  "kNN launches (those that exit at once behind the end of an alignment excluded) of `python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-compute-e2e` (the timed compute steps + the profiled loop steps of configs[1]); bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
                  "(gfx950 FETCH_SIZE counts 128-B requests as 64 B: MI355X_MICROARCH.md HBM section; WRITE_SIZE uncalibrated)",

@@ -20,9 +20,6 @@
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is opened lazily (dlopen) by lsgpu_icp_comm_init
-#ifdef LSGPU_EXPERIMENTS
-#include <rocprim/device/device_radix_sort.hpp>   // experiments build only, behind LSGPU_ROCPRIM_SORT: the library sort as a cross-check of lsgpu_sort.hip.h
-#endif
 
 #include "../../include/lsgpu_icp.h"
 #include "lsgpu_grid.hip.h"
@@ -31,9 +28,6 @@
 #include "lsgpu_knn.hip.h"
 #include "lsgpu_knn_k.hip.h"
 #include "lsgpu_cone.hip.h"
-#ifdef LSGPU_EXPERIMENTS
-#include "lsgpu_knn_rows.hip.h"   // measured-slower variants, kept as the record of what was tried
-#endif
 #include "lsgpu_solve.hip.h"
 #include "lsgpu_host_math.h"
 #include "lsgpu_ssn.hip.h"
@@ -262,9 +256,6 @@ struct lsgpu_icp {
   DevBuf<uint32_t> sel_win;   // committed select (split-scan mode): kSelWinRows x 512 window histogram
   DevBuf<uint2> amb_key;      // fused select: the distances of the limit's slice the normal equations set aside ...
   DevBuf<double> amb_val;     // ... and their contributions (kSelAmbCap x 32)
-#ifdef LSGPU_EXPERIMENTS
-  DevBuf<uint32_t> work;      // compacted list of searching queries (k_knn_classify -> k_knn_rows)
-#endif
 
   // device filters (lsgpu_ssn.hip.h)
   DevBuf<SsnSeg> ssn_seg_a, ssn_seg_b;
@@ -374,7 +365,6 @@ static constexpr int kNeBlocksMax = 2048;
 static const int kNeBlocks = tuning().ne_blocks;   // 64 .. kNeBlocksMax (lsgpu_tuning.h)
 static constexpr int kStatBlocks = 512;
 static constexpr int kHistBlocks = 256;
-static constexpr int kFallbackBlocksSettled = 1024;
 static constexpr int kFallbackBlocks = 8192;  // x 4 waves: one query per wave for up to 32 k stragglers, round robin beyond
 
 extern "C" {
@@ -463,9 +453,6 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   for (auto& c : h->clouds) c.release();
   h->submap.release();
   h->ref_in.release(); h->nrm_in.release(); h->scr_main.release(); h->scr_side.release();
-#ifdef LSGPU_EXPERIMENTS
-  h->work.release();
-#endif
   h->pts.release();
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
   h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
@@ -525,40 +512,23 @@ static void radix_pass(lsgpu_icp* h, const uint64_t* kin, const uint32_t* vin, u
 static int sort_pairs(lsgpu_icp* h, int64_t n, int nbits) {
   HIPC(h->sc->keys_alt.reserve(n));
   HIPC(h->sc->vals_alt.reserve(n));
-#ifdef LSGPU_EXPERIMENTS
-  const bool lib_sort = tuning().rocprim_sort;
-#else
-  const bool lib_sort = false;
-#endif
-  if (!lib_sort) {   // own radix sort (lsgpu_sort.hip.h)
-    const int items_env = tuning().sort_items;
-    const int items = items_env ? items_env : n >= (1 << 21) ? 16 : n >= (1 << 19) ? 8 : 4;
-    const int nblocks = (int)((n + 256 * items - 1) / (256 * items));
-    HIPC(h->sc->sort_hist.reserve((size_t)256 * nblocks + 256));
-    const int passes = std::max(1, (nbits + 7) / 8);   // (no key bits: one pass over an all-zero digit = a stable copy)
-    uint64_t *kin = h->sc->keys.p, *kout = h->sc->keys_alt.p;
-    uint32_t *vin = h->sc->vals.p, *vout = h->sc->vals_alt.p;
-    for (int p = 0; p < passes; ++p) {
-      const int shift = 8 * p, width = std::max(0, std::min(8, nbits - shift));
-      const uint32_t mask = (1u << width) - 1u;
-      if (items == 16) radix_pass<16>(h, kin, vin, kout, vout, n, shift, mask, nblocks);
-      else if (items == 8) radix_pass<8>(h, kin, vin, kout, vout, n, shift, mask, nblocks);
-      else radix_pass<4>(h, kin, vin, kout, vout, n, shift, mask, nblocks);
-      std::swap(kin, kout); std::swap(vin, vout);
-    }
-    HIPC(hipGetLastError());
-    if ((passes & 1) == 0) { std::swap(h->sc->keys, h->sc->keys_alt); std::swap(h->sc->vals, h->sc->vals_alt); }  // result is in `keys`
-    return LSGPU_OK;
+  const int items_env = tuning().sort_items;
+  const int items = items_env ? items_env : n >= (1 << 21) ? 16 : n >= (1 << 19) ? 8 : 4;
+  const int nblocks = (int)((n + 256 * items - 1) / (256 * items));
+  HIPC(h->sc->sort_hist.reserve((size_t)256 * nblocks + 256));
+  const int passes = std::max(1, (nbits + 7) / 8);   // (no key bits: one pass over an all-zero digit = a stable copy)
+  uint64_t *kin = h->sc->keys.p, *kout = h->sc->keys_alt.p;
+  uint32_t *vin = h->sc->vals.p, *vout = h->sc->vals_alt.p;
+  for (int p = 0; p < passes; ++p) {
+    const int shift = 8 * p, width = std::max(0, std::min(8, nbits - shift));
+    const uint32_t mask = (1u << width) - 1u;
+    if (items == 16) radix_pass<16>(h, kin, vin, kout, vout, n, shift, mask, nblocks);
+    else if (items == 8) radix_pass<8>(h, kin, vin, kout, vout, n, shift, mask, nblocks);
+    else radix_pass<4>(h, kin, vin, kout, vout, n, shift, mask, nblocks);
+    std::swap(kin, kout); std::swap(vin, vout);
   }
-#ifdef LSGPU_EXPERIMENTS
-  size_t bytes = 0;
-  HIPC(rocprim::radix_sort_pairs(nullptr, bytes, h->sc->keys.p, h->sc->keys_alt.p, h->sc->vals.p,
-                                 h->sc->vals_alt.p, (size_t)n, 0, nbits, h->cur));
-  HIPC(h->sc->sort_tmp.reserve(bytes));
-  bytes = h->sc->sort_tmp.cap;
-  HIPC(rocprim::radix_sort_pairs((void*)h->sc->sort_tmp.p, bytes, h->sc->keys.p, h->sc->keys_alt.p, h->sc->vals.p,
-                                 h->sc->vals_alt.p, (size_t)n, 0, nbits, h->cur));
-#endif
+  HIPC(hipGetLastError());
+  if ((passes & 1) == 0) { std::swap(h->sc->keys, h->sc->keys_alt); std::swap(h->sc->vals, h->sc->vals_alt); }  // result is in `keys`
   return LSGPU_OK;  // sorted: keys_alt / vals_alt
 }
 
@@ -599,9 +569,6 @@ static int prepare_queries(lsgpu_icp* h, const float* q_xyz1, int64_t nq, const 
   HIPC(h->rdq.reserve(nq));
   HIPC(h->prev.reserve(nq));
   HIPC(h->lb.reserve(nq));
-#ifdef LSGPU_EXPERIMENTS
-  HIPC(h->work.reserve(nq));
-#endif
   // order of the queries inside the waves: chosen on the device from the cloud's angular sampling density
   const int qorder = tuning().query_order;   // -1: automatic
   const float qelev = tuning().q_elev, qsect = tuning().q_sect;   // 0: automatic
@@ -653,9 +620,6 @@ static KnnArgs knn_args(lsgpu_icp* h, const Mat34& T) {
   a.ntiles = (int)((h->nq + 63) / 64); a.pad_index = (int)h->nr;
   a.chunk_budget = tuning().chunk_budget;
   a.cell_cache = h->cell_cache.p; a.cell_tags = h->cell_tags.p; a.cache_gen = h->cache_gen;
-#ifdef LSGPU_EXPERIMENTS
-  a.sparse_lanes = 0; a.xcd_swizzle = 0; a.work = h->work.p; a.work_count = h->counters.p + 34;
-#endif
   a.dbg = h->knn_dbg.p;
   a.dbg_wave = h->knn_dbg_wave.p;
   { a.dbg_flags = tuning().knn_dbg;
@@ -688,18 +652,12 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
   // `wide`: the balls may still be large (first iterations of an align, retries, kernel-level API): spread
   // waves with wide balls go to the wave-per-query pass, which is launched after the tile kernel
   const Tuning& tn = tuning();
-  // settled launches (capped, balls already small): EVERY spread wave hands its lanes on -- 64 divergent per-lane
-  // searches held single waves for 190 k cycles, the tail of a 46 k-cycle launch
-  const bool settled = capped && !wide && st && tn.route_all;
-  a.spread_route_r = wide ? tn.route_r : settled ? 1e-30f : 0.f;
+  const bool settled = capped && !wide && st;   // (capped, balls already small)
+  a.spread_route_r = wide ? tn.route_r : 0.f;
   a.chunk_budget = wide ? tn.chunk_budget_wide : tn.chunk_budget;
-#ifdef LSGPU_EXPERIMENTS
-  a.sparse_lanes = settled && tn.rowq ? tn.sparse_lanes : 0;
-#endif
   // front rows: spread tiles are remembered from the first searches on and searched row-wise by the first workgroups
-  // of the settled launches themselves -- no hand-over, no second launch (LSGPU_NO_FRONT: the separate row pass)
-  const bool front = tn.front && st && h->spread_cnt.p;
-  if (front) {
+  // of the settled launches themselves -- no hand-over, no second launch
+  if (st && h->spread_cnt.p) {   // (lsgpu_icp_align reserves the list before its loop)
     a.spread_flag = h->spread_flag.p; a.spread_list = h->spread_list.p; a.spread_cnt = h->spread_cnt.p;
     // (the front is sized from the list's length as the host last saw it -- it travels with the state every few
     // iterations --, from a guess before that: surplus workgroups exit at once, a listed tile beyond the front, or one
@@ -707,7 +665,6 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
     if (settled) {
       const int tiles = h->n_spread_known ? (int)h->n_spread_host : std::min(tn.front_guess, a.ntiles);
       a.front_blocks = kFrontPerTile * tiles;
-      a.spread_route_r = 0.f;
     }
   }
   if (predicted && !wide && capped && st) { a.sel_hist2 = h->hist.p + kHistBins; a.sel_below = h->sel_aux.p; }
@@ -788,37 +745,6 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
     HIPC(hipGetLastError());
     return LSGPU_OK;
   }
-#ifdef LSGPU_EXPERIMENTS
-  // measured-slower variants (DESIGN.md "Rejected after measurement"), compiled only into the experiments build:
-  //   knn_rows 1: settled launches classify first and search row-wise on the compacted list; 2: k_knn_rows also stands
-  //   in for k_knn_tile everywhere else; knn_lane: one lane per query in capped launches; tile_waves 4; xcd_swizzle
-  if (tn.knn_rows >= 1 && capped && !wide && st && !tn.knn_lane) {
-    hipLaunchKernelGGL(k_knn_classify, dim3((nq + kClassifyPerBlock - 1) / kClassifyPerBlock), dim3(256), 0, h->stream, a);
-    hipLaunchKernelGGL(k_knn_rows<true>, dim3(a.ntiles), dim3(64), 0, h->stream, a);
-    if (timed) { HIPC(hipEventRecord(ev->b, h->stream)); ev->second = true; HIPC(hipEventRecord(ev->c, h->stream)); }
-    HIPC(hipGetLastError());
-    return LSGPU_OK;
-  }
-  if (tn.knn_rows >= 2 && !tn.knn_lane) {
-    a.spread_route_r = 0.f;  // (no routing in the row-wise kernel; stragglers by radius still go to the fallback)
-    hipLaunchKernelGGL(k_knn_rows<false>, dim3(a.ntiles), dim3(64), 0, h->stream, a);
-    if (timed) HIPC(hipEventRecord(ev->b, h->stream));
-    if (!capped) hipLaunchKernelGGL(k_knn_fallback, dim3(kFallbackBlocks), dim3(256), 0, h->stream, a);
-    if (timed) { ev->second = true; HIPC(hipEventRecord(ev->c, h->stream)); }
-    HIPC(hipGetLastError());
-    return LSGPU_OK;
-  }
-  if (capped && tn.knn_lane) {
-    hipLaunchKernelGGL(k_knn_lane, dim3(nblk(nq)), dim3(256), 0, h->stream, a);
-    if (timed) { HIPC(hipEventRecord(ev->b, h->stream)); ev->second = true; HIPC(hipEventRecord(ev->c, h->stream)); }
-    HIPC(hipGetLastError());
-    return LSGPU_OK;
-  }
-  a.xcd_swizzle = tn.xcd_swizzle;
-  if (tn.tile_waves == 4)
-    hipLaunchKernelGGL((k_knn_tile<4, false>), dim3((a.ntiles + 3) / 4), dim3(256), 0, h->stream, a);
-  else
-#endif
   if (wide && tn.lazy_need)   // balls still as wide as the last ICP step: the instantiation that re-tests chunks before fetching them
     hipLaunchKernelGGL((k_knn_tile<1, true>), dim3(a.ntiles + a.front_blocks), dim3(64), 0, h->stream, a);
   else if (!wide && tn.lane_split)   // settled: most tiles have fewer than 32 searching lanes -- their candidates are shared out over the idle ones
@@ -826,18 +752,10 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
   else
     hipLaunchKernelGGL((k_knn_tile<1, false>), dim3(a.ntiles + a.front_blocks), dim3(64), 0, h->stream, a);
   if (timed) HIPC(hipEventRecord(ev->b, h->stream));
-  // stragglers (balls > r_cap) only exist in uncapped launches; a settled launch without front rows hands a few
-  // thousand queries at most to the row pass (one DPP row per query)
-  bool second = true;
-  if (a.front_blocks > 0) {
-    second = false;   // nothing was handed over
-  } else if (settled && tn.rowq) {
-    hipLaunchKernelGGL(k_knn_rowq, dim3(tn.rowq_blocks), dim3(256), 0, h->stream, a);
-  } else if (!capped || a.spread_route_r > 0.f) {
-    hipLaunchKernelGGL(k_knn_fallback, dim3(settled ? kFallbackBlocksSettled : kFallbackBlocks), dim3(256), 0, h->stream, a);
-  } else {
-    second = false;
-  }
+  // stragglers (balls > r_cap) only exist in uncapped launches, routed waves only in wide ones: capped launches that
+  // are not wide hand nothing over
+  const bool second = !capped || a.spread_route_r > 0.f;
+  if (second) hipLaunchKernelGGL(k_knn_fallback, dim3(kFallbackBlocks), dim3(256), 0, h->stream, a);
   if (timed && second) { ev->second = true; HIPC(hipEventRecord(ev->c, h->stream)); }   // (an event pair around nothing still reads ~5 us)
   if (pay_voxel) { HIPC(hipEventRecord(h->ev_pay[1], h->stream)); h->pay_voxel_timed = true; }
   if (pricing) {
@@ -1590,41 +1508,24 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
   SsnSeg* nxt = h->ssn_seg_b.p;
   const uint32_t* idx = nullptr;
   const int* root_axis = nullptr;   // per root of the in-workgroup levels: the axis its order follows (segmented level sorts)
-  // levels [0, glevels) with global sorts; the rest inside one workgroup per segment once a segment fits
-  // its LDS (<= kSsnLdsMax points, <= kSsnLdsLevels levels to go)
+  // levels [0, glevels) with global passes; the rest inside one workgroup per segment (k_ssn_tree) once a segment holds
+  // at most root_max points and log2(root_max / 8) levels to go
   int glevels = 0;
-  // (k_ssn_tree: up to ssn_root points and log2(ssn_root / 8) levels per workgroup; k_ssn_finish, LSGPU_SSN_OLD_FINISH: 2048 / 8)
-  const bool tree_finish = !tuning().ssn_old_finish;
   // (one workgroup per root: 8192-point roots leave half the chip idle on a scan of a million points -- 128 roots, 248 us --
   // where 4096-point roots and one more global level take 50 us less; a three-scan sub-map has 383 roots of 8192)
   const int root_auto = n >= 200ll * 8192 ? 8192 : n >= 200ll * 4096 ? 4096 : 2048;
-  const int root_max = tree_finish ? (tuning().ssn_root ? tuning().ssn_root : root_auto) : kSsnLdsMax;
-  int root_levels = kSsnLdsLevels;
-  if (tree_finish) { root_levels = 0; while ((8 << root_levels) < root_max) ++root_levels; }
+  const int root_max = tuning().ssn_root ? tuning().ssn_root : root_auto;
+  int root_levels = 0;
+  while ((8 << root_levels) < root_max) ++root_levels;
   {
-    const bool lds_finish = !tuning().ssn_global;
     int64_t c = n;
-    while (glevels < levels && !(lds_finish && c <= root_max && levels - glevels <= root_levels)) { c -= c / 2; ++glevels; }
+    while (glevels < levels && !(c <= root_max && levels - glevels <= root_levels)) { c -= c / 2; ++glevels; }
   }
-  // the sort-free levels hand SETS over (points in original-index order + a signature): only k_ssn_tree knows how to take
-  // them; the round-4 finish kernel and the all-global mode continue a sorted order, so they imply the sorted levels
-  const bool select_levels = !force_sort_levels && !tuning().ssn_sort_levels && !tuning().ssn_full_sort && tree_finish &&
-                             !tuning().ssn_global && glevels > 0;
+  // the sort-free levels hand SETS over (points in original-index order + a signature) to k_ssn_tree; the segmented
+  // sorts (LSGPU_SSN_SORT_LEVELS, and the fallback below) hand it a sorted order
+  const bool select_levels = !force_sort_levels && !tuning().ssn_sort_levels && glevels > 0;
   const uint32_t* root_sig = nullptr;   // per root of the in-workgroup levels: its signature (sort-free upper levels)
-  if (tuning().ssn_full_sort) {   // rounds 1-3: the whole cloud sorted by (segment, coordinate) at every level
-    for (int L = 0; L < glevels; ++L) {
-      hipLaunchKernelGGL(k_ssn_keys, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, idx,
-                         L ? h->ssn_seg_of.p : (const uint32_t*)nullptr, cur, knn, h->sc->keys.p, h->sc->vals.p);
-      int rc = sort_pairs(h, n, 32 + L);
-      if (rc) return rc;
-      idx = h->sc->vals_alt.p;
-      const int ns = 1 << L;
-      hipLaunchKernelGGL(k_ssn_split, dim3(nblk(ns)), dim3(256), 0, h->stream, src, idx, cur, ns, knn, nxt,
-                         (const int*)nullptr, (int*)nullptr);
-      hipLaunchKernelGGL(k_ssn_assign, dim3(nblk(n)), dim3(256), 0, h->stream, (int)n, cur, knn, h->ssn_seg_of.p, L == 0 ? 1 : 0);
-      std::swap(cur, nxt);
-    }
-  } else if (select_levels) {
+  if (select_levels) {
     // Sort-free upper levels (lsgpu_ssn_select.hip.h): a segment is a set + a signature, a level is the exact median in the
     // segment's total order (two 8-bit histogram passes over the range its points span + a per-segment selection among the
     // candidates left) and one stable partition: five launches per level, no sort.
@@ -1774,9 +1675,7 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
       idx = h->sc->vals.p;
     }
     uint32_t* idx_rw = const_cast<uint32_t*>(idx);
-    if (!tree_finish)
-      hipLaunchKernelGGL(k_ssn_finish, dim3(1 << glevels), dim3(256), 0, h->stream, src, idx_rw, cur, knn, levels - glevels, h->ssn_seg_of.p, nxt);
-    else if (root_max == 8192)
+    if (root_max == 8192)
       hipLaunchKernelGGL(k_ssn_tree<8192>, dim3(1 << glevels), dim3(1024), 0, h->stream, src, idx_rw, cur, knn, levels - glevels, h->ssn_seg_of.p, nxt, root_axis, root_sig);
     else if (root_max == 4096)
       hipLaunchKernelGGL(k_ssn_tree<4096>, dim3(1 << glevels), dim3(512), 0, h->stream, src, idx_rw, cur, knn, levels - glevels, h->ssn_seg_of.p, nxt, root_axis, root_sig);
@@ -2618,7 +2517,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   ia.state = *hst;
   ia.sel0 = SelState{0u, k};   // sel[0] = {0, rank}: constant during an align
   ia.state_dev = h->state.p; ia.chk_hist = h->chk_hist.p; ia.sel = h->sel.p;
-  ia.counters3 = h->counters.p + 32;   // stragglers, (unused), work-list length
+  ia.counters3 = h->counters.p + 32;   // stragglers, (unused), heavy-tile ticket
   ia.ne_ticket = h->ne_tickets.p; ia.sel_aux = h->sel_aux.p; ia.spread_flag = h->spread_flag.p;
   ia.spread_cnt = h->spread_cnt.p; ia.sel_win = h->sel_win.p; ia.hist = h->hist.p;
   ia.n_sel_aux = kSelFailFlag + 4; ia.n_spread_flag = (int)((nq + 63) / 64); ia.n_sel_win = kSelWinRows * 512;

@@ -926,10 +926,10 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     const double nw_dbg = s_on ? (double)an : nw;   // (stats build: the trace's `searching` field shows how many distances were set aside)
     out[31] = nw_dbg; fin[31] = nw_dbg;
 #else
-    out[31] = nw; fin[31] = nw;  // queries that had to search in this iteration (k_knn_classify), for the trace
+    out[31] = nw; fin[31] = nw;  // heavy-tile tickets the wide launch's k_knn_tile took in this iteration, for the trace
 #endif
     __hip_atomic_store(strag_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(strag_count + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // work-list length (k_knn_classify)
+    __hip_atomic_store(strag_count + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the wide launches' heavy-tile ticket (k_knn_tile; nothing else uses this word)
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (spread_cnt) {  // tiles found spread in this iteration's search join the front rows from the next launch on
       const uint32_t n = __hip_atomic_load(spread_cnt + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

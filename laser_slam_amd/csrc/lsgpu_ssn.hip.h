@@ -287,200 +287,6 @@ __global__ __launch_bounds__(256) void k_ssn_assign(int n, const SsnSeg* __restr
   seg_of[pos] = c;
 }
 
-// ---- the last levels inside one workgroup.  Once a segment holds <= kSsnLdsMax points the remaining
-// levels need no global sort: one block per segment keeps the coordinates in LDS and, per level, sorts
-// 64-bit keys (local segment | ordered cut coordinate | current position) with a bitonic network -- the
-// position in the lowest bits makes the order stable, i.e. identical to the global stable radix sort --
-// then derives the children exactly like k_ssn_split / k_ssn_assign.
-constexpr int kSsnLdsMax = 2048;
-constexpr int kSsnLdsSegs = 256;  // local segments at the last in-block level (>= kSsnLdsMax / (knn / 2))
-
-constexpr int kSsnLdsLevels = 8;  // log2(kSsnLdsSegs)
-struct SsnLds {                   // 68 KB: two workgroups per CU
-  float c[3][kSsnLdsMax];
-  uint32_t key[2][kSsnLdsMax];    // ping-pong: ordered cut coordinate of the element ...
-  uint16_t from[2][kSsnLdsMax];   // ... and the position it had when the level started
-  uint32_t cnt[4][256];           // radix pass: per wave and digit
-  uint32_t wtot[4];
-  uint16_t perm[kSsnLdsMax];
-  uint16_t sof[kSsnLdsMax];
-  SsnSeg seg[kSsnLdsSegs];
-};
-
-// One stable radix pass (8 bits) over the block's `cnt` elements in LDS, src -> dst.  digit_of(i) is evaluated for the
-// element at position i of `src`.  Ranks as in k_rs_scatter (lsgpu_sort.hip.h): wave by wave, 64 consecutive elements
-// at a time, equal digits found with 8 ballots, the lowest lane advances the wave's counter.
-template <class DigitOf>
-__device__ __forceinline__ void ssn_lds_radix_pass(SsnLds& L, int src, int cnt, DigitOf digit_of) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int dst = src ^ 1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) L.cnt[i][tid] = 0u;
-  __syncthreads();
-  constexpr int kIt = kSsnLdsMax / 256;   // 8 groups of 64 per wave
-  uint32_t rank[kIt], dig[kIt];
-  const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int i = w * (kSsnLdsMax / 4) + it * 64 + lane;
-    const bool valid = i < cnt;
-    const uint32_t d = valid ? digit_of(i) : 0u;
-    dig[it] = d;
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long m = __ballot(bit);
-      peers &= bit ? m : ~m;
-    }
-    const int leader = valid ? __ffsll((long long)peers) - 1 : lane;
-    uint32_t old = 0u;
-    if (valid && lane == leader) {
-      old = L.cnt[w][d];
-      L.cnt[w][d] = old + (uint32_t)__popcll(peers);
-    }
-    old = (uint32_t)__shfl((int)old, leader, 64);
-    rank[it] = old + (uint32_t)__popcll(peers & lt);
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-  }
-  __syncthreads();
-  {  // thread d: digit base (exclusive scan over the digits) + the waves before
-    uint32_t c[4], tot = 0u;
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) { c[ww] = L.cnt[ww][tid]; tot += c[ww]; }
-    uint32_t incl = tot;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = (uint32_t)__shfl_up((int)incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) L.wtot[w] = incl;
-    __syncthreads();
-    uint32_t run = incl - tot;
-    for (int ww = 0; ww < w; ++ww) run += L.wtot[ww];
-#pragma unroll
-    for (int ww = 0; ww < 4; ++ww) { L.cnt[ww][tid] = run; run += c[ww]; }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int it = 0; it < kIt; ++it) {
-    const int i = w * (kSsnLdsMax / 4) + it * 64 + lane;
-    if (i < cnt) {
-      const uint32_t pos = L.cnt[w][dig[it]] + rank[it];
-      L.key[dst][pos] = L.key[src][i];
-      L.from[dst][pos] = L.from[src][i];
-    }
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void k_ssn_finish(const float4* __restrict__ p, uint32_t* __restrict__ idx,
-                                                    const SsnSeg* __restrict__ segs, int knn, int rem,
-                                                    uint32_t* __restrict__ seg_of, SsnSeg* __restrict__ segs_out) {
-  __shared__ SsnLds L;
-  const int tid = threadIdx.x;
-  const SsnSeg root = segs[blockIdx.x];
-  const int cnt = (int)root.count;
-  for (int i = tid; i < cnt; i += 256) {
-    const uint32_t gi = idx[root.start + i];
-    const float4 v = p[gi];
-    L.c[0][i] = v.x; L.c[1][i] = v.y; L.c[2][i] = v.z;
-    L.perm[i] = (uint16_t)i;
-    L.sof[i] = 0;
-  }
-  if (tid == 0) { SsnSeg r = root; r.start = 0; L.seg[0] = r; }
-  __syncthreads();
-  for (int l = 0; l < rem; ++l) {
-    const int ns = 1 << l;
-    // Stable sort by (segment, ordered cut coordinate).  The positions are grouped by segment already, in segment
-    // order, so: four stable radix passes over the coordinate's bytes, then one over the segment number brings the
-    // groups back together with each group sorted -- the same order as one stable sort of the combined key (what the
-    // global levels do), with 15 barriers instead of the 66 of a bitonic network over 2048 keys.
-    for (int i = tid; i < cnt; i += 256) {
-      const uint32_t sgi = L.sof[i];
-      const SsnSeg& sg = L.seg[sgi];
-      uint32_t low = 0;
-      if (sg.count > (uint32_t)knn) low = float_order_key(L.c[ssn_cut_axis(sg)][L.perm[i]]);
-      L.key[0][i] = low;
-      L.from[0][i] = (uint16_t)i;
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int shift = 0; shift < 32; shift += 8) {
-      ssn_lds_radix_pass(L, cur, cnt, [&](int i) { return (L.key[cur][i] >> shift) & 255u; });
-      cur ^= 1;
-    }
-    if (ns > 1) {
-      ssn_lds_radix_pass(L, cur, cnt, [&](int i) { return (uint32_t)L.sof[L.from[cur][i]]; });
-      cur ^= 1;
-    }
-    // apply the permutation (read everything, then write)
-    uint16_t np[kSsnLdsMax / 256];
-#pragma unroll
-    for (int r = 0; r < kSsnLdsMax / 256; ++r) {
-      const int i = tid + r * 256;
-      np[r] = i < cnt ? L.perm[L.from[cur][i]] : (uint16_t)0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < kSsnLdsMax / 256; ++r) {
-      const int i = tid + r * 256;
-      if (i < cnt) L.perm[i] = np[r];
-    }
-    __syncthreads();
-    // children (computed from the parents, written once nobody reads the parents any more)
-    SsnSeg a, b;
-    if (tid < ns) {
-      const SsnSeg sg = L.seg[tid];
-      a = sg; b = sg;
-      if (sg.count > (uint32_t)knn) {
-        const int cut = ssn_cut_axis(sg);
-        const uint32_t right = sg.count / 2, left = sg.count - right;
-        const float cutval = L.c[cut][L.perm[sg.start + left]];
-        a.count = left; a.hi[cut] = cutval;
-        b.start = sg.start + left; b.count = right; b.lo[cut] = cutval;
-      } else {
-        b.start = sg.start + sg.count; b.count = 0;
-      }
-    }
-    for (int i = tid; i < cnt; i += 256) {
-      const uint32_t s = L.sof[i];
-      const SsnSeg& sg = L.seg[s];
-      uint32_t c = 2u * s;
-      if (sg.count > (uint32_t)knn) {
-        const uint32_t left = sg.count - sg.count / 2;
-        c += ((uint32_t)i - sg.start) >= left ? 1u : 0u;
-      }
-      L.sof[i] = (uint16_t)c;
-    }
-    __syncthreads();
-    if (tid < ns) { L.seg[2 * tid] = a; L.seg[2 * tid + 1] = b; }
-    __syncthreads();
-  }
-  const uint32_t base_seg = (uint32_t)blockIdx.x << rem;
-  uint32_t gi[kSsnLdsMax / 256];  // in place: read the block's whole index range before writing it
-#pragma unroll
-  for (int r = 0; r < kSsnLdsMax / 256; ++r) {
-    const int i = tid + r * 256;
-    gi[r] = i < cnt ? idx[root.start + L.perm[i]] : 0u;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kSsnLdsMax / 256; ++r) {
-    const int i = tid + r * 256;
-    if (i < cnt) {
-      idx[root.start + i] = gi[r];
-      seg_of[root.start + i] = base_seg + L.sof[i];
-    }
-  }
-  for (int s = tid; s < (1 << rem); s += 256) {
-    SsnSeg sg = L.seg[s];
-    sg.start += root.start;
-    segs_out[base_seg + s] = sg;
-  }
-}
-
 // one thread per box: normal (or "dropped"); box_pts = number of points that draw a random number
 __global__ __launch_bounds__(128) void k_ssn_boxes(const float4* __restrict__ p, const uint32_t* __restrict__ idx,
                                                    const SsnSeg* __restrict__ segs, int nseg,

@@ -1,6 +1,6 @@
 // lsgpu_ssn_tree.hip.h -- the lower levels of SamplingSurfaceNormalDataPointsFilter's box tree inside ONE workgroup
 // (laser_slam/configurations/icp_default.yaml:5-7; the filter PointMatcher::ICP::compute applies to the reference at
-// laser_slam/src/laser_track.cpp:496).  Round 5; replaces k_ssn_finish (lsgpu_ssn.hip.h) as the default.
+// laser_slam/src/laser_track.cpp:496).  Round 5; replaced k_ssn_finish (rounds 2-4, since removed).
 //
 // What the levels compute (lsgpu_ssn.hip.h): every segment that still holds more than knn points is put into the STABLE
 // order of its cut coordinate and halved; equal coordinates keep the order they had -- the rule the oracle and the host
@@ -27,8 +27,8 @@
 // tests/test_oracle.py::test_presorted_lists_equal_the_chain_of_stable_sorts (numpy model of the steps above).
 // The workgroup holds up to B = 8192 points (1024 threads, 152 KB of the CU's 160 KB LDS; 4096 / 2048 for the A/B
 // switch), i.e. two more levels than k_ssn_finish's 2048 leave the global segmented sorts (~100 us each at 1 M points).
-// Same boxes, same order, same normals as before: the bit-exact filter tests and the switch test (LSGPU_SSN_OLD_FINISH)
-// compare the two.
+// Same boxes, same order, same normals as the chain of stable sorts: the bit-exact filter tests compare it with the
+// oracle, and the switch test with the segmented-sort levels (LSGPU_SSN_SORT_LEVELS).
 #pragma once
 #include "lsgpu_ssn.hip.h"
 

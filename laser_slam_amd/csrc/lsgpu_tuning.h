@@ -26,22 +26,14 @@
 //   LSGPU_NO_COMMIT             keep launching the select kernels when the limit is steady
 //   LSGPU_NO_COMM_COMMIT        the same, only for handles with a communicator (split-scan mode)
 //   LSGPU_NO_SEED_CAP           first search uncapped (no quantile of the seed distances)
-//   LSGPU_NO_FRONT              spread tiles go through the separate row pass instead of the front of the tile launch
 //   LSGPU_FRONT_GUESS     2048  tiles the front of the grid is sized for before the host has seen the list
 //   LSGPU_NO_LAZY               wide launches (first iterations) use the plain tile kernel instead of the instantiation that re-tests chunks before fetching them
 //   LSGPU_NO_SPLIT              settled launches of the voxel search evaluate every candidate in all 64 lanes (no lane split, lsgpu_knn.hip.h)
 //   LSGPU_NO_SIDE_STREAM        lsgpu_icp_compute: reading filter + query order AFTER the grid build, on the same stream (not beside it)
 //   LSGPU_NO_LOOKAHEAD          no iteration enqueued behind the copy of the loop state: the device idles while the host looks at it
-//   LSGPU_NO_ROUTE_ALL          (with NO_FRONT) settled spread waves search per lane inside the tile kernel
-//   LSGPU_NO_ROWQ               (with NO_FRONT) handed-over queries go to the wave-per-query kernel
-//   LSGPU_ROWQ_BLOCKS     2048  (with NO_FRONT) grid of the row pass
 //   LSGPU_SORT_ITEMS         0  keys per thread of the radix passes (0: by size; 4, 8, 16)
-//   LSGPU_SSN_FULL_SORT         the reference filter's levels as whole-cloud sorts by (segment, coordinate) (rounds 1-3) instead of segmented sorts
-//   LSGPU_SSN_GLOBAL            every level of the reference filter as a global sort (no in-LDS finish; implies LSGPU_SSN_SORT_LEVELS)
 //   LSGPU_SSN_SORT_LEVELS       the upper levels of the reference filter with a segmented sort per level (round 4, lsgpu_segsort.hip.h) instead of
 //                               the sort-free levels of lsgpu_ssn_select.hip.h (exact median by selection + one stable partition)
-//   LSGPU_SSN_OLD_FINISH        the last levels with k_ssn_finish (rounds 2-4: 2048 points per workgroup, a radix sort per level) instead of
-//                               k_ssn_tree (presorted axes, a stable partition per level); continues a sorted order: implies LSGPU_SSN_SORT_LEVELS
 //   LSGPU_SSN_ROOT        8192  points per workgroup of k_ssn_tree (2048, 4096, 8192)
 //   LSGPU_NE_BLOCKS        256  blocks of k_normal_eq_loop (64 .. 2048)
 //   LSGPU_SPLIT_UPDATE          the per-iteration update as its own launch (profiling)
@@ -57,10 +49,6 @@
 //   LSGPU_CONE_ROWS        128  rows (bins of the sine of the elevation) of the direction index
 //   LSGPU_CONE_COLS       8192  columns (bins of the pseudo-azimuth) of the direction index
 //   LSGPU_KNN_DBG            0  ablation flags of the -DLSGPU_KNN_STATS build (ignored by the product build)
-// Experiment switches, compiled in only with -DLSGPU_EXPERIMENTS (measured-slower variants kept as the record of what was
-// tried: DESIGN.md "Rejected after measurement"); the product build reports them as unknown:
-//   LSGPU_KNN_ROWS (0/1/2), LSGPU_KNN_LANE, LSGPU_SPARSE_LANES, LSGPU_TILE_WAVES (1/4), LSGPU_XCD_SWIZZLE,
-//   LSGPU_ROCPRIM_SORT (rocPRIM's radix sort instead of lsgpu_sort.hip.h: the library sort as a cross-check)
 
 #pragma once
 #include <cstdio>
@@ -86,7 +74,6 @@ struct Tuning {
   bool two_pass_select = true;   // ... also where the select kernels run: they stop after their second pass (LSGPU_THREE_PASS_SELECT)
   bool short_last_group = true;   // the host sizes a group of launches from the checker's trend (LSGPU_FULL_GROUPS: always six)
   bool fused_select = true;   // the normal-equation kernel finds the trim limit itself (LSGPU_NO_FUSED_SELECT: the select kernels / the window table)
-  bool front = true;
   bool lazy_need = true;
   bool lane_split = true;    // LSGPU_NO_SPLIT: k_knn_tile<1, false> instead of <1, false, true> for the settled voxel searches
   bool lookahead = true;     // LSGPU_NO_LOOKAHEAD: the host waits for the whole stream when it looks at the loop state
@@ -94,12 +81,7 @@ struct Tuning {
                              // (the one launch decision that depends on wall-clock timings: off => the same kernels every run)
   bool side_stream = true;   // LSGPU_NO_SIDE_STREAM: lsgpu_icp_compute runs the reading's filter + query order after the grid build instead of beside it
   int front_guess = 2048;
-  bool route_all = true, rowq = true;
-  int rowq_blocks = 2048;
   int sort_items = 0;
-  bool ssn_global = false;
-  bool ssn_full_sort = false;
-  bool ssn_old_finish = false;
   bool ssn_sort_levels = false;
   int ssn_root = 0;   // points per root of k_ssn_tree (2048 / 4096 / 8192); 0: by the cloud's size, so that there are about as many roots as compute units
   int ne_blocks = 256;
@@ -112,14 +94,6 @@ struct Tuning {
   float cone_max_occupancy = 7.0f;
   float cone_heavy_steps = 1024.f;   // the index's price check: a lane whose windows would hold more steps of four than this is heavy
   float cone_heavy_share = 0.07f;   // ... and an align with more than this share of heavy lanes among the searching ones keeps the voxel grid
-#ifdef LSGPU_EXPERIMENTS
-  int knn_rows = 0;
-  bool knn_lane = false;
-  int sparse_lanes = 0;
-  int tile_waves = 1;
-  int xcd_swizzle = 0;
-  bool rocprim_sort = false;
-#endif
 };
 
 namespace tuning_detail {
@@ -157,24 +131,17 @@ inline Tuning read() {
   t.sel_amb_cap = (int)number("LSGPU_SEL_AMB_CAP", 256, 0, 256);
   t.comm_commit = !flag("LSGPU_NO_COMM_COMMIT");
   t.seed_cap = !flag("LSGPU_NO_SEED_CAP");
-  t.front = !flag("LSGPU_NO_FRONT");
   t.lazy_need = !flag("LSGPU_NO_LAZY");
   t.lane_split = !flag("LSGPU_NO_SPLIT");
   t.side_stream = !flag("LSGPU_NO_SIDE_STREAM");
   t.lookahead = !flag("LSGPU_NO_LOOKAHEAD");
   t.index_rest = !flag("LSGPU_NO_INDEX_REST");
   t.front_guess = (int)number("LSGPU_FRONT_GUESS", 2048, 0, 8192);
-  t.route_all = !flag("LSGPU_NO_ROUTE_ALL");
-  t.rowq = !flag("LSGPU_NO_ROWQ");
-  t.rowq_blocks = (int)number("LSGPU_ROWQ_BLOCKS", 2048, 1, 65535);
   t.sort_items = (int)number("LSGPU_SORT_ITEMS", 0, 0, 16);
   if (t.sort_items != 0 && t.sort_items != 4 && t.sort_items != 8 && t.sort_items != 16) {
     fprintf(stderr, "liblsgpu_icp: LSGPU_SORT_ITEMS must be 4, 8 or 16; choosing by size\n");
     t.sort_items = 0;
   }
-  t.ssn_global = flag("LSGPU_SSN_GLOBAL");
-  t.ssn_full_sort = flag("LSGPU_SSN_FULL_SORT");
-  t.ssn_old_finish = flag("LSGPU_SSN_OLD_FINISH");
   t.ssn_sort_levels = flag("LSGPU_SSN_SORT_LEVELS");
   t.ssn_root = (int)number("LSGPU_SSN_ROOT", 0, 0, 8192);
   if (t.ssn_root != 0 && t.ssn_root != 2048 && t.ssn_root != 4096 && t.ssn_root != 8192) {
@@ -194,26 +161,12 @@ inline Tuning read() {
   t.cone_cols = (int)number("LSGPU_CONE_COLS", 8192, 64, 65536) & ~3;
   static const char* known[] = {"LSGPU_QUERY_ORDER", "LSGPU_Q_ELEV", "LSGPU_Q_SECT", "LSGPU_GAP", "LSGPU_BUDGET", "LSGPU_BUDGET_WIDE", "LSGPU_WIDE_ITERS",
                                 "LSGPU_ROUTE_R", "LSGPU_ROUTE_CHUNKS", "LSGPU_ROUTE_HEAVY_MAX", "LSGPU_ROUTE_DENSE", "LSGPU_SPLIT_UPDATE", "LSGPU_NO_PREDICT", "LSGPU_NO_COMMIT",
-                                "LSGPU_NO_COMM_COMMIT", "LSGPU_NO_SEED_CAP", "LSGPU_NO_FRONT", "LSGPU_NO_LAZY", "LSGPU_NO_SPLIT", "LSGPU_NO_SIDE_STREAM", "LSGPU_NO_LOOKAHEAD", "LSGPU_NO_INDEX_REST", "LSGPU_CELLS_SPLIT", "LSGPU_NO_FUSED_SELECT", "LSGPU_FULL_GROUPS", "LSGPU_THREE_PASS_SELECT", "LSGPU_SEL_AMB_CAP", "LSGPU_FRONT_GUESS", "LSGPU_NO_ROUTE_ALL",
-                                "LSGPU_NO_ROWQ", "LSGPU_ROWQ_BLOCKS", "LSGPU_SORT_ITEMS", "LSGPU_SSN_GLOBAL", "LSGPU_SSN_FULL_SORT", "LSGPU_SSN_OLD_FINISH", "LSGPU_SSN_ROOT", "LSGPU_SSN_SORT_LEVELS",
+                                "LSGPU_NO_COMM_COMMIT", "LSGPU_NO_SEED_CAP", "LSGPU_NO_LAZY", "LSGPU_NO_SPLIT", "LSGPU_NO_SIDE_STREAM", "LSGPU_NO_LOOKAHEAD", "LSGPU_NO_INDEX_REST", "LSGPU_CELLS_SPLIT", "LSGPU_NO_FUSED_SELECT", "LSGPU_FULL_GROUPS", "LSGPU_THREE_PASS_SELECT", "LSGPU_SEL_AMB_CAP", "LSGPU_FRONT_GUESS",
+                                "LSGPU_SORT_ITEMS", "LSGPU_SSN_ROOT", "LSGPU_SSN_SORT_LEVELS",
                                 "LSGPU_NE_BLOCKS", "LSGPU_COMM_TIMEOUT_MS", "LSGPU_KNN_DBG", "LSGPU_NO_CONE", "LSGPU_NO_CONE_PROBE", "LSGPU_CONE_ROWS", "LSGPU_CONE_COLS", "LSGPU_CONE_FROM", "LSGPU_CONE_MAX_OCC", "LSGPU_CONE_HEAVY_STEPS", "LSGPU_CONE_HEAVY_SHARE",
                                 // read by the Python / C++ hosts and the test drivers, not by this library:
                                 "LSGPU_SO", "LSGPU_STATS_SO", "LSGPU_BATCH_POOLS", "LSGPU_BATCH_UNIQ", "LSGPU_GS_DEBUG", "LSGPU_GOLDEN_DIR", "LSGPU_SEQ_PERTURB", "LSGPU_SEQ_POSES", "LSGPU_TEST_INPUT_FILTERS",
-#ifdef LSGPU_EXPERIMENTS
-                                "LSGPU_KNN_ROWS", "LSGPU_KNN_LANE", "LSGPU_SPARSE_LANES", "LSGPU_TILE_WAVES", "LSGPU_XCD_SWIZZLE", "LSGPU_ROCPRIM_SORT",
-#endif
                                 nullptr};
-#ifdef LSGPU_EXPERIMENTS
-  t.knn_rows = (int)number("LSGPU_KNN_ROWS", 0, 0, 2);
-  t.knn_lane = flag("LSGPU_KNN_LANE");
-  t.sparse_lanes = (int)number("LSGPU_SPARSE_LANES", 0, 0, 64);
-  t.tile_waves = (int)number("LSGPU_TILE_WAVES", 1, 1, 4) == 4 ? 4 : 1;
-  t.xcd_swizzle = (int)number("LSGPU_XCD_SWIZZLE", 0, 0, 1 << 16);
-  t.rocprim_sort = flag("LSGPU_ROCPRIM_SORT");
-  // the front rows only exist in the one-wave tile kernel; the row-wise experiment does not fill the window table
-  if (t.knn_lane || t.knn_rows != 0 || t.tile_waves == 4 || t.sparse_lanes != 0) t.front = false;
-  if (t.knn_rows != 0) t.commit_select = false;
-#endif
   for (char** e = environ; e && *e; ++e) {
     if (strncmp(*e, "LSGPU_", 6) != 0) continue;
     const char* eq = strchr(*e, '=');

@@ -332,10 +332,11 @@ def test_radius_cap_does_not_change_results(icp_mod, pair64k):
 @pytest.mark.timeout(600)
 def test_experiment_switches_do_not_change_results():
     """DESIGN.md's claim about the LSGPU_* switches -- they move work between exact paths and never change a result -- on
-    a 14-iteration alignment of a 262 k-point pair: front rows / separate row pass / per-lane search for spread tiles,
-    committed / predicted / plain select, own radix sort / library sort, the row-wise experiment, 4-wave tile blocks, no
-    first-iteration cap.  Every variant runs in its own process (the switches are read once) and must return
-    bit-identical transform, per-iteration limit / inlier count / normal matrix / T, distances and filtered reference.
+    a 14-iteration alignment of a 262 k-point pair: voxel grid / direction index for the settled launches, lane split,
+    routing of heavy and dense tiles, committed / predicted / plain select, sort widths, sort-free / segmented-sort levels
+    and root sizes of the reference filter, no first-iteration cap, the fenced build.  Every variant runs in its own
+    process (the switches are read once) and must return bit-identical transform, per-iteration limit / inlier count /
+    normal matrix / T, distances and filtered reference.
     LSGPU_QUERY_ORDER changes the order in which the 29 double sums of the normal equations are added, hence their last
     bits: for it the search results, the first iteration's limit and inlier count are bit-identical, the transform
     agrees to 1e-6 and the iteration count is the same.  So do LSGPU_NO_FUSED_SELECT and LSGPU_SEL_AMB_CAP: the sum is
@@ -348,32 +349,24 @@ def test_experiment_switches_do_not_change_results():
     # grid (k_knn_tile), whose own switches only act there
     tile = {"LSGPU_NO_CONE": "1"}
     variants = [{}, tile, dict(tile, LSGPU_NO_SPLIT="1"),   # (the settled voxel searches share a tile's candidates out over its idle lanes: k_knn_tile<1, false, true>; without: every lane looks at every candidate)
-                dict(tile, LSGPU_NO_FRONT="1"), dict(tile, LSGPU_NO_FRONT="1", LSGPU_NO_ROWQ="1"),
-                dict(tile, LSGPU_NO_FRONT="1", LSGPU_NO_ROUTE_ALL="1"), {"LSGPU_NO_COMMIT": "1"}, dict(tile, LSGPU_NO_COMMIT="1"),
+                {"LSGPU_NO_COMMIT": "1"}, dict(tile, LSGPU_NO_COMMIT="1"),
                 {"LSGPU_NO_PREDICT": "1"}, dict(tile, LSGPU_NO_PREDICT="1"),
                 {"LSGPU_CONE_ROWS": "32", "LSGPU_CONE_COLS": "1024"}, {"LSGPU_CONE_ROWS": "512", "LSGPU_CONE_COLS": "32768"},
                 {"LSGPU_NO_CONE_PROBE": "1"}, {"LSGPU_CONE_FROM": "1"}, {"LSGPU_CONE_HEAVY_SHARE": "2"}, dict(tile, LSGPU_ROUTE_DENSE="16"), dict(tile, LSGPU_ROUTE_DENSE="1073741824"),
                 {"LSGPU_CONE_HEAVY_STEPS": "8", "LSGPU_CONE_HEAVY_SHARE": "0.5"},   # (too dear at first, priced again before every look)
                 {"LSGPU_ROUTE_HEAVY_MAX": "-1"}, {"LSGPU_ROUTE_HEAVY_MAX": "0"}, {"LSGPU_ROUTE_HEAVY_MAX": "3", "LSGPU_ROUTE_CHUNKS": "64"},   # heavy tiles of the wide launches: all / none / the first three to the wave-per-query pass
                 {"LSGPU_SORT_ITEMS": "4"}, {"LSGPU_NO_SEED_CAP": "1"}, {"LSGPU_NO_LAZY": "1"}, {"LSGPU_NO_SIDE_STREAM": "1"}, {"LSGPU_NO_LOOKAHEAD": "1"},
-                dict(tile, LSGPU_FRONT_GUESS="8"), {"LSGPU_SSN_GLOBAL": "1"}, {"LSGPU_SSN_FULL_SORT": "1"}, {"LSGPU_SSN_FULL_SORT": "1", "LSGPU_SSN_GLOBAL": "1"},
-                {"LSGPU_SSN_OLD_FINISH": "1"}, {"LSGPU_SSN_ROOT": "2048"}, {"LSGPU_SSN_ROOT": "4096"},   # k_ssn_finish / smaller roots of k_ssn_tree
-                {"LSGPU_SSN_SORT_LEVELS": "1"}, {"LSGPU_SSN_SORT_LEVELS": "1", "LSGPU_SSN_OLD_FINISH": "1"},   # a segmented sort per upper level (round 4) / all of round 4's filter
+                dict(tile, LSGPU_FRONT_GUESS="8"),
+                {"LSGPU_SSN_ROOT": "2048"}, {"LSGPU_SSN_ROOT": "4096"},   # smaller roots of k_ssn_tree
+                {"LSGPU_SSN_SORT_LEVELS": "1"},   # a segmented sort per upper level (round 4; the fallback of the sort-free levels)
                 {"LSGPU_THREE_PASS_SELECT": "1"},   # (the select's third pass instead of the normal equations' set-aside ranking: same limit, same sums)
                 {"LSGPU_QUERY_ORDER": "0"},
                 # the fused select (round 6): without it (select kernels / window table), and with room for only 3 distances of
                 # the limit's slice -- fuller slices void the fused iteration, which is repeated with the select in full
                 {"LSGPU_NO_FUSED_SELECT": "1"}, {"LSGPU_SEL_AMB_CAP": "3"}, {"LSGPU_SEL_AMB_CAP": "0"}]
-    # the measured-slower variants only exist in the -DLSGPU_EXPERIMENTS build (devtools/build.sh); when that build is
-    # around it has to give the same bits as the product, switch by switch
     fenced_so = os.path.join(ROOT, "tests", "liblsgpu_icp_fenced.so")   # built by `make -C laser_slam_amd/csrc` (build())
     assert os.path.exists(fenced_so), "run __graft_entry__.build() first"
     variants.append({"LSGPU_SO": fenced_so})        # release / acquire fences instead of the fence-free hand-off: same bits
-    exp_so = os.path.join(ROOT, "devtools", "liblsgpu_exp.so")
-    if os.path.exists(exp_so) and os.path.getmtime(exp_so) >= os.path.getmtime(os.path.join(ROOT, "laser_slam_amd", "liblsgpu_icp.so")) - 600:   # (a stale build says nothing)
-        variants += [dict(v, LSGPU_SO=exp_so) for v in ({}, dict(tile, LSGPU_KNN_ROWS="1"), dict(tile, LSGPU_TILE_WAVES="4"),
-                                                        dict(tile, LSGPU_NO_FRONT="1", LSGPU_SPARSE_LANES="16"),
-                                                        {"LSGPU_ROCPRIM_SORT": "1"})]          # (the library sort as a cross-check of lsgpu_sort.hip.h)
     results = []
     for env_add in variants:
         env = dict(os.environ)
