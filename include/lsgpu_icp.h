@@ -25,7 +25,8 @@
  * device tensor.
  *
  * Modules: the chain of icp_default.yaml, PointToPointErrorMinimizer in place of PointToPlaneErrorMinimizer
- * (lsgpu_icp_config.error_minimizer), and KDTreeMatcher with knn 1..LSGPU_MATCHER_KNN_MAX (lsgpu_icp_config.matcher_knn).
+ * (lsgpu_icp_config.error_minimizer), KDTreeMatcher with knn 1..LSGPU_MATCHER_KNN_MAX (lsgpu_icp_config.matcher_knn) and
+ * maxDist (matcher_max_dist), and any subset of Trimmed- / Max- / Min- / MedianDistOutlierFilter (outlier_*).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -36,6 +37,8 @@
 extern "C" {
 #endif
 
+/* 4 still: the four chain fields of lsgpu_icp_config (matcher_max_dist ...) took reserved ints that had to be 0, the struct
+ * kept its size and every offset, and 0 means what it meant -- a caller built against the earlier header runs unchanged. */
 #define LSGPU_ABI_VERSION 4
 
 /* Return codes.  NO_CONVERGENCE is PointMatcher::ConvergenceError: laser_track.cpp:499-502 catches it
@@ -62,8 +65,30 @@ typedef struct lsgpu_icp_config {
   int   reserved[1];      /* reserved[0] = 1 disables the trimmed-radius cap (debug)       */
   int   error_minimizer;  /* LSGPU_MINIMIZER_* (0, the default: point-to-plane); any other value: LSGPU_BAD_CONFIG */
   int   matcher_knn;      /* KDTreeMatcher knn: 0 or 1 one neighbour; 2..LSGPU_MATCHER_KNN_MAX k nearest matches; other: BAD_CONFIG */
-  int   reserved_[5];
+  /* 0 (what lsgpu_icp_config_yaml / _default and a zero-filled struct hold) = absent; see "maxDist and outlier-filter chains" */
+  float matcher_max_dist;       /* KDTreeMatcher maxDist [m]: a match is valid iff d2 <= maxDist^2; +inf = absent           */
+  float outlier_max_dist;       /* MaxDistOutlierFilter maxDist [m]: keep d2 <= maxDist^2; +inf = absent                    */
+  float outlier_min_dist;       /* MinDistOutlierFilter minDist [m]: keep d2 >= minDist^2                                   */
+  float outlier_median_factor;  /* MedianDistOutlierFilter factor: keep d2 <= factor * median(d2)                           */
+  int   reserved_[1];
 } lsgpu_icp_config;
+
+/* maxDist and outlier-filter chains.  All comparisons on squared distances in float; maxDist * maxDist etc. are one
+ * float multiply.
+ *   matcher_max_dist: a match further than maxDist is INVALID: index -1, d2 +inf, weight 0 under every outlier filter and with
+ *     none.  With knn = k each of the k entries is judged on its own; the valid ones come first, in the usual order.  The
+ *     search never looks further than maxDist, from its first launch on.  lsgpu_knn / lsgpu_knn_k on such a handle return
+ *     -1 / +inf for invalid matches.
+ *   Quantiles (the trim limit, the median) are taken over the m valid matches only: sorted(finite d2)[min(m - 1,
+ *     (int64)((float)m * q))] -- as lsgpu_trim_limit, which skips +inf inputs (none finite: LSGPU_NO_CONVERGENCE).
+ *   Outlier filters: trim_ratio (TrimmedDist, 1 = none), outlier_max_dist, outlier_min_dist, outlier_median_factor; every
+ *     filter sees the same matches, the 0/1 weights are multiplied, so a pair is kept iff it passes every filter and the order
+ *     of the modules does not matter.  lsgpu_iter_trace.limit / lsgpu_icp_stats.final_limit are the iteration's effective
+ *     upper limit: the smallest of {trim limit, outlier_max_dist^2, factor * median} present; n_used counts kept pairs.
+ *     Nothing kept: LSGPU_NO_CONVERGENCE, T_out = T_init.
+ *   Negative or NaN values, and +inf for outlier_min_dist / outlier_median_factor, are LSGPU_BAD_CONFIG from lsgpu_icp_create
+ *   (checked before the device is touched).  A handle with any of the four fields searches with the k-best kernels for every
+ *   knn and runs the full select in every iteration (csrc/lsgpu_policy.h, plan_chain); lsgpu_icp_comm_init refuses it. */
 
 /* KDTreeMatcher knn (lsgpu_icp_config.matcher_knn), epsilon 0.  With knn = k >= 2 every reading point is paired with its k
  * nearest reference points (Matches: k x N dists / ids): TrimmedDistOutlierFilter ranks all k N distances (limit =
@@ -225,7 +250,9 @@ int lsgpu_knn(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[1
  * matcher_knn), ids indexing the reference as given to set_reference.  LSGPU_BAD_ARG if the reference has fewer than k
  * points or k nq does not fit the loop's 32-bit counts. */
 int lsgpu_knn_k(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16], int k, int32_t* ids, float* d2);
-/* TrimmedDistOutlierFilter (yaml:14-16): limit = sorted(d2)[floor(n*ratio)]. */
+/* TrimmedDistOutlierFilter (yaml:14-16): limit = sorted(d2)[floor(n*ratio)], n counting the finite inputs only (+inf = an
+ * invalid match, skipped; the count and the rank are taken on the device); LSGPU_NO_CONVERGENCE if none is finite.  A ratio
+ * <= 0 asks for rank 0, the smallest input, whatever the count (rank from the host, as before). */
 int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, float* limit);
 /* PointToPlaneErrorMinimizer accumulation (yaml:18-19): out = 21 upper-tri of sum J J^T (row major
  * order a<=c), 6 of -sum J r, sum w, sum w r^2  -> double[29]. */

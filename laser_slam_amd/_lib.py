@@ -58,7 +58,11 @@ class IcpConfig(C.Structure):
         ("reserved", C.c_int * 1),          # reserved[0] = 1 disables the trimmed-radius cap (debug)
         ("error_minimizer", C.c_int),       # MINIMIZER_*
         ("matcher_knn", C.c_int),           # KDTreeMatcher knn: 0 / 1 one neighbour, 2..MATCHER_KNN_MAX k nearest matches
-        ("reserved_", C.c_int * 5),
+        ("matcher_max_dist", C.c_float),        # KDTreeMatcher maxDist [m]; 0 / inf: absent
+        ("outlier_max_dist", C.c_float),        # MaxDistOutlierFilter maxDist [m]; 0 / inf: absent
+        ("outlier_min_dist", C.c_float),        # MinDistOutlierFilter minDist [m]; 0: absent
+        ("outlier_median_factor", C.c_float),   # MedianDistOutlierFilter factor; 0: absent
+        ("reserved_", C.c_int * 1),
     ]
 
 

@@ -253,7 +253,8 @@ class ICP {
   }
 
   // Accepts the module chain of laser_slam/configurations/icp_default.yaml, with PointToPlaneErrorMinimizer or
-  // PointToPointErrorMinimizer and KDTreeMatcher knn 1..LSGPU_MATCHER_KNN_MAX (epsilon 0); any other module is a configuration error (PointMatcher's registrar throws on unknown
+  // PointToPointErrorMinimizer, KDTreeMatcher knn 1..LSGPU_MATCHER_KNN_MAX (epsilon 0) with maxDist, and any subset of
+  // Trimmed- / Max- / Min- / MedianDistOutlierFilter (each at most once, any order); any other module is a configuration error (PointMatcher's registrar throws on unknown
   // names as well).
   void loadFromYaml(std::istream& in) {
     lsgpu_icp_config c;
@@ -266,7 +267,7 @@ class ICP {
     // not expressible for the reference filter: the normals come from it); the modules the device loop cannot run
     // without are required.
     bool has_reading = false, has_reference = false, has_matcher = false, has_outlier = false, has_minimizer = false,
-         has_counter = false, has_differential = false;
+         has_counter = false, has_differential = false, has_max = false, has_min = false, has_median = false;
     prob = -1.0f;   // no reading filter module: lsgpu_chain_config::reading_prob < 0 (every point, no draws)
     c.trim_ratio = 1.0f;
     for (const auto& m : mods) {
@@ -275,6 +276,29 @@ class ICP {
       auto num = [&](const char* key, double def) {
         auto it = m.params.find(key);
         return it == m.params.end() ? def : std::stod(it->second);
+      };
+      // a threshold of the matcher / an outlier filter: a number ("inf" included), never NaN; the module's name in the text
+      auto fnum = [&](const std::string& mod, const char* key, double def) {
+        auto it = m.params.find(key);
+        if (it == m.params.end()) return def;
+        std::string v = it->second;
+        // YAML writes infinity as .inf / .Inf / .INF (std::stod wants it without the dot); "-.inf" is then -inf, which
+        // every caller refuses as out of range.  Any other leading dot is a plain float (.5 is 0.5)
+        const size_t sign = (!v.empty() && (v[0] == '+' || v[0] == '-')) ? 1 : 0;
+        const std::string rest = v.substr(sign);
+        if (rest == ".inf" || rest == ".Inf" || rest == ".INF") v = v.substr(0, sign) + "inf";
+        double x = 0.0;
+        try { size_t used = 0; x = std::stod(v, &used); if (used != v.size()) throw std::invalid_argument(v); }
+        catch (const std::exception&) { throw ConfigError(mod + ": " + key + " is not a number"); }
+        if (std::isnan(x)) throw ConfigError(mod + ": " + key + " is not a number");
+        return x;
+      };
+      auto only = [&](const std::string& mod, std::initializer_list<const char*> known) {
+        for (const auto& kv : m.params) {
+          bool ok = false;
+          for (const char* k : known) ok = ok || kv.first == k;
+          if (!ok) throw ConfigError(mod + ": unknown parameter " + kv.first);
+        }
       };
       if (sec == "readingDataPointsFilters" && name == "RandomSamplingDataPointsFilter") {
         if (has_reading) throw ConfigError("readingDataPointsFilters: one RandomSamplingDataPointsFilter at most");
@@ -286,14 +310,37 @@ class ICP {
         if ((int)num("samplingMethod", 0) != 0) throw ConfigError("samplingMethod != 0 is not implemented");
       } else if (sec == "matcher" && name == "KDTreeMatcher") {
         has_matcher = true;
-        // knn 1..LSGPU_MATCHER_KNN_MAX, exact search only; its other parameters (maxDist, searchType, ...) are not read
+        // knn 1..LSGPU_MATCHER_KNN_MAX, exact search only, maxDist; its other parameters (searchType, ...) are not read
+        const double md = fnum(name, "maxDist", INFINITY);
+        if (!(md > 0.0)) throw ConfigError("KDTreeMatcher: maxDist must be > 0");
+        c.matcher_max_dist = std::isinf(md) ? 0.f : (float)md;
         const double k = num("knn", 1);
         if (!(k >= 1 && k <= LSGPU_MATCHER_KNN_MAX) || k != (double)(int)k || num("epsilon", 0) != 0.0)
           throw ConfigError("KDTreeMatcher: knn 1.." + std::to_string(LSGPU_MATCHER_KNN_MAX) + " with epsilon 0 is implemented");
         c.matcher_knn = (int)k;
       } else if (sec == "outlierFilters" && name == "TrimmedDistOutlierFilter") {
         if (has_outlier) throw ConfigError("outlierFilters: one TrimmedDistOutlierFilter at most");
-        has_outlier = true; c.trim_ratio = (float)num("ratio", 0.85);
+        only(name, {"ratio"});
+        has_outlier = true; c.trim_ratio = (float)fnum(name, "ratio", 0.85);
+        if (!(c.trim_ratio > 0.f && c.trim_ratio <= 1.f)) throw ConfigError("TrimmedDistOutlierFilter: ratio must be in (0, 1]");
+      } else if (sec == "outlierFilters" && name == "MaxDistOutlierFilter") {
+        if (has_max) throw ConfigError("outlierFilters: one MaxDistOutlierFilter at most");
+        only(name, {"maxDist"});
+        const double md = fnum(name, "maxDist", 1.0);
+        if (!(md > 0.0)) throw ConfigError("MaxDistOutlierFilter: maxDist must be > 0");
+        has_max = true; c.outlier_max_dist = std::isinf(md) ? 0.f : (float)md;
+      } else if (sec == "outlierFilters" && name == "MinDistOutlierFilter") {
+        if (has_min) throw ConfigError("outlierFilters: one MinDistOutlierFilter at most");
+        only(name, {"minDist"});
+        const double md = fnum(name, "minDist", 1.0);
+        if (!(md >= 0.0) || std::isinf(md)) throw ConfigError("MinDistOutlierFilter: minDist must be >= 0 and finite");
+        has_min = true; c.outlier_min_dist = (float)md;
+      } else if (sec == "outlierFilters" && name == "MedianDistOutlierFilter") {
+        if (has_median) throw ConfigError("outlierFilters: one MedianDistOutlierFilter at most");
+        only(name, {"factor"});
+        const double f = fnum(name, "factor", 3.0);
+        if (!(f > 0.0) || std::isinf(f)) throw ConfigError("MedianDistOutlierFilter: factor must be > 0 and finite");
+        has_median = true; c.outlier_median_factor = (float)f;
       } else if (sec == "errorMinimizer" && (name == "PointToPlaneErrorMinimizer" || name == "PointToPointErrorMinimizer")) {
         if (has_minimizer) throw ConfigError("errorMinimizer: one module at most");
         has_minimizer = true;

@@ -294,6 +294,8 @@ struct lsgpu_icp {
   DevBuf<float4> kmatch; DevBuf<float> kd2;
   DevBuf<uint32_t> hist;      // 3 * kHistBins
   DevBuf<SelState> sel;       // [0] input rank, [1] after pass 2, [2] after pass 3
+  DevBuf<uint32_t> hist_med;  // MedianDistOutlierFilter: the second run of the select's refining passes (3 * kHistBins, [0] unused) ...
+  DevBuf<SelState> sel_med;   // ... and its three states
   DevBuf<double> ne_partials; // kNeBlocks * 32
   DevBuf<double> ne_gpartials;  // (kNeBlocksMax / kNeGroup) * 32: first-level sums of k_normal_eq_loop
   DevBuf<uint32_t> ne_tickets;  // 1 + kNeBlocksMax / kNeGroup
@@ -422,6 +424,11 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
       (cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_PLANE && cfg->error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT) ||
       cfg->matcher_knn < 0 || cfg->matcher_knn > LSGPU_MATCHER_KNN_MAX)
     return LSGPU_BAD_CONFIG;
+  // the chain's thresholds: 0 = absent; negative / NaN never; +inf only where it means "no bound" (the two maxDist)
+  if (!(cfg->matcher_max_dist >= 0.f) || !(cfg->outlier_max_dist >= 0.f) ||
+      !(cfg->outlier_min_dist >= 0.f) || std::isinf(cfg->outlier_min_dist) ||
+      !(cfg->outlier_median_factor >= 0.f) || std::isinf(cfg->outlier_median_factor))
+    return LSGPU_BAD_CONFIG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     (void)hipGetLastError();
@@ -548,6 +555,7 @@ static int ensure_loop_buffers(lsgpu_icp* h, int64_t nq) {
   HIPC(h->strag.reserve(nq));
   HIPC(h->hist.reserve(3 * kHistBins));
   HIPC(h->sel.reserve(4));
+  HIPC(h->hist_med.reserve(3 * kHistBins)); HIPC(h->sel_med.reserve(4));
   HIPC(h->ne_partials.reserve((size_t)kNeBlocksMax * 32));
   HIPC(h->ne_gpartials.reserve((size_t)(kNeBlocksMax / kNeGroup + 1) * 32));
   HIPC(h->ne_tickets.reserve((size_t)(kNeBlocksMax / kNeGroup + 2)));
@@ -599,7 +607,17 @@ static int prepare_queries(lsgpu_icp* h, const float* q_xyz1, int64_t nq, const 
 }
 
 static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zero_hist, const IcpState* st,
-                      bool use_comm, bool predicted, int passes = 3);
+                      bool use_comm, bool predicted, int passes = 3, float rank_ratio = 0.f, bool with_median = false);
+
+// KDTreeMatcher maxDist of the handle, squared (one float multiply); +inf: none
+static float matcher_max_d2(const lsgpu_icp* h) {
+  const float m = h->cfg.matcher_max_dist;
+  return (m > 0.f && !std::isinf(m)) ? m * m : INFINITY;
+}
+// does the handle take the chain plan (lsgpu_policy.h)?
+static bool chain_on(const lsgpu_icp* h) {
+  return policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor);
+}
 
 static float price_share(const lsgpu_icp* h) {   // heavy lanes / searching lanes of the priced launch (its counters are on the host)
   uint64_t heavy = 0, searching = 0;
@@ -771,12 +789,17 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
 // ---- k nearest matches (lsgpu_knn_k.hip.h): the k-best search of the queries in h->rdq into h->kmatch / h->kd2.
 //   st    : loop state (T from it, `done` exits) or nullptr (T from the argument: kernel-level API)
 //   seed  : the queries have no warm start yet (first iteration of an align, kernel-level API)
+template <int K, bool MAXD>
+static void launch_knn_k_(lsgpu_icp* h, const KnnKArgs& a, bool seed) {
+  const int nq = a.nq;
+  if (seed) hipLaunchKernelGGL((k_knnk_seed<K, MAXD>), dim3(nblk(nq)), dim3(256), 0, h->stream, a);
+  hipLaunchKernelGGL((k_knnk_tile<K, MAXD>), dim3((nq + 63) / 64), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL((k_knnk_fallback<K, MAXD>), dim3(kFallbackBlocks), dim3(256), 0, h->stream, a);
+}
 template <int K>
 static void launch_knn_k(lsgpu_icp* h, const KnnKArgs& a, bool seed) {
-  const int nq = a.nq;
-  if (seed) hipLaunchKernelGGL(k_knnk_seed<K>, dim3(nblk(nq)), dim3(256), 0, h->stream, a);
-  hipLaunchKernelGGL(k_knnk_tile<K>, dim3((nq + 63) / 64), dim3(64), 0, h->stream, a);
-  hipLaunchKernelGGL(k_knnk_fallback<K>, dim3(kFallbackBlocks), dim3(256), 0, h->stream, a);
+  if (a.max_d2 < INFINITY) launch_knn_k_<K, true>(h, a, seed);   // KDTreeMatcher maxDist: every bound cut to it
+  else launch_knn_k_<K, false>(h, a, seed);
 }
 
 static int run_knn_k(lsgpu_icp* h, int k, const Mat34& T, const IcpState* st, bool seed, bool timed) {
@@ -785,7 +808,7 @@ static int run_knn_k(lsgpu_icp* h, int k, const Mat34& T, const IcpState* st, bo
   KnnKArgs a;
   a.rdq = h->rdq.p; a.nq = (int)nq; a.T = T; a.st = st; a.g = h->grid; a.pts = h->pts.p; a.chunks = h->chunks.p;
   a.kmatch = h->kmatch.p; a.kd2 = h->kd2.p; a.strag = h->strag.p; a.strag_count = h->counters.p + 32;
-  a.r_cap = kKnnKRCap;
+  a.r_cap = kKnnKRCap; a.max_d2 = matcher_max_d2(h);
   if (!st) HIPC(hipMemsetAsync(a.strag_count, 0, sizeof(uint32_t), h->stream));  // (align: k_align_init, then the normal equations re-arm it)
   lsgpu_icp::KnnEv* ev = nullptr;
   if (timed) {   // (the same event record as run_knn: main launches a..b, fallback b..c)
@@ -826,10 +849,13 @@ static int run_knn_k(lsgpu_icp* h, int k, const Mat34& T, const IcpState* st, bo
   } while (0)
 
 // TrimmedDist order statistic of d2[0..n) -> rank k; leaves hist3 + sel[2] for select_limit().
+// rank_ratio > 0: the rank is not `k` but taken on the device from the number of FINITE distances (k_chain_rank:
+// quantiles skip invalid matches); with_median: a second run of the refining passes finds the 0.5 quantile into
+// hist_med / sel_med.  Neither in the split-scan mode.
 static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zero_hist, const IcpState* st,
-                      bool use_comm, bool predicted, int passes) {
+                      bool use_comm, bool predicted, int passes, float rank_ratio, bool with_median) {
   if (zero_hist) HIPC(hipMemsetAsync(h->hist.p, 0, 3 * kHistBins * sizeof(uint32_t), h->stream));
-  if (zero_hist) {  // sel[0] = {0, k}: constant during an align, uploaded once
+  if (zero_hist && !(rank_ratio > 0.f)) {  // sel[0] = {0, k}: constant during an align, uploaded once
     SelState s0{0u, k};
     std::memcpy(h->h_pinned + 56, &s0, sizeof(s0));
     HIPC(hipMemcpyAsync(h->sel.p, h->h_pinned + 56, sizeof(SelState), hipMemcpyHostToDevice, h->stream));
@@ -837,6 +863,16 @@ static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zer
   const int nb = std::min(kHistBlocks, nblk(n));
   const int pr = predicted && st ? 1 : 0;
   hipLaunchKernelGGL(k_hist1, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p, st, pr);
+  if (rank_ratio > 0.f) {
+    hipLaunchKernelGGL(k_chain_rank, dim3(1), dim3(256), 0, h->stream, h->hist.p, st, rank_ratio, h->sel.p,
+                       with_median ? h->sel_med.p : (SelState*)nullptr, h->hist_med.p);
+    if (with_median) {   // the median's run: same first table, its own second and third
+      hipLaunchKernelGGL(k_hist_refine<2>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p,
+                         h->sel_med.p, h->sel_med.p + 1, h->hist_med.p + kHistBins, st, 0, h->sel_aux.p);
+      hipLaunchKernelGGL(k_hist_refine<3>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist_med.p + kHistBins,
+                         h->sel_med.p + 1, h->sel_med.p + 2, h->hist_med.p + 2 * kHistBins, st, 0, h->sel_aux.p);
+    }
+  }
   if (use_comm && h->comm) { comm_mark(h, true); RCCLC(rccl_api()->AllReduce(h->hist.p, h->hist.p, kHistBins, ncclUint32, ncclSum, h->comm, h->stream)); comm_mark(h, false); }
   hipLaunchKernelGGL(k_hist_refine<2>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p,
                      h->sel.p, h->sel.p + 1, h->hist.p + kHistBins, st, pr, h->sel_aux.p);
@@ -855,7 +891,7 @@ static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zer
 // is a direction index built for the current reference at all?  (host-side facts only)
 static bool cone_wanted(const lsgpu_icp* h) {
   const int64_t nr = h->nr;
-  if (h->cfg.matcher_knn >= 2) return false;   // (the k-match loop searches the voxel grid only)
+  if (h->cfg.matcher_knn >= 2 || chain_on(h)) return false;   // (the k-match loop and the chain plan search the voxel grid only)
   if (!(tuning().cone && h->cone_origin_inside && nr >= 1024)) return false;
   // a reference with more points than 0.6 x the occupancy limit x the number of bins cannot come out below the limit
   // (measured: 4.3 / 6.3 / 8.5 points per occupied bin at 3.0 / 4.0 / 5.0 per bin): spare it the build (1.8 ms at 8 M points)
@@ -1082,6 +1118,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
     h->err = "comm_init: the split-scan mode runs knn 1 only (matcher_knn >= 2 is not supported there)";
     return LSGPU_BAD_CONFIG;
   }
+  if (chain_on(h)) {
+    h->err = "comm_init: the split-scan mode runs neither KDTreeMatcher maxDist nor Max- / Min- / MedianDistOutlierFilter";
+    return LSGPU_BAD_CONFIG;
+  }
   if (!api) { h->err = "librccl.so.1 could not be loaded"; return LSGPU_HIP_ERROR; }
   HIPC(hipSetDevice(h->device));
   if (h->comm) { (void)api->CommDestroy(h->comm); h->comm = nullptr; }
@@ -1121,10 +1161,15 @@ int lsgpu_knn(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[1
   const Mat34 Id = to_mat34(I);
   int rc = prepare_queries(h, query_xyz1, nq, Id);
   if (rc) return rc;
+  const bool maxd = matcher_max_d2(h) < INFINITY;   // KDTreeMatcher maxDist: the bounded k-best search with k = 1
+  if (maxd) {
+    rc = run_knn_k(h, 1, Tm, nullptr, true, false);
+    if (rc) return rc;
+  }
   policy::Iteration probe;   // a seeded, uncapped, wide search outside any loop
   probe.seed = true; probe.capped = false; probe.wide = true;
   h->pol.begin_align(false, false, false, 0.f);
-  rc = run_knn(h, Tm, nullptr, probe, false);
+  if (!maxd) rc = run_knn(h, Tm, nullptr, probe, false);
   if (rc) return rc;
   const bool dev_out = is_device_ptr(ids);
   int* ids_o = ids; float* d2_o = d2;
@@ -1132,8 +1177,12 @@ int lsgpu_knn(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[1
     HIPC(h->ids_io.reserve(nq)); HIPC(h->d2_io.reserve(nq));
     ids_o = h->ids_io.p; d2_o = h->d2_io.p;
   }
-  hipLaunchKernelGGL(k_knn_unpermute, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rdq.p, (int)nq,
-                     h->ids.p, h->d2.p, h->pts.p, ids_o, d2_o);
+  if (maxd)
+    hipLaunchKernelGGL(k_knnk_unpermute, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rdq.p, (int)nq, 1, h->kmatch.p,
+                       h->kd2.p, h->pts.p, ids_o, d2_o);
+  else
+    hipLaunchKernelGGL(k_knn_unpermute, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rdq.p, (int)nq,
+                       h->ids.p, h->d2.p, h->pts.p, ids_o, d2_o);
   HIPC(hipGetLastError());
   if (!dev_out) {
     HIPC(hipMemcpyAsync(ids, ids_o, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1193,7 +1242,11 @@ int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, floa
     HIPC(hipMemcpyAsync(h->d2_io.p, d2, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     src = h->d2_io.p;
   }
-  rc = run_select(h, src, (int)n, trim_rank(n, ratio), true, nullptr, false, false);
+  // ratio > 0: the rank over the FINITE distances, taken on the device (Matches::getDistsQuantile skips invalid matches; the
+  // host's rank argument is not read on that route).  A ratio that is not positive asks for rank 0 whatever the count: the
+  // host-side rank, as before.
+  if (ratio > 0.f) rc = run_select(h, src, (int)n, 0u, true, nullptr, false, false, 3, ratio, false);
+  else rc = run_select(h, src, (int)n, trim_rank(n, ratio), true, nullptr, false, false);
   if (rc) return rc;
   hipLaunchKernelGGL(k_limit_out, dim3(1), dim3(256), 0, h->stream, h->hist.p + 2 * kHistBins,
                      h->sel.p + 2, h->limit_dev.p);
@@ -1201,6 +1254,7 @@ int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, floa
   HIPC(hipMemcpyAsync(hl, h->limit_dev.p, 4, hipMemcpyDeviceToHost, h->stream));
   HIPC(hipStreamSynchronize(h->stream));
   *limit = *hl;
+  if (*hl == INFINITY) { h->err = "trim_limit: no finite distance (no outlier to filter)"; return LSGPU_NO_CONVERGENCE; }
   return LSGPU_OK;
 }
 
@@ -2403,6 +2457,17 @@ static NeLoopFn ne_loop_pairs(bool p2p, int k) {
        k_normal_eq_loop<kPointToPoint, 8>}};
   return tab[p2p ? 1 : 0][k];
 }
+// ... and the chain plan's (KDTreeMatcher maxDist / outlier-filter chains, k = 1..LSGPU_MATCHER_KNN_MAX)
+static NeLoopFn ne_loop_chain(bool p2p, int k) {
+  static const NeLoopFn tab[2][kKnnKMax + 1] = {
+      {nullptr, k_normal_eq_loop<kPointToPlane, 1, true>, k_normal_eq_loop<kPointToPlane, 2, true>, k_normal_eq_loop<kPointToPlane, 3, true>,
+       k_normal_eq_loop<kPointToPlane, 4, true>, k_normal_eq_loop<kPointToPlane, 5, true>, k_normal_eq_loop<kPointToPlane, 6, true>,
+       k_normal_eq_loop<kPointToPlane, 7, true>, k_normal_eq_loop<kPointToPlane, 8, true>},
+      {nullptr, k_normal_eq_loop<kPointToPoint, 1, true>, k_normal_eq_loop<kPointToPoint, 2, true>, k_normal_eq_loop<kPointToPoint, 3, true>,
+       k_normal_eq_loop<kPointToPoint, 4, true>, k_normal_eq_loop<kPointToPoint, 5, true>, k_normal_eq_loop<kPointToPoint, 6, true>,
+       k_normal_eq_loop<kPointToPoint, 7, true>, k_normal_eq_loop<kPointToPoint, 8, true>}};
+  return tab[p2p ? 1 : 0][k];
+}
 
 int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
                     float T_out[16], lsgpu_icp_stats* stats) {
@@ -2425,6 +2490,12 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   // KDTreeMatcher knn: 1, or k >= 2 nearest matches per reading point (k N pairs; the split-scan mode refuses such handles)
   const int kk = h->cfg.matcher_knn >= 2 ? h->cfg.matcher_knn : 1;
   const bool kmatch = kk > 1;
+  // KDTreeMatcher maxDist / Max-, Min-, MedianDistOutlierFilter: the chain plan (lsgpu_policy.h), whatever k
+  const bool chain = chain_on(h);
+  ChainArgs ca{};
+  ca.lo2 = h->cfg.outlier_min_dist * h->cfg.outlier_min_dist;
+  ca.max2 = (h->cfg.outlier_max_dist > 0.f && !std::isinf(h->cfg.outlier_max_dist)) ? h->cfg.outlier_max_dist * h->cfg.outlier_max_dist : INFINITY;
+  ca.med_factor = h->cfg.outlier_median_factor; ca.has_median = h->cfg.outlier_median_factor > 0.f ? 1 : 0;
   if (h->nr <= 0 || nq <= 0 || !reading_xyz1) {  // empty cloud: ConvergenceError upstream
     h->err = "align: empty reading or no reference";
     local_rc = LSGPU_NO_CONVERGENCE;
@@ -2497,7 +2568,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 4; ++c) hst->T_rows[r * 4 + c] = hst->T_iter[c * 4 + r];
   hst->prev_limit = INFINITY; hst->cap2 = INFINITY;
-  hst->cap_enabled = (h->cfg.reserved[0] == 0 && !kmatch) ? 1 : 0;   // (no radius cap in the k-match loop)
+  hst->cap_enabled = (h->cfg.reserved[0] == 0 && !kmatch && !chain) ? 1 : 0;   // (no radius cap in the k-match loop / the chain plan)
   hst->minimizer = h->cfg.error_minimizer;
   hst->max_iter = max_it; hst->smooth = h->cfg.smooth_length;
   hst->lim_rot = h->cfg.min_diff_rot; hst->lim_trans = h->cfg.min_diff_trans;
@@ -2512,7 +2583,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   HIPC(h->spread_flag.reserve((size_t)((nq + 63) / 64))); HIPC(h->spread_list.reserve(kFrontMax)); HIPC(h->spread_cnt.reserve(2));
   HIPC(h->sel_win.reserve((size_t)kSelWinRows * 512));
   HIPC(h->amb_key.reserve((size_t)kSelAmbCap)); HIPC(h->amb_val.reserve((size_t)kSelAmbCap * 32));
-  hst->sel_wide = (!h->comm && tuning().fused_select && !kmatch) ? 1 : 0;
+  hst->sel_wide = (!h->comm && tuning().fused_select && !kmatch && !chain) ? 1 : 0;
   h->n_spread_host = 0; h->n_spread_known = false;
   ia.state = *hst;
   ia.sel0 = SelState{0u, k};   // sel[0] = {0, rank}: constant during an align
@@ -2533,7 +2604,8 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   const bool p2p = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
   const auto ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
   const auto update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
-  const NeLoopFn ne_loop_k = kmatch ? ne_loop_pairs(p2p, kk) : nullptr;
+  const NeLoopFn ne_loop_k = chain ? ne_loop_chain(p2p, kk) : kmatch ? ne_loop_pairs(p2p, kk) : nullptr;
+  ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
   // The launch policy (lsgpu_policy.h) decides what every iteration is made of and when the host looks at the loop
   // state; this function executes its decisions.  (tests/cpp/policy_check.cpp drives the same state machine on the CPU.)
   policy::Config& pc = h->pol_cfg;
@@ -2545,7 +2617,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   pc.seed_cap = tuning().seed_cap; pc.cap_enabled = h->cfg.reserved[0] == 0;
   pc.two_pass_select = !h->comm && tuning().fused_select && tuning().two_pass_select;
   pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
-  pc.kmatch = kmatch;
+  pc.kmatch = kmatch; pc.chain = chain;
   policy::State& pol = h->pol;
   if (h->cone_build_in_align) { h->cone_ok = cone_wanted(h); h->cone_decided = false; }   // (its build follows the first iteration, below)
   // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
@@ -2563,12 +2635,14 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     // all-reduce (the host knows beforehand that no select kernel will run: sel_streak comes from the global limit,
     // so every rank takes the same decision); un-committed iterations there run the plain three-pass select.
     int r = LSGPU_OK;
-    if (kmatch) {   // the k-match plan (lsgpu_policy.h): k-best search, three-pass select on the k N distances, pair-indexed sums
+    if (kmatch || chain) {   // the k-match / chain plan (lsgpu_policy.h): k-best search, three-pass select on the k N distances, pair-indexed sums
       const int np = (int)(kk * nq);
       r = run_knn_k(h, kk, Tdummy, h->state.p, itn.seed, timed);                                     // 6a+6b
       if (r) return r;
       ev_of_launch.push_back(h->knn_events_used ? h->knn_events_used - 1 : 0);
-      r = run_select(h, h->kd2.p, np, k, false /* armed by k_align_init / the previous k_normal_eq_loop */, h->state.p, true, false);  // 6c
+      // (chain: the rank from the device's count of valid matches, the median beside it if the chain holds that filter)
+      r = run_select(h, h->kd2.p, np, k, false /* armed by k_align_init / the previous k_normal_eq_loop */, h->state.p, true, false, 3,
+                     chain ? h->cfg.trim_ratio : 0.f, chain && ca.has_median);  // 6c
       if (r) return r;
       lsgpu_icp::KnnEv* evk = (timed && h->knn_events_used) ? &h->knn_events[h->knn_events_used - 1] : nullptr;
       if (evk) HIPC(hipEventRecord(evk->d, h->stream));
@@ -2577,7 +2651,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
                          h->counters.p + 32, h->ne_tickets.p, h->ne_partials.p, h->ne_gpartials.p, h->ne_out.p,
                          h->chk_hist.p, h->trace_dev.p, max_it, 0, split_update ? 0 : 1,
                          h->sel_aux.p, (uint32_t*)nullptr, 0, (uint32_t*)nullptr,
-                         0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0);   // 6d (+6e)
+                         0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0, ca);   // 6d (+6e)
       if (split_update)
         hipLaunchKernelGGL(update, dim3(1), dim3(64), 0, h->stream, h->state.p, h->ne_out.p,
                            h->chk_hist.p, h->trace_dev.p, max_it, 0, h->sel_aux.p);                       // 6d+6e
@@ -2612,7 +2686,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
                        h->chk_hist.p, h->trace_dev.p, max_it, itn.capped ? 1 : 0, (h->comm || split_update) ? 0 : 1,
                        h->sel_aux.p, (h->comm || !tuning().fused_select) ? h->sel_win.p : nullptr, itn.committed ? 1 : 0, h->spread_cnt.p,
                        (itn.predicted && itn.knn) ? 1 : 0, h->sel_aux.p + kSelFailFlag + 2, h->amb_key.p, h->amb_val.p, tuning().sel_amb_cap,
-                       (!itn.full_select && !itn.committed) ? 1 : 0);   // 6d (+6e)
+                       (!itn.full_select && !itn.committed) ? 1 : 0, ChainArgs{});   // 6d (+6e)
     if (h->comm || split_update) {   // split scan: every rank gets the sums over all shards (the limit, slot 29, is already global)
       if (h->comm) comm_mark(h, true);
       if (h->comm && rccl_api()->AllReduce(h->ne_out.p, h->ne_out.p, kNe, ncclDouble, ncclSum, h->comm, h->stream) != ncclSuccess) {

@@ -1,5 +1,5 @@
 // lsgpu_knn_k.hip.h -- exact k-nearest correspondence search: KDTreeMatcher::findClosests with knn = k (2..8 in the ICP
-// loop, 1..8 through lsgpu_knn_k), epsilon 0.  Matches then holds k x N dists / ids (one column per reading point) and
+// loop, 1..8 on the chain plan and through lsgpu_knn_k), epsilon 0.  Matches then holds k x N dists / ids (one column per reading point) and
 // every pair goes on to the outlier filter and the error minimizer ("k nearest matches").
 //
 // Restatement choices (choice 13):
@@ -25,6 +25,11 @@
 //   * lanes whose ball is wider than r_cap go to k_knnk_fallback: one wave per query, chunks culled lane-parallel against
 //     the single ball, nearest box first, the surviving chunks evaluated one point per lane into per-lane lists that
 //     are merged at the end (k rounds of a wave minimum).
+//   * MAXD instantiations (KDTreeMatcher maxDist, DESIGN.md §5 choice 14): every bound above -- the seed's, the warm
+//     start's, the fallback's -- is cut to maxDist^2 before anything is searched, so no launch looks further than maxDist
+//     from its first one on.  An empty list entry IS the bound (the sentinel ranks behind a real point at exactly that
+//     distance: d2 == maxDist^2 is valid), entries left empty are stored invalid (index -1, d2 +inf) behind the valid
+//     ones, and a query with an invalid entry searches the whole maxDist ball again in the next iteration.
 // Output: pair p = j * K + s (j = sorted query, s = rank) -> kmatch[p] = {x, y, z, sorted index bits} of the matched
 // reference point, kd2[p] = its squared distance.  kmatch is also the next search's warm start.
 #pragma once
@@ -50,6 +55,7 @@ struct KnnKArgs {
   uint32_t* strag;          // queries handed to k_knnk_fallback ...
   uint32_t* strag_count;    // ... and their number (re-armed by the normal-equation kernel of the loop)
   float r_cap;              // lanes with a wider ball go to the fallback
+  float max_d2;             // MAXD instantiations: KDTreeMatcher maxDist squared -- a match is valid iff d2 <= max_d2
 };
 
 // (d, i) before (e, j) in the order of a column: ascending distance, then the smaller sorted index
@@ -102,7 +108,7 @@ __device__ __forceinline__ void kbest_store(const KnnKArgs& a, int j, const floa
 // k points near the query: climb the pyramid from level 0 until the cell holding the query (clamped into the grid) has
 // at least K points, keep the K best of its first 256.  (The top level is one cell with every point, and the handle
 // refuses a reference with fewer than K points.)
-template <int K>
+template <int K, bool MAXD = false>
 __global__ __launch_bounds__(256) void k_knnk_seed(KnnKArgs a) {
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= a.nq) return;
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(256) void k_knnk_seed(KnnKArgs a) {
   const int fy = fine_coord(q.y, g.oy, g.inv_hf, lim);
   const int fz = fine_coord(q.z, g.oz, g.inv_hf, lim);
   float D[K]; int I[K];
-  kbest_init<K>(D, I, INFINITY);
+  kbest_init<K>(D, I, MAXD ? a.max_d2 : INFINITY);
   for (int l = 0; l <= g.bits; ++l) {
     const int sh = g.fine + l;
     uint32_t cs, ce;
@@ -136,7 +142,7 @@ __global__ __launch_bounds__(256) void k_knnk_seed(KnnKArgs a) {
 }
 
 // ---------------------------------------------------------------- tile search, 64 queries per wave
-template <int K>
+template <int K, bool MAXD = false>
 __global__ __launch_bounds__(64) void k_knnk_tile(KnnKArgs a) {
   __shared__ float4 stage[kChunkMax];
   Mat34 T; float cap2;
@@ -151,6 +157,7 @@ __global__ __launch_bounds__(64) void k_knnk_tile(KnnKArgs a) {
     const float3 q = xform(T, r.x, r.y, r.z);
     qx = q.x; qy = q.y; qz = q.z;
     ub = kbest_warm_bound<K>(a, j, qx, qy, qz);
+    if (MAXD) ub = fminf(ub, a.max_d2);
   }
   const float R = sqrtf(ub) * (1.0f + 1e-5f) + 1e-7f + kFineSlack * g.hf;
   const bool wide = valid && !(R <= a.r_cap);   // (an infinite bound included)
@@ -222,7 +229,7 @@ __global__ __launch_bounds__(64) void k_knnk_tile(KnnKArgs a) {
 }
 
 // ---------------------------------------------------------------- exact fallback, one wave per query
-template <int K>
+template <int K, bool MAXD = false>
 __global__ __launch_bounds__(256) void k_knnk_fallback(KnnKArgs a) {
   const int lane = threadIdx.x & 63;
   const uint32_t nw = gridDim.x * 4u;
@@ -235,7 +242,8 @@ __global__ __launch_bounds__(256) void k_knnk_fallback(KnnKArgs a) {
     const int j = (int)a.strag[s];
     const float4 r = a.rdq[j];
     const float3 q = xform(T, r.x, r.y, r.z);
-    const float ub = kbest_warm_bound<K>(a, j, q.x, q.y, q.z);
+    float ub = kbest_warm_bound<K>(a, j, q.x, q.y, q.z);
+    if (MAXD) ub = fminf(ub, a.max_d2);
     float D[K]; int I[K];
     kbest_init<K>(D, I, ub);
     float bound = ub;

@@ -33,7 +33,17 @@ struct Config {               // constant during an alignment (from Tuning and t
   float cone_max_occupancy = 7.f;
   double straggler_share = 0.02;     // lanes the index could not serve, per settled iteration, above which it is dropped
   bool kmatch = false;        // k nearest matches (lsgpu_icp_config.matcher_knn >= 2): see State::plan
+  bool chain = false;         // KDTreeMatcher maxDist or a Max- / Min- / MedianDistOutlierFilter (chain_fields): see State::plan_chain
 };
+
+// Which handles take the chain plan: any of the four fields lsgpu_icp_config gained for KDTreeMatcher maxDist and the
+// outlier-filter chain (0 = absent; +inf = absent for the two maxDist fields).  A configuration with none of them is
+// planned exactly as before the fields existed.
+inline bool chain_fields(float matcher_max_dist, float outlier_max_dist, float outlier_min_dist, float outlier_median_factor) {
+  const bool md = matcher_max_dist > 0.f && !std::isinf(matcher_max_dist);
+  const bool od = outlier_max_dist > 0.f && !std::isinf(outlier_max_dist);
+  return md || od || outlier_min_dist > 0.f || outlier_median_factor > 0.f;
+}
 
 struct Iteration {            // one enqueued iteration: what the search, the select and the normal equations are told
   bool knn = true;            // false: select + normal equations + update on the distances already there (a missed prediction)
@@ -104,6 +114,7 @@ struct State {
 
   // ---- what the next iteration is made of
   Iteration plan(const Config& c, bool seed, bool capped, bool wide, bool knn, bool price_next) {
+    if (c.chain) return plan_chain(seed, knn);
     if (c.kmatch) return plan_kmatch(seed, knn);
     Iteration it;
     it.knn = knn; it.seed = seed; it.capped = capped; it.wide = wide;
@@ -132,6 +143,13 @@ struct State {
     it.ordinal = enq;
     return it;
   }
+
+  // The chain plan (first version): whatever k, the k-best search on the voxel grid -- every bound of it cut to the
+  // matcher's maxDist from the seed launch on --, the full select every iteration (its rank comes from the device's count
+  // of valid matches, a second run of its refining passes finds the median when the chain needs it) and the chain
+  // instantiation of the normal equations.  None of the accelerations of the one-neighbour loop: their tables assume that
+  // every query has a match and that the rank is known to the host.  No look can ask for a repeat.
+  Iteration plan_chain(bool seed, bool knn) { return plan_kmatch(seed, knn); }
 
   // the loop between two looks: true -> enqueue a plain iteration (fills `it`), false -> look at the loop state
   bool next_in_group(const Config& c, Iteration* it) {

@@ -160,6 +160,50 @@ __global__ __launch_bounds__(256) void k_limit_out(const uint32_t* __restrict__ 
   if (threadIdx.x == 0) *out = lim;
 }
 
+// ---------------------------------------------------------------- outlier-filter chains ("maxDist and
+// outlier-filter chains").  With KDTreeMatcher maxDist a match may be invalid (d2 = +inf), and Matches::getDistsQuantile
+// ranks the m FINITE distances only: rank = min(m - 1, (int64)((float)m * q)).  m changes with every iteration, so the
+// rank is taken on the device from the select's first table, which has seen every distance of the iteration (+inf falls
+// into bin 0x7F8; m = 0 leaves rank 0 and the +inf "limit" no pair passes).  One block between k_hist1 and
+// k_hist_refine<2>: it writes the select's input {0, rank(ratio)} and, for MedianDistOutlierFilter, the input of a second
+// run of the two refining passes, {0, rank(0.5)}, whose two tables it also clears.
+constexpr uint32_t kHistInfBin = 0x7F800000u >> 20;
+__global__ __launch_bounds__(256) void k_chain_rank(const uint32_t* __restrict__ hist1, const IcpState* __restrict__ ist,
+                                                    float ratio, SelState* __restrict__ sel0,
+                                                    SelState* __restrict__ sel_med0 /* nullable */,
+                                                    uint32_t* __restrict__ hist_med /* 3 x kHistBins, [0] unused */) {
+  __shared__ uint32_t part[4];
+  if (ist && ist->done) return;
+  uint32_t m = 0u;
+  for (uint32_t i = threadIdx.x; i < kHistInfBin; i += 256u) m += hist1[i];
+  m = wave_sum_u32(m);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = part[0] + part[1] + part[2] + part[3];
+  auto rank = [m](float q) -> uint32_t {
+    if (m == 0u) return 0u;
+    const long long k = (long long)((float)m * q);
+    return k >= (long long)m ? m - 1u : k < 0 ? 0u : (uint32_t)k;
+  };
+  if (threadIdx.x == 0) {
+    sel0->prefix = 0u; sel0->k = rank(ratio);
+    if (sel_med0) { sel_med0->prefix = 0u; sel_med0->k = rank(0.5f); }
+  }
+  if (sel_med0)
+    for (int i = threadIdx.x; i < 2 * kHistBins; i += 256) hist_med[kHistBins + i] = 0u;
+}
+
+// What a chain adds to the loop's normal-equation kernel (CHAIN instantiations): a pair is kept iff
+// lo2 <= d2 && d2 <= hi, hi = min(trim limit, max2, med_factor x median) -- the iteration's effective upper limit.
+struct ChainArgs {
+  float lo2;                  // MinDistOutlierFilter: minDist^2 (0: none)
+  float max2;                 // MaxDistOutlierFilter: maxDist^2 (+inf: none)
+  float med_factor;           // MedianDistOutlierFilter: factor ...
+  int has_median;             // ... if the chain holds one
+  const uint32_t* hist_med;   // the median's select: 3 x kHistBins ([0] unused: the first table is shared) ...
+  const SelState* sel_med;    // ... and its three states
+};
+
 // First iteration: the select just ran over the SEED distances (upper bounds of the true ones); its result is a
 // valid cap for the first search (limit(true distances) <= limit(upper bounds)).
 __global__ __launch_bounds__(256) void k_seed_cap(uint32_t* __restrict__ hist /* 3 x kHistBins */,
@@ -456,7 +500,9 @@ constexpr int kNeUnroll = LSGPU_NE_UNROLL;  // points whose loads are in flight 
 // KP > 1: the pair-indexed instantiation of the k-match loop (KDTreeMatcher knn = KP, lsgpu_knn_k.hip.h): `nq` counts
 // pairs, `match` / `d2` hold KP entries per query and pair j reads query j / KP.  The select, the sums, their order and
 // the update are those of the 1-NN loop; its launches pass no fused / predicted / committed select.
-template <int MIN, int KP = 1>
+// CHAIN: the instantiations of a chain with KDTreeMatcher maxDist / Max-, Min-, MedianDistOutlierFilter (ChainArgs; the
+// matches come from the k-best search for every KP, 1 included); like KP > 1 they run behind a full select.
+template <int MIN, int KP = 1, bool CHAIN = false>
 __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict__ rdq, int nq,
                                                         IcpState* __restrict__ ist,
                                                         const float4* __restrict__ match,
@@ -480,7 +526,8 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
                                                         uint32_t* __restrict__ amb_cnt, uint2* __restrict__ amb_key /* kSelAmbCap x {query, distance bits} */,
                                                         double* __restrict__ amb_val /* kSelAmbCap x 32 */,
                                                         int amb_cap /* <= kSelAmbCap: a slice with more distances is summed in place */,
-                                                        int two_pass /* the select stopped after its second pass: the limit's slice is known, the limit is not */) {
+                                                        int two_pass /* the select stopped after its second pass: the limit's slice is known, the limit is not */,
+                                                        ChainArgs chain /* read by the CHAIN instantiations only */) {
   __shared__ uint32_t sc[260];
   __shared__ double fin[32];
   __shared__ double red[8][33];
@@ -602,6 +649,10 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     }
   } else {
     limit = select_limit(hist + 2 * kHistBins, st, sc);
+    if constexpr (CHAIN) {   // the smallest of the upper thresholds present
+      if (chain.has_median) limit = fminf(limit, chain.med_factor * select_limit(chain.hist_med + 2 * kHistBins, chain.sel_med + 2, sc));
+      limit = fminf(limit, chain.max2);
+    }
     if (wide) {
       // the same sum as the fused select's: the inliers of the limit's slice are set aside and added in query order --
       // if the slice holds no more than the fused path could have set aside (its count: four bins of the select's
@@ -635,7 +686,8 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
         const bool in_s = sl == s_slice;
         // fused: below the limit's slice = an inlier, inside it = set aside (the exact limit is one of those);
         // otherwise the limit is known and only the slice's inliers are set aside
-        const bool inl = resolve ? sl <= s_slice : dd[u] <= limit;
+        bool inl = resolve ? sl <= s_slice : dd[u] <= limit;
+        if constexpr (CHAIN) inl = inl && chain.lo2 <= dd[u];
         amb[u] = use[u] && inl && in_s;
         use[u] = use[u] && inl;
       }

@@ -16,6 +16,7 @@ arrays (host) or torch CUDA tensors (HBM-resident, zero copy).
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -78,16 +79,24 @@ def _raise(code: int, what: str, h=None):
 class IcpHandle:
     """One lsgpu_icp handle == one reference ``icp_`` member: one device, one HIP stream."""
 
-    def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None):
+    def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
+                 matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
-        every reading point is paired with its k nearest reference points)."""
+        every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
+        outlier_max_dist / outlier_min_dist / outlier_median_factor: Max- / Min- / MedianDistOutlierFilter's parameter
+        (None: cfg's; 0: no such module; see lsgpu_icp_config)."""
         L = _lib.lib()
         if cfg is None:
             cfg = IcpConfig()
             L.lsgpu_icp_config_yaml(C.byref(cfg))
-        if error_minimizer is not None or matcher_knn is not None:
+        thresholds = {"matcher_max_dist": matcher_max_dist, "outlier_max_dist": outlier_max_dist,
+                      "outlier_min_dist": outlier_min_dist, "outlier_median_factor": outlier_median_factor}
+        if error_minimizer is not None or matcher_knn is not None or any(v is not None for v in thresholds.values()):
             cfg = IcpConfig.from_buffer_copy(cfg)       # (the caller's config stays as it is)
+            for name, v in thresholds.items():
+                if v is not None:
+                    setattr(cfg, name, float(v))
             if error_minimizer is not None:
                 cfg.error_minimizer = _MINIMIZERS.get(error_minimizer, error_minimizer)
             if matcher_knn is not None:
@@ -551,7 +560,8 @@ _SUPPORTED = {
     "readingDataPointsFilters": {"RandomSamplingDataPointsFilter"},
     "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter"},
     "matcher": {"KDTreeMatcher"},
-    "outlierFilters": {"TrimmedDistOutlierFilter"},
+    "outlierFilters": {"TrimmedDistOutlierFilter", "MaxDistOutlierFilter", "MinDistOutlierFilter",
+                       "MedianDistOutlierFilter"},
     "errorMinimizer": {"PointToPlaneErrorMinimizer", "PointToPointErrorMinimizer"},
     "transformationCheckers": {"CounterTransformationChecker", "DifferentialTransformationChecker"},
 }
@@ -574,6 +584,10 @@ class ChainConfig:
     seed: int = -1                          # >= 0: srand(seed) before the filters
     error_minimizer: str = "PointToPlaneErrorMinimizer"   # yaml:18-19, or "PointToPointErrorMinimizer"
     matcher_knn: int = 1                    # yaml:11  KDTreeMatcher knn (1.._lib.MATCHER_KNN_MAX), epsilon 0
+    matcher_max_dist: float = 0.0           # KDTreeMatcher maxDist [m]; 0: absent (inf)
+    outlier_max_dist: float = 0.0           # MaxDistOutlierFilter maxDist [m]; 0: no such module
+    outlier_min_dist: float = 0.0           # MinDistOutlierFilter minDist [m]; 0: no such module (or minDist 0: keeps all)
+    outlier_median_factor: float = 0.0      # MedianDistOutlierFilter factor; 0: no such module
     extra: dict = field(default_factory=dict)
 
 
@@ -629,6 +643,23 @@ class ICP:
                         out.append((k, p or {}))
             return out
 
+        def bad(text):
+            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", text)
+
+        def only(name, params, *known):      # a parameter the module does not have is a configuration error
+            for k in params:
+                if k not in known:
+                    bad(f"{name}: unknown parameter {k}")
+
+        def one_float(name, params, key, default):
+            try:
+                v = float(params.get(key, default))
+            except (TypeError, ValueError):
+                bad(f"{name}: {key} is not a number")
+            if math.isnan(v):
+                bad(f"{name}: {key} is not a number")
+            return v
+
         for section, allowed in _SUPPORTED.items():
             for name, params in modules(section):
                 if name not in allowed:
@@ -645,14 +676,37 @@ class ICP:
                     if int(params.get("samplingMethod", 0)) != 0:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "samplingMethod != 0")
                 elif name == "KDTreeMatcher":
-                    # (its other parameters -- maxDist, searchType, ... -- are not read: a finite maxDist is ignored)
+                    # (its other parameters -- searchType, ... -- are not read)
+                    md = one_float(name, params, "maxDist", math.inf)
+                    if not md > 0.0:
+                        bad(f"KDTreeMatcher: maxDist must be > 0 (got {md})")
+                    ch.matcher_max_dist = 0.0 if math.isinf(md) else md
                     knn = int(params.get("knn", 1))
                     if not 1 <= knn <= _lib.MATCHER_KNN_MAX or float(params.get("epsilon", 0)) != 0.0:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml",
                                          f"KDTreeMatcher: knn 1..{_lib.MATCHER_KNN_MAX} with epsilon 0 is implemented")
                     ch.matcher_knn = knn
                 elif name == "TrimmedDistOutlierFilter":
-                    ch.trim_ratio = float(params.get("ratio", 0.85))
+                    only(name, params, "ratio")
+                    ch.trim_ratio = one_float(name, params, "ratio", 0.85)
+                    if not 0.0 < ch.trim_ratio <= 1.0:
+                        bad(f"TrimmedDistOutlierFilter: ratio must be in (0, 1] (got {ch.trim_ratio})")
+                elif name == "MaxDistOutlierFilter":
+                    only(name, params, "maxDist")
+                    md = one_float(name, params, "maxDist", 1.0)
+                    if not md > 0.0:
+                        bad(f"MaxDistOutlierFilter: maxDist must be > 0 (got {md})")
+                    ch.outlier_max_dist = 0.0 if math.isinf(md) else md
+                elif name == "MinDistOutlierFilter":
+                    only(name, params, "minDist")
+                    ch.outlier_min_dist = one_float(name, params, "minDist", 1.0)
+                    if not 0.0 <= ch.outlier_min_dist < math.inf:
+                        bad(f"MinDistOutlierFilter: minDist must be >= 0 and finite (got {ch.outlier_min_dist})")
+                elif name == "MedianDistOutlierFilter":
+                    only(name, params, "factor")
+                    ch.outlier_median_factor = one_float(name, params, "factor", 3.0)
+                    if not 0.0 < ch.outlier_median_factor < math.inf:
+                        bad(f"MedianDistOutlierFilter: factor must be > 0 and finite (got {ch.outlier_median_factor})")
                 elif name in _MINIMIZERS:
                     if "minimizer" in seen:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "errorMinimizer: one module at most")
@@ -688,7 +742,9 @@ class ICP:
             cfg.min_diff_rot = self.chain.min_diff_rot
             cfg.min_diff_trans = self.chain.min_diff_trans
             cfg.smooth_length = self.chain.smooth_length
-            self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer, self.chain.matcher_knn)
+            self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer, self.chain.matcher_knn,
+                                     self.chain.matcher_max_dist, self.chain.outlier_max_dist,
+                                     self.chain.outlier_min_dist, self.chain.outlier_median_factor)
         return self._handle
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
