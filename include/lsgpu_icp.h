@@ -26,7 +26,9 @@
  *
  * Modules: the chain of icp_default.yaml, PointToPointErrorMinimizer in place of PointToPlaneErrorMinimizer
  * (lsgpu_icp_config.error_minimizer), KDTreeMatcher with knn 1..LSGPU_MATCHER_KNN_MAX (lsgpu_icp_config.matcher_knn) and
- * maxDist (matcher_max_dist), and any subset of Trimmed- / Max- / Min- / MedianDistOutlierFilter (outlier_*).
+ * maxDist (matcher_max_dist), any subset of Trimmed- / Max- / Min- / MedianDistOutlierFilter (outlier_*), and
+ * SurfaceNormalDataPointsFilter in place of SamplingSurfaceNormalDataPointsFilter as the reference filter
+ * (lsgpu_chain_config.sn_knn).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -287,21 +289,46 @@ typedef struct lsgpu_chain_config {
   int     ssn_knn;          /* SamplingSurfaceNormalDataPointsFilter.knn      yaml:6-7 (10); 0: NO reference filter
                              * module -- the reference as given, no normals, no draw (point-to-point handles only) */
   float   ssn_ratio;        /* SamplingSurfaceNormalDataPointsFilter.ratio    yaml:6-7 (0.5)  */
-  int     pad_;
+  int     sn_knn;           /* SurfaceNormalDataPointsFilter.knn (3..32) as THE reference filter module; 0 (both presets, a
+                             * zero-filled struct): absent.  Not together with ssn_knn > 0: LSGPU_BAD_CONFIG */
   int64_t seed;             /* >= 0: reseed before the reference filter; < 0: continue        */
 } lsgpu_chain_config;
 void lsgpu_chain_config_yaml(lsgpu_chain_config* c);     /* icp_default.yaml values           */
 void lsgpu_chain_config_default(lsgpu_chain_config* c);  /* ICP::setDefault(): 0.75, 7, 0.5   */
+/* What lsgpu_icp_compute accepts, without a handle or a device: LSGPU_OK, or LSGPU_BAD_CONFIG for ssn_knn / sn_knn outside
+ * {0, 3..32}, both of them > 0, or neither with the point-to-plane minimizer (error_minimizer: LSGPU_MINIMIZER_*), which
+ * needs the normals one of them provides. */
+int lsgpu_chain_config_check(const lsgpu_chain_config* c, int error_minimizer);
 
 /* SamplingSurfaceNormalDataPointsFilter on the device.  3 <= knn <= 32.  out_xyz1 (4 floats/pt) and
  * out_normals (3 floats/pt) need room for n points; host or device pointers. */
 int lsgpu_icp_filter_reference(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float ratio,
                                int64_t seed, float* out_xyz1, float* out_normals, int64_t* n_out);
+/* SurfaceNormalDataPointsFilter (keepNormals 1, epsilon 0, no maxDist) -- the contract, for the device and the host
+ * version (lsgpu_filter_surface_normal) alike, which agree bit for bit:
+ *   Every point is kept, in its place, and no rand() draw is consumed; 3 <= knn <= 32 and n >= knn, else LSGPU_BAD_ARG.
+ *   Coordinates: everything below is taken on the cloud CENTRED ON ITS MEAN exactly as lsgpu_icp_set_reference centres
+ *     it -- mean = (float)(sum in double / n) per coordinate, c = p - mean, one float subtraction per coordinate.
+ *   The neighbourhood of point i is its knn nearest points of the same cloud, ITSELF INCLUDED (at distance 0; first
+ *     unless an exact duplicate of it has a smaller index), exact search, d2 = fma(dz,dz, fma(dy,dy, dx*dx)) in float; neighbours in ascending d2, ties to the smaller index
+ *     of the cloud as given -- the same rule picks between a knn-th and a (knn+1)-th point at the same distance.
+ *   Normal: mean of the neighbourhood (float sum in that order / (float)knn), C = sum e e^T in float, rank test and
+ *     eigenvector of the smallest eigenvalue as for a box of the sampling filter (csrc/lsgpu_box_normal.h, box_normal).
+ *     A neighbourhood that fails the rank test (rank + 1 < 3: all its points on one line) gets the normal (0, 1, 0).
+ * Device entry point: out_normals 3 floats per point; out_ids (nullable) knn indices per point, point major, into the
+ * cloud as given, in that order (self first, but for a duplicate with a smaller index); out_d2 (nullable, only with out_ids) the matching squared distances.  Host or device
+ * pointers.  The search runs on the structures lsgpu_icp_set_reference builds, so the call LEAVES THE CLOUD AS THE
+ * HANDLE'S REFERENCE with these normals -- as lsgpu_icp_set_reference(h, xyz1, out_normals, n) would. */
+int lsgpu_icp_filter_reference_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals,
+                                       int32_t* out_ids, float* out_d2);
 /* RandomSamplingDataPointsFilter on the device: keeps point i iff draw_i < prob, order preserved. */
 int lsgpu_icp_filter_reading(lsgpu_icp* h, const float* xyz1, int64_t n, float prob, int64_t seed,
                              float* out_xyz1, int64_t* n_out);
 /* ICP::compute.  Returns like lsgpu_icp_align (LSGPU_NO_CONVERGENCE also when a filter leaves no
- * point); stats->t_reserved[0] = milliseconds spent in the two filters + set_reference. */
+ * point); stats->t_reserved[0] = milliseconds spent in the two filters + set_reference.
+ * chain->sn_knn > 0: the reference filter is SurfaceNormalDataPointsFilter -- the whole reference, its normals computed
+ * on the grid set_reference has just built; a reference with fewer than sn_knn points is LSGPU_BAD_ARG.  A point-to-point
+ * handle reads no normals and skips the computation. */
 int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1,
                       int64_t nr, const float T_init[16], const lsgpu_chain_config* chain,
                       float T_out[16], lsgpu_icp_stats* stats);
@@ -409,6 +436,10 @@ int64_t lsgpu_filter_random_sampling(int64_t n, float prob, int64_t seed, int64_
 /* SamplingSurfaceNormalDataPointsFilter (yaml:5-7), samplingMethod 0, keepNormals 1. */
 int64_t lsgpu_filter_sampling_surface_normal(const float* xyz1, int64_t n, int knn, float ratio,
                                              int64_t seed, float* out_xyz1, float* out_normals);
+/* SurfaceNormalDataPointsFilter on the host (a checker: sort-based exact search): the contract and the outputs of
+ * lsgpu_icp_filter_reference_normals, bit for bit.  Returns LSGPU_OK or LSGPU_BAD_ARG. */
+int lsgpu_filter_surface_normal(const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
+                                float* out_d2);
 /* RigidTransformation::checkParameters / correctParameters (common.hpp:136-149). */
 int  lsgpu_check_rigid(const float T[16]);
 void lsgpu_correct_rigid(const float T[16], float out[16]);

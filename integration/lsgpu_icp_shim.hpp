@@ -102,7 +102,7 @@ class LsgpuICP {
       throw std::runtime_error("LsgpuICP: lsgpu_icp_create failed (no ROCm GPU visible?)");
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.seed = seed_;
+    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
     TransformationParameters T = T_init;
     const int rc = lsgpu_icp_compute(h_, Traits::features(reading), Traits::size(reading), Traits::features(reference),
                                      Traits::size(reference), T_init.data(), &chain, T.data(), &stats_);
@@ -116,6 +116,7 @@ class LsgpuICP {
   void take(const laser_slam_amd::ICP& parsed) {
     cfg_ = parsed.config();
     prob_ = parsed.readingSamplingProb(); knn_ = parsed.surfaceNormalKnn(); ratio_ = parsed.surfaceNormalRatio();
+    sn_knn_ = parsed.referenceNormalKnn();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -125,6 +126,7 @@ class LsgpuICP {
   lsgpu_icp_stats stats_{};
   float prob_ = 0.75f, ratio_ = 0.5f;
   int knn_ = 7;
+  int sn_knn_ = 0;                                      // SurfaceNormalDataPointsFilter as the reference filter (0: absent)
   int64_t seed_ = -1;
 };
 

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "lsgpu_filter_sampling_surface_normal", "lsgpu_check_rigid", "lsgpu_correct_rigid", "lsgpu_rotation_distance",
     "lsgpu_strerror", "lsgpu_last_error", "lsgpu_abi_version", "lsgpu_apply_point_filters",
     "lsgpu_cloud_from_pointcloud2", "lsgpu_cloud_to_pointxyz",
+    "lsgpu_icp_filter_reference_normals", "lsgpu_filter_surface_normal", "lsgpu_chain_config_check",
 ]
 
 
@@ -41,7 +42,7 @@ class ChainCfg(C.Structure):
         ("reading_prob", C.c_float),
         ("ssn_knn", C.c_int),
         ("ssn_ratio", C.c_float),
-        ("pad_", C.c_int),
+        ("sn_knn", C.c_int),           # SurfaceNormalDataPointsFilter knn (3..32); 0: absent.  Not with ssn_knn > 0
         ("seed", C.c_int64),
     ]
 
@@ -178,6 +179,9 @@ def lib() -> C.CDLL:
     L.lsgpu_chain_config_default.argtypes = [C.POINTER(ChainCfg)]
     L.lsgpu_chain_config_default.restype = None
     L.lsgpu_icp_filter_reference.argtypes = [vp, fp, i64, C.c_int, C.c_float, i64, fp, fp, C.POINTER(i64)]
+    L.lsgpu_chain_config_check.argtypes = [C.POINTER(ChainCfg), C.c_int]
+    L.lsgpu_icp_filter_reference_normals.argtypes = [vp, fp, i64, C.c_int, fp, fp, fp]
+    L.lsgpu_filter_surface_normal.argtypes = [fp, i64, C.c_int, fp, fp, fp]
     L.lsgpu_icp_filter_reading.argtypes = [vp, fp, i64, C.c_float, i64, fp, C.POINTER(i64)]
     L.lsgpu_icp_compute.argtypes = [vp, fp, i64, fp, i64, C.POINTER(C.c_float), C.POINTER(ChainCfg),
                                     C.POINTER(C.c_float), C.POINTER(IcpStats)]

@@ -248,19 +248,20 @@ class ICP {
   // PointToPlane / Counter 40 + Differential 1e-3, 1e-3, 3
   void setDefault() {
     lsgpu_icp_config_default(&cfg_);
-    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f;
+    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f; sn_knn_ = 0;
     release();
   }
 
   // Accepts the module chain of laser_slam/configurations/icp_default.yaml, with PointToPlaneErrorMinimizer or
   // PointToPointErrorMinimizer, KDTreeMatcher knn 1..LSGPU_MATCHER_KNN_MAX (epsilon 0) with maxDist, and any subset of
-  // Trimmed- / Max- / Min- / MedianDistOutlierFilter (each at most once, any order); any other module is a configuration error (PointMatcher's registrar throws on unknown
-  // names as well).
+  // Trimmed- / Max- / Min- / MedianDistOutlierFilter (each at most once, any order), and SurfaceNormalDataPointsFilter in
+  // place of SamplingSurfaceNormalDataPointsFilter as THE reference filter; any other module is a configuration error
+  // (PointMatcher's registrar throws on unknown names as well).
   void loadFromYaml(std::istream& in) {
     lsgpu_icp_config c;
     lsgpu_icp_config_default(&c);
     float prob = 0.75f, ratio = 0.5f;
-    int knn = 7;
+    int knn = 7, sn_knn = 0;
     const auto mods = parseYaml(in);
     // libpointmatcher's loadFromYaml starts from EMPTY chains: a section the file does not mention means "no such
     // module", not "the default module".  A missing filter section therefore keeps every point (prob / ratio 1 is
@@ -304,10 +305,26 @@ class ICP {
         if (has_reading) throw ConfigError("readingDataPointsFilters: one RandomSamplingDataPointsFilter at most");
         has_reading = true; prob = (float)num("prob", 0.75);
       } else if (sec == "referenceDataPointsFilters" && name == "SamplingSurfaceNormalDataPointsFilter") {
-        if (has_reference) throw ConfigError("referenceDataPointsFilters: one SamplingSurfaceNormalDataPointsFilter at most");
+        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
         has_reference = true;
         knn = (int)num("knn", 7); ratio = (float)num("ratio", 0.5);
         if ((int)num("samplingMethod", 0) != 0) throw ConfigError("samplingMethod != 0 is not implemented");
+      } else if (sec == "referenceDataPointsFilters" && name == "SurfaceNormalDataPointsFilter") {
+        // every point, the normal of its knn nearest neighbours: keepNormals 1 alone, exact (epsilon 0), no maxDist
+        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
+        only(name, {"knn", "epsilon", "maxDist", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
+                    "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"});
+        has_reference = true;
+        const double k = fnum(name, "knn", 5);
+        if (!(k >= 3 && k <= 32) || k != (double)(int)k) throw ConfigError(name + ": knn must be in [3, 32]");
+        if (fnum(name, "epsilon", 0.0) != 0.0) throw ConfigError(name + ": epsilon must be 0 (the search is exact)");
+        const double md = fnum(name, "maxDist", INFINITY);
+        if (!(std::isinf(md) && md > 0.0)) throw ConfigError(name + ": maxDist must be absent or inf");
+        if (fnum(name, "keepNormals", 1) != 1.0) throw ConfigError(name + ": keepNormals must be 1 (the module is there for the normals)");
+        for (const char* key : {"keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
+                                "sortEigen", "smoothNormals"})
+          if (fnum(name, key, 0) != 0.0) throw ConfigError(name + ": " + key + " must be 0 or absent");
+        sn_knn = (int)k;
       } else if (sec == "matcher" && name == "KDTreeMatcher") {
         has_matcher = true;
         // knn 1..LSGPU_MATCHER_KNN_MAX, exact search only, maxDist; its other parameters (searchType, ...) are not read
@@ -362,11 +379,11 @@ class ICP {
     if (!has_matcher) throw ConfigError("matcher: KDTreeMatcher is required");
     if (!has_minimizer) throw ConfigError("errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer is required");
     if (!has_reference && c.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
-      throw ConfigError("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter is required (it provides the normals of PointToPlaneErrorMinimizer)");
-    if (!has_reference) knn = 0;
+      throw ConfigError("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter is required (it provides the normals of PointToPlaneErrorMinimizer)");
+    if (!has_reference || sn_knn > 0) knn = 0;
     if (!has_counter) throw ConfigError("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
     if (!has_differential) { c.min_diff_rot = -1.f; c.min_diff_trans = -1.f; c.smooth_length = 1; }  // never satisfied: the counter stops
-    cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio;
+    cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio; sn_knn_ = sn_knn;
     release();
   }
 
@@ -400,7 +417,7 @@ class ICP {
     // readingDataPointsFilters, the loop (lsgpu_icp_compute)
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.seed = seed_;
+    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
     TransformationParameters T = T_init;
     const int rc = lsgpu_icp_compute(h_, reading.features.data(), nq, reference.features.data(), nr, T_init.data(),
                                      &chain, T.data(), &stats_);
@@ -440,7 +457,7 @@ class ICP {
     if (refs.size() != ref_T.size()) throw std::logic_error("one transform per reference cloud");
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.seed = seed_;
+    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
     TransformationParameters T = T_init;
@@ -465,7 +482,7 @@ class ICP {
     if (refs.size() != ref_T.size()) throw std::logic_error("one transform per reference cloud");
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.seed = seed_;
+    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
     TransformationParameters T = T_init;
@@ -519,7 +536,8 @@ class ICP {
   const lsgpu_icp_config& config() const { return cfg_; }
   lsgpu_icp* handle() { ensureHandle(); return h_; }  // the C-ABI handle (device conversions of ros_msgs.hpp)
   float readingSamplingProb() const { return prob_; }
-  int surfaceNormalKnn() const { return knn_; }
+  int surfaceNormalKnn() const { return knn_; }            // SamplingSurfaceNormalDataPointsFilter's knn (0: no such module)
+  int referenceNormalKnn() const { return sn_knn_; }       // SurfaceNormalDataPointsFilter's knn (0: no such module)
   float surfaceNormalRatio() const { return ratio_; }
 
  private:
@@ -586,6 +604,7 @@ class ICP {
   lsgpu_icp_stats stats_{};
   float prob_ = 0.75f, ratio_ = 0.5f;
   int knn_ = 7;
+  int sn_knn_ = 0;
   int64_t seed_ = -1;
   unsigned generation_ = 0;
 #ifdef LSGPU_TEST_SEAMS

@@ -2,6 +2,7 @@
 // inside PointMatcher::ICP::compute, laser_slam/src/laser_track.cpp:496):
 //   RandomSamplingDataPointsFilter           laser_slam/configurations/icp_default.yaml:1-3
 //   SamplingSurfaceNormalDataPointsFilter    laser_slam/configurations/icp_default.yaml:5-7
+//   SurfaceNormalDataPointsFilter            (a user's chain; the contract is in include/lsgpu_icp.h)
 //   RigidTransformation check / correct      laser_slam/include/laser_slam/common.hpp:136-149
 // GPU versions of the two filters are SURVEY.md §8f row N1/N3 ("next").
 #include <algorithm>
@@ -133,6 +134,69 @@ int64_t lsgpu_filter_sampling_surface_normal(const float* xyz1, int64_t n, int k
   b.build(0, n, mn, mx);
   b.emit(n);
   return b.n_out;
+}
+
+// SurfaceNormalDataPointsFilter.  A checker: the exact search sweeps outwards from the point along the x-sorted cloud
+// and stops where dx * dx alone exceeds the knn-th distance found so far (d2 = fma(dz,dz, fma(dy,dy, dx*dx)) >= dx * dx
+// in float as well: adding a non-negative term never rounds below the other operand).
+int lsgpu_filter_surface_normal(const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
+                                float* out_d2) {
+  if (!xyz1 || !out_normals || knn < 3 || knn > 32 || n < knn || n > 0x7FFFFFF0ll / knn || (out_d2 && !out_ids))
+    return LSGPU_BAD_ARG;
+  // centred as lsgpu_icp_set_reference centres the reference: float mean from double sums, one float subtraction
+  double sum[3] = {0.0, 0.0, 0.0};
+  for (int64_t i = 0; i < n; ++i)
+    for (int d = 0; d < 3; ++d) sum[d] += (double)xyz1[4 * i + d];
+  float mean[3];
+  for (int d = 0; d < 3; ++d) mean[d] = (float)(sum[d] / (double)n);
+  std::vector<float> c(3 * (size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    for (int d = 0; d < 3; ++d) c[3 * (size_t)i + d] = xyz1[4 * i + d] - mean[d];
+  std::vector<int32_t> order((size_t)n), pos((size_t)n);
+  std::iota(order.begin(), order.end(), 0);
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return c[3 * (size_t)a] < c[3 * (size_t)b]; });
+  std::vector<float> sx((size_t)n);
+  for (int64_t r = 0; r < n; ++r) { pos[(size_t)order[(size_t)r]] = (int32_t)r; sx[(size_t)r] = c[3 * (size_t)order[(size_t)r]]; }
+  float D[32]; int32_t I[32];
+  for (int64_t i = 0; i < n; ++i) {
+    const float qx = c[3 * (size_t)i], qy = c[3 * (size_t)i + 1], qz = c[3 * (size_t)i + 2];
+    int have = 0;
+    auto offer = [&](int64_t r) {
+      const int32_t t = order[(size_t)r];
+      const float dx = qx - c[3 * (size_t)t], dy = qy - c[3 * (size_t)t + 1], dz = qz - c[3 * (size_t)t + 2];
+      const float d = std::fmaf(dz, dz, std::fmaf(dy, dy, dx * dx));
+      if (have == knn && !(d < D[knn - 1] || (d == D[knn - 1] && t < I[knn - 1]))) return;
+      int s = have < knn ? have++ : knn - 1;
+      for (; s > 0 && (d < D[s - 1] || (d == D[s - 1] && t < I[s - 1])); --s) { D[s] = D[s - 1]; I[s] = I[s - 1]; }
+      D[s] = d; I[s] = t;
+    };
+    int64_t lo = pos[(size_t)i], hi = pos[(size_t)i] + 1;   // [lo, hi) has been offered once `lo` is
+    offer(lo);
+    bool left = lo > 0, right = hi < n;
+    while (left || right) {
+      if (left) {
+        const float dx = qx - sx[(size_t)(lo - 1)];
+        if (have == knn && dx * dx > D[knn - 1]) left = false;
+        else { offer(--lo); left = lo > 0; }
+      }
+      if (right) {
+        const float dx = qx - sx[(size_t)hi];
+        if (have == knn && dx * dx > D[knn - 1]) right = false;
+        else { offer(hi++); right = hi < n; }
+      }
+    }
+    if (out_ids)
+      for (int s = 0; s < knn; ++s) {
+        out_ids[(size_t)i * (size_t)knn + s] = I[s];
+        if (out_d2) out_d2[(size_t)i * (size_t)knn + s] = D[s];
+      }
+    float nv[3];
+    if (!lsgpu::boxnormal::box_normal(knn, [&](int k, int d) { return c[3 * (size_t)I[k] + d]; }, nv)) {
+      nv[0] = 0.f; nv[1] = 1.f; nv[2] = 0.f;   // upstream leaves the eigenvectors at identity: column 1
+    }
+    std::memcpy(out_normals + 3 * i, nv, 12);
+  }
+  return LSGPU_OK;
 }
 
 int lsgpu_check_rigid(const float T[16]) { return std::fabs(1.0f - det3(T)) <= 0.001f; }

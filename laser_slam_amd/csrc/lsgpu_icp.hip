@@ -27,6 +27,7 @@
 #include "lsgpu_policy.h"
 #include "lsgpu_knn.hip.h"
 #include "lsgpu_knn_k.hip.h"
+#include "lsgpu_snf.hip.h"
 #include "lsgpu_cone.hip.h"
 #include "lsgpu_solve.hip.h"
 #include "lsgpu_host_math.h"
@@ -292,6 +293,8 @@ struct lsgpu_icp {
   DevBuf<uint32_t> strag;
   // k-match loop (lsgpu_icp_config.matcher_knn >= 2) and lsgpu_knn_k: k entries per sorted query (lsgpu_knn_k.hip.h)
   DevBuf<float4> kmatch; DevBuf<float> kd2;
+  // SurfaceNormalDataPointsFilter (lsgpu_snf.hip.h): the points its tile kernel hands to the wave-per-point pass
+  DevBuf<uint2> snf_strag; DevBuf<uint32_t> snf_count;
   DevBuf<uint32_t> hist;      // 3 * kHistBins
   DevBuf<SelState> sel;       // [0] input rank, [1] after pass 2, [2] after pass 3
   DevBuf<uint32_t> hist_med;  // MedianDistOutlierFilter: the second run of the select's refining passes (3 * kHistBins, [0] unused) ...
@@ -401,6 +404,15 @@ void lsgpu_chain_config_default(lsgpu_chain_config* c) {  // ICP::setDefault(), 
   c->reading_prob = 0.75f; c->ssn_knn = 7; c->ssn_ratio = 0.5f; c->seed = -1;
 }
 
+int lsgpu_chain_config_check(const lsgpu_chain_config* c, int error_minimizer) {
+  if (!c) return LSGPU_BAD_CONFIG;
+  auto knn_ok = [](int k) { return k == 0 || (k >= 3 && k <= kSsnMaxKnn); };
+  static_assert(kSnfMinKnn == 3 && kSnfMaxKnn == kSsnMaxKnn, "both reference filters take knn 3..32");
+  if (!knn_ok(c->ssn_knn) || !knn_ok(c->sn_knn) || (c->ssn_knn > 0 && c->sn_knn > 0)) return LSGPU_BAD_CONFIG;
+  if (c->ssn_knn == 0 && c->sn_knn == 0 && error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT) return LSGPU_BAD_CONFIG;
+  return LSGPU_OK;
+}
+
 int lsgpu_abi_version(void) { return LSGPU_ABI_VERSION; }
 
 const char* lsgpu_strerror(int code) {
@@ -464,7 +476,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
   h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
-  h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
+  h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->sel.release(); h->ne_partials.release(); h->ne_gpartials.release(); h->ne_tickets.release(); h->ne_out.release(); h->limit_dev.release();
   for (auto& e : h->comm_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : h->knn_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); (void)hipEventDestroy(e.d); (void)hipEventDestroy(e.e); }
@@ -1816,7 +1828,58 @@ static int random_sampling_device(lsgpu_icp* h, const float4* src, int64_t n, fl
   return random_sampling_wait(h, n_out);
 }
 
+// SurfaceNormalDataPointsFilter on the reference the handle holds (set_reference has just been enqueued on h->stream):
+// normals of the sorted points into h->nrm; ids / d2 (device, nullable) in the order the cloud was given.
+template <int K>
+static void launch_snf(lsgpu_icp* h, const SnfArgs& a) {
+  hipLaunchKernelGGL((k_snf_tile<K>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL((k_snf_fallback<K>), dim3((unsigned)std::min((a.n + 63) / 64, 4096)), dim3(64), 0, h->stream, a);   // (strides over the list: usually short)
+}
+static int snf_device(lsgpu_icp* h, int knn, int* ids, float* d2) {
+  const int64_t n = h->nr;
+  if (knn < kSnfMinKnn || knn > kSnfMaxKnn || n < knn) return LSGPU_BAD_ARG;
+  HIPC(h->snf_strag.reserve(n)); HIPC(h->snf_count.reserve(1));
+  HIPC(hipMemsetAsync(h->snf_count.p, 0, sizeof(uint32_t), h->stream));
+  SnfArgs a;
+  a.n = (int)n; a.knn = knn; a.g = h->grid; a.pts = h->pts.p; a.inv = h->ref_inv.p; a.chunks = h->chunks.p;
+  a.nrm = h->nrm.p; a.ids = ids; a.d2 = ids ? d2 : nullptr;
+  a.strag = h->snf_strag.p; a.strag_count = h->snf_count.p; a.r_cap = kSnfRCap;
+  // list lengths: the first knn entries of the next larger list are exact (lsgpu_snf.hip.h)
+  if (knn <= 4) launch_snf<4>(h, a);
+  else if (knn <= 8) launch_snf<8>(h, a);
+  else if (knn <= 16) launch_snf<16>(h, a);
+  else launch_snf<32>(h, a);
+  HIPC(hipGetLastError());
+  return LSGPU_OK;
+}
+
 extern "C" {
+
+int lsgpu_icp_filter_reference_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals,
+                                       int32_t* out_ids, float* out_d2) {
+  if (!h || !out_normals || (out_d2 && !out_ids)) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (knn < kSnfMinKnn || knn > kSnfMaxKnn) { h->err = "filter_reference_normals: knn must be in [3, 32]"; return LSGPU_BAD_ARG; }
+  if (!xyz1 || n < knn) { h->err = "filter_reference_normals: the cloud has fewer points than knn"; return LSGPU_BAD_ARG; }
+  if (n > 0x7FFFFFF0ll / knn) { h->err = "filter_reference_normals: knn x n exceeds the 32-bit pair count"; return LSGPU_BAD_ARG; }
+  int rc = lsgpu_icp_set_reference(h, xyz1, nullptr, n);
+  if (rc) return rc;
+  const int64_t np = (int64_t)knn * n;
+  const bool dev_n = is_device_ptr(out_normals), dev_i = out_ids && is_device_ptr(out_ids), dev_d = out_d2 && is_device_ptr(out_d2);
+  float* on = out_normals; int* oi = out_ids; float* od = out_d2;
+  if (!dev_n) { HIPC(h->flt_nrm.reserve(3 * n)); on = h->flt_nrm.p; }
+  if (out_ids && !dev_i) { HIPC(h->ids_io.reserve(np)); oi = h->ids_io.p; }
+  if (out_ids && !dev_d) { HIPC(h->d2_io.reserve(np)); od = h->d2_io.p; }   // (the kernels write both or neither)
+  rc = snf_device(h, knn, oi, od);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(n)), dim3(256), 0, h->stream, h->pts.p, (int)n, h->nrm.p, on);
+  HIPC(hipGetLastError());
+  if (!dev_n) HIPC(hipMemcpyAsync(out_normals, on, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
+  if (out_ids && !dev_i) HIPC(hipMemcpyAsync(out_ids, oi, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
+  if (out_d2 && !dev_d) HIPC(hipMemcpyAsync(out_d2, od, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  return LSGPU_OK;
+}
 
 int lsgpu_icp_filter_reference(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float ratio,
                                int64_t seed, float* out_xyz1, float* out_normals, int64_t* n_out) {
@@ -1866,10 +1929,9 @@ int lsgpu_icp_filter_reading(lsgpu_icp* h, const float* xyz1, int64_t n, float p
   return LSGPU_OK;
 }
 
-// ssn_knn in [3, kSsnMaxKnn]; or 0 (no reference filter module) on a point-to-point handle, which needs no normals
+// one reference filter module, knn in [3, 32]; or none on a point-to-point handle, which needs no normals
 static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain) {
-  if (chain->ssn_knn == 0) return h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
-  return chain->ssn_knn >= 3 && chain->ssn_knn <= kSsnMaxKnn;
+  return lsgpu_chain_config_check(chain, h->cfg.error_minimizer) == LSGPU_OK;
 }
 
 int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1,
@@ -1880,13 +1942,17 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   std::memcpy(T_out, T_init, 16 * sizeof(float));
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (!chain_ok(h, chain)) {
-    h->err = "compute: ssn_knn must be in [3, 32] (0, no reference filter, only with the point-to-point minimizer)";
+    h->err = "compute: one reference filter, ssn_knn or sn_knn in [3, 32] (none only with the point-to-point minimizer)";
     return LSGPU_BAD_CONFIG;
   }
   const bool ref_filter = chain->ssn_knn != 0;
+  // SurfaceNormalDataPointsFilter keeps every point and draws nothing: the reference goes to set_reference as given and
+  // the normals are computed on the grid it builds (a point-to-point handle reads none: skipped)
+  const bool ref_normals = chain->sn_knn != 0 && h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT;
   if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
   if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
   if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
+  if (nr < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
   HIPC(hipSetDevice(h->device));
   const double t0 = wall_ms();
   // the draws of both filters, produced on a helper thread from now on: at most one per reference point, then one per
@@ -2048,6 +2114,10 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   h->hook_before_ref_sync = nullptr; h->hook_after_grid = nullptr;
   h->defer_cone = false;
   if (rc) return rc;
+  if (ref_normals) {
+    rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
+    if (rc) return rc;
+  }
   if (side) {
     // the direction index of the reference is not needed before the loop's third search: lsgpu_icp_align enqueues its
     // build on the side stream (behind the queries' order, with that stream's sort scratch) once the loop's first

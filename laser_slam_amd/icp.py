@@ -196,6 +196,32 @@ class IcpHandle:
             _raise(rc, "lsgpu_icp_filter_reference", self._h)
         return o[:m.value], nr[:m.value]
 
+    def filter_reference_normals(self, xyz1, knn: int = 5, with_neighbours: bool = False):
+        """SurfaceNormalDataPointsFilter on the GPU: every point keeps its place and gets the PCA normal of its knn
+        nearest neighbours, itself included (include/lsgpu_icp.h has the contract) -> normals (n, 3), or
+        (normals, ids (n, knn) int32, d2 (n, knn)) with `with_neighbours`.  torch CUDA input gives torch CUDA output,
+        anything else numpy.  The cloud becomes the handle's reference, with these normals."""
+        p, _k, n = _as_f32(xyz1, 4)
+        knn = int(knn)
+        if not 3 <= knn <= 32:                                   # (before any output is sized with it)
+            raise LsgpuError(_lib.BAD_ARG, "lsgpu_icp_filter_reference_normals", "knn must be in [3, 32]")
+        dev = _is_torch(xyz1) and xyz1.is_cuda
+        if dev:
+            nr = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xyz1.device)
+            ids = torch.empty((max(n, 1), knn), dtype=torch.int32, device=xyz1.device) if with_neighbours else None
+            d2 = torch.empty((max(n, 1), knn), dtype=torch.float32, device=xyz1.device) if with_neighbours else None
+            torch.cuda.synchronize()
+            pn, pi, pd = nr.data_ptr(), (ids.data_ptr() if with_neighbours else None), (d2.data_ptr() if with_neighbours else None)
+        else:
+            nr = np.empty((max(n, 1), 3), np.float32)
+            ids = np.empty((max(n, 1), knn), np.int32) if with_neighbours else None
+            d2 = np.empty((max(n, 1), knn), np.float32) if with_neighbours else None
+            pn, pi, pd = nr.ctypes.data, (ids.ctypes.data if with_neighbours else None), (d2.ctypes.data if with_neighbours else None)
+        rc = _lib.lib().lsgpu_icp_filter_reference_normals(self._h, p, n, int(knn), pn, pi, pd)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_filter_reference_normals", self._h)
+        return (nr[:n], ids[:n], d2[:n]) if with_neighbours else nr[:n]
+
     def filter_reading(self, xyz1, prob: float = 0.5, seed: int = -1):
         """RandomSamplingDataPointsFilter (icp_default.yaml:1-3) on the GPU -> xyz1'."""
         p, _k, n = _as_f32(xyz1, 4)
@@ -213,12 +239,13 @@ class IcpHandle:
         return o[:m.value]
 
     def compute(self, reading_xyz1, reference_xyz1, T_init, reading_prob: float = 0.5, ssn_knn: int = 10,
-                ssn_ratio: float = 0.5, seed: int = -1):
+                ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0):
         """``icp_.compute(reading, reference, T_init)`` entirely on the device: reference filter,
-        set_reference, reading filter, align.  -> (T 4x4, IcpStats); raises ConvergenceError."""
+        set_reference, reading filter, align.  -> (T 4x4, IcpStats); raises ConvergenceError.
+        sn_knn > 0 (with ssn_knn 0): SurfaceNormalDataPointsFilter is the reference filter."""
         q, _k1, nq = _as_f32(reading_xyz1, 4)
         r, _k2, nr = _as_f32(reference_xyz1, 4)
-        ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, 0, seed)
+        ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, int(sn_knn), seed)
         ti = _t16(T_init)
         to = np.empty(16, np.float32)
         st = IcpStats()
@@ -320,14 +347,14 @@ class IcpHandle:
         return n.value
 
     def compute_clouds(self, reading_slot: int, ref_slots, ref_T, T_init, reading_prob: float = 0.5,
-                       ssn_knn: int = 10, ssn_ratio: float = 0.5, seed: int = -1):
+                       ssn_knn: int = 10, ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0):
         """ICP::compute with reading = cloud `reading_slot` and reference = concat(T_i * cloud ref_slots[i])."""
         k = len(ref_slots)
         slots = (C.c_int * max(k, 1))(*ref_slots)
         Ts = None
         if ref_T is not None:
             Ts = np.concatenate([_t16(T) for T in ref_T]) if k else np.zeros(0, np.float32)
-        ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, 0, seed)
+        ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, int(sn_knn), seed)
         ti = _t16(T_init)
         to = np.empty(16, np.float32)
         st = IcpStats()
@@ -338,7 +365,7 @@ class IcpHandle:
         return to.reshape(4, 4).T.copy(), st
 
     def compute_clouds_upload(self, reading_slot: int, reading_xyz1, ref_slots, ref_T, T_init, reading_prob: float = 0.5,
-                              ssn_knn: int = 10, ssn_ratio: float = 0.5, seed: int = -1):
+                              ssn_knn: int = 10, ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0):
         """upload_cloud(reading_slot, reading) + compute_clouds(reading_slot, ...) in one call: the host reading crosses
         PCIe while the sub-map is assembled and filtered (the call shape of LaserTrack::localScanToSubMap)."""
         rd = np.ascontiguousarray(reading_xyz1, np.float32)
@@ -347,7 +374,7 @@ class IcpHandle:
         Ts = None
         if ref_T is not None:
             Ts = np.concatenate([_t16(T) for T in ref_T]) if k else np.zeros(0, np.float32)
-        ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, 0, seed)
+        ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, int(sn_knn), seed)
         ti = _t16(T_init)
         to = np.empty(16, np.float32)
         st = IcpStats()
@@ -525,6 +552,27 @@ def sampling_surface_normal(xyz1, knn: int = 10, ratio: float = 0.5, seed: int =
     return o[:m].copy(), nr[:m].copy()
 
 
+def surface_normal(xyz1, knn: int = 5, with_neighbours: bool = False):
+    """SurfaceNormalDataPointsFilter on the host (lsgpu_filter_surface_normal; the device filter's checker, bit for bit)
+    -> normals (n, 3), or (normals, ids (n, knn), d2 (n, knn)) with `with_neighbours`."""
+    a = np.ascontiguousarray(xyz1, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"expected (N,4) array, got {a.shape}")
+    n = a.shape[0]
+    knn = int(knn)
+    if not 3 <= knn <= 32:
+        raise LsgpuError(_lib.BAD_ARG, "lsgpu_filter_surface_normal", "knn must be in [3, 32]")
+    nr = np.empty((max(n, 1), 3), np.float32)
+    ids = np.empty((max(n, 1), max(knn, 1)), np.int32) if with_neighbours else None
+    d2 = np.empty((max(n, 1), max(knn, 1)), np.float32) if with_neighbours else None
+    rc = _lib.lib().lsgpu_filter_surface_normal(a.ctypes.data if n else None, n, int(knn), nr.ctypes.data,
+                                                ids.ctypes.data if with_neighbours else None,
+                                                d2.ctypes.data if with_neighbours else None)
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_filter_surface_normal")
+    return (nr[:n], ids[:n], d2[:n]) if with_neighbours else nr[:n]
+
+
 def point_to_point_solve(sums) -> np.ndarray:
     """lsgpu_point_to_point_solve: the point-to-point step dT (4x4 float32) from the 29 sums of
     IcpHandle.point_to_point -- host only, the same function the device loop runs.  Raises ConvergenceError for
@@ -558,7 +606,7 @@ def correct_rigid(T) -> np.ndarray:
 
 _SUPPORTED = {
     "readingDataPointsFilters": {"RandomSamplingDataPointsFilter"},
-    "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter"},
+    "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter", "SurfaceNormalDataPointsFilter"},
     "matcher": {"KDTreeMatcher"},
     "outlierFilters": {"TrimmedDistOutlierFilter", "MaxDistOutlierFilter", "MinDistOutlierFilter",
                        "MedianDistOutlierFilter"},
@@ -576,6 +624,7 @@ class ChainConfig:
     reading_sampling_prob: float = 0.5      # yaml:3   (module default 0.75)
     surface_normal_knn: int = 10            # yaml:7   (module default 7); 0: no reference filter (point-to-point only)
     surface_normal_ratio: float = 0.5       # module default
+    reference_normal_knn: int = 0           # SurfaceNormalDataPointsFilter knn (module default 5) as the reference filter; 0: absent
     trim_ratio: float = 0.75                # yaml:16  (module default 0.85)
     max_iterations: int = 40                # yaml:23
     min_diff_rot: float = 0.001             # yaml:25
@@ -675,6 +724,26 @@ class ICP:
                     ch.surface_normal_ratio = float(params.get("ratio", 0.5))
                     if int(params.get("samplingMethod", 0)) != 0:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "samplingMethod != 0")
+                elif name == "SurfaceNormalDataPointsFilter":
+                    # every point, the normal of its knn nearest neighbours: what the device filter computes is
+                    # keepNormals 1 alone, exact (epsilon 0), unbounded (no maxDist)
+                    only(name, params, "knn", "epsilon", "maxDist", "keepNormals", "keepDensities", "keepEigenValues",
+                         "keepEigenVectors", "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals")
+                    kf = one_float(name, params, "knn", 5)
+                    if not 3 <= kf <= 32 or kf != int(kf):
+                        bad(f"{name}: knn must be an integer in [3, 32] (got {params.get('knn')})")
+                    knn = int(kf)
+                    if one_float(name, params, "epsilon", 0.0) != 0.0:
+                        bad(f"{name}: epsilon must be 0 (the search is exact)")
+                    if not math.isinf(one_float(name, params, "maxDist", math.inf)) or one_float(name, params, "maxDist", math.inf) < 0:
+                        bad(f"{name}: maxDist must be absent or inf")
+                    if one_float(name, params, "keepNormals", 1) != 1:
+                        bad(f"{name}: keepNormals must be 1 (the module is there for the normals)")
+                    for key in ("keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
+                                "sortEigen", "smoothNormals"):
+                        if one_float(name, params, key, 0) != 0:
+                            bad(f"{name}: {key} must be 0 or absent")
+                    ch.reference_normal_knn = knn
                 elif name == "KDTreeMatcher":
                     # (its other parameters -- searchType, ... -- are not read)
                     md = one_float(name, params, "maxDist", math.inf)
@@ -722,13 +791,21 @@ class ICP:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "readingStepDataPointsFilters")
         # the point-to-point minimizer reads no normals: without a reference filter module the reference is used as given
         p2p = ch.error_minimizer == "PointToPointErrorMinimizer"
-        if p2p and "SamplingSurfaceNormalDataPointsFilter" not in seen:
+        if len(modules("referenceDataPointsFilters")) > 1:
+            bad("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or "
+                "SurfaceNormalDataPointsFilter)")
+        if "SurfaceNormalDataPointsFilter" in seen or "SamplingSurfaceNormalDataPointsFilter" in seen:
+            seen.add("reference normals")                       # either filter provides them
+        if "SamplingSurfaceNormalDataPointsFilter" not in seen:
             ch.surface_normal_knn = 0
-        for need, why in (("SamplingSurfaceNormalDataPointsFilter", "it provides the normals of the point-to-plane minimizer"),
+        labels = {"reference normals": "referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or "
+                                       "SurfaceNormalDataPointsFilter",
+                  "minimizer": "errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer"}
+        for need, why in (("reference normals", "it provides the normals of the point-to-plane minimizer"),
                           ("KDTreeMatcher", "the matcher"), ("minimizer", "the error minimizer"),
                           ("CounterTransformationChecker", "the loop would not stop")):
-            if need not in seen and not (p2p and need == "SamplingSurfaceNormalDataPointsFilter"):
-                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{need} is required ({why})")
+            if need not in seen and not (p2p and need == "reference normals"):
+                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{labels.get(need, need)} is required ({why})")
         # inspector / logger (yaml:32-44) only produce debug dumps: accepted and ignored
         self.chain = ch
         self._handle = None
@@ -753,6 +830,6 @@ class ICP:
         h = self._ensure_handle()
         ch = self.chain
         T, st = h.compute(reading_xyz1, reference_xyz1, T_init, ch.reading_sampling_prob,
-                          ch.surface_normal_knn, ch.surface_normal_ratio, ch.seed)
+                          ch.surface_normal_knn, ch.surface_normal_ratio, ch.seed, ch.reference_normal_knn)
         self.last_stats = st
         return T
