@@ -28,7 +28,7 @@
  * (lsgpu_icp_config.error_minimizer), KDTreeMatcher with knn 1..LSGPU_MATCHER_KNN_MAX (lsgpu_icp_config.matcher_knn) and
  * maxDist (matcher_max_dist), any subset of Trimmed- / Max- / Min- / MedianDistOutlierFilter (outlier_*), and
  * SurfaceNormalDataPointsFilter in place of SamplingSurfaceNormalDataPointsFilter as the reference filter
- * (lsgpu_chain_config.sn_knn).
+ * (lsgpu_chain_config.sn_knn), and RobustOutlierFilter (lsgpu_icp_set_robust_filter).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -447,6 +447,66 @@ void lsgpu_correct_rigid(const float T[16], float out[16]);
  * Quaternion(R_a).angularDistance(Quaternion(R_b)) = 2 atan2(|vec|, |w|) of q_a * conj(q_b), in float -- the same code
  * the device-side checker runs (csrc/lsgpu_host_math.h). */
 float lsgpu_rotation_distance(const float Ta[16], const float Tb[16]);
+
+/* ---- RobustOutlierFilter: M-estimator weights with a MAD scale (DESIGN.md §3 "RobustOutlierFilter", §5 choices 18-23) ----
+ * The one outlier filter whose weights are real numbers.  Per iteration, over the matches every other outlier filter sees:
+ *   scale     none: 1.  mad: over the m valid (finite) squared match distances d2, med = sorted(d2)[m / 2],
+ *             mad = sorted(|d2 - med|)[m / 2] (float), scale = sqrtf(mad); recomputed in iteration it (1-based, restarted by
+ *             every align) iff nb_iteration_for_scale == 0 || it <= nb_iteration_for_scale, else the last scale is kept.
+ *             Always the matcher's point-to-point d2.  No valid match or scale == 0: LSGPU_NO_CONVERGENCE, T_out = T_init.
+ *   distance  point2point: e = d2.  point2plane: e = r r, r = n . (p - q) as the point-to-plane pass computes it (float).
+ *   weight    e2 = e / (scale scale), k = tuning, k2 = k k, float, one operation per rounding:
+ *             cauchy 1 / (1 + e2 / k2)   huber e2 < k2 ? 1 : k / sqrtf(e2)   tukey e2 < k2 ? (1 - e2 / k2)^2 : 0
+ *             gm k2 / (k + e2)^2   sc e2 > k ? 4 k2 / (k + e2)^2 : 1   L1 1 / sqrtf(e2);
+ *             approximation finite: w = 0 where e2 >= approximation^2.  A non-finite weight: LSGPU_NO_CONVERGENCE.
+ *   The weights of all outlier filters multiply; a pair with weight 0 or an invalid match is not used; n_used counts the pairs
+ *   with w > 0; limit stays the binary filters' effective upper limit (+inf with none).  Point-to-plane: A = sum w J J^T,
+ *   b = -sum w J r.  Point-to-point: sum w p, sum w q, sum w q p^T; slot 27 = sum w, slot 28 = sum w e^2 -- in the sums of
+ *   lsgpu_normal_eq / lsgpu_point_to_point as well (their scale: the MAD of the d2 they are given, or 1).
+ *   With matcher_knn = k >= 2 every pair is weighted on its own.  A handle with the filter takes the chain plan
+ *   (csrc/lsgpu_policy.h); lsgpu_icp_comm_init refuses it.  welsch / student and the berg / std scale estimators are
+ *   LSGPU_BAD_CONFIG (exp / pow cannot be made bit-identical between host and device). */
+enum { LSGPU_ROBUST_CAUCHY = 0, LSGPU_ROBUST_HUBER = 1, LSGPU_ROBUST_TUKEY = 2, LSGPU_ROBUST_GM = 3, LSGPU_ROBUST_SC = 4,
+       LSGPU_ROBUST_L1 = 5, LSGPU_ROBUST_WELSCH = 6 /* refused */, LSGPU_ROBUST_STUDENT = 7 /* refused */ };
+enum { LSGPU_ROBUST_SCALE_NONE = 0, LSGPU_ROBUST_SCALE_MAD = 1, LSGPU_ROBUST_SCALE_BERG = 2 /* refused */,
+       LSGPU_ROBUST_SCALE_STD = 3 /* refused */ };
+enum { LSGPU_ROBUST_DIST_POINT2POINT = 0, LSGPU_ROBUST_DIST_POINT2PLANE = 1 };
+typedef struct lsgpu_robust_config {
+  int   robust_fct;              /* LSGPU_ROBUST_*            robustFct            (cauchy)      */
+  float tuning;                  /*                           tuning               (1.0)         */
+  int   scale_estimator;         /* LSGPU_ROBUST_SCALE_*      scaleEstimator       (mad)         */
+  int   nb_iteration_for_scale;  /*                           nbIterationForScale  (0: always)   */
+  int   distance_type;           /* LSGPU_ROBUST_DIST_*       distanceType         (point2point) */
+  float approximation;           /*                           approximation        (+inf: none)  */
+  int   reserved[2];             /* 0 */
+} lsgpu_robust_config;
+void lsgpu_robust_config_default(lsgpu_robust_config* c);   /* the module's defaults */
+/* What lsgpu_icp_set_robust_filter accepts, without a handle or a device: LSGPU_OK, or LSGPU_BAD_CONFIG for a refused or
+ * unknown value, a negative or NaN tuning / approximation, a negative nb_iteration_for_scale, or point2plane on a
+ * point-to-point handle (error_minimizer: LSGPU_MINIMIZER_*) whose reference has no normals (have_normals 0). */
+int lsgpu_robust_config_check(const lsgpu_robust_config* c, int error_minimizer, int have_normals);
+/* Gives the handle the filter (cfg is copied), NULL removes it.  Bad values: LSGPU_BAD_CONFIG before the device is touched
+ * (the handle keeps what it had).  point2plane on a point-to-point handle is checked again by align, which knows whether
+ * set_reference was given normals. */
+int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg);
+/* Host twins (no GPU, no handle), bit-identical with the device loop.  lsgpu_robust_scale: median and MAD scale of the finite
+ * entries of d2 (+inf = invalid match); LSGPU_NO_CONVERGENCE if there is none.  lsgpu_robust_weights: w_out[i] of e[i]
+ * (d2, or r r for point2plane) under cfg's function, tuning and approximation with the given scale. */
+int lsgpu_robust_scale(const float* d2, int64_t n, float* median, float* scale);
+int lsgpu_robust_weights(const lsgpu_robust_config* cfg, float scale, const float* e, int64_t n, float* w_out);
+/* One record per iteration of the last align of a handle with the filter; returns the number written. */
+typedef struct lsgpu_robust_trace {
+  float  median;       /* of the valid d2 when the scale was last computed (0 with none)       */
+  float  scale;        /* the scale the iteration's weights used                                */
+  double w_sum;        /* sum of the weights of the used pairs (slot 27)                        */
+  int    recomputed;   /* 1: the scale was computed in this iteration                           */
+  int    reserved;
+} lsgpu_robust_trace;
+int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap);
+/* The point-to-plane step from the 27 sums of lsgpu_normal_eq (21 upper-tri of A, 6 of b): dT (4x4 float, column major).
+ * Host only; the same function the device loop runs, bit for bit -- the sibling of lsgpu_point_to_point_solve.
+ * LSGPU_NO_CONVERGENCE if A is not positive definite. */
+int lsgpu_point_to_plane_solve(const double sums[27], float dT[16]);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

@@ -98,8 +98,15 @@ class LsgpuICP {
   // x,y,z,1 per point and TransformationParameters is a 4x4 column-major float matrix: both are passed as they are.
   TransformationParameters compute(const DataPoints& reading, const DataPoints& reference,
                                    const TransformationParameters& T_init) {
-    if (!h_ && lsgpu_icp_create(&cfg_, device_, &h_) != LSGPU_OK)
-      throw std::runtime_error("LsgpuICP: lsgpu_icp_create failed (no ROCm GPU visible?)");
+    if (!h_) {
+      if (lsgpu_icp_create(&cfg_, device_, &h_) != LSGPU_OK)
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_create failed (no ROCm GPU visible?)");
+      if (has_robust_ && lsgpu_icp_set_robust_filter(h_, &robust_) != LSGPU_OK) {   // RobustOutlierFilter of the loaded chain
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_robust_filter: " + why);
+      }
+    }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
     chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
@@ -117,6 +124,8 @@ class LsgpuICP {
     cfg_ = parsed.config();
     prob_ = parsed.readingSamplingProb(); knn_ = parsed.surfaceNormalKnn(); ratio_ = parsed.surfaceNormalRatio();
     sn_knn_ = parsed.referenceNormalKnn();
+    has_robust_ = parsed.robustFilter() != nullptr;
+    if (has_robust_) robust_ = *parsed.robustFilter();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -127,6 +136,8 @@ class LsgpuICP {
   float prob_ = 0.75f, ratio_ = 0.5f;
   int knn_ = 7;
   int sn_knn_ = 0;                                      // SurfaceNormalDataPointsFilter as the reference filter (0: absent)
+  lsgpu_robust_config robust_{};                        // RobustOutlierFilter's parameters ...
+  bool has_robust_ = false;                             // ... if the chain holds one
   int64_t seed_ = -1;
 };
 

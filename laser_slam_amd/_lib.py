@@ -34,7 +34,28 @@ ABI_SYMBOLS = [
     "lsgpu_strerror", "lsgpu_last_error", "lsgpu_abi_version", "lsgpu_apply_point_filters",
     "lsgpu_cloud_from_pointcloud2", "lsgpu_cloud_to_pointxyz",
     "lsgpu_icp_filter_reference_normals", "lsgpu_filter_surface_normal", "lsgpu_chain_config_check",
+    "lsgpu_robust_config_default", "lsgpu_robust_config_check", "lsgpu_icp_set_robust_filter", "lsgpu_robust_scale",
+    "lsgpu_robust_weights", "lsgpu_icp_get_robust_trace", "lsgpu_point_to_plane_solve",
 ]
+
+# lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
+ROBUST_FCT = {"cauchy": 0, "huber": 1, "tukey": 2, "gm": 3, "sc": 4, "L1": 5, "welsch": 6, "student": 7}
+ROBUST_SCALE = {"none": 0, "mad": 1, "berg": 2, "std": 3}
+ROBUST_DIST = {"point2point": 0, "point2plane": 1}
+
+
+class RobustCfg(C.Structure):
+    """lsgpu_robust_config (include/lsgpu_icp.h): RobustOutlierFilter's parameters."""
+    _fields_ = [("robust_fct", C.c_int), ("tuning", C.c_float), ("scale_estimator", C.c_int),
+                ("nb_iteration_for_scale", C.c_int), ("distance_type", C.c_int), ("approximation", C.c_float),
+                ("reserved", C.c_int * 2)]
+
+
+class RobustTrace(C.Structure):
+    """lsgpu_robust_trace: one record per iteration of a handle with RobustOutlierFilter."""
+    _fields_ = [("median", C.c_float), ("scale", C.c_float), ("w_sum", C.c_double), ("recomputed", C.c_int),
+                ("reserved", C.c_int)]
+
 
 
 class ChainCfg(C.Structure):
@@ -232,6 +253,14 @@ def lib() -> C.CDLL:
     L.lsgpu_last_error.argtypes = [vp]
     L.lsgpu_last_error.restype = C.c_char_p
     L.lsgpu_abi_version.restype = C.c_int
+    L.lsgpu_robust_config_default.argtypes = [C.POINTER(RobustCfg)]
+    L.lsgpu_robust_config_default.restype = None
+    L.lsgpu_robust_config_check.argtypes = [C.POINTER(RobustCfg), C.c_int, C.c_int]
+    L.lsgpu_icp_set_robust_filter.argtypes = [vp, C.POINTER(RobustCfg)]
+    L.lsgpu_robust_scale.argtypes = [fp, i64, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.lsgpu_robust_weights.argtypes = [C.POINTER(RobustCfg), C.c_float, fp, i64, fp]
+    L.lsgpu_icp_get_robust_trace.argtypes = [vp, C.POINTER(RobustTrace), C.c_int]
+    L.lsgpu_point_to_plane_solve.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_float)]
     _lib = L
     return L
 

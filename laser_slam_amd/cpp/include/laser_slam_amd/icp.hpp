@@ -248,15 +248,16 @@ class ICP {
   // PointToPlane / Counter 40 + Differential 1e-3, 1e-3, 3
   void setDefault() {
     lsgpu_icp_config_default(&cfg_);
-    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f; sn_knn_ = 0;
+    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f; sn_knn_ = 0; has_robust_ = false;
     release();
   }
 
   // Accepts the module chain of laser_slam/configurations/icp_default.yaml, with PointToPlaneErrorMinimizer or
   // PointToPointErrorMinimizer, KDTreeMatcher knn 1..LSGPU_MATCHER_KNN_MAX (epsilon 0) with maxDist, and any subset of
   // Trimmed- / Max- / Min- / MedianDistOutlierFilter (each at most once, any order), and SurfaceNormalDataPointsFilter in
-  // place of SamplingSurfaceNormalDataPointsFilter as THE reference filter; any other module is a configuration error
-  // (PointMatcher's registrar throws on unknown names as well).
+  // place of SamplingSurfaceNormalDataPointsFilter as THE reference filter, and one RobustOutlierFilter (cauchy, huber,
+  // tukey, gm, sc, L1 with scaleEstimator none / mad); any other module is a configuration error (PointMatcher's registrar
+  // throws on unknown names as well).
   void loadFromYaml(std::istream& in) {
     lsgpu_icp_config c;
     lsgpu_icp_config_default(&c);
@@ -268,7 +269,10 @@ class ICP {
     // not expressible for the reference filter: the normals come from it); the modules the device loop cannot run
     // without are required.
     bool has_reading = false, has_reference = false, has_matcher = false, has_outlier = false, has_minimizer = false,
-         has_counter = false, has_differential = false, has_max = false, has_min = false, has_median = false;
+         has_counter = false, has_differential = false, has_max = false, has_min = false, has_median = false,
+         has_robust = false;
+    lsgpu_robust_config rb;
+    lsgpu_robust_config_default(&rb);
     prob = -1.0f;   // no reading filter module: lsgpu_chain_config::reading_prob < 0 (every point, no draws)
     c.trim_ratio = 1.0f;
     for (const auto& m : mods) {
@@ -358,6 +362,32 @@ class ICP {
         const double f = fnum(name, "factor", 3.0);
         if (!(f > 0.0) || std::isinf(f)) throw ConfigError("MedianDistOutlierFilter: factor must be > 0 and finite");
         has_median = true; c.outlier_median_factor = (float)f;
+      } else if (sec == "outlierFilters" && name == "RobustOutlierFilter") {
+        if (has_robust) throw ConfigError("outlierFilters: one RobustOutlierFilter at most");
+        only(name, {"robustFct", "tuning", "scaleEstimator", "nbIterationForScale", "distanceType", "approximation"});
+        auto word = [&](const char* key, const char* def) {
+          auto it = m.params.find(key);
+          return it == m.params.end() ? std::string(def) : it->second;
+        };
+        auto pick = [&](const char* key, const std::string& v, std::initializer_list<const char*> names) {
+          int i = 0;
+          for (const char* n : names) { if (v == n) return i; ++i; }
+          throw ConfigError(name + ": unknown " + key + " " + v);
+        };
+        const std::string fct = word("robustFct", "cauchy"), est = word("scaleEstimator", "mad");
+        if (fct == "welsch" || fct == "student")
+          throw ConfigError(name + ": robustFct " + fct + " is not implemented on the HIP path (exp / pow are not bit-identical between host and device)");
+        if (est == "berg" || est == "std")
+          throw ConfigError(name + ": scaleEstimator " + est + " is not implemented on the HIP path (none and mad are)");
+        rb.robust_fct = pick("robustFct", fct, {"cauchy", "huber", "tukey", "gm", "sc", "L1"});
+        rb.scale_estimator = pick("scaleEstimator", est, {"none", "mad"});
+        rb.distance_type = pick("distanceType", word("distanceType", "point2point"), {"point2point", "point2plane"});
+        const double k = fnum(name, "tuning", 1.0), ap = fnum(name, "approximation", INFINITY), nb = fnum(name, "nbIterationForScale", 0);
+        if (!(k >= 0.0)) throw ConfigError(name + ": tuning must be >= 0");
+        if (!(ap >= 0.0)) throw ConfigError(name + ": approximation must be >= 0");
+        if (!(nb >= 0.0) || nb != (double)(int)nb) throw ConfigError(name + ": nbIterationForScale must be an integer >= 0");
+        rb.tuning = (float)k; rb.approximation = (float)ap; rb.nb_iteration_for_scale = (int)nb;
+        has_robust = true;
       } else if (sec == "errorMinimizer" && (name == "PointToPlaneErrorMinimizer" || name == "PointToPointErrorMinimizer")) {
         if (has_minimizer) throw ConfigError("errorMinimizer: one module at most");
         has_minimizer = true;
@@ -381,9 +411,13 @@ class ICP {
     if (!has_reference && c.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
       throw ConfigError("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter is required (it provides the normals of PointToPlaneErrorMinimizer)");
     if (!has_reference || sn_knn > 0) knn = 0;
+    if (has_robust && lsgpu_robust_config_check(&rb, c.error_minimizer, has_reference ? 1 : 0) != LSGPU_OK)
+      throw ConfigError(rb.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE && !has_reference
+                            ? "RobustOutlierFilter: distanceType point2plane needs reference normals (a referenceDataPointsFilters module)"
+                            : "RobustOutlierFilter: refused configuration");
     if (!has_counter) throw ConfigError("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
     if (!has_differential) { c.min_diff_rot = -1.f; c.min_diff_trans = -1.f; c.smooth_length = 1; }  // never satisfied: the counter stops
-    cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio; sn_knn_ = sn_knn;
+    cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio; sn_knn_ = sn_knn; robust_ = rb; has_robust_ = has_robust;
     release();
   }
 
@@ -539,6 +573,7 @@ class ICP {
   int surfaceNormalKnn() const { return knn_; }            // SamplingSurfaceNormalDataPointsFilter's knn (0: no such module)
   int referenceNormalKnn() const { return sn_knn_; }       // SurfaceNormalDataPointsFilter's knn (0: no such module)
   float surfaceNormalRatio() const { return ratio_; }
+  const lsgpu_robust_config* robustFilter() const { return has_robust_ ? &robust_ : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
 
  private:
   using Module = detail::YamlModule;
@@ -588,6 +623,11 @@ class ICP {
     const int rc = lsgpu_icp_create(&cfg_, device_, &h_);
     if (rc == LSGPU_BAD_CONFIG) throw ConfigError("lsgpu_icp_create: bad configuration");
     if (rc != LSGPU_OK) throw DeviceError("lsgpu_icp_create failed (no ROCm GPU visible?)");
+    if (has_robust_ && lsgpu_icp_set_robust_filter(h_, &robust_) != LSGPU_OK) {
+      const std::string msg = std::string("lsgpu_icp_set_robust_filter: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
   }
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
   void check(int rc, const char* what) {
@@ -605,6 +645,8 @@ class ICP {
   float prob_ = 0.75f, ratio_ = 0.5f;
   int knn_ = 7;
   int sn_knn_ = 0;
+  lsgpu_robust_config robust_{};
+  bool has_robust_ = false;
   int64_t seed_ = -1;
   unsigned generation_ = 0;
 #ifdef LSGPU_TEST_SEAMS

@@ -19,6 +19,7 @@
 
 #include "../../include/lsgpu_icp.h"
 #include "lsgpu_box_normal.h"
+#include "lsgpu_robust.h"
 #include "lsgpu_rand.h"
 
 namespace {
@@ -223,6 +224,56 @@ int lsgpu_point_to_point_solve(const double sums[29], float T_out[16]) {
     lsgpu::hostmath::identity4(T_out);
     return LSGPU_NO_CONVERGENCE;
   }
+  return LSGPU_OK;
+}
+
+int lsgpu_point_to_plane_solve(const double sums[27], float dT[16]) {
+  if (!sums || !dT) return LSGPU_BAD_ARG;
+  double A[36], b[6];
+  float x[6];
+  lsgpu::hostmath::unpack_normal_eq(sums, A, b);
+  if (!lsgpu::hostmath::llt_solve6(A, b, x)) {
+    lsgpu::hostmath::identity4(dT);
+    return LSGPU_NO_CONVERGENCE;
+  }
+  lsgpu::hostmath::delta_from_x(x, dT);
+  return LSGPU_OK;
+}
+
+// ---- RobustOutlierFilter: the host twins of the device loop's scale and weights (csrc/lsgpu_robust.h)
+void lsgpu_robust_config_default(lsgpu_robust_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->robust_fct = LSGPU_ROBUST_CAUCHY; c->tuning = 1.f; c->scale_estimator = LSGPU_ROBUST_SCALE_MAD;
+  c->nb_iteration_for_scale = 0; c->distance_type = LSGPU_ROBUST_DIST_POINT2POINT; c->approximation = INFINITY;
+}
+
+int lsgpu_robust_config_check(const lsgpu_robust_config* c, int error_minimizer, int have_normals) {
+  return lsgpu::robust::check(c, error_minimizer, have_normals, nullptr);
+}
+
+int lsgpu_robust_scale(const float* d2, int64_t n, float* median, float* scale) {
+  if (!d2 || n < 0 || !median || !scale) return LSGPU_BAD_ARG;
+  std::vector<float> v;
+  v.reserve((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    if (std::isfinite(d2[i])) v.push_back(d2[i]);
+  if (v.empty()) return LSGPU_NO_CONVERGENCE;
+  const size_t mid = v.size() / 2;
+  std::nth_element(v.begin(), v.begin() + (std::ptrdiff_t)mid, v.end());
+  const float med = v[mid];
+  for (float& x : v) x = std::fabs(x - med);
+  std::nth_element(v.begin(), v.begin() + (std::ptrdiff_t)mid, v.end());
+  *median = med;
+  *scale = sqrtf(v[mid]);
+  return LSGPU_OK;
+}
+
+int lsgpu_robust_weights(const lsgpu_robust_config* cfg, float scale, const float* e, int64_t n, float* w_out) {
+  if (!cfg || n < 0 || (n > 0 && (!e || !w_out))) return LSGPU_BAD_ARG;
+  if (lsgpu::robust::check(cfg, LSGPU_MINIMIZER_POINT_TO_PLANE, 1, nullptr) != LSGPU_OK) return LSGPU_BAD_CONFIG;
+  const lsgpu::robust::Params p = lsgpu::robust::params(*cfg);
+  for (int64_t i = 0; i < n; ++i) w_out[i] = lsgpu::robust::weight(p.fct, e[i], scale, p.k, p.approx2);
   return LSGPU_OK;
 }
 

@@ -299,6 +299,12 @@ struct lsgpu_icp {
   DevBuf<SelState> sel;       // [0] input rank, [1] after pass 2, [2] after pass 3
   DevBuf<uint32_t> hist_med;  // MedianDistOutlierFilter: the second run of the select's refining passes (3 * kHistBins, [0] unused) ...
   DevBuf<SelState> sel_med;   // ... and its three states
+  // RobustOutlierFilter (lsgpu_icp_set_robust_filter): the MAD's select over |d2 - median|, the loop's robust state, its trace
+  bool robust_on = false;
+  lsgpu_robust_config robust{};
+  bool have_normals = false;  // the last set_reference was given normals (or a reference filter computed them)
+  DevBuf<uint32_t> rb_hist; DevBuf<SelState> rb_sel; DevBuf<RobustState> rb_state; DevBuf<lsgpu_robust_trace> rb_trace_dev;
+  size_t rb_trace_n = 0;      // records of the last alignment in rb_trace_dev
   DevBuf<double> ne_partials; // kNeBlocks * 32
   DevBuf<double> ne_gpartials;  // (kNeBlocksMax / kNeGroup) * 32: first-level sums of k_normal_eq_loop
   DevBuf<uint32_t> ne_tickets;  // 1 + kNeBlocksMax / kNeGroup
@@ -413,6 +419,30 @@ int lsgpu_chain_config_check(const lsgpu_chain_config* c, int error_minimizer) {
   return LSGPU_OK;
 }
 
+int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->robust_on = false; return LSGPU_OK; }
+  const char* why = nullptr;
+  // (whether the reference has normals is known to align / the stand-alone sums, which check point2plane again)
+  if (robust::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (h->comm) { h->err = "RobustOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
+  h->robust = *cfg;
+  h->robust_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap) {
+  if (!h || !out || cap <= 0 || !h->rb_trace_n) return 0;
+  const int n = std::min<int>(cap, (int)h->rb_trace_n);
+  if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+      hipMemcpy(out, h->rb_trace_dev.p, (size_t)n * sizeof(lsgpu_robust_trace), hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return n;
+}
+
 int lsgpu_abi_version(void) { return LSGPU_ABI_VERSION; }
 
 const char* lsgpu_strerror(int code) {
@@ -477,6 +507,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
+  h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
   h->sel.release(); h->ne_partials.release(); h->ne_gpartials.release(); h->ne_tickets.release(); h->ne_out.release(); h->limit_dev.release();
   for (auto& e : h->comm_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : h->knn_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); (void)hipEventDestroy(e.d); (void)hipEventDestroy(e.e); }
@@ -628,7 +659,7 @@ static float matcher_max_d2(const lsgpu_icp* h) {
 }
 // does the handle take the chain plan (lsgpu_policy.h)?
 static bool chain_on(const lsgpu_icp* h) {
-  return policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor);
+  return policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor, h->robust_on);
 }
 
 static float price_share(const lsgpu_icp* h) {   // heavy lanes / searching lanes of the priced launch (its counters are on the host)
@@ -874,26 +905,42 @@ static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zer
   }
   const int nb = std::min(kHistBlocks, nblk(n));
   const int pr = predicted && st ? 1 : 0;
-  hipLaunchKernelGGL(k_hist1, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p, st, pr);
+  hipLaunchKernelGGL(k_hist1<HistPlain>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p, st, pr, HistPlain{});
   if (rank_ratio > 0.f) {
     hipLaunchKernelGGL(k_chain_rank, dim3(1), dim3(256), 0, h->stream, h->hist.p, st, rank_ratio, h->sel.p,
                        with_median ? h->sel_med.p : (SelState*)nullptr, h->hist_med.p);
     if (with_median) {   // the median's run: same first table, its own second and third
-      hipLaunchKernelGGL(k_hist_refine<2>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p,
-                         h->sel_med.p, h->sel_med.p + 1, h->hist_med.p + kHistBins, st, 0, h->sel_aux.p);
-      hipLaunchKernelGGL(k_hist_refine<3>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist_med.p + kHistBins,
-                         h->sel_med.p + 1, h->sel_med.p + 2, h->hist_med.p + 2 * kHistBins, st, 0, h->sel_aux.p);
+      hipLaunchKernelGGL((k_hist_refine<2, HistPlain>), dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p,
+                         h->sel_med.p, h->sel_med.p + 1, h->hist_med.p + kHistBins, st, 0, h->sel_aux.p, HistPlain{});
+      hipLaunchKernelGGL((k_hist_refine<3, HistPlain>), dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist_med.p + kHistBins,
+                         h->sel_med.p + 1, h->sel_med.p + 2, h->hist_med.p + 2 * kHistBins, st, 0, h->sel_aux.p, HistPlain{});
     }
   }
   if (use_comm && h->comm) { comm_mark(h, true); RCCLC(rccl_api()->AllReduce(h->hist.p, h->hist.p, kHistBins, ncclUint32, ncclSum, h->comm, h->stream)); comm_mark(h, false); }
-  hipLaunchKernelGGL(k_hist_refine<2>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p,
-                     h->sel.p, h->sel.p + 1, h->hist.p + kHistBins, st, pr, h->sel_aux.p);
+  hipLaunchKernelGGL((k_hist_refine<2, HistPlain>), dim3(nb), dim3(256), 0, h->stream, d2, n, h->hist.p,
+                     h->sel.p, h->sel.p + 1, h->hist.p + kHistBins, st, pr, h->sel_aux.p, HistPlain{});
   if (use_comm && h->comm) { comm_mark(h, true); RCCLC(rccl_api()->AllReduce(h->hist.p + kHistBins, h->hist.p + kHistBins, kHistBins, ncclUint32, ncclSum, h->comm, h->stream)); comm_mark(h, false); }
   if (passes < 3) { HIPC(hipGetLastError()); return LSGPU_OK; }   // (fused select: k_normal_eq_loop settles the limit inside its slice)
-  hipLaunchKernelGGL(k_hist_refine<3>, dim3(nb), dim3(256), 0, h->stream, d2, n,
+  hipLaunchKernelGGL((k_hist_refine<3, HistPlain>), dim3(nb), dim3(256), 0, h->stream, d2, n,
                      h->hist.p + kHistBins, h->sel.p + 1, h->sel.p + 2, h->hist.p + 2 * kHistBins, st, pr,
-                     h->sel_aux.p);
+                     h->sel_aux.p, HistPlain{});
   if (use_comm && h->comm) { comm_mark(h, true); RCCLC(rccl_api()->AllReduce(h->hist.p + 2 * kHistBins, h->hist.p + 2 * kHistBins, kHistBins, ncclUint32, ncclSum, h->comm, h->stream)); comm_mark(h, false); }
+  HIPC(hipGetLastError());
+  return LSGPU_OK;
+}
+
+// RobustOutlierFilter's MAD, behind a run_select with the median (hist / hist_med still hold this iteration's tables): the
+// three passes of the select over |d2 - median| with rank m / 2; the weighted k_normal_eq_loop reads the result.
+static int run_mad(lsgpu_icp* h, const float* d2, int n, const IcpState* st) {
+  const int nb = std::min(kHistBlocks, nblk(n));
+  hipLaunchKernelGGL(k_mad_begin, dim3(1), dim3(256), 0, h->stream, h->hist.p, st, h->hist_med.p, h->sel_med.p, h->rb_state.p,
+                     h->rb_sel.p, h->rb_hist.p);
+  const HistAbsDev x{&h->rb_state.p->median};
+  hipLaunchKernelGGL(k_hist1<HistAbsDev>, dim3(nb), dim3(256), 0, h->stream, d2, n, h->rb_hist.p, st, 0, x);
+  hipLaunchKernelGGL((k_hist_refine<2, HistAbsDev>), dim3(nb), dim3(256), 0, h->stream, d2, n, h->rb_hist.p, h->rb_sel.p,
+                     h->rb_sel.p + 1, h->rb_hist.p + kHistBins, st, 0, h->sel_aux.p, x);
+  hipLaunchKernelGGL((k_hist_refine<3, HistAbsDev>), dim3(nb), dim3(256), 0, h->stream, d2, n, h->rb_hist.p + kHistBins,
+                     h->rb_sel.p + 1, h->rb_sel.p + 2, h->rb_hist.p + 2 * kHistBins, st, 0, h->sel_aux.p, x);
   HIPC(hipGetLastError());
   return LSGPU_OK;
 }
@@ -980,6 +1027,7 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   if (!ref_xyz1 || nr <= 0 || nr > 0x7FFFFFF0ll) { h->err = "set_reference: empty or oversize cloud"; h->nr = 0; return LSGPU_BAD_ARG; }
   HIPC(hipSetDevice(h->device));
   h->nr = 0;
+  h->have_normals = ref_normals != nullptr;
   const float4* src = nullptr;
   int rc = stage_points(h, ref_xyz1, nr, h->ref_in, &src);
   if (rc) return rc;
@@ -1131,7 +1179,8 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
     return LSGPU_BAD_CONFIG;
   }
   if (chain_on(h)) {
-    h->err = "comm_init: the split-scan mode runs neither KDTreeMatcher maxDist nor Max- / Min- / MedianDistOutlierFilter";
+    h->err = h->robust_on ? "comm_init: the split-scan mode does not run RobustOutlierFilter"
+                          : "comm_init: the split-scan mode runs neither KDTreeMatcher maxDist nor Max- / Min- / MedianDistOutlierFilter";
     return LSGPU_BAD_CONFIG;
   }
   if (!api) { h->err = "librccl.so.1 could not be loaded"; return LSGPU_HIP_ERROR; }
@@ -1299,9 +1348,29 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
   float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const Mat34 Tm = to_mat34(T ? T : I);
   const int nb = std::min(kNeBlocks, nblk(nq));
-  hipLaunchKernelGGL((k_normal_eq<true, false, MIN>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm,
-                     idp, dp, h->pts.p, MIN == kPointToPoint ? (const float4*)nullptr : h->nrm.p, h->ref_inv.p,
-                     (const uint32_t*)nullptr, (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p);
+  if (h->robust_on) {
+    // RobustOutlierFilter: the pairs' weights go into the sums; the scale is the MAD of the distances given (host twin)
+    const robust::Params rp = robust::params(h->robust);
+    if (rp.plane && !h->have_normals) { h->err = std::string(what) + ": RobustOutlierFilter distanceType point2plane needs reference normals"; return LSGPU_BAD_CONFIG; }
+    float scale = 1.f, med = 0.f;
+    if (rp.mad) {
+      std::vector<float> hd((size_t)nq);
+      HIPC(hipMemcpyAsync(hd.data(), dp, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
+      HIPC(hipStreamSynchronize(h->stream));
+      if (lsgpu_robust_scale(hd.data(), nq, &med, &scale) != LSGPU_OK || !(scale > 0.f)) {
+        h->err = std::string(what) + ": RobustOutlierFilter has no valid match or a MAD scale of 0";
+        return LSGPU_NO_CONVERGENCE;
+      }
+    }
+    hipLaunchKernelGGL((k_normal_eq<true, false, MIN, true>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm,
+                       idp, dp, h->pts.p, (MIN == kPointToPoint && !rp.plane) ? (const float4*)nullptr : h->nrm.p, h->ref_inv.p,
+                       (const uint32_t*)nullptr, (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p, rp, scale);
+  } else {
+    hipLaunchKernelGGL((k_normal_eq<true, false, MIN>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm,
+                       idp, dp, h->pts.p, MIN == kPointToPoint ? (const float4*)nullptr : h->nrm.p, h->ref_inv.p,
+                       (const uint32_t*)nullptr, (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p,
+                       robust::Params{}, 1.f);
+  }
   hipLaunchKernelGGL(k_ne_final, dim3(1), dim3(1024), 0, h->stream, h->ne_partials.p, nb, h->ne_out.p);
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h->h_pinned, h->ne_out.p, kNe * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1948,7 +2017,8 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   const bool ref_filter = chain->ssn_knn != 0;
   // SurfaceNormalDataPointsFilter keeps every point and draws nothing: the reference goes to set_reference as given and
   // the normals are computed on the grid it builds (a point-to-point handle reads none: skipped)
-  const bool ref_normals = chain->sn_knn != 0 && h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT;
+  const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;   // (its residuals need the normals)
+  const bool ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane);
   if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
   if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
   if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
@@ -2117,6 +2187,7 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   if (ref_normals) {
     rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
     if (rc) return rc;
+    h->have_normals = true;
   }
   if (side) {
     // the direction index of the reference is not needed before the loop's third search: lsgpu_icp_align enqueues its
@@ -2539,6 +2610,18 @@ static NeLoopFn ne_loop_chain(bool p2p, int k) {
   return tab[p2p ? 1 : 0][k];
 }
 
+// ... and the weighted ones of a handle with RobustOutlierFilter (always the chain plan)
+static NeLoopFn ne_loop_robust(bool p2p, int k) {
+  static const NeLoopFn tab[2][kKnnKMax + 1] = {
+      {nullptr, k_normal_eq_loop<kPointToPlane, 1, true, true>, k_normal_eq_loop<kPointToPlane, 2, true, true>, k_normal_eq_loop<kPointToPlane, 3, true, true>,
+       k_normal_eq_loop<kPointToPlane, 4, true, true>, k_normal_eq_loop<kPointToPlane, 5, true, true>, k_normal_eq_loop<kPointToPlane, 6, true, true>,
+       k_normal_eq_loop<kPointToPlane, 7, true, true>, k_normal_eq_loop<kPointToPlane, 8, true, true>},
+      {nullptr, k_normal_eq_loop<kPointToPoint, 1, true, true>, k_normal_eq_loop<kPointToPoint, 2, true, true>, k_normal_eq_loop<kPointToPoint, 3, true, true>,
+       k_normal_eq_loop<kPointToPoint, 4, true, true>, k_normal_eq_loop<kPointToPoint, 5, true, true>, k_normal_eq_loop<kPointToPoint, 6, true, true>,
+       k_normal_eq_loop<kPointToPoint, 7, true, true>, k_normal_eq_loop<kPointToPoint, 8, true, true>}};
+  return tab[p2p ? 1 : 0][k];
+}
+
 int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
                     float T_out[16], lsgpu_icp_stats* stats) {
   if (!h || !T_init || !T_out) return LSGPU_BAD_ARG;
@@ -2547,7 +2630,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   lsgpu_icp_stats st;
   std::memset(&st, 0, sizeof(st));
   if (stats) *stats = st;
-  h->trace.clear(); h->trace_on_device = 0;
+  h->trace.clear(); h->trace_on_device = 0; h->rb_trace_n = 0;
   // queries that lsgpu_icp_compute ordered and moved on its side stream belong to THIS call and to no later one, whatever
   // way it ends (a guess that is refused below would otherwise leave queries moved by that guess to the next call with the
   // same pointer and size)
@@ -2566,6 +2649,13 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   ca.lo2 = h->cfg.outlier_min_dist * h->cfg.outlier_min_dist;
   ca.max2 = (h->cfg.outlier_max_dist > 0.f && !std::isinf(h->cfg.outlier_max_dist)) ? h->cfg.outlier_max_dist * h->cfg.outlier_max_dist : INFINITY;
   ca.med_factor = h->cfg.outlier_median_factor; ca.has_median = h->cfg.outlier_median_factor > 0.f ? 1 : 0;
+  const bool robust = h->robust_on;
+  if (robust) { ca.rb = robust::params(h->robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
+  if (robust && ca.rb.plane && !h->have_normals) {
+    h->err = "align: RobustOutlierFilter distanceType point2plane needs reference normals";
+    h->cone_build_in_align = false;
+    return LSGPU_BAD_CONFIG;
+  }
   if (h->nr <= 0 || nq <= 0 || !reading_xyz1) {  // empty cloud: ConvergenceError upstream
     h->err = "align: empty reading or no reference";
     local_rc = LSGPU_NO_CONVERGENCE;
@@ -2631,6 +2721,12 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   HIPC(h->state.reserve(1));
   HIPC(h->chk_hist.reserve((size_t)8 * (max_it + 2)));
   HIPC(h->trace_dev.reserve((size_t)max_it));
+  if (robust) {
+    HIPC(h->rb_hist.reserve(3 * kHistBins)); HIPC(h->rb_sel.reserve(4)); HIPC(h->rb_state.reserve(1));
+    HIPC(h->rb_trace_dev.reserve((size_t)max_it));
+    HIPC(hipMemsetAsync(h->rb_state.p, 0, sizeof(RobustState), h->stream));
+    ca.rb_hist = h->rb_hist.p; ca.rb_sel = h->rb_sel.p; ca.rb_state = h->rb_state.p; ca.rb_trace = h->rb_trace_dev.p;
+  }
   IcpState* hst = reinterpret_cast<IcpState*>(h->h_pinned + 64);  // pinned staging (<= 512 B); [0..47] D2H, [48..63] H2D
   static_assert(sizeof(IcpState) <= 64 * sizeof(double), "IcpState staging");
   std::memset(hst, 0, sizeof(IcpState));
@@ -2674,7 +2770,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   const bool p2p = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
   const auto ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
   const auto update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
-  const NeLoopFn ne_loop_k = chain ? ne_loop_chain(p2p, kk) : kmatch ? ne_loop_pairs(p2p, kk) : nullptr;
+  const NeLoopFn ne_loop_k = robust ? ne_loop_robust(p2p, kk) : chain ? ne_loop_chain(p2p, kk) : kmatch ? ne_loop_pairs(p2p, kk) : nullptr;
   ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
   // The launch policy (lsgpu_policy.h) decides what every iteration is made of and when the host looks at the loop
   // state; this function executes its decisions.  (tests/cpp/policy_check.cpp drives the same state machine on the CPU.)
@@ -2688,6 +2784,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   pc.two_pass_select = !h->comm && tuning().fused_select && tuning().two_pass_select;
   pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
   pc.kmatch = kmatch; pc.chain = chain;
+  pc.robust_mad = robust && ca.rb.mad; pc.robust_scale_iters = robust ? h->robust.nb_iteration_for_scale : 0;
   policy::State& pol = h->pol;
   if (h->cone_build_in_align) { h->cone_ok = cone_wanted(h); h->cone_decided = false; }   // (its build follows the first iteration, below)
   // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
@@ -2711,18 +2808,22 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
       if (r) return r;
       ev_of_launch.push_back(h->knn_events_used ? h->knn_events_used - 1 : 0);
       // (chain: the rank from the device's count of valid matches, the median beside it if the chain holds that filter)
+      // (RobustOutlierFilter's MAD needs the median too; the MAD's own select runs only where the scale is recomputed)
       r = run_select(h, h->kd2.p, np, k, false /* armed by k_align_init / the previous k_normal_eq_loop */, h->state.p, true, false, 3,
-                     chain ? h->cfg.trim_ratio : 0.f, chain && ca.has_median);  // 6c
+                     chain ? h->cfg.trim_ratio : 0.f, chain && (ca.has_median || itn.mad));  // 6c
       if (r) return r;
+      if (itn.mad) { r = run_mad(h, h->kd2.p, np, h->state.p); if (r) return r; }
+      ChainArgs ca_it = ca;
+      ca_it.rb_recompute = itn.mad ? 1 : 0;
       lsgpu_icp::KnnEv* evk = (timed && h->knn_events_used) ? &h->knn_events[h->knn_events_used - 1] : nullptr;
       if (evk) HIPC(hipEventRecord(evk->d, h->stream));
       hipLaunchKernelGGL(ne_loop_k, dim3(nb), dim3(256), 0, h->stream, h->rdq.p, np,
-                         h->state.p, h->kmatch.p, h->kd2.p, p2p ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
+                         h->state.p, h->kmatch.p, h->kd2.p, (p2p && !(robust && ca.rb.plane)) ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
                          h->counters.p + 32, h->ne_tickets.p, h->ne_partials.p, h->ne_gpartials.p, h->ne_out.p,
-                         h->chk_hist.p, h->trace_dev.p, max_it, 0, split_update ? 0 : 1,
+                         h->chk_hist.p, h->trace_dev.p, max_it, 0, (split_update && !robust) ? 0 : 1,
                          h->sel_aux.p, (uint32_t*)nullptr, 0, (uint32_t*)nullptr,
-                         0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0, ca);   // 6d (+6e)
-      if (split_update)
+                         0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0, ca_it);   // 6d (+6e)
+      if (split_update && !robust)
         hipLaunchKernelGGL(update, dim3(1), dim3(64), 0, h->stream, h->state.p, h->ne_out.p,
                            h->chk_hist.p, h->trace_dev.p, max_it, 0, h->sel_aux.p);                       // 6d+6e
       if (evk) HIPC(hipEventRecord(evk->e, h->stream));
@@ -2877,7 +2978,9 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   rc = hst->status;
   if (rc == LSGPU_NO_CONVERGENCE)
     h->err = hst->err_code == 1 ? "no point to minimize" : hst->err_code == 2 ? "normal matrix not positive definite"
-           : hst->err_code == 4 ? "non-finite point-to-point solution" : "NaN in transformation checker";
+           : hst->err_code == 4 ? "non-finite point-to-point solution"
+           : hst->err_code == 5 ? "RobustOutlierFilter: no valid match or a MAD scale of 0"
+           : hst->err_code == 6 ? "RobustOutlierFilter: a weight is not finite" : "NaN in transformation checker";
   st.iterations = it;
   st.converged = hst->converged;
   st.stragglers = (int64_t)hst->stragglers;
@@ -2888,6 +2991,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   // statistics that came out of it travel with the loop state.
   h->trace.clear();
   h->trace_on_device = (size_t)std::min(it, max_it);
+  h->rb_trace_n = robust ? h->trace_on_device : 0;
   h->trace_knn_us.clear();
   if (it > 0) { st.final_limit = hst->last_limit; st.final_n_used = (int64_t)hst->last_used; }
   if (rc == LSGPU_OK) {  // step 7

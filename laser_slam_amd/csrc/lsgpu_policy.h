@@ -34,15 +34,19 @@ struct Config {               // constant during an alignment (from Tuning and t
   double straggler_share = 0.02;     // lanes the index could not serve, per settled iteration, above which it is dropped
   bool kmatch = false;        // k nearest matches (lsgpu_icp_config.matcher_knn >= 2): see State::plan
   bool chain = false;         // KDTreeMatcher maxDist or a Max- / Min- / MedianDistOutlierFilter (chain_fields): see State::plan_chain
+  bool robust_mad = false;    // RobustOutlierFilter with the MAD scale (a chain handle): see State::plan_chain
+  int robust_scale_iters = 0; // ... its nbIterationForScale (0: the scale is recomputed in every iteration)
 };
 
 // Which handles take the chain plan: any of the four fields lsgpu_icp_config gained for KDTreeMatcher maxDist and the
 // outlier-filter chain (0 = absent; +inf = absent for the two maxDist fields).  A configuration with none of them is
 // planned exactly as before the fields existed.
-inline bool chain_fields(float matcher_max_dist, float outlier_max_dist, float outlier_min_dist, float outlier_median_factor) {
+// A handle with RobustOutlierFilter (lsgpu_icp_set_robust_filter) takes it too, whatever the four fields hold.
+inline bool chain_fields(float matcher_max_dist, float outlier_max_dist, float outlier_min_dist, float outlier_median_factor,
+                         bool robust_filter = false) {
   const bool md = matcher_max_dist > 0.f && !std::isinf(matcher_max_dist);
   const bool od = outlier_max_dist > 0.f && !std::isinf(outlier_max_dist);
-  return md || od || outlier_min_dist > 0.f || outlier_median_factor > 0.f;
+  return md || od || outlier_min_dist > 0.f || outlier_median_factor > 0.f || robust_filter;
 }
 
 struct Iteration {            // one enqueued iteration: what the search, the select and the normal equations are told
@@ -55,6 +59,7 @@ struct Iteration {            // one enqueued iteration: what the search, the se
   bool dense_wait = false;    // (its first one: a denser reference waits one iteration more)
   bool price = false;         // this search prices the index for the one behind it
   int ordinal = 0;            // its place in the alignment (0 = the seeded first iteration)
+  bool mad = false;           // RobustOutlierFilter recomputes its MAD scale in this iteration: the median's select and the MAD's run
 };
 
 enum class KnnKernel { Cone, ConeProbe, Tile };
@@ -114,7 +119,7 @@ struct State {
 
   // ---- what the next iteration is made of
   Iteration plan(const Config& c, bool seed, bool capped, bool wide, bool knn, bool price_next) {
-    if (c.chain) return plan_chain(seed, knn);
+    if (c.chain) return plan_chain(c, seed, knn);
     if (c.kmatch) return plan_kmatch(seed, knn);
     Iteration it;
     it.knn = knn; it.seed = seed; it.capped = capped; it.wide = wide;
@@ -149,7 +154,14 @@ struct State {
   // of valid matches, a second run of its refining passes finds the median when the chain needs it) and the chain
   // instantiation of the normal equations.  None of the accelerations of the one-neighbour loop: their tables assume that
   // every query has a match and that the rank is known to the host.  No look can ask for a repeat.
-  Iteration plan_chain(bool seed, bool knn) { return plan_kmatch(seed, knn); }
+  // RobustOutlierFilter with the MAD scale: iteration `it` (1-based: ordinal + 1; the chain plan never repeats an iteration,
+  // so the ordinal is the device's count) recomputes the scale iff nbIterationForScale == 0 || it <= nbIterationForScale --
+  // only those iterations launch the median's select and the MAD's; the others weight with the scale in the loop state.
+  Iteration plan_chain(const Config& c, bool seed, bool knn) {
+    Iteration it = plan_kmatch(seed, knn);
+    it.mad = c.robust_mad && (c.robust_scale_iters == 0 || enq + 1 <= c.robust_scale_iters);
+    return it;
+  }
 
   // the loop between two looks: true -> enqueue a plain iteration (fills `it`), false -> look at the loop state
   bool next_in_group(const Config& c, Iteration* it) {

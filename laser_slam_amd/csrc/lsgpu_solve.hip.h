@@ -3,6 +3,7 @@
 #pragma once
 #include "lsgpu_common.hip.h"
 #include "lsgpu_host_math.h"
+#include "lsgpu_robust.h"
 #include "../../include/lsgpu_icp.h"
 
 namespace lsgpu {
@@ -78,29 +79,44 @@ __device__ __forceinline__ void hist_sweep(const float* __restrict__ d2, int n, 
   if (blockIdx.x == 0 && (int)threadIdx.x < (n & 3)) f(__float_as_uint(d2[(n4 << 2) + threadIdx.x]));
 }
 
+// What the select ranks: the distances themselves (HistPlain), or their absolute deviations from a value in device memory
+// (HistAbsDev: the second order statistic of RobustOutlierFilter's MAD scale, |d2 - median| in float; the sign bit is
+// masked, so every key -- a NaN's too -- stays below 2^31 and its top 12 bits inside the table).
+struct HistPlain {
+  __device__ __forceinline__ float origin() const { return 0.f; }
+  static __device__ __forceinline__ uint32_t map(uint32_t b, float) { return b; }
+};
+struct HistAbsDev {
+  const float* med;
+  __device__ __forceinline__ float origin() const { return *med; }
+  static __device__ __forceinline__ uint32_t map(uint32_t b, float o) { return __float_as_uint(__uint_as_float(b) - o) & 0x7FFFFFFFu; }
+};
+
+template <class X = HistPlain>
 __global__ __launch_bounds__(256) void k_hist1(const float* __restrict__ d2, int n,
                                                uint32_t* __restrict__ hist,
-                                               const IcpState* __restrict__ ist, int predicted) {
+                                               const IcpState* __restrict__ ist, int predicted, X x) {
   __shared__ uint32_t sh[kHistBins];
   if (ist && ist->done) return;
   if (predicted && ist->sel_mode) return;  // the kNN kernel of this iteration did passes 1 and 2
   for (int i = threadIdx.x; i < kHistBins; i += 256) sh[i] = 0;
   __syncthreads();
-  hist_sweep(d2, n, [&](uint32_t b) { atomicAdd(&sh[b >> 20], 1u); });
+  const float org = x.origin();
+  hist_sweep(d2, n, [&](uint32_t b0) { const uint32_t b = X::map(b0, org); atomicAdd(&sh[b >> 20], 1u); });
   __syncthreads();
   for (int i = threadIdx.x; i < kHistBins; i += 256)
     if (sh[i]) atomicAdd(&hist[i], sh[i]);
 }
 
 // PASS 2: shift 9, 11 bits, parent = hist1 ; PASS 3: shift 0, 9 bits, parent = hist2
-template <int PASS>
+template <int PASS, class X = HistPlain>
 __global__ __launch_bounds__(256) void k_hist_refine(const float* __restrict__ d2, int n,
                                                      const uint32_t* __restrict__ parent,
                                                      const SelState* __restrict__ st_in,
                                                      SelState* __restrict__ st_out,
                                                      uint32_t* __restrict__ hist,
                                                      const IcpState* __restrict__ ist, int predicted,
-                                                     uint32_t* __restrict__ sel_aux) {
+                                                     uint32_t* __restrict__ sel_aux, X x) {
   __shared__ uint32_t sh[kHistBins];
   __shared__ uint32_t sc[260];
   if (ist && ist->done) return;
@@ -137,7 +153,8 @@ __global__ __launch_bounds__(256) void k_hist_refine(const float* __restrict__ d
   constexpr int SH_HI = (PASS == 2) ? 20 : 9;
   constexpr int SH_LO = (PASS == 2) ? 9 : 0;
   constexpr uint32_t MASK = (PASS == 2) ? 0x7FFu : 0x1FFu;
-  hist_sweep(d2, n, [&](uint32_t b) { if ((b >> SH_HI) == prefix) atomicAdd(&sh[(b >> SH_LO) & MASK], 1u); });
+  const float org = x.origin();
+  hist_sweep(d2, n, [&](uint32_t b0) { const uint32_t b = X::map(b0, org); if ((b >> SH_HI) == prefix) atomicAdd(&sh[(b >> SH_LO) & MASK], 1u); });
   __syncthreads();
   for (int i = threadIdx.x; i < kHistBins; i += 256)
     if (sh[i]) atomicAdd(&hist[i], sh[i]);
@@ -193,6 +210,20 @@ __global__ __launch_bounds__(256) void k_chain_rank(const uint32_t* __restrict__
     for (int i = threadIdx.x; i < 2 * kHistBins; i += 256) hist_med[kHistBins + i] = 0u;
 }
 
+// RobustOutlierFilter's part of the loop state (its own two words: IcpState keeps its size, and with it the LDS copy every
+// instantiation of k_normal_eq_loop holds): written by k_mad_begin (median) and by the update lane (scale), read by the
+// prologue of the next weighted launch -- the loop stays on the device.
+struct RobustState { float scale, median; };
+// what the weighted launch's last block hands its update lane
+struct RobustIter {
+  long long used;     // pairs with w > 0
+  double bad;         // pairs whose weight was not finite
+  float scale, median;
+  int recomputed, mad;
+  RobustState* state;
+  lsgpu_robust_trace* trace;
+};
+
 // What a chain adds to the loop's normal-equation kernel (CHAIN instantiations): a pair is kept iff
 // lo2 <= d2 && d2 <= hi, hi = min(trim limit, max2, med_factor x median) -- the iteration's effective upper limit.
 struct ChainArgs {
@@ -202,7 +233,36 @@ struct ChainArgs {
   int has_median;             // ... if the chain holds one
   const uint32_t* hist_med;   // the median's select: 3 x kHistBins ([0] unused: the first table is shared) ...
   const SelState* sel_med;    // ... and its three states
+  // RobustOutlierFilter (read by the RB instantiations only)
+  robust::Params rb;
+  int has_trim;               // a TrimmedDistOutlierFilter is in the chain (ratio < 1); without it the trim limit is +inf
+  int rb_recompute;           // this iteration computes the MAD scale (the MAD's select ran in front of the launch)
+  const uint32_t* rb_hist;    // the MAD's select over |d2 - median|: 3 x kHistBins ...
+  const SelState* rb_sel;     // ... and its three states
+  RobustState* rb_state;      // the scale and the median, kept from iteration to iteration
+  lsgpu_robust_trace* rb_trace;
 };
+
+// Start of the MAD's select (one block, behind the median's select): the median goes to the loop's robust state, where the
+// three histogram passes over |d2 - median| read it (HistAbsDev); the rank m / 2 comes from the select's first table, which
+// has seen every distance of the iteration (k_chain_rank); the MAD's tables are cleared.
+__global__ __launch_bounds__(256) void k_mad_begin(const uint32_t* __restrict__ hist1, const IcpState* __restrict__ ist,
+                                                   const uint32_t* __restrict__ hist_med, const SelState* __restrict__ sel_med,
+                                                   RobustState* __restrict__ rs, SelState* __restrict__ rb_sel,
+                                                   uint32_t* __restrict__ rb_hist /* 3 x kHistBins */) {
+  __shared__ uint32_t sc[260];
+  __shared__ uint32_t part[4];
+  if (ist && ist->done) return;
+  uint32_t m = 0u;
+  for (uint32_t i = threadIdx.x; i < kHistInfBin; i += 256u) m += hist1[i];
+  m = wave_sum_u32(m);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = part[0] + part[1] + part[2] + part[3];
+  const float med = select_limit(hist_med + 2 * kHistBins, sel_med + 2, sc);
+  if (threadIdx.x == 0) { rs->median = med; rb_sel->prefix = 0u; rb_sel->k = m / 2u; }
+  for (int i = threadIdx.x; i < 3 * kHistBins; i += 256) rb_hist[i] = 0u;
+}
 
 // First iteration: the select just ran over the SEED distances (upper bounds of the true ones); its result is a
 // valid cap for the first search (limit(true distances) <= limit(upper bounds)).
@@ -275,7 +335,8 @@ __device__ __forceinline__ void p2p_terms(const float3 p, const float4 q, double
   v[15] = ((double)e0 * (double)e0 + (double)e1 * (double)e1) + (double)e2 * (double)e2;
 }
 
-template <bool IDS_ORIG, bool LIMIT_DEV, int MIN = kPointToPlane>
+// RB: the sums of a handle with RobustOutlierFilter -- every kept pair weighted by robust::weight (rb, rb_scale)
+template <bool IDS_ORIG, bool LIMIT_DEV, int MIN = kPointToPlane, bool RB = false>
 __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rdq, int nq, Mat34 T,
                                                    const int* __restrict__ ids,
                                                    const float* __restrict__ d2,
@@ -285,7 +346,8 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
                                                    const uint32_t* __restrict__ hist3,
                                                    const SelState* __restrict__ st, float limit_val,
                                                    float* __restrict__ limit_out,
-                                                   double* __restrict__ partials) {
+                                                   double* __restrict__ partials,
+                                                   robust::Params rb, float rb_scale) {
   __shared__ uint32_t sc[260];
   __shared__ double red[4][kNe];
   float limit = limit_val;
@@ -307,6 +369,22 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
     if constexpr (MIN == kPointToPoint) {
       double v[16];
       p2p_terms(p, q, v);
+      if constexpr (RB) {
+        float e = d;
+        if (rb.plane) {
+          const float4 n = nrm[id];
+          const float res = (p.x - q.x) * n.x + (p.y - q.y) * n.y + (p.z - q.z) * n.z;
+          e = res * res;
+        }
+        const float wf = robust::weight(rb.fct, e, rb_scale, rb.k, rb.approx2);
+        if (!(wf > 0.f)) continue;
+        const double wd = (double)wf;
+#pragma unroll
+        for (int k = 0; k < 15; ++k) acc[k] += wd * v[k];
+        acc[27] += wd;
+        acc[28] += wd * v[15];
+        continue;
+      }
 #pragma unroll
       for (int k = 0; k < 15; ++k) acc[k] += v[k];
       acc[27] += 1.0;
@@ -320,6 +398,22 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
     J[2] = p.x * n.y - p.y * n.x;
     J[3] = n.x; J[4] = n.y; J[5] = n.z;
     const float res = (p.x - q.x) * n.x + (p.y - q.y) * n.y + (p.z - q.z) * n.z;
+    if constexpr (RB) {
+      const float wf = robust::weight(rb.fct, rb.plane ? res * res : d, rb_scale, rb.k, rb.approx2);
+      if (!(wf > 0.f)) continue;
+      const double wd = (double)wf;
+      int k = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int c = a; c < 6; ++c) acc[k++] += wd * ((double)J[a] * (double)J[c]);
+      }
+#pragma unroll
+      for (int a = 0; a < 6; ++a) acc[21 + a] -= wd * ((double)J[a] * (double)res);
+      acc[27] += wd;
+      acc[28] += wd * ((double)res * (double)res);
+      continue;
+    }
     int k = 0;
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
@@ -358,10 +452,12 @@ __device__ unsigned long long g_ne_tail[4];   // (wall clock at points of the la
 // One lane: 6x6 float LLT solve, AngleAxis update, T_iter <- dT * T_iter, Counter + Differential
 // checkers, trace record, next cap.  Same code as the host (lsgpu_host_math.h).  MIN: the handle's minimizer
 // (point-to-point: point_to_point_delta instead of the LLT solve; the trace keeps its layout, see lsgpu_iter_trace).
-template <int MIN>
+// RB: the weighted launch of a handle with RobustOutlierFilter (`rb`: what its last block found)
+template <int MIN, bool RB = false>
 __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float* chk_hist,
                                        lsgpu_iter_trace* trace, int trace_cap, int capped_launch,
-                                       uint32_t* sel_aux, int sel_failed = -1 /* -1: read (and clear) the flag in sel_aux */) {
+                                       uint32_t* sel_aux, int sel_failed = -1 /* -1: read (and clear) the flag in sel_aux */,
+                                       const RobustIter* rb = nullptr) {
   if (st->done) return;
   if (sel_failed < 0) {
     sel_failed = (sel_aux && sel_aux[kSelFailFlag]) ? 1 : 0;
@@ -386,7 +482,12 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
   const long long u0 = clock64();
 #endif
   st->stragglers += nstrag;
-  const long long used = (long long)ne_out[27];
+  long long used = (long long)ne_out[27];
+  if constexpr (RB) {   // slot 27 holds the sum of the weights: the pairs are counted beside it
+    used = rb->used;
+    if (rb->mad && !(rb->scale > 0.f && rb->scale < INFINITY)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 5; st->done = 1; return; }
+    if (rb->bad > 0.0) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 6; st->done = 1; return; }
+  }
   if (used <= 0) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 1; st->done = 1; return; }
   double A[36], b[6];
   float x[6], dT[16], Tn[16];
@@ -423,7 +524,12 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
     for (int i = 0; i < 6; ++i) { tr.b[i] = b[i]; tr.x[i] = x[i]; }
     }
     tr.knn_main_us = 0.f; tr.knn_fallback_us = 0.f; tr.stragglers = (uint32_t)nstrag; tr.reserved = (uint32_t)ne_out[31];
+    if constexpr (RB) {
+      lsgpu_robust_trace& rt = rb->trace[it];
+      rt.median = rb->median; rt.scale = rb->scale; rt.w_sum = ne_out[27]; rt.recomputed = rb->recomputed; rt.reserved = 0;
+    }
   }
+  if constexpr (RB) rb->state->scale = rb->scale;
 #ifdef LSGPU_KNN_STATS
   const long long u3 = clock64();
 #endif
@@ -502,7 +608,11 @@ constexpr int kNeUnroll = LSGPU_NE_UNROLL;  // points whose loads are in flight 
 // the update are those of the 1-NN loop; its launches pass no fused / predicted / committed select.
 // CHAIN: the instantiations of a chain with KDTreeMatcher maxDist / Max-, Min-, MedianDistOutlierFilter (ChainArgs; the
 // matches come from the k-best search for every KP, 1 included); like KP > 1 they run behind a full select.
-template <int MIN, int KP = 1, bool CHAIN = false>
+// RB: the weighted instantiations of a handle with RobustOutlierFilter (always CHAIN; ChainArgs::rb ...): every pair the
+// binary filters keep gets the weight robust::weight(e) -- e its d2, or the square of the residual this pass computes
+// anyway -- computed here, in registers; the sums are weighted, the pairs with w > 0 and the non-finite weights are counted
+// in columns 29 / 30 of the partials.  The scale comes from the MAD's select (rb_recompute) or from the robust state.
+template <int MIN, int KP = 1, bool CHAIN = false, bool RB = false>
 __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict__ rdq, int nq,
                                                         IcpState* __restrict__ ist,
                                                         const float4* __restrict__ match,
@@ -649,6 +759,7 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     }
   } else {
     limit = select_limit(hist + 2 * kHistBins, st, sc);
+    if constexpr (RB) { if (!chain.has_trim) limit = INFINITY; }
     if constexpr (CHAIN) {   // the smallest of the upper thresholds present
       if (chain.has_median) limit = fminf(limit, chain.med_factor * select_limit(chain.hist_med + 2 * kHistBins, chain.sel_med + 2, sc));
       limit = fminf(limit, chain.max2);
@@ -668,6 +779,16 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   const long long c1 = clock64();
   if (threadIdx.x == 0) atomicMin(&g_ne_dbg[10], (unsigned long long)wall_clock64());
 #endif
+  float rb_scale = 1.f, rb_med = 0.f;
+  double rb_cnt = 0.0, rb_bad = 0.0;
+  if constexpr (RB) {
+    if (chain.rb.mad) {
+      rb_med = chain.rb_state->median;
+      if (chain.rb_recompute) rb_scale = sqrtf(select_limit(chain.rb_hist + 2 * kHistBins, chain.rb_sel + 2, sc));
+      else rb_scale = chain.rb_state->scale;
+    }
+  }
+  const bool rb_normals = MIN != kPointToPoint || (RB && chain.rb.plane);   // (point2plane distances of a point-to-point handle read the normal too)
   double acc[kNe];
 #pragma unroll
   for (int k = 0; k < kNe; ++k) acc[k] = 0.0;
@@ -702,6 +823,7 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     // SLOWER: 31.5 -> 34.6 us per launch, profiles/r03b_bench.json; it adds 16 MB of HBM stream to save cache hits)
     for (int u = 0; u < kNeUnroll; ++u) {
       if constexpr (MIN != kPointToPoint) nn[u] = use[u] ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
+      else if constexpr (RB) nn[u] = (use[u] && rb_normals) ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int u = 0; u < kNeUnroll; ++u) {
@@ -724,6 +846,24 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
                              ((unsigned long long)__float_as_uint(dd[u]) << 32) | (unsigned long long)(uint32_t)(j0 + u * stride),
                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        continue;
+      }
+      if constexpr (RB) {
+        float e = dd[u];
+        if (chain.rb.plane) {
+          const float4 n = nn[u];
+          const float res = (p.x - q.x) * n.x + (p.y - q.y) * n.y + (p.z - q.z) * n.z;
+          e = res * res;
+        }
+        const float wf = robust::weight(chain.rb.fct, e, rb_scale, chain.rb.k, chain.rb.approx2);
+        if (!(fabsf(wf) < INFINITY)) { rb_bad += 1.0; continue; }
+        if (!(wf > 0.f)) continue;
+        rb_cnt += 1.0;
+        const double wd = (double)wf;
+#pragma unroll
+        for (int k = 0; k < 15; ++k) acc[k] += wd * v[k];
+        acc[27] += wd;
+        acc[28] += wd * v[15];
         continue;
       }
 #pragma unroll
@@ -755,6 +895,24 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
       }
       continue;
     }
+    if constexpr (RB) {
+      const float wf = robust::weight(chain.rb.fct, chain.rb.plane ? res * res : dd[u], rb_scale, chain.rb.k, chain.rb.approx2);
+      if (!(fabsf(wf) < INFINITY)) { rb_bad += 1.0; continue; }
+      if (!(wf > 0.f)) continue;
+      rb_cnt += 1.0;
+      const double wd = (double)wf;
+      int k = 0;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int c = a; c < 6; ++c) acc[k++] += wd * ((double)J[a] * (double)J[c]);
+      }
+#pragma unroll
+      for (int a = 0; a < 6; ++a) acc[21 + a] -= wd * ((double)J[a] * (double)res);
+      acc[27] += wd;
+      acc[28] += wd * ((double)res * (double)res);
+      continue;
+    }
     int k = 0;
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
@@ -775,16 +933,18 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
 #pragma unroll
   for (int k = 0; k < kNe; ++k) acc[k] = ne_slot_unused<MIN>(k) ? 0.0 : wave_sum(acc[k]);
   const int w = threadIdx.x >> 6;
+  if constexpr (RB) { rb_cnt = wave_sum(rb_cnt); rb_bad = wave_sum(rb_bad); }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < kNe; ++k) red[w][k] = acc[k];
+    if constexpr (RB) { red[w][29] = rb_cnt; red[w][30] = rb_bad; }
   }
   __syncthreads();
   // Hand-off between blocks WITHOUT fences: the partial sums are written and read with agent-scope (sc1) accesses,
   // which go past the per-CU L1 and the per-XCD L2 on both sides (MI355X_MICROARCH.md, inter-workgroup visibility:
   // "sc1 stores and loads both sides"); a release / acquire fence pair costs 1.7-6.5 us per block on this chip and
   // every block would pay it.  s_waitcnt vmcnt(0) orders a block's stores before its ticket.
-  if (threadIdx.x < kNe)
+  if (threadIdx.x < (RB ? kNe + 2 : kNe))
     __hip_atomic_store(&partials[(size_t)blockIdx.x * 32 + threadIdx.x],
                        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x],
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -968,6 +1128,14 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     }
     out[threadIdx.x] = t; fin[threadIdx.x] = t;
   }
+  if constexpr (RB) {   // the pair count and the non-finite count: columns 29 / 30, parked in the padding column of `red`
+    if (threadIdx.x == 29 || threadIdx.x == 30) {
+      double t = red[0][threadIdx.x];
+#pragma unroll
+      for (int g = 1; g < 8; ++g) t += red[g][threadIdx.x];
+      red[threadIdx.x - 29][32] = t;
+    }
+  }
   if (threadIdx.x == 32) {
     if (wide) __hip_atomic_store(amb_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const double ns = (double)cnt_sh[0];
@@ -998,7 +1166,13 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   // wave 0's first lane advances the loop state; the other waves re-arm the iteration's scratch meanwhile (every
   // block has read hist3 / the window table by now)
   if (threadIdx.x == 0) {
-    if (fuse_update) icp_update_lane<MIN>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh);
+    if constexpr (RB) {   // (the weighted launches always run the update themselves)
+      RobustIter ri;
+      ri.used = (long long)red[0][32]; ri.bad = red[1][32]; ri.scale = rb_scale; ri.median = rb_med;
+      ri.recomputed = (chain.rb.mad && chain.rb_recompute) ? 1 : 0; ri.mad = chain.rb.mad;
+      ri.state = chain.rb_state; ri.trace = chain.rb_trace;
+      icp_update_lane<MIN, true>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh, &ri);
+    } else if (fuse_update) icp_update_lane<MIN>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh);
     else if (sel_aux && fail_sh) sel_aux[kSelFailFlag] = 1u;   // the stand-alone update kernel reads it there
   } else if (threadIdx.x >= 64) {
     const int t = (int)threadIdx.x - 64;

@@ -80,13 +80,20 @@ class IcpHandle:
     """One lsgpu_icp handle == one reference ``icp_`` member: one device, one HIP stream."""
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
-                 matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None):
+                 matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
+                 robust=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
         outlier_max_dist / outlier_min_dist / outlier_median_factor: Max- / Min- / MedianDistOutlierFilter's parameter
-        (None: cfg's; 0: no such module; see lsgpu_icp_config)."""
+        (None: cfg's; 0: no such module; see lsgpu_icp_config).  robust: None, or RobustOutlierFilter's parameters (a
+        RobustConfig, a dict of its fields, or an _lib.RobustCfg) -- lsgpu_icp_set_robust_filter."""
         L = _lib.lib()
+        rb = robust_cfg(robust) if robust is not None else None
+        if rb is not None:                                      # refused values: before the device is touched
+            mini = _MINIMIZERS.get(error_minimizer, error_minimizer) if error_minimizer is not None else (cfg.error_minimizer if cfg is not None else 0)
+            if L.lsgpu_robust_config_check(C.byref(rb), int(mini), 1) != _lib.OK:
+                raise LsgpuError(_lib.BAD_CONFIG, "lsgpu_robust_config_check", "RobustOutlierFilter: " + _robust_why(rb))
         if cfg is None:
             cfg = IcpConfig()
             L.lsgpu_icp_config_yaml(C.byref(cfg))
@@ -108,6 +115,24 @@ class IcpHandle:
         if rc != _lib.OK:
             self._h = None
             _raise(rc, "lsgpu_icp_create (is a ROCm GPU visible?)")
+        self.robust = None
+        if rb is not None:
+            self.set_robust_filter(rb)
+
+    def set_robust_filter(self, robust):
+        """lsgpu_icp_set_robust_filter: RobustOutlierFilter on this handle (None removes it)."""
+        rb = robust_cfg(robust) if robust is not None else None
+        rc = _lib.lib().lsgpu_icp_set_robust_filter(self._h, C.byref(rb) if rb is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_robust_filter", self._h)
+        self.robust = rb
+
+    def robust_trace(self, cap: int = 64):
+        """lsgpu_icp_get_robust_trace: per iteration of the last align {median, scale, w_sum, recomputed}."""
+        buf = (_lib.RobustTrace * cap)()
+        n = _lib.lib().lsgpu_icp_get_robust_trace(self._h, buf, cap)
+        return [dict(median=np.float32(buf[i].median), scale=np.float32(buf[i].scale), w_sum=float(buf[i].w_sum),
+                     recomputed=int(buf[i].recomputed)) for i in range(n)]
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None and _lib._lib is not None:
@@ -587,6 +612,80 @@ def point_to_point_solve(sums) -> np.ndarray:
     return out.reshape(4, 4).T.copy()
 
 
+def point_to_plane_solve(sums) -> np.ndarray:
+    """lsgpu_point_to_plane_solve: the point-to-plane step dT (4x4 float32) from the first 27 sums of lsgpu_normal_eq --
+    host only, the same function the device loop runs.  Raises ConvergenceError if A is not positive definite."""
+    s = np.ascontiguousarray(sums, np.float64).ravel()
+    if s.size < 27:
+        raise ValueError("expected at least 27 sums")
+    out = np.empty(16, np.float32)
+    rc = _lib.lib().lsgpu_point_to_plane_solve(s.ctypes.data_as(C.POINTER(C.c_double)), _fp(out))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_point_to_plane_solve")
+    return out.reshape(4, 4).T.copy()
+
+
+@dataclass
+class RobustConfig:
+    """RobustOutlierFilter's parameters, with the module's defaults."""
+    robust_fct: str = "cauchy"
+    tuning: float = 1.0
+    scale_estimator: str = "mad"
+    nb_iteration_for_scale: int = 0
+    distance_type: str = "point2point"
+    approximation: float = math.inf
+
+
+def robust_cfg(r) -> "_lib.RobustCfg":
+    """RobustConfig / dict of its fields / _lib.RobustCfg -> _lib.RobustCfg.  Unknown names raise (bad config)."""
+    if isinstance(r, _lib.RobustCfg):
+        return r
+    if isinstance(r, dict):
+        r = RobustConfig(**r)
+    for table, v, what in ((_lib.ROBUST_FCT, r.robust_fct, "robustFct"), (_lib.ROBUST_SCALE, r.scale_estimator, "scaleEstimator"),
+                           (_lib.ROBUST_DIST, r.distance_type, "distanceType")):
+        if v not in table:
+            raise LsgpuError(_lib.BAD_CONFIG, "RobustOutlierFilter", f"RobustOutlierFilter: unknown {what} {v}")
+    return _lib.RobustCfg(_lib.ROBUST_FCT[r.robust_fct], float(r.tuning), _lib.ROBUST_SCALE[r.scale_estimator],
+                          int(r.nb_iteration_for_scale), _lib.ROBUST_DIST[r.distance_type], float(r.approximation))
+
+
+def _robust_why(rb) -> str:
+    if rb.robust_fct in (_lib.ROBUST_FCT["welsch"], _lib.ROBUST_FCT["student"]):
+        return "robustFct welsch / student are not implemented (exp / pow are not bit-identical between host and device)"
+    if rb.scale_estimator in (_lib.ROBUST_SCALE["berg"], _lib.ROBUST_SCALE["std"]):
+        return "scaleEstimator berg / std are not implemented (none and mad are)"
+    if not rb.tuning >= 0:
+        return "tuning must be >= 0"
+    if not rb.approximation >= 0:
+        return "approximation must be >= 0"
+    if rb.nb_iteration_for_scale < 0:
+        return "nbIterationForScale must be >= 0"
+    return "refused configuration"
+
+
+def robust_scale(d2):
+    """lsgpu_robust_scale: (median, MAD scale) of the finite entries of d2, float32 -- the device loop's, bit for bit."""
+    a = np.ascontiguousarray(d2, np.float32).ravel()
+    med, sc = C.c_float(), C.c_float()
+    rc = _lib.lib().lsgpu_robust_scale(a.ctypes.data if a.size else None, a.size, C.byref(med), C.byref(sc))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_robust_scale")
+    return np.float32(med.value), np.float32(sc.value)
+
+
+def robust_weights(robust, scale, e) -> np.ndarray:
+    """lsgpu_robust_weights: the weights of e (d2, or r r for point2plane) -- the device loop's, bit for bit."""
+    rb = robust_cfg(robust)
+    a = np.ascontiguousarray(e, np.float32).ravel()
+    w = np.empty(a.size, np.float32)
+    rc = _lib.lib().lsgpu_robust_weights(C.byref(rb), float(scale), a.ctypes.data if a.size else None, a.size,
+                                         w.ctypes.data if a.size else None)
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_robust_weights")
+    return w
+
+
 def check_rigid(T) -> bool:
     return bool(_lib.lib().lsgpu_check_rigid(_fp(_t16(T))))
 
@@ -609,7 +708,7 @@ _SUPPORTED = {
     "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter", "SurfaceNormalDataPointsFilter"},
     "matcher": {"KDTreeMatcher"},
     "outlierFilters": {"TrimmedDistOutlierFilter", "MaxDistOutlierFilter", "MinDistOutlierFilter",
-                       "MedianDistOutlierFilter"},
+                       "MedianDistOutlierFilter", "RobustOutlierFilter"},
     "errorMinimizer": {"PointToPlaneErrorMinimizer", "PointToPointErrorMinimizer"},
     "transformationCheckers": {"CounterTransformationChecker", "DifferentialTransformationChecker"},
 }
@@ -637,7 +736,20 @@ class ChainConfig:
     outlier_max_dist: float = 0.0           # MaxDistOutlierFilter maxDist [m]; 0: no such module
     outlier_min_dist: float = 0.0           # MinDistOutlierFilter minDist [m]; 0: no such module (or minDist 0: keeps all)
     outlier_median_factor: float = 0.0      # MedianDistOutlierFilter factor; 0: no such module
-    extra: dict = field(default_factory=dict)
+    extra: dict = field(default_factory=dict)   # "robust": RobustOutlierFilter's parameters (see `robust`)
+
+    @property
+    def robust(self) -> Optional["RobustConfig"]:
+        """RobustOutlierFilter's parameters (a RobustConfig); None: no such module.  Kept in `extra`, so that the fields of
+        a chain without the module are what they were."""
+        return self.extra.get("robust")
+
+    @robust.setter
+    def robust(self, value):
+        if value is None:
+            self.extra.pop("robust", None)
+        else:
+            self.extra["robust"] = value
 
 
 class ICP:
@@ -776,6 +888,33 @@ class ICP:
                     ch.outlier_median_factor = one_float(name, params, "factor", 3.0)
                     if not 0.0 < ch.outlier_median_factor < math.inf:
                         bad(f"MedianDistOutlierFilter: factor must be > 0 and finite (got {ch.outlier_median_factor})")
+                elif name == "RobustOutlierFilter":
+                    only(name, params, "robustFct", "tuning", "scaleEstimator", "nbIterationForScale", "distanceType",
+                         "approximation")
+                    rb = RobustConfig(str(params.get("robustFct", "cauchy")), one_float(name, params, "tuning", 1.0),
+                                      str(params.get("scaleEstimator", "mad")), 0,
+                                      str(params.get("distanceType", "point2point")),
+                                      one_float(name, params, "approximation", math.inf))
+                    nb = one_float(name, params, "nbIterationForScale", 0)
+                    if nb < 0 or nb != int(nb):
+                        bad(f"{name}: nbIterationForScale must be an integer >= 0 (got {params.get('nbIterationForScale')})")
+                    rb.nb_iteration_for_scale = int(nb)
+                    if rb.robust_fct in ("welsch", "student"):
+                        bad(f"{name}: robustFct {rb.robust_fct} is not implemented on the HIP path (exp / pow are not "
+                            "bit-identical between host and device)")
+                    if rb.robust_fct not in _lib.ROBUST_FCT:
+                        bad(f"{name}: unknown robustFct {rb.robust_fct}")
+                    if rb.scale_estimator in ("berg", "std"):
+                        bad(f"{name}: scaleEstimator {rb.scale_estimator} is not implemented on the HIP path (none and mad are)")
+                    if rb.scale_estimator not in _lib.ROBUST_SCALE:
+                        bad(f"{name}: unknown scaleEstimator {rb.scale_estimator}")
+                    if rb.distance_type not in _lib.ROBUST_DIST:
+                        bad(f"{name}: unknown distanceType {rb.distance_type}")
+                    if not rb.tuning >= 0.0:
+                        bad(f"{name}: tuning must be >= 0 (got {rb.tuning})")
+                    if not rb.approximation >= 0.0:
+                        bad(f"{name}: approximation must be >= 0 (got {rb.approximation})")
+                    ch.robust = rb
                 elif name in _MINIMIZERS:
                     if "minimizer" in seen:
                         raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "errorMinimizer: one module at most")
@@ -806,6 +945,8 @@ class ICP:
                           ("CounterTransformationChecker", "the loop would not stop")):
             if need not in seen and not (p2p and need == "reference normals"):
                 raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{labels.get(need, need)} is required ({why})")
+        if ch.robust is not None and ch.robust.distance_type == "point2plane" and "reference normals" not in seen:
+            bad("RobustOutlierFilter: distanceType point2plane needs reference normals (a referenceDataPointsFilters module)")
         # inspector / logger (yaml:32-44) only produce debug dumps: accepted and ignored
         self.chain = ch
         self._handle = None
@@ -821,7 +962,8 @@ class ICP:
             cfg.smooth_length = self.chain.smooth_length
             self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer, self.chain.matcher_knn,
                                      self.chain.matcher_max_dist, self.chain.outlier_max_dist,
-                                     self.chain.outlier_min_dist, self.chain.outlier_median_factor)
+                                     self.chain.outlier_min_dist, self.chain.outlier_median_factor,
+                                     robust=self.chain.robust)
         return self._handle
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
