@@ -62,7 +62,7 @@ typedef struct lsgpu_icp_config {
   float min_diff_rot;     /* Differential... minDiffRotErr   [rad]     yaml:25  (0.001) */
   float min_diff_trans;   /* Differential... minDiffTransErr [m]       yaml:26  (0.01)  */
   int   smooth_length;    /* Differential... smoothLength              yaml:27  (4)     */
-  float cell_size;        /* finest voxel edge [m]; <= 0: automatic                      */
+  float cell_size;        /* finest voxel edge [m]; <= 0: automatic; NaN / +inf: BAD_CONFIG (see "The voxel grid's geometry") */
   int   profile_kernels;  /* 1: HIP-event time every kNN launch (see lsgpu_icp_stats)    */
   int   reserved[1];      /* reserved[0] = 1 disables the trimmed-radius cap (debug)       */
   int   error_minimizer;  /* LSGPU_MINIMIZER_* (0, the default: point-to-plane); any other value: LSGPU_BAD_CONFIG */
@@ -74,6 +74,15 @@ typedef struct lsgpu_icp_config {
   float outlier_median_factor;  /* MedianDistOutlierFilter factor: keep d2 <= factor * median(d2)                           */
   int   reserved_[1];
 } lsgpu_icp_config;
+
+/* The voxel grid's geometry (lsgpu_icp_config.cell_size; read by every lsgpu_icp_set_reference, reported by
+ * lsgpu_icp_get_info).  The level-0 cell edge starts at h0 = cell_size if cell_size > 0, else 0.125 m (any value <= 0,
+ * -inf included, is "automatic").  With ext the longest edge of the reference's bounding box: bits_per_axis grows from 11
+ * to 13 (fine_bits falls from 5 to 3) while h0 * (2^bits - 1) < 1.0001 ext, then h0 doubles until the box fits.  So every
+ * finite positive cell_size is legal, however small (the doubling ends after at most a few hundred steps) or large (the whole
+ * cloud in one cell); it changes the time a search takes, never a result.  NaN and +inf are LSGPU_BAD_CONFIG from
+ * lsgpu_icp_create, checked before the device is touched.  A reference with a NaN or infinite coordinate is LSGPU_BAD_ARG
+ * from lsgpu_icp_set_reference ("non-finite coordinates" in lsgpu_last_error); the handle then holds no reference. */
 
 /* maxDist and outlier-filter chains.  All comparisons on squared distances in float; maxDist * maxDist etc. are one
  * float multiply.

@@ -471,6 +471,8 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
       !(cfg->outlier_min_dist >= 0.f) || std::isinf(cfg->outlier_min_dist) ||
       !(cfg->outlier_median_factor >= 0.f) || std::isinf(cfg->outlier_median_factor))
     return LSGPU_BAD_CONFIG;
+  // the level-0 cell edge: <= 0 automatic, any finite positive value legal; NaN / +inf have no grid (hf = inf, inv_hf = 0)
+  if (std::isnan(cfg->cell_size) || (std::isinf(cfg->cell_size) && cfg->cell_size > 0.f)) return LSGPU_BAD_CONFIG;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     (void)hipGetLastError();
