@@ -28,7 +28,9 @@
  * (lsgpu_icp_config.error_minimizer), KDTreeMatcher with knn 1..LSGPU_MATCHER_KNN_MAX (lsgpu_icp_config.matcher_knn) and
  * maxDist (matcher_max_dist), any subset of Trimmed- / Max- / Min- / MedianDistOutlierFilter (outlier_*), and
  * SurfaceNormalDataPointsFilter in place of SamplingSurfaceNormalDataPointsFilter as the reference filter
- * (lsgpu_chain_config.sn_knn), and RobustOutlierFilter (lsgpu_icp_set_robust_filter).
+ * (lsgpu_chain_config.sn_knn), and RobustOutlierFilter (lsgpu_icp_set_robust_filter), and SurfaceNormalOutlierFilter with
+ * SurfaceNormalDataPointsFilter on the reading and ObservationDirection- + OrientNormalsDataPointsFilter on either cloud
+ * (lsgpu_icp_set_normals).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -516,6 +518,67 @@ int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap);
  * Host only; the same function the device loop runs, bit for bit -- the sibling of lsgpu_point_to_point_solve.
  * LSGPU_NO_CONVERGENCE if A is not positive definite. */
 int lsgpu_point_to_plane_solve(const double sums[27], float dT[16]);
+
+/* ---- SurfaceNormalOutlierFilter, reading normals and oriented normals (DESIGN.md §3 "SurfaceNormalOutlierFilter", §5 choices 24-29) ----
+ * SurfaceNormalOutlierFilter (maxAngle): eps = (float)cos((double)maxAngle), taken once when the filter is given to the handle.
+ *   Per iteration, for reading point x and each of its k matches: an invalid match has weight 0; else
+ *   nr = normalized(R_iter n0[x]), n0 = R_init n_reading[x] the reading normal as step 5 of ICP::compute moves it with the
+ *   reading (once per alignment; R_iter is the rotation of the iteration's T_iter and is applied to n0, never to the last
+ *   iteration's result), both rotations with the fma chain of lsgpu_rotate_descriptors; nf = normalized(n_reference[id]);
+ *   v = fma(nr.z, nf.z, fma(nr.y, nf.y, nr.x nf.x)); weight 0 iff v < eps (a NaN v keeps the pair).
+ *   normalized(a) = a / sqrtf(fma(az, az, fma(ay, ay, ax ax))), a vector of length 0 stays as it is.
+ *   The weight multiplies those of the other outlier filters: the trim / median order statistics still see every valid
+ *   distance, n_used counts the pairs of weight > 0, limit keeps its meaning, nothing kept is LSGPU_NO_CONVERGENCE.
+ *   Without reading normals (plain lsgpu_icp_align) or without reference normals the filter is inert.  A handle with the
+ *   filter takes the chain plan; lsgpu_icp_comm_init refuses it.  lsgpu_normal_eq / lsgpu_point_to_point are handed no
+ *   reading normals and do not apply the test.
+ * Orientation (ObservationDirectionDataPointsFilter {x, y, z} directly followed by OrientNormalsDataPointsFilter
+ *   {towardCenter}): for every point p of the cloud in the frame it was given in, o = sensor - p (three float subtractions),
+ *   s = fma(o.z, n.z, fma(o.y, n.y, o.x n.x)); n is negated if s < 0 (towardCenter 1) or s > 0 (towardCenter 0).
+ * Reading normals (reading_sn_knn): the contract of lsgpu_icp_filter_reference_normals on the reading's KEPT points (after
+ *   RandomSamplingDataPointsFilter); fewer kept points than knn: LSGPU_BAD_ARG.  lsgpu_icp_compute then runs on one stream
+ *   (the reading's side cannot overlap the reference's grid build: both use the handle's grid). */
+typedef struct lsgpu_normals_config {
+  float max_angle;              /* SurfaceNormalOutlierFilter maxAngle [rad], 0 .. 3.1416 (1.57); < 0: no such filter      */
+  int   reading_sn_knn;         /* SurfaceNormalDataPointsFilter on the reading: knn 3..32; 0: absent                      */
+  int   reading_orient;         /* orientation pair on the reading: 0 off, 1 towardCenter, 2 away                          */
+  int   reference_orient;       /* ... on the reference                                                                    */
+  float reading_sensor[3];      /* ObservationDirectionDataPointsFilter x, y, z of the reading section                     */
+  float reference_sensor[3];    /* ... of the reference section                                                            */
+  int   reading_normals_given;  /* 1: the caller hands the reading normals to lsgpu_icp_align_normals (kernel-level use)   */
+  int   reserved[1];            /* 0 */
+} lsgpu_normals_config;
+void lsgpu_normals_config_default(lsgpu_normals_config* c);   /* no filter, no reading normals, no orientation */
+/* Without a handle or a device: LSGPU_OK, or LSGPU_BAD_CONFIG for a value out of range, an orientation without normals in
+ * front of it, the outlier filter without reading normals or without reference normals (have_reference_normals 0), or
+ * reading normals that no module reads (max_angle < 0). */
+int lsgpu_normals_config_check(const lsgpu_normals_config* c, int error_minimizer, int have_reference_normals);
+/* Gives the handle the configuration (copied), NULL removes it.  Bad values: LSGPU_BAD_CONFIG before the device is touched. */
+int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg);
+/* SurfaceNormalDataPointsFilter on a reading, then (orient 1 / 2) the orientation towards / away from sensor[3] (nullable
+ * with orient 0): out_normals 3 floats per point, in the cloud's order.  The search runs on a grid of its own: the
+ * handle's reference is what it was. */
+int lsgpu_icp_reading_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, int orient, const float sensor[3],
+                              float* out_normals);
+/* lsgpu_icp_align with the reading's normals (3 floats per point, the reading's order; NULL: lsgpu_icp_align). */
+int lsgpu_icp_align_normals(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reading_normals,
+                            const float T_init[16], float T_out[16], lsgpu_icp_stats* stats);
+/* The reference normals the handle holds, in the order the reference was given to set_reference (3 floats per point; after
+ * lsgpu_icp_compute: the filtered reference's).  LSGPU_BAD_ARG without normals. */
+int lsgpu_icp_get_reference_normals(lsgpu_icp* h, float* out_normals, int64_t cap_points);
+/* Host twins (no GPU, no handle), bit-identical with the device.  lsgpu_orient_normals flips `normals` in place (mode 1 / 2).
+ * lsgpu_normal_angle_weights: w[i k + j] of reading point i's j-th match ids[i k + j] (< 0: invalid, weight 0) under T
+ * (4x4 column major: its rotation is applied to reading_normals, which are n0 above). */
+int lsgpu_orient_normals(const float* xyz1, int64_t n, const float sensor[3], int mode, float* normals);
+int lsgpu_normal_angle_weights(const float T[16], const float* reading_normals, int64_t nq, const float* reference_normals,
+                               const int32_t* ids, int k, float max_angle, float* w);
+/* One record per iteration of the last align that applied the filter; returns the number written. */
+typedef struct lsgpu_normal_angle_trace {
+  int64_t rejected;   /* pairs the angle test alone rejected: valid, kept by every binary distance filter, v < eps */
+  float   eps;
+  int     reserved;
+} lsgpu_normal_angle_trace;
+int lsgpu_icp_get_normal_angle_trace(lsgpu_icp* h, lsgpu_normal_angle_trace* out, int cap);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

@@ -106,6 +106,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_robust_filter: " + why);
       }
+      if (has_normals_ && lsgpu_icp_set_normals(h_, &normals_) != LSGPU_OK) {   // SurfaceNormalOutlierFilter / normals of the loaded chain
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_normals: " + why);
+      }
     }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
@@ -126,6 +131,8 @@ class LsgpuICP {
     sn_knn_ = parsed.referenceNormalKnn();
     has_robust_ = parsed.robustFilter() != nullptr;
     if (has_robust_) robust_ = *parsed.robustFilter();
+    has_normals_ = parsed.normalsConfig() != nullptr;
+    if (has_normals_) normals_ = *parsed.normalsConfig();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -138,6 +145,8 @@ class LsgpuICP {
   int sn_knn_ = 0;                                      // SurfaceNormalDataPointsFilter as the reference filter (0: absent)
   lsgpu_robust_config robust_{};                        // RobustOutlierFilter's parameters ...
   bool has_robust_ = false;                             // ... if the chain holds one
+  lsgpu_normals_config normals_{};                      // SurfaceNormalOutlierFilter, reading normals, orientation pairs ...
+  bool has_normals_ = false;                            // ... if the chain holds any of them
   int64_t seed_ = -1;
 };
 

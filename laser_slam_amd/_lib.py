@@ -36,6 +36,9 @@ ABI_SYMBOLS = [
     "lsgpu_icp_filter_reference_normals", "lsgpu_filter_surface_normal", "lsgpu_chain_config_check",
     "lsgpu_robust_config_default", "lsgpu_robust_config_check", "lsgpu_icp_set_robust_filter", "lsgpu_robust_scale",
     "lsgpu_robust_weights", "lsgpu_icp_get_robust_trace", "lsgpu_point_to_plane_solve",
+    "lsgpu_normals_config_default", "lsgpu_normals_config_check", "lsgpu_icp_set_normals", "lsgpu_icp_reading_normals",
+    "lsgpu_icp_align_normals", "lsgpu_icp_get_reference_normals", "lsgpu_orient_normals", "lsgpu_normal_angle_weights",
+    "lsgpu_icp_get_normal_angle_trace",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -49,6 +52,18 @@ class RobustCfg(C.Structure):
     _fields_ = [("robust_fct", C.c_int), ("tuning", C.c_float), ("scale_estimator", C.c_int),
                 ("nb_iteration_for_scale", C.c_int), ("distance_type", C.c_int), ("approximation", C.c_float),
                 ("reserved", C.c_int * 2)]
+
+
+class NormalsCfg(C.Structure):
+    """lsgpu_normals_config (include/lsgpu_icp.h): SurfaceNormalOutlierFilter, reading normals, oriented normals."""
+    _fields_ = [("max_angle", C.c_float), ("reading_sn_knn", C.c_int), ("reading_orient", C.c_int),
+                ("reference_orient", C.c_int), ("reading_sensor", C.c_float * 3), ("reference_sensor", C.c_float * 3),
+                ("reading_normals_given", C.c_int), ("reserved", C.c_int * 1)]
+
+
+class NormalAngleTrace(C.Structure):
+    """lsgpu_normal_angle_trace: one record per iteration of an align that applied SurfaceNormalOutlierFilter."""
+    _fields_ = [("rejected", C.c_int64), ("eps", C.c_float), ("reserved", C.c_int)]
 
 
 class RobustTrace(C.Structure):
@@ -261,6 +276,16 @@ def lib() -> C.CDLL:
     L.lsgpu_robust_weights.argtypes = [C.POINTER(RobustCfg), C.c_float, fp, i64, fp]
     L.lsgpu_icp_get_robust_trace.argtypes = [vp, C.POINTER(RobustTrace), C.c_int]
     L.lsgpu_point_to_plane_solve.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_float)]
+    L.lsgpu_normals_config_default.argtypes = [C.POINTER(NormalsCfg)]
+    L.lsgpu_normals_config_default.restype = None
+    L.lsgpu_normals_config_check.argtypes = [C.POINTER(NormalsCfg), C.c_int, C.c_int]
+    L.lsgpu_icp_set_normals.argtypes = [vp, C.POINTER(NormalsCfg)]
+    L.lsgpu_icp_reading_normals.argtypes = [vp, fp, i64, C.c_int, C.c_int, C.POINTER(C.c_float), fp]
+    L.lsgpu_icp_align_normals.argtypes = [vp, fp, i64, fp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(IcpStats)]
+    L.lsgpu_icp_get_reference_normals.argtypes = [vp, fp, i64]
+    L.lsgpu_orient_normals.argtypes = [fp, i64, C.POINTER(C.c_float), C.c_int, fp]
+    L.lsgpu_normal_angle_weights.argtypes = [C.POINTER(C.c_float), fp, i64, fp, vp, C.c_int, C.c_float, fp]
+    L.lsgpu_icp_get_normal_angle_trace.argtypes = [vp, C.POINTER(NormalAngleTrace), C.c_int]
     _lib = L
     return L
 

@@ -248,7 +248,7 @@ class ICP {
   // PointToPlane / Counter 40 + Differential 1e-3, 1e-3, 3
   void setDefault() {
     lsgpu_icp_config_default(&cfg_);
-    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f; sn_knn_ = 0; has_robust_ = false;
+    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f; sn_knn_ = 0; has_robust_ = false; has_normals_ = false;
     release();
   }
 
@@ -273,6 +273,13 @@ class ICP {
          has_robust = false;
     lsgpu_robust_config rb;
     lsgpu_robust_config_default(&rb);
+    // SurfaceNormalOutlierFilter, SurfaceNormalDataPointsFilter on the reading, the orientation pair (ObservationDirection
+    // directly followed by OrientNormals, directly behind the module that produces the normals) on either side
+    lsgpu_normals_config nc;
+    lsgpu_normals_config_default(&nc);
+    int rd_stage = 0, ref_stage = 0;   // 1 sampling (reading) / normals (reference), 2 reading normals, 3 ObservationDirection, 4 OrientNormals
+    const char* const kPair = " is implemented only as the pair ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter "
+                              "directly behind the module that produces the normals";
     prob = -1.0f;   // no reading filter module: lsgpu_chain_config::reading_prob < 0 (every point, no draws)
     c.trim_ratio = 1.0f;
     for (const auto& m : mods) {
@@ -305,20 +312,10 @@ class ICP {
           if (!ok) throw ConfigError(mod + ": unknown parameter " + kv.first);
         }
       };
-      if (sec == "readingDataPointsFilters" && name == "RandomSamplingDataPointsFilter") {
-        if (has_reading) throw ConfigError("readingDataPointsFilters: one RandomSamplingDataPointsFilter at most");
-        has_reading = true; prob = (float)num("prob", 0.75);
-      } else if (sec == "referenceDataPointsFilters" && name == "SamplingSurfaceNormalDataPointsFilter") {
-        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
-        has_reference = true;
-        knn = (int)num("knn", 7); ratio = (float)num("ratio", 0.5);
-        if ((int)num("samplingMethod", 0) != 0) throw ConfigError("samplingMethod != 0 is not implemented");
-      } else if (sec == "referenceDataPointsFilters" && name == "SurfaceNormalDataPointsFilter") {
-        // every point, the normal of its knn nearest neighbours: keepNormals 1 alone, exact (epsilon 0), no maxDist
-        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
+      // SurfaceNormalDataPointsFilter's parameters (either side): keepNormals 1 alone, exact (epsilon 0), no maxDist -> knn
+      auto sn_params = [&]() {
         only(name, {"knn", "epsilon", "maxDist", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
                     "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"});
-        has_reference = true;
         const double k = fnum(name, "knn", 5);
         if (!(k >= 3 && k <= 32) || k != (double)(int)k) throw ConfigError(name + ": knn must be in [3, 32]");
         if (fnum(name, "epsilon", 0.0) != 0.0) throw ConfigError(name + ": epsilon must be 0 (the search is exact)");
@@ -328,7 +325,54 @@ class ICP {
         for (const char* key : {"keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
                                 "sortEigen", "smoothNormals"})
           if (fnum(name, key, 0) != 0.0) throw ConfigError(name + ": " + key + " must be 0 or absent");
-        sn_knn = (int)k;
+        return (int)k;
+      };
+      const bool rd_sec = sec == "readingDataPointsFilters", ref_sec = sec == "referenceDataPointsFilters";
+      if (rd_sec && name == "RandomSamplingDataPointsFilter") {
+        if (has_reading) throw ConfigError("readingDataPointsFilters: one RandomSamplingDataPointsFilter at most");
+        if (rd_stage >= 2)
+          throw ConfigError("readingDataPointsFilters: SurfaceNormalDataPointsFilter before RandomSamplingDataPointsFilter is not "
+                            "implemented (the normals would have to be gathered through the sampling)");
+        has_reading = true; prob = (float)num("prob", 0.75); rd_stage = 1;
+      } else if (rd_sec && name == "SurfaceNormalDataPointsFilter") {
+        if (rd_stage >= 2) throw ConfigError("readingDataPointsFilters: SurfaceNormalDataPointsFilter given twice");
+        nc.reading_sn_knn = sn_params(); rd_stage = 2;
+      } else if ((rd_sec || ref_sec) && name == "ObservationDirectionDataPointsFilter") {
+        int& stage = rd_sec ? rd_stage : ref_stage;
+        if (stage != (rd_sec ? 2 : 1)) throw ConfigError(sec + ": " + name + kPair);
+        only(name, {"x", "y", "z"});
+        float* sv = rd_sec ? nc.reading_sensor : nc.reference_sensor;
+        const char* keys[3] = {"x", "y", "z"};
+        for (int i = 0; i < 3; ++i) {
+          const double v = fnum(name, keys[i], 0.0);
+          if (std::isinf(v)) throw ConfigError(name + ": x, y, z must be finite");
+          sv[i] = (float)v;
+        }
+        stage = 3;
+      } else if ((rd_sec || ref_sec) && name == "OrientNormalsDataPointsFilter") {
+        int& stage = rd_sec ? rd_stage : ref_stage;
+        if (stage != 3) throw ConfigError(sec + ": " + name + kPair);
+        only(name, {"towardCenter"});
+        const double tc = fnum(name, "towardCenter", 1);
+        if (tc != 0.0 && tc != 1.0) throw ConfigError(name + ": towardCenter must be 0 or 1");
+        (rd_sec ? nc.reading_orient : nc.reference_orient) = tc == 1.0 ? 1 : 2;
+        stage = 4;
+      } else if (sec == "outlierFilters" && name == "SurfaceNormalOutlierFilter") {
+        if (nc.max_angle >= 0.f) throw ConfigError("outlierFilters: one SurfaceNormalOutlierFilter at most");
+        only(name, {"maxAngle"});
+        const double a = fnum(name, "maxAngle", 1.57);
+        if (!(a >= 0.0 && a <= 3.1416)) throw ConfigError(name + ": maxAngle must be in [0, 3.1416]");
+        nc.max_angle = (float)a;
+      } else if (sec == "referenceDataPointsFilters" && name == "SamplingSurfaceNormalDataPointsFilter") {
+        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
+        has_reference = true; ref_stage = 1;
+        knn = (int)num("knn", 7); ratio = (float)num("ratio", 0.5);
+        if ((int)num("samplingMethod", 0) != 0) throw ConfigError("samplingMethod != 0 is not implemented");
+      } else if (sec == "referenceDataPointsFilters" && name == "SurfaceNormalDataPointsFilter") {
+        // every point, the normal of its knn nearest neighbours: keepNormals 1 alone, exact (epsilon 0), no maxDist
+        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
+        sn_knn = sn_params();
+        has_reference = true; ref_stage = 1;
       } else if (sec == "matcher" && name == "KDTreeMatcher") {
         has_matcher = true;
         // knn 1..LSGPU_MATCHER_KNN_MAX, exact search only, maxDist; its other parameters (searchType, ...) are not read
@@ -415,9 +459,24 @@ class ICP {
       throw ConfigError(rb.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE && !has_reference
                             ? "RobustOutlierFilter: distanceType point2plane needs reference normals (a referenceDataPointsFilters module)"
                             : "RobustOutlierFilter: refused configuration");
+    if (rd_stage == 3 || ref_stage == 3)
+      throw ConfigError(std::string(rd_stage == 3 ? "readingDataPointsFilters" : "referenceDataPointsFilters") +
+                        ": ObservationDirectionDataPointsFilter" + kPair);
+    const bool has_normals = nc.max_angle >= 0.f || nc.reading_sn_knn != 0 || nc.reading_orient != 0 || nc.reference_orient != 0;
+    if (nc.reading_sn_knn != 0 && !(nc.max_angle >= 0.f))
+      throw ConfigError("readingDataPointsFilters: module SurfaceNormalDataPointsFilter is not implemented on the HIP path unless the "
+                        "chain holds SurfaceNormalOutlierFilter (no other module reads reading normals)");
+    if (nc.max_angle >= 0.f && nc.reading_sn_knn == 0)
+      throw ConfigError("SurfaceNormalOutlierFilter: the reading section provides no normals (SurfaceNormalDataPointsFilter in "
+                        "readingDataPointsFilters)");
+    if (nc.max_angle >= 0.f && !has_reference)
+      throw ConfigError("SurfaceNormalOutlierFilter: the reference section provides no normals (a referenceDataPointsFilters module)");
+    if (has_normals && lsgpu_normals_config_check(&nc, c.error_minimizer, has_reference ? 1 : 0) != LSGPU_OK)
+      throw ConfigError("SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter: refused configuration");
     if (!has_counter) throw ConfigError("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
     if (!has_differential) { c.min_diff_rot = -1.f; c.min_diff_trans = -1.f; c.smooth_length = 1; }  // never satisfied: the counter stops
     cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio; sn_knn_ = sn_knn; robust_ = rb; has_robust_ = has_robust;
+    normals_ = nc; has_normals_ = has_normals;
     release();
   }
 
@@ -574,6 +633,8 @@ class ICP {
   int referenceNormalKnn() const { return sn_knn_; }       // SurfaceNormalDataPointsFilter's knn (0: no such module)
   float surfaceNormalRatio() const { return ratio_; }
   const lsgpu_robust_config* robustFilter() const { return has_robust_ ? &robust_ : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
+  // SurfaceNormalOutlierFilter / reading normals / the orientation pairs (nullptr: none of these modules)
+  const lsgpu_normals_config* normalsConfig() const { return has_normals_ ? &normals_ : nullptr; }
 
  private:
   using Module = detail::YamlModule;
@@ -628,6 +689,11 @@ class ICP {
       release();
       throw ConfigError(msg);
     }
+    if (has_normals_ && lsgpu_icp_set_normals(h_, &normals_) != LSGPU_OK) {
+      const std::string msg = std::string("lsgpu_icp_set_normals: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
   }
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
   void check(int rc, const char* what) {
@@ -647,6 +713,8 @@ class ICP {
   int sn_knn_ = 0;
   lsgpu_robust_config robust_{};
   bool has_robust_ = false;
+  lsgpu_normals_config normals_{};
+  bool has_normals_ = false;
   int64_t seed_ = -1;
   unsigned generation_ = 0;
 #ifdef LSGPU_TEST_SEAMS

@@ -20,6 +20,7 @@
 #include "../../include/lsgpu_icp.h"
 #include "lsgpu_box_normal.h"
 #include "lsgpu_robust.h"
+#include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
 
 namespace {
@@ -274,6 +275,49 @@ int lsgpu_robust_weights(const lsgpu_robust_config* cfg, float scale, const floa
   if (lsgpu::robust::check(cfg, LSGPU_MINIMIZER_POINT_TO_PLANE, 1, nullptr) != LSGPU_OK) return LSGPU_BAD_CONFIG;
   const lsgpu::robust::Params p = lsgpu::robust::params(*cfg);
   for (int64_t i = 0; i < n; ++i) w_out[i] = lsgpu::robust::weight(p.fct, e[i], scale, p.k, p.approx2);
+  return LSGPU_OK;
+}
+
+// ---- SurfaceNormalOutlierFilter and the orientation step: the host twins of the device code (csrc/lsgpu_normal_angle.h)
+void lsgpu_normals_config_default(lsgpu_normals_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->max_angle = -1.f;
+}
+
+int lsgpu_normals_config_check(const lsgpu_normals_config* c, int error_minimizer, int have_reference_normals) {
+  return lsgpu::normal_angle::check(c, error_minimizer, have_reference_normals, nullptr);
+}
+
+int lsgpu_orient_normals(const float* xyz1, int64_t n, const float sensor[3], int mode, float* normals) {
+  if (n < 0 || (mode != 1 && mode != 2) || !sensor || (n > 0 && (!xyz1 || !normals))) return LSGPU_BAD_ARG;
+  for (int64_t i = 0; i < n; ++i) {
+    float* v = normals + 3 * i;
+    const float* p = xyz1 + 4 * i;
+    if (lsgpu::normal_angle::flips(p[0], p[1], p[2], sensor[0], sensor[1], sensor[2], v[0], v[1], v[2], mode)) {
+      v[0] = -v[0]; v[1] = -v[1]; v[2] = -v[2];
+    }
+  }
+  return LSGPU_OK;
+}
+
+int lsgpu_normal_angle_weights(const float T[16], const float* reading_normals, int64_t nq, const float* reference_normals,
+                               const int32_t* ids, int k, float max_angle, float* w) {
+  if (!T || nq < 0 || k < 1 || (nq > 0 && (!reading_normals || !reference_normals || !ids || !w))) return LSGPU_BAD_ARG;
+  if (!(max_angle >= 0.f && max_angle <= 3.1416f)) return LSGPU_BAD_CONFIG;
+  const float eps = lsgpu::normal_angle::eps_of(max_angle);
+  float rows[12];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) rows[r * 4 + c] = T[c * 4 + r];
+  for (int64_t i = 0; i < nq; ++i) {
+    const float* rn = reading_normals + 3 * i;
+    for (int j = 0; j < k; ++j) {
+      const int32_t id = ids[i * k + j];
+      if (id < 0) { w[i * k + j] = 0.f; continue; }
+      const float* f = reference_normals + 3 * (int64_t)id;
+      w[i * k + j] = lsgpu::normal_angle::keep(rows, rn[0], rn[1], rn[2], f[0], f[1], f[2], eps) ? 1.f : 0.f;
+    }
+  }
   return LSGPU_OK;
 }
 

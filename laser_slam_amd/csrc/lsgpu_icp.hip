@@ -305,6 +305,15 @@ struct lsgpu_icp {
   bool have_normals = false;  // the last set_reference was given normals (or a reference filter computed them)
   DevBuf<uint32_t> rb_hist; DevBuf<SelState> rb_sel; DevBuf<RobustState> rb_state; DevBuf<lsgpu_robust_trace> rb_trace_dev;
   size_t rb_trace_n = 0;      // records of the last alignment in rb_trace_dev
+  // SurfaceNormalOutlierFilter / reading normals / orientation (lsgpu_icp_set_normals)
+  bool normals_on = false;
+  lsgpu_normals_config normals{};
+  DevBuf<float> rd_nrm;       // the reading's normals, 3 floats per point in the reading's order (lsgpu_icp_compute's step, or the caller's) ...
+  const float* rd_nrm_for = nullptr; int64_t rd_nrm_n = 0;   // ... which belong to the NEXT align of this reading, and to no later one
+  DevBuf<float> rd_nrm0;      // ... moved by R_init (step 5): what the loop's angle test reads
+  DevBuf<float> nrm_io;       // staging of lsgpu_icp_get_reference_normals
+  DevBuf<lsgpu_normal_angle_trace> na_trace_dev;
+  size_t na_trace_n = 0;      // records of the last alignment in na_trace_dev
   DevBuf<double> ne_partials; // kNeBlocks * 32
   DevBuf<double> ne_gpartials;  // (kNeBlocksMax / kNeGroup) * 32: first-level sums of k_normal_eq_loop
   DevBuf<uint32_t> ne_tickets;  // 1 + kNeBlocksMax / kNeGroup
@@ -443,6 +452,30 @@ int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap) {
   return n;
 }
 
+int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->normals_on = false; return LSGPU_OK; }
+  const char* why = nullptr;
+  // (whether the reference has normals is known to align, for which a filter without them is inert)
+  if (normal_angle::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (h->comm) { h->err = "SurfaceNormalOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
+  h->normals = *cfg;
+  h->normals_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_get_normal_angle_trace(lsgpu_icp* h, lsgpu_normal_angle_trace* out, int cap) {
+  if (!h || !out || cap <= 0 || !h->na_trace_n) return 0;
+  const int n = std::min<int>(cap, (int)h->na_trace_n);
+  if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+      hipMemcpy(out, h->na_trace_dev.p, (size_t)n * sizeof(lsgpu_normal_angle_trace), hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return n;
+}
+
 int lsgpu_abi_version(void) { return LSGPU_ABI_VERSION; }
 
 const char* lsgpu_strerror(int code) {
@@ -510,6 +543,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
+  h->rd_nrm.release(); h->rd_nrm0.release(); h->nrm_io.release(); h->na_trace_dev.release();
   h->sel.release(); h->ne_partials.release(); h->ne_gpartials.release(); h->ne_tickets.release(); h->ne_out.release(); h->limit_dev.release();
   for (auto& e : h->comm_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : h->knn_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); (void)hipEventDestroy(e.d); (void)hipEventDestroy(e.e); }
@@ -661,7 +695,8 @@ static float matcher_max_d2(const lsgpu_icp* h) {
 }
 // does the handle take the chain plan (lsgpu_policy.h)?
 static bool chain_on(const lsgpu_icp* h) {
-  return policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor, h->robust_on);
+  return policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor,
+                              h->robust_on, h->normals_on && h->normals.max_angle >= 0.f);
 }
 
 static float price_share(const lsgpu_icp* h) {   // heavy lanes / searching lanes of the priced launch (its counters are on the host)
@@ -1181,7 +1216,8 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
     return LSGPU_BAD_CONFIG;
   }
   if (chain_on(h)) {
-    h->err = h->robust_on ? "comm_init: the split-scan mode does not run RobustOutlierFilter"
+    h->err = (h->normals_on && h->normals.max_angle >= 0.f) ? "comm_init: the split-scan mode does not run SurfaceNormalOutlierFilter"
+           : h->robust_on ? "comm_init: the split-scan mode does not run RobustOutlierFilter"
                           : "comm_init: the split-scan mode runs neither KDTreeMatcher maxDist nor Max- / Min- / MedianDistOutlierFilter";
     return LSGPU_BAD_CONFIG;
   }
@@ -2000,6 +2036,68 @@ int lsgpu_icp_filter_reading(lsgpu_icp* h, const float* xyz1, int64_t n, float p
   return LSGPU_OK;
 }
 
+int lsgpu_icp_reading_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, int orient, const float sensor[3],
+                              float* out_normals) {
+  if (!h || !out_normals || orient < 0 || orient > 2 || (orient && !sensor)) return LSGPU_BAD_ARG;
+  h->err.clear();
+  // a grid of its own: a second handle with this one's configuration, on its device -- the reference stays what it was
+  lsgpu_icp* tmp = nullptr;
+  lsgpu_icp_config cfg = h->cfg;
+  cfg.profile_kernels = 0;
+  int rc = lsgpu_icp_create(&cfg, h->device, &tmp);
+  if (rc) { h->err = "reading_normals: no scratch handle"; return rc; }
+  const bool dev_n = is_device_ptr(out_normals);
+  float* on = out_normals;
+  rc = LSGPU_OK;
+  if (!dev_n) { if (tmp->rd_nrm.reserve((size_t)3 * std::max<int64_t>(n, 1)) != hipSuccess) rc = LSGPU_HIP_ERROR; on = tmp->rd_nrm.p; }
+  if (!rc) rc = lsgpu_icp_filter_reference_normals(tmp, xyz1, n, knn, on, nullptr, nullptr);
+  if (!rc && orient) {
+    const float4* src = nullptr;
+    tmp->cur = tmp->stream;
+    rc = stage_points(tmp, xyz1, n, tmp->flt_in, &src);
+    if (!rc) {
+      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(n)), dim3(256), 0, tmp->stream, src, (const float4*)nullptr, (int)n,
+                         sensor[0], sensor[1], sensor[2], orient, on, (float4*)nullptr);
+      if (hipGetLastError() != hipSuccess) rc = LSGPU_HIP_ERROR;
+    }
+  }
+  if (!rc && !dev_n && hipMemcpyAsync(out_normals, on, (size_t)n * 12, hipMemcpyDeviceToHost, tmp->stream) != hipSuccess) rc = LSGPU_HIP_ERROR;
+  if (!rc && hipStreamSynchronize(tmp->stream) != hipSuccess) rc = LSGPU_HIP_ERROR;
+  if (rc) h->err = std::string("reading_normals: ") + (tmp->err.empty() ? lsgpu_strerror(rc) : tmp->err);
+  lsgpu_icp_destroy(tmp);
+  return rc;
+}
+
+int lsgpu_icp_align_normals(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reading_normals,
+                            const float T_init[16], float T_out[16], lsgpu_icp_stats* stats) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->rd_nrm_for = nullptr; h->rd_nrm_n = 0;
+  if (reading_normals && reading_xyz1 && nq > 0 && nq <= 0x7FFFFFF0ll) {
+    HIPC(hipSetDevice(h->device));
+    HIPC(h->rd_nrm.reserve((size_t)3 * nq));
+    HIPC(hipMemcpyAsync(h->rd_nrm.p, reading_normals, (size_t)nq * 12,
+                        is_device_ptr(reading_normals) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    h->rd_nrm_for = reading_xyz1; h->rd_nrm_n = nq;
+  }
+  return lsgpu_icp_align(h, reading_xyz1, nq, T_init, T_out, stats);
+}
+
+int lsgpu_icp_get_reference_normals(lsgpu_icp* h, float* out_normals, int64_t cap_points) {
+  if (!h || !out_normals) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (h->nr <= 0 || !h->have_normals || cap_points < h->nr) { h->err = "get_reference_normals: no reference normals, or too small a buffer"; return LSGPU_BAD_ARG; }
+  HIPC(hipSetDevice(h->device));
+  const int64_t n = h->nr;
+  const bool dev_n = is_device_ptr(out_normals);
+  float* on = out_normals;
+  if (!dev_n) { HIPC(h->nrm_io.reserve((size_t)3 * n)); on = h->nrm_io.p; }
+  hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(n)), dim3(256), 0, h->stream, h->pts.p, (int)n, h->nrm.p, on);
+  HIPC(hipGetLastError());
+  if (!dev_n) HIPC(hipMemcpyAsync(out_normals, on, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  return LSGPU_OK;
+}
+
 // one reference filter module, knn in [3, 32]; or none on a point-to-point handle, which needs no normals
 static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain) {
   return lsgpu_chain_config_check(chain, h->cfg.error_minimizer) == LSGPU_OK;
@@ -2020,7 +2118,16 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   // SurfaceNormalDataPointsFilter keeps every point and draws nothing: the reference goes to set_reference as given and
   // the normals are computed on the grid it builds (a point-to-point handle reads none: skipped)
   const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;   // (its residuals need the normals)
-  const bool ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane);
+  // lsgpu_icp_set_normals: the angle filter reads the reference normals whatever the minimizer; the reading's normals are
+  // computed on the handle's grid BEFORE the reference takes it (rd_normals), which rules the side stream out
+  const lsgpu_normals_config* nc = h->normals_on ? &h->normals : nullptr;
+  const bool na_filter = nc && nc->max_angle >= 0.f;
+  const bool rd_normals = nc && nc->reading_sn_knn > 0;
+  if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0) {
+    h->err = "compute: SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter need the normals of a reference filter";
+    return LSGPU_BAD_CONFIG;
+  }
+  const bool ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter);
   if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
   if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
   if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
@@ -2101,7 +2208,7 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   // with its own sort scratch, from inside set_reference (right before its one host round trip), and the queries are
   // moved into the reference's frame as soon as set_reference knows the mean.  Both are chains of short launches that
   // leave most of the chip idle; side by side the shorter one disappears (LSGPU_NO_SIDE_STREAM: one after the other).
-  const bool side = tuning().side_stream && !h->comm;
+  const bool side = tuning().side_stream && !h->comm && !rd_normals;
   const float4* rd_src = nullptr;
   const float4* rd_dev = nullptr;
   auto reading_ready = [&](hipStream_t on) -> int {   // the reading's upload, if it is ours, has to be there
@@ -2181,6 +2288,29 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
       return LSGPU_OK;
     };
   }
+  if (rd_normals) {
+    // the reading's filter, then SurfaceNormalDataPointsFilter on the points it kept: the grid of the kept reading, the
+    // normals on it, copied out in the reading's order -- all before the reference's own set_reference below
+    rc = reading_ready(h->stream);
+    if (!rc) rc = reading_filter(false);
+    if (rc) return rc;
+    if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
+    if (nqf < nc->reading_sn_knn) { h->err = "compute: the kept reading has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
+    h->defer_cone = true;   // (no direction index of the reading)
+    rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(rd_dev), nullptr, nqf);
+    h->defer_cone = false;
+    if (!rc) rc = snf_device(h, nc->reading_sn_knn, nullptr, nullptr);
+    if (rc) return rc;
+    HIPC(h->rd_nrm.reserve((size_t)3 * nqf));
+    hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nqf)), dim3(256), 0, h->stream, h->pts.p, (int)nqf, h->nrm.p, h->rd_nrm.p);
+    if (nc->reading_orient)
+      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nqf)), dim3(256), 0, h->stream, rd_dev, (const float4*)nullptr, (int)nqf,
+                         nc->reading_sensor[0], nc->reading_sensor[1], nc->reading_sensor[2], nc->reading_orient, h->rd_nrm.p, (float4*)nullptr);
+    HIPC(hipGetLastError());
+  }
+  if (nc && nc->reference_orient && ref_nrm)   // the sampling filter's normals, beside its points
+    hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, (const float4*)nullptr, (int)nrf,
+                       nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, h->flt_nrm.p, (float4*)nullptr);
   h->defer_cone = side;
   rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(ref_pts), ref_nrm, nrf);
   h->hook_before_ref_sync = nullptr; h->hook_after_grid = nullptr;
@@ -2190,6 +2320,11 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
     rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
     if (rc) return rc;
     h->have_normals = true;
+    if (nc && nc->reference_orient) {   // on the sorted normals; the position is the point as given (ref_pts, by the sorted point's index)
+      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, h->pts.p, (int)nrf,
+                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, (float*)nullptr, h->nrm.p);
+      HIPC(hipGetLastError());
+    }
   }
   if (side) {
     // the direction index of the reference is not needed before the loop's third search: lsgpu_icp_align enqueues its
@@ -2199,7 +2334,7 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
     if (!h->cone_done) HIPC(hipEventCreateWithFlags(&h->cone_done, hipEventDisableTiming));
     h->cone_build_in_align = true;
   }
-  if (!side) {
+  if (!side && !rd_normals) {
     rc = reading_ready(h->stream);
     if (!rc) rc = reading_filter(false);
     if (rc) return rc;
@@ -2208,6 +2343,7 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
   const double t_filters = wall_ms() - t0;
   if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
   if (side_prepared) { h->prepared_rd = reinterpret_cast<const float*>(rd_dev); h->prepared_nq = nqf; }
+  if (rd_normals) { h->rd_nrm_for = reinterpret_cast<const float*>(rd_dev); h->rd_nrm_n = nqf; }
   // steps 5-7
   rc = lsgpu_icp_align(h, reinterpret_cast<const float*>(rd_dev), nqf, T_init, T_out, stats);
   if (stats) stats->t_reserved[0] = t_filters;
@@ -2639,6 +2775,10 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   const float* const prepared_rd = h->prepared_rd;
   const int64_t prepared_nq = h->prepared_nq;
   h->prepared_rd = nullptr; h->prepared_nq = 0;
+  // ... and so do reading normals (lsgpu_icp_compute's step / lsgpu_icp_align_normals)
+  const float* const normals_for = h->rd_nrm_for;
+  const int64_t normals_n = h->rd_nrm_n;
+  h->rd_nrm_for = nullptr; h->rd_nrm_n = 0; h->na_trace_n = 0;
   // Local reasons not to start.  In the split-scan mode they are NOT returned yet: a rank that left here would
   // leave its peers blocked in the first collective, so every rank first takes part in the entry handshake below.
   int local_rc = LSGPU_OK;
@@ -2653,6 +2793,9 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   ca.med_factor = h->cfg.outlier_median_factor; ca.has_median = h->cfg.outlier_median_factor > 0.f ? 1 : 0;
   const bool robust = h->robust_on;
   if (robust) { ca.rb = robust::params(h->robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
+  // SurfaceNormalOutlierFilter: inert without reading normals or without reference normals (as upstream)
+  const bool angle = chain && h->normals_on && h->normals.max_angle >= 0.f && h->have_normals && reading_xyz1 &&
+                     normals_for == reading_xyz1 && normals_n == nq;
   if (robust && ca.rb.plane && !h->have_normals) {
     h->err = "align: RobustOutlierFilter distanceType point2plane needs reference normals";
     h->cone_build_in_align = false;
@@ -2728,6 +2871,13 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     HIPC(h->rb_trace_dev.reserve((size_t)max_it));
     HIPC(hipMemsetAsync(h->rb_state.p, 0, sizeof(RobustState), h->stream));
     ca.rb_hist = h->rb_hist.p; ca.rb_sel = h->rb_sel.p; ca.rb_state = h->rb_state.p; ca.rb_trace = h->rb_trace_dev.p;
+  }
+  if (angle) {
+    // step 5 moves the reading's descriptors with the reading: n0 = R_init n, once per alignment (lsgpu_rotate_descriptors' chain)
+    HIPC(h->rd_nrm0.reserve((size_t)3 * nq)); HIPC(h->na_trace_dev.reserve((size_t)max_it));
+    hipLaunchKernelGGL(k_rotate3, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rd_nrm.p, nq, to_mat34(T_rm_in), h->rd_nrm0.p);
+    HIPC(hipGetLastError());
+    ca.na_rn = h->rd_nrm0.p; ca.na_eps = normal_angle::eps_of(h->normals.max_angle); ca.na_trace = h->na_trace_dev.p;
   }
   IcpState* hst = reinterpret_cast<IcpState*>(h->h_pinned + 64);  // pinned staging (<= 512 B); [0..47] D2H, [48..63] H2D
   static_assert(sizeof(IcpState) <= 64 * sizeof(double), "IcpState staging");
@@ -2820,12 +2970,12 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
       lsgpu_icp::KnnEv* evk = (timed && h->knn_events_used) ? &h->knn_events[h->knn_events_used - 1] : nullptr;
       if (evk) HIPC(hipEventRecord(evk->d, h->stream));
       hipLaunchKernelGGL(ne_loop_k, dim3(nb), dim3(256), 0, h->stream, h->rdq.p, np,
-                         h->state.p, h->kmatch.p, h->kd2.p, (p2p && !(robust && ca.rb.plane)) ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
+                         h->state.p, h->kmatch.p, h->kd2.p, (p2p && !(robust && ca.rb.plane) && !angle) ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
                          h->counters.p + 32, h->ne_tickets.p, h->ne_partials.p, h->ne_gpartials.p, h->ne_out.p,
-                         h->chk_hist.p, h->trace_dev.p, max_it, 0, (split_update && !robust) ? 0 : 1,
+                         h->chk_hist.p, h->trace_dev.p, max_it, 0, (split_update && !robust && !angle) ? 0 : 1,
                          h->sel_aux.p, (uint32_t*)nullptr, 0, (uint32_t*)nullptr,
                          0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0, ca_it);   // 6d (+6e)
-      if (split_update && !robust)
+      if (split_update && !robust && !angle)
         hipLaunchKernelGGL(update, dim3(1), dim3(64), 0, h->stream, h->state.p, h->ne_out.p,
                            h->chk_hist.p, h->trace_dev.p, max_it, 0, h->sel_aux.p);                       // 6d+6e
       if (evk) HIPC(hipEventRecord(evk->e, h->stream));
@@ -2994,6 +3144,7 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   h->trace.clear();
   h->trace_on_device = (size_t)std::min(it, max_it);
   h->rb_trace_n = robust ? h->trace_on_device : 0;
+  h->na_trace_n = angle ? h->trace_on_device : 0;
   h->trace_knn_us.clear();
   if (it > 0) { st.final_limit = hst->last_limit; st.final_n_used = (int64_t)hst->last_used; }
   if (rc == LSGPU_OK) {  // step 7

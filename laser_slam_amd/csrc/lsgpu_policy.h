@@ -42,11 +42,13 @@ struct Config {               // constant during an alignment (from Tuning and t
 // outlier-filter chain (0 = absent; +inf = absent for the two maxDist fields).  A configuration with none of them is
 // planned exactly as before the fields existed.
 // A handle with RobustOutlierFilter (lsgpu_icp_set_robust_filter) takes it too, whatever the four fields hold.
+// So does a handle with SurfaceNormalOutlierFilter (lsgpu_icp_set_normals, max_angle >= 0): its test sits in the chain
+// instantiations of the normal equations.
 inline bool chain_fields(float matcher_max_dist, float outlier_max_dist, float outlier_min_dist, float outlier_median_factor,
-                         bool robust_filter = false) {
+                         bool robust_filter = false, bool normal_angle_filter = false) {
   const bool md = matcher_max_dist > 0.f && !std::isinf(matcher_max_dist);
   const bool od = outlier_max_dist > 0.f && !std::isinf(outlier_max_dist);
-  return md || od || outlier_min_dist > 0.f || outlier_median_factor > 0.f || robust_filter;
+  return md || od || outlier_min_dist > 0.f || outlier_median_factor > 0.f || robust_filter || normal_angle_filter;
 }
 
 struct Iteration {            // one enqueued iteration: what the search, the select and the normal equations are told

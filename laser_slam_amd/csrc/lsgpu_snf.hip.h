@@ -26,6 +26,7 @@
 #pragma once
 #include "lsgpu_common.hip.h"
 #include "lsgpu_box_normal.h"
+#include "lsgpu_normal_angle.h"
 #include "lsgpu_knn_k.hip.h"
 
 namespace lsgpu {
@@ -264,6 +265,27 @@ __global__ __launch_bounds__(256) void k_snf_unpermute(const float4* __restrict_
   const size_t o = (size_t)__float_as_uint(pts[j].w);
   const float4 v = nrm[j];
   out[3 * o + 0] = v.x; out[3 * o + 1] = v.y; out[3 * o + 2] = v.z;
+}
+
+// OrientNormalsDataPointsFilter behind ObservationDirectionDataPointsFilter (lsgpu_normal_angle.h, flips): one thread per
+// point, the normal negated where the rule says so.  Two layouts: normals of a cloud in its own order (nrm3, 3 floats per
+// point, beside pos) -- the filtered reference before set_reference, the reading -- or the Morton-sorted float4 normals of
+// the handle's reference (nrm4; sorted[j].w = the point's index in the cloud as given, whose staged copy `pos` supplies the
+// uncentred position: the very bits the caller gave, no reconstruction from the centred point).
+__global__ __launch_bounds__(256) void k_orient_normals(const float4* __restrict__ pos, const float4* __restrict__ sorted, int n,
+                                                        float sx, float sy, float sz, int mode, float* __restrict__ nrm3,
+                                                        float4* __restrict__ nrm4) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  if (sorted) {
+    const float4 p = pos[(size_t)__float_as_uint(sorted[j].w)];
+    float4 v = nrm4[j];
+    if (normal_angle::flips(p.x, p.y, p.z, sx, sy, sz, v.x, v.y, v.z, mode)) { v.x = -v.x; v.y = -v.y; v.z = -v.z; nrm4[j] = v; }
+  } else {
+    const float4 p = pos[j];
+    const float x = nrm3[3 * (size_t)j], y = nrm3[3 * (size_t)j + 1], z = nrm3[3 * (size_t)j + 2];
+    if (normal_angle::flips(p.x, p.y, p.z, sx, sy, sz, x, y, z, mode)) { nrm3[3 * (size_t)j] = -x; nrm3[3 * (size_t)j + 1] = -y; nrm3[3 * (size_t)j + 2] = -z; }
+  }
 }
 
 }  // namespace lsgpu

@@ -4,6 +4,7 @@
 #include "lsgpu_common.hip.h"
 #include "lsgpu_host_math.h"
 #include "lsgpu_robust.h"
+#include "lsgpu_normal_angle.h"
 #include "../../include/lsgpu_icp.h"
 
 namespace lsgpu {
@@ -241,6 +242,10 @@ struct ChainArgs {
   const SelState* rb_sel;     // ... and its three states
   RobustState* rb_state;      // the scale and the median, kept from iteration to iteration
   lsgpu_robust_trace* rb_trace;
+  // SurfaceNormalOutlierFilter (lsgpu_normal_angle.h; na_rn null: no such filter, or an inert one -- a wave-uniform branch)
+  const float* na_rn;         // the reading normals n0 (moved by R_init), 3 floats per reading point, indexed by rdq's w
+  float na_eps;               // (float)cos(maxAngle)
+  lsgpu_normal_angle_trace* na_trace;
 };
 
 // Start of the MAD's select (one block, behind the median's select): the median goes to the loop's robust state, where the
@@ -789,6 +794,9 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     }
   }
   const bool rb_normals = MIN != kPointToPoint || (RB && chain.rb.plane);   // (point2plane distances of a point-to-point handle read the normal too)
+  const float* na_rn = nullptr;   // SurfaceNormalOutlierFilter: the same for every lane of the launch
+  if constexpr (CHAIN) na_rn = chain.na_rn;
+  double na_rej = 0.0;            // pairs the angle test alone rejects
   double acc[kNe];
 #pragma unroll
   for (int k = 0; k < kNe; ++k) acc[k] = 0.0;
@@ -823,13 +831,20 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     // SLOWER: 31.5 -> 34.6 us per launch, profiles/r03b_bench.json; it adds 16 MB of HBM stream to save cache hits)
     for (int u = 0; u < kNeUnroll; ++u) {
       if constexpr (MIN != kPointToPoint) nn[u] = use[u] ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
-      else if constexpr (RB) nn[u] = (use[u] && rb_normals) ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
+      else if constexpr (RB) nn[u] = (use[u] && (rb_normals || na_rn)) ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
+      else if constexpr (CHAIN) nn[u] = (use[u] && na_rn) ? nrm[__float_as_int(qq[u].w)] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int u = 0; u < kNeUnroll; ++u) {
     if (!use[u]) continue;
     const float4 q = qq[u];
     const float4 r = rr[u];
+    if constexpr (CHAIN) {
+      if (na_rn) {   // SurfaceNormalOutlierFilter: the reading normal by the query's caller index, the match's normal is here already
+        const float* rn = na_rn + 3 * (size_t)__float_as_uint(r.w);
+        if (!normal_angle::keep(T.m, rn[0], rn[1], rn[2], nn[u].x, nn[u].y, nn[u].z, chain.na_eps)) { na_rej += 1.0; continue; }
+      }
+    }
     const float3 p = xform(T, r.x, r.y, r.z);
     if constexpr (MIN == kPointToPoint) {
       double v[16];
@@ -934,17 +949,19 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   for (int k = 0; k < kNe; ++k) acc[k] = ne_slot_unused<MIN>(k) ? 0.0 : wave_sum(acc[k]);
   const int w = threadIdx.x >> 6;
   if constexpr (RB) { rb_cnt = wave_sum(rb_cnt); rb_bad = wave_sum(rb_bad); }
+  if constexpr (CHAIN) { if (na_rn) na_rej = wave_sum(na_rej); }
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < kNe; ++k) red[w][k] = acc[k];
     if constexpr (RB) { red[w][29] = rb_cnt; red[w][30] = rb_bad; }
+    if constexpr (CHAIN) red[w][31] = na_rej;   // column 31 of the partials: the angle test's count
   }
   __syncthreads();
   // Hand-off between blocks WITHOUT fences: the partial sums are written and read with agent-scope (sc1) accesses,
   // which go past the per-CU L1 and the per-XCD L2 on both sides (MI355X_MICROARCH.md, inter-workgroup visibility:
   // "sc1 stores and loads both sides"); a release / acquire fence pair costs 1.7-6.5 us per block on this chip and
   // every block would pay it.  s_waitcnt vmcnt(0) orders a block's stores before its ticket.
-  if (threadIdx.x < (RB ? kNe + 2 : kNe))
+  if (threadIdx.x < (RB ? kNe + 2 : kNe) || (CHAIN && threadIdx.x == 31))
     __hip_atomic_store(&partials[(size_t)blockIdx.x * 32 + threadIdx.x],
                        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x],
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1136,6 +1153,14 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
       red[threadIdx.x - 29][32] = t;
     }
   }
+  if constexpr (CHAIN) {   // the angle test's count: column 31, parked beside them
+    if (threadIdx.x == 31) {
+      double t = red[0][31];
+#pragma unroll
+      for (int g = 1; g < 8; ++g) t += red[g][31];
+      red[2][32] = t;
+    }
+  }
   if (threadIdx.x == 32) {
     if (wide) __hip_atomic_store(amb_cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const double ns = (double)cnt_sh[0];
@@ -1166,6 +1191,12 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   // wave 0's first lane advances the loop state; the other waves re-arm the iteration's scratch meanwhile (every
   // block has read hist3 / the window table by now)
   if (threadIdx.x == 0) {
+    if constexpr (CHAIN) {   // (a launch with the angle test always runs the update itself: the record goes beside the iteration's)
+      if (na_rn && chain.na_trace && !st_sh.done && st_sh.iter < trace_cap) {
+        lsgpu_normal_angle_trace& nt = chain.na_trace[st_sh.iter];
+        nt.rejected = (long long)red[2][32]; nt.eps = chain.na_eps; nt.reserved = 0;
+      }
+    }
     if constexpr (RB) {   // (the weighted launches always run the update themselves)
       RobustIter ri;
       ri.used = (long long)red[0][32]; ri.bad = red[1][32]; ri.scale = rb_scale; ri.median = rb_med;

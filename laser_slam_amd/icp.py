@@ -81,14 +81,20 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None):
+                 robust=None, normals=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
         outlier_max_dist / outlier_min_dist / outlier_median_factor: Max- / Min- / MedianDistOutlierFilter's parameter
         (None: cfg's; 0: no such module; see lsgpu_icp_config).  robust: None, or RobustOutlierFilter's parameters (a
-        RobustConfig, a dict of its fields, or an _lib.RobustCfg) -- lsgpu_icp_set_robust_filter."""
+        RobustConfig, a dict of its fields, or an _lib.RobustCfg) -- lsgpu_icp_set_robust_filter.  normals: None, or a
+        NormalsConfig / dict of its fields / _lib.NormalsCfg (SurfaceNormalOutlierFilter, reading normals, oriented
+        normals) -- lsgpu_icp_set_normals."""
         L = _lib.lib()
+        nc = normals_cfg(normals) if normals is not None else None
+        if nc is not None:                                      # refused values: before the device is touched
+            if L.lsgpu_normals_config_check(C.byref(nc), 0, 1) != _lib.OK:
+                raise LsgpuError(_lib.BAD_CONFIG, "lsgpu_normals_config_check", _normals_why(nc))
         rb = robust_cfg(robust) if robust is not None else None
         if rb is not None:                                      # refused values: before the device is touched
             mini = _MINIMIZERS.get(error_minimizer, error_minimizer) if error_minimizer is not None else (cfg.error_minimizer if cfg is not None else 0)
@@ -118,6 +124,56 @@ class IcpHandle:
         self.robust = None
         if rb is not None:
             self.set_robust_filter(rb)
+        self.normals = None
+        if nc is not None:
+            self.set_normals(nc)
+
+    def set_normals(self, normals):
+        """lsgpu_icp_set_normals: SurfaceNormalOutlierFilter / reading normals / oriented normals (None removes them)."""
+        nc = normals_cfg(normals) if normals is not None else None
+        rc = _lib.lib().lsgpu_icp_set_normals(self._h, C.byref(nc) if nc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_normals", self._h)
+        self.normals = nc
+
+    def normal_angle_trace(self, cap: int = 64):
+        """lsgpu_icp_get_normal_angle_trace: per iteration of the last align {rejected, eps}."""
+        buf = (_lib.NormalAngleTrace * cap)()
+        n = _lib.lib().lsgpu_icp_get_normal_angle_trace(self._h, buf, cap)
+        return [dict(rejected=int(buf[i].rejected), eps=np.float32(buf[i].eps)) for i in range(n)]
+
+    def reading_normals(self, xyz1, knn: int = 5, orient: int = 0, sensor=(0.0, 0.0, 0.0)) -> np.ndarray:
+        """lsgpu_icp_reading_normals: SurfaceNormalDataPointsFilter on a reading (+ orientation); the handle's reference stays."""
+        p, _k, n = _as_f32(xyz1, 4)
+        out = np.empty((n, 3), np.float32)
+        sv = np.asarray(sensor, np.float32)
+        rc = _lib.lib().lsgpu_icp_reading_normals(self._h, p, n, int(knn), int(orient), _fp(sv), out.ctypes.data)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_reading_normals", self._h)
+        return out
+
+    def reference_normals(self) -> np.ndarray:
+        """lsgpu_icp_get_reference_normals: the handle's reference normals in the order the reference was given."""
+        n = int(self.info().n_reference)
+        out = np.empty((n, 3), np.float32)
+        rc = _lib.lib().lsgpu_icp_get_reference_normals(self._h, out.ctypes.data, n)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_get_reference_normals", self._h)
+        return out
+
+    def align_normals(self, reading_xyz1, reading_normals, T_init):
+        """lsgpu_icp_align_normals: align with the reading's normals (n x 3) -> (T 4x4 float32, IcpStats)."""
+        p, _k, n = _as_f32(reading_xyz1, 4)
+        q, _k2, m = _as_f32(reading_normals, 3)
+        if m != n:
+            raise ValueError("normals must have one row per reading point")
+        ti = _t16(T_init)
+        to = np.empty(16, np.float32)
+        st = IcpStats()
+        rc = _lib.lib().lsgpu_icp_align_normals(self._h, p, n, q, _fp(ti), _fp(to), C.byref(st))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_align_normals", self._h)
+        return to.reshape(4, 4).T.copy(), st
 
     def set_robust_filter(self, robust):
         """lsgpu_icp_set_robust_filter: RobustOutlierFilter on this handle (None removes it)."""
@@ -664,6 +720,74 @@ def _robust_why(rb) -> str:
     return "refused configuration"
 
 
+@dataclass
+class NormalsConfig:
+    """lsgpu_normals_config: SurfaceNormalOutlierFilter (max_angle < 0: none), SurfaceNormalDataPointsFilter on the reading
+    (reading_sn_knn, 0: none), the orientation pairs (0 off, 1 towardCenter, 2 away) and their sensor positions."""
+    max_angle: float = -1.0
+    reading_sn_knn: int = 0
+    reading_orient: int = 0
+    reference_orient: int = 0
+    reading_sensor: tuple = (0.0, 0.0, 0.0)
+    reference_sensor: tuple = (0.0, 0.0, 0.0)
+    reading_normals_given: int = 0
+
+
+def normals_cfg(n) -> "_lib.NormalsCfg":
+    if isinstance(n, _lib.NormalsCfg):
+        return n
+    if isinstance(n, dict):
+        n = NormalsConfig(**n)
+    c = _lib.NormalsCfg()
+    c.max_angle = float(n.max_angle)
+    c.reading_sn_knn, c.reading_orient, c.reference_orient = int(n.reading_sn_knn), int(n.reading_orient), int(n.reference_orient)
+    for i in range(3):
+        c.reading_sensor[i] = float(n.reading_sensor[i])
+        c.reference_sensor[i] = float(n.reference_sensor[i])
+    c.reading_normals_given = int(n.reading_normals_given)
+    return c
+
+
+def _normals_why(nc) -> str:
+    if math.isnan(nc.max_angle) or nc.max_angle > 3.1416:
+        return "SurfaceNormalOutlierFilter: maxAngle must be in [0, 3.1416]"
+    if nc.reading_sn_knn and not 3 <= nc.reading_sn_knn <= 32:
+        return "SurfaceNormalDataPointsFilter (reading): knn must be in [3, 32]"
+    if nc.max_angle >= 0 and not nc.reading_sn_knn and not nc.reading_normals_given:
+        return "SurfaceNormalOutlierFilter: the reading section provides no normals (SurfaceNormalDataPointsFilter)"
+    if nc.reading_sn_knn and not nc.max_angle >= 0:
+        return ("SurfaceNormalDataPointsFilter (reading): only SurfaceNormalOutlierFilter reads reading normals, and the "
+                "chain holds none")
+    return "SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter: a value is out of range"
+
+
+def orient_normals(xyz1, normals, sensor, toward_center: bool = True) -> np.ndarray:
+    """lsgpu_orient_normals: the orientation step on the host -- the device's, bit for bit.  Returns the oriented copy."""
+    p = np.ascontiguousarray(xyz1, np.float32)
+    out = np.ascontiguousarray(normals, np.float32).copy()
+    sv = np.asarray(sensor, np.float32)
+    rc = _lib.lib().lsgpu_orient_normals(p.ctypes.data if p.size else None, len(p), _fp(sv), 1 if toward_center else 2,
+                                         out.ctypes.data if out.size else None)
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_orient_normals")
+    return out
+
+
+def normal_angle_weights(T, reading_normals, reference_normals, ids, max_angle: float) -> np.ndarray:
+    """lsgpu_normal_angle_weights: SurfaceNormalOutlierFilter's 0 / 1 weights (ids: n or n x k) -- the device loop's."""
+    rn = np.ascontiguousarray(reading_normals, np.float32)
+    fn = np.ascontiguousarray(reference_normals, np.float32)
+    idv = np.ascontiguousarray(ids, np.int32)
+    k = 1 if idv.ndim == 1 else idv.shape[1]
+    w = np.empty(idv.shape, np.float32)
+    rc = _lib.lib().lsgpu_normal_angle_weights(_fp(_t16(T)), rn.ctypes.data if rn.size else None, len(rn), fn.ctypes.data if fn.size else None,
+                                               idv.ctypes.data if idv.size else None, k, float(max_angle),
+                                               w.ctypes.data if w.size else None)
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_normal_angle_weights")
+    return w
+
+
 def robust_scale(d2):
     """lsgpu_robust_scale: (median, MAD scale) of the finite entries of d2, float32 -- the device loop's, bit for bit."""
     a = np.ascontiguousarray(d2, np.float32).ravel()
@@ -704,11 +828,13 @@ def correct_rigid(T) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------
 
 _SUPPORTED = {
-    "readingDataPointsFilters": {"RandomSamplingDataPointsFilter"},
-    "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter", "SurfaceNormalDataPointsFilter"},
+    "readingDataPointsFilters": {"RandomSamplingDataPointsFilter", "SurfaceNormalDataPointsFilter",
+                                 "ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter"},
+    "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter", "SurfaceNormalDataPointsFilter",
+                                   "ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter"},
     "matcher": {"KDTreeMatcher"},
     "outlierFilters": {"TrimmedDistOutlierFilter", "MaxDistOutlierFilter", "MinDistOutlierFilter",
-                       "MedianDistOutlierFilter", "RobustOutlierFilter"},
+                       "MedianDistOutlierFilter", "RobustOutlierFilter", "SurfaceNormalOutlierFilter"},
     "errorMinimizer": {"PointToPlaneErrorMinimizer", "PointToPointErrorMinimizer"},
     "transformationCheckers": {"CounterTransformationChecker", "DifferentialTransformationChecker"},
 }
@@ -736,7 +862,20 @@ class ChainConfig:
     outlier_max_dist: float = 0.0           # MaxDistOutlierFilter maxDist [m]; 0: no such module
     outlier_min_dist: float = 0.0           # MinDistOutlierFilter minDist [m]; 0: no such module (or minDist 0: keeps all)
     outlier_median_factor: float = 0.0      # MedianDistOutlierFilter factor; 0: no such module
-    extra: dict = field(default_factory=dict)   # "robust": RobustOutlierFilter's parameters (see `robust`)
+    extra: dict = field(default_factory=dict)   # "robust": RobustOutlierFilter's parameters (see `robust`); "normals": see `normals`
+
+    @property
+    def normals(self) -> Optional["NormalsConfig"]:
+        """SurfaceNormalOutlierFilter / reading normals / oriented normals (a NormalsConfig); None: none of these modules.
+        Kept in `extra`, like `robust`."""
+        return self.extra.get("normals")
+
+    @normals.setter
+    def normals(self, value):
+        if value is None:
+            self.extra.pop("normals", None)
+        else:
+            self.extra["normals"] = value
 
     @property
     def robust(self) -> Optional["RobustConfig"]:
@@ -789,6 +928,8 @@ class ICP:
         ch = ChainConfig(reading_sampling_prob=-1.0, surface_normal_knn=7, trim_ratio=1.0,
                          min_diff_rot=-1.0, min_diff_trans=-1.0, smooth_length=1)
         seen = set()
+        order, sensor, toward = {}, {}, {}
+        nrm = NormalsConfig()
 
         def modules(section):
             v = doc.get(section)
@@ -826,10 +967,32 @@ class ICP:
                 if name not in allowed:
                     raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml",
                                      f"{section}: module {name} is not implemented on the HIP path")
-                if name in seen and name != "KDTreeMatcher":
+                reading = section == "readingDataPointsFilters"
+                side_key = name
+                if name in ("ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter") or \
+                        (reading and name == "SurfaceNormalDataPointsFilter"):
+                    side_key = section + ":" + name       # (these may appear once per section)
+                if side_key in seen and name != "KDTreeMatcher":
                     raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{section}: {name} given twice")
-                seen.add(name)
-                if name == "RandomSamplingDataPointsFilter":
+                seen.add(side_key)
+                order.setdefault(section, []).append(name)
+                if name == "ObservationDirectionDataPointsFilter":
+                    only(name, params, "x", "y", "z")
+                    sensor[section] = tuple(one_float(name, params, k, 0.0) for k in ("x", "y", "z"))
+                    if not all(math.isfinite(v) for v in sensor[section]):
+                        bad(f"{name}: x, y, z must be finite")
+                elif name == "OrientNormalsDataPointsFilter":
+                    only(name, params, "towardCenter")
+                    tc = one_float(name, params, "towardCenter", 1)
+                    if tc not in (0, 1):
+                        bad(f"{name}: towardCenter must be 0 or 1 (got {params.get('towardCenter')})")
+                    toward[section] = 1 if tc == 1 else 2
+                elif name == "SurfaceNormalOutlierFilter":
+                    only(name, params, "maxAngle")
+                    nrm.max_angle = one_float(name, params, "maxAngle", 1.57)
+                    if not 0.0 <= nrm.max_angle <= 3.1416:
+                        bad(f"{name}: maxAngle must be in [0, 3.1416] (got {nrm.max_angle})")
+                elif name == "RandomSamplingDataPointsFilter":
                     ch.reading_sampling_prob = float(params.get("prob", 0.75))
                 elif name == "SamplingSurfaceNormalDataPointsFilter":
                     ch.surface_normal_knn = int(params.get("knn", 7))
@@ -855,7 +1018,10 @@ class ICP:
                                 "sortEigen", "smoothNormals"):
                         if one_float(name, params, key, 0) != 0:
                             bad(f"{name}: {key} must be 0 or absent")
-                    ch.reference_normal_knn = knn
+                    if reading:
+                        nrm.reading_sn_knn = knn
+                    else:
+                        ch.reference_normal_knn = knn
                 elif name == "KDTreeMatcher":
                     # (its other parameters -- searchType, ... -- are not read)
                     md = one_float(name, params, "maxDist", math.inf)
@@ -930,7 +1096,50 @@ class ICP:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "readingStepDataPointsFilters")
         # the point-to-point minimizer reads no normals: without a reference filter module the reference is used as given
         p2p = ch.error_minimizer == "PointToPointErrorMinimizer"
-        if len(modules("referenceDataPointsFilters")) > 1:
+        ref_order, rd_order = order.get("referenceDataPointsFilters", []), order.get("readingDataPointsFilters", [])
+        pair = ["ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter"]
+
+        def oriented(section, names, head):
+            """names = head [+ the orientation pair]: -> 0 / 1 / 2; anything else is refused with the module's name"""
+            rest = names[len(head):]
+            if names[:len(head)] != head or rest not in ([], pair):
+                for n in pair:
+                    if n in names:
+                        bad(f"{section}: {n} is implemented only as the pair ObservationDirectionDataPointsFilter, "
+                            "OrientNormalsDataPointsFilter directly behind the module that produces the normals")
+                return None
+            return toward[section] if rest else 0
+        if "SurfaceNormalDataPointsFilter" in rd_order and "RandomSamplingDataPointsFilter" in rd_order and \
+                rd_order.index("SurfaceNormalDataPointsFilter") < rd_order.index("RandomSamplingDataPointsFilter"):
+            bad("readingDataPointsFilters: SurfaceNormalDataPointsFilter before RandomSamplingDataPointsFilter is not "
+                "implemented (the normals would have to be gathered through the sampling)")
+        rd_head = [n for n in rd_order if n in ("RandomSamplingDataPointsFilter", "SurfaceNormalDataPointsFilter")]
+        if rd_head and rd_head[-1] != "SurfaceNormalDataPointsFilter" and any(n in rd_order for n in pair):
+            bad("readingDataPointsFilters: OrientNormalsDataPointsFilter / ObservationDirectionDataPointsFilter need the normals "
+                "of a SurfaceNormalDataPointsFilter in front of them")
+        nrm.reading_orient = oriented("readingDataPointsFilters", rd_order, rd_head) or 0
+        if any(n in rd_order for n in pair) and nrm.reading_sn_knn == 0:
+            bad("readingDataPointsFilters: OrientNormalsDataPointsFilter / ObservationDirectionDataPointsFilter need the normals "
+                "of a SurfaceNormalDataPointsFilter in front of them")
+        ref_head = [n for n in ref_order if n not in pair]
+        if len(ref_head) == 1:
+            nrm.reference_orient = oriented("referenceDataPointsFilters", ref_order, ref_head) or 0
+        elif any(n in ref_order for n in pair) and not ref_head:
+            bad("referenceDataPointsFilters: OrientNormalsDataPointsFilter / ObservationDirectionDataPointsFilter need the normals "
+                "of a reference filter in front of them")
+        nrm.reading_sensor = sensor.get("readingDataPointsFilters", (0.0, 0.0, 0.0))
+        nrm.reference_sensor = sensor.get("referenceDataPointsFilters", (0.0, 0.0, 0.0))
+        if nrm.reading_sn_knn and nrm.max_angle < 0:
+            bad("readingDataPointsFilters: module SurfaceNormalDataPointsFilter is not implemented on the HIP path unless the "
+                "chain holds SurfaceNormalOutlierFilter (no other module reads reading normals)")
+        if nrm.max_angle >= 0 and not nrm.reading_sn_knn:
+            bad("SurfaceNormalOutlierFilter: the reading section provides no normals (SurfaceNormalDataPointsFilter in "
+                "readingDataPointsFilters)")
+        if nrm.max_angle >= 0 and not ref_head:
+            bad("SurfaceNormalOutlierFilter: the reference section provides no normals (a referenceDataPointsFilters module)")
+        if nrm != NormalsConfig():
+            ch.normals = nrm
+        if len(ref_head) > 1:
             bad("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or "
                 "SurfaceNormalDataPointsFilter)")
         if "SurfaceNormalDataPointsFilter" in seen or "SamplingSurfaceNormalDataPointsFilter" in seen:
@@ -963,7 +1172,7 @@ class ICP:
             self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer, self.chain.matcher_knn,
                                      self.chain.matcher_max_dist, self.chain.outlier_max_dist,
                                      self.chain.outlier_min_dist, self.chain.outlier_median_factor,
-                                     robust=self.chain.robust)
+                                     robust=self.chain.robust, normals=self.chain.normals)
         return self._handle
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
