@@ -42,7 +42,9 @@ extern "C" {
 #endif
 
 /* 4 still: the four chain fields of lsgpu_icp_config (matcher_max_dist ...) took reserved ints that had to be 0, the struct
- * kept its size and every offset, and 0 means what it meant -- a caller built against the earlier header runs unchanged. */
+ * kept its size and every offset, and 0 means what it meant -- a caller built against the earlier header runs unchanged.
+ * lsgpu_chain_load and the two *_config_why accessors are additions: new symbols and new structs, nothing that existed
+ * changed its layout or its meaning. */
 #define LSGPU_ABI_VERSION 4
 
 /* Return codes.  NO_CONVERGENCE is PointMatcher::ConvergenceError: laser_track.cpp:499-502 catches it
@@ -579,6 +581,40 @@ typedef struct lsgpu_normal_angle_trace {
   int     reserved;
 } lsgpu_normal_angle_trace;
 int lsgpu_icp_get_normal_angle_trace(lsgpu_icp* h, lsgpu_normal_angle_trace* out, int cap);
+
+/* ---- the module chain of a YAML document: PointMatcher::ICP::loadFromYaml (laser_slam/src/laser_track.cpp:17) ----
+ * One rule set for every front end (csrc/lsgpu_chain_loader.cpp; DESIGN.md §3 "The chain loader").  A front end parses the
+ * YAML syntax and hands over the modules in document order: the top-level section, the module's name and its parameters, every
+ * value as the scalar's TEXT ("0.75", ".inf", "huber").  The library decides the rest: which modules the device path has, their
+ * parameters, defaults and ranges, what may be given once, the order inside the two filter sections, and what the loop cannot
+ * run without.  Modules of the sections `inspector` and `logger` are skipped; any other unknown section or module is refused.
+ * Host only: no handle, no device. */
+typedef struct lsgpu_yaml_param  { const char* key; const char* value; } lsgpu_yaml_param;
+typedef struct lsgpu_yaml_module {
+  const char* section;              /* "readingDataPointsFilters", "matcher", ...                                  */
+  const char* name;                 /* "RandomSamplingDataPointsFilter", ...                                       */
+  const lsgpu_yaml_param* params;   /* n_params of them (NULL with 0)                                              */
+  int n_params;
+  int reserved;                     /* 0 */
+} lsgpu_yaml_module;
+typedef struct lsgpu_loaded_chain {
+  lsgpu_icp_config     icp;         /* trim ratio (1: no TrimmedDist), checkers (no Differential: -1, -1, 1), minimizer,
+                                     * matcher knn / maxDist, Max- / Min- / MedianDist thresholds; the rest as _config_default */
+  lsgpu_chain_config   chain;       /* reading_prob (< 0: no reading filter), ssn_knn, ssn_ratio, sn_knn; seed -1  */
+  lsgpu_robust_config  robust;      /* RobustOutlierFilter (the module's defaults with has_robust 0)               */
+  int has_robust;
+  lsgpu_normals_config normals;     /* SurfaceNormalOutlierFilter, reading normals, orientation pairs              */
+  int has_normals;                  /* 0: none of these modules (normals holds lsgpu_normals_config_default)       */
+  int reserved[6];                  /* 0 */
+} lsgpu_loaded_chain;
+/* LSGPU_OK and *out (every byte of it, padding 0), or LSGPU_BAD_CONFIG with the reason -- the module's name in it, or the
+ * section's for an unknown section -- written to why[0 .. why_cap), truncated if need be and always NUL-terminated; *out is
+ * then left as it was.  why may be NULL.  NULL pointers inside mods, or a NULL out: LSGPU_BAD_ARG. */
+int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* out, char* why, int why_cap);
+/* The reason lsgpu_robust_config_check / lsgpu_normals_config_check refuse a configuration (a static string, the module's
+ * name in it), or NULL where they return LSGPU_OK: what ICP::loadFromYaml (laser_track.cpp:17) reports for such a module. */
+const char* lsgpu_robust_config_why(const lsgpu_robust_config* c, int error_minimizer, int have_normals);
+const char* lsgpu_normals_config_why(const lsgpu_normals_config* c, int error_minimizer, int have_reference_normals);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "lsgpu_normals_config_default", "lsgpu_normals_config_check", "lsgpu_icp_set_normals", "lsgpu_icp_reading_normals",
     "lsgpu_icp_align_normals", "lsgpu_icp_get_reference_normals", "lsgpu_orient_normals", "lsgpu_normal_angle_weights",
     "lsgpu_icp_get_normal_angle_trace",
+    "lsgpu_chain_load", "lsgpu_robust_config_why", "lsgpu_normals_config_why",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -101,6 +102,23 @@ class IcpConfig(C.Structure):
         ("outlier_median_factor", C.c_float),   # MedianDistOutlierFilter factor; 0: absent
         ("reserved_", C.c_int * 1),
     ]
+
+
+class YamlParam(C.Structure):
+    """lsgpu_yaml_param: one parameter of a module, the value as the scalar's text."""
+    _fields_ = [("key", C.c_char_p), ("value", C.c_char_p)]
+
+
+class YamlModule(C.Structure):
+    """lsgpu_yaml_module: one module of a YAML chain document, as lsgpu_chain_load takes it."""
+    _fields_ = [("section", C.c_char_p), ("name", C.c_char_p), ("params", C.POINTER(YamlParam)), ("n_params", C.c_int),
+                ("reserved", C.c_int)]
+
+
+class LoadedChain(C.Structure):
+    """lsgpu_loaded_chain: what lsgpu_chain_load makes of a document."""
+    _fields_ = [("icp", IcpConfig), ("chain", ChainCfg), ("robust", RobustCfg), ("has_robust", C.c_int),
+                ("normals", NormalsCfg), ("has_normals", C.c_int), ("reserved", C.c_int * 6)]
 
 
 class IcpStats(C.Structure):
@@ -286,6 +304,11 @@ def lib() -> C.CDLL:
     L.lsgpu_orient_normals.argtypes = [fp, i64, C.POINTER(C.c_float), C.c_int, fp]
     L.lsgpu_normal_angle_weights.argtypes = [C.POINTER(C.c_float), fp, i64, fp, vp, C.c_int, C.c_float, fp]
     L.lsgpu_icp_get_normal_angle_trace.argtypes = [vp, C.POINTER(NormalAngleTrace), C.c_int]
+    L.lsgpu_chain_load.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(LoadedChain), C.c_char_p, C.c_int]
+    L.lsgpu_robust_config_why.argtypes = [C.POINTER(RobustCfg), C.c_int, C.c_int]
+    L.lsgpu_robust_config_why.restype = C.c_char_p
+    L.lsgpu_normals_config_why.argtypes = [C.POINTER(NormalsCfg), C.c_int, C.c_int]
+    L.lsgpu_normals_config_why.restype = C.c_char_p
     _lib = L
     return L
 

@@ -247,236 +247,27 @@ class ICP {
   // ICP::setDefault(): RandomSampling 0.75 / SamplingSurfaceNormal knn 7 / KDTree 1,0 / TrimmedDist 0.85 /
   // PointToPlane / Counter 40 + Differential 1e-3, 1e-3, 3
   void setDefault() {
-    lsgpu_icp_config_default(&cfg_);
-    prob_ = 0.75f; knn_ = 7; ratio_ = 0.5f; sn_knn_ = 0; has_robust_ = false; has_normals_ = false;
+    std::memset(&loaded_, 0, sizeof(loaded_));
+    lsgpu_icp_config_default(&loaded_.icp);
+    lsgpu_chain_config_default(&loaded_.chain);
     release();
   }
 
-  // Accepts the module chain of laser_slam/configurations/icp_default.yaml, with PointToPlaneErrorMinimizer or
-  // PointToPointErrorMinimizer, KDTreeMatcher knn 1..LSGPU_MATCHER_KNN_MAX (epsilon 0) with maxDist, and any subset of
-  // Trimmed- / Max- / Min- / MedianDistOutlierFilter (each at most once, any order), and SurfaceNormalDataPointsFilter in
-  // place of SamplingSurfaceNormalDataPointsFilter as THE reference filter, and one RobustOutlierFilter (cauchy, huber,
-  // tukey, gm, sc, L1 with scaleEstimator none / mad); any other module is a configuration error (PointMatcher's registrar
-  // throws on unknown names as well).
+  // The syntax is read here (parseYaml), the modules are handed to lsgpu_chain_load as text: which modules the device path
+  // has, their parameters, ranges and order are the library's rule set (csrc/lsgpu_chain_loader.cpp), shared with the Python
+  // facade.  Any other module is a configuration error (PointMatcher's registrar throws on unknown names as well).
   void loadFromYaml(std::istream& in) {
-    lsgpu_icp_config c;
-    lsgpu_icp_config_default(&c);
-    float prob = 0.75f, ratio = 0.5f;
-    int knn = 7, sn_knn = 0;
     const auto mods = parseYaml(in);
-    // libpointmatcher's loadFromYaml starts from EMPTY chains: a section the file does not mention means "no such
-    // module", not "the default module".  A missing filter section therefore keeps every point (prob / ratio 1 is
-    // not expressible for the reference filter: the normals come from it); the modules the device loop cannot run
-    // without are required.
-    bool has_reading = false, has_reference = false, has_matcher = false, has_outlier = false, has_minimizer = false,
-         has_counter = false, has_differential = false, has_max = false, has_min = false, has_median = false,
-         has_robust = false;
-    lsgpu_robust_config rb;
-    lsgpu_robust_config_default(&rb);
-    // SurfaceNormalOutlierFilter, SurfaceNormalDataPointsFilter on the reading, the orientation pair (ObservationDirection
-    // directly followed by OrientNormals, directly behind the module that produces the normals) on either side
-    lsgpu_normals_config nc;
-    lsgpu_normals_config_default(&nc);
-    int rd_stage = 0, ref_stage = 0;   // 1 sampling (reading) / normals (reference), 2 reading normals, 3 ObservationDirection, 4 OrientNormals
-    const char* const kPair = " is implemented only as the pair ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter "
-                              "directly behind the module that produces the normals";
-    prob = -1.0f;   // no reading filter module: lsgpu_chain_config::reading_prob < 0 (every point, no draws)
-    c.trim_ratio = 1.0f;
-    for (const auto& m : mods) {
-      const std::string& sec = m.section;
-      const std::string& name = m.name;
-      auto num = [&](const char* key, double def) {
-        auto it = m.params.find(key);
-        return it == m.params.end() ? def : std::stod(it->second);
-      };
-      // a threshold of the matcher / an outlier filter: a number ("inf" included), never NaN; the module's name in the text
-      auto fnum = [&](const std::string& mod, const char* key, double def) {
-        auto it = m.params.find(key);
-        if (it == m.params.end()) return def;
-        std::string v = it->second;
-        // YAML writes infinity as .inf / .Inf / .INF (std::stod wants it without the dot); "-.inf" is then -inf, which
-        // every caller refuses as out of range.  Any other leading dot is a plain float (.5 is 0.5)
-        const size_t sign = (!v.empty() && (v[0] == '+' || v[0] == '-')) ? 1 : 0;
-        const std::string rest = v.substr(sign);
-        if (rest == ".inf" || rest == ".Inf" || rest == ".INF") v = v.substr(0, sign) + "inf";
-        double x = 0.0;
-        try { size_t used = 0; x = std::stod(v, &used); if (used != v.size()) throw std::invalid_argument(v); }
-        catch (const std::exception&) { throw ConfigError(mod + ": " + key + " is not a number"); }
-        if (std::isnan(x)) throw ConfigError(mod + ": " + key + " is not a number");
-        return x;
-      };
-      auto only = [&](const std::string& mod, std::initializer_list<const char*> known) {
-        for (const auto& kv : m.params) {
-          bool ok = false;
-          for (const char* k : known) ok = ok || kv.first == k;
-          if (!ok) throw ConfigError(mod + ": unknown parameter " + kv.first);
-        }
-      };
-      // SurfaceNormalDataPointsFilter's parameters (either side): keepNormals 1 alone, exact (epsilon 0), no maxDist -> knn
-      auto sn_params = [&]() {
-        only(name, {"knn", "epsilon", "maxDist", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
-                    "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"});
-        const double k = fnum(name, "knn", 5);
-        if (!(k >= 3 && k <= 32) || k != (double)(int)k) throw ConfigError(name + ": knn must be in [3, 32]");
-        if (fnum(name, "epsilon", 0.0) != 0.0) throw ConfigError(name + ": epsilon must be 0 (the search is exact)");
-        const double md = fnum(name, "maxDist", INFINITY);
-        if (!(std::isinf(md) && md > 0.0)) throw ConfigError(name + ": maxDist must be absent or inf");
-        if (fnum(name, "keepNormals", 1) != 1.0) throw ConfigError(name + ": keepNormals must be 1 (the module is there for the normals)");
-        for (const char* key : {"keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
-                                "sortEigen", "smoothNormals"})
-          if (fnum(name, key, 0) != 0.0) throw ConfigError(name + ": " + key + " must be 0 or absent");
-        return (int)k;
-      };
-      const bool rd_sec = sec == "readingDataPointsFilters", ref_sec = sec == "referenceDataPointsFilters";
-      if (rd_sec && name == "RandomSamplingDataPointsFilter") {
-        if (has_reading) throw ConfigError("readingDataPointsFilters: one RandomSamplingDataPointsFilter at most");
-        if (rd_stage >= 2)
-          throw ConfigError("readingDataPointsFilters: SurfaceNormalDataPointsFilter before RandomSamplingDataPointsFilter is not "
-                            "implemented (the normals would have to be gathered through the sampling)");
-        has_reading = true; prob = (float)num("prob", 0.75); rd_stage = 1;
-      } else if (rd_sec && name == "SurfaceNormalDataPointsFilter") {
-        if (rd_stage >= 2) throw ConfigError("readingDataPointsFilters: SurfaceNormalDataPointsFilter given twice");
-        nc.reading_sn_knn = sn_params(); rd_stage = 2;
-      } else if ((rd_sec || ref_sec) && name == "ObservationDirectionDataPointsFilter") {
-        int& stage = rd_sec ? rd_stage : ref_stage;
-        if (stage != (rd_sec ? 2 : 1)) throw ConfigError(sec + ": " + name + kPair);
-        only(name, {"x", "y", "z"});
-        float* sv = rd_sec ? nc.reading_sensor : nc.reference_sensor;
-        const char* keys[3] = {"x", "y", "z"};
-        for (int i = 0; i < 3; ++i) {
-          const double v = fnum(name, keys[i], 0.0);
-          if (std::isinf(v)) throw ConfigError(name + ": x, y, z must be finite");
-          sv[i] = (float)v;
-        }
-        stage = 3;
-      } else if ((rd_sec || ref_sec) && name == "OrientNormalsDataPointsFilter") {
-        int& stage = rd_sec ? rd_stage : ref_stage;
-        if (stage != 3) throw ConfigError(sec + ": " + name + kPair);
-        only(name, {"towardCenter"});
-        const double tc = fnum(name, "towardCenter", 1);
-        if (tc != 0.0 && tc != 1.0) throw ConfigError(name + ": towardCenter must be 0 or 1");
-        (rd_sec ? nc.reading_orient : nc.reference_orient) = tc == 1.0 ? 1 : 2;
-        stage = 4;
-      } else if (sec == "outlierFilters" && name == "SurfaceNormalOutlierFilter") {
-        if (nc.max_angle >= 0.f) throw ConfigError("outlierFilters: one SurfaceNormalOutlierFilter at most");
-        only(name, {"maxAngle"});
-        const double a = fnum(name, "maxAngle", 1.57);
-        if (!(a >= 0.0 && a <= 3.1416)) throw ConfigError(name + ": maxAngle must be in [0, 3.1416]");
-        nc.max_angle = (float)a;
-      } else if (sec == "referenceDataPointsFilters" && name == "SamplingSurfaceNormalDataPointsFilter") {
-        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
-        has_reference = true; ref_stage = 1;
-        knn = (int)num("knn", 7); ratio = (float)num("ratio", 0.5);
-        if ((int)num("samplingMethod", 0) != 0) throw ConfigError("samplingMethod != 0 is not implemented");
-      } else if (sec == "referenceDataPointsFilters" && name == "SurfaceNormalDataPointsFilter") {
-        // every point, the normal of its knn nearest neighbours: keepNormals 1 alone, exact (epsilon 0), no maxDist
-        if (has_reference) throw ConfigError("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter)");
-        sn_knn = sn_params();
-        has_reference = true; ref_stage = 1;
-      } else if (sec == "matcher" && name == "KDTreeMatcher") {
-        has_matcher = true;
-        // knn 1..LSGPU_MATCHER_KNN_MAX, exact search only, maxDist; its other parameters (searchType, ...) are not read
-        const double md = fnum(name, "maxDist", INFINITY);
-        if (!(md > 0.0)) throw ConfigError("KDTreeMatcher: maxDist must be > 0");
-        c.matcher_max_dist = std::isinf(md) ? 0.f : (float)md;
-        const double k = num("knn", 1);
-        if (!(k >= 1 && k <= LSGPU_MATCHER_KNN_MAX) || k != (double)(int)k || num("epsilon", 0) != 0.0)
-          throw ConfigError("KDTreeMatcher: knn 1.." + std::to_string(LSGPU_MATCHER_KNN_MAX) + " with epsilon 0 is implemented");
-        c.matcher_knn = (int)k;
-      } else if (sec == "outlierFilters" && name == "TrimmedDistOutlierFilter") {
-        if (has_outlier) throw ConfigError("outlierFilters: one TrimmedDistOutlierFilter at most");
-        only(name, {"ratio"});
-        has_outlier = true; c.trim_ratio = (float)fnum(name, "ratio", 0.85);
-        if (!(c.trim_ratio > 0.f && c.trim_ratio <= 1.f)) throw ConfigError("TrimmedDistOutlierFilter: ratio must be in (0, 1]");
-      } else if (sec == "outlierFilters" && name == "MaxDistOutlierFilter") {
-        if (has_max) throw ConfigError("outlierFilters: one MaxDistOutlierFilter at most");
-        only(name, {"maxDist"});
-        const double md = fnum(name, "maxDist", 1.0);
-        if (!(md > 0.0)) throw ConfigError("MaxDistOutlierFilter: maxDist must be > 0");
-        has_max = true; c.outlier_max_dist = std::isinf(md) ? 0.f : (float)md;
-      } else if (sec == "outlierFilters" && name == "MinDistOutlierFilter") {
-        if (has_min) throw ConfigError("outlierFilters: one MinDistOutlierFilter at most");
-        only(name, {"minDist"});
-        const double md = fnum(name, "minDist", 1.0);
-        if (!(md >= 0.0) || std::isinf(md)) throw ConfigError("MinDistOutlierFilter: minDist must be >= 0 and finite");
-        has_min = true; c.outlier_min_dist = (float)md;
-      } else if (sec == "outlierFilters" && name == "MedianDistOutlierFilter") {
-        if (has_median) throw ConfigError("outlierFilters: one MedianDistOutlierFilter at most");
-        only(name, {"factor"});
-        const double f = fnum(name, "factor", 3.0);
-        if (!(f > 0.0) || std::isinf(f)) throw ConfigError("MedianDistOutlierFilter: factor must be > 0 and finite");
-        has_median = true; c.outlier_median_factor = (float)f;
-      } else if (sec == "outlierFilters" && name == "RobustOutlierFilter") {
-        if (has_robust) throw ConfigError("outlierFilters: one RobustOutlierFilter at most");
-        only(name, {"robustFct", "tuning", "scaleEstimator", "nbIterationForScale", "distanceType", "approximation"});
-        auto word = [&](const char* key, const char* def) {
-          auto it = m.params.find(key);
-          return it == m.params.end() ? std::string(def) : it->second;
-        };
-        auto pick = [&](const char* key, const std::string& v, std::initializer_list<const char*> names) {
-          int i = 0;
-          for (const char* n : names) { if (v == n) return i; ++i; }
-          throw ConfigError(name + ": unknown " + key + " " + v);
-        };
-        const std::string fct = word("robustFct", "cauchy"), est = word("scaleEstimator", "mad");
-        if (fct == "welsch" || fct == "student")
-          throw ConfigError(name + ": robustFct " + fct + " is not implemented on the HIP path (exp / pow are not bit-identical between host and device)");
-        if (est == "berg" || est == "std")
-          throw ConfigError(name + ": scaleEstimator " + est + " is not implemented on the HIP path (none and mad are)");
-        rb.robust_fct = pick("robustFct", fct, {"cauchy", "huber", "tukey", "gm", "sc", "L1"});
-        rb.scale_estimator = pick("scaleEstimator", est, {"none", "mad"});
-        rb.distance_type = pick("distanceType", word("distanceType", "point2point"), {"point2point", "point2plane"});
-        const double k = fnum(name, "tuning", 1.0), ap = fnum(name, "approximation", INFINITY), nb = fnum(name, "nbIterationForScale", 0);
-        if (!(k >= 0.0)) throw ConfigError(name + ": tuning must be >= 0");
-        if (!(ap >= 0.0)) throw ConfigError(name + ": approximation must be >= 0");
-        if (!(nb >= 0.0) || nb != (double)(int)nb) throw ConfigError(name + ": nbIterationForScale must be an integer >= 0");
-        rb.tuning = (float)k; rb.approximation = (float)ap; rb.nb_iteration_for_scale = (int)nb;
-        has_robust = true;
-      } else if (sec == "errorMinimizer" && (name == "PointToPlaneErrorMinimizer" || name == "PointToPointErrorMinimizer")) {
-        if (has_minimizer) throw ConfigError("errorMinimizer: one module at most");
-        has_minimizer = true;
-        c.error_minimizer = name == "PointToPointErrorMinimizer" ? LSGPU_MINIMIZER_POINT_TO_POINT : LSGPU_MINIMIZER_POINT_TO_PLANE;
-      }
-      else if (sec == "transformationCheckers" && name == "CounterTransformationChecker") {
-        has_counter = true; c.max_iterations = (int)num("maxIterationCount", 40);
-      } else if (sec == "transformationCheckers" && name == "DifferentialTransformationChecker") {
-        has_differential = true;
-        c.min_diff_rot = (float)num("minDiffRotErr", 0.001);
-        c.min_diff_trans = (float)num("minDiffTransErr", 0.001);
-        c.smooth_length = (int)num("smoothLength", 3);
-      } else if (sec == "inspector" || sec == "logger") {}  // debug output only (yaml:32-44)
-      else throw ConfigError(sec + ": module " + name + " is not implemented on the HIP path");
+    std::vector<std::vector<lsgpu_yaml_param>> params(mods.size());
+    std::vector<lsgpu_yaml_module> list(mods.size());
+    for (size_t i = 0; i < mods.size(); ++i) {
+      for (const auto& kv : mods[i].params) params[i].push_back({kv.first.c_str(), kv.second.c_str()});
+      list[i] = {mods[i].section.c_str(), mods[i].name.c_str(), params[i].data(), (int)params[i].size(), 0};
     }
-    // what the device loop needs: normals for the point-to-plane minimiser, the 1-NN matcher, the minimiser itself
-    // and a stopping rule.  (Absent reading filter: every point; absent outlier filter: every pair, ratio 1; absent
-    // reference filter with the point-to-point minimiser, which reads no normals: the reference as given, knn 0.)
-    if (!has_matcher) throw ConfigError("matcher: KDTreeMatcher is required");
-    if (!has_minimizer) throw ConfigError("errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer is required");
-    if (!has_reference && c.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
-      throw ConfigError("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter is required (it provides the normals of PointToPlaneErrorMinimizer)");
-    if (!has_reference || sn_knn > 0) knn = 0;
-    if (has_robust && lsgpu_robust_config_check(&rb, c.error_minimizer, has_reference ? 1 : 0) != LSGPU_OK)
-      throw ConfigError(rb.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE && !has_reference
-                            ? "RobustOutlierFilter: distanceType point2plane needs reference normals (a referenceDataPointsFilters module)"
-                            : "RobustOutlierFilter: refused configuration");
-    if (rd_stage == 3 || ref_stage == 3)
-      throw ConfigError(std::string(rd_stage == 3 ? "readingDataPointsFilters" : "referenceDataPointsFilters") +
-                        ": ObservationDirectionDataPointsFilter" + kPair);
-    const bool has_normals = nc.max_angle >= 0.f || nc.reading_sn_knn != 0 || nc.reading_orient != 0 || nc.reference_orient != 0;
-    if (nc.reading_sn_knn != 0 && !(nc.max_angle >= 0.f))
-      throw ConfigError("readingDataPointsFilters: module SurfaceNormalDataPointsFilter is not implemented on the HIP path unless the "
-                        "chain holds SurfaceNormalOutlierFilter (no other module reads reading normals)");
-    if (nc.max_angle >= 0.f && nc.reading_sn_knn == 0)
-      throw ConfigError("SurfaceNormalOutlierFilter: the reading section provides no normals (SurfaceNormalDataPointsFilter in "
-                        "readingDataPointsFilters)");
-    if (nc.max_angle >= 0.f && !has_reference)
-      throw ConfigError("SurfaceNormalOutlierFilter: the reference section provides no normals (a referenceDataPointsFilters module)");
-    if (has_normals && lsgpu_normals_config_check(&nc, c.error_minimizer, has_reference ? 1 : 0) != LSGPU_OK)
-      throw ConfigError("SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter: refused configuration");
-    if (!has_counter) throw ConfigError("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
-    if (!has_differential) { c.min_diff_rot = -1.f; c.min_diff_trans = -1.f; c.smooth_length = 1; }  // never satisfied: the counter stops
-    cfg_ = c; prob_ = prob; knn_ = knn; ratio_ = ratio; sn_knn_ = sn_knn; robust_ = rb; has_robust_ = has_robust;
-    normals_ = nc; has_normals_ = has_normals;
+    lsgpu_loaded_chain loaded;
+    char why[512];
+    if (lsgpu_chain_load(list.data(), (int)list.size(), &loaded, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
+    loaded_ = loaded;
     release();
   }
 
@@ -508,9 +299,8 @@ class ICP {
     if (nr <= 0 || nq <= 0) { requireRigid(T_init); throw ConvergenceError("empty cloud"); }
     // ICP::compute steps 1-7 on the device: referenceDataPointsFilters, centring + grid,
     // readingDataPointsFilters, the loop (lsgpu_icp_compute)
-    lsgpu_chain_config chain;
-    lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
+    lsgpu_chain_config chain = loaded_.chain;
+    chain.seed = seed_;
     TransformationParameters T = T_init;
     const int rc = lsgpu_icp_compute(h_, reading.features.data(), nq, reference.features.data(), nr, T_init.data(),
                                      &chain, T.data(), &stats_);
@@ -548,9 +338,8 @@ class ICP {
       ensureHandle();
     }
     if (refs.size() != ref_T.size()) throw std::logic_error("one transform per reference cloud");
-    lsgpu_chain_config chain;
-    lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
+    lsgpu_chain_config chain = loaded_.chain;
+    chain.seed = seed_;
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
     TransformationParameters T = T_init;
@@ -573,9 +362,8 @@ class ICP {
       ensureHandle();
     }
     if (refs.size() != ref_T.size()) throw std::logic_error("one transform per reference cloud");
-    lsgpu_chain_config chain;
-    lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
+    lsgpu_chain_config chain = loaded_.chain;
+    chain.seed = seed_;
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
     TransformationParameters T = T_init;
@@ -626,15 +414,15 @@ class ICP {
   }
 
   const lsgpu_icp_stats& lastStats() const { return stats_; }
-  const lsgpu_icp_config& config() const { return cfg_; }
+  const lsgpu_icp_config& config() const { return loaded_.icp; }
   lsgpu_icp* handle() { ensureHandle(); return h_; }  // the C-ABI handle (device conversions of ros_msgs.hpp)
-  float readingSamplingProb() const { return prob_; }
-  int surfaceNormalKnn() const { return knn_; }            // SamplingSurfaceNormalDataPointsFilter's knn (0: no such module)
-  int referenceNormalKnn() const { return sn_knn_; }       // SurfaceNormalDataPointsFilter's knn (0: no such module)
-  float surfaceNormalRatio() const { return ratio_; }
-  const lsgpu_robust_config* robustFilter() const { return has_robust_ ? &robust_ : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
+  float readingSamplingProb() const { return loaded_.chain.reading_prob; }
+  int surfaceNormalKnn() const { return loaded_.chain.ssn_knn; }      // SamplingSurfaceNormalDataPointsFilter's knn (0: no such module)
+  int referenceNormalKnn() const { return loaded_.chain.sn_knn; }     // SurfaceNormalDataPointsFilter's knn (0: no such module)
+  float surfaceNormalRatio() const { return loaded_.chain.ssn_ratio; }
+  const lsgpu_robust_config* robustFilter() const { return loaded_.has_robust ? &loaded_.robust : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
   // SurfaceNormalOutlierFilter / reading normals / the orientation pairs (nullptr: none of these modules)
-  const lsgpu_normals_config* normalsConfig() const { return has_normals_ ? &normals_ : nullptr; }
+  const lsgpu_normals_config* normalsConfig() const { return loaded_.has_normals ? &loaded_.normals : nullptr; }
 
  private:
   using Module = detail::YamlModule;
@@ -681,15 +469,15 @@ class ICP {
 
   void ensureHandle() {
     if (h_) return;
-    const int rc = lsgpu_icp_create(&cfg_, device_, &h_);
+    const int rc = lsgpu_icp_create(&loaded_.icp, device_, &h_);
     if (rc == LSGPU_BAD_CONFIG) throw ConfigError("lsgpu_icp_create: bad configuration");
     if (rc != LSGPU_OK) throw DeviceError("lsgpu_icp_create failed (no ROCm GPU visible?)");
-    if (has_robust_ && lsgpu_icp_set_robust_filter(h_, &robust_) != LSGPU_OK) {
+    if (loaded_.has_robust && lsgpu_icp_set_robust_filter(h_, &loaded_.robust) != LSGPU_OK) {
       const std::string msg = std::string("lsgpu_icp_set_robust_filter: ") + lsgpu_last_error(h_);
       release();
       throw ConfigError(msg);
     }
-    if (has_normals_ && lsgpu_icp_set_normals(h_, &normals_) != LSGPU_OK) {
+    if (loaded_.has_normals && lsgpu_icp_set_normals(h_, &loaded_.normals) != LSGPU_OK) {
       const std::string msg = std::string("lsgpu_icp_set_normals: ") + lsgpu_last_error(h_);
       release();
       throw ConfigError(msg);
@@ -705,16 +493,9 @@ class ICP {
   }
 
   int device_ = 0;
-  lsgpu_icp_config cfg_{};
+  lsgpu_loaded_chain loaded_{};   // what loadFromYaml / setDefault left: the handle's config, the filters of compute()
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
-  float prob_ = 0.75f, ratio_ = 0.5f;
-  int knn_ = 7;
-  int sn_knn_ = 0;
-  lsgpu_robust_config robust_{};
-  bool has_robust_ = false;
-  lsgpu_normals_config normals_{};
-  bool has_normals_ = false;
   int64_t seed_ = -1;
   unsigned generation_ = 0;
 #ifdef LSGPU_TEST_SEAMS

@@ -1,0 +1,323 @@
+// lsgpu_chain_loader.cpp -- lsgpu_chain_load: THE rule set of PointMatcher::ICP::loadFromYaml (laser_slam/src/laser_track.cpp:17)
+// for the device path.  Host only, no HIP.  The C++ facade (cpp/include/laser_slam_amd/icp.hpp) and the Python facade
+// (icp.py) parse the YAML syntax and hand the modules over as text; which modules exist, their parameters, defaults and
+// ranges, what may be given once, the order inside the two filter sections and what the device loop cannot run without are
+// decided here and nowhere else.
+//
+// A new module is one row of kRows and one handler.  The row gives the refusal of an unknown parameter, of a second
+// instance and (by its absence) "is not implemented on the HIP path"; the handler reads the parameters with num() / whole()
+// and writes the ABI structs.  What needs more than one module is checked in finish().
+#include <cctype>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <exception>
+#include <initializer_list>
+#include <string>
+
+#include "../../include/lsgpu_icp.h"
+#include "lsgpu_normal_angle.h"
+#include "lsgpu_robust.h"
+
+namespace {
+
+struct Refusal { std::string why; };
+[[noreturn]] void refuse(const std::string& why) { throw Refusal{why}; }
+
+const char* const kPair = " is implemented only as the pair ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter "
+                          "directly behind the module that produces the normals";
+const char* const kOneReference = "referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or "
+                                  "SurfaceNormalDataPointsFilter)";
+const char* const kSurfaceNormalParams = "knn epsilon maxDist keepNormals keepDensities keepEigenValues keepEigenVectors "
+                                         "keepMatchedIds keepMeanDist sortEigen smoothNormals";
+
+bool listed(const char* list, const char* word) {   // is `word` one of the space-separated words of `list`?
+  const size_t n = std::strlen(word);
+  for (const char* p = list; *p;) {
+    const char* e = std::strchr(p, ' ');
+    const size_t len = e ? (size_t)(e - p) : std::strlen(p);
+    if (len == n && std::strncmp(p, word, n) == 0) return true;
+    p += len + (e ? 1 : 0);
+  }
+  return false;
+}
+
+struct Load {
+  lsgpu_loaded_chain out;
+  const lsgpu_yaml_module* m = nullptr;   // the module being read
+  // where a filter section has got to: 1 RandomSampling (reading) / the module that gives the normals (reference),
+  // 2 SurfaceNormal on the reading, 3 ObservationDirection, 4 OrientNormals
+  int stage[2] = {0, 0};
+  bool matcher = false, minimizer = false, counter = false, robust = false;
+
+  std::string name() const { return m->name; }
+  int side() const { return std::strcmp(m->section, "readingDataPointsFilters") == 0 ? 0 : 1; }
+  const char* text(const char* key) const {   // (a key given twice: the last one, as in a map)
+    const char* v = nullptr;
+    for (int i = 0; i < m->n_params; ++i)
+      if (std::strcmp(m->params[i].key, key) == 0) v = m->params[i].value;
+    return v;
+  }
+  std::string word(const char* key, const char* def) const { const char* v = text(key); return v ? v : def; }
+  // A number: the whole token, "inf" and YAML's .inf / .Inf / .INF (signed or not) included, never NaN.  Any other leading
+  // dot is a plain float (.5 is 0.5)
+  double num(const char* key, double def) const {
+    const char* v = text(key);
+    if (!v) return def;
+    std::string s(v);
+    const size_t sign = (!s.empty() && (s[0] == '+' || s[0] == '-')) ? 1 : 0;
+    const std::string rest = s.substr(sign);
+    if (rest == ".inf" || rest == ".Inf" || rest == ".INF") s = s.substr(0, sign) + "inf";
+    char* end = nullptr;
+    const double x = s.empty() || std::isspace((unsigned char)s[0]) ? NAN : std::strtod(s.c_str(), &end);
+    if (std::isnan(x) || *end != '\0') refuse(name() + ": " + key + " is not a number");
+    return x;
+  }
+  double finite(const char* key, double def) const {
+    const double x = num(key, def);
+    if (std::isinf(x)) refuse(name() + ": " + key + " must be finite");
+    return x;
+  }
+  // An integer parameter of the modules of icp_default.yaml (knn of the sampling filter, the checkers' counts): digits, and
+  // a fraction that is dropped -- both facades always took 7.5 as 7 there, and neither an exponent or an infinity
+  int truncated(const char* key, int def) const {
+    const char* v = text(key);
+    const double x = num(key, def);
+    if ((v && v[std::strspn(v, "+-.0123456789")] != '\0') || !(std::fabs(x) < 2147483648.0)) refuse(name() + ": " + key + " is not an integer");
+    return (int)x;
+  }
+  bool whole(double x) const { return std::fabs(x) < 2147483648.0 && x == (double)(int)x; }
+};
+
+// SurfaceNormalDataPointsFilter's parameters (either side): keepNormals 1 alone, exact (epsilon 0), no maxDist -> knn
+int surface_normal_knn(const Load& l) {
+  const std::string n = l.name();
+  const double k = l.num("knn", 5);
+  if (!(k >= 3 && k <= 32) || !l.whole(k)) refuse(n + ": knn must be an integer in [3, 32]");
+  if (l.num("epsilon", 0.0) != 0.0) refuse(n + ": epsilon must be 0 (the search is exact)");
+  const double md = l.num("maxDist", INFINITY);
+  if (!(std::isinf(md) && md > 0.0)) refuse(n + ": maxDist must be absent or inf");
+  if (l.num("keepNormals", 1) != 1.0) refuse(n + ": keepNormals must be 1 (the module is there for the normals)");
+  for (const char* key : {"keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
+                          "sortEigen", "smoothNormals"})
+    if (l.num(key, 0) != 0.0) refuse(n + ": " + key + " must be 0 or absent");
+  return (int)k;
+}
+
+void random_sampling(Load& l) {
+  if (l.stage[0] >= 2)
+    refuse("readingDataPointsFilters: SurfaceNormalDataPointsFilter before RandomSamplingDataPointsFilter is not "
+           "implemented (the normals would have to be gathered through the sampling)");
+  l.out.chain.reading_prob = (float)l.finite("prob", 0.75);
+  l.stage[0] = 1;
+}
+void reading_normals(Load& l) { l.out.normals.reading_sn_knn = surface_normal_knn(l); l.stage[0] = 2; }
+void sampling_surface_normal(Load& l) {
+  if (l.stage[1]) refuse(kOneReference);
+  l.out.chain.ssn_knn = l.truncated("knn", 7);
+  l.out.chain.ssn_ratio = (float)l.finite("ratio", 0.5);
+  if (l.truncated("samplingMethod", 0) != 0) refuse(l.name() + ": samplingMethod != 0 is not implemented");
+  l.stage[1] = 1;
+}
+void reference_normals(Load& l) {
+  if (l.stage[1]) refuse(kOneReference);
+  l.out.chain.sn_knn = surface_normal_knn(l);
+  l.stage[1] = 1;
+}
+void observation_direction(Load& l) {
+  const int s = l.side();
+  if (l.stage[s] != (s == 0 ? 2 : 1)) refuse(std::string(l.m->section) + ": " + l.name() + kPair);
+  float* sensor = s == 0 ? l.out.normals.reading_sensor : l.out.normals.reference_sensor;
+  const char* keys[3] = {"x", "y", "z"};
+  for (int i = 0; i < 3; ++i) {
+    sensor[i] = (float)l.finite(keys[i], 0.0);
+  }
+  l.stage[s] = 3;
+}
+void orient_normals(Load& l) {
+  const int s = l.side();
+  if (l.stage[s] != 3) refuse(std::string(l.m->section) + ": " + l.name() + kPair);
+  const double tc = l.num("towardCenter", 1);
+  if (tc != 0.0 && tc != 1.0) refuse(l.name() + ": towardCenter must be 0 or 1");
+  (s == 0 ? l.out.normals.reading_orient : l.out.normals.reference_orient) = tc == 1.0 ? 1 : 2;
+  l.stage[s] = 4;
+}
+// knn 1..LSGPU_MATCHER_KNN_MAX, exact search only, maxDist; searchType is accepted and not read.  The one module that may be
+// given again (the last one counts): both facades always took it so
+void kd_tree_matcher(Load& l) {
+  const double md = l.num("maxDist", INFINITY);
+  if (!(md > 0.0)) refuse("KDTreeMatcher: maxDist must be > 0");
+  l.out.icp.matcher_max_dist = std::isinf(md) ? 0.f : (float)md;
+  const double k = l.num("knn", 1);
+  if (!(k >= 1 && k <= LSGPU_MATCHER_KNN_MAX) || !l.whole(k) || l.num("epsilon", 0) != 0.0)
+    refuse("KDTreeMatcher: knn 1.." + std::to_string(LSGPU_MATCHER_KNN_MAX) + " with epsilon 0 is implemented");
+  l.out.icp.matcher_knn = (int)k;
+  l.matcher = true;
+}
+void trimmed_dist(Load& l) {
+  const double r = l.num("ratio", 0.85);
+  if (!(r > 0.0 && r <= 1.0)) refuse(l.name() + ": ratio must be in (0, 1]");
+  l.out.icp.trim_ratio = (float)r;
+}
+void max_dist(Load& l) {
+  const double md = l.num("maxDist", 1.0);
+  if (!(md > 0.0)) refuse(l.name() + ": maxDist must be > 0");
+  l.out.icp.outlier_max_dist = std::isinf(md) ? 0.f : (float)md;
+}
+void min_dist(Load& l) {
+  const double md = l.finite("minDist", 1.0);
+  if (!(md >= 0.0)) refuse(l.name() + ": minDist must be >= 0");
+  l.out.icp.outlier_min_dist = (float)md;
+}
+void median_dist(Load& l) {
+  const double f = l.finite("factor", 3.0);
+  if (!(f > 0.0)) refuse(l.name() + ": factor must be > 0");
+  l.out.icp.outlier_median_factor = (float)f;
+}
+void robust_outlier(Load& l) {
+  const std::string n = l.name();
+  auto pick = [&](const char* key, const std::string& v, std::initializer_list<const char*> names) {
+    int i = 0;
+    for (const char* s : names) { if (v == s) return i; ++i; }
+    refuse(n + ": unknown " + key + " " + v);
+  };
+  const std::string fct = l.word("robustFct", "cauchy"), est = l.word("scaleEstimator", "mad");
+  if (fct == "welsch" || fct == "student")
+    refuse(n + ": robustFct " + fct + " is not implemented on the HIP path (exp / pow are not bit-identical between host and device)");
+  if (est == "berg" || est == "std") refuse(n + ": scaleEstimator " + est + " is not implemented on the HIP path (none and mad are)");
+  lsgpu_robust_config& rb = l.out.robust;
+  rb.robust_fct = pick("robustFct", fct, {"cauchy", "huber", "tukey", "gm", "sc", "L1"});
+  rb.scale_estimator = pick("scaleEstimator", est, {"none", "mad"});
+  rb.distance_type = pick("distanceType", l.word("distanceType", "point2point"), {"point2point", "point2plane"});
+  const double nb = l.num("nbIterationForScale", 0);
+  if (!(nb >= 0.0) || !l.whole(nb)) refuse(n + ": nbIterationForScale must be an integer >= 0");
+  rb.tuning = (float)l.num("tuning", 1.0);
+  rb.approximation = (float)l.num("approximation", INFINITY);
+  rb.nb_iteration_for_scale = (int)nb;
+  l.robust = true;   // (tuning / approximation: robust::check in finish())
+}
+void surface_normal_outlier(Load& l) {
+  const double a = l.num("maxAngle", 1.57);
+  if (!(a >= 0.0 && a <= 3.1416)) refuse(l.name() + ": maxAngle must be in [0, 3.1416]");
+  l.out.normals.max_angle = (float)a;
+}
+void error_minimizer(Load& l) {
+  if (l.minimizer) refuse("errorMinimizer: one module at most");
+  l.out.icp.error_minimizer = l.name() == "PointToPointErrorMinimizer" ? LSGPU_MINIMIZER_POINT_TO_POINT : LSGPU_MINIMIZER_POINT_TO_PLANE;
+  l.minimizer = true;
+}
+void counter_checker(Load& l) { l.out.icp.max_iterations = l.truncated("maxIterationCount", 40); l.counter = true; }
+void differential_checker(Load& l) {
+  l.out.icp.min_diff_rot = (float)l.finite("minDiffRotErr", 0.001);
+  l.out.icp.min_diff_trans = (float)l.finite("minDiffTransErr", 0.001);
+  l.out.icp.smooth_length = l.truncated("smoothLength", 3);
+}
+
+struct Row {
+  const char* section;
+  const char* name;
+  const char* params;   // the parameters the module has, space-separated; nullptr: not looked at
+  bool once;            // a second instance in the section is refused here (false: the handler says what may come twice)
+  void (*load)(Load&);
+};
+const Row kRows[] = {
+    {"readingDataPointsFilters", "RandomSamplingDataPointsFilter", "prob", true, random_sampling},
+    {"readingDataPointsFilters", "SurfaceNormalDataPointsFilter", kSurfaceNormalParams, true, reading_normals},
+    {"readingDataPointsFilters", "ObservationDirectionDataPointsFilter", "x y z", true, observation_direction},
+    {"readingDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
+    {"referenceDataPointsFilters", "SamplingSurfaceNormalDataPointsFilter", "knn ratio samplingMethod", false, sampling_surface_normal},
+    {"referenceDataPointsFilters", "SurfaceNormalDataPointsFilter", kSurfaceNormalParams, false, reference_normals},
+    {"referenceDataPointsFilters", "ObservationDirectionDataPointsFilter", "x y z", true, observation_direction},
+    {"referenceDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
+    {"matcher", "KDTreeMatcher", "knn epsilon searchType maxDist", false, kd_tree_matcher},
+    {"outlierFilters", "TrimmedDistOutlierFilter", "ratio", true, trimmed_dist},
+    {"outlierFilters", "MaxDistOutlierFilter", "maxDist", true, max_dist},
+    {"outlierFilters", "MinDistOutlierFilter", "minDist", true, min_dist},
+    {"outlierFilters", "MedianDistOutlierFilter", "factor", true, median_dist},
+    {"outlierFilters", "RobustOutlierFilter", "robustFct tuning scaleEstimator nbIterationForScale distanceType approximation", true, robust_outlier},
+    {"outlierFilters", "SurfaceNormalOutlierFilter", "maxAngle", true, surface_normal_outlier},
+    {"errorMinimizer", "PointToPlaneErrorMinimizer", nullptr, false, error_minimizer},
+    {"errorMinimizer", "PointToPointErrorMinimizer", nullptr, false, error_minimizer},
+    {"transformationCheckers", "CounterTransformationChecker", "maxIterationCount", true, counter_checker},
+    {"transformationCheckers", "DifferentialTransformationChecker", "minDiffRotErr minDiffTransErr smoothLength", true, differential_checker},
+};
+constexpr int kNumRows = (int)(sizeof(kRows) / sizeof(kRows[0]));
+
+// What the device loop needs: a matcher, a minimiser, a stopping rule, normals for whoever reads them.  (Absent reading
+// filter: every point; absent outlier filter: every pair; absent reference filter with the point-to-point minimiser, which
+// reads no normals: the reference as given; absent differential checker: the counter stops the loop.)
+void finish(Load& l) {
+  lsgpu_loaded_chain& o = l.out;
+  const int have_normals = l.stage[1] != 0;
+  if (!l.matcher) refuse("matcher: KDTreeMatcher is required");
+  if (!l.minimizer) refuse("errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer is required");
+  if (!have_normals && o.icp.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
+    refuse("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter is required (it "
+           "provides the normals of PointToPlaneErrorMinimizer)");
+  const char* why = nullptr;
+  if (l.robust && lsgpu::robust::check(&o.robust, o.icp.error_minimizer, have_normals, &why) != LSGPU_OK) refuse(why);
+  for (int s = 0; s < 2; ++s)
+    if (l.stage[s] == 3)
+      refuse(std::string(s == 0 ? "readingDataPointsFilters" : "referenceDataPointsFilters") + ": ObservationDirectionDataPointsFilter" + kPair);
+  if (lsgpu::normal_angle::check(&o.normals, o.icp.error_minimizer, have_normals, &why) != LSGPU_OK) refuse(why);
+  if (!l.counter) refuse("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
+  o.has_robust = l.robust ? 1 : 0;
+  o.has_normals = o.normals.max_angle >= 0.f || o.normals.reading_sn_knn != 0 || o.normals.reading_orient != 0 || o.normals.reference_orient != 0;
+}
+
+void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
+  // libpointmatcher's loadFromYaml starts from EMPTY chains: a section the file does not mention means "no such module",
+  // not "the default module"
+  std::memset(&l.out, 0, sizeof(l.out));
+  lsgpu_icp_config_default(&l.out.icp);
+  l.out.icp.trim_ratio = 1.0f;
+  l.out.icp.min_diff_rot = -1.f; l.out.icp.min_diff_trans = -1.f; l.out.icp.smooth_length = 1;   // never satisfied
+  lsgpu_chain_config_default(&l.out.chain);
+  l.out.chain.reading_prob = -1.0f;   // no reading filter: every point, no draws
+  l.out.chain.ssn_knn = 0;
+  lsgpu_robust_config_default(&l.out.robust);
+  lsgpu_normals_config_default(&l.out.normals);
+  bool seen[kNumRows] = {};
+  for (int i = 0; i < n_mods; ++i) {
+    const lsgpu_yaml_module& m = mods[i];
+    if (!std::strcmp(m.section, "inspector") || !std::strcmp(m.section, "logger")) continue;   // debug output only (yaml:32-44)
+    int r = 0;
+    while (r < kNumRows && (std::strcmp(kRows[r].section, m.section) || std::strcmp(kRows[r].name, m.name))) ++r;
+    if (r == kNumRows) refuse(std::string(m.section) + ": module " + m.name + " is not implemented on the HIP path");
+    if (seen[r] && kRows[r].once) refuse(std::string(m.section) + ": " + m.name + " given twice");
+    seen[r] = true;
+    for (int p = 0; kRows[r].params && p < m.n_params; ++p)
+      if (!listed(kRows[r].params, m.params[p].key)) refuse(std::string(m.name) + ": unknown parameter " + m.params[p].key);
+    l.m = &m;
+    kRows[r].load(l);
+  }
+  finish(l);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  if (!out || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
+  for (int i = 0; i < n_mods; ++i) {
+    if (!mods[i].section || !mods[i].name || mods[i].n_params < 0 || (mods[i].n_params > 0 && !mods[i].params)) return LSGPU_BAD_ARG;
+    for (int p = 0; p < mods[i].n_params; ++p)
+      if (!mods[i].params[p].key || !mods[i].params[p].value) return LSGPU_BAD_ARG;
+  }
+  try {
+    Load l;
+    load(mods, n_mods, l);
+    *out = l.out;
+    return LSGPU_OK;
+  } catch (const Refusal& r) {
+    if (why && why_cap > 0) std::snprintf(why, (size_t)why_cap, "%s", r.why.c_str());
+    return LSGPU_BAD_CONFIG;
+  } catch (const std::exception&) {   // (no exception crosses the ABI)
+    return LSGPU_BAD_ARG;
+  }
+}
+
+}  // extern "C"

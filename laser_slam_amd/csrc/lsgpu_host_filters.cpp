@@ -252,6 +252,11 @@ void lsgpu_robust_config_default(lsgpu_robust_config* c) {
 int lsgpu_robust_config_check(const lsgpu_robust_config* c, int error_minimizer, int have_normals) {
   return lsgpu::robust::check(c, error_minimizer, have_normals, nullptr);
 }
+const char* lsgpu_robust_config_why(const lsgpu_robust_config* c, int error_minimizer, int have_normals) {
+  const char* why = nullptr;
+  lsgpu::robust::check(c, error_minimizer, have_normals, &why);
+  return why;
+}
 
 int lsgpu_robust_scale(const float* d2, int64_t n, float* median, float* scale) {
   if (!d2 || n < 0 || !median || !scale) return LSGPU_BAD_ARG;
@@ -287,6 +292,11 @@ void lsgpu_normals_config_default(lsgpu_normals_config* c) {
 
 int lsgpu_normals_config_check(const lsgpu_normals_config* c, int error_minimizer, int have_reference_normals) {
   return lsgpu::normal_angle::check(c, error_minimizer, have_reference_normals, nullptr);
+}
+const char* lsgpu_normals_config_why(const lsgpu_normals_config* c, int error_minimizer, int have_reference_normals) {
+  const char* why = nullptr;
+  lsgpu::normal_angle::check(c, error_minimizer, have_reference_normals, &why);
+  return why;
 }
 
 int lsgpu_orient_normals(const float* xyz1, int64_t n, const float sensor[3], int mode, float* normals) {

@@ -93,13 +93,15 @@ class IcpHandle:
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
-            if L.lsgpu_normals_config_check(C.byref(nc), 0, 1) != _lib.OK:
-                raise LsgpuError(_lib.BAD_CONFIG, "lsgpu_normals_config_check", _normals_why(nc))
+            why = L.lsgpu_normals_config_why(C.byref(nc), 0, 1)
+            if why:
+                raise LsgpuError(_lib.BAD_CONFIG, "lsgpu_normals_config_check", why.decode())
         rb = robust_cfg(robust) if robust is not None else None
         if rb is not None:                                      # refused values: before the device is touched
             mini = _MINIMIZERS.get(error_minimizer, error_minimizer) if error_minimizer is not None else (cfg.error_minimizer if cfg is not None else 0)
-            if L.lsgpu_robust_config_check(C.byref(rb), int(mini), 1) != _lib.OK:
-                raise LsgpuError(_lib.BAD_CONFIG, "lsgpu_robust_config_check", "RobustOutlierFilter: " + _robust_why(rb))
+            why = L.lsgpu_robust_config_why(C.byref(rb), int(mini), 1)
+            if why:
+                raise LsgpuError(_lib.BAD_CONFIG, "lsgpu_robust_config_check", why.decode())
         if cfg is None:
             cfg = IcpConfig()
             L.lsgpu_icp_config_yaml(C.byref(cfg))
@@ -706,20 +708,6 @@ def robust_cfg(r) -> "_lib.RobustCfg":
                           int(r.nb_iteration_for_scale), _lib.ROBUST_DIST[r.distance_type], float(r.approximation))
 
 
-def _robust_why(rb) -> str:
-    if rb.robust_fct in (_lib.ROBUST_FCT["welsch"], _lib.ROBUST_FCT["student"]):
-        return "robustFct welsch / student are not implemented (exp / pow are not bit-identical between host and device)"
-    if rb.scale_estimator in (_lib.ROBUST_SCALE["berg"], _lib.ROBUST_SCALE["std"]):
-        return "scaleEstimator berg / std are not implemented (none and mad are)"
-    if not rb.tuning >= 0:
-        return "tuning must be >= 0"
-    if not rb.approximation >= 0:
-        return "approximation must be >= 0"
-    if rb.nb_iteration_for_scale < 0:
-        return "nbIterationForScale must be >= 0"
-    return "refused configuration"
-
-
 @dataclass
 class NormalsConfig:
     """lsgpu_normals_config: SurfaceNormalOutlierFilter (max_angle < 0: none), SurfaceNormalDataPointsFilter on the reading
@@ -746,19 +734,6 @@ def normals_cfg(n) -> "_lib.NormalsCfg":
         c.reference_sensor[i] = float(n.reference_sensor[i])
     c.reading_normals_given = int(n.reading_normals_given)
     return c
-
-
-def _normals_why(nc) -> str:
-    if math.isnan(nc.max_angle) or nc.max_angle > 3.1416:
-        return "SurfaceNormalOutlierFilter: maxAngle must be in [0, 3.1416]"
-    if nc.reading_sn_knn and not 3 <= nc.reading_sn_knn <= 32:
-        return "SurfaceNormalDataPointsFilter (reading): knn must be in [3, 32]"
-    if nc.max_angle >= 0 and not nc.reading_sn_knn and not nc.reading_normals_given:
-        return "SurfaceNormalOutlierFilter: the reading section provides no normals (SurfaceNormalDataPointsFilter)"
-    if nc.reading_sn_knn and not nc.max_angle >= 0:
-        return ("SurfaceNormalDataPointsFilter (reading): only SurfaceNormalOutlierFilter reads reading normals, and the "
-                "chain holds none")
-    return "SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter: a value is out of range"
 
 
 def orient_normals(xyz1, normals, sensor, toward_center: bool = True) -> np.ndarray:
@@ -827,18 +802,6 @@ def correct_rigid(T) -> np.ndarray:
 
 # ---------------------------------------------------------------------------------------------
 
-_SUPPORTED = {
-    "readingDataPointsFilters": {"RandomSamplingDataPointsFilter", "SurfaceNormalDataPointsFilter",
-                                 "ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter"},
-    "referenceDataPointsFilters": {"SamplingSurfaceNormalDataPointsFilter", "SurfaceNormalDataPointsFilter",
-                                   "ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter"},
-    "matcher": {"KDTreeMatcher"},
-    "outlierFilters": {"TrimmedDistOutlierFilter", "MaxDistOutlierFilter", "MinDistOutlierFilter",
-                       "MedianDistOutlierFilter", "RobustOutlierFilter", "SurfaceNormalOutlierFilter"},
-    "errorMinimizer": {"PointToPlaneErrorMinimizer", "PointToPointErrorMinimizer"},
-    "transformationCheckers": {"CounterTransformationChecker", "DifferentialTransformationChecker"},
-}
-
 _MINIMIZERS = {"PointToPlaneErrorMinimizer": _lib.MINIMIZER_POINT_TO_PLANE,
                "PointToPointErrorMinimizer": _lib.MINIMIZER_POINT_TO_POINT}
 
@@ -891,6 +854,56 @@ class ChainConfig:
             self.extra["robust"] = value
 
 
+def chain_load(doc):
+    """lsgpu_chain_load on a YAML chain document read with yaml.BaseLoader (every scalar stays text): its modules, section by
+    section in the document's order -> (return code, reason of a refusal, _lib.LoadedChain).  The rules are the library's."""
+    mods = []
+    for section, v in doc.items():
+        for it in (v if isinstance(v, list) else [v]):
+            if isinstance(it, str) and it:                      # `- Name` / `section: Name`
+                mods.append((section, it, {}))
+            elif isinstance(it, dict):                          # `- Name: {params}` / `Name:` with an indented block
+                mods += [(section, name, p if isinstance(p, dict) else {}) for name, p in it.items()]
+    arr = (_lib.YamlModule * max(len(mods), 1))()
+    keep = []
+    for a, (section, name, params) in zip(arr, mods):
+        kv = sorted((str(k).encode(), str(v).encode()) for k, v in params.items())   # by key, as the C++ facade's std::map
+        ps = (_lib.YamlParam * max(len(kv), 1))(*[_lib.YamlParam(k, v) for k, v in kv])
+        keep.append(ps)
+        a.section, a.name, a.params, a.n_params = str(section).encode(), str(name).encode(), ps, len(kv)
+    out = _lib.LoadedChain()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load(arr, len(mods), C.byref(out), why, len(why))
+    return rc, why.value.decode(), out
+
+
+def _f32(x) -> float:
+    """The shortest decimal that is this float32 (0.75, not 0.75000000000000011...): what the document said."""
+    return float(str(np.float32(x)))
+
+
+def _chain_config(lc) -> "ChainConfig":
+    """_lib.LoadedChain -> ChainConfig"""
+    i, c = lc.icp, lc.chain
+    name = {v: k for k, v in _MINIMIZERS.items()}[i.error_minimizer]
+    ch = ChainConfig(reading_sampling_prob=_f32(c.reading_prob), surface_normal_knn=c.ssn_knn,
+                     surface_normal_ratio=_f32(c.ssn_ratio), reference_normal_knn=c.sn_knn, trim_ratio=_f32(i.trim_ratio),
+                     max_iterations=i.max_iterations, min_diff_rot=_f32(i.min_diff_rot), min_diff_trans=_f32(i.min_diff_trans),
+                     smooth_length=i.smooth_length, error_minimizer=name, matcher_knn=i.matcher_knn,
+                     matcher_max_dist=_f32(i.matcher_max_dist), outlier_max_dist=_f32(i.outlier_max_dist),
+                     outlier_min_dist=_f32(i.outlier_min_dist), outlier_median_factor=_f32(i.outlier_median_factor))
+    if lc.has_robust:
+        r = lc.robust
+        word = lambda table, v: next(k for k, x in table.items() if x == v)
+        ch.robust = RobustConfig(word(_lib.ROBUST_FCT, r.robust_fct), _f32(r.tuning), word(_lib.ROBUST_SCALE, r.scale_estimator),
+                                 r.nb_iteration_for_scale, word(_lib.ROBUST_DIST, r.distance_type), _f32(r.approximation))
+    if lc.has_normals:
+        n = lc.normals
+        ch.normals = NormalsConfig(_f32(n.max_angle), n.reading_sn_knn, n.reading_orient, n.reference_orient,
+                                   tuple(_f32(v) for v in n.reading_sensor), tuple(_f32(v) for v in n.reference_sensor))
+    return ch
+
+
 class ICP:
     """Drop-in for the reference's ``PointMatcher::ICP icp_`` member."""
 
@@ -913,251 +926,22 @@ class ICP:
         PointMatcher's registrar does for unknown module names."""
         import yaml
         if hasattr(stream, "read"):
-            doc = yaml.safe_load(stream.read())
+            text = stream.read()
         else:
             try:
                 with open(stream) as f:
-                    doc = yaml.safe_load(f.read())
+                    text = f.read()
             except (OSError, ValueError):
-                doc = yaml.safe_load(stream)
+                text = stream
+        doc = yaml.load(text, Loader=yaml.BaseLoader)           # scalars stay text: the library reads the numbers
+        if doc is None:
+            doc = {}
         if not isinstance(doc, dict):
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "not a YAML mapping")
-        # libpointmatcher's loadFromYaml starts from EMPTY chains: a section the file does not mention means "no such
-        # module".  No reading filter = every point and no draw (reading_prob < 0), no outlier filter = every pair (ratio 1), no differential
-        # checker = only the counter stops the loop; the modules the device loop cannot run without are required.
-        ch = ChainConfig(reading_sampling_prob=-1.0, surface_normal_knn=7, trim_ratio=1.0,
-                         min_diff_rot=-1.0, min_diff_trans=-1.0, smooth_length=1)
-        seen = set()
-        order, sensor, toward = {}, {}, {}
-        nrm = NormalsConfig()
-
-        def modules(section):
-            v = doc.get(section)
-            if v is None:
-                return []
-            items = v if isinstance(v, list) else [v]
-            out = []
-            for it in items:
-                if isinstance(it, str):
-                    out.append((it, {}))
-                elif isinstance(it, dict):
-                    for k, p in it.items():
-                        out.append((k, p or {}))
-            return out
-
-        def bad(text):
-            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", text)
-
-        def only(name, params, *known):      # a parameter the module does not have is a configuration error
-            for k in params:
-                if k not in known:
-                    bad(f"{name}: unknown parameter {k}")
-
-        def one_float(name, params, key, default):
-            try:
-                v = float(params.get(key, default))
-            except (TypeError, ValueError):
-                bad(f"{name}: {key} is not a number")
-            if math.isnan(v):
-                bad(f"{name}: {key} is not a number")
-            return v
-
-        for section, allowed in _SUPPORTED.items():
-            for name, params in modules(section):
-                if name not in allowed:
-                    raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml",
-                                     f"{section}: module {name} is not implemented on the HIP path")
-                reading = section == "readingDataPointsFilters"
-                side_key = name
-                if name in ("ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter") or \
-                        (reading and name == "SurfaceNormalDataPointsFilter"):
-                    side_key = section + ":" + name       # (these may appear once per section)
-                if side_key in seen and name != "KDTreeMatcher":
-                    raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{section}: {name} given twice")
-                seen.add(side_key)
-                order.setdefault(section, []).append(name)
-                if name == "ObservationDirectionDataPointsFilter":
-                    only(name, params, "x", "y", "z")
-                    sensor[section] = tuple(one_float(name, params, k, 0.0) for k in ("x", "y", "z"))
-                    if not all(math.isfinite(v) for v in sensor[section]):
-                        bad(f"{name}: x, y, z must be finite")
-                elif name == "OrientNormalsDataPointsFilter":
-                    only(name, params, "towardCenter")
-                    tc = one_float(name, params, "towardCenter", 1)
-                    if tc not in (0, 1):
-                        bad(f"{name}: towardCenter must be 0 or 1 (got {params.get('towardCenter')})")
-                    toward[section] = 1 if tc == 1 else 2
-                elif name == "SurfaceNormalOutlierFilter":
-                    only(name, params, "maxAngle")
-                    nrm.max_angle = one_float(name, params, "maxAngle", 1.57)
-                    if not 0.0 <= nrm.max_angle <= 3.1416:
-                        bad(f"{name}: maxAngle must be in [0, 3.1416] (got {nrm.max_angle})")
-                elif name == "RandomSamplingDataPointsFilter":
-                    ch.reading_sampling_prob = float(params.get("prob", 0.75))
-                elif name == "SamplingSurfaceNormalDataPointsFilter":
-                    ch.surface_normal_knn = int(params.get("knn", 7))
-                    ch.surface_normal_ratio = float(params.get("ratio", 0.5))
-                    if int(params.get("samplingMethod", 0)) != 0:
-                        raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "samplingMethod != 0")
-                elif name == "SurfaceNormalDataPointsFilter":
-                    # every point, the normal of its knn nearest neighbours: what the device filter computes is
-                    # keepNormals 1 alone, exact (epsilon 0), unbounded (no maxDist)
-                    only(name, params, "knn", "epsilon", "maxDist", "keepNormals", "keepDensities", "keepEigenValues",
-                         "keepEigenVectors", "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals")
-                    kf = one_float(name, params, "knn", 5)
-                    if not 3 <= kf <= 32 or kf != int(kf):
-                        bad(f"{name}: knn must be an integer in [3, 32] (got {params.get('knn')})")
-                    knn = int(kf)
-                    if one_float(name, params, "epsilon", 0.0) != 0.0:
-                        bad(f"{name}: epsilon must be 0 (the search is exact)")
-                    if not math.isinf(one_float(name, params, "maxDist", math.inf)) or one_float(name, params, "maxDist", math.inf) < 0:
-                        bad(f"{name}: maxDist must be absent or inf")
-                    if one_float(name, params, "keepNormals", 1) != 1:
-                        bad(f"{name}: keepNormals must be 1 (the module is there for the normals)")
-                    for key in ("keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
-                                "sortEigen", "smoothNormals"):
-                        if one_float(name, params, key, 0) != 0:
-                            bad(f"{name}: {key} must be 0 or absent")
-                    if reading:
-                        nrm.reading_sn_knn = knn
-                    else:
-                        ch.reference_normal_knn = knn
-                elif name == "KDTreeMatcher":
-                    # (its other parameters -- searchType, ... -- are not read)
-                    md = one_float(name, params, "maxDist", math.inf)
-                    if not md > 0.0:
-                        bad(f"KDTreeMatcher: maxDist must be > 0 (got {md})")
-                    ch.matcher_max_dist = 0.0 if math.isinf(md) else md
-                    knn = int(params.get("knn", 1))
-                    if not 1 <= knn <= _lib.MATCHER_KNN_MAX or float(params.get("epsilon", 0)) != 0.0:
-                        raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml",
-                                         f"KDTreeMatcher: knn 1..{_lib.MATCHER_KNN_MAX} with epsilon 0 is implemented")
-                    ch.matcher_knn = knn
-                elif name == "TrimmedDistOutlierFilter":
-                    only(name, params, "ratio")
-                    ch.trim_ratio = one_float(name, params, "ratio", 0.85)
-                    if not 0.0 < ch.trim_ratio <= 1.0:
-                        bad(f"TrimmedDistOutlierFilter: ratio must be in (0, 1] (got {ch.trim_ratio})")
-                elif name == "MaxDistOutlierFilter":
-                    only(name, params, "maxDist")
-                    md = one_float(name, params, "maxDist", 1.0)
-                    if not md > 0.0:
-                        bad(f"MaxDistOutlierFilter: maxDist must be > 0 (got {md})")
-                    ch.outlier_max_dist = 0.0 if math.isinf(md) else md
-                elif name == "MinDistOutlierFilter":
-                    only(name, params, "minDist")
-                    ch.outlier_min_dist = one_float(name, params, "minDist", 1.0)
-                    if not 0.0 <= ch.outlier_min_dist < math.inf:
-                        bad(f"MinDistOutlierFilter: minDist must be >= 0 and finite (got {ch.outlier_min_dist})")
-                elif name == "MedianDistOutlierFilter":
-                    only(name, params, "factor")
-                    ch.outlier_median_factor = one_float(name, params, "factor", 3.0)
-                    if not 0.0 < ch.outlier_median_factor < math.inf:
-                        bad(f"MedianDistOutlierFilter: factor must be > 0 and finite (got {ch.outlier_median_factor})")
-                elif name == "RobustOutlierFilter":
-                    only(name, params, "robustFct", "tuning", "scaleEstimator", "nbIterationForScale", "distanceType",
-                         "approximation")
-                    rb = RobustConfig(str(params.get("robustFct", "cauchy")), one_float(name, params, "tuning", 1.0),
-                                      str(params.get("scaleEstimator", "mad")), 0,
-                                      str(params.get("distanceType", "point2point")),
-                                      one_float(name, params, "approximation", math.inf))
-                    nb = one_float(name, params, "nbIterationForScale", 0)
-                    if nb < 0 or nb != int(nb):
-                        bad(f"{name}: nbIterationForScale must be an integer >= 0 (got {params.get('nbIterationForScale')})")
-                    rb.nb_iteration_for_scale = int(nb)
-                    if rb.robust_fct in ("welsch", "student"):
-                        bad(f"{name}: robustFct {rb.robust_fct} is not implemented on the HIP path (exp / pow are not "
-                            "bit-identical between host and device)")
-                    if rb.robust_fct not in _lib.ROBUST_FCT:
-                        bad(f"{name}: unknown robustFct {rb.robust_fct}")
-                    if rb.scale_estimator in ("berg", "std"):
-                        bad(f"{name}: scaleEstimator {rb.scale_estimator} is not implemented on the HIP path (none and mad are)")
-                    if rb.scale_estimator not in _lib.ROBUST_SCALE:
-                        bad(f"{name}: unknown scaleEstimator {rb.scale_estimator}")
-                    if rb.distance_type not in _lib.ROBUST_DIST:
-                        bad(f"{name}: unknown distanceType {rb.distance_type}")
-                    if not rb.tuning >= 0.0:
-                        bad(f"{name}: tuning must be >= 0 (got {rb.tuning})")
-                    if not rb.approximation >= 0.0:
-                        bad(f"{name}: approximation must be >= 0 (got {rb.approximation})")
-                    ch.robust = rb
-                elif name in _MINIMIZERS:
-                    if "minimizer" in seen:
-                        raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "errorMinimizer: one module at most")
-                    seen.add("minimizer")
-                    ch.error_minimizer = name
-                elif name == "CounterTransformationChecker":
-                    ch.max_iterations = int(params.get("maxIterationCount", 40))
-                elif name == "DifferentialTransformationChecker":
-                    ch.min_diff_rot = float(params.get("minDiffRotErr", 0.001))
-                    ch.min_diff_trans = float(params.get("minDiffTransErr", 0.001))
-                    ch.smooth_length = int(params.get("smoothLength", 3))
-        if modules("readingStepDataPointsFilters"):
-            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "readingStepDataPointsFilters")
-        # the point-to-point minimizer reads no normals: without a reference filter module the reference is used as given
-        p2p = ch.error_minimizer == "PointToPointErrorMinimizer"
-        ref_order, rd_order = order.get("referenceDataPointsFilters", []), order.get("readingDataPointsFilters", [])
-        pair = ["ObservationDirectionDataPointsFilter", "OrientNormalsDataPointsFilter"]
-
-        def oriented(section, names, head):
-            """names = head [+ the orientation pair]: -> 0 / 1 / 2; anything else is refused with the module's name"""
-            rest = names[len(head):]
-            if names[:len(head)] != head or rest not in ([], pair):
-                for n in pair:
-                    if n in names:
-                        bad(f"{section}: {n} is implemented only as the pair ObservationDirectionDataPointsFilter, "
-                            "OrientNormalsDataPointsFilter directly behind the module that produces the normals")
-                return None
-            return toward[section] if rest else 0
-        if "SurfaceNormalDataPointsFilter" in rd_order and "RandomSamplingDataPointsFilter" in rd_order and \
-                rd_order.index("SurfaceNormalDataPointsFilter") < rd_order.index("RandomSamplingDataPointsFilter"):
-            bad("readingDataPointsFilters: SurfaceNormalDataPointsFilter before RandomSamplingDataPointsFilter is not "
-                "implemented (the normals would have to be gathered through the sampling)")
-        rd_head = [n for n in rd_order if n in ("RandomSamplingDataPointsFilter", "SurfaceNormalDataPointsFilter")]
-        if rd_head and rd_head[-1] != "SurfaceNormalDataPointsFilter" and any(n in rd_order for n in pair):
-            bad("readingDataPointsFilters: OrientNormalsDataPointsFilter / ObservationDirectionDataPointsFilter need the normals "
-                "of a SurfaceNormalDataPointsFilter in front of them")
-        nrm.reading_orient = oriented("readingDataPointsFilters", rd_order, rd_head) or 0
-        if any(n in rd_order for n in pair) and nrm.reading_sn_knn == 0:
-            bad("readingDataPointsFilters: OrientNormalsDataPointsFilter / ObservationDirectionDataPointsFilter need the normals "
-                "of a SurfaceNormalDataPointsFilter in front of them")
-        ref_head = [n for n in ref_order if n not in pair]
-        if len(ref_head) == 1:
-            nrm.reference_orient = oriented("referenceDataPointsFilters", ref_order, ref_head) or 0
-        elif any(n in ref_order for n in pair) and not ref_head:
-            bad("referenceDataPointsFilters: OrientNormalsDataPointsFilter / ObservationDirectionDataPointsFilter need the normals "
-                "of a reference filter in front of them")
-        nrm.reading_sensor = sensor.get("readingDataPointsFilters", (0.0, 0.0, 0.0))
-        nrm.reference_sensor = sensor.get("referenceDataPointsFilters", (0.0, 0.0, 0.0))
-        if nrm.reading_sn_knn and nrm.max_angle < 0:
-            bad("readingDataPointsFilters: module SurfaceNormalDataPointsFilter is not implemented on the HIP path unless the "
-                "chain holds SurfaceNormalOutlierFilter (no other module reads reading normals)")
-        if nrm.max_angle >= 0 and not nrm.reading_sn_knn:
-            bad("SurfaceNormalOutlierFilter: the reading section provides no normals (SurfaceNormalDataPointsFilter in "
-                "readingDataPointsFilters)")
-        if nrm.max_angle >= 0 and not ref_head:
-            bad("SurfaceNormalOutlierFilter: the reference section provides no normals (a referenceDataPointsFilters module)")
-        if nrm != NormalsConfig():
-            ch.normals = nrm
-        if len(ref_head) > 1:
-            bad("referenceDataPointsFilters: one module at most (SamplingSurfaceNormalDataPointsFilter or "
-                "SurfaceNormalDataPointsFilter)")
-        if "SurfaceNormalDataPointsFilter" in seen or "SamplingSurfaceNormalDataPointsFilter" in seen:
-            seen.add("reference normals")                       # either filter provides them
-        if "SamplingSurfaceNormalDataPointsFilter" not in seen:
-            ch.surface_normal_knn = 0
-        labels = {"reference normals": "referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or "
-                                       "SurfaceNormalDataPointsFilter",
-                  "minimizer": "errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer"}
-        for need, why in (("reference normals", "it provides the normals of the point-to-plane minimizer"),
-                          ("KDTreeMatcher", "the matcher"), ("minimizer", "the error minimizer"),
-                          ("CounterTransformationChecker", "the loop would not stop")):
-            if need not in seen and not (p2p and need == "reference normals"):
-                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", f"{labels.get(need, need)} is required ({why})")
-        if ch.robust is not None and ch.robust.distance_type == "point2plane" and "reference normals" not in seen:
-            bad("RobustOutlierFilter: distanceType point2plane needs reference normals (a referenceDataPointsFilters module)")
-        # inspector / logger (yaml:32-44) only produce debug dumps: accepted and ignored
-        self.chain = ch
+        rc, why, loaded = chain_load(doc)
+        if rc != _lib.OK:
+            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+        self.chain = _chain_config(loaded)
         self._handle = None
 
     def _ensure_handle(self) -> IcpHandle:
