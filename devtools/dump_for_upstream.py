@@ -13,6 +13,9 @@ For a synthetic HDL-64E pair (default: the 4 k-point pair of the parity tests, `
   reading_filtered.csv                       what RandomSamplingDataPointsFilter leaves: choice 8 (the draws continue the
                                              reference filter's; the process starts at srand(1) like an unseeded one)
   input_filtered.csv                         reading.csv through tests/golden/input_filters.yaml (srand(1) again): choice 9
+  input_filters.yaml                         only with --voxel-grid VX,VY,VZ[,useCentroid]: the golden input chain with a
+                                             VoxelGridDataPointsFilter appended -- the chain input_filtered.csv (and, with
+                                             --submap, scan*_input_filtered.csv) then went through: choices 30-34
   oracle_trace.csv                           per iteration: iter, limit (squared metres), n_used, T_iter (16, column major)
   oracle_result.txt                          rc, iterations, converged, final T (4 x 4 row major)
   README.txt                                 what is what, and which file / column each restatement choice would change
@@ -31,9 +34,10 @@ float relative pose + concatenate, :474-486), the guess is T_a^-1 T_b of the odo
 
 The files regenerate byte for byte (tests/test_oracle.py::test_upstream_dump_regenerates).  INTEGRATION.md has the
 C++ program that replays them on a real PointMatcher<float>::ICP and prints a trace in the same format.
-usage: dump_for_upstream.py OUT_DIR [--n-az 64] [--chain tests/golden/icp_chain_tight.yaml] [--submap]
+usage: dump_for_upstream.py OUT_DIR [--n-az 64] [--chain tests/golden/icp_chain_tight.yaml] [--submap] [--voxel-grid 0.5,0.5,0.5]
 """
 import argparse
+import ctypes as C
 import os
 import shutil
 import sys
@@ -58,6 +62,12 @@ CHOICES = """Restatement choices of oracle/icp_oracle.h and where a different up
 10 kept points in ascending ORIGINAL index             reference_filtered.csv: row order (upstream sorts indicesToKeep before it compacts)
 11 box eigenvectors: Jacobi in double on the float C   reference_filtered.csv: last digits of nx, ny, nz (upstream: EigenSolver in float)
 """
+VOXEL_CHOICES = """30 VoxelGrid: float bounds, numDiv = (uint)((1 + maxB) - minB)   input_filtered.csv: number of rows
+31 VoxelGrid: cell indices clamped to numDiv - 1                 input_filtered.csv: rows at the cloud's upper faces
+32 VoxelGrid: centroid = first point + the others in input order, / count   input_filtered.csv: last digits of x, y, z
+33 VoxelGrid: output in the order of the voxels' first points    input_filtered.csv: row order
+34 VoxelGrid: the pad row and descriptors are the first point's  input_filtered.csv: nothing (pad is 1)
+"""
 
 
 def g(v) -> str:
@@ -72,10 +82,18 @@ def parse_chain(path):
     return m.chain
 
 
-def input_filter_chain(path):
-    """tests/golden/input_filters.yaml -> oracle PointFilter array (the five module types of the golden chain)."""
+def voxel_grid_yaml(vsize=(1.0, 1.0, 1.0), use_centroid=1, average_existing_descriptors=1) -> str:
+    """The module as one item of a libpointmatcher DataPointsFilters file ("%.9g": the float comes back bit for bit)."""
+    return ("- VoxelGridDataPointsFilter:\n    vSizeX: %s\n    vSizeY: %s\n    vSizeZ: %s\n    useCentroid: %d\n"
+            "    averageExistingDescriptors: %d\n" % (g(np.float32(vsize[0])), g(np.float32(vsize[1])), g(np.float32(vsize[2])),
+                                                       int(use_centroid), int(average_existing_descriptors)))
+
+
+def input_filter_chain(path, text=None):
+    """tests/golden/input_filters.yaml (or the text of such a file) -> oracle PointFilter array.  VoxelGridDataPointsFilter
+    (type 7) is not in the oracle: run_input_filters hands it to the library's host twin."""
     import yaml
-    doc = yaml.safe_load(open(path).read()) or []
+    doc = yaml.safe_load(open(path).read() if text is None else text) or []
     arr = (O.PointFilter * len(doc))()
     for a, item in zip(arr, doc):
         (name, p), = item.items() if isinstance(item, dict) else ((item, {}),)
@@ -95,9 +113,35 @@ def input_filter_chain(path):
             a.type = 5; a.v[0] = float(p.get("prob", 0.75))
         elif name == "RemoveNaNDataPointsFilter":
             a.type = 6
+        elif name == "VoxelGridDataPointsFilter":
+            a.type, a.flag, a.dim = 7, int(p.get("useCentroid", 1)), int(p.get("averageExistingDescriptors", 1))
+            for i, k in enumerate(("vSizeX", "vSizeY", "vSizeZ")):
+                a.v[i] = float(p.get(k, 1.0))
         else:
             raise SystemExit("input filter %s is not in the restatement" % name)
     return arr
+
+
+def run_input_filters(flt, cloud, seed):
+    """The chain on one cloud: the oracle for every run of its own modules (one draw stream, `seed` before the first), the
+    host twin of the library (lsgpu_filter_voxel_grid_points, no GPU) for VoxelGridDataPointsFilter, which draws nothing.
+    None if a module is handed an empty cloud."""
+    from laser_slam_amd import icp
+    i, n = 0, len(flt)
+    while i < n and cloud is not None:
+        if cloud.shape[0] == 0:
+            return None
+        if flt[i].type == 7:
+            cloud = icp.voxel_grid_points(cloud, [flt[i].v[k] for k in range(3)], flt[i].flag)
+            i += 1
+            continue
+        j = i
+        while j < n and flt[j].type != 7:
+            j += 1
+        part = (O.PointFilter * (j - i)).from_address(C.addressof(flt) + i * C.sizeof(O.PointFilter))   # (FixStep's state stays in flt)
+        cloud = O.apply_point_filters(part, cloud, seed=seed)
+        seed, i = -1, j
+    return cloud
 
 
 def write_mat(path, T):
@@ -106,20 +150,32 @@ def write_mat(path, T):
             f.write(" ".join(g(T[r, c]) for c in range(4)) + "\n")
 
 
-def submap_inputs(out_dir, n_az):
+def input_chain_for_dump(out_dir, voxel_grid):
+    """The golden input chain; with `voxel_grid` (vSizeX, vSizeY, vSizeZ[, useCentroid]) the module is appended and the
+    chain's text written to OUT_DIR/input_filters.yaml."""
+    path = os.path.join(ROOT, "tests", "golden", "input_filters.yaml")
+    if not voxel_grid:
+        return input_filter_chain(path)
+    text = open(path).read().rstrip("\n") + "\n" + voxel_grid_yaml(voxel_grid[:3], int(voxel_grid[3]) if len(voxel_grid) > 3 else 1, 0)
+    with open(os.path.join(out_dir, "input_filters.yaml"), "w") as f:
+        f.write(text)
+    return input_filter_chain(None, text)
+
+
+def submap_inputs(out_dir, n_az, voxel_grid=None):
     """laser_track.cpp:146, 466-496 on four synthetic scans: input filters, sub-map of three in the frame of scan 2, the
     odometry guess.  Returns (reading, reference, T_init 4x4 float64, seed for the ICP's first draw)."""
     scene = synth.Scene(1234)
     truth = [synth.se3(0.8 * i, 0.05 * i, synth.SENSOR_HEIGHT, yaw=np.deg2rad(2.0 * i)) for i in range(4)]
     odom = [T @ synth.se3(0.1, -0.05, 0.0, yaw=np.deg2rad(0.5)) for T in truth]     # (the drive of bench.py's value_track)
-    flt = input_filter_chain(os.path.join(ROOT, "tests", "golden", "input_filters.yaml"))
+    flt = input_chain_for_dump(out_dir, voxel_grid)
     filtered = []
     with open(os.path.join(out_dir, "poses.txt"), "w") as f:
         for i in range(4):
             raw = synth.hdl64_scan(scene, truth[i], n_az, 10 + i)
             cloud_io.save_vtk(os.path.join(out_dir, "scan%d.vtk" % i), raw)
             cloud_io.save_csv(os.path.join(out_dir, "scan%d.csv" % i), raw)
-            kept = O.apply_point_filters(flt, raw, seed=1 if i == 0 else -1)       # one process, one rand() stream
+            kept = run_input_filters(flt, raw, 1 if i == 0 else -1)                # one process, one rand() stream
             kept = kept if kept is not None else raw[:0]
             cloud_io.save_csv(os.path.join(out_dir, "scan%d_input_filtered.csv" % i), kept)
             filtered.append(kept)
@@ -134,12 +190,12 @@ def submap_inputs(out_dir, n_az):
     return filtered[3], np.ascontiguousarray(np.concatenate(parts, 0)), np.linalg.inv(odom[a]) @ odom[3], -1
 
 
-def dump(out_dir, n_az, chain_path, submap=False):
+def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
     os.makedirs(out_dir, exist_ok=True)
     ch = parse_chain(chain_path)
     shutil.copyfile(chain_path, os.path.join(out_dir, "icp.yaml"))
     if submap:
-        rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az)
+        rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az, voxel_grid)
     else:
         ref, rd, T_true, T_init = synth.scan_pair(n_az)
         icp_seed = 1
@@ -159,8 +215,8 @@ def dump(out_dir, n_az, chain_path, submap=False):
     cloud_io.save_csv(os.path.join(out_dir, "reference_filtered.csv"), rf, rn)
     cloud_io.save_csv(os.path.join(out_dir, "reading_filtered.csv"), rdf)
     if not submap:
-        flt = input_filter_chain(os.path.join(ROOT, "tests", "golden", "input_filters.yaml"))
-        kept = O.apply_point_filters(flt, rd, seed=1)
+        flt = input_chain_for_dump(out_dir, voxel_grid)
+        kept = run_input_filters(flt, rd, 1)
         cloud_io.save_csv(os.path.join(out_dir, "input_filtered.csv"), kept if kept is not None else rd[:0])
     cfg = O.config_yaml(accum_double=0, trim_ratio=ch.trim_ratio, max_iterations=ch.max_iterations,
                         min_diff_rot=ch.min_diff_rot, min_diff_trans=ch.min_diff_trans, smooth_length=ch.smooth_length)
@@ -183,7 +239,7 @@ def dump(out_dir, n_az, chain_path, submap=False):
                 "Replay on libpointmatcher: INTEGRATION.md, \"Diffing against a real libpointmatcher\".\n\n%s"
                 % (n_az, rd.shape[0], ref.shape[0], os.path.relpath(chain_path, ROOT), g(ch.reading_sampling_prob),
                    ch.surface_normal_knn, g(ch.surface_normal_ratio), g(ch.trim_ratio), ch.max_iterations,
-                   g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length, CHOICES))
+                   g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length, CHOICES + (VOXEL_CHOICES if voxel_grid else "")))
     return rc, st.iterations
 
 
@@ -193,6 +249,11 @@ if __name__ == "__main__":
     ap.add_argument("--n-az", type=int, default=64)
     ap.add_argument("--chain", default=os.path.join(ROOT, "tests", "golden", "icp_chain.yaml"))
     ap.add_argument("--submap", action="store_true", help="the call shape of LaserTrack::localScanToSubMap (four scans, input filters, three-scan sub-map)")
+    ap.add_argument("--voxel-grid", default=None, metavar="VX,VY,VZ[,USE_CENTROID]",
+                    help="append VoxelGridDataPointsFilter to the input filter chain and write the chain to OUT_DIR/input_filters.yaml")
     a = ap.parse_args()
-    rc, it = dump(a.out_dir, a.n_az, a.chain, a.submap)
+    vg = [float(x) for x in a.voxel_grid.split(",")] if a.voxel_grid else None
+    if vg is not None and len(vg) not in (3, 4):
+        ap.error("--voxel-grid takes VX,VY,VZ or VX,VY,VZ,USE_CENTROID")
+    rc, it = dump(a.out_dir, a.n_az, a.chain, a.submap, vg)
     print("wrote %s: oracle rc %d, %d iterations" % (a.out_dir, rc, it))

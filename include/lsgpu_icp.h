@@ -400,27 +400,55 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
  *                                step *= stepMult, clamped at endStep (the step persists from scan to scan: `state`)
  *   RandomSamplingDataPointsFilter   keeps point i iff draw_i < prob
  *   RemoveNaNDataPointsFilter        drops the points with a NaN among their four feature rows x, y, z, pad (Inf stays)
+ *   VoxelGridDataPointsFilter        one point per occupied voxel of a grid anchored at the cloud's own minimum (below)
  * (MaxPointCountDataPointsFilter is NOT offered: which points it keeps depends on the libpointmatcher version --
  *  std::random_shuffle in the 1.2 line, sequential selection sampling later -- and on the C++ library's shuffle; it
  *  cannot be restated from the reference, which configures none.  Unknown module names are configuration errors.)
  * |p| = sqrt(fma(z,z,fma(y,y,x*x))) in float.  Draws: the library's glibc-sequence stream (see lsgpu_icp_compute);
  * seed >= 0 reseeds it before the first filter.  LSGPU_NO_CONVERGENCE if a filter is handed an empty cloud
- * (PointMatcher::ConvergenceError "no points to filter" upstream); an empty chain copies the cloud. */
+ * (PointMatcher::ConvergenceError "no points to filter" upstream); an empty chain copies the cloud.
+ *
+ * VoxelGridDataPointsFilter (libpointmatcher's module; NOT pcl::VoxelGrid of lsgpu_filter_voxel_grid, whose grid is anchored at
+ * integer multiples of the leaf and whose output is in voxel-index order).  Restated from knowledge of upstream's
+ * VoxelGridDataPointsFilter::inPlaceFilter, parity unpinned (DESIGN.md §5 choices 30-34).  lsgpu_point_filter: v[0..2] =
+ * vSizeX / vSizeY / vSizeZ (default 1; finite and > 0), flag = useCentroid (default 1), dim = averageExistingDescriptors
+ * (default 1); the last two take 0 or 1 only.  A bad parameter is LSGPU_BAD_CONFIG before anything runs.
+ *   Arithmetic: float throughout, one rounding per operation (`/` is the correctly rounded division: the library is built
+ *     without fast-math and with -ffp-contract=off, csrc/Makefile).
+ *   Bounds, per axis a: minB = min_a / vSize_a, maxB = max_a / vSize_a (min / max over the cloud handed to the module),
+ *     numDiv_a = (uint)((1.0f + maxB) - minB), numVox = numDivX numDivY numDivZ.  A numDiv of 0 (1 + maxB rounds to maxB
+ *     once |maxB| >= 2^24) counts as 1.  numVox > 2^31 - 1: LSGPU_BAD_CONFIG "too many voxels" (InvalidParameter upstream).
+ *   Voxel of a point: i = (uint)floorf(x / vSizeX - minBX), j, k likewise; idx = i + j numDivX + k numDivX numDivY.
+ *     DEVIATION: i, j, k are clamped to numDiv - 1 -- upstream indexes out of range in the rounding corner where
+ *     maxB - minB rounds up to an integer.
+ *   The first point of a voxel is the one with the smallest input index in it.
+ *   useCentroid 1: per coordinate, s starts as the first point's, every further point of the voxel is added in ascending input
+ *     index (s += v), the result is s / (float)count.  useCentroid 0: the voxel's centre vSize_a (minB_a + (float)i_a + 0.5f),
+ *     evaluated in that order.  The 4th component of the output point is the first point's (the facades' tag travels there).
+ *   Output: one point per occupied voxel, in ascending order of the voxels' FIRST POINTS (upstream's sorted pointsToKeep),
+ *     not in voxel-index order.  No draw is consumed.
+ *   A NaN or +-inf coordinate in the cloud handed to the module: LSGPU_BAD_ARG (put RemoveNaNDataPointsFilter in front).
+ *   Descriptors: the library sees none.  The C++ facade picks the first point's normal through the tag
+ *     (averageExistingDescriptors 0); with averageExistingDescriptors 1 on a cloud that carries normals its apply() throws
+ *     ConfigError -- averaging descriptors is not implemented.  Without descriptors both values are accepted.
+ *   lsgpu_filter_voxel_grid_points is the host twin, bit for bit. */
 enum {
   LSGPU_FILTER_MAX_DIST = 1,
   LSGPU_FILTER_MIN_DIST = 2,
   LSGPU_FILTER_BOUNDING_BOX = 3,
   LSGPU_FILTER_FIX_STEP_SAMPLING = 4,
   LSGPU_FILTER_RANDOM_SAMPLING = 5,
-  LSGPU_FILTER_REMOVE_NAN = 6
+  LSGPU_FILTER_REMOVE_NAN = 6,
+  LSGPU_FILTER_VOXEL_GRID = 7
 };
 typedef struct lsgpu_point_filter {
   int    type;     /* LSGPU_FILTER_*                                                                          */
-  int    dim;      /* Max/MinDist: -1 radial, 0..2 one axis                                                   */
-  int    flag;     /* BoundingBox: removeInside                                                               */
+  int    dim;      /* Max/MinDist: -1 radial, 0..2 one axis   VoxelGrid: averageExistingDescriptors           */
+  int    flag;     /* BoundingBox: removeInside               VoxelGrid: useCentroid                          */
   int    pad_;
   float  v[6];     /* MaxDist {maxDist}  MinDist {minDist}  BoundingBox {xMin,xMax,yMin,yMax,zMin,zMax}        */
                    /* FixStepSampling {startStep,endStep,stepMult}  RandomSampling {prob}                      */
+                   /* VoxelGrid {vSizeX,vSizeY,vSizeZ}                                                         */
   double state;    /* FixStepSampling: current step (0: start at startStep); updated by every apply            */
 } lsgpu_point_filter;
 int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
@@ -453,6 +481,12 @@ int64_t lsgpu_filter_sampling_surface_normal(const float* xyz1, int64_t n, int k
  * lsgpu_icp_filter_reference_normals, bit for bit.  Returns LSGPU_OK or LSGPU_BAD_ARG. */
 int lsgpu_filter_surface_normal(const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
                                 float* out_d2);
+/* VoxelGridDataPointsFilter of the input filter chain on the host (no GPU, no handle): upstream's sequential loop with the
+ * contract and the float arithmetic above, bit for bit the output of lsgpu_apply_point_filters with this one module.
+ * out_xyz1 needs room for n points.  Returns the number of output points, or -LSGPU_BAD_CONFIG (a bad vsize / use_centroid,
+ * too many voxels), -LSGPU_BAD_ARG (a NULL pointer, a NaN or infinite coordinate), -LSGPU_NO_CONVERGENCE (n <= 0). */
+int64_t lsgpu_filter_voxel_grid_points(const float* xyz1, int64_t n, const float vsize[3], int use_centroid,
+                                       float* out_xyz1);
 /* RigidTransformation::checkParameters / correctParameters (common.hpp:136-149). */
 int  lsgpu_check_rigid(const float T[16]);
 void lsgpu_correct_rigid(const float T[16], float out[16]);

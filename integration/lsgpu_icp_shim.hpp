@@ -10,7 +10,8 @@
 // The header is a template over the PointMatcher type so that the SAME code is compiled and tested in this
 // repository against the dependency-free mirror types (LsgpuMirrorPM below, tests/cpp/shim_check.cpp) and compiles
 // against the real `PointMatcher<float>` (Eigen matrices) through LsgpuCloudTraits: the only operations it needs from
-// a cloud are "pointer to the (dim+1) x N column-major features", "number of points" and "keep these columns".
+// a cloud are "pointer to the (dim+1) x N column-major features", "number of points", "has descriptors" and "keep these
+// columns".
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -28,6 +29,7 @@ struct LsgpuCloudTraits {
   using DataPoints = typename PM::DataPoints;
   static const float* features(const DataPoints& d) { return d.features.data(); }      // 4 x N, column major
   static int64_t size(const DataPoints& d) { return (int64_t)d.features.cols(); }
+  static bool hasDescriptors(const DataPoints& d) { return d.descriptors.cols() > 0; }
   // keep the listed columns (ascending) of features and of every descriptor, drop the others
   static void keepColumns(DataPoints& d, const std::vector<int64_t>& cols) {
     for (size_t j = 0; j < cols.size(); ++j) {
@@ -53,6 +55,7 @@ struct LsgpuCloudTraits<LsgpuMirrorPM> {
   using DataPoints = laser_slam_amd::DataPoints;
   static const float* features(const DataPoints& d) { return d.features.data(); }
   static int64_t size(const DataPoints& d) { return d.getNbPoints(); }
+  static bool hasDescriptors(const DataPoints& d) { return !d.normals.empty(); }
   static void keepColumns(DataPoints& d, const std::vector<int64_t>& cols) {
     const bool nrm = !d.normals.empty();
     for (size_t j = 0; j < cols.size(); ++j) {
@@ -182,6 +185,14 @@ class LsgpuDataPointsFilters {
     if (filters_.empty()) return;
     const int64_t n = Traits::size(cloud);
     if (n == 0) throw typename PM::ConvergenceError("no points to filter");   // as DataPointsFilters::apply does upstream
+    // VoxelGridDataPointsFilter writes new points (below); of the descriptors it can only hand on the first point's
+    bool writes_points = false;
+    for (const auto& f : filters_) {
+      writes_points = writes_points || f.type == LSGPU_FILTER_VOXEL_GRID;
+      if (f.type == LSGPU_FILTER_VOXEL_GRID && f.dim != 0 && Traits::hasDescriptors(cloud))
+        throw std::runtime_error("LsgpuDataPointsFilters: VoxelGridDataPointsFilter: averageExistingDescriptors 1 on a cloud with "
+                                 "descriptors is not implemented (set averageExistingDescriptors: 0 to keep the first point's)");
+    }
     if (!h_) {
       lsgpu_icp_config c;
       lsgpu_icp_config_default(&c);
@@ -197,6 +208,10 @@ class LsgpuDataPointsFilters {
     std::vector<int64_t> cols((size_t)m);
     for (int64_t j = 0; j < m; ++j) { uint32_t tag; std::memcpy(&tag, &out[4 * (size_t)j + 3], 4); cols[(size_t)j] = (int64_t)tag; }
     Traits::keepColumns(cloud, cols);
+    if (writes_points) {   // the surviving column is the voxel's first point (pad row and descriptors); x, y, z are the voxel's point
+      float* feat = const_cast<float*>(Traits::features(cloud));
+      for (int64_t j = 0; j < m; ++j) std::memcpy(feat + 4 * (size_t)j, &out[4 * (size_t)j], 3 * sizeof(float));
+    }
   }
 
  private:

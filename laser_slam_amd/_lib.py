@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "lsgpu_icp_align_normals", "lsgpu_icp_get_reference_normals", "lsgpu_orient_normals", "lsgpu_normal_angle_weights",
     "lsgpu_icp_get_normal_angle_trace",
     "lsgpu_chain_load", "lsgpu_robust_config_why", "lsgpu_normals_config_why",
+    "lsgpu_filter_voxel_grid_points",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -189,6 +190,7 @@ class PointFilter(C.Structure):
 
 
 FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_FIX_STEP_SAMPLING, FILTER_RANDOM_SAMPLING, FILTER_REMOVE_NAN = 1, 2, 3, 4, 5, 6
+FILTER_VOXEL_GRID = 7   # VoxelGridDataPointsFilter: v[0..2] = vSizeX/Y/Z, flag = useCentroid, dim = averageExistingDescriptors
 
 
 class LsgpuError(RuntimeError):
@@ -276,6 +278,8 @@ def lib() -> C.CDLL:
     L.lsgpu_filter_random_sampling.restype = i64
     L.lsgpu_filter_sampling_surface_normal.argtypes = [fp, i64, C.c_int, C.c_float, i64, fp, fp]
     L.lsgpu_filter_sampling_surface_normal.restype = i64
+    L.lsgpu_filter_voxel_grid_points.argtypes = [fp, i64, C.POINTER(C.c_float), C.c_int, fp]
+    L.lsgpu_filter_voxel_grid_points.restype = i64
     L.lsgpu_check_rigid.argtypes = [C.POINTER(C.c_float)]
     L.lsgpu_rotation_distance.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.lsgpu_rotation_distance.restype = C.c_float

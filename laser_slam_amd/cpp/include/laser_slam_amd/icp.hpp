@@ -203,6 +203,17 @@ class DataPointsFilters {
       } else if (m.name == "RemoveNaNDataPointsFilter") {
         only({});
         f.type = LSGPU_FILTER_REMOVE_NAN;
+      } else if (m.name == "VoxelGridDataPointsFilter") {
+        // libpointmatcher's voxel grid (include/lsgpu_icp.h, "the input filter chain"): flag = useCentroid, dim =
+        // averageExistingDescriptors; the values are judged here as lsgpu_apply_point_filters judges them
+        only({"vSizeX", "vSizeY", "vSizeZ", "useCentroid", "averageExistingDescriptors"});
+        f.type = LSGPU_FILTER_VOXEL_GRID;
+        f.v[0] = (float)num("vSizeX", 1.0); f.v[1] = (float)num("vSizeY", 1.0); f.v[2] = (float)num("vSizeZ", 1.0);
+        const double uc = num("useCentroid", 1), avg = num("averageExistingDescriptors", 1);
+        for (int a = 0; a < 3; ++a)
+          if (!(f.v[a] > 0.f) || !std::isfinite(f.v[a])) throw ConfigError(m.name + ": vSizeX / vSizeY / vSizeZ must be finite and > 0");
+        if ((uc != 0 && uc != 1) || (avg != 0 && avg != 1)) throw ConfigError(m.name + ": useCentroid and averageExistingDescriptors take 0 or 1");
+        f.flag = (int)uc; f.dim = (int)avg;
       } else {
         throw ConfigError("input filters: module " + m.name + " is not implemented on the HIP path");
       }
@@ -506,6 +517,13 @@ class ICP {
 
 inline void DataPointsFilters::apply(DataPoints& cloud) {
   if (filters_.empty()) return;
+  // VoxelGridDataPointsFilter writes new points: the tag it hands on is the voxel's first point's, so the normal picked
+  // further down is that point's (averageExistingDescriptors 0).  Averaging the descriptors of a voxel is not implemented.
+  if (!cloud.normals.empty())
+    for (const auto& f : filters_)
+      if (f.type == LSGPU_FILTER_VOXEL_GRID && f.dim != 0)
+        throw ConfigError("VoxelGridDataPointsFilter: averageExistingDescriptors 1 on a cloud with descriptors is not implemented "
+                          "(set averageExistingDescriptors: 0 to keep the first point's)");
   if (!h_) {
     lsgpu_icp_config c;
     lsgpu_icp_config_default(&c);

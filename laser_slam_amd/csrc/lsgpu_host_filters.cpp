@@ -3,6 +3,7 @@
 //   RandomSamplingDataPointsFilter           laser_slam/configurations/icp_default.yaml:1-3
 //   SamplingSurfaceNormalDataPointsFilter    laser_slam/configurations/icp_default.yaml:5-7
 //   SurfaceNormalDataPointsFilter            (a user's chain; the contract is in include/lsgpu_icp.h)
+//   VoxelGridDataPointsFilter                (the input filter chain; the contract is in include/lsgpu_icp.h)
 //   RigidTransformation check / correct      laser_slam/include/laser_slam/common.hpp:136-149
 // GPU versions of the two filters are SURVEY.md §8f row N1/N3 ("next").
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -22,6 +24,7 @@
 #include "lsgpu_robust.h"
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
+#include "lsgpu_voxel_filter.h"
 
 namespace {
 
@@ -136,6 +139,58 @@ int64_t lsgpu_filter_sampling_surface_normal(const float* xyz1, int64_t n, int k
   b.build(0, n, mn, mx);
   b.emit(n);
   return b.n_out;
+}
+
+// VoxelGridDataPointsFilter: upstream's sequential loop -- every point in input order goes to its voxel, whose sums start
+// as its first point and grow by one float addition per further point.  Upstream keeps a vector of numVox voxels; a map
+// from the voxel index to the voxel's slot gives the same result without the memory, and the slots, made in input
+// order, are already in the order of the first points.
+int64_t lsgpu_filter_voxel_grid_points(const float* xyz1, int64_t n, const float vsize[3], int use_centroid,
+                                       float* out_xyz1) {
+  if (!vsize) return -LSGPU_BAD_ARG;
+  if (lsgpu::voxelf::why_bad_params(vsize, use_centroid, 0)) return -LSGPU_BAD_CONFIG;
+  if (n <= 0) return -LSGPU_NO_CONVERGENCE;
+  if (!xyz1 || !out_xyz1 || n > 0x7FFFFFF0ll) return -LSGPU_BAD_ARG;
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) lo[a] = hi[a] = xyz1[a];
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const float c = xyz1[4 * i + a];
+      if (!std::isfinite(c)) return -LSGPU_BAD_ARG;
+      lo[a] = std::min(lo[a], c); hi[a] = std::max(hi[a], c);
+    }
+  lsgpu::voxelf::Geom g;
+  if (lsgpu::voxelf::make_geom(lo, hi, vsize, &g) != LSGPU_OK) return -LSGPU_BAD_CONFIG;
+  struct Voxel { uint32_t key, count; float s[3], w; };
+  std::vector<Voxel> voxels;
+  std::unordered_map<uint32_t, uint32_t> slot_of;
+  for (int64_t i = 0; i < n; ++i) {
+    const float* p = xyz1 + 4 * i;
+    const uint32_t key = lsgpu::voxelf::voxel_index(g, p[0], p[1], p[2]);
+    const auto it = slot_of.find(key);
+    if (it == slot_of.end()) {
+      slot_of.emplace(key, (uint32_t)voxels.size());
+      voxels.push_back(Voxel{key, 1u, {p[0], p[1], p[2]}, p[3]});
+    } else {
+      Voxel& v = voxels[it->second];
+      for (int a = 0; a < 3; ++a) v.s[a] += p[a];
+      ++v.count;
+    }
+  }
+  for (size_t o = 0; o < voxels.size(); ++o) {
+    const Voxel& v = voxels[o];
+    float* q = out_xyz1 + 4 * o;
+    if (use_centroid) {
+      const float c = (float)v.count;
+      for (int a = 0; a < 3; ++a) q[a] = v.s[a] / c;
+    } else {
+      const uint32_t nxy = g.ndiv[0] * g.ndiv[1];
+      const uint32_t ck = v.key / nxy, rem = v.key - ck * nxy, cj = rem / g.ndiv[0], ci = rem - cj * g.ndiv[0];
+      q[0] = lsgpu::voxelf::centre(g, 0, ci); q[1] = lsgpu::voxelf::centre(g, 1, cj); q[2] = lsgpu::voxelf::centre(g, 2, ck);
+    }
+    std::memcpy(q + 3, &v.w, 4);
+  }
+  return (int64_t)voxels.size();
 }
 
 // SurfaceNormalDataPointsFilter.  A checker: the exact search sweeps outwards from the point along the x-sorted cloud

@@ -32,6 +32,7 @@
 #include "lsgpu_solve.hip.h"
 #include "lsgpu_host_math.h"
 #include "lsgpu_ssn.hip.h"
+#include "lsgpu_voxel_filter.hip.h"
 #include "lsgpu_ssn_tree.hip.h"
 #include "lsgpu_ssn_select.hip.h"
 #include "lsgpu_sort.hip.h"
@@ -278,6 +279,7 @@ struct lsgpu_icp {
   int gs_plan_levels = -1;
   std::vector<uint32_t> gs_lvl_first, gs_lvl_blocks;
   DevBuf<float4> flt_in, flt_in2, flt_ref, flt_rd;
+  DevBuf<float4> vgf_out;   // VoxelGridDataPointsFilter (lsgpu_voxel_filter.hip.h): the voxels' points at their first points' positions
   DevBuf<float> flt_nrm;
   float* draws_pinned = nullptr;  // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
@@ -539,7 +541,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->ref_in.release(); h->nrm_in.release(); h->scr_main.release(); h->scr_side.release();
   h->pts.release();
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
-  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
+  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
@@ -2445,6 +2447,57 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
   return LSGPU_OK;
 }
 
+// VoxelGridDataPointsFilter (include/lsgpu_icp.h, "the input filter chain"): src (m points, device) -> dst (device, room for
+// m; none of src and h->vgf_out), one point per occupied voxel in the order of the voxels' first points.  No draw.
+static int voxel_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m, const lsgpu_point_filter& f, float4* dst,
+                                    int64_t* m_out) {
+  // the cloud's minimum and maximum, and with them the verdict on its finiteness: a NaN's ordered key lies beyond the
+  // infinities', so a cloud with any NaN or infinity has a bound that is not finite
+  HIPC(h->ssn_bb.reserve(8));
+  HIPC(hipMemsetAsync(h->ssn_bb.p, 0xFF, 12, h->stream));
+  HIPC(hipMemsetAsync(h->ssn_bb.p + 3, 0, 12, h->stream));
+  hipLaunchKernelGGL(k_ssn_bounds, dim3(std::min(nblk(m), 256)), dim3(256), 0, h->stream, src, (int)m, h->ssn_bb.p);
+  uint32_t* hb = reinterpret_cast<uint32_t*>(h->h_pinned + 104);
+  HIPC(hipMemcpyAsync(hb, h->ssn_bb.p, 24, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  auto from_key = [](uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; float v; std::memcpy(&v, &u, 4); return v; };
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = from_key(hb[a]); hi[a] = from_key(hb[3 + a]);
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {
+      h->err = "apply_point_filters: VoxelGridDataPointsFilter was handed a NaN or infinite coordinate; put RemoveNaNDataPointsFilter "
+               "(and a MaxDist / BoundingBox filter against infinities) in front of it";
+      return LSGPU_BAD_ARG;
+    }
+  }
+  voxelf::Geom g;
+  if (voxelf::make_geom(lo, hi, f.v, &g) != LSGPU_OK) {
+    h->err = "apply_point_filters: VoxelGridDataPointsFilter: too many voxels (more than 2^31 - 1) for this cloud, the voxel sizes are too small";
+    return LSGPU_BAD_CONFIG;
+  }
+  const uint32_t nvox = g.ndiv[0] * g.ndiv[1] * g.ndiv[2];
+  int nbits = 1;
+  while (nbits < 31 && (nvox - 1u) >> nbits) ++nbits;
+  HIPC(h->sc->keys.reserve(m));
+  HIPC(h->sc->vals.reserve(m));
+  HIPC(h->vgf_out.reserve(m));
+  hipLaunchKernelGGL(k_vgf_keys, dim3(nblk(m)), dim3(256), 0, h->stream, src, (int)m, g, h->sc->keys.p, h->sc->vals.p);
+  int rc = sort_pairs(h, m, nbits);  // stable: the points of a voxel keep input order
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_vgf_reduce, dim3(nblk(m)), dim3(256), 0, h->stream, src, h->sc->keys_alt.p, h->sc->vals_alt.p, (int)m, g,
+                     f.flag ? 1 : 0, h->vgf_out.p, h->ssn_keep.p);
+  rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_compact_points, dim3(nblk(m)), dim3(256), 0, h->stream, h->vgf_out.p, (int)m, h->ssn_keep.p,
+                     h->ssn_out_pos.p, dst);
+  HIPC(hipGetLastError());
+  uint32_t unused = 0, kept = 0;
+  rc = scan_totals(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m, &unused, &kept);
+  if (rc) return rc;
+  *m_out = kept;
+  return LSGPU_OK;
+}
+
 int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
                               int64_t n, int64_t seed, float* out_xyz1, int64_t* n_out) {
   if (!h || !n_out || n_filters < 0 || (n_filters > 0 && !filters) || n < 0 || (n > 0 && (!xyz1 || !out_xyz1))) return LSGPU_BAD_ARG;
@@ -2457,7 +2510,11 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
                     : f.type == LSGPU_FILTER_BOUNDING_BOX ? true
                     : f.type == LSGPU_FILTER_FIX_STEP_SAMPLING ? (f.v[0] >= 1.f && f.v[1] >= 1.f && f.v[2] > 0.f)
                     : f.type == LSGPU_FILTER_RANDOM_SAMPLING ? (f.v[0] >= 0.f && f.v[0] <= 1.f)
-                    : f.type == LSGPU_FILTER_REMOVE_NAN ? true : false;
+                    : f.type == LSGPU_FILTER_REMOVE_NAN ? true
+                    : f.type == LSGPU_FILTER_VOXEL_GRID ? true : false;
+    if (ok && f.type == LSGPU_FILTER_VOXEL_GRID) {
+      if (const char* why = voxelf::why_bad_params(f.v, f.flag, f.dim)) { h->err = std::string("apply_point_filters: ") + why; return LSGPU_BAD_CONFIG; }
+    }
     if (!ok) { h->err = "apply_point_filters: unknown filter type or parameter out of range"; return LSGPU_BAD_CONFIG; }
   }
   if (seed >= 0) DrawStream::global().take(seed, 0, nullptr);
@@ -2482,6 +2539,13 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
   for (int k = 0; k < n_filters; ++k) {
     lsgpu_point_filter& f = filters[k];
     if (m == 0) { h->err = "apply_point_filters: no points to filter"; return LSGPU_NO_CONVERGENCE; }
+    if (f.type == LSGPU_FILTER_VOXEL_GRID) {
+      rc = voxel_grid_filter_device(h, cur, m, f, ping, &m);
+      if (rc) return rc;
+      cur = ping;
+      std::swap(ping, pong);
+      continue;
+    }
     PointFilterDev d;
     std::memset(&d, 0, sizeof(d));
     d.type = f.type; d.dim = f.dim; d.flag = f.flag;

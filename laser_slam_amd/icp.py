@@ -656,6 +656,21 @@ def surface_normal(xyz1, knn: int = 5, with_neighbours: bool = False):
     return (nr[:n], ids[:n], d2[:n]) if with_neighbours else nr[:n]
 
 
+def voxel_grid_points(xyz1, vsize=(1.0, 1.0, 1.0), use_centroid: bool = True) -> np.ndarray:
+    """VoxelGridDataPointsFilter of the input filter chain on the host (lsgpu_filter_voxel_grid_points; bit for bit what
+    IcpHandle.apply_point_filters gives with this one module) -> one point per occupied voxel, in first-point order."""
+    a = np.ascontiguousarray(xyz1, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"expected (N,4) array, got {a.shape}")
+    n = a.shape[0]
+    v = (C.c_float * 3)(*[float(x) for x in vsize])
+    o = np.empty((max(n, 1), 4), np.float32)
+    m = _lib.lib().lsgpu_filter_voxel_grid_points(a.ctypes.data if n else None, n, v, int(use_centroid), o.ctypes.data)
+    if m < 0:
+        _raise(int(-m), "lsgpu_filter_voxel_grid_points")
+    return o[:m].copy()
+
+
 def point_to_point_solve(sums) -> np.ndarray:
     """lsgpu_point_to_point_solve: the point-to-point step dT (4x4 float32) from the 29 sums of
     IcpHandle.point_to_point -- host only, the same function the device loop runs.  Raises ConvergenceError for
