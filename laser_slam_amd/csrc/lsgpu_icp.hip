@@ -15,6 +15,7 @@
 #include <functional>
 #include <system_error>
 #include <thread>
+#include <utility>
 
 #include <dlfcn.h>
 
@@ -149,12 +150,23 @@ inline int nblk(int64_t n) { return (int)((n + 255) / 256); }
 
 }  // namespace
 
-struct lsgpu_icp;
-static int wait_stream(lsgpu_icp* h);
-
-namespace {
-
-}  // namespace
+// The handle's pinned (host-coherent, device-mapped) staging block: the few words and small records that cross between
+// host and device outside the clouds.  One member per use and no member shared, so a record that grows moves its
+// neighbours instead of running into them.  k_to_host stores 4-byte words into it from the device, hipMemcpyAsync reads
+// and writes the rest.  Every use starts a 64-byte line of its own (as the loop state and the bounds did at their old
+// offsets): a copy never shares a line with words another use writes, and the copies keep their aligned path.
+struct Staging {
+  alignas(64) uint32_t cells[kMaxLevels];   // set_reference: occupied cells per level ...
+  uint32_t nchunks;                         // ... and the number of chunks
+  alignas(64) GeomDev geom;                 // ... and the grid geometry derived on the device
+  alignas(64) double ne[32];                // stand-alone normal equations: the 29 sums (ne_out's layout: 29 + limit slot)
+  alignas(64) float limit;                  // lsgpu_trim_limit
+  alignas(64) SelState sel0;                // run_select: sel[0] = {0, rank} on its way to the device
+  alignas(64) long long handshake[2];       // split-scan entry handshake of an align: {shard size, cannot-start flag}
+  alignas(64) IcpState state;               // the loop state of the running align, as of the host's last look
+  alignas(64) uint32_t totals[2][4];        // scan_totals, [side_totals_slot]: {last input, last scanned} of two scans
+  alignas(64) uint32_t bounds[6];           // cloud_bounds: ordered keys of the minimum and the maximum
+};
 
 struct lsgpu_icp {
   lsgpu_icp_config cfg;
@@ -190,7 +202,7 @@ struct lsgpu_icp {
   hipEvent_t draws_done = nullptr, draws_first_done = nullptr;
   hipStream_t side_stream = nullptr;   // lsgpu_icp_compute: reading filter + query order, beside the grid build
   hipEvent_t side_done = nullptr;
-  int side_totals_slot = 0;            // scan_totals staging: the side path uses its own words of h_pinned
+  int side_totals_slot = 0;            // scan_totals staging: the side path uses its own row of pin->totals
   std::function<int()> hook_before_ref_sync, hook_after_grid;   // set by lsgpu_icp_compute: before set_reference waits for its cell counts / once the whole grid build is enqueued
   const float* prepared_rd = nullptr;  // queries already ordered by the side path (consumed by the next align)
   int64_t prepared_nq = 0;
@@ -321,7 +333,7 @@ struct lsgpu_icp {
   DevBuf<uint32_t> ne_tickets;  // 1 + kNeBlocksMax / kNeGroup
   DevBuf<double> ne_out;      // 32 (29 + limit slot)
   DevBuf<float> limit_dev;
-  double* h_pinned = nullptr; // 64 doubles of pinned host staging
+  Staging* pin = nullptr;     // pinned host staging, one member per use
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_state = nullptr;   // lsgpu_icp_align: completion of a loop-state copy (the stream goes on behind it)
   // lsgpu_icp_align may return with ONE more iteration queued on `stream` behind its last look at the loop state (it
@@ -389,6 +401,19 @@ static constexpr int kStatBlocks = 512;
 static constexpr int kHistBlocks = 256;
 static constexpr int kFallbackBlocks = 8192;  // x 4 waves: one query per wave for up to 32 k stragglers, round robin beyond
 
+// up to `cap` of the `have` records the last alignment left in `dev` -> out; the number copied
+template <class T>
+static int fetch_trace(lsgpu_icp* h, const T* dev, size_t have, T* out, int cap) {
+  if (!out || cap <= 0 || !have) return 0;
+  const int n = std::min<int>(cap, (int)have);
+  if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+      hipMemcpy(out, dev, (size_t)n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return n;
+}
+
 extern "C" {
 
 void lsgpu_icp_config_yaml(lsgpu_icp_config* c) {  // icp_default.yaml:14-27
@@ -444,14 +469,7 @@ int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg) {
 }
 
 int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap) {
-  if (!h || !out || cap <= 0 || !h->rb_trace_n) return 0;
-  const int n = std::min<int>(cap, (int)h->rb_trace_n);
-  if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-      hipMemcpy(out, h->rb_trace_dev.p, (size_t)n * sizeof(lsgpu_robust_trace), hipMemcpyDeviceToHost) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return n;
+  return h ? fetch_trace(h, h->rb_trace_dev.p, h->rb_trace_n, out, cap) : 0;
 }
 
 int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
@@ -468,14 +486,7 @@ int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
 }
 
 int lsgpu_icp_get_normal_angle_trace(lsgpu_icp* h, lsgpu_normal_angle_trace* out, int cap) {
-  if (!h || !out || cap <= 0 || !h->na_trace_n) return 0;
-  const int n = std::min<int>(cap, (int)h->na_trace_n);
-  if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
-      hipMemcpy(out, h->na_trace_dev.p, (size_t)n * sizeof(lsgpu_normal_angle_trace), hipMemcpyDeviceToHost) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return n;
+  return h ? fetch_trace(h, h->na_trace_dev.p, h->na_trace_n, out, cap) : 0;
 }
 
 int lsgpu_abi_version(void) { return LSGPU_ABI_VERSION; }
@@ -519,7 +530,7 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
   std::memset(&h->grid, 0, sizeof(h->grid));
   if (hipSetDevice(device) != hipSuccess ||
       hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_pinned, 128 * sizeof(double), hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void**)&h->pin, sizeof(Staging), hipHostMallocDefault) != hipSuccess ||
       hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
     (void)hipGetLastError();
     delete h;
@@ -556,7 +567,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   if (h->cone_done) (void)hipEventDestroy(h->cone_done);
   if (h->cone_occ_ready) (void)hipEventDestroy(h->cone_occ_ready);
   for (auto& e : h->ev_pay) if (e) (void)hipEventDestroy(e);
-  if (h->h_pinned) (void)hipHostFree(h->h_pinned);
+  if (h->pin) (void)hipHostFree(h->pin);
   if (h->h_price) (void)hipHostFree(h->h_price);
   if (h->h_cone_occ) (void)hipHostFree(h->h_cone_occ);
   if (h->h_gs_err) (void)hipHostFree(h->h_gs_err);
@@ -620,14 +631,18 @@ static int sort_pairs(lsgpu_icp* h, int64_t n, int nbits) {
   return LSGPU_OK;  // sorted: keys_alt / vals_alt
 }
 
-// Stage a cloud on the device: returns a device pointer valid on h->stream.
-static int stage_points(lsgpu_icp* h, const float* src, int64_t n, DevBuf<float4>& buf,
-                        const float4** out) {
-  if (is_device_ptr(src)) { *out = reinterpret_cast<const float4*>(src); return LSGPU_OK; }
-  HIPC(buf.reserve(n));
-  HIPC(hipMemcpyAsync(buf.p, src, (size_t)n * 16, hipMemcpyHostToDevice, h->cur));
+// Stage an array of the caller's on the device (`count` elements of T): a device pointer is taken as it is, host memory is
+// copied into `buf` on the current stream.  Returns a device pointer valid on that stream.
+template <class T, class U>
+static int stage_in(lsgpu_icp* h, const U* src, size_t count, DevBuf<T>& buf, const T** out) {
+  if (is_device_ptr(src)) { *out = reinterpret_cast<const T*>(src); return LSGPU_OK; }
+  HIPC(buf.reserve(count));
+  HIPC(hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->cur));
   *out = buf.p;
   return LSGPU_OK;
+}
+static int stage_points(lsgpu_icp* h, const float* src, int64_t n, DevBuf<float4>& buf, const float4** out) {
+  return stage_in(h, src, (size_t)n, buf, out);
 }
 
 static int ensure_loop_buffers(lsgpu_icp* h, int64_t nq) {
@@ -707,6 +722,20 @@ static float price_share(const lsgpu_icp* h) {   // heavy lanes / searching lane
   return searching ? (float)((double)heavy / (double)searching) : 0.f;
 }
 
+// the next event record of a profiled align (a pool, reused across aligns), its first event on the stream
+static int knn_event_begin(lsgpu_icp* h, lsgpu_icp::KnnEv** ev) {
+  if (h->knn_events_used == h->knn_events.size()) {
+    lsgpu_icp::KnnEv n{};
+    HIPC(hipEventCreate(&n.a)); HIPC(hipEventCreate(&n.b)); HIPC(hipEventCreate(&n.c));
+    HIPC(hipEventCreate(&n.d)); HIPC(hipEventCreate(&n.e));
+    h->knn_events.push_back(n);
+  }
+  *ev = &h->knn_events[h->knn_events_used++];
+  (*ev)->second = false;
+  HIPC(hipEventRecord((*ev)->a, h->stream));
+  return LSGPU_OK;
+}
+
 static KnnArgs knn_args(lsgpu_icp* h, const Mat34& T) {
   KnnArgs a;
   a.rdq = h->rdq.p; a.nq = (int)h->nq; a.T = T; a.g = h->grid; a.pts = h->pts.p;
@@ -727,8 +756,6 @@ static KnnArgs knn_args(lsgpu_icp* h, const Mat34& T) {
   return a;
 }
 
-// findClosests for the queries in h->rdq moved by T: fills h->ids (sorted-reference index), h->d2.
-// seed: the queries have no warm start yet (first iteration of an align, or the kernel-level API).
 // findClosests for the queries in h->rdq: fills h->ids (sorted-reference index), h->d2, h->prev.
 //   T / st   : the transform comes from the argument (kernel-level API) or from the loop state
 //   seed     : the queries have no warm start yet (first iteration, kernel-level API)
@@ -796,17 +823,7 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
   const bool pay_voxel = pay_probe && !seed && it.ordinal == pc.cone_from - 1 && !h->pay_voxel_timed;
   if (pay_voxel) HIPC(hipEventRecord(h->ev_pay[0], h->stream));
   lsgpu_icp::KnnEv* ev = nullptr;
-  if (timed) {
-    if (h->knn_events_used == h->knn_events.size()) {
-      lsgpu_icp::KnnEv n{};
-      HIPC(hipEventCreate(&n.a)); HIPC(hipEventCreate(&n.b)); HIPC(hipEventCreate(&n.c));
-      HIPC(hipEventCreate(&n.d)); HIPC(hipEventCreate(&n.e));
-      h->knn_events.push_back(n);
-    }
-    ev = &h->knn_events[h->knn_events_used++];
-    ev->second = false;
-    HIPC(hipEventRecord(ev->a, h->stream));
-  }
+  if (timed) { const int re = knn_event_begin(h, &ev); if (re) return re; }
   if (pol.wants_occupancy(it, st != nullptr)) {
     // first search through the index for this reference: is it worth it?  The windows of a lane grow with the number of
     // reference points per direction -- measured on local maps of K scans of 1 M points (devtools/cone_density.py), kNN
@@ -884,6 +901,12 @@ static void launch_knn_k(lsgpu_icp* h, const KnnKArgs& a, bool seed) {
   else launch_knn_k_<K, false>(h, a, seed);
 }
 
+template <size_t... I>
+static void launch_knn_k_any(lsgpu_icp* h, const KnnKArgs& a, bool seed, int k, std::index_sequence<I...>) {
+  static void (*const tab[])(lsgpu_icp*, const KnnKArgs&, bool) = {launch_knn_k<(int)I + 1>...};   // k = 1 .. kKnnKMax
+  tab[k - 1](h, a, seed);
+}
+
 static int run_knn_k(lsgpu_icp* h, int k, const Mat34& T, const IcpState* st, bool seed, bool timed) {
   const int64_t nq = h->nq;
   HIPC(h->kmatch.reserve((size_t)k * nq)); HIPC(h->kd2.reserve((size_t)k * nq));
@@ -893,29 +916,9 @@ static int run_knn_k(lsgpu_icp* h, int k, const Mat34& T, const IcpState* st, bo
   a.r_cap = kKnnKRCap; a.max_d2 = matcher_max_d2(h);
   if (!st) HIPC(hipMemsetAsync(a.strag_count, 0, sizeof(uint32_t), h->stream));  // (align: k_align_init, then the normal equations re-arm it)
   lsgpu_icp::KnnEv* ev = nullptr;
-  if (timed) {   // (the same event record as run_knn: main launches a..b, fallback b..c)
-    if (h->knn_events_used == h->knn_events.size()) {
-      lsgpu_icp::KnnEv n{};
-      HIPC(hipEventCreate(&n.a)); HIPC(hipEventCreate(&n.b)); HIPC(hipEventCreate(&n.c));
-      HIPC(hipEventCreate(&n.d)); HIPC(hipEventCreate(&n.e));
-      h->knn_events.push_back(n);
-    }
-    ev = &h->knn_events[h->knn_events_used++];
-    ev->second = false;
-    HIPC(hipEventRecord(ev->a, h->stream));
-  }
-  switch (k) {
-    case 1: launch_knn_k<1>(h, a, seed); break;
-    case 2: launch_knn_k<2>(h, a, seed); break;
-    case 3: launch_knn_k<3>(h, a, seed); break;
-    case 4: launch_knn_k<4>(h, a, seed); break;
-    case 5: launch_knn_k<5>(h, a, seed); break;
-    case 6: launch_knn_k<6>(h, a, seed); break;
-    case 7: launch_knn_k<7>(h, a, seed); break;
-    case 8: launch_knn_k<8>(h, a, seed); break;
-    default: h->err = "knn_k: k out of range"; return LSGPU_BAD_ARG;
-  }
-  static_assert(kKnnKMax == 8, "one instantiation per k");
+  if (timed) { const int re = knn_event_begin(h, &ev); if (re) return re; }   // (the same event record as run_knn: main launches a..b, fallback b..c)
+  if (k < 1 || k > kKnnKMax) { h->err = "knn_k: k out of range"; return LSGPU_BAD_ARG; }
+  launch_knn_k_any(h, a, seed, k, std::make_index_sequence<kKnnKMax>{});
   if (timed) { HIPC(hipEventRecord(ev->b, h->stream)); }
   HIPC(hipGetLastError());
   return LSGPU_OK;
@@ -938,9 +941,8 @@ static int run_select(lsgpu_icp* h, const float* d2, int n, uint32_t k, bool zer
                       bool use_comm, bool predicted, int passes, float rank_ratio, bool with_median) {
   if (zero_hist) HIPC(hipMemsetAsync(h->hist.p, 0, 3 * kHistBins * sizeof(uint32_t), h->stream));
   if (zero_hist && !(rank_ratio > 0.f)) {  // sel[0] = {0, k}: constant during an align, uploaded once
-    SelState s0{0u, k};
-    std::memcpy(h->h_pinned + 56, &s0, sizeof(s0));
-    HIPC(hipMemcpyAsync(h->sel.p, h->h_pinned + 56, sizeof(SelState), hipMemcpyHostToDevice, h->stream));
+    h->pin->sel0 = SelState{0u, k};
+    HIPC(hipMemcpyAsync(h->sel.p, &h->pin->sel0, sizeof(SelState), hipMemcpyHostToDevice, h->stream));
   }
   const int nb = std::min(kHistBlocks, nblk(n));
   const int pr = predicted && st ? 1 : 0;
@@ -1028,9 +1030,8 @@ static int build_cone_index(lsgpu_icp* h) {
   // the number of occupied bins travels to the host behind the build; lsgpu_icp_align looks at it before its first
   // search through the index (the device is busy with the first two iterations by then)
   if (!h->cone_occ_ready) HIPC(hipEventCreateWithFlags(&h->cone_occ_ready, hipEventDisableTiming));
-  // (its own pinned word -- the 128-double staging block also carries the loop state, the scan totals and the grid's
-  // words --, and an earlier build's copy may still be in flight on the side stream when the next one starts: wait for it
-  // before the word is reset)
+  // (its own pinned word, not a member of the staging block: an earlier build's copy may still be in flight on the side
+  // stream when the next one starts -- wait for it before the word is reset)
   if (!h->h_cone_occ) HIPC(hipHostMalloc((void**)&h->h_cone_occ, 64, hipHostMallocDefault));
   else if (hipEventSynchronize(h->cone_occ_ready) != hipSuccess) (void)hipGetLastError();
   uint32_t* ho = h->h_cone_occ;
@@ -1071,14 +1072,7 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   int rc = stage_points(h, ref_xyz1, nr, h->ref_in, &src);
   if (rc) return rc;
   const float* nsrc = nullptr;
-  if (ref_normals) {
-    if (is_device_ptr(ref_normals)) nsrc = ref_normals;
-    else {
-      HIPC(h->nrm_in.reserve(3 * nr));
-      HIPC(hipMemcpyAsync(h->nrm_in.p, ref_normals, (size_t)nr * 12, hipMemcpyHostToDevice, h->stream));
-      nsrc = h->nrm_in.p;
-    }
-  }
+  if (ref_normals && (rc = stage_in(h, ref_normals, (size_t)3 * nr, h->nrm_in, &nsrc))) return rc;
   // ---- mean + bounding box (step 2) and the grid geometry, all on the device: nothing below waits for the host
   // until the cell counts are needed (one round trip per set_reference; there used to be two)
   HIPC(h->stat_partials.reserve(kStatBlocks + 1));
@@ -1107,15 +1101,14 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   HIPC(hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint32_t), h->stream));
   hipLaunchKernelGGL(k_cells_count, dim3(std::min(512, nblk(nr))), dim3(256), 0, h->stream, h->sc->keys_alt.p, nr, h->geom.p,
                      h->counters.p);
-  uint32_t* hc = reinterpret_cast<uint32_t*>(h->h_pinned);
-  GeomDev* hg = reinterpret_cast<GeomDev*>(h->h_pinned + 16);
-  static_assert(sizeof(GeomDev) <= 16 * sizeof(double), "geometry staging");
+  const uint32_t* hc = h->pin->cells;
+  const GeomDev* hg = &h->pin->geom;
   {
     static_assert(sizeof(GeomDev) % 4 == 0, "copied word by word");
     ToHost c{}; int used = 0;
-    to_host_add(&c, &used, h->counters.p, hc, kMaxLevels * sizeof(uint32_t));
-    to_host_add(&c, &used, h->cidx.p + (nr - 1), hc + 20, sizeof(uint32_t));
-    to_host_add(&c, &used, h->geom.p, hg, sizeof(GeomDev));
+    to_host_add(&c, &used, h->counters.p, h->pin->cells, sizeof h->pin->cells);
+    to_host_add(&c, &used, h->cidx.p + (nr - 1), &h->pin->nchunks, sizeof(uint32_t));
+    to_host_add(&c, &used, h->geom.p, &h->pin->geom, sizeof(GeomDev));
     hipLaunchKernelGGL(k_to_host, dim3(1), dim3(64), 0, h->stream, c);
     HIPC(hipGetLastError());
   }
@@ -1132,7 +1125,7 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   std::memset(&g, 0, sizeof(g));
   g.ox = hg->ox; g.oy = hg->oy; g.oz = hg->oz;
   g.h0 = h0; g.hf = hg->hf; g.inv_hf = hg->inv_hf; g.fine = fine; g.bits = bits;
-  const uint32_t nchunks = hc[20];
+  const uint32_t nchunks = h->pin->nchunks;
   size_t total = 0, off[kMaxLevels];
   uint32_t cap[kMaxLevels], ncell[kMaxLevels];
   for (int l = 0; l <= bits; ++l) ncell[l] = hc[l];
@@ -1337,12 +1330,8 @@ int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, floa
   HIPC(hipSetDevice(h->device));
   int rc = ensure_loop_buffers(h, 1);
   if (rc) return rc;
-  const float* src = d2;
-  if (!is_device_ptr(d2)) {
-    HIPC(h->d2_io.reserve(n));
-    HIPC(hipMemcpyAsync(h->d2_io.p, d2, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    src = h->d2_io.p;
-  }
+  const float* src = nullptr;
+  if ((rc = stage_in(h, d2, (size_t)n, h->d2_io, &src))) return rc;
   // ratio > 0: the rank over the FINITE distances, taken on the device (Matches::getDistsQuantile skips invalid matches; the
   // host's rank argument is not read on that route).  A ratio that is not positive asks for rank 0 whatever the count: the
   // host-side rank, as before.
@@ -1351,11 +1340,10 @@ int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, floa
   if (rc) return rc;
   hipLaunchKernelGGL(k_limit_out, dim3(1), dim3(256), 0, h->stream, h->hist.p + 2 * kHistBins,
                      h->sel.p + 2, h->limit_dev.p);
-  float* hl = reinterpret_cast<float*>(h->h_pinned);
-  HIPC(hipMemcpyAsync(hl, h->limit_dev.p, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipMemcpyAsync(&h->pin->limit, h->limit_dev.p, 4, hipMemcpyDeviceToHost, h->stream));
   HIPC(hipStreamSynchronize(h->stream));
-  *limit = *hl;
-  if (*hl == INFINITY) { h->err = "trim_limit: no finite distance (no outlier to filter)"; return LSGPU_NO_CONVERGENCE; }
+  *limit = h->pin->limit;
+  if (*limit == INFINITY) { h->err = "trim_limit: no finite distance (no outlier to filter)"; return LSGPU_NO_CONVERGENCE; }
   return LSGPU_OK;
 }
 
@@ -1374,17 +1362,9 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
   const float4* q = nullptr;
   rc = stage_points(h, query_xyz1, nq, h->q_in, &q);
   if (rc) return rc;
-  const int* idp = ids; const float* dp = d2;
-  if (!is_device_ptr(ids)) {
-    HIPC(h->ids_io.reserve(nq));
-    HIPC(hipMemcpyAsync(h->ids_io.p, ids, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
-    idp = h->ids_io.p;
-  }
-  if (!is_device_ptr(d2)) {
-    HIPC(h->d2_io.reserve(nq));
-    HIPC(hipMemcpyAsync(h->d2_io.p, d2, (size_t)nq * 4, hipMemcpyHostToDevice, h->stream));
-    dp = h->d2_io.p;
-  }
+  const int* idp = nullptr; const float* dp = nullptr;
+  if ((rc = stage_in(h, ids, (size_t)nq, h->ids_io, &idp))) return rc;
+  if ((rc = stage_in(h, d2, (size_t)nq, h->d2_io, &dp))) return rc;
   float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const Mat34 Tm = to_mat34(T ? T : I);
   const int nb = std::min(kNeBlocks, nblk(nq));
@@ -1413,9 +1393,9 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
   }
   hipLaunchKernelGGL(k_ne_final, dim3(1), dim3(1024), 0, h->stream, h->ne_partials.p, nb, h->ne_out.p);
   HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(h->h_pinned, h->ne_out.p, kNe * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipMemcpyAsync(h->pin->ne, h->ne_out.p, kNe * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPC(hipStreamSynchronize(h->stream));
-  std::memcpy(out, h->h_pinned, kNe * sizeof(double));
+  std::memcpy(out, h->pin->ne, kNe * sizeof(double));
   return LSGPU_OK;
 }
 
@@ -1456,12 +1436,9 @@ int lsgpu_rotate_descriptors(lsgpu_icp* h, const float T[16], const float* desc3
   if (!desc3 || !out || n < 0 || n > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
   if (!lsgpu_check_rigid(T)) { h->err = "rotate_descriptors: the matrix is not rigid"; return LSGPU_BAD_ARG; }   // TransformationError upstream
   HIPC(hipSetDevice(h->device));
-  const float* src = desc3;
-  if (!is_device_ptr(desc3)) {
-    HIPC(h->flt_nrm.reserve(3 * n));
-    HIPC(hipMemcpyAsync(h->flt_nrm.p, desc3, (size_t)n * 12, hipMemcpyHostToDevice, h->stream));
-    src = h->flt_nrm.p;
-  }
+  const float* src = nullptr;
+  const int rc = stage_in(h, desc3, (size_t)3 * n, h->flt_nrm, &src);
+  if (rc) return rc;
   const bool dev_out = is_device_ptr(out);
   float* dst = out;
   if (!dev_out) { HIPC(h->ssn_box_normal.reserve(3 * n)); dst = h->ssn_box_normal.p; }
@@ -1616,7 +1593,7 @@ struct DrawAhead {
 static int scan_totals_enqueue(lsgpu_icp* h, const uint32_t* in_a, const uint32_t* sc_a, size_t na,
                                const uint32_t* in_b, const uint32_t* sc_b, size_t nb,
                                const void* extra_src = nullptr, void* extra_dst = nullptr, size_t extra_bytes = 0) {
-  uint32_t* hp = reinterpret_cast<uint32_t*>(h->h_pinned + 100 + 4 * h->side_totals_slot);
+  uint32_t* hp = h->pin->totals[h->side_totals_slot];
   hp[0] = hp[1] = hp[2] = hp[3] = 0;
   ToHost c{}; int used = 0;
   if (in_a) {
@@ -1632,7 +1609,7 @@ static int scan_totals_enqueue(lsgpu_icp* h, const uint32_t* in_a, const uint32_
 }
 // ... and the host's wait for them (synchronises the current stream)
 static int scan_totals_wait(lsgpu_icp* h, uint32_t* tot_a, uint32_t* tot_b, bool b_flags = false) {
-  const uint32_t* hp = reinterpret_cast<const uint32_t*>(h->h_pinned + 100 + 4 * h->side_totals_slot);
+  const uint32_t* hp = h->pin->totals[h->side_totals_slot];
   HIPC(hipStreamSynchronize(h->cur));
   *tot_a = hp[0] + hp[1];
   *tot_b = (b_flags ? (hp[2] ? 1u : 0u) : hp[2]) + hp[3];   // (b_flags: the scanned words are flags, any non-zero word counts 1)
@@ -1644,6 +1621,69 @@ static int scan_totals(lsgpu_icp* h, const uint32_t* in_a, const uint32_t* sc_a,
   const int rc = scan_totals_enqueue(h, in_a, sc_a, na, in_b, sc_b, nb, extra_src, extra_dst, extra_bytes);
   return rc ? rc : scan_totals_wait(h, tot_a, tot_b, b_flags);
 }
+
+// The filters' compaction on the current stream: the keep flags in h->ssn_keep -> their exclusive scan in h->ssn_out_pos ->
+// the kept points of src at the front of dst, order preserved, and the number kept on its way to the totals words ...
+static int compact_kept_enqueue(lsgpu_icp* h, const float4* src, int64_t n, float4* dst) {
+  const int rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->cur, src, (int)n, h->ssn_keep.p, h->ssn_out_pos.p, dst);
+  HIPC(hipGetLastError());
+  return scan_totals_enqueue(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
+}
+// ... and the host's wait for that number (lsgpu_icp_compute puts the rest of the grid build on the other stream in between)
+static int compact_kept_wait(lsgpu_icp* h, int64_t* kept) {
+  uint32_t unused = 0, k = 0;
+  const int rc = scan_totals_wait(h, &unused, &k);
+  if (rc) return rc;
+  *kept = k;
+  return LSGPU_OK;
+}
+static int compact_kept(lsgpu_icp* h, const float4* src, int64_t n, float4* dst, int64_t* kept) {
+  const int rc = compact_kept_enqueue(h, src, n, dst);
+  return rc ? rc : compact_kept_wait(h, kept);
+}
+
+// host twin of float_from_order_key (lsgpu_ssn.hip.h)
+static float host_float_from_order_key(uint32_t k) {
+  const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+// Minimum and maximum of a cloud on the device (n points, current stream; waits for it).  A NaN's ordered key lies beyond
+// the infinities', so a cloud with any NaN or infinity has a bound that is not finite: the verdict is the caller's.
+static int cloud_bounds(lsgpu_icp* h, const float4* src, int64_t n, float lo[3], float hi[3]) {
+  HIPC(h->ssn_bb.reserve(8));
+  HIPC(hipMemsetAsync(h->ssn_bb.p, 0xFF, 12, h->cur));
+  HIPC(hipMemsetAsync(h->ssn_bb.p + 3, 0, 12, h->cur));
+  hipLaunchKernelGGL(k_ssn_bounds, dim3(std::min(nblk(n), 256)), dim3(256), 0, h->cur, src, (int)n, h->ssn_bb.p);
+  HIPC(hipMemcpyAsync(h->pin->bounds, h->ssn_bb.p, sizeof h->pin->bounds, hipMemcpyDeviceToHost, h->cur));
+  HIPC(hipStreamSynchronize(h->cur));
+  for (int d = 0; d < 3; ++d) { lo[d] = host_float_from_order_key(h->pin->bounds[d]); hi[d] = host_float_from_order_key(h->pin->bounds[3 + d]); }
+  return LSGPU_OK;
+}
+
+// Where an entry point's kernels write a result of the caller's: into the caller's buffer if that is device memory, or
+// else into a buffer of the handle, from which copy_back() sends the elements that count to the host.
+template <class T>
+struct OutStage {
+  void* user = nullptr;
+  T* p = nullptr;        // what the kernels write
+  bool staged = false;
+  void classify(void* out) { user = out; p = static_cast<T*>(out); staged = !is_device_ptr(out); }
+  int open(lsgpu_icp* h, void* out, DevBuf<T>& buf, size_t room) {
+    classify(out);
+    if (staged) { HIPC(buf.reserve(room)); p = buf.p; }
+    return LSGPU_OK;
+  }
+  // n elements of `from` (device) to the caller's buffer, wherever that is
+  int send(lsgpu_icp* h, const T* from, size_t n) {
+    if (n) HIPC(hipMemcpyAsync(user, from, n * sizeof(T), staged ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+    return LSGPU_OK;
+  }
+  int copy_back(lsgpu_icp* h, size_t n) { return staged ? send(h, p, n) : LSGPU_OK; }
+};
 
 // SamplingSurfaceNormal on device memory: src (n points) -> out_xyz1 / out_nrm (device, room for n)
 // (`ahead`: draws begun by the caller, this filter's first at ahead->used; nullptr: the filter draws for itself)
@@ -1901,15 +1941,7 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
 }
 
 // RandomSampling on device memory (order preserved)
-// (defer_wait: everything is enqueued, the host's wait for the number of points kept is left to random_sampling_wait --
-// lsgpu_icp_compute puts the rest of the grid build on the other stream in between)
-static int random_sampling_wait(lsgpu_icp* h, int64_t* n_out) {
-  uint32_t unused = 0, kept = 0;
-  const int rc = scan_totals_wait(h, &unused, &kept);
-  if (rc) return rc;
-  *n_out = kept;
-  return LSGPU_OK;
-}
+// (defer_wait: everything is enqueued, the host's wait for the number of points kept is left to compact_kept_wait)
 static int random_sampling_device(lsgpu_icp* h, const float4* src, int64_t n, float prob, int64_t seed,
                                   float4* out_xyz1, int64_t* n_out, DrawAhead* ahead = nullptr, bool defer_wait = false) {
   *n_out = 0;
@@ -1927,14 +1959,9 @@ static int random_sampling_device(lsgpu_icp* h, const float4* src, int64_t n, fl
   rc = ahead->ready();
   if (rc) return rc;
   hipLaunchKernelGGL(k_draw_select, dim3(nblk(n)), dim3(256), 0, h->cur, (int)n, h->ssn_draws.p + first_draw, prob, h->ssn_keep.p);
-  rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->cur, src, (int)n, h->ssn_keep.p,
-                     h->ssn_out_pos.p, out_xyz1);
-  HIPC(hipGetLastError());
-  rc = scan_totals_enqueue(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
+  rc = compact_kept_enqueue(h, src, n, out_xyz1);
   if (rc || defer_wait) return rc;
-  return random_sampling_wait(h, n_out);
+  return compact_kept_wait(h, n_out);
 }
 
 // SurfaceNormalDataPointsFilter on the reference the handle holds (set_reference has just been enqueued on h->stream):
@@ -1974,18 +2001,17 @@ int lsgpu_icp_filter_reference_normals(lsgpu_icp* h, const float* xyz1, int64_t 
   int rc = lsgpu_icp_set_reference(h, xyz1, nullptr, n);
   if (rc) return rc;
   const int64_t np = (int64_t)knn * n;
-  const bool dev_n = is_device_ptr(out_normals), dev_i = out_ids && is_device_ptr(out_ids), dev_d = out_d2 && is_device_ptr(out_d2);
-  float* on = out_normals; int* oi = out_ids; float* od = out_d2;
-  if (!dev_n) { HIPC(h->flt_nrm.reserve(3 * n)); on = h->flt_nrm.p; }
-  if (out_ids && !dev_i) { HIPC(h->ids_io.reserve(np)); oi = h->ids_io.p; }
-  if (out_ids && !dev_d) { HIPC(h->d2_io.reserve(np)); od = h->d2_io.p; }   // (the kernels write both or neither)
-  rc = snf_device(h, knn, oi, od);
+  OutStage<float> on; OutStage<int> oi; OutStage<float> od;
+  if ((rc = on.open(h, out_normals, h->flt_nrm, 3 * n))) return rc;
+  if (out_ids && (rc = oi.open(h, out_ids, h->ids_io, np))) return rc;
+  if (out_ids && (rc = od.open(h, out_d2, h->d2_io, np))) return rc;   // (the kernels write both or neither: no out_d2, the handle's buffer)
+  rc = snf_device(h, knn, oi.p, od.p);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(n)), dim3(256), 0, h->stream, h->pts.p, (int)n, h->nrm.p, on);
+  hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(n)), dim3(256), 0, h->stream, h->pts.p, (int)n, h->nrm.p, on.p);
   HIPC(hipGetLastError());
-  if (!dev_n) HIPC(hipMemcpyAsync(out_normals, on, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-  if (out_ids && !dev_i) HIPC(hipMemcpyAsync(out_ids, oi, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
-  if (out_d2 && !dev_d) HIPC(hipMemcpyAsync(out_d2, od, (size_t)np * 4, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = on.copy_back(h, 3 * n))) return rc;
+  if ((rc = oi.copy_back(h, np))) return rc;
+  if (out_d2 && (rc = od.copy_back(h, np))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2003,15 +2029,13 @@ int lsgpu_icp_filter_reference(lsgpu_icp* h, const float* xyz1, int64_t n, int k
   const float4* src = nullptr;
   int rc = stage_points(h, xyz1, n, h->flt_in, &src);
   if (rc) return rc;
-  const bool dev_x = is_device_ptr(out_xyz1), dev_n = is_device_ptr(out_normals);
-  float4* ox = reinterpret_cast<float4*>(out_xyz1);
-  float* on = out_normals;
-  if (!dev_x) { HIPC(h->flt_ref.reserve(n)); ox = h->flt_ref.p; }
-  if (!dev_n) { HIPC(h->flt_nrm.reserve(3 * n)); on = h->flt_nrm.p; }
-  rc = ssn_device(h, src, n, knn, ratio, -1, ox, on, n_out);
+  OutStage<float4> ox; OutStage<float> on;
+  if ((rc = ox.open(h, out_xyz1, h->flt_ref, n))) return rc;
+  if ((rc = on.open(h, out_normals, h->flt_nrm, 3 * n))) return rc;
+  rc = ssn_device(h, src, n, knn, ratio, -1, ox.p, on.p, n_out);
   if (rc) return rc;
-  if (!dev_x && *n_out) HIPC(hipMemcpyAsync(out_xyz1, ox, (size_t)*n_out * 16, hipMemcpyDeviceToHost, h->stream));
-  if (!dev_n && *n_out) HIPC(hipMemcpyAsync(out_normals, on, (size_t)*n_out * 12, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = ox.copy_back(h, *n_out))) return rc;
+  if ((rc = on.copy_back(h, 3 * *n_out))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2028,12 +2052,11 @@ int lsgpu_icp_filter_reading(lsgpu_icp* h, const float* xyz1, int64_t n, float p
   const float4* src = nullptr;
   int rc = stage_points(h, xyz1, n, h->flt_in, &src);
   if (rc) return rc;
-  const bool dev_x = is_device_ptr(out_xyz1);
-  float4* ox = reinterpret_cast<float4*>(out_xyz1);
-  if (!dev_x) { HIPC(h->flt_rd.reserve(n)); ox = h->flt_rd.p; }
-  rc = random_sampling_device(h, src, n, prob, -1, ox, n_out);
+  OutStage<float4> ox;
+  if ((rc = ox.open(h, out_xyz1, h->flt_rd, n))) return rc;
+  rc = random_sampling_device(h, src, n, prob, -1, ox.p, n_out);
   if (rc) return rc;
-  if (!dev_x && *n_out) HIPC(hipMemcpyAsync(out_xyz1, ox, (size_t)*n_out * 16, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = ox.copy_back(h, *n_out))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2272,7 +2295,7 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
     h->hook_before_ref_sync = [&]() -> int {
       side_guard.enter();
       int r = LSGPU_OK;
-      if (chain->reading_prob >= 0.f) r = random_sampling_wait(h, &nqf);   // (the number of points kept)
+      if (chain->reading_prob >= 0.f) r = compact_kept_wait(h, &nqf);   // (the number of points kept)
       if (!r && nqf > 0) r = prepare_queries(h, reinterpret_cast<const float*>(rd_dev), nqf, Mat34{}, /*gather*/ false);
       side_guard.leave();
       return r;
@@ -2363,23 +2386,15 @@ int lsgpu_filter_cylinder(lsgpu_icp* h, const float* xyz1, int64_t n, const floa
   const float4* src = nullptr;
   int rc = stage_points(h, xyz1, n, h->flt_in, &src);
   if (rc) return rc;
-  const bool dev_x = is_device_ptr(out_xyz1);
-  float4* ox = reinterpret_cast<float4*>(out_xyz1);
-  if (!dev_x) { HIPC(h->flt_rd.reserve(n)); ox = h->flt_rd.p; }
+  OutStage<float4> ox;
+  if ((rc = ox.open(h, out_xyz1, h->flt_rd, n))) return rc;
   HIPC(h->ssn_keep.reserve(n));
   HIPC(h->ssn_out_pos.reserve(n));
   hipLaunchKernelGGL(k_cylinder_select, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, center[0], center[1],
                      center[2], radius_m * radius_m, height_m / 2.0, remove_point_inside, h->ssn_keep.p);
-  rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
+  rc = compact_kept(h, src, n, ox.p, n_out);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, h->ssn_keep.p,
-                     h->ssn_out_pos.p, ox);
-  HIPC(hipGetLastError());
-  uint32_t unused = 0, kept = 0;
-  rc = scan_totals(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n, &unused, &kept);
-  if (rc) return rc;
-  *n_out = kept;
-  if (!dev_x && kept) HIPC(hipMemcpyAsync(out_xyz1, ox, (size_t)kept * 16, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = ox.copy_back(h, *n_out))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2396,21 +2411,15 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
   const float4* src = nullptr;
   int rc = stage_points(h, xyz1, n, h->flt_in, &src);
   if (rc) return rc;
-  // getMinMax3D
-  HIPC(h->ssn_bb.reserve(8));
-  HIPC(hipMemsetAsync(h->ssn_bb.p, 0xFF, 12, h->stream));
-  HIPC(hipMemsetAsync(h->ssn_bb.p + 3, 0, 12, h->stream));
-  hipLaunchKernelGGL(k_ssn_bounds, dim3(std::min(nblk(n), 256)), dim3(256), 0, h->stream, src, (int)n, h->ssn_bb.p);
-  uint32_t* hb = reinterpret_cast<uint32_t*>(h->h_pinned + 104);
-  HIPC(hipMemcpyAsync(hb, h->ssn_bb.p, 24, hipMemcpyDeviceToHost, h->stream));
-  HIPC(hipStreamSynchronize(h->stream));
-  auto from_key = [](uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; float f; std::memcpy(&f, &u, 4); return f; };
+  float lo[3], hi[3];   // getMinMax3D
+  rc = cloud_bounds(h, src, n, lo, hi);
+  if (rc) return rc;
   float inv[3];
   int minb[3], divb[3];
   for (int d = 0; d < 3; ++d) {
     inv[d] = 1.0f / leaf[d];
-    minb[d] = (int)std::floor(from_key(hb[d]) * inv[d]);
-    const int maxb = (int)std::floor(from_key(hb[3 + d]) * inv[d]);
+    minb[d] = (int)std::floor(lo[d] * inv[d]);
+    const int maxb = (int)std::floor(hi[d] * inv[d]);
     divb[d] = maxb - minb[d] + 1;
   }
   if ((int64_t)divb[0] * (int64_t)divb[1] * (int64_t)divb[2] > 2147483647ll) {
@@ -2430,19 +2439,11 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
   hipLaunchKernelGGL(k_voxel_heads, dim3(nblk(n)), dim3(256), 0, h->stream, h->sc->keys_alt.p, (int)n, h->ssn_seg_of.p);
   hipLaunchKernelGGL(k_voxel_centroids, dim3(nblk(n)), dim3(256), 0, h->stream, src, h->sc->keys_alt.p, h->sc->vals_alt.p, (int)n,
                      min_points, h->ssn_seg_of.p, h->flt_ref.p, h->ssn_keep.p);
-  rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
+  OutStage<float4> ox;
+  if ((rc = ox.open(h, out_xyz1, h->flt_rd, n))) return rc;
+  rc = compact_kept(h, h->flt_ref.p, n, ox.p, n_out);
   if (rc) return rc;
-  const bool dev_x = is_device_ptr(out_xyz1);
-  float4* ox = reinterpret_cast<float4*>(out_xyz1);
-  if (!dev_x) { HIPC(h->flt_rd.reserve(n)); ox = h->flt_rd.p; }
-  hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->stream, h->flt_ref.p, (int)n, h->ssn_keep.p,
-                     h->ssn_out_pos.p, ox);
-  HIPC(hipGetLastError());
-  uint32_t unused = 0, kept = 0;
-  rc = scan_totals(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n, &unused, &kept);
-  if (rc) return rc;
-  *n_out = kept;
-  if (!dev_x && kept) HIPC(hipMemcpyAsync(out_xyz1, ox, (size_t)kept * 16, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = ox.copy_back(h, *n_out))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2451,19 +2452,11 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
 // m; none of src and h->vgf_out), one point per occupied voxel in the order of the voxels' first points.  No draw.
 static int voxel_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m, const lsgpu_point_filter& f, float4* dst,
                                     int64_t* m_out) {
-  // the cloud's minimum and maximum, and with them the verdict on its finiteness: a NaN's ordered key lies beyond the
-  // infinities', so a cloud with any NaN or infinity has a bound that is not finite
-  HIPC(h->ssn_bb.reserve(8));
-  HIPC(hipMemsetAsync(h->ssn_bb.p, 0xFF, 12, h->stream));
-  HIPC(hipMemsetAsync(h->ssn_bb.p + 3, 0, 12, h->stream));
-  hipLaunchKernelGGL(k_ssn_bounds, dim3(std::min(nblk(m), 256)), dim3(256), 0, h->stream, src, (int)m, h->ssn_bb.p);
-  uint32_t* hb = reinterpret_cast<uint32_t*>(h->h_pinned + 104);
-  HIPC(hipMemcpyAsync(hb, h->ssn_bb.p, 24, hipMemcpyDeviceToHost, h->stream));
-  HIPC(hipStreamSynchronize(h->stream));
-  auto from_key = [](uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; float v; std::memcpy(&v, &u, 4); return v; };
+  // the cloud's minimum and maximum, and with them the verdict on its finiteness
   float lo[3], hi[3];
+  int rc = cloud_bounds(h, src, m, lo, hi);
+  if (rc) return rc;
   for (int a = 0; a < 3; ++a) {
-    lo[a] = from_key(hb[a]); hi[a] = from_key(hb[3 + a]);
     if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {
       h->err = "apply_point_filters: VoxelGridDataPointsFilter was handed a NaN or infinite coordinate; put RemoveNaNDataPointsFilter "
                "(and a MaxDist / BoundingBox filter against infinities) in front of it";
@@ -2482,20 +2475,11 @@ static int voxel_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m, 
   HIPC(h->sc->vals.reserve(m));
   HIPC(h->vgf_out.reserve(m));
   hipLaunchKernelGGL(k_vgf_keys, dim3(nblk(m)), dim3(256), 0, h->stream, src, (int)m, g, h->sc->keys.p, h->sc->vals.p);
-  int rc = sort_pairs(h, m, nbits);  // stable: the points of a voxel keep input order
+  rc = sort_pairs(h, m, nbits);  // stable: the points of a voxel keep input order
   if (rc) return rc;
   hipLaunchKernelGGL(k_vgf_reduce, dim3(nblk(m)), dim3(256), 0, h->stream, src, h->sc->keys_alt.p, h->sc->vals_alt.p, (int)m, g,
                      f.flag ? 1 : 0, h->vgf_out.p, h->ssn_keep.p);
-  rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_compact_points, dim3(nblk(m)), dim3(256), 0, h->stream, h->vgf_out.p, (int)m, h->ssn_keep.p,
-                     h->ssn_out_pos.p, dst);
-  HIPC(hipGetLastError());
-  uint32_t unused = 0, kept = 0;
-  rc = scan_totals(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m, &unused, &kept);
-  if (rc) return rc;
-  *m_out = kept;
-  return LSGPU_OK;
+  return compact_kept(h, h->vgf_out.p, m, dst, m_out);
 }
 
 int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
@@ -2568,15 +2552,8 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
     }
     hipLaunchKernelGGL(k_point_filter_select, dim3(nblk(m)), dim3(256), 0, h->stream, cur, (int)m, d, h->ssn_draws.p,
                        h->ssn_keep.p);
-    rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m);
+    rc = compact_kept(h, cur, m, ping, &m);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_compact_points, dim3(nblk(m)), dim3(256), 0, h->stream, cur, (int)m, h->ssn_keep.p,
-                       h->ssn_out_pos.p, ping);
-    HIPC(hipGetLastError());
-    uint32_t unused = 0, kept = 0;
-    rc = scan_totals(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m, &unused, &kept);
-    if (rc) return rc;
-    m = kept;
     cur = ping;
     std::swap(ping, pong);
   }
@@ -2608,24 +2585,20 @@ int lsgpu_cloud_from_pointcloud2(lsgpu_icp* h, const unsigned char* data, int64_
   HIPC(h->ssn_out_pos.reserve(n));
   hipLaunchKernelGGL(k_pc2_unpack, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, point_step, off_x, off_y, off_z,
                      is_bigendian ? 1 : 0, drop_non_finite ? 1 : 0, h->flt_in.p, h->ssn_keep.p);
-  const bool dev_x = is_device_ptr(out_xyz1);
+  OutStage<float4> ox;   // (the result is unpacked, and compacted, in the handle's buffers whatever the caller's is)
+  ox.classify(out_xyz1);
   int64_t m = n;
   const float4* res = h->flt_in.p;
   if (drop_non_finite) {
     HIPC(h->flt_rd.reserve(n));
-    int rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
+    const int rc = compact_kept(h, h->flt_in.p, n, h->flt_rd.p, &m);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->stream, h->flt_in.p, (int)n, h->ssn_keep.p,
-                       h->ssn_out_pos.p, h->flt_rd.p);
-    uint32_t unused = 0, kept = 0;
-    rc = scan_totals(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n, &unused, &kept);
-    if (rc) return rc;
-    m = kept;
     res = h->flt_rd.p;
   }
   HIPC(hipGetLastError());
   *n_out = m;
-  if (m) HIPC(hipMemcpyAsync(out_xyz1, res, (size_t)m * 16, dev_x ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  const int rc = ox.send(h, res, (size_t)m);
+  if (rc) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2638,12 +2611,11 @@ int lsgpu_cloud_to_pointxyz(lsgpu_icp* h, const float* xyz1, int64_t n, unsigned
   const float4* src = nullptr;
   int rc = stage_points(h, xyz1, n, h->flt_in, &src);
   if (rc) return rc;
-  const bool dev_o = is_device_ptr(out_data);
-  float4* dst = reinterpret_cast<float4*>(out_data);
-  if (!dev_o) { HIPC(h->flt_rd.reserve(n)); dst = h->flt_rd.p; }
-  hipLaunchKernelGGL(k_pc2_pack, dim3(nblk(n)), dim3(256), 0, h->stream, src, n, dst);
+  OutStage<float4> dst;
+  if ((rc = dst.open(h, out_data, h->flt_rd, n))) return rc;
+  hipLaunchKernelGGL(k_pc2_pack, dim3(nblk(n)), dim3(256), 0, h->stream, src, n, dst.p);
   HIPC(hipGetLastError());
-  if (!dev_o) HIPC(hipMemcpyAsync(out_data, dst, (size_t)n * 16, hipMemcpyDeviceToHost, h->stream));
+  if ((rc = dst.copy_back(h, n))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
@@ -2788,235 +2760,242 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
   return rc;
 }
 
-// the pair-indexed instantiations of the loop's normal-equation kernel (k-match loop, k = 2..LSGPU_MATCHER_KNN_MAX)
+}  // extern "C"
+
+// The loop's normal-equation kernel for k matches per reading point (k-match loop, k >= 2), for the chain plan (KDTreeMatcher
+// maxDist / outlier-filter chains, any k) and for RobustOutlierFilter's weighted pairs (always the chain plan).
+// nullptr: k = 1 without a chain -- the plain k_normal_eq_loop<minimizer> serves that case.
 using NeLoopFn = decltype(&k_normal_eq_loop<kPointToPlane>);
-static NeLoopFn ne_loop_pairs(bool p2p, int k) {
-  static const NeLoopFn tab[2][kKnnKMax + 1] = {
-      {nullptr, nullptr, k_normal_eq_loop<kPointToPlane, 2>, k_normal_eq_loop<kPointToPlane, 3>, k_normal_eq_loop<kPointToPlane, 4>,
-       k_normal_eq_loop<kPointToPlane, 5>, k_normal_eq_loop<kPointToPlane, 6>, k_normal_eq_loop<kPointToPlane, 7>,
-       k_normal_eq_loop<kPointToPlane, 8>},
-      {nullptr, nullptr, k_normal_eq_loop<kPointToPoint, 2>, k_normal_eq_loop<kPointToPoint, 3>, k_normal_eq_loop<kPointToPoint, 4>,
-       k_normal_eq_loop<kPointToPoint, 5>, k_normal_eq_loop<kPointToPoint, 6>, k_normal_eq_loop<kPointToPoint, 7>,
-       k_normal_eq_loop<kPointToPoint, 8>}};
-  return tab[p2p ? 1 : 0][k];
+using UpdateFn = decltype(&k_icp_update<kPointToPlane>);
+template <int MIN, bool CHAIN, bool RB, size_t... I>
+static NeLoopFn ne_loop_of_k(int k, std::index_sequence<I...>) {
+  static const NeLoopFn tab[] = {k_normal_eq_loop<MIN, (int)I + 1, CHAIN, RB>...};   // k = 1 .. kKnnKMax
+  return tab[k - 1];
 }
-// ... and the chain plan's (KDTreeMatcher maxDist / outlier-filter chains, k = 1..LSGPU_MATCHER_KNN_MAX)
-static NeLoopFn ne_loop_chain(bool p2p, int k) {
-  static const NeLoopFn tab[2][kKnnKMax + 1] = {
-      {nullptr, k_normal_eq_loop<kPointToPlane, 1, true>, k_normal_eq_loop<kPointToPlane, 2, true>, k_normal_eq_loop<kPointToPlane, 3, true>,
-       k_normal_eq_loop<kPointToPlane, 4, true>, k_normal_eq_loop<kPointToPlane, 5, true>, k_normal_eq_loop<kPointToPlane, 6, true>,
-       k_normal_eq_loop<kPointToPlane, 7, true>, k_normal_eq_loop<kPointToPlane, 8, true>},
-      {nullptr, k_normal_eq_loop<kPointToPoint, 1, true>, k_normal_eq_loop<kPointToPoint, 2, true>, k_normal_eq_loop<kPointToPoint, 3, true>,
-       k_normal_eq_loop<kPointToPoint, 4, true>, k_normal_eq_loop<kPointToPoint, 5, true>, k_normal_eq_loop<kPointToPoint, 6, true>,
-       k_normal_eq_loop<kPointToPoint, 7, true>, k_normal_eq_loop<kPointToPoint, 8, true>}};
-  return tab[p2p ? 1 : 0][k];
+template <bool CHAIN, bool RB>
+static NeLoopFn ne_loop_of(bool p2p, int k) {
+  using Ks = std::make_index_sequence<kKnnKMax>;
+  return p2p ? ne_loop_of_k<kPointToPoint, CHAIN, RB>(k, Ks{}) : ne_loop_of_k<kPointToPlane, CHAIN, RB>(k, Ks{});
+}
+static NeLoopFn ne_loop_fn(bool p2p, int k, bool chain, bool robust) {
+  if (robust) return ne_loop_of<true, true>(p2p, k);
+  if (chain) return ne_loop_of<true, false>(p2p, k);
+  return k >= 2 ? ne_loop_of<false, false>(p2p, k) : nullptr;
 }
 
-// ... and the weighted ones of a handle with RobustOutlierFilter (always the chain plan)
-static NeLoopFn ne_loop_robust(bool p2p, int k) {
-  static const NeLoopFn tab[2][kKnnKMax + 1] = {
-      {nullptr, k_normal_eq_loop<kPointToPlane, 1, true, true>, k_normal_eq_loop<kPointToPlane, 2, true, true>, k_normal_eq_loop<kPointToPlane, 3, true, true>,
-       k_normal_eq_loop<kPointToPlane, 4, true, true>, k_normal_eq_loop<kPointToPlane, 5, true, true>, k_normal_eq_loop<kPointToPlane, 6, true, true>,
-       k_normal_eq_loop<kPointToPlane, 7, true, true>, k_normal_eq_loop<kPointToPlane, 8, true, true>},
-      {nullptr, k_normal_eq_loop<kPointToPoint, 1, true, true>, k_normal_eq_loop<kPointToPoint, 2, true, true>, k_normal_eq_loop<kPointToPoint, 3, true, true>,
-       k_normal_eq_loop<kPointToPoint, 4, true, true>, k_normal_eq_loop<kPointToPoint, 5, true, true>, k_normal_eq_loop<kPointToPoint, 6, true, true>,
-       k_normal_eq_loop<kPointToPoint, 7, true, true>, k_normal_eq_loop<kPointToPoint, 8, true, true>}};
-  return tab[p2p ? 1 : 0][k];
-}
-
-int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
-                    float T_out[16], lsgpu_icp_stats* stats) {
-  if (!h || !T_init || !T_out) return LSGPU_BAD_ARG;
-  h->err.clear();
-  std::memcpy(T_out, T_init, 16 * sizeof(float));
-  lsgpu_icp_stats st;
-  std::memset(&st, 0, sizeof(st));
-  if (stats) *stats = st;
-  h->trace.clear(); h->trace_on_device = 0; h->rb_trace_n = 0;
-  // queries that lsgpu_icp_compute ordered and moved on its side stream belong to THIS call and to no later one, whatever
-  // way it ends (a guess that is refused below would otherwise leave queries moved by that guess to the next call with the
-  // same pointer and size)
-  const float* const prepared_rd = h->prepared_rd;
-  const int64_t prepared_nq = h->prepared_nq;
-  h->prepared_rd = nullptr; h->prepared_nq = 0;
-  // ... and so do reading normals (lsgpu_icp_compute's step / lsgpu_icp_align_normals)
-  const float* const normals_for = h->rd_nrm_for;
-  const int64_t normals_n = h->rd_nrm_n;
-  h->rd_nrm_for = nullptr; h->rd_nrm_n = 0; h->na_trace_n = 0;
-  // Local reasons not to start.  In the split-scan mode they are NOT returned yet: a rank that left here would
-  // leave its peers blocked in the first collective, so every rank first takes part in the entry handshake below.
-  int local_rc = LSGPU_OK;
-  // KDTreeMatcher knn: 1, or k >= 2 nearest matches per reading point (k N pairs; the split-scan mode refuses such handles)
-  const int kk = h->cfg.matcher_knn >= 2 ? h->cfg.matcher_knn : 1;
-  const bool kmatch = kk > 1;
-  // KDTreeMatcher maxDist / Max-, Min-, MedianDistOutlierFilter: the chain plan (lsgpu_policy.h), whatever k
-  const bool chain = chain_on(h);
+// One call of lsgpu_icp_align: the state its phases share, and the phases in the order they run -- start, init_loop_state,
+// configure_policy, feed (which enqueues iterations and fetches the loop state), harvest.  Each returns an LSGPU code.
+struct AlignRun {
+  lsgpu_icp* const h;
+  const float* const reading_xyz1; const int64_t nq; const float* const T_init;   // the call's arguments
+  int kk = 1;   // KDTreeMatcher knn: 1, or k >= 2 nearest matches per reading point (k N pairs; the split-scan mode refuses such handles)
+  bool kmatch = false, chain = false, robust = false, angle = false;
   ChainArgs ca{};
-  ca.lo2 = h->cfg.outlier_min_dist * h->cfg.outlier_min_dist;
-  ca.max2 = (h->cfg.outlier_max_dist > 0.f && !std::isinf(h->cfg.outlier_max_dist)) ? h->cfg.outlier_max_dist * h->cfg.outlier_max_dist : INFINITY;
-  ca.med_factor = h->cfg.outlier_median_factor; ca.has_median = h->cfg.outlier_median_factor > 0.f ? 1 : 0;
-  const bool robust = h->robust_on;
-  if (robust) { ca.rb = robust::params(h->robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
-  // SurfaceNormalOutlierFilter: inert without reading normals or without reference normals (as upstream)
-  const bool angle = chain && h->normals_on && h->normals.max_angle >= 0.f && h->have_normals && reading_xyz1 &&
-                     normals_for == reading_xyz1 && normals_n == nq;
-  if (robust && ca.rb.plane && !h->have_normals) {
-    h->err = "align: RobustOutlierFilter distanceType point2plane needs reference normals";
-    h->cone_build_in_align = false;
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->nr <= 0 || nq <= 0 || !reading_xyz1) {  // empty cloud: ConvergenceError upstream
-    h->err = "align: empty reading or no reference";
-    local_rc = LSGPU_NO_CONVERGENCE;
-  } else if (nq > 0x7FFFFFF0ll) {
-    local_rc = LSGPU_BAD_ARG;
-  } else if (kmatch && h->nr < kk) {
-    h->err = "align: the reference has fewer points than the matcher's knn";
-    local_rc = LSGPU_BAD_ARG;
-  } else if (kmatch && nq > 0x7FFFFFF0ll / kk) {
-    h->err = "align: knn x reading points exceeds the 32-bit pair count";
-    local_rc = LSGPU_BAD_ARG;
-  } else if (!lsgpu_check_rigid(T_init)) {
-    // step 5 moves the reading with RigidTransformation::compute, which throws TransformationError for such a matrix
-    // (after both filters have run, as here when the call came through lsgpu_icp_compute)
-    h->err = "align: the initial guess is not a rigid transformation (|1 - det R| > 1e-3)";
-    local_rc = LSGPU_BAD_ARG;
-  }
-  if (local_rc && !h->comm) { h->cone_build_in_align = false; return local_rc; }
-  HIPC(hipSetDevice(h->device));
-  const double t0 = wall_ms();
-  h->knn_events_used = 0;
-  h->comm_events_used = 0;
-  h->time_comm = h->comm != nullptr && h->cfg.profile_kernels != 0;
-  h->tail_pending = false;   // (from here on everything is behind it on h->stream itself)
-
-  // step 5: T_refMean_dataIn = T_refIn_refMean^-1 * T_init (pure translation inverse)
+  double t0 = 0.0;
   float T_rm_in[16];
-  std::memcpy(T_rm_in, T_init, sizeof(T_rm_in));
-  for (int d = 0; d < 3; ++d) T_rm_in[12 + d] = T_init[12 + d] - h->mean[d];
-  // (lsgpu_icp_compute may have ordered and moved these very queries on its side stream already: the loop's stream
-  // only has to wait for that)
-  const bool prepared = !local_rc && !h->comm && prepared_rd == reading_xyz1 && prepared_nq == nq;
-  int rc = local_rc;
-  if (!rc) {
-    if (prepared) HIPC(hipStreamWaitEvent(h->stream, h->side_done, 0));
-    else rc = prepare_queries(h, reading_xyz1, nq, to_mat34(T_rm_in));
-  }
-  if (rc && !h->comm) return rc;
-  int64_t nq_total = nq;
-  if (h->comm) {
-    // entry handshake: {shard size, cannot-start flag} summed over the ranks.  TrimmedDist ranks over ALL matches, so
-    // the rank uses the global count; and either every rank enters the loop or none does.
-    long long* hn = reinterpret_cast<long long*>(h->h_pinned + 60);
-    hn[0] = rc ? 0 : (long long)nq;
-    hn[1] = rc ? 1 : 0;
-    HIPC(hipMemcpyAsync(h->comm_tmp.p, hn, 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    RCCLC(rccl_api()->AllReduce(h->comm_tmp.p, h->comm_tmp.p + 2, 2, ncclInt64, ncclSum, h->comm, h->stream));
-    HIPC(hipMemcpyAsync(hn, h->comm_tmp.p + 2, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    const int w = wait_stream(h);
-    if (w) return w;
-    nq_total = (int64_t)hn[0];
-    if (rc) return rc;
-    if (hn[1] != 0) {
-      h->err = "align (split-scan): another rank could not start; all ranks give up together";
-      return LSGPU_NO_CONVERGENCE;
+  int64_t nq_total = 0;
+  int max_it = 0, nb = 0;
+  IcpState* hst = nullptr;   // the staging block's copy of the loop state
+  uint32_t k = 0;            // TrimmedDist rank
+  bool p2p = false, timed = false, split_update = false;
+  Mat34 Tdummy;
+  NeLoopFn ne_loop = nullptr, ne_loop_k = nullptr; UpdateFn update = nullptr;   // this handle's instantiations
+  std::vector<size_t> ev_of_launch;  // event index of every enqueued iteration
+
+  // Start checks, the reading's order (step 5) and, in the split-scan mode, the entry handshake.
+  int start() {
+    h->trace.clear(); h->trace_on_device = 0; h->rb_trace_n = 0;
+    // queries that lsgpu_icp_compute ordered and moved on its side stream belong to THIS call and to no later one, whatever
+    // way it ends (a guess that is refused below would otherwise leave queries moved by that guess to the next call with the
+    // same pointer and size)
+    const float* const prepared_rd = h->prepared_rd;
+    const int64_t prepared_nq = h->prepared_nq;
+    h->prepared_rd = nullptr; h->prepared_nq = 0;
+    // ... and so do reading normals (lsgpu_icp_compute's step / lsgpu_icp_align_normals)
+    const float* const normals_for = h->rd_nrm_for;
+    const int64_t normals_n = h->rd_nrm_n;
+    h->rd_nrm_for = nullptr; h->rd_nrm_n = 0; h->na_trace_n = 0;
+    // Local reasons not to start.  In the split-scan mode they are NOT returned yet: a rank that left here would
+    // leave its peers blocked in the first collective, so every rank first takes part in the entry handshake below.
+    int local_rc = LSGPU_OK;
+    kk = h->cfg.matcher_knn >= 2 ? h->cfg.matcher_knn : 1;
+    kmatch = kk > 1;
+    // KDTreeMatcher maxDist / Max-, Min-, MedianDistOutlierFilter: the chain plan (lsgpu_policy.h), whatever k
+    chain = chain_on(h);
+    ca.lo2 = h->cfg.outlier_min_dist * h->cfg.outlier_min_dist;
+    ca.max2 = (h->cfg.outlier_max_dist > 0.f && !std::isinf(h->cfg.outlier_max_dist)) ? h->cfg.outlier_max_dist * h->cfg.outlier_max_dist : INFINITY;
+    ca.med_factor = h->cfg.outlier_median_factor; ca.has_median = h->cfg.outlier_median_factor > 0.f ? 1 : 0;
+    robust = h->robust_on;
+    if (robust) { ca.rb = robust::params(h->robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
+    // SurfaceNormalOutlierFilter: inert without reading normals or without reference normals (as upstream)
+    angle = chain && h->normals_on && h->normals.max_angle >= 0.f && h->have_normals && reading_xyz1 &&
+            normals_for == reading_xyz1 && normals_n == nq;
+    if (robust && ca.rb.plane && !h->have_normals) {
+      h->err = "align: RobustOutlierFilter distanceType point2plane needs reference normals";
+      h->cone_build_in_align = false;
+      return LSGPU_BAD_CONFIG;
     }
+    if (h->nr <= 0 || nq <= 0 || !reading_xyz1) {  // empty cloud: ConvergenceError upstream
+      h->err = "align: empty reading or no reference";
+      local_rc = LSGPU_NO_CONVERGENCE;
+    } else if (nq > 0x7FFFFFF0ll) {
+      local_rc = LSGPU_BAD_ARG;
+    } else if (kmatch && h->nr < kk) {
+      h->err = "align: the reference has fewer points than the matcher's knn";
+      local_rc = LSGPU_BAD_ARG;
+    } else if (kmatch && nq > 0x7FFFFFF0ll / kk) {
+      h->err = "align: knn x reading points exceeds the 32-bit pair count";
+      local_rc = LSGPU_BAD_ARG;
+    } else if (!lsgpu_check_rigid(T_init)) {
+      // step 5 moves the reading with RigidTransformation::compute, which throws TransformationError for such a matrix
+      // (after both filters have run, as here when the call came through lsgpu_icp_compute)
+      h->err = "align: the initial guess is not a rigid transformation (|1 - det R| > 1e-3)";
+      local_rc = LSGPU_BAD_ARG;
+    }
+    if (local_rc && !h->comm) { h->cone_build_in_align = false; return local_rc; }
+    HIPC(hipSetDevice(h->device));
+    t0 = wall_ms();
+    h->knn_events_used = 0;
+    h->comm_events_used = 0;
+    h->time_comm = h->comm != nullptr && h->cfg.profile_kernels != 0;
+    h->tail_pending = false;   // (from here on everything is behind it on h->stream itself)
+
+    // step 5: T_refMean_dataIn = T_refIn_refMean^-1 * T_init (pure translation inverse)
+    std::memcpy(T_rm_in, T_init, sizeof(T_rm_in));
+    for (int d = 0; d < 3; ++d) T_rm_in[12 + d] = T_init[12 + d] - h->mean[d];
+    // (lsgpu_icp_compute may have ordered and moved these very queries on its side stream already: the loop's stream
+    // only has to wait for that)
+    const bool prepared = !local_rc && !h->comm && prepared_rd == reading_xyz1 && prepared_nq == nq;
+    int rc = local_rc;
+    if (!rc) {
+      if (prepared) HIPC(hipStreamWaitEvent(h->stream, h->side_done, 0));
+      else rc = prepare_queries(h, reading_xyz1, nq, to_mat34(T_rm_in));
+    }
+    if (rc && !h->comm) return rc;
+    nq_total = nq;
+    if (h->comm) {
+      // entry handshake: {shard size, cannot-start flag} summed over the ranks.  TrimmedDist ranks over ALL matches, so
+      // the rank uses the global count; and either every rank enters the loop or none does.
+      long long* hn = h->pin->handshake;
+      hn[0] = rc ? 0 : (long long)nq;
+      hn[1] = rc ? 1 : 0;
+      HIPC(hipMemcpyAsync(h->comm_tmp.p, hn, 2 * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+      RCCLC(rccl_api()->AllReduce(h->comm_tmp.p, h->comm_tmp.p + 2, 2, ncclInt64, ncclSum, h->comm, h->stream));
+      HIPC(hipMemcpyAsync(hn, h->comm_tmp.p + 2, 2 * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+      const int w = wait_stream(h);
+      if (w) return w;
+      nq_total = (int64_t)hn[0];
+      if (rc) return rc;
+      if (hn[1] != 0) {
+        h->err = "align (split-scan): another rank could not start; all ranks give up together";
+        return LSGPU_NO_CONVERGENCE;
+      }
+    }
+    return LSGPU_OK;
   }
 
   // step 6: the loop runs on the device.  Every iteration is {kNN, select x3, normal equations,
   // update}; k_icp_update solves, moves T_iter, runs the checkers and raises `done`, after which the
   // remaining enqueued launches exit immediately.  The host only looks at the state every few iterations.
-  const int max_it = h->cfg.max_iterations;
-  HIPC(h->state.reserve(1));
-  HIPC(h->chk_hist.reserve((size_t)8 * (max_it + 2)));
-  HIPC(h->trace_dev.reserve((size_t)max_it));
-  if (robust) {
-    HIPC(h->rb_hist.reserve(3 * kHistBins)); HIPC(h->rb_sel.reserve(4)); HIPC(h->rb_state.reserve(1));
-    HIPC(h->rb_trace_dev.reserve((size_t)max_it));
-    HIPC(hipMemsetAsync(h->rb_state.p, 0, sizeof(RobustState), h->stream));
-    ca.rb_hist = h->rb_hist.p; ca.rb_sel = h->rb_sel.p; ca.rb_state = h->rb_state.p; ca.rb_trace = h->rb_trace_dev.p;
-  }
-  if (angle) {
-    // step 5 moves the reading's descriptors with the reading: n0 = R_init n, once per alignment (lsgpu_rotate_descriptors' chain)
-    HIPC(h->rd_nrm0.reserve((size_t)3 * nq)); HIPC(h->na_trace_dev.reserve((size_t)max_it));
-    hipLaunchKernelGGL(k_rotate3, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rd_nrm.p, nq, to_mat34(T_rm_in), h->rd_nrm0.p);
+  // Here: the loop's buffers, its initial state (one launch, k_align_init) and the kernels this handle's loop is made of.
+  int init_loop_state() {
+    max_it = h->cfg.max_iterations;
+    HIPC(h->state.reserve(1));
+    HIPC(h->chk_hist.reserve((size_t)8 * (max_it + 2)));
+    HIPC(h->trace_dev.reserve((size_t)max_it));
+    if (robust) {
+      HIPC(h->rb_hist.reserve(3 * kHistBins)); HIPC(h->rb_sel.reserve(4)); HIPC(h->rb_state.reserve(1));
+      HIPC(h->rb_trace_dev.reserve((size_t)max_it));
+      HIPC(hipMemsetAsync(h->rb_state.p, 0, sizeof(RobustState), h->stream));
+      ca.rb_hist = h->rb_hist.p; ca.rb_sel = h->rb_sel.p; ca.rb_state = h->rb_state.p; ca.rb_trace = h->rb_trace_dev.p;
+    }
+    if (angle) {
+      // step 5 moves the reading's descriptors with the reading: n0 = R_init n, once per alignment (lsgpu_rotate_descriptors' chain)
+      HIPC(h->rd_nrm0.reserve((size_t)3 * nq)); HIPC(h->na_trace_dev.reserve((size_t)max_it));
+      hipLaunchKernelGGL(k_rotate3, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rd_nrm.p, nq, to_mat34(T_rm_in), h->rd_nrm0.p);
+      HIPC(hipGetLastError());
+      ca.na_rn = h->rd_nrm0.p; ca.na_eps = normal_angle::eps_of(h->normals.max_angle); ca.na_trace = h->na_trace_dev.p;
+    }
+    hst = &h->pin->state;
+    std::memset(hst, 0, sizeof(IcpState));
+    hostmath::identity4(hst->T_iter);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) hst->T_rows[r * 4 + c] = hst->T_iter[c * 4 + r];
+    hst->prev_limit = INFINITY; hst->cap2 = INFINITY;
+    hst->cap_enabled = (h->cfg.reserved[0] == 0 && !kmatch && !chain) ? 1 : 0;   // (no radius cap in the k-match loop / the chain plan)
+    hst->minimizer = h->cfg.error_minimizer;
+    hst->max_iter = max_it; hst->smooth = h->cfg.smooth_length;
+    hst->lim_rot = h->cfg.min_diff_rot; hst->lim_trans = h->cfg.min_diff_trans;
+    AlignInitArgs ia{};
+    {  // checkers.init(T_iter): history starts with the identity
+      hostmath::CheckerState cs{0, 0};
+      hostmath::checker_push(&cs, ia.chk0, hst->T_iter);
+      hst->counter = cs.counter; hst->n_hist = cs.n_hist;
+    }
+    k = trim_rank((int64_t)kk * nq_total, h->cfg.trim_ratio);   // (TrimmedDist ranks all k N distances)
+    HIPC(h->sel_aux.reserve(kSelFailFlag + 4));
+    HIPC(h->spread_flag.reserve((size_t)((nq + 63) / 64))); HIPC(h->spread_list.reserve(kFrontMax)); HIPC(h->spread_cnt.reserve(2));
+    HIPC(h->sel_win.reserve((size_t)kSelWinRows * 512));
+    HIPC(h->amb_key.reserve((size_t)kSelAmbCap)); HIPC(h->amb_val.reserve((size_t)kSelAmbCap * 32));
+    hst->sel_wide = (!h->comm && tuning().fused_select && !kmatch && !chain) ? 1 : 0;
+    h->n_spread_host = 0; h->n_spread_known = false;
+    ia.state = *hst;
+    ia.sel0 = SelState{0u, k};   // sel[0] = {0, rank}: constant during an align
+    ia.state_dev = h->state.p; ia.chk_hist = h->chk_hist.p; ia.sel = h->sel.p;
+    ia.counters3 = h->counters.p + 32;   // stragglers, (unused), heavy-tile ticket
+    ia.ne_ticket = h->ne_tickets.p; ia.sel_aux = h->sel_aux.p; ia.spread_flag = h->spread_flag.p;
+    ia.spread_cnt = h->spread_cnt.p; ia.sel_win = h->sel_win.p; ia.hist = h->hist.p;
+    ia.n_sel_aux = kSelFailFlag + 4; ia.n_spread_flag = (int)((nq + 63) / 64); ia.n_sel_win = kSelWinRows * 512;
+    hipLaunchKernelGGL(k_align_init, dim3(64), dim3(256), 0, h->stream, ia);
     HIPC(hipGetLastError());
-    ca.na_rn = h->rd_nrm0.p; ca.na_eps = normal_angle::eps_of(h->normals.max_angle); ca.na_trace = h->na_trace_dev.p;
-  }
-  IcpState* hst = reinterpret_cast<IcpState*>(h->h_pinned + 64);  // pinned staging (<= 512 B); [0..47] D2H, [48..63] H2D
-  static_assert(sizeof(IcpState) <= 64 * sizeof(double), "IcpState staging");
-  std::memset(hst, 0, sizeof(IcpState));
-  hostmath::identity4(hst->T_iter);
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) hst->T_rows[r * 4 + c] = hst->T_iter[c * 4 + r];
-  hst->prev_limit = INFINITY; hst->cap2 = INFINITY;
-  hst->cap_enabled = (h->cfg.reserved[0] == 0 && !kmatch && !chain) ? 1 : 0;   // (no radius cap in the k-match loop / the chain plan)
-  hst->minimizer = h->cfg.error_minimizer;
-  hst->max_iter = max_it; hst->smooth = h->cfg.smooth_length;
-  hst->lim_rot = h->cfg.min_diff_rot; hst->lim_trans = h->cfg.min_diff_trans;
-  AlignInitArgs ia{};
-  {  // checkers.init(T_iter): history starts with the identity
-    hostmath::CheckerState cs{0, 0};
-    hostmath::checker_push(&cs, ia.chk0, hst->T_iter);
-    hst->counter = cs.counter; hst->n_hist = cs.n_hist;
-  }
-  const uint32_t k = trim_rank((int64_t)kk * nq_total, h->cfg.trim_ratio);   // (TrimmedDist ranks all k N distances)
-  HIPC(h->sel_aux.reserve(kSelFailFlag + 4));
-  HIPC(h->spread_flag.reserve((size_t)((nq + 63) / 64))); HIPC(h->spread_list.reserve(kFrontMax)); HIPC(h->spread_cnt.reserve(2));
-  HIPC(h->sel_win.reserve((size_t)kSelWinRows * 512));
-  HIPC(h->amb_key.reserve((size_t)kSelAmbCap)); HIPC(h->amb_val.reserve((size_t)kSelAmbCap * 32));
-  hst->sel_wide = (!h->comm && tuning().fused_select && !kmatch && !chain) ? 1 : 0;
-  h->n_spread_host = 0; h->n_spread_known = false;
-  ia.state = *hst;
-  ia.sel0 = SelState{0u, k};   // sel[0] = {0, rank}: constant during an align
-  ia.state_dev = h->state.p; ia.chk_hist = h->chk_hist.p; ia.sel = h->sel.p;
-  ia.counters3 = h->counters.p + 32;   // stragglers, (unused), heavy-tile ticket
-  ia.ne_ticket = h->ne_tickets.p; ia.sel_aux = h->sel_aux.p; ia.spread_flag = h->spread_flag.p;
-  ia.spread_cnt = h->spread_cnt.p; ia.sel_win = h->sel_win.p; ia.hist = h->hist.p;
-  ia.n_sel_aux = kSelFailFlag + 4; ia.n_spread_flag = (int)((nq + 63) / 64); ia.n_sel_win = kSelWinRows * 512;
-  hipLaunchKernelGGL(k_align_init, dim3(64), dim3(256), 0, h->stream, ia);
-  HIPC(hipGetLastError());
 
-  const int nb = std::min(kNeBlocks, nblk((int64_t)kk * nq));
-  const bool timed = h->cfg.profile_kernels != 0;
-  const Mat34 Tdummy = to_mat34(hst->T_iter);
-  std::vector<size_t> ev_of_launch;  // event index of every enqueued iteration
-  const bool split_update = tuning().split_update;  // (profiling: the update as its own launch)
-  // the minimizer's instantiations of the accumulation and of the update (point-to-point reads no normals)
-  const bool p2p = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
-  const auto ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
-  const auto update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
-  const NeLoopFn ne_loop_k = robust ? ne_loop_robust(p2p, kk) : chain ? ne_loop_chain(p2p, kk) : kmatch ? ne_loop_pairs(p2p, kk) : nullptr;
-  ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
+    nb = std::min(kNeBlocks, nblk((int64_t)kk * nq));
+    timed = h->cfg.profile_kernels != 0;
+    Tdummy = to_mat34(hst->T_iter);
+    split_update = tuning().split_update;  // (profiling: the update as its own launch)
+    // the minimizer's instantiations of the accumulation and of the update (point-to-point reads no normals)
+    p2p = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT;
+    ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
+    update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
+    ne_loop_k = ne_loop_fn(p2p, kk, chain, robust);
+    ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
+    return LSGPU_OK;
+  }
+
   // The launch policy (lsgpu_policy.h) decides what every iteration is made of and when the host looks at the loop
-  // state; this function executes its decisions.  (tests/cpp/policy_check.cpp drives the same state machine on the CPU.)
-  policy::Config& pc = h->pol_cfg;
-  pc = policy::Config();
-  pc.cone_from = tuning().cone_from; pc.wide_iters = tuning().wide_iters; pc.group = 6;
-  pc.enq_limit = 8 * max_it + 64;   // (only guards against a device that never finishes, see below)
-  pc.predict_select = tuning().predict_select; pc.commit_select = tuning().commit_select; pc.comm_commit = tuning().comm_commit;
-  pc.lookahead = tuning().lookahead; pc.comm = h->comm != nullptr;
-  pc.seed_cap = tuning().seed_cap; pc.cap_enabled = h->cfg.reserved[0] == 0;
-  pc.two_pass_select = !h->comm && tuning().fused_select && tuning().two_pass_select;
-  pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
-  pc.kmatch = kmatch; pc.chain = chain;
-  pc.robust_mad = robust && ca.rb.mad; pc.robust_scale_iters = robust ? h->robust.nb_iteration_for_scale : 0;
-  policy::State& pol = h->pol;
-  if (h->cone_build_in_align) { h->cone_ok = cone_wanted(h); h->cone_decided = false; }   // (its build follows the first iteration, below)
-  // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
-  // itself the build when that is still to come)
-  // (a reference of a markedly different size is another scene or another sub-map depth: the judgement starts over)
-  if (h->index_rest > 0 && (h->nr > 2 * h->index_rest_nr || 2 * h->nr < h->index_rest_nr)) h->index_rest = 0;
-  const bool index_rests = h->index_rest > 0 && h->cone_ok;
-  if (index_rests) { --h->index_rest; if (h->cone_build_in_align) { h->cone_build_in_align = false; h->cone_ok = false; } }
-  pol.begin_align(h->cone_ok && !index_rests, h->cone_decided, h->cone_dense, h->cone_occupancy);
-  h->pay_voxel_timed = h->pay_index_timed = false;
-  if (!h->ev_pay[0]) for (auto& e : h->ev_pay) HIPC(hipEventCreate(&e));
-  auto enqueue_iteration = [&](const policy::Iteration& itn) -> int {
-    // itn.knn == false: only select + normal equations + update on the distances already there (after a missed
-    // prediction).  RCCL mode: the per-shard tables of a *committed* iteration are summed over the ranks in ONE grouped
-    // all-reduce (the host knows beforehand that no select kernel will run: sel_streak comes from the global limit,
-    // so every rank takes the same decision); un-committed iterations there run the plain three-pass select.
+  // state; feed() executes its decisions.  (tests/cpp/policy_check.cpp drives the same state machine on the CPU.)
+  int configure_policy() {
+    policy::Config& pc = h->pol_cfg;
+    pc = policy::Config();
+    pc.cone_from = tuning().cone_from; pc.wide_iters = tuning().wide_iters; pc.group = 6;
+    pc.enq_limit = 8 * max_it + 64;   // (only guards against a device that never finishes, see below)
+    pc.predict_select = tuning().predict_select; pc.commit_select = tuning().commit_select; pc.comm_commit = tuning().comm_commit;
+    pc.lookahead = tuning().lookahead; pc.comm = h->comm != nullptr;
+    pc.seed_cap = tuning().seed_cap; pc.cap_enabled = h->cfg.reserved[0] == 0;
+    pc.two_pass_select = !h->comm && tuning().fused_select && tuning().two_pass_select;
+    pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
+    pc.kmatch = kmatch; pc.chain = chain;
+    pc.robust_mad = robust && ca.rb.mad; pc.robust_scale_iters = robust ? h->robust.nb_iteration_for_scale : 0;
+    if (h->cone_build_in_align) { h->cone_ok = cone_wanted(h); h->cone_decided = false; }   // (its build follows the first iteration: feed())
+    // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
+    // itself the build when that is still to come)
+    // (a reference of a markedly different size is another scene or another sub-map depth: the judgement starts over)
+    if (h->index_rest > 0 && (h->nr > 2 * h->index_rest_nr || 2 * h->nr < h->index_rest_nr)) h->index_rest = 0;
+    const bool index_rests = h->index_rest > 0 && h->cone_ok;
+    if (index_rests) { --h->index_rest; if (h->cone_build_in_align) { h->cone_build_in_align = false; h->cone_ok = false; } }
+    h->pol.begin_align(h->cone_ok && !index_rests, h->cone_decided, h->cone_dense, h->cone_occupancy);
+    h->pay_voxel_timed = h->pay_index_timed = false;
+    if (!h->ev_pay[0]) for (auto& e : h->ev_pay) HIPC(hipEventCreate(&e));
+    if (pc.lookahead && !pc.comm && !h->ev_state) HIPC(hipEventCreateWithFlags(&h->ev_state, hipEventDisableTiming));   // (fetch_state's look-ahead)
+    return LSGPU_OK;
+  }
+
+  // One iteration on the stream.
+  // itn.knn == false: only select + normal equations + update on the distances already there (after a missed
+  // prediction).  RCCL mode: the per-shard tables of a *committed* iteration are summed over the ranks in ONE grouped
+  // all-reduce (the host knows beforehand that no select kernel will run: sel_streak comes from the global limit,
+  // so every rank takes the same decision); un-committed iterations there run the plain three-pass select.
+  int enqueue_iteration(const policy::Iteration& itn) {
     int r = LSGPU_OK;
     if (kmatch || chain) {   // the k-match / chain plan (lsgpu_policy.h): k-best search, three-pass select on the k N distances, pair-indexed sums
       const int np = (int)(kk * nq);
@@ -3086,17 +3065,17 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
     }
     if (ev) HIPC(hipEventRecord(ev->e, h->stream));
     return hipGetLastError() == hipSuccess ? LSGPU_OK : LSGPU_HIP_ERROR;
-  };
+  }
+
   // A look at the loop state.  Look-ahead (not in the split-scan mode): ONE more iteration is enqueued behind the copy
   // before the host waits for it, so the device works through the round trip instead of idling (~25 us + a cold first
   // launch per look); that iteration carries the decisions of the previous look, like the later iterations of any group,
   // and exits at once if the state it finds says `done`.
-  if (pc.lookahead && !pc.comm && !h->ev_state) HIPC(hipEventCreateWithFlags(&h->ev_state, hipEventDisableTiming));
-  auto fetch_state = [&](int* enqueued_ahead) -> int {
+  int fetch_state(int* enqueued_ahead) {
     *enqueued_ahead = 0;
     HIPC(hipMemcpyAsync(hst, h->state.p, sizeof(IcpState), hipMemcpyDeviceToHost, h->stream));
     policy::Iteration ahead_it;
-    if (pol.lookahead_iteration(pc, &ahead_it)) {
+    if (h->pol.lookahead_iteration(h->pol_cfg, &ahead_it)) {
       HIPC(hipEventRecord(h->ev_state, h->stream));
       const int r = enqueue_iteration(ahead_it);
       if (r) return r;
@@ -3105,121 +3084,119 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
       return LSGPU_OK;
     }
     return wait_stream(h);  // (bounded in the split-scan mode: a dead peer must not hang this rank)
-  };
+  }
 
-  // iteration 0: seeded; capped by the trim quantile of the seed distances (a guaranteed bound: no retry can follow)
-  rc = enqueue_iteration(pol.plan(pc, true, pc.seed_cap && pc.cap_enabled, true, true, false));
-  if (rc) return rc;
-  pol.enq = 1; pol.since_check = 1;
-  if (h->cone_build_in_align) {
-    // lsgpu_icp_compute left the direction index's build to this point: the device is busy with the first search, the
-    // ~15 launches of the build go to the side stream (its own sort scratch) while it is
-    h->cone_build_in_align = false;
-    h->cur = h->side_stream; h->sc = &h->scr_side;
-    int rb = build_cone_index(h);
-    if (!rb && h->cone_ok) {
-      if (hipEventRecord(h->cone_done, h->side_stream) != hipSuccess) { (void)hipGetLastError(); rb = LSGPU_HIP_ERROR; h->err = "align: event record"; }
-      h->cone_pending = true;
-    }
-    h->cur = h->stream; h->sc = &h->scr_main;
-    if (rb) return rb;
-  }
-  // The device decides when the loop ends (CounterTransformationChecker raises `done` after max_iterations at the
-  // latest); the host keeps feeding groups of launches until it sees `done`.  Launches enqueued behind an
-  // iteration that had to be repeated exit at once, so the number of enqueues is NOT bounded by max_iterations;
-  // the policy's enq_limit only guards against a device that never finishes.
-  for (;;) {
-    policy::Iteration itn;
-    if (pol.next_in_group(pc, &itn)) {
-      rc = enqueue_iteration(itn);
-      if (rc) return rc;
-      continue;
-    }
-    int ahead = 0;
-    const bool repriced = pol.wants_reprice();   // (the last launch in front of this look priced the index again: its counters
-    rc = fetch_state(&ahead);                    //  were copied in front of the state, they are on the host when the state is)
+  // The feed loop: iteration 0, the deferred build of the direction index, then groups of iterations and looks until `done`.
+  int feed() {
+    policy::Config& pc = h->pol_cfg;
+    policy::State& pol = h->pol;
+    // iteration 0: seeded; capped by the trim quantile of the seed distances (a guaranteed bound: no retry can follow)
+    int rc = enqueue_iteration(pol.plan(pc, true, pc.seed_cap && pc.cap_enabled, true, true, false));
     if (rc) return rc;
-    h->n_spread_host = hst->n_spread; h->n_spread_known = true;
-    policy::LookInput li;
-    li.done = hst->done; li.status = hst->status; li.iter = hst->iter; li.sel_streak = hst->sel_streak;
-    if (hst->sel_fails >= 2) pc.two_pass_select = false;   // (slices fuller than the normal equations can set aside: the select's third pass is back)
-    li.stragglers = hst->stragglers; li.nq = nq; li.status_cap_failed = kStatusCapFailed; li.status_sel_failed = kStatusSelFailed;
-    if (tuning().short_last_group) { li.chk_rot = hst->chk_rot; li.chk_trans = hst->chk_trans; li.lim_rot = hst->lim_rot; li.lim_trans = hst->lim_trans; li.chk_rot_prev = hst->chk_rot_prev; li.chk_trans_prev = hst->chk_trans_prev; }
-    const policy::LookVerdict verdict = pol.on_look(pc, li, ahead, repriced ? price_share(h) : -1.f);
-    if (verdict == policy::LookVerdict::RepeatUncapped) {
-      // the cap prediction failed for iteration hst->iter: repeat it uncapped, then carry on
-      hst->done = 0; hst->status = 0;
-      HIPC(hipMemcpyAsync(h->state.p, hst, sizeof(IcpState), hipMemcpyHostToDevice, h->stream));
-      HIPC(hipStreamSynchronize(h->stream));
-      rc = enqueue_iteration(pol.repeat_uncapped(pc));
-      if (rc) return rc;
-      continue;
-    }
-    if (verdict == policy::LookVerdict::RepeatSelect) {
-      // the limit left the predicted 12-bit bin in iteration hst->iter: its distances stand, the full select
-      // and everything after it run again
-      hst->sel_streak = 0;
-      hst->done = 0; hst->status = 0;
-      HIPC(hipMemcpyAsync(h->state.p, hst, sizeof(IcpState), hipMemcpyHostToDevice, h->stream));
-      HIPC(hipStreamSynchronize(h->stream));
-      rc = enqueue_iteration(pol.repeat_select(pc));
-      if (rc) return rc;
-      continue;
-    }
-    if (verdict == policy::LookVerdict::Done) {
-      if (ahead) {   // one launch is still queued behind the look that saw `done`
-        if (!h->ev_tail) HIPC(hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
-        HIPC(hipEventRecord(h->ev_tail, h->stream));
-        h->tail_pending = true;
+    pol.enq = 1; pol.since_check = 1;
+    if (h->cone_build_in_align) {
+      // lsgpu_icp_compute left the direction index's build to this point: the device is busy with the first search, the
+      // ~15 launches of the build go to the side stream (its own sort scratch) while it is
+      h->cone_build_in_align = false;
+      h->cur = h->side_stream; h->sc = &h->scr_side;
+      int rb = build_cone_index(h);
+      if (!rb && h->cone_ok) {
+        if (hipEventRecord(h->cone_done, h->side_stream) != hipSuccess) { (void)hipGetLastError(); rb = LSGPU_HIP_ERROR; h->err = "align: event record"; }
+        h->cone_pending = true;
       }
-      break;
+      h->cur = h->stream; h->sc = &h->scr_main;
+      if (rb) return rb;
     }
-    if (verdict == policy::LookVerdict::GiveUp) {
-      h->err = "align: the device loop did not finish";
-      return LSGPU_HIP_ERROR;
+    // The device decides when the loop ends (CounterTransformationChecker raises `done` after max_iterations at the
+    // latest); the host keeps feeding groups of launches until it sees `done`.  Launches enqueued behind an
+    // iteration that had to be repeated exit at once, so the number of enqueues is NOT bounded by max_iterations;
+    // the policy's enq_limit only guards against a device that never finishes.
+    for (;;) {
+      policy::Iteration itn;
+      if (pol.next_in_group(pc, &itn)) {
+        rc = enqueue_iteration(itn);
+        if (rc) return rc;
+        continue;
+      }
+      int ahead = 0;
+      const bool repriced = pol.wants_reprice();   // (the last launch in front of this look priced the index again: its counters
+      rc = fetch_state(&ahead);                    //  were copied in front of the state, they are on the host when the state is)
+      if (rc) return rc;
+      h->n_spread_host = hst->n_spread; h->n_spread_known = true;
+      policy::LookInput li;
+      li.done = hst->done; li.status = hst->status; li.iter = hst->iter; li.sel_streak = hst->sel_streak;
+      if (hst->sel_fails >= 2) pc.two_pass_select = false;   // (slices fuller than the normal equations can set aside: the select's third pass is back)
+      li.stragglers = hst->stragglers; li.nq = nq; li.status_cap_failed = kStatusCapFailed; li.status_sel_failed = kStatusSelFailed;
+      if (tuning().short_last_group) { li.chk_rot = hst->chk_rot; li.chk_trans = hst->chk_trans; li.lim_rot = hst->lim_rot; li.lim_trans = hst->lim_trans; li.chk_rot_prev = hst->chk_rot_prev; li.chk_trans_prev = hst->chk_trans_prev; }
+      const policy::LookVerdict verdict = pol.on_look(pc, li, ahead, repriced ? price_share(h) : -1.f);
+      if (verdict == policy::LookVerdict::RepeatUncapped || verdict == policy::LookVerdict::RepeatSelect) {
+        // RepeatUncapped: the cap prediction failed for iteration hst->iter: repeat it uncapped, then carry on.
+        // RepeatSelect: the limit left the predicted 12-bit bin in iteration hst->iter: its distances stand, the full
+        // select and everything after it run again.
+        const bool select_only = verdict == policy::LookVerdict::RepeatSelect;
+        if (select_only) hst->sel_streak = 0;
+        hst->done = 0; hst->status = 0;
+        HIPC(hipMemcpyAsync(h->state.p, hst, sizeof(IcpState), hipMemcpyHostToDevice, h->stream));
+        HIPC(hipStreamSynchronize(h->stream));
+        rc = enqueue_iteration(select_only ? pol.repeat_select(pc) : pol.repeat_uncapped(pc));
+        if (rc) return rc;
+        continue;
+      }
+      if (verdict == policy::LookVerdict::Done) {
+        if (ahead) {   // one launch is still queued behind the look that saw `done`
+          if (!h->ev_tail) HIPC(hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
+          HIPC(hipEventRecord(h->ev_tail, h->stream));
+          h->tail_pending = true;
+        }
+        return LSGPU_OK;
+      }
+      if (verdict == policy::LookVerdict::GiveUp) {
+        h->err = "align: the device loop did not finish";
+        return LSGPU_HIP_ERROR;
+      }
     }
   }
-  st.cap_retries = pol.cap_retries;
-  const int sel_retries = pol.sel_retries, committed_iterations = pol.committed_iterations;
-  if (h->pay_voxel_timed && h->pay_index_timed) {   // (both launches are long over: the loop's end was seen behind them)
-    float t_voxel = 0.f, t_index = 0.f;
-    if (hipEventElapsedTime(&t_voxel, h->ev_pay[0], h->ev_pay[1]) == hipSuccess && hipEventElapsedTime(&t_index, h->ev_pay[2], h->ev_pay[3]) == hipSuccess) {
-      h->pay_voxel_us = t_voxel * 1e3f; h->pay_index_us = t_index * 1e3f;
-      if (tuning().index_rest && policy::index_not_paying(t_voxel * 1e3f, t_index * 1e3f)) { h->index_rest = policy::kIndexRestAligns; h->index_rest_nr = h->nr; }
-    } else {
-      (void)hipGetLastError();
+
+  // The harvest: the index's pay-off judgement, status text, T_out (step 7), statistics and timings.  Returns the loop's status.
+  int harvest(float T_out[16], lsgpu_icp_stats& st) {
+    const policy::State& pol = h->pol;
+    st.cap_retries = pol.cap_retries;
+    if (h->pay_voxel_timed && h->pay_index_timed) {   // (both launches are long over: the loop's end was seen behind them)
+      float t_voxel = 0.f, t_index = 0.f;
+      if (hipEventElapsedTime(&t_voxel, h->ev_pay[0], h->ev_pay[1]) == hipSuccess && hipEventElapsedTime(&t_index, h->ev_pay[2], h->ev_pay[3]) == hipSuccess) {
+        h->pay_voxel_us = t_voxel * 1e3f; h->pay_index_us = t_index * 1e3f;
+        if (tuning().index_rest && policy::index_not_paying(t_voxel * 1e3f, t_index * 1e3f)) { h->index_rest = policy::kIndexRestAligns; h->index_rest_nr = h->nr; }
+      } else {
+        (void)hipGetLastError();
+      }
     }
-  }
-  const int it = hst->iter;
-  rc = hst->status;
-  if (rc == LSGPU_NO_CONVERGENCE)
-    h->err = hst->err_code == 1 ? "no point to minimize" : hst->err_code == 2 ? "normal matrix not positive definite"
-           : hst->err_code == 4 ? "non-finite point-to-point solution"
-           : hst->err_code == 5 ? "RobustOutlierFilter: no valid match or a MAD scale of 0"
-           : hst->err_code == 6 ? "RobustOutlierFilter: a weight is not finite" : "NaN in transformation checker";
-  st.iterations = it;
-  st.converged = hst->converged;
-  st.stragglers = (int64_t)hst->stragglers;
-  float T_iter[16];
-  std::memcpy(T_iter, hst->T_iter, sizeof(T_iter));
-  // The per-iteration trace stays in device memory until lsgpu_icp_get_trace asks for it (the synchronous copy cost every
-  // alignment 37 us -- 5 % of a 200 k-point pair -- for a record nobody but the tests and the profiler reads); the two
-  // statistics that came out of it travel with the loop state.
-  h->trace.clear();
-  h->trace_on_device = (size_t)std::min(it, max_it);
-  h->rb_trace_n = robust ? h->trace_on_device : 0;
-  h->na_trace_n = angle ? h->trace_on_device : 0;
-  h->trace_knn_us.clear();
-  if (it > 0) { st.final_limit = hst->last_limit; st.final_n_used = (int64_t)hst->last_used; }
-  if (rc == LSGPU_OK) {  // step 7
-    float Tmean[16], tmp[16];
-    hostmath::identity4(Tmean);
-    for (int d = 0; d < 3; ++d) Tmean[12 + d] = h->mean[d];
-    hostmath::mul4(T_iter, T_rm_in, tmp);
-    hostmath::mul4(Tmean, tmp, T_out);
-  }
-  // kNN timing: launches that actually ran are the first `it` (+ retries) enqueued ones
-  {
+    const int it = hst->iter;
+    const int rc = hst->status;
+    if (rc == LSGPU_NO_CONVERGENCE)
+      h->err = hst->err_code == 1 ? "no point to minimize" : hst->err_code == 2 ? "normal matrix not positive definite"
+             : hst->err_code == 4 ? "non-finite point-to-point solution"
+             : hst->err_code == 5 ? "RobustOutlierFilter: no valid match or a MAD scale of 0"
+             : hst->err_code == 6 ? "RobustOutlierFilter: a weight is not finite" : "NaN in transformation checker";
+    st.iterations = it;
+    st.converged = hst->converged;
+    st.stragglers = (int64_t)hst->stragglers;
+    // The per-iteration trace stays in device memory until lsgpu_icp_get_trace asks for it (the synchronous copy cost every
+    // alignment 37 us -- 5 % of a 200 k-point pair -- for a record nobody but the tests and the profiler reads); the two
+    // statistics that came out of it travel with the loop state.
+    h->trace.clear();
+    h->trace_on_device = (size_t)std::min(it, max_it);
+    h->rb_trace_n = robust ? h->trace_on_device : 0;
+    h->na_trace_n = angle ? h->trace_on_device : 0;
+    h->trace_knn_us.clear();
+    if (it > 0) { st.final_limit = hst->last_limit; st.final_n_used = (int64_t)hst->last_used; }
+    if (rc == LSGPU_OK) {  // step 7
+      float Tmean[16], tmp[16];
+      hostmath::identity4(Tmean);
+      for (int d = 0; d < 3; ++d) Tmean[12 + d] = h->mean[d];
+      hostmath::mul4(hst->T_iter, T_rm_in, tmp);
+      hostmath::mul4(Tmean, tmp, T_out);
+    }
+    // kNN timing: launches that actually ran are the first `it` (+ retries) enqueued ones
     size_t t = 0;
     for (size_t i = 0; i < h->knn_events_used && i < ev_of_launch.size(); ++i) {
       const auto& e = h->knn_events[ev_of_launch[i]];
@@ -3236,26 +3213,45 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
       else (void)hipGetLastError();
       if (t < h->trace_on_device) { h->trace_knn_us.push_back({m1 * 1e3f, m2 * 1e3f}); ++t; }
     }
-  }
-  if (h->time_comm) {   // time inside the collectives (launches enqueued behind the end exit at once and add next to nothing)
-    for (size_t i = 0; i < h->comm_events_used; ++i) {
-      float m = 0.f;
-      if (hipEventElapsedTime(&m, h->comm_events[i].first, h->comm_events[i].second) == hipSuccess) { st.t_comm_ms += m; st.comm_calls++; }
-      else (void)hipGetLastError();
+    if (h->time_comm) {   // time inside the collectives (launches enqueued behind the end exit at once and add next to nothing)
+      for (size_t i = 0; i < h->comm_events_used; ++i) {
+        float m = 0.f;
+        if (hipEventElapsedTime(&m, h->comm_events[i].first, h->comm_events[i].second) == hipSuccess) { st.t_comm_ms += m; st.comm_calls++; }
+        else (void)hipGetLastError();
+      }
     }
+    st.direction_index_launches = pol.cone_launches;   // (enqueued; those behind the end of the loop exited at once)
+    st.direction_index_occupancy = h->cone_decided ? h->cone_occupancy : 0.f;
+    st.direction_index_heavy_share = pol.cone_heavy;
+    st.pad_ = pol.sel_retries;  // (select predictions that missed; informational)
+    st.committed_select_iterations = pol.committed_iterations;
+    st.spread_tiles = (int)hst->n_spread;
+    st.t_total_ms = wall_ms() - t0;
+    return rc;
   }
-  st.direction_index_launches = h->pol.cone_launches;   // (enqueued; those behind the end of the loop exited at once)
-  st.direction_index_occupancy = h->cone_decided ? h->cone_occupancy : 0.f;
-  st.direction_index_heavy_share = h->pol.cone_heavy;
-  st.pad_ = sel_retries;  // (select predictions that missed; informational)
-  st.committed_select_iterations = committed_iterations;
-  st.spread_tiles = (int)hst->n_spread;
-  st.t_total_ms = wall_ms() - t0;
+};
+
+extern "C" {
+
+int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
+                    float T_out[16], lsgpu_icp_stats* stats) {
+  if (!h || !T_init || !T_out) return LSGPU_BAD_ARG;
+  h->err.clear();
+  std::memcpy(T_out, T_init, 16 * sizeof(float));
+  lsgpu_icp_stats st;
+  std::memset(&st, 0, sizeof(st));
+  if (stats) *stats = st;
+  AlignRun run{h, reading_xyz1, nq, T_init};
+  int rc = run.start();
+  if (!rc) rc = run.init_loop_state();
+  if (!rc) rc = run.configure_policy();
+  if (!rc) rc = run.feed();
+  if (rc) return rc;
+  rc = run.harvest(T_out, st);
   if (stats) *stats = st;
   return rc;
 }
 
-// dev only (LSGPU_KNN_STATS build): per-wave records of the last k_knn_tile launch / global counters
 int lsgpu_icp_align_batch(lsgpu_icp* const* handles, int n_handles, int64_t n_pairs,
                           const float* const* reference_xyz1, const float* const* reference_normals,
                           const int64_t* n_reference, const float* const* reading_xyz1,
@@ -3309,6 +3305,7 @@ int lsgpu_icp_align_batch(lsgpu_icp* const* handles, int n_handles, int64_t n_pa
   return ret;
 }
 
+// dev only (LSGPU_KNN_STATS build): per-wave records of the last k_knn_tile launch / global counters
 int lsgpu_dev_knn_wave_stats(lsgpu_icp* h, unsigned int* out, int nwaves) {
   if (!h) return LSGPU_BAD_ARG;
   if (!out) { HIPC(h->knn_dbg_wave.reserve((size_t)nwaves)); HIPC(hipMemset(h->knn_dbg_wave.p, 0, (size_t)nwaves * 16)); return LSGPU_OK; }

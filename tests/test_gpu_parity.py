@@ -1352,3 +1352,39 @@ def test_pointcloud2_conversion_round_trip(icp_mod):
         with pytest.raises(icp_mod.LsgpuError):
             h.cloud_from_pointcloud2(rec, n, step, 1, 5, 20)                            # z would leave the record
         assert h.cloud_from_pointcloud2(b"", 0, step, 1, 5, 9).shape[0] == 0
+
+
+def test_staging_members_do_not_disturb_one_another(icp_mod):
+    """One handle, every user of its pinned staging block in turn: an alignment of the 4 k-point golden pair, then the
+    PCL-style voxel grid, the input filter chain (VoxelGrid + RandomSampling, fixed seed), the cylinder filter and a
+    stand-alone trim limit, then the same alignment again.  The second alignment repeats the first bit for bit, and every
+    filter gives what it gives on a fresh handle.  The filters' cloud is one point longer than a scan tile (kScanTile,
+    lsgpu_scan.hip.h), so their compaction takes the multi-block scan."""
+    from laser_slam_amd import _lib
+    g = np.load(os.path.join(ROOT, "tests", "golden", "icp_pair4k.npz"))
+    scan_tile = 4096   # kScanTile in laser_slam_amd/csrc/lsgpu_scan.hip.h: the elements one block of the scan takes
+    cloud = np.ascontiguousarray(np.concatenate([g["ref"], g["rd"]])[:scan_tile + 1], np.float32)
+    assert cloud.shape == (scan_tile + 1, 4)
+    d2 = (cloud[:, :3] * cloud[:, :3]).sum(1).astype(np.float32)
+    specs = [(_lib.FILTER_VOXEL_GRID, 1, 1, [0.5, 0.5, 0.5]), (_lib.FILTER_RANDOM_SAMPLING, 0, 0, [0.6])]
+    filters = [lambda h: h.filter_voxel_grid(cloud, 0.4, 1),
+               lambda h: h.apply_point_filters(_chain(_lib, specs), cloud, seed=17),
+               lambda h: h.filter_cylinder(cloud, (0.0, 0.0, -1.7), 8.0, 4.0, False),
+               lambda h: np.array([h.trim_limit(d2, 0.75)], np.float32)]
+
+    def align(h):
+        T, st = h.align(g["rd"], g["T_init"])
+        return np.array(T).view(np.uint32).tolist(), st.iterations, np.float32(st.final_limit).view(np.uint32), st.final_n_used
+
+    with icp_mod.IcpHandle() as h:
+        h.set_reference(g["ref"], g["nrm"])
+        first = align(h)
+        got = [np.array(f(h)) for f in filters]
+        second = align(h)
+    assert first[1] > 1 and first[3] > 0
+    assert second == first
+    for f, a in zip(filters, got):
+        with icp_mod.IcpHandle() as fresh:
+            want = np.array(f(fresh))
+        assert a.shape == want.shape and np.array_equal(a.view(np.uint32), want.view(np.uint32))
+    assert all(0 < a.shape[0] < cloud.shape[0] for a in got[:3]) and np.isfinite(got[3]).all()
