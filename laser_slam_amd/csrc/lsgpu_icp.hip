@@ -12,7 +12,6 @@
 #include <string>
 #include <vector>
 #include <chrono>
-#include <functional>
 #include <system_error>
 #include <thread>
 #include <utility>
@@ -164,7 +163,7 @@ struct Staging {
   alignas(64) SelState sel0;                // run_select: sel[0] = {0, rank} on its way to the device
   alignas(64) long long handshake[2];       // split-scan entry handshake of an align: {shard size, cannot-start flag}
   alignas(64) IcpState state;               // the loop state of the running align, as of the host's last look
-  alignas(64) uint32_t totals[2][4];        // scan_totals, [side_totals_slot]: {last input, last scanned} of two scans
+  alignas(64) uint32_t totals[2][4];        // scan_totals, [lane.totals_row]: {last input, last scanned} of two scans
   alignas(64) uint32_t bounds[6];           // cloud_bounds: ordered keys of the minimum and the maximum
 };
 
@@ -173,8 +172,6 @@ struct lsgpu_icp {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;   // lsgpu_icp_compute: the reading's H2D, overlapped with the reference filter
-  float4* upload_into = nullptr;       // lsgpu_icp_compute_clouds_upload: that H2D goes into the reading's slot instead of the staging buffer
-  bool upload_done = false;            // ... and has been enqueued (every return path of lsgpu_icp_compute drains the copy stream)
   hipEvent_t copy_done = nullptr;
   hipEvent_t ref_up_done = nullptr;    // the reference's H2D on `stream`: the reading's copy queues behind it
   std::string err;
@@ -187,7 +184,8 @@ struct lsgpu_icp {
   lsgpu_icp_info info;
   DevBuf<float4> ref_in;   DevBuf<float> nrm_in;
   // Scratch of the sorts and scans.  Two sets: lsgpu_icp_compute orders the queries on a second stream while the
-  // reference grid is built on the first (`sc` / `cur` = the set and the stream the helpers below enqueue on).
+  // reference grid is built on the first.  A lane is what the helpers below enqueue on (stream, set, row of pin->totals):
+  // `lane` is the main one except inside a LaneScope.
   struct SortScratch {
     DevBuf<uint64_t> keys, keys_alt;
     DevBuf<uint32_t> vals, vals_alt;
@@ -196,16 +194,13 @@ struct lsgpu_icp {
     void release() { keys.release(); keys_alt.release(); vals.release(); vals_alt.release(); sort_tmp.release(); sort_hist.release(); }
   };
   SortScratch scr_main, scr_side;
-  SortScratch* sc = &scr_main;
-  hipStream_t cur = nullptr;           // == stream except while lsgpu_icp_compute enqueues its side work
+  struct Lane { hipStream_t stream; SortScratch* scratch; int totals_row; } lane{nullptr, &scr_main, 0};
+  Lane main_lane() { return Lane{stream, &scr_main, 0}; }
+  Lane side_lane() { return Lane{side_stream, &scr_side, 1}; }   // (lsgpu_icp_compute's side work, its align's deferred index build)
   hipStream_t draw_stream = nullptr;   // H2D of the filters' draws, issued by the helper thread that produces them
   hipEvent_t draws_done = nullptr, draws_first_done = nullptr;
   hipStream_t side_stream = nullptr;   // lsgpu_icp_compute: reading filter + query order, beside the grid build
   hipEvent_t side_done = nullptr;
-  int side_totals_slot = 0;            // scan_totals staging: the side path uses its own row of pin->totals
-  std::function<int()> hook_before_ref_sync, hook_after_grid;   // set by lsgpu_icp_compute: before set_reference waits for its cell counts / once the whole grid build is enqueued
-  const float* prepared_rd = nullptr;  // queries already ordered by the side path (consumed by the next align)
-  int64_t prepared_nq = 0;
   DevBuf<float4> pts, nrm;
   DevBuf<uint32_t> ref_inv;
   DevBuf<HashEntry> tables;
@@ -220,8 +215,6 @@ struct lsgpu_icp {
   DevBuf<float4> cone_rowz;
   ConeDev cone;
   bool cone_ok = false;       // built (or being built on the side stream: cone_pending) for the current reference
-  bool defer_cone = false;    // lsgpu_icp_compute: set_reference leaves the build to the side stream
-  bool cone_build_in_align = false;   // ... and the next align enqueues it there behind its first iteration
   bool cone_pending = false;  // the loop's stream has not yet waited for cone_done
   hipEvent_t cone_done = nullptr;
   DevBuf<uint32_t> cone_occ;          // occupied (row, column) bins of the index
@@ -323,7 +316,6 @@ struct lsgpu_icp {
   bool normals_on = false;
   lsgpu_normals_config normals{};
   DevBuf<float> rd_nrm;       // the reading's normals, 3 floats per point in the reading's order (lsgpu_icp_compute's step, or the caller's) ...
-  const float* rd_nrm_for = nullptr; int64_t rd_nrm_n = 0;   // ... which belong to the NEXT align of this reading, and to no later one
   DevBuf<float> rd_nrm0;      // ... moved by R_init (step 5): what the loop's angle test reads
   DevBuf<float> nrm_io;       // staging of lsgpu_icp_get_reference_normals
   DevBuf<lsgpu_normal_angle_trace> na_trace_dev;
@@ -351,6 +343,12 @@ struct lsgpu_icp {
   std::vector<lsgpu_iter_trace> trace;
   size_t trace_on_device = 0;   // records of the last alignment still in trace_dev (fetched by lsgpu_icp_get_trace)
   std::vector<std::pair<float, float>> trace_knn_us;   // their search timings (profiled runs), merged in on the fetch
+};
+
+struct LaneScope {   // the one way to leave the main lane: the helpers enqueue on `to` while the scope lives, on the main lane after it
+  lsgpu_icp* const h;
+  LaneScope(lsgpu_icp* hh, const lsgpu_icp::Lane& to) : h(hh) { h->lane = to; }
+  ~LaneScope() { h->lane = h->main_lane(); }
 };
 
 // Wait for the handle's stream.  Plain handles block; a handle with a communicator polls with a deadline
@@ -536,7 +534,7 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
     delete h;
     return LSGPU_HIP_ERROR;
   }
-  h->cur = h->stream;
+  h->lane = h->main_lane();
   *out = h;
   return LSGPU_OK;
 }
@@ -597,27 +595,27 @@ static int scan_u32(lsgpu_icp* h, const uint32_t* in, uint32_t* out, size_t n, b
 template <int ITEMS>
 static void radix_pass(lsgpu_icp* h, const uint64_t* kin, const uint32_t* vin, uint64_t* kout, uint32_t* vout, int64_t n,
                        int shift, uint32_t mask, int nblocks) {
-  uint32_t* bh = h->sc->sort_hist.p;
+  uint32_t* bh = h->lane.scratch->sort_hist.p;
   uint32_t* dtot = bh + (size_t)256 * nblocks;
   // (the scan as the tail of k_rs_hist -- last block, ticket -- was measured 2 % slower end to end than this launch)
-  hipLaunchKernelGGL(k_rs_hist<ITEMS>, dim3(nblocks), dim3(256), 0, h->cur, kin, n, shift, mask, bh, nblocks);
-  hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, h->cur, bh, nblocks, dtot);
-  hipLaunchKernelGGL(k_rs_scatter<ITEMS>, dim3(nblocks), dim3(256), 0, h->cur, kin, vin, kout, vout, n, shift, mask,
+  hipLaunchKernelGGL(k_rs_hist<ITEMS>, dim3(nblocks), dim3(256), 0, h->lane.stream, kin, n, shift, mask, bh, nblocks);
+  hipLaunchKernelGGL(k_rs_scan, dim3(256), dim3(256), 0, h->lane.stream, bh, nblocks, dtot);
+  hipLaunchKernelGGL(k_rs_scatter<ITEMS>, dim3(nblocks), dim3(256), 0, h->lane.stream, kin, vin, kout, vout, n, shift, mask,
                      bh, dtot, nblocks);
 }
 
-// Stable sort of (h->sc->keys, h->sc->vals)[0..n) by the low `nbits` key bits; the result is in h->sc->keys_alt / h->sc->vals_alt
+// Stable sort of (h->lane.scratch->keys, h->lane.scratch->vals)[0..n) by the low `nbits` key bits; the result is in h->lane.scratch->keys_alt / h->lane.scratch->vals_alt
 // (callers re-read those members: the two buffer pairs may have changed places).
 static int sort_pairs(lsgpu_icp* h, int64_t n, int nbits) {
-  HIPC(h->sc->keys_alt.reserve(n));
-  HIPC(h->sc->vals_alt.reserve(n));
+  HIPC(h->lane.scratch->keys_alt.reserve(n));
+  HIPC(h->lane.scratch->vals_alt.reserve(n));
   const int items_env = tuning().sort_items;
   const int items = items_env ? items_env : n >= (1 << 21) ? 16 : n >= (1 << 19) ? 8 : 4;
   const int nblocks = (int)((n + 256 * items - 1) / (256 * items));
-  HIPC(h->sc->sort_hist.reserve((size_t)256 * nblocks + 256));
+  HIPC(h->lane.scratch->sort_hist.reserve((size_t)256 * nblocks + 256));
   const int passes = std::max(1, (nbits + 7) / 8);   // (no key bits: one pass over an all-zero digit = a stable copy)
-  uint64_t *kin = h->sc->keys.p, *kout = h->sc->keys_alt.p;
-  uint32_t *vin = h->sc->vals.p, *vout = h->sc->vals_alt.p;
+  uint64_t *kin = h->lane.scratch->keys.p, *kout = h->lane.scratch->keys_alt.p;
+  uint32_t *vin = h->lane.scratch->vals.p, *vout = h->lane.scratch->vals_alt.p;
   for (int p = 0; p < passes; ++p) {
     const int shift = 8 * p, width = std::max(0, std::min(8, nbits - shift));
     const uint32_t mask = (1u << width) - 1u;
@@ -627,7 +625,7 @@ static int sort_pairs(lsgpu_icp* h, int64_t n, int nbits) {
     std::swap(kin, kout); std::swap(vin, vout);
   }
   HIPC(hipGetLastError());
-  if ((passes & 1) == 0) { std::swap(h->sc->keys, h->sc->keys_alt); std::swap(h->sc->vals, h->sc->vals_alt); }  // result is in `keys`
+  if ((passes & 1) == 0) { std::swap(h->lane.scratch->keys, h->lane.scratch->keys_alt); std::swap(h->lane.scratch->vals, h->lane.scratch->vals_alt); }  // result is in `keys`
   return LSGPU_OK;  // sorted: keys_alt / vals_alt
 }
 
@@ -637,7 +635,7 @@ template <class T, class U>
 static int stage_in(lsgpu_icp* h, const U* src, size_t count, DevBuf<T>& buf, const T** out) {
   if (is_device_ptr(src)) { *out = reinterpret_cast<const T*>(src); return LSGPU_OK; }
   HIPC(buf.reserve(count));
-  HIPC(hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->cur));
+  HIPC(hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->lane.stream));
   *out = buf.p;
   return LSGPU_OK;
 }
@@ -668,8 +666,8 @@ static int prepare_queries(lsgpu_icp* h, const float* q_xyz1, int64_t nq, const 
   const float4* src = nullptr;
   int rc = stage_points(h, q_xyz1, nq, h->q_in, &src);
   if (rc) return rc;
-  HIPC(h->sc->keys.reserve(nq));
-  HIPC(h->sc->vals.reserve(nq));
+  HIPC(h->lane.scratch->keys.reserve(nq));
+  HIPC(h->lane.scratch->vals.reserve(nq));
   HIPC(h->rdq.reserve(nq));
   HIPC(h->prev.reserve(nq));
   HIPC(h->lb.reserve(nq));
@@ -677,16 +675,16 @@ static int prepare_queries(lsgpu_icp* h, const float* q_xyz1, int64_t nq, const 
   const int qorder = tuning().query_order;   // -1: automatic
   const float qelev = tuning().q_elev, qsect = tuning().q_sect;   // 0: automatic
   HIPC(h->ang_cells.reserve(kDecCells + 8));
-  HIPC(hipMemsetAsync(h->ang_cells.p, 0, (kDecCells + 8) * sizeof(uint32_t), h->cur));
-  if (qorder != 0) hipLaunchKernelGGL(k_query_ang_hist, dim3(nblk(nq)), dim3(256), 0, h->cur, src, nq, h->ang_cells.p);
-  hipLaunchKernelGGL(k_query_order, dim3(1), dim3(1024), 0, h->cur, h->ang_cells.p, qorder, qelev, qsect);
-  hipLaunchKernelGGL(k_query_keys, dim3(nblk(nq)), dim3(256), 0, h->cur, src, nq, h->sc->keys.p, h->sc->vals.p,
+  HIPC(hipMemsetAsync(h->ang_cells.p, 0, (kDecCells + 8) * sizeof(uint32_t), h->lane.stream));
+  if (qorder != 0) hipLaunchKernelGGL(k_query_ang_hist, dim3(nblk(nq)), dim3(256), 0, h->lane.stream, src, nq, h->ang_cells.p);
+  hipLaunchKernelGGL(k_query_order, dim3(1), dim3(1024), 0, h->lane.stream, h->ang_cells.p, qorder, qelev, qsect);
+  hipLaunchKernelGGL(k_query_keys, dim3(nblk(nq)), dim3(256), 0, h->lane.stream, src, nq, h->lane.scratch->keys.p, h->lane.scratch->vals.p,
                      h->ang_cells.p + kDecCells + 2);
   rc = sort_pairs(h, nq, 48);
   if (rc) return rc;
   if (gather) {
-    hipLaunchKernelGGL(k_query_gather, dim3(nblk(nq)), dim3(256), 0, h->cur, src, nq,
-                       h->sc->vals_alt.p, T, h->rdq.p);
+    hipLaunchKernelGGL(k_query_gather, dim3(nblk(nq)), dim3(256), 0, h->lane.stream, src, nq,
+                       h->lane.scratch->vals_alt.p, T, h->rdq.p);
     HIPC(hipGetLastError());
   }
   h->nq = nq;
@@ -695,7 +693,7 @@ static int prepare_queries(lsgpu_icp* h, const float* q_xyz1, int64_t nq, const 
     const bool grow = nt > h->cell_tags.cap;
     HIPC(h->cell_cache.reserve(nt * 64));
     HIPC(h->cell_tags.reserve(nt));
-    if (grow) HIPC(hipMemsetAsync(h->cell_tags.p, 0, h->cell_tags.cap * sizeof(ulonglong2), h->cur));
+    if (grow) HIPC(hipMemsetAsync(h->cell_tags.p, 0, h->cell_tags.cap * sizeof(ulonglong2), h->lane.stream));
     if (++h->cache_gen == 0) h->cache_gen = 1;
   }
   h->dbg_launch_no = 0;
@@ -1013,19 +1011,19 @@ static int build_cone_index(lsgpu_icp* h) {
   HIPC(h->cone_soa.reserve((size_t)kConeGF4 * npad));
   HIPC(h->cone_map.reserve(npad));
   HIPC(h->cone_tab.reserve(nkeys + 1)); HIPC(h->cone_rowz.reserve((size_t)c.rows));
-  HIPC(h->sc->keys.reserve(nr)); HIPC(h->sc->vals.reserve(nr));
+  HIPC(h->lane.scratch->keys.reserve(nr)); HIPC(h->lane.scratch->vals.reserve(nr));
   c.soa = reinterpret_cast<const float4*>(h->cone_soa.p); c.map = h->cone_map.p; c.tab = h->cone_tab.p; c.rowz = h->cone_rowz.p;
-  hipLaunchKernelGGL(k_cone_keys, dim3(nblk(nr)), dim3(256), 0, h->cur, h->pts.p, nr, c,
-                     h->sc->keys.p, h->sc->vals.p);
+  hipLaunchKernelGGL(k_cone_keys, dim3(nblk(nr)), dim3(256), 0, h->lane.stream, h->pts.p, nr, c,
+                     h->lane.scratch->keys.p, h->lane.scratch->vals.p);
   int nbits = 1;
   while (((size_t)1 << nbits) < nkeys) ++nbits;
   const int rc = sort_pairs(h, nr, nbits);
   if (rc) return rc;
   HIPC(h->cone_occ.reserve(1));
-  HIPC(hipMemsetAsync(h->cone_occ.p, 0, sizeof(uint32_t), h->cur));
-  hipLaunchKernelGGL(k_cone_gather, dim3(nblk((int64_t)npad)), dim3(256), 0, h->cur, h->pts.p, h->sc->vals_alt.p,
-                     h->sc->keys_alt.p, nr, c, h->cone_soa.p, h->cone_map.p, h->cone_tab.p);
-  hipLaunchKernelGGL(k_cone_rows, dim3(c.rows), dim3(256), 0, h->cur, c, h->cone_rowz.p, h->cone_occ.p);
+  HIPC(hipMemsetAsync(h->cone_occ.p, 0, sizeof(uint32_t), h->lane.stream));
+  hipLaunchKernelGGL(k_cone_gather, dim3(nblk((int64_t)npad)), dim3(256), 0, h->lane.stream, h->pts.p, h->lane.scratch->vals_alt.p,
+                     h->lane.scratch->keys_alt.p, nr, c, h->cone_soa.p, h->cone_map.p, h->cone_tab.p);
+  hipLaunchKernelGGL(k_cone_rows, dim3(c.rows), dim3(256), 0, h->lane.stream, c, h->cone_rowz.p, h->cone_occ.p);
   HIPC(hipGetLastError());
   // the number of occupied bins travels to the host behind the build; lsgpu_icp_align looks at it before its first
   // search through the index (the device is busy with the first two iterations by then)
@@ -1036,8 +1034,8 @@ static int build_cone_index(lsgpu_icp* h) {
   else if (hipEventSynchronize(h->cone_occ_ready) != hipSuccess) (void)hipGetLastError();
   uint32_t* ho = h->h_cone_occ;
   *ho = 0u;
-  HIPC(hipMemcpyAsync(ho, h->cone_occ.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->cur));
-  HIPC(hipEventRecord(h->cone_occ_ready, h->cur));
+  HIPC(hipMemcpyAsync(ho, h->cone_occ.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->lane.stream));
+  HIPC(hipEventRecord(h->cone_occ_ready, h->lane.stream));
   h->cone = c;
   h->cone_ok = true;
   h->cone_decided = false;
@@ -1051,21 +1049,17 @@ static uint32_t trim_rank(int64_t n, float ratio) {
   return (uint32_t)k;
 }
 
-extern "C" {
+// What the callers inside this file know about the align they start and its C signature does not carry: the queries are
+// ordered and moved already, on the side lane (the loop's stream waits for side_done); h->rd_nrm holds the normals of this
+// very reading; the direction index's build goes to the side lane behind the first iteration.
+struct AlignExtras { bool queries_prepared, reading_normals, build_index_on_side; };
+static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16], float T_out[16], lsgpu_icp_stats* stats, AlignExtras extras);
 
-int lsgpu_icp_get_reference_mean(lsgpu_icp* h, float mean[3]) {
-  if (!h || !mean) return LSGPU_BAD_ARG;
-  if (h->nr <= 0) return LSGPU_BAD_ARG;
-  std::memcpy(mean, h->mean, 3 * sizeof(float));
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* ref_normals,
-                            int64_t nr) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!ref_xyz1 || nr <= 0 || nr > 0x7FFFFFF0ll) { h->err = "set_reference: empty or oversize cloud"; h->nr = 0; return LSGPU_BAD_ARG; }
-  HIPC(hipSetDevice(h->device));
+// The reference's grid (steps 2-3) in two halves around its one host round trip; lsgpu_icp_compute enqueues the reading's
+// side between and behind them.  First half: staging, stats and geometry, keys, sort, gather, chunks, cell counts -> host.
+// Second half, behind the wait for those counts: table sizes, chunk bounds and boxes, the SoA copy, the cell tables -- the
+// handle has its grid then; the direction index is build_cone_index's, called by whoever wants it built now.
+static int ref_build_front(lsgpu_icp* h, const float* ref_xyz1, const float* ref_normals, int64_t nr) {
   h->nr = 0;
   h->have_normals = ref_normals != nullptr;
   const float4* src = nullptr;
@@ -1083,26 +1077,24 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
                      h->stat_partials.p + kStatBlocks, nr, h->cfg.cell_size, h->geom.p);
   // ---- keys, sort, gather: 16 key bits per axis in total (`bits` address level-0 cells, `fine` order points inside
   // a cell; the split is chosen by k_ref_stats_final), i.e. always 48 key bits
-  HIPC(h->sc->keys.reserve(nr)); HIPC(h->sc->vals.reserve(nr));
+  HIPC(h->lane.scratch->keys.reserve(nr)); HIPC(h->lane.scratch->vals.reserve(nr));
   HIPC(h->pts.reserve(nr + 8)); HIPC(h->nrm.reserve(nr)); HIPC(h->ref_inv.reserve(nr));
-  hipLaunchKernelGGL(k_ref_keys, dim3(nblk(nr)), dim3(256), 0, h->stream, src, nr, h->geom.p, h->sc->keys.p, h->sc->vals.p);
+  hipLaunchKernelGGL(k_ref_keys, dim3(nblk(nr)), dim3(256), 0, h->stream, src, nr, h->geom.p, h->lane.scratch->keys.p, h->lane.scratch->vals.p);
   rc = sort_pairs(h, nr, 48);
   if (rc) return rc;
   hipLaunchKernelGGL(k_ref_gather, dim3(nblk(nr + 8)), dim3(256), 0, h->stream, src, nsrc, nr,
-                     h->sc->vals_alt.p, h->geom.p, h->pts.p, h->nrm.p, h->ref_inv.p);
+                     h->lane.scratch->vals_alt.p, h->geom.p, h->pts.p, h->nrm.p, h->ref_inv.p);
   // ---- chunks: flags -> inclusive scan -> bounds
   HIPC(h->flags.reserve(nr)); HIPC(h->cidx.reserve(nr));
-  hipLaunchKernelGGL(k_chunk_flags, dim3(nblk(nr)), dim3(256), 0, h->stream, h->sc->keys_alt.p, nr, h->geom.p,
+  hipLaunchKernelGGL(k_chunk_flags, dim3(nblk(nr)), dim3(256), 0, h->stream, h->lane.scratch->keys_alt.p, nr, h->geom.p,
                      h->flags.p);
   rc = scan_u32(h, h->flags.p, h->cidx.p, (size_t)nr, /*inclusive*/ true);
   if (rc) return rc;
   // ---- cell counts per level (+ chunk count, + the geometry) -> host, to size the tables
   HIPC(h->counters.reserve(64));
   HIPC(hipMemsetAsync(h->counters.p, 0, 64 * sizeof(uint32_t), h->stream));
-  hipLaunchKernelGGL(k_cells_count, dim3(std::min(512, nblk(nr))), dim3(256), 0, h->stream, h->sc->keys_alt.p, nr, h->geom.p,
+  hipLaunchKernelGGL(k_cells_count, dim3(std::min(512, nblk(nr))), dim3(256), 0, h->stream, h->lane.scratch->keys_alt.p, nr, h->geom.p,
                      h->counters.p);
-  const uint32_t* hc = h->pin->cells;
-  const GeomDev* hg = &h->pin->geom;
   {
     static_assert(sizeof(GeomDev) % 4 == 0, "copied word by word");
     ToHost c{}; int used = 0;
@@ -1112,10 +1104,11 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
     hipLaunchKernelGGL(k_to_host, dim3(1), dim3(64), 0, h->stream, c);
     HIPC(hipGetLastError());
   }
-  if (h->hook_before_ref_sync) {   // lsgpu_icp_compute: the reading's side of the work is enqueued on its own stream now
-    rc = h->hook_before_ref_sync();
-    if (rc) return rc;
-  }
+  return LSGPU_OK;
+}
+static int ref_build_back(lsgpu_icp* h, int64_t nr) {
+  const uint32_t* hc = h->pin->cells;
+  const GeomDev* hg = &h->pin->geom;
   HIPC(hipStreamSynchronize(h->stream));
   if (hg->bad) { h->err = "set_reference: non-finite coordinates"; return LSGPU_BAD_ARG; }
   for (int d = 0; d < 3; ++d) h->mean[d] = hg->mean[d];
@@ -1146,7 +1139,7 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   HIPC(h->chunk_groups.reserve((size_t)nchunks / kChunkGroup + 1));
   hipLaunchKernelGGL(k_chunk_cnt4, dim3((nchunks + 255) / 256), dim3(256), 0, h->stream, h->bounds.p, nchunks,
                      h->soa_cnt4.p, (const ChunkDesc*)h->chunks.p, h->chunk_groups.p);
-  rc = scan_u32(h, h->soa_cnt4.p, h->soa_first.p, nchunks);
+  const int rc = scan_u32(h, h->soa_cnt4.p, h->soa_first.p, nchunks);
   if (rc) return rc;
   hipLaunchKernelGGL(k_soa_fill, dim3((nchunks + 3) / 4), dim3(256), 0, h->stream, h->pts.p, h->bounds.p,
                      h->soa_first.p, nchunks, h->soa.p, h->soa_base.p);
@@ -1160,26 +1153,16 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   }
   if (getenv("LSGPU_CELLS_SPLIT")) {   // (dev: one launch per level, to time them)
     for (int l = 0; l <= bits; ++l)
-      hipLaunchKernelGGL(k_cells_fill, dim3((nchunks + 255) / 256, 1), dim3(256), 0, h->stream, h->sc->keys_alt.p, h->bounds.p, nchunks, fine, bits, ts, l);
+      hipLaunchKernelGGL(k_cells_fill, dim3((nchunks + 255) / 256, 1), dim3(256), 0, h->stream, h->lane.scratch->keys_alt.p, h->bounds.p, nchunks, fine, bits, ts, l);
   } else
-  hipLaunchKernelGGL(k_cells_fill, dim3((nchunks + 255) / 256, bits + 1), dim3(256), 0, h->stream, h->sc->keys_alt.p,
+  hipLaunchKernelGGL(k_cells_fill, dim3((nchunks + 255) / 256, bits + 1), dim3(256), 0, h->stream, h->lane.scratch->keys_alt.p,
                      h->bounds.p, nchunks, fine, bits, ts, 0);
   HIPC(hipGetLastError());  // (no sync: align / knn follow on the same stream)
   h->grid = g;
   h->nr = nr;
   h->nchunks = nchunks;
-  if (h->hook_after_grid) {    // lsgpu_icp_compute: the mean is known and this stream is busy -- now the queries' side
-    rc = h->hook_after_grid();
-    if (rc) return rc;
-  }
-  // ---- direction index for the settled launches (after k_cells_fill: its sort reuses the Morton keys' buffers).
-  // lsgpu_icp_compute builds it on its side stream instead, beside the first iterations of the loop (defer_cone).
-  h->cone_ok = false; h->cone_pending = false; h->cone_build_in_align = false;
+  h->cone_ok = false; h->cone_pending = false;   // (no direction index of this reference yet)
   h->cone_zeta_lo = hg->zeta_lo; h->cone_zeta_hi = hg->zeta_hi; h->cone_origin_inside = hg->origin_inside != 0;
-  if (!h->defer_cone) {
-    rc = build_cone_index(h);
-    if (rc) return rc;
-  }
   std::memset(&h->info, 0, sizeof(h->info));
   h->info.n_reference = nr;
   h->info.bits_per_axis = bits;
@@ -1189,6 +1172,27 @@ int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* re
   for (int l = 0; l <= bits; ++l) h->info.cells[l] = ncell[l];
   h->info.table_bytes = total * sizeof(HashEntry);
   return LSGPU_OK;
+}
+
+extern "C" {
+
+int lsgpu_icp_get_reference_mean(lsgpu_icp* h, float mean[3]) {
+  if (!h || !mean) return LSGPU_BAD_ARG;
+  if (h->nr <= 0) return LSGPU_BAD_ARG;
+  std::memcpy(mean, h->mean, 3 * sizeof(float));
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_set_reference(lsgpu_icp* h, const float* ref_xyz1, const float* ref_normals,
+                            int64_t nr) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!ref_xyz1 || nr <= 0 || nr > 0x7FFFFFF0ll) { h->err = "set_reference: empty or oversize cloud"; h->nr = 0; return LSGPU_BAD_ARG; }
+  HIPC(hipSetDevice(h->device));
+  int rc = ref_build_front(h, ref_xyz1, ref_normals, nr);
+  if (!rc) rc = ref_build_back(h, nr);
+  // the direction index for the settled launches (after k_cells_fill: its sort reuses the Morton keys' buffers)
+  return rc ? rc : build_cone_index(h);
 }
 
 int lsgpu_comm_get_unique_id(void* id) {
@@ -1457,15 +1461,15 @@ static int scan_u32(lsgpu_icp* h, const uint32_t* in, uint32_t* out, size_t n, b
   const int nb = (int)((n + kScanTile - 1) / kScanTile);
   uint32_t* sums = nullptr;
   if (nb > 1) {
-    HIPC(h->sc->sort_tmp.reserve((size_t)nb * sizeof(uint32_t)));
-    sums = reinterpret_cast<uint32_t*>(h->sc->sort_tmp.p);
-    if (nonzero) hipLaunchKernelGGL(k_scan_sums<true>, dim3(nb), dim3(256), 0, h->cur, in, n, sums);
-    else hipLaunchKernelGGL(k_scan_sums<false>, dim3(nb), dim3(256), 0, h->cur, in, n, sums);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, h->cur, sums, nb);
+    HIPC(h->lane.scratch->sort_tmp.reserve((size_t)nb * sizeof(uint32_t)));
+    sums = reinterpret_cast<uint32_t*>(h->lane.scratch->sort_tmp.p);
+    if (nonzero) hipLaunchKernelGGL(k_scan_sums<true>, dim3(nb), dim3(256), 0, h->lane.stream, in, n, sums);
+    else hipLaunchKernelGGL(k_scan_sums<false>, dim3(nb), dim3(256), 0, h->lane.stream, in, n, sums);
+    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, h->lane.stream, sums, nb);
   }
-  if (nonzero) hipLaunchKernelGGL((k_scan_write<false, true>), dim3(nb), dim3(256), 0, h->cur, in, out, n, (const uint32_t*)sums);   // (exclusive: the one use)
-  else if (inclusive) hipLaunchKernelGGL((k_scan_write<true, false>), dim3(nb), dim3(256), 0, h->cur, in, out, n, (const uint32_t*)sums);
-  else hipLaunchKernelGGL((k_scan_write<false, false>), dim3(nb), dim3(256), 0, h->cur, in, out, n, (const uint32_t*)sums);
+  if (nonzero) hipLaunchKernelGGL((k_scan_write<false, true>), dim3(nb), dim3(256), 0, h->lane.stream, in, out, n, (const uint32_t*)sums);   // (exclusive: the one use)
+  else if (inclusive) hipLaunchKernelGGL((k_scan_write<true, false>), dim3(nb), dim3(256), 0, h->lane.stream, in, out, n, (const uint32_t*)sums);
+  else hipLaunchKernelGGL((k_scan_write<false, false>), dim3(nb), dim3(256), 0, h->lane.stream, in, out, n, (const uint32_t*)sums);
   HIPC(hipGetLastError());
   return LSGPU_OK;
 }
@@ -1554,17 +1558,17 @@ struct DrawAhead {
     }
     return LSGPU_OK;
   }
-  int ready(size_t upto = ~(size_t)0) {   // the stream the caller enqueues on (h->cur) waits for the draws [0, upto)
+  int ready(size_t upto = ~(size_t)0) {   // the stream the caller enqueues on (h->lane.stream) waits for the draws [0, upto)
     if (kmax && kfirst && upto <= kfirst) {   // the first part has its own event: no need for the rest to exist yet
       while (!first_sent.load(std::memory_order_acquire)) std::this_thread::yield();
       if (upload_err != hipSuccess) { (void)hipGetLastError(); HIPC(upload_err); }
-      HIPC(hipStreamWaitEvent(h->cur, h->draws_first_done, 0));
+      HIPC(hipStreamWaitEvent(h->lane.stream, h->draws_first_done, 0));
       return LSGPU_OK;
     }
     if (worker.joinable()) worker.join();
     if (kmax) {
       if (upload_err != hipSuccess) { (void)hipGetLastError(); HIPC(upload_err); }
-      HIPC(hipStreamWaitEvent(h->cur, h->draws_done, 0));
+      HIPC(hipStreamWaitEvent(h->lane.stream, h->draws_done, 0));
       waited = true;
     }
     return LSGPU_OK;
@@ -1593,7 +1597,7 @@ struct DrawAhead {
 static int scan_totals_enqueue(lsgpu_icp* h, const uint32_t* in_a, const uint32_t* sc_a, size_t na,
                                const uint32_t* in_b, const uint32_t* sc_b, size_t nb,
                                const void* extra_src = nullptr, void* extra_dst = nullptr, size_t extra_bytes = 0) {
-  uint32_t* hp = h->pin->totals[h->side_totals_slot];
+  uint32_t* hp = h->pin->totals[h->lane.totals_row];
   hp[0] = hp[1] = hp[2] = hp[3] = 0;
   ToHost c{}; int used = 0;
   if (in_a) {
@@ -1603,14 +1607,14 @@ static int scan_totals_enqueue(lsgpu_icp* h, const uint32_t* in_a, const uint32_
   to_host_add(&c, &used, in_b + (nb - 1), hp + 2, 4);
   to_host_add(&c, &used, sc_b + (nb - 1), hp + 3, 4);
   if (extra_src) to_host_add(&c, &used, extra_src, extra_dst, extra_bytes);
-  hipLaunchKernelGGL(k_to_host, dim3(1), dim3(64), 0, h->cur, c);
+  hipLaunchKernelGGL(k_to_host, dim3(1), dim3(64), 0, h->lane.stream, c);
   HIPC(hipGetLastError());
   return LSGPU_OK;
 }
 // ... and the host's wait for them (synchronises the current stream)
 static int scan_totals_wait(lsgpu_icp* h, uint32_t* tot_a, uint32_t* tot_b, bool b_flags = false) {
-  const uint32_t* hp = h->pin->totals[h->side_totals_slot];
-  HIPC(hipStreamSynchronize(h->cur));
+  const uint32_t* hp = h->pin->totals[h->lane.totals_row];
+  HIPC(hipStreamSynchronize(h->lane.stream));
   *tot_a = hp[0] + hp[1];
   *tot_b = (b_flags ? (hp[2] ? 1u : 0u) : hp[2]) + hp[3];   // (b_flags: the scanned words are flags, any non-zero word counts 1)
   return LSGPU_OK;
@@ -1627,7 +1631,7 @@ static int scan_totals(lsgpu_icp* h, const uint32_t* in_a, const uint32_t* sc_a,
 static int compact_kept_enqueue(lsgpu_icp* h, const float4* src, int64_t n, float4* dst) {
   const int rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->cur, src, (int)n, h->ssn_keep.p, h->ssn_out_pos.p, dst);
+  hipLaunchKernelGGL(k_compact_points, dim3(nblk(n)), dim3(256), 0, h->lane.stream, src, (int)n, h->ssn_keep.p, h->ssn_out_pos.p, dst);
   HIPC(hipGetLastError());
   return scan_totals_enqueue(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n);
 }
@@ -1655,11 +1659,11 @@ static float host_float_from_order_key(uint32_t k) {
 // the infinities', so a cloud with any NaN or infinity has a bound that is not finite: the verdict is the caller's.
 static int cloud_bounds(lsgpu_icp* h, const float4* src, int64_t n, float lo[3], float hi[3]) {
   HIPC(h->ssn_bb.reserve(8));
-  HIPC(hipMemsetAsync(h->ssn_bb.p, 0xFF, 12, h->cur));
-  HIPC(hipMemsetAsync(h->ssn_bb.p + 3, 0, 12, h->cur));
-  hipLaunchKernelGGL(k_ssn_bounds, dim3(std::min(nblk(n), 256)), dim3(256), 0, h->cur, src, (int)n, h->ssn_bb.p);
-  HIPC(hipMemcpyAsync(h->pin->bounds, h->ssn_bb.p, sizeof h->pin->bounds, hipMemcpyDeviceToHost, h->cur));
-  HIPC(hipStreamSynchronize(h->cur));
+  HIPC(hipMemsetAsync(h->ssn_bb.p, 0xFF, 12, h->lane.stream));
+  HIPC(hipMemsetAsync(h->ssn_bb.p + 3, 0, 12, h->lane.stream));
+  hipLaunchKernelGGL(k_ssn_bounds, dim3(std::min(nblk(n), 256)), dim3(256), 0, h->lane.stream, src, (int)n, h->ssn_bb.p);
+  HIPC(hipMemcpyAsync(h->pin->bounds, h->ssn_bb.p, sizeof h->pin->bounds, hipMemcpyDeviceToHost, h->lane.stream));
+  HIPC(hipStreamSynchronize(h->lane.stream));
   for (int d = 0; d < 3; ++d) { lo[d] = host_float_from_order_key(h->pin->bounds[d]); hi[d] = host_float_from_order_key(h->pin->bounds[3 + d]); }
   return LSGPU_OK;
 }
@@ -1710,8 +1714,8 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
   HIPC(h->ssn_keep.reserve(n));
   HIPC(h->ssn_out_pos.reserve(n));
   HIPC(h->ssn_bb.reserve(8));
-  HIPC(h->sc->keys.reserve(n));
-  HIPC(h->sc->vals.reserve(n));
+  HIPC(h->lane.scratch->keys.reserve(n));
+  HIPC(h->lane.scratch->vals.reserve(n));
   {   // the cloud's bounds and the root segment in one launch (k_ssn_bounds_root: a ticket that is zero between calls)
     const bool fresh = h->ssn_bounds_ws.cap == 0;
     HIPC(h->ssn_bounds_ws.reserve(8 + 6 * kSsnBoundsBlocks));
@@ -1846,14 +1850,14 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
     // (uint32 key, uint32 index) pairs, every segment inside its own range of the arrays
     const size_t nseg_g = (size_t)1 << glevels;
     const int cap = (int)(n / kSegTile + (int64_t)(nseg_g / 2) + 2);
-    HIPC(h->sc->vals_alt.reserve(n));
+    HIPC(h->lane.scratch->vals_alt.reserve(n));
     HIPC(h->ssn_axis_a.reserve(nseg_g)); HIPC(h->ssn_axis_b.reserve(nseg_g)); HIPC(h->ssn_seg_fb.reserve(nseg_g));
-    HIPC(h->ssn_blocktab.reserve((size_t)cap)); HIPC(h->sc->sort_hist.reserve((size_t)256 * cap + 256 + 4));
-    uint32_t* keyA = reinterpret_cast<uint32_t*>(h->sc->keys.p);
+    HIPC(h->ssn_blocktab.reserve((size_t)cap)); HIPC(h->lane.scratch->sort_hist.reserve((size_t)256 * cap + 256 + 4));
+    uint32_t* keyA = reinterpret_cast<uint32_t*>(h->lane.scratch->keys.p);
     uint32_t* keyB = keyA + n;
-    uint32_t* valA = h->sc->vals.p;
-    uint32_t* valB = h->sc->vals_alt.p;
-    uint32_t* bh = h->sc->sort_hist.p;
+    uint32_t* valA = h->lane.scratch->vals.p;
+    uint32_t* valB = h->lane.scratch->vals_alt.p;
+    uint32_t* bh = h->lane.scratch->sort_hist.p;
     uint32_t* dtot = bh + (size_t)256 * cap;
     uint32_t* nblocks_dev = dtot + 256;
     int* ax_cur = h->ssn_axis_a.p;
@@ -1886,8 +1890,8 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
   if (glevels < levels) {
     if (glevels == 0) {  // the whole cloud fits one workgroup: identity order to start from
       hipLaunchKernelGGL(k_ssn_keys, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, cur, knn, h->sc->keys.p, h->sc->vals.p);
-      idx = h->sc->vals.p;
+                         (const uint32_t*)nullptr, cur, knn, h->lane.scratch->keys.p, h->lane.scratch->vals.p);
+      idx = h->lane.scratch->vals.p;
     }
     uint32_t* idx_rw = const_cast<uint32_t*>(idx);
     if (root_max == 8192)
@@ -1900,9 +1904,9 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
   }
   if (levels == 0) {  // a single box: identity order
     hipLaunchKernelGGL(k_ssn_keys, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr, cur, knn, h->sc->keys.p, h->sc->vals.p);
+                       (const uint32_t*)nullptr, cur, knn, h->lane.scratch->keys.p, h->lane.scratch->vals.p);
     HIPC(hipMemsetAsync(h->ssn_seg_of.p, 0, (size_t)n * 4, h->stream));
-    idx = h->sc->vals.p;
+    idx = h->lane.scratch->vals.p;
   }
   hipLaunchKernelGGL(k_ssn_boxes, dim3((int)((nseg + 127) / 128)), dim3(128), 0, h->stream, src, idx, cur, (int)nseg,
                      h->ssn_box_normal.p, h->ssn_box_pts.p);
@@ -1958,7 +1962,7 @@ static int random_sampling_device(lsgpu_icp* h, const float4* src, int64_t n, fl
   ahead->used = first_draw + (size_t)n;  // one draw per point, whatever happens next
   rc = ahead->ready();
   if (rc) return rc;
-  hipLaunchKernelGGL(k_draw_select, dim3(nblk(n)), dim3(256), 0, h->cur, (int)n, h->ssn_draws.p + first_draw, prob, h->ssn_keep.p);
+  hipLaunchKernelGGL(k_draw_select, dim3(nblk(n)), dim3(256), 0, h->lane.stream, (int)n, h->ssn_draws.p + first_draw, prob, h->ssn_keep.p);
   rc = compact_kept_enqueue(h, src, n, out_xyz1);
   if (rc || defer_wait) return rc;
   return compact_kept_wait(h, n_out);
@@ -2078,7 +2082,6 @@ int lsgpu_icp_reading_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int kn
   if (!rc) rc = lsgpu_icp_filter_reference_normals(tmp, xyz1, n, knn, on, nullptr, nullptr);
   if (!rc && orient) {
     const float4* src = nullptr;
-    tmp->cur = tmp->stream;
     rc = stage_points(tmp, xyz1, n, tmp->flt_in, &src);
     if (!rc) {
       hipLaunchKernelGGL(k_orient_normals, dim3(nblk(n)), dim3(256), 0, tmp->stream, src, (const float4*)nullptr, (int)n,
@@ -2096,15 +2099,15 @@ int lsgpu_icp_reading_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int kn
 int lsgpu_icp_align_normals(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reading_normals,
                             const float T_init[16], float T_out[16], lsgpu_icp_stats* stats) {
   if (!h) return LSGPU_BAD_ARG;
-  h->rd_nrm_for = nullptr; h->rd_nrm_n = 0;
+  AlignExtras extras{};
   if (reading_normals && reading_xyz1 && nq > 0 && nq <= 0x7FFFFFF0ll) {
     HIPC(hipSetDevice(h->device));
     HIPC(h->rd_nrm.reserve((size_t)3 * nq));
     HIPC(hipMemcpyAsync(h->rd_nrm.p, reading_normals, (size_t)nq * 12,
                         is_device_ptr(reading_normals) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    h->rd_nrm_for = reading_xyz1; h->rd_nrm_n = nq;
+    extras.reading_normals = true;
   }
-  return lsgpu_icp_align(h, reading_xyz1, nq, T_init, T_out, stats);
+  return align_run(h, reading_xyz1, nq, T_init, T_out, stats, extras);
 }
 
 int lsgpu_icp_get_reference_normals(lsgpu_icp* h, float* out_normals, int64_t cap_points) {
@@ -2128,60 +2131,82 @@ static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain) {
   return lsgpu_chain_config_check(chain, h->cfg.error_minimizer) == LSGPU_OK;
 }
 
-int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1,
-                      int64_t nr, const float T_init[16], const lsgpu_chain_config* chain,
-                      float T_out[16], lsgpu_icp_stats* stats) {
-  if (!h || !T_init || !T_out || !chain) return LSGPU_BAD_ARG;
-  h->err.clear();
-  std::memcpy(T_out, T_init, 16 * sizeof(float));
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (!chain_ok(h, chain)) {
-    h->err = "compute: one reference filter, ssn_knn or sn_knn in [3, 32] (none only with the point-to-point minimizer)";
-    return LSGPU_BAD_CONFIG;
+}  // extern "C"
+
+// One call of lsgpu_icp_compute: what its phases share, and the phases in the order they run -- check, start_uploads,
+// filter_reference, the reading's side in one of its three places (reading_on_side_lane in front of the grid build,
+// reading_with_normals before the reference takes the grid, reading_filter after it), build_reference, finish.
+struct ComputeRun {
+  lsgpu_icp* const h;
+  const float* const reading_xyz1; const int64_t nq; const float* const reference_xyz1; const int64_t nr;   // the call's arguments
+  const float* const T_init; const lsgpu_chain_config* const chain;
+  // lsgpu_icp_compute_clouds_upload: the reading's H2D goes into its slot instead of the staging buffer, and the caller
+  // learns whether it went out (it reads the flag after the return: the uploader is joined by then)
+  float4* const upload_into; bool* const upload_enqueued;
+  bool ref_filter = false, ref_normals = false, rd_normals = false, side = false;   // what the chain and the handle ask for
+  const lsgpu_normals_config* nc = nullptr; double t0 = 0.0;
+  DrawAhead draws; std::thread uploader; hipError_t upload_err = hipSuccess;
+  bool overlap_upload = false, side_used = false;   // the copy stream / the side stream has work of this call
+  const float4 *src = nullptr, *ref_pts = nullptr; const float* ref_nrm = nullptr;   // the reference on the device: as given, as the grid gets it
+  const float4 *rd_src = nullptr, *rd_dev = nullptr; int64_t nrf = 0, nqf = 0;       // the reading: as given, as the loop gets it; points kept
+  AlignExtras extras{};   // what finish() tells the align
+  // every return path drains the side stream, joins the uploader and drains its stream: a pinned host reading is read by DMA,
+  // and the caller may free or reuse it as soon as this call has returned, error or not (after a completed alignment the
+  // copy is long over and the wait returns at once)
+  ~ComputeRun() {
+    if (side_used && h->side_stream) (void)hipStreamSynchronize(h->side_stream);
+    if (uploader.joinable()) uploader.join();
+    if (overlap_upload && h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
   }
-  const bool ref_filter = chain->ssn_knn != 0;
-  // SurfaceNormalDataPointsFilter keeps every point and draws nothing: the reference goes to set_reference as given and
-  // the normals are computed on the grid it builds (a point-to-point handle reads none: skipped)
-  const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;   // (its residuals need the normals)
-  // lsgpu_icp_set_normals: the angle filter reads the reference normals whatever the minimizer; the reading's normals are
-  // computed on the handle's grid BEFORE the reference takes it (rd_normals), which rules the side stream out
-  const lsgpu_normals_config* nc = h->normals_on ? &h->normals : nullptr;
-  const bool na_filter = nc && nc->max_angle >= 0.f;
-  const bool rd_normals = nc && nc->reading_sn_knn > 0;
-  if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0) {
-    h->err = "compute: SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter need the normals of a reference filter";
-    return LSGPU_BAD_CONFIG;
+
+  int check() {
+    if (!chain_ok(h, chain)) {
+      h->err = "compute: one reference filter, ssn_knn or sn_knn in [3, 32] (none only with the point-to-point minimizer)";
+      return LSGPU_BAD_CONFIG;
+    }
+    ref_filter = chain->ssn_knn != 0;
+    // SurfaceNormalDataPointsFilter keeps every point and draws nothing: the reference goes to the grid build as given and
+    // the normals are computed on the grid it builds (a point-to-point handle reads none: skipped)
+    const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;   // (its residuals need the normals)
+    // lsgpu_icp_set_normals: the angle filter reads the reference normals whatever the minimizer; the reading's normals are
+    // computed on the handle's grid BEFORE the reference takes it (rd_normals), which rules the side stream out
+    nc = h->normals_on ? &h->normals : nullptr;
+    const bool na_filter = nc && nc->max_angle >= 0.f;
+    rd_normals = nc && nc->reading_sn_knn > 0;
+    if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0) {
+      h->err = "compute: SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter need the normals of a reference filter";
+      return LSGPU_BAD_CONFIG;
+    }
+    ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter);
+    if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
+    if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
+    if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
+    if (nr < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
+    HIPC(hipSetDevice(h->device));
+    t0 = wall_ms();
+    // steps 2-4.  The grid build (steps 2-3, h->stream) and the reading's side -- its filter (step 4) and the queries' order
+    // (the first part of step 5) -- do not depend on each other: the latter goes to a second stream with its own sort scratch.
+    // Both are chains of short launches that leave most of the chip idle; side by side the shorter one disappears
+    // (LSGPU_NO_SIDE_STREAM: one after the other).
+    side = tuning().side_stream && !h->comm && !rd_normals;
+    return LSGPU_OK;
   }
-  const bool ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter);
-  if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
-  if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
-  if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
-  if (nr < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
-  HIPC(hipSetDevice(h->device));
-  const double t0 = wall_ms();
-  // the draws of both filters, produced on a helper thread from now on: at most one per reference point, then one per
-  // reading point
-  DrawAhead draws;
-  {
+
+  int start_uploads() {
+    // the draws of both filters, produced on a helper thread from now on: at most one per reference point, then one per reading point
     const size_t ref_draws = ref_filter ? (size_t)nr : (size_t)0;
-    const int rc0 = draws.begin(h, -1, ref_draws + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq), ref_draws);   // (the reference filter's share first)
-    if (rc0) return rc0;
-  }
-  // step 1: reference filter (yaml:5-7)
-  const float4* src = nullptr;
-  int rc = stage_points(h, reference_xyz1, nr, h->flt_in, &src);
-  if (rc) return rc;
-  // A reading handed over in HOST memory crosses PCIe while the reference is being filtered: its own stream, and its own
-  // host thread, because a copy from pageable memory keeps the calling thread until the last chunk is staged
-  // (SURVEY.md §8d counts H2D in scans/s).  The loop's stream waits for it right before the reading filter.
-  std::thread uploader;
-  hipError_t upload_err = hipSuccess;
-  const bool overlap_upload = !is_device_ptr(reading_xyz1);
-  if (overlap_upload) {
+    int rc = draws.begin(h, -1, ref_draws + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq), ref_draws);   // (the reference filter's share first)
+    if (!rc) rc = stage_points(h, reference_xyz1, nr, h->flt_in, &src);   // (step 1 starts here)
+    if (rc) return rc;
+    if (is_device_ptr(reading_xyz1)) { rd_src = reinterpret_cast<const float4*>(reading_xyz1); return LSGPU_OK; }
+    // A reading handed over in HOST memory crosses PCIe while the reference is being filtered: its own stream, and its own
+    // host thread, because a copy from pageable memory keeps the calling thread until the last chunk is staged
+    // (SURVEY.md §8d counts H2D in scans/s).  The loop's stream waits for it right before the reading filter.
     if (!h->copy_stream) HIPC(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     if (!h->copy_done) HIPC(hipEventCreateWithFlags(&h->copy_done, hipEventDisableTiming));
-    float4* up_dst = h->upload_into;     // (a cloud slot: lsgpu_icp_compute_clouds_upload)
+    float4* up_dst = upload_into;
     if (!up_dst) { HIPC(h->flt_in2.reserve(nq)); up_dst = h->flt_in2.p; }
+    overlap_upload = true; rd_src = up_dst;
     order_after_tail(h, h->copy_stream);
     // the reference's own upload goes first: it is in front of everything, the reading is not needed before the reading
     // filter, and two copies at once share the link (from pinned buffers they did: the pinned path was the slower one)
@@ -2190,64 +2215,39 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
       HIPC(hipEventRecord(h->ref_up_done, h->stream));
       HIPC(hipStreamWaitEvent(h->copy_stream, h->ref_up_done, 0));
     }
-    auto upload = [&, up_dst] {
+    auto upload = [this, up_dst] {
       hipError_t e = hipSetDevice(h->device);
       if (e == hipSuccess) e = hipMemcpyAsync(up_dst, reading_xyz1, (size_t)nq * 16, hipMemcpyHostToDevice, h->copy_stream);
       if (e == hipSuccess) e = hipEventRecord(h->copy_done, h->copy_stream);
       upload_err = e;
-      if (e == hipSuccess) h->upload_done = true;
+      if (e == hipSuccess && upload_enqueued) *upload_enqueued = true;
     };
-    try {
-      uploader = std::thread(upload);
-    } catch (const std::system_error&) {   // no thread to be had: copy here (no overlap)
-      upload();
-    }
+    try { uploader = std::thread(upload); }
+    catch (const std::system_error&) { upload(); }   // no thread to be had: copy here (no overlap)
+    return LSGPU_OK;
   }
-  // every return path joins the uploader and drains its stream: a pinned host reading is read by DMA, and the caller
-  // may free or reuse it as soon as this call has returned, error or not (after a completed alignment the copy is long
-  // over and the wait returns at once)
-  struct Joiner {
-    std::thread& t; lsgpu_icp* h; bool started;
-    ~Joiner() {
-      if (t.joinable()) t.join();
-      if (started && h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+
+  int filter_reference() {   // step 1: reference filter (yaml:5-7)
+    ref_pts = src; nrf = nr;   // (no reference filter module: the reference as given, no normals, no draw)
+    if (ref_filter) {
+      HIPC(h->flt_ref.reserve(nr)); HIPC(h->flt_nrm.reserve(3 * nr));
+      const int rc = ssn_device(h, src, nr, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
+      if (rc) return rc;
+      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+      ref_pts = h->flt_ref.p; ref_nrm = h->flt_nrm.p;
     }
-  } joiner{uploader, h, overlap_upload};
-  int64_t nrf = 0, nqf = 0;
-  const float4* ref_pts = src;          // (no reference filter module: the reference as given, no normals, no draw)
-  const float* ref_nrm = nullptr;
-  if (ref_filter) {
-    HIPC(h->flt_ref.reserve(nr));
-    HIPC(h->flt_nrm.reserve(3 * nr));
-    rc = ssn_device(h, src, nr, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
-    if (rc) return rc;
-    if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
-    ref_pts = h->flt_ref.p; ref_nrm = h->flt_nrm.p;
-  } else {
-    nrf = nr;
+    // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
+    draws.commit_now(draws.used + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq));
+    return LSGPU_OK;
   }
-  // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
-  draws.commit_now(draws.used + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq));
-  // steps 2-4.  The grid build (steps 2-3, h->stream) and the reading's side -- its filter (step 4) and the ordering of
-  // the queries (the first part of step 5) -- do not depend on each other: the latter is enqueued on a second stream,
-  // with its own sort scratch, from inside set_reference (right before its one host round trip), and the queries are
-  // moved into the reference's frame as soon as set_reference knows the mean.  Both are chains of short launches that
-  // leave most of the chip idle; side by side the shorter one disappears (LSGPU_NO_SIDE_STREAM: one after the other).
-  const bool side = tuning().side_stream && !h->comm && !rd_normals;
-  const float4* rd_src = nullptr;
-  const float4* rd_dev = nullptr;
-  auto reading_ready = [&](hipStream_t on) -> int {   // the reading's upload, if it is ours, has to be there
+
+  // step 4, on the current lane: the reading's upload, if it is ours, has to be there; then the reading filter (yaml:1-3)
+  int reading_filter(bool defer_wait) {
     if (overlap_upload) {
       if (uploader.joinable()) uploader.join();
       if (upload_err != hipSuccess) { h->err = std::string("compute: reading upload: ") + hipGetErrorString(upload_err); (void)hipGetLastError(); return LSGPU_HIP_ERROR; }
-      HIPC(hipStreamWaitEvent(on, h->copy_done, 0));
-      rd_src = h->upload_into ? h->upload_into : h->flt_in2.p;
-    } else {
-      rd_src = reinterpret_cast<const float4*>(reading_xyz1);
+      HIPC(hipStreamWaitEvent(h->lane.stream, h->copy_done, 0));
     }
-    return LSGPU_OK;
-  };
-  auto reading_filter = [&](bool defer_wait) -> int {   // step 4: reading filter (yaml:1-3), on h->cur
     rd_dev = rd_src;
     if (chain->reading_prob < 0.f) {
       // no readingDataPointsFilters section: upstream runs no module at all -- every point, NO rand() call (a
@@ -2256,74 +2256,59 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
       return LSGPU_OK;
     }
     HIPC(h->flt_rd.reserve(nq));
-    const int r = random_sampling_device(h, rd_src, nq, chain->reading_prob, -1, h->flt_rd.p, &nqf, &draws, defer_wait);
     rd_dev = h->flt_rd.p;
-    return r;
-  };
-  struct SideGuard {   // whatever happens, the helpers go back to the main stream and the side stream is drained
-    lsgpu_icp* h; bool used = false;
-    void enter() { used = true; h->cur = h->side_stream; h->sc = &h->scr_side; h->side_totals_slot = 1; }
-    void leave() { h->cur = h->stream; h->sc = &h->scr_main; h->side_totals_slot = 0; }
-    ~SideGuard() {
-      leave();
-      h->hook_before_ref_sync = nullptr; h->hook_after_grid = nullptr;
-      if (used && h->side_stream) (void)hipStreamSynchronize(h->side_stream);
-    }
-  } side_guard{h};
-  bool side_prepared = false;
-  if (side) {
+    return random_sampling_device(h, rd_src, nq, chain->reading_prob, -1, h->flt_rd.p, &nqf, &draws, defer_wait);
+  }
+
+  // The reading's side with the side stream on.  Order of the host's work (round 5, from rocprofv3's timeline of a step).
+  // The host thread that enqueues both chains is the scarce resource here (~4 us per launch), and what it waits for decides
+  // what idles:
+  //   1. the reading's filter goes out NOW, in front of the whole grid build (it only needs the draws and the upload);
+  //   2. the ordering of the queries (~25 launches) goes out while the first half of the grid build runs, right before
+  //      the host waits for the grid's cell counts -- the number of reading points kept is long there;
+  //   3. the second half of the grid build goes out right behind that wait;
+  //   4. the move of the queries into the reference's frame (it needs the mean) behind it.
+  // Before, the host enqueued the reading's whole side -- a wait and ~60 launches -- between the grid's two halves: the
+  // loop's stream sat idle for 0.3 ms behind the cell counts, then the loop waited for the queries.
+  // (1 is reading_on_side_lane; build_reference does 2 to 4: order_queries_on_side_lane, ref_build_back, move_queries.)
+  int reading_on_side_lane() {
     // (Tried: this stream at the lowest stream priority, so that the loop's short kernels never wait for a compute unit behind
     // the direction index's build.  Measured slower, 5.27 -> 5.41..5.60 ms per compute from host buffers, level from resident
     // ones: the reading's filter and query order run here too and ARE on the critical path.)
     if (!h->side_stream) HIPC(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
     if (!h->side_done) HIPC(hipEventCreateWithFlags(&h->side_done, hipEventDisableTiming));
-    order_after_tail(h, h->side_stream);
-    // Order of the host's work (round 5, from rocprofv3's timeline of a step).  The host thread that enqueues both chains
-    // is the scarce resource here (~4 us per launch), and what it waits for decides what idles:
-    //   1. the reading's filter goes out NOW, in front of the whole grid build (it only needs the draws and the upload);
-    //   2. the ordering of the queries (~25 launches) goes out while the first half of the grid build runs, right before
-    //      set_reference waits for its cell counts -- the number of reading points kept is long there;
-    //   3. the second half of the grid build goes out right behind that wait;
-    //   4. the move of the queries into the reference's frame (it needs the mean) behind it.
-    // Before, the host enqueued the reading's whole side -- a wait and ~60 launches -- between the grid's two halves: the
-    // loop's stream sat idle for 0.3 ms behind the cell counts, then the loop waited for the queries.
-    side_guard.enter();
-    rc = reading_ready(h->side_stream);
-    if (!rc) rc = reading_filter(/*defer_wait*/ true);
-    side_guard.leave();
-    if (rc) return rc;
-    h->hook_before_ref_sync = [&]() -> int {
-      side_guard.enter();
-      int r = LSGPU_OK;
-      if (chain->reading_prob >= 0.f) r = compact_kept_wait(h, &nqf);   // (the number of points kept)
-      if (!r && nqf > 0) r = prepare_queries(h, reinterpret_cast<const float*>(rd_dev), nqf, Mat34{}, /*gather*/ false);
-      side_guard.leave();
-      return r;
-    };
-    h->hook_after_grid = [&]() -> int {
-      if (nqf <= 0) return LSGPU_OK;
-      float T_rm_in[16];
-      std::memcpy(T_rm_in, T_init, sizeof(T_rm_in));
-      for (int d = 0; d < 3; ++d) T_rm_in[12 + d] = T_init[12 + d] - h->mean[d];   // (as lsgpu_icp_align, step 5)
-      hipLaunchKernelGGL(k_query_gather, dim3(nblk(nqf)), dim3(256), 0, h->side_stream, rd_dev, nqf, h->scr_side.vals_alt.p,
-                         to_mat34(T_rm_in), h->rdq.p);
-      HIPC(hipGetLastError());
-      HIPC(hipEventRecord(h->side_done, h->side_stream));
-      side_prepared = true;
-      return LSGPU_OK;
-    };
+    order_after_tail(h, h->side_stream); side_used = true;
+    LaneScope on_side(h, h->side_lane());
+    return reading_filter(/*defer_wait*/ true);
   }
-  if (rd_normals) {
-    // the reading's filter, then SurfaceNormalDataPointsFilter on the points it kept: the grid of the kept reading, the
-    // normals on it, copied out in the reading's order -- all before the reference's own set_reference below
-    rc = reading_ready(h->stream);
-    if (!rc) rc = reading_filter(false);
+  int order_queries_on_side_lane() {
+    LaneScope on_side(h, h->side_lane());
+    const int rc = chain->reading_prob >= 0.f ? compact_kept_wait(h, &nqf) : LSGPU_OK;   // (the number of points kept)
+    return rc || nqf <= 0 ? rc : prepare_queries(h, reinterpret_cast<const float*>(rd_dev), nqf, Mat34{}, /*gather*/ false);
+  }
+  int move_queries() {   // the mean is known and the main stream is busy -- now the queries' side
+    if (nqf <= 0) return LSGPU_OK;
+    float T_rm_in[16];
+    std::memcpy(T_rm_in, T_init, sizeof(T_rm_in));
+    for (int d = 0; d < 3; ++d) T_rm_in[12 + d] = T_init[12 + d] - h->mean[d];   // (as the align, step 5)
+    hipLaunchKernelGGL(k_query_gather, dim3(nblk(nqf)), dim3(256), 0, h->side_stream, rd_dev, nqf, h->scr_side.vals_alt.p,
+                       to_mat34(T_rm_in), h->rdq.p);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(h->side_done, h->side_stream));
+    extras.queries_prepared = true;
+    return LSGPU_OK;
+  }
+
+  // The reading's side when its normals are wanted: the reading's filter, then SurfaceNormalDataPointsFilter on the points
+  // it kept -- the grid of the kept reading (no direction index of it), the normals on it, copied out in the reading's
+  // order -- all on the main stream, before the reference's own grid build
+  int reading_with_normals() {
+    int rc = reading_filter(false);
     if (rc) return rc;
     if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
     if (nqf < nc->reading_sn_knn) { h->err = "compute: the kept reading has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
-    h->defer_cone = true;   // (no direction index of the reading)
-    rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(rd_dev), nullptr, nqf);
-    h->defer_cone = false;
+    rc = ref_build_front(h, reinterpret_cast<const float*>(rd_dev), nullptr, nqf);
+    if (!rc) rc = ref_build_back(h, nqf);
     if (!rc) rc = snf_device(h, nc->reading_sn_knn, nullptr, nullptr);
     if (rc) return rc;
     HIPC(h->rd_nrm.reserve((size_t)3 * nqf));
@@ -2332,47 +2317,76 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
       hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nqf)), dim3(256), 0, h->stream, rd_dev, (const float4*)nullptr, (int)nqf,
                          nc->reading_sensor[0], nc->reading_sensor[1], nc->reading_sensor[2], nc->reading_orient, h->rd_nrm.p, (float4*)nullptr);
     HIPC(hipGetLastError());
+    extras.reading_normals = true;
+    return LSGPU_OK;
   }
-  if (nc && nc->reference_orient && ref_nrm)   // the sampling filter's normals, beside its points
-    hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, (const float4*)nullptr, (int)nrf,
-                       nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, h->flt_nrm.p, (float4*)nullptr);
-  h->defer_cone = side;
-  rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(ref_pts), ref_nrm, nrf);
-  h->hook_before_ref_sync = nullptr; h->hook_after_grid = nullptr;
-  h->defer_cone = false;
-  if (rc) return rc;
-  if (ref_normals) {
-    rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
+
+  // steps 2-3: the reference's grid, the queries' side between and behind its halves, and the normals the chain computes on it
+  int build_reference() {
+    if (nc && nc->reference_orient && ref_nrm)   // the sampling filter's normals, beside its points
+      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, (const float4*)nullptr, (int)nrf,
+                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, h->flt_nrm.p, (float4*)nullptr);
+    int rc = ref_build_front(h, reinterpret_cast<const float*>(ref_pts), ref_nrm, nrf);
+    if (!rc && side) rc = order_queries_on_side_lane();
+    if (!rc) rc = ref_build_back(h, nrf);
+    if (!rc && side) rc = move_queries();
+    if (!rc && !side) rc = build_cone_index(h);
+    if (!rc && ref_normals) rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
     if (rc) return rc;
-    h->have_normals = true;
-    if (nc && nc->reference_orient) {   // on the sorted normals; the position is the point as given (ref_pts, by the sorted point's index)
-      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, h->pts.p, (int)nrf,
-                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, (float*)nullptr, h->nrm.p);
-      HIPC(hipGetLastError());
+    if (ref_normals) {
+      h->have_normals = true;
+      if (nc && nc->reference_orient) {   // on the sorted normals; the position is the point as given (ref_pts, by the sorted point's index)
+        hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, h->pts.p, (int)nrf,
+                           nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, (float*)nullptr, h->nrm.p);
+        HIPC(hipGetLastError());
+      }
     }
+    if (side) {
+      // the direction index of the reference is not needed before the loop's third search: the align enqueues its
+      // build on the side stream (behind the queries' order, with that stream's sort scratch) once the loop's first
+      // iteration is out -- beside the first two iterations instead of in front of the loop (0.16 ms per 1 M-point
+      // compute), and without holding the host back from starting the loop (round 5)
+      if (!h->cone_done) HIPC(hipEventCreateWithFlags(&h->cone_done, hipEventDisableTiming));
+      extras.build_index_on_side = true;
+    }
+    return LSGPU_OK;
   }
-  if (side) {
-    // the direction index of the reference is not needed before the loop's third search: lsgpu_icp_align enqueues its
-    // build on the side stream (behind the queries' order, with that stream's sort scratch) once the loop's first
-    // iteration is out -- beside the first two iterations instead of in front of the loop (0.16 ms per 1 M-point
-    // compute), and without holding the host back from starting the loop (round 5)
-    if (!h->cone_done) HIPC(hipEventCreateWithFlags(&h->cone_done, hipEventDisableTiming));
-    h->cone_build_in_align = true;
+
+  int finish(float T_out[16], lsgpu_icp_stats* stats) {   // steps 5-7
+    draws.finish();
+    const double t_filters = wall_ms() - t0;
+    if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
+    const int rc = align_run(h, reinterpret_cast<const float*>(rd_dev), nqf, T_init, T_out, stats, extras);
+    if (stats) stats->t_reserved[0] = t_filters;
+    return rc;
   }
-  if (!side && !rd_normals) {
-    rc = reading_ready(h->stream);
-    if (!rc) rc = reading_filter(false);
-    if (rc) return rc;
-  }
-  draws.finish();
-  const double t_filters = wall_ms() - t0;
-  if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
-  if (side_prepared) { h->prepared_rd = reinterpret_cast<const float*>(rd_dev); h->prepared_nq = nqf; }
-  if (rd_normals) { h->rd_nrm_for = reinterpret_cast<const float*>(rd_dev); h->rd_nrm_n = nqf; }
-  // steps 5-7
-  rc = lsgpu_icp_align(h, reinterpret_cast<const float*>(rd_dev), nqf, T_init, T_out, stats);
-  if (stats) stats->t_reserved[0] = t_filters;
-  return rc;
+};
+
+// lsgpu_icp_compute, told by lsgpu_icp_compute_clouds_upload where the reading's upload goes (nullptr, nullptr otherwise)
+static int compute_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1, int64_t nr,
+                       const float T_init[16], const lsgpu_chain_config* chain, float T_out[16], lsgpu_icp_stats* stats,
+                       float4* upload_into, bool* upload_enqueued) {
+  if (!h || !T_init || !T_out || !chain) return LSGPU_BAD_ARG;
+  h->err.clear();
+  std::memcpy(T_out, T_init, 16 * sizeof(float));
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  ComputeRun run{h, reading_xyz1, nq, reference_xyz1, nr, T_init, chain, upload_into, upload_enqueued};
+  int rc = run.check();
+  if (!rc) rc = run.start_uploads();
+  if (!rc) rc = run.filter_reference();
+  if (!rc && run.side) rc = run.reading_on_side_lane();
+  if (!rc && run.rd_normals) rc = run.reading_with_normals();
+  if (!rc) rc = run.build_reference();
+  if (!rc && !run.side && !run.rd_normals) rc = run.reading_filter(false);   // (the reading's side after the grid build)
+  return rc ? rc : run.finish(T_out, stats);
+}
+
+extern "C" {
+
+int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1,
+                      int64_t nr, const float T_init[16], const lsgpu_chain_config* chain,
+                      float T_out[16], lsgpu_icp_stats* stats) {
+  return compute_run(h, reading_xyz1, nq, reference_xyz1, nr, T_init, chain, T_out, stats, nullptr, nullptr);
 }
 
 int lsgpu_filter_cylinder(lsgpu_icp* h, const float* xyz1, int64_t n, const float center[3], double radius_m,
@@ -2426,18 +2440,18 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
     h->err = "voxel_grid: leaf size too small for the cloud, the voxel index would overflow";
     return LSGPU_BAD_ARG;
   }
-  HIPC(h->sc->keys.reserve(n));
-  HIPC(h->sc->vals.reserve(n));
+  HIPC(h->lane.scratch->keys.reserve(n));
+  HIPC(h->lane.scratch->vals.reserve(n));
   HIPC(h->ssn_keep.reserve(n));
   HIPC(h->ssn_out_pos.reserve(n));
   HIPC(h->ssn_seg_of.reserve(n));   // voxel head flags
   HIPC(h->flt_ref.reserve(n));      // centroids by sorted position
   hipLaunchKernelGGL(k_voxel_keys, dim3(nblk(n)), dim3(256), 0, h->stream, src, (int)n, inv[0], inv[1], inv[2],
-                     minb[0], minb[1], minb[2], divb[0], divb[0] * divb[1], h->sc->keys.p, h->sc->vals.p);
+                     minb[0], minb[1], minb[2], divb[0], divb[0] * divb[1], h->lane.scratch->keys.p, h->lane.scratch->vals.p);
   rc = sort_pairs(h, n, 31);  // stable: equal voxels keep input order
   if (rc) return rc;
-  hipLaunchKernelGGL(k_voxel_heads, dim3(nblk(n)), dim3(256), 0, h->stream, h->sc->keys_alt.p, (int)n, h->ssn_seg_of.p);
-  hipLaunchKernelGGL(k_voxel_centroids, dim3(nblk(n)), dim3(256), 0, h->stream, src, h->sc->keys_alt.p, h->sc->vals_alt.p, (int)n,
+  hipLaunchKernelGGL(k_voxel_heads, dim3(nblk(n)), dim3(256), 0, h->stream, h->lane.scratch->keys_alt.p, (int)n, h->ssn_seg_of.p);
+  hipLaunchKernelGGL(k_voxel_centroids, dim3(nblk(n)), dim3(256), 0, h->stream, src, h->lane.scratch->keys_alt.p, h->lane.scratch->vals_alt.p, (int)n,
                      min_points, h->ssn_seg_of.p, h->flt_ref.p, h->ssn_keep.p);
   OutStage<float4> ox;
   if ((rc = ox.open(h, out_xyz1, h->flt_rd, n))) return rc;
@@ -2471,13 +2485,13 @@ static int voxel_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m, 
   const uint32_t nvox = g.ndiv[0] * g.ndiv[1] * g.ndiv[2];
   int nbits = 1;
   while (nbits < 31 && (nvox - 1u) >> nbits) ++nbits;
-  HIPC(h->sc->keys.reserve(m));
-  HIPC(h->sc->vals.reserve(m));
+  HIPC(h->lane.scratch->keys.reserve(m));
+  HIPC(h->lane.scratch->vals.reserve(m));
   HIPC(h->vgf_out.reserve(m));
-  hipLaunchKernelGGL(k_vgf_keys, dim3(nblk(m)), dim3(256), 0, h->stream, src, (int)m, g, h->sc->keys.p, h->sc->vals.p);
+  hipLaunchKernelGGL(k_vgf_keys, dim3(nblk(m)), dim3(256), 0, h->stream, src, (int)m, g, h->lane.scratch->keys.p, h->lane.scratch->vals.p);
   rc = sort_pairs(h, m, nbits);  // stable: the points of a voxel keep input order
   if (rc) return rc;
-  hipLaunchKernelGGL(k_vgf_reduce, dim3(nblk(m)), dim3(256), 0, h->stream, src, h->sc->keys_alt.p, h->sc->vals_alt.p, (int)m, g,
+  hipLaunchKernelGGL(k_vgf_reduce, dim3(nblk(m)), dim3(256), 0, h->stream, src, h->lane.scratch->keys_alt.p, h->lane.scratch->vals_alt.p, (int)m, g,
                      f.flag ? 1 : 0, h->vgf_out.p, h->ssn_keep.p);
   return compact_kept(h, h->vgf_out.p, m, dst, m_out);
 }
@@ -2576,9 +2590,9 @@ int lsgpu_cloud_from_pointcloud2(lsgpu_icp* h, const unsigned char* data, int64_
   HIPC(hipSetDevice(h->device));
   const unsigned char* src = data;
   if (!is_device_ptr(data)) {  // the message's byte block crosses PCIe once, as it is
-    HIPC(h->sc->sort_tmp.reserve((size_t)n * (size_t)point_step));
-    HIPC(hipMemcpyAsync(h->sc->sort_tmp.p, data, (size_t)n * (size_t)point_step, hipMemcpyHostToDevice, h->stream));
-    src = reinterpret_cast<const unsigned char*>(h->sc->sort_tmp.p);
+    HIPC(h->lane.scratch->sort_tmp.reserve((size_t)n * (size_t)point_step));
+    HIPC(hipMemcpyAsync(h->lane.scratch->sort_tmp.p, data, (size_t)n * (size_t)point_step, hipMemcpyHostToDevice, h->stream));
+    src = reinterpret_cast<const unsigned char*>(h->lane.scratch->sort_tmp.p);
   }
   HIPC(h->flt_in.reserve(n));
   HIPC(h->ssn_keep.reserve(n));
@@ -2700,9 +2714,9 @@ int lsgpu_icp_compute_clouds(lsgpu_icp* h, int reading_slot, const int* ref_slot
     const int rca = assemble_submap(h, ref_slots, ref_T, n_ref, total);
     if (rca) return rca;
   }
-  const int rc = lsgpu_icp_compute(h, reinterpret_cast<const float*>(h->clouds[reading_slot].p), h->cloud_n[reading_slot],
-                                   reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats);
-  return rc;  // (the assembly is stream-ordered: its time is part of compute's filter time, stats->t_reserved[0])
+  // (the assembly is stream-ordered: its time is part of compute's filter time, stats->t_reserved[0])
+  return compute_run(h, reinterpret_cast<const float*>(h->clouds[reading_slot].p), h->cloud_n[reading_slot],
+                     reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats, nullptr, nullptr);
 }
 
 // lsgpu_cloud_upload(reading_slot) + lsgpu_icp_compute_clouds in one call: the new scan crosses PCIe WHILE the sub-map --
@@ -2745,17 +2759,15 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
       return rcu ? rcu : rca;
     }
   }
-  h->upload_into = h->clouds[reading_slot].p;
-  h->upload_done = false;
-  const int rc = lsgpu_icp_compute(h, reading_xyz1, nq, reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats);
-  h->upload_into = nullptr;
-  if (!h->upload_done) {   // the call returned before its upload went out: the plain copy, so that the slot holds the scan
+  bool upload_enqueued = false;
+  const int rc = compute_run(h, reading_xyz1, nq, reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats,
+                             h->clouds[reading_slot].p, &upload_enqueued);
+  if (!upload_enqueued) {   // the call returned before its upload went out: the plain copy, so that the slot holds the scan
     const std::string why = h->err;
     HIPC(hipMemcpyAsync(h->clouds[reading_slot].p, reading_xyz1, (size_t)nq * 16, hipMemcpyDefault, h->stream));
     HIPC(hipStreamSynchronize(h->stream));
     h->err = why;
   }
-  h->upload_done = false;
   h->cloud_n[reading_slot] = nq;
   return rc;
 }
@@ -2788,6 +2800,7 @@ static NeLoopFn ne_loop_fn(bool p2p, int k, bool chain, bool robust) {
 struct AlignRun {
   lsgpu_icp* const h;
   const float* const reading_xyz1; const int64_t nq; const float* const T_init;   // the call's arguments
+  AlignExtras x;   // ... and what a caller inside this file adds to them (build_index_on_side: unless configure_policy calls it off)
   int kk = 1;   // KDTreeMatcher knn: 1, or k >= 2 nearest matches per reading point (k N pairs; the split-scan mode refuses such handles)
   bool kmatch = false, chain = false, robust = false, angle = false;
   ChainArgs ca{};
@@ -2804,17 +2817,7 @@ struct AlignRun {
 
   // Start checks, the reading's order (step 5) and, in the split-scan mode, the entry handshake.
   int start() {
-    h->trace.clear(); h->trace_on_device = 0; h->rb_trace_n = 0;
-    // queries that lsgpu_icp_compute ordered and moved on its side stream belong to THIS call and to no later one, whatever
-    // way it ends (a guess that is refused below would otherwise leave queries moved by that guess to the next call with the
-    // same pointer and size)
-    const float* const prepared_rd = h->prepared_rd;
-    const int64_t prepared_nq = h->prepared_nq;
-    h->prepared_rd = nullptr; h->prepared_nq = 0;
-    // ... and so do reading normals (lsgpu_icp_compute's step / lsgpu_icp_align_normals)
-    const float* const normals_for = h->rd_nrm_for;
-    const int64_t normals_n = h->rd_nrm_n;
-    h->rd_nrm_for = nullptr; h->rd_nrm_n = 0; h->na_trace_n = 0;
+    h->trace.clear(); h->trace_on_device = 0; h->rb_trace_n = 0; h->na_trace_n = 0;
     // Local reasons not to start.  In the split-scan mode they are NOT returned yet: a rank that left here would
     // leave its peers blocked in the first collective, so every rank first takes part in the entry handshake below.
     int local_rc = LSGPU_OK;
@@ -2828,11 +2831,9 @@ struct AlignRun {
     robust = h->robust_on;
     if (robust) { ca.rb = robust::params(h->robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
     // SurfaceNormalOutlierFilter: inert without reading normals or without reference normals (as upstream)
-    angle = chain && h->normals_on && h->normals.max_angle >= 0.f && h->have_normals && reading_xyz1 &&
-            normals_for == reading_xyz1 && normals_n == nq;
+    angle = chain && h->normals_on && h->normals.max_angle >= 0.f && h->have_normals && reading_xyz1 && x.reading_normals;
     if (robust && ca.rb.plane && !h->have_normals) {
       h->err = "align: RobustOutlierFilter distanceType point2plane needs reference normals";
-      h->cone_build_in_align = false;
       return LSGPU_BAD_CONFIG;
     }
     if (h->nr <= 0 || nq <= 0 || !reading_xyz1) {  // empty cloud: ConvergenceError upstream
@@ -2852,7 +2853,7 @@ struct AlignRun {
       h->err = "align: the initial guess is not a rigid transformation (|1 - det R| > 1e-3)";
       local_rc = LSGPU_BAD_ARG;
     }
-    if (local_rc && !h->comm) { h->cone_build_in_align = false; return local_rc; }
+    if (local_rc && !h->comm) return local_rc;
     HIPC(hipSetDevice(h->device));
     t0 = wall_ms();
     h->knn_events_used = 0;
@@ -2863,14 +2864,9 @@ struct AlignRun {
     // step 5: T_refMean_dataIn = T_refIn_refMean^-1 * T_init (pure translation inverse)
     std::memcpy(T_rm_in, T_init, sizeof(T_rm_in));
     for (int d = 0; d < 3; ++d) T_rm_in[12 + d] = T_init[12 + d] - h->mean[d];
-    // (lsgpu_icp_compute may have ordered and moved these very queries on its side stream already: the loop's stream
-    // only has to wait for that)
-    const bool prepared = !local_rc && !h->comm && prepared_rd == reading_xyz1 && prepared_nq == nq;
     int rc = local_rc;
-    if (!rc) {
-      if (prepared) HIPC(hipStreamWaitEvent(h->stream, h->side_done, 0));
-      else rc = prepare_queries(h, reading_xyz1, nq, to_mat34(T_rm_in));
-    }
+    if (!rc && x.queries_prepared && !h->comm) HIPC(hipStreamWaitEvent(h->stream, h->side_done, 0));   // (ordered and moved on the side lane already)
+    else if (!rc) rc = prepare_queries(h, reading_xyz1, nq, to_mat34(T_rm_in));
     if (rc && !h->comm) return rc;
     nq_total = nq;
     if (h->comm) {
@@ -2976,14 +2972,15 @@ struct AlignRun {
     pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
     pc.kmatch = kmatch; pc.chain = chain;
     pc.robust_mad = robust && ca.rb.mad; pc.robust_scale_iters = robust ? h->robust.nb_iteration_for_scale : 0;
-    if (h->cone_build_in_align) { h->cone_ok = cone_wanted(h); h->cone_decided = false; }   // (its build follows the first iteration: feed())
+    const bool index = x.build_index_on_side ? cone_wanted(h) : h->cone_ok;   // (built behind the first iteration, feed(): h->cone_ok is false until then)
+    if (x.build_index_on_side) h->cone_decided = false;
     // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
     // itself the build when that is still to come)
     // (a reference of a markedly different size is another scene or another sub-map depth: the judgement starts over)
     if (h->index_rest > 0 && (h->nr > 2 * h->index_rest_nr || 2 * h->nr < h->index_rest_nr)) h->index_rest = 0;
-    const bool index_rests = h->index_rest > 0 && h->cone_ok;
-    if (index_rests) { --h->index_rest; if (h->cone_build_in_align) { h->cone_build_in_align = false; h->cone_ok = false; } }
-    h->pol.begin_align(h->cone_ok && !index_rests, h->cone_decided, h->cone_dense, h->cone_occupancy);
+    const bool index_rests = h->index_rest > 0 && index;
+    if (index_rests) { --h->index_rest; x.build_index_on_side = false; }
+    h->pol.begin_align(index && !index_rests, h->cone_decided, h->cone_dense, h->cone_occupancy);
     h->pay_voxel_timed = h->pay_index_timed = false;
     if (!h->ev_pay[0]) for (auto& e : h->ev_pay) HIPC(hipEventCreate(&e));
     if (pc.lookahead && !pc.comm && !h->ev_state) HIPC(hipEventCreateWithFlags(&h->ev_state, hipEventDisableTiming));   // (fetch_state's look-ahead)
@@ -3094,17 +3091,15 @@ struct AlignRun {
     int rc = enqueue_iteration(pol.plan(pc, true, pc.seed_cap && pc.cap_enabled, true, true, false));
     if (rc) return rc;
     pol.enq = 1; pol.since_check = 1;
-    if (h->cone_build_in_align) {
+    if (x.build_index_on_side) {
       // lsgpu_icp_compute left the direction index's build to this point: the device is busy with the first search, the
       // ~15 launches of the build go to the side stream (its own sort scratch) while it is
-      h->cone_build_in_align = false;
-      h->cur = h->side_stream; h->sc = &h->scr_side;
+      LaneScope on_side(h, h->side_lane());
       int rb = build_cone_index(h);
       if (!rb && h->cone_ok) {
         if (hipEventRecord(h->cone_done, h->side_stream) != hipSuccess) { (void)hipGetLastError(); rb = LSGPU_HIP_ERROR; h->err = "align: event record"; }
         h->cone_pending = true;
       }
-      h->cur = h->stream; h->sc = &h->scr_main;
       if (rb) return rb;
     }
     // The device decides when the loop ends (CounterTransformationChecker raises `done` after max_iterations at the
@@ -3233,15 +3228,15 @@ struct AlignRun {
 
 extern "C" {
 
-int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
-                    float T_out[16], lsgpu_icp_stats* stats) {
+static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16], float T_out[16],
+                     lsgpu_icp_stats* stats, AlignExtras extras) {
   if (!h || !T_init || !T_out) return LSGPU_BAD_ARG;
   h->err.clear();
   std::memcpy(T_out, T_init, 16 * sizeof(float));
   lsgpu_icp_stats st;
   std::memset(&st, 0, sizeof(st));
   if (stats) *stats = st;
-  AlignRun run{h, reading_xyz1, nq, T_init};
+  AlignRun run{h, reading_xyz1, nq, T_init, extras};
   int rc = run.start();
   if (!rc) rc = run.init_loop_state();
   if (!rc) rc = run.configure_policy();
@@ -3250,6 +3245,11 @@ int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const f
   rc = run.harvest(T_out, st);
   if (stats) *stats = st;
   return rc;
+}
+
+int lsgpu_icp_align(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16],
+                    float T_out[16], lsgpu_icp_stats* stats) {
+  return align_run(h, reading_xyz1, nq, T_init, T_out, stats, {});
 }
 
 int lsgpu_icp_align_batch(lsgpu_icp* const* handles, int n_handles, int64_t n_pairs,
