@@ -30,7 +30,8 @@
  * SurfaceNormalDataPointsFilter in place of SamplingSurfaceNormalDataPointsFilter as the reference filter
  * (lsgpu_chain_config.sn_knn), and RobustOutlierFilter (lsgpu_icp_set_robust_filter), and SurfaceNormalOutlierFilter with
  * SurfaceNormalDataPointsFilter on the reading and ObservationDirection- + OrientNormalsDataPointsFilter on either cloud
- * (lsgpu_icp_set_normals).
+ * (lsgpu_icp_set_normals), and PointToPlaneWithCovErrorMinimizer: the point-to-plane step plus the 6x6 covariance of the result
+ * (lsgpu_icp_set_covariance, lsgpu_icp_get_quality).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -639,7 +640,9 @@ typedef struct lsgpu_loaded_chain {
   int has_robust;
   lsgpu_normals_config normals;     /* SurfaceNormalOutlierFilter, reading normals, orientation pairs              */
   int has_normals;                  /* 0: none of these modules (normals holds lsgpu_normals_config_default)       */
-  int reserved[6];                  /* 0 */
+  int reserved[6];                  /* [0] = 1: errorMinimizer PointToPlaneWithCovErrorMinimizer (icp.error_minimizer stays
+                                     * LSGPU_MINIMIZER_POINT_TO_PLANE), [1] = the IEEE-754 bits of (float)sensorStdDev then, else 0;
+                                     * read them with lsgpu_loaded_chain_covariance.  [2..5] 0 */
 } lsgpu_loaded_chain;
 /* LSGPU_OK and *out (every byte of it, padding 0), or LSGPU_BAD_CONFIG with the reason -- the module's name in it, or the
  * section's for an unknown section -- written to why[0 .. why_cap), truncated if need be and always NUL-terminated; *out is
@@ -649,6 +652,62 @@ int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
  * name in it), or NULL where they return LSGPU_OK: what ICP::loadFromYaml (laser_track.cpp:17) reports for such a module. */
 const char* lsgpu_robust_config_why(const lsgpu_robust_config* c, int error_minimizer, int have_normals);
 const char* lsgpu_normals_config_why(const lsgpu_normals_config* c, int error_minimizer, int have_reference_normals);
+
+/* ---- PointToPlaneWithCovErrorMinimizer: the covariance of an alignment (DESIGN.md §3 "PointToPlaneWithCovErrorMinimizer", §5 choice 35) ----
+ * The module solves the step of PointToPlaneErrorMinimizer -- T_out, the statistics and the trace of a handle do not change
+ * with it -- and estimates the 6x6 covariance of the result (Censi's closed form; upstream: errorMinimizer->getCovariance()).
+ * Everything in the reference-mean frame, as lsgpu_normal_eq.  The pairs are those of the LAST EXECUTED iteration at the
+ * pose it matched at: p = the reading point at T_iter before that iteration's update, q = its match, n = the match's normal;
+ * a pair counts iff that iteration gave it a non-zero weight (a valid match, lo2 <= d2 <= limit with the iteration's effective
+ * upper limit and MinDistOutlierFilter's lo2).  dT = that iteration's step (lsgpu_point_to_plane_solve).  In double on the host:
+ *   beta = -asin(dT(2,0)), alpha = atan2(dT(2,1), dT(2,2)), gamma = atan2(dT(1,0) / cos beta, dT(0,0) / cos beta),
+ *   w = (alpha, beta, gamma), t = dT(0..2, 3), each rounded to float.  Per pair, float, one rounding per operation, sums of
+ *   three terms left to right ((x + y) + z):
+ *   r_p = sqrtf(p.p), u = p / r_p, r_q = sqrtf(q.q), v = q / r_q, m = u x n, c = w x p, g = w x u,
+ *   E = n . (((p + c) + t) - q), N_rd = n . (u + g), N_rf = -(n . v),
+ *   h = [n ; r_p m]   a = [n N_rd ; m (E + r_p N_rd)]   b = [n N_rf ; (r_q m) N_rf]      (translation first, then rotation)
+ *   H = sum h h^T, M = sum (a a^T + b b^T): the products and the sums in double.  cov = sensorStdDev^2 H^-1 M H^-1 in double.
+ * The weights of the outlier filters are not applied (upstream ignores them here).  r_p = 0 or r_q = 0 (a point exactly on the
+ * reference mean) divides by zero as upstream does: the sums become non-finite, which counts as singular.
+ * Scope: knn 1, any subset of Trimmed- / Max- / Min- / MedianDistOutlierFilter, KDTreeMatcher maxDist.  A handle with
+ * matcher_knn >= 2, RobustOutlierFilter, SurfaceNormalOutlierFilter, the point-to-point minimizer or a communicator refuses
+ * lsgpu_icp_set_covariance (LSGPU_BAD_CONFIG, the module named in lsgpu_last_error), and a handle with the covariance refuses
+ * those (lsgpu_icp_set_robust_filter, lsgpu_icp_set_normals with max_angle >= 0, lsgpu_icp_comm_init).
+ * Cost: one exact search at the last iteration's pose and one pass over its pairs after the loop, only on handles that asked. */
+typedef struct lsgpu_covariance_config {
+  float sensor_std_dev;   /* sensorStdDev [m] (0.01): finite and >= 0 */
+  int   reserved[3];      /* 0 */
+} lsgpu_covariance_config;
+void lsgpu_covariance_config_default(lsgpu_covariance_config* c);
+/* Switches the covariance on (cfg is copied), NULL switches it off.  Bad values and the refused combinations above:
+ * LSGPU_BAD_CONFIG before the device is touched (the handle keeps what it had). */
+int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg);
+typedef struct lsgpu_icp_quality {
+  double  covariance[36];   /* row major, symmetric; order x y z (translation), then alpha beta gamma (rotation about x, y, z) */
+  double  residual;         /* sum (n . (p - q))^2 over the pairs                                                          */
+  int64_t n_pairs;          /* == lsgpu_icp_stats.final_n_used                                                             */
+  float   used_ratio;       /* n_pairs / nq: getWeightedPointUsedRatio of a binary chain                                   */
+  int     reserved[3];      /* 0 */
+} lsgpu_icp_quality;
+/* The quality record of the handle's LAST alignment (lsgpu_icp_align, _align_normals, _compute, _compute_clouds,
+ * _compute_clouds_upload; after lsgpu_icp_align_batch: of the last pair each handle ran).  LSGPU_BAD_CONFIG if the covariance
+ * is not switched on (the reason in lsgpu_last_error); LSGPU_NO_CONVERGENCE if there was no alignment yet, the last one did not
+ * return LSGPU_OK, or H is singular; *out is written only with LSGPU_OK. */
+int lsgpu_icp_get_quality(lsgpu_icp* h, lsgpu_icp_quality* out);
+/* Kernel-level entry, the inputs of lsgpu_normal_eq plus the step: out[0..20] = upper triangle of H (row major, a <= c),
+ * [21..41] = of M, [42] = the pair count, [43] = sum (n . (p - q))^2.  A pair counts iff its id is valid, d2 <= limit and
+ * d2 >= the handle's MinDistOutlierFilter threshold squared.  dT NULL: the identity.  Reproducible run to run. */
+int lsgpu_point_to_plane_cov(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16], const int32_t* ids,
+                             const float* d2, float limit, const float dT[16], double out[44]);
+/* cov (row major 6x6, one triangle computed and mirrored) from those 44 sums.  Host only (no GPU, no handle); the function the
+ * library itself calls after the loop, bit for bit.  LSGPU_NO_CONVERGENCE, cov untouched: a pair count <= 0, a non-finite sum,
+ * or a singular H -- a Cholesky pivot of H no greater than 1e-6 times its own diagonal entry (the accuracy of the float
+ * per-pair terms: below it the data do not determine the direction).  LSGPU_BAD_CONFIG: sensor_std_dev negative or non-finite. */
+int lsgpu_point_to_plane_cov_solve(const double sums[44], float sensor_std_dev, double cov[36]);
+/* The covariance slots of a loaded chain: 1 and *sensor_std_dev (nullable) if the document names
+ * PointToPlaneWithCovErrorMinimizer, else 0 and *sensor_std_dev untouched.  Host only.  (An exported function, not an inline one:
+ * every function this header names is a symbol of the library, which is what the FFI front ends bind.) */
+int lsgpu_loaded_chain_covariance(const lsgpu_loaded_chain* c, float* sensor_std_dev);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

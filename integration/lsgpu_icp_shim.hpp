@@ -13,6 +13,7 @@
 // a cloud are "pointer to the (dim+1) x N column-major features", "number of points", "has descriptors" and "keep these
 // columns".
 #pragma once
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <istream>
@@ -40,6 +41,14 @@ struct LsgpuCloudTraits {
     d.features.conservativeResize(d.features.rows(), (Eigen_Index)cols.size());
     if (d.descriptors.cols() > 0) d.descriptors.conservativeResize(d.descriptors.rows(), (Eigen_Index)cols.size());
   }
+  // the 6 x 6 matrix errorMinimizer->getCovariance() returns (PointMatcher<float>::Matrix) from 36 doubles, row major
+  using Matrix = typename PM::Matrix;
+  static Matrix matrix6(const double* c) {
+    Matrix m(6, 6);
+    for (int r = 0; r < 6; ++r)
+      for (int k = 0; k < 6; ++k) m(r, k) = (float)c[r * 6 + k];
+    return m;
+  }
  private:
   using Eigen_Index = decltype(std::declval<DataPoints>().features.cols());
 };
@@ -65,6 +74,12 @@ struct LsgpuCloudTraits<LsgpuMirrorPM> {
     }
     d.features.resize(4 * cols.size());
     if (nrm) d.normals.resize(3 * cols.size());
+  }
+  using Matrix = std::array<float, 36>;   // row major
+  static Matrix matrix6(const double* c) {
+    Matrix m;
+    for (int i = 0; i < 36; ++i) m[i] = (float)c[i];
+    return m;
   }
 };
 
@@ -114,6 +129,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_normals: " + why);
       }
+      if (has_cov_ && lsgpu_icp_set_covariance(h_, &cov_) != LSGPU_OK) {   // PointToPlaneWithCovErrorMinimizer of the loaded chain
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_covariance: " + why);
+      }
     }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
@@ -126,6 +146,16 @@ class LsgpuICP {
     return T;
   }
   const lsgpu_icp_stats& lastStats() const { return stats_; }
+  // icp.errorMinimizer->getCovariance() becomes icp.getCovariance(): the 6 x 6 covariance of the last compute() of a chain
+  // with PointToPlaneWithCovErrorMinimizer, in the PointMatcher matrix type (float).  Throws ConvergenceError before a
+  // successful compute() and for a singular H, std::runtime_error if the chain does not name the module.
+  typename Traits::Matrix getCovariance() {
+    lsgpu_icp_quality q;
+    const int rc = h_ ? lsgpu_icp_get_quality(h_, &q) : (has_cov_ ? LSGPU_NO_CONVERGENCE : LSGPU_BAD_CONFIG);
+    if (rc == LSGPU_NO_CONVERGENCE) throw typename PM::ConvergenceError(h_ ? lsgpu_last_error(h_) : "getCovariance: no compute() yet");
+    if (rc != LSGPU_OK) throw std::runtime_error(std::string("LsgpuICP::getCovariance: ") + lsgpu_strerror(rc) + (h_ ? std::string(" [") + lsgpu_last_error(h_) + "]" : std::string()));
+    return Traits::matrix6(q.covariance);
+  }
 
  private:
   void take(const laser_slam_amd::ICP& parsed) {
@@ -136,6 +166,8 @@ class LsgpuICP {
     if (has_robust_) robust_ = *parsed.robustFilter();
     has_normals_ = parsed.normalsConfig() != nullptr;
     if (has_normals_) normals_ = *parsed.normalsConfig();
+    lsgpu_covariance_config_default(&cov_);
+    has_cov_ = parsed.covarianceConfig(&cov_.sensor_std_dev);
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -150,6 +182,8 @@ class LsgpuICP {
   bool has_robust_ = false;                             // ... if the chain holds one
   lsgpu_normals_config normals_{};                      // SurfaceNormalOutlierFilter, reading normals, orientation pairs ...
   bool has_normals_ = false;                            // ... if the chain holds any of them
+  lsgpu_covariance_config cov_{};                       // PointToPlaneWithCovErrorMinimizer's sensorStdDev ...
+  bool has_cov_ = false;                                // ... if the chain names the module
   int64_t seed_ = -1;
 };
 

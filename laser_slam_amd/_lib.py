@@ -41,6 +41,8 @@ ABI_SYMBOLS = [
     "lsgpu_icp_get_normal_angle_trace",
     "lsgpu_chain_load", "lsgpu_robust_config_why", "lsgpu_normals_config_why",
     "lsgpu_filter_voxel_grid_points",
+    "lsgpu_covariance_config_default", "lsgpu_icp_set_covariance", "lsgpu_icp_get_quality", "lsgpu_point_to_plane_cov",
+    "lsgpu_point_to_plane_cov_solve", "lsgpu_loaded_chain_covariance",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -73,6 +75,17 @@ class RobustTrace(C.Structure):
     _fields_ = [("median", C.c_float), ("scale", C.c_float), ("w_sum", C.c_double), ("recomputed", C.c_int),
                 ("reserved", C.c_int)]
 
+
+
+class CovarianceCfg(C.Structure):
+    """lsgpu_covariance_config: PointToPlaneWithCovErrorMinimizer's parameter."""
+    _fields_ = [("sensor_std_dev", C.c_float), ("reserved", C.c_int * 3)]
+
+
+class IcpQuality(C.Structure):
+    """lsgpu_icp_quality: the covariance (6x6 row major: x y z alpha beta gamma) and the pair statistics of the last alignment."""
+    _fields_ = [("covariance", C.c_double * 36), ("residual", C.c_double), ("n_pairs", C.c_int64),
+                ("used_ratio", C.c_float), ("reserved", C.c_int * 3)]
 
 
 class ChainCfg(C.Structure):
@@ -313,6 +326,14 @@ def lib() -> C.CDLL:
     L.lsgpu_robust_config_why.restype = C.c_char_p
     L.lsgpu_normals_config_why.argtypes = [C.POINTER(NormalsCfg), C.c_int, C.c_int]
     L.lsgpu_normals_config_why.restype = C.c_char_p
+    L.lsgpu_covariance_config_default.argtypes = [C.POINTER(CovarianceCfg)]
+    L.lsgpu_covariance_config_default.restype = None
+    L.lsgpu_icp_set_covariance.argtypes = [vp, C.POINTER(CovarianceCfg)]
+    L.lsgpu_icp_get_quality.argtypes = [vp, C.POINTER(IcpQuality)]
+    L.lsgpu_point_to_plane_cov.argtypes = [vp, fp, i64, C.POINTER(C.c_float), fp, fp, C.c_float, C.POINTER(C.c_float),
+                                           C.POINTER(C.c_double)]
+    L.lsgpu_point_to_plane_cov_solve.argtypes = [C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_double)]
+    L.lsgpu_loaded_chain_covariance.argtypes = [C.POINTER(LoadedChain), C.POINTER(C.c_float)]
     _lib = L
     return L
 

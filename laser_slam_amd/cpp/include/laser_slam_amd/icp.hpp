@@ -424,6 +424,25 @@ class ICP {
     return T;
   }
 
+  // PointToPlaneWithCovErrorMinimizer (errorMinimizer->getCovariance() upstream): the quality record of the last compute --
+  // the 6x6 covariance (row major; x y z, then the rotations about x y z), the squared plane residual, the pair count and
+  // the used ratio.  ConfigError if the chain does not name the module; ConvergenceError before a successful compute or
+  // for a singular H.
+  lsgpu_icp_quality quality() {
+    ensureHandle();
+    lsgpu_icp_quality q;
+    check(lsgpu_icp_get_quality(h_, &q), "lsgpu_icp_get_quality");
+    return q;
+  }
+  std::array<double, 36> covariance() {
+    const lsgpu_icp_quality q = quality();
+    std::array<double, 36> c;
+    std::memcpy(c.data(), q.covariance, sizeof(q.covariance));
+    return c;
+  }
+  // sensorStdDev of the loaded chain's PointToPlaneWithCovErrorMinimizer; false: the chain does not name the module
+  bool covarianceConfig(float* sensor_std_dev) const { return lsgpu_loaded_chain_covariance(&loaded_, sensor_std_dev) != 0; }
+
   const lsgpu_icp_stats& lastStats() const { return stats_; }
   const lsgpu_icp_config& config() const { return loaded_.icp; }
   lsgpu_icp* handle() { ensureHandle(); return h_; }  // the C-ABI handle (device conversions of ros_msgs.hpp)
@@ -490,6 +509,13 @@ class ICP {
     }
     if (loaded_.has_normals && lsgpu_icp_set_normals(h_, &loaded_.normals) != LSGPU_OK) {
       const std::string msg = std::string("lsgpu_icp_set_normals: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
+    lsgpu_covariance_config cc;
+    lsgpu_covariance_config_default(&cc);
+    if (lsgpu_loaded_chain_covariance(&loaded_, &cc.sensor_std_dev) && lsgpu_icp_set_covariance(h_, &cc) != LSGPU_OK) {
+      const std::string msg = std::string("lsgpu_icp_set_covariance: ") + lsgpu_last_error(h_);
       release();
       throw ConfigError(msg);
     }

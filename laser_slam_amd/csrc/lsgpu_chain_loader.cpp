@@ -49,7 +49,7 @@ struct Load {
   // where a filter section has got to: 1 RandomSampling (reading) / the module that gives the normals (reference),
   // 2 SurfaceNormal on the reading, 3 ObservationDirection, 4 OrientNormals
   int stage[2] = {0, 0};
-  bool matcher = false, minimizer = false, counter = false, robust = false;
+  bool matcher = false, minimizer = false, counter = false, robust = false, with_cov = false;
 
   std::string name() const { return m->name; }
   int side() const { return std::strcmp(m->section, "readingDataPointsFilters") == 0 ? 0 : 1; }
@@ -203,9 +203,19 @@ void surface_normal_outlier(Load& l) {
   l.out.normals.max_angle = (float)a;
 }
 void error_minimizer(Load& l) {
-  if (l.minimizer) refuse("errorMinimizer: one module at most");
+  if (l.minimizer) refuse("errorMinimizer: one module at most (" + l.name() + " is a second one)");
   l.out.icp.error_minimizer = l.name() == "PointToPointErrorMinimizer" ? LSGPU_MINIMIZER_POINT_TO_POINT : LSGPU_MINIMIZER_POINT_TO_PLANE;
   l.minimizer = true;
+}
+// the step of PointToPlaneErrorMinimizer plus the covariance of the result: the two slots of lsgpu_loaded_chain.reserved
+void error_minimizer_with_cov(Load& l) {
+  error_minimizer(l);
+  const double sd = l.finite("sensorStdDev", 0.01);
+  if (!(sd >= 0.0)) refuse(l.name() + ": sensorStdDev must be >= 0");
+  const float f = (float)sd;
+  l.out.reserved[0] = 1;
+  std::memcpy(&l.out.reserved[1], &f, sizeof(f));
+  l.with_cov = true;
 }
 void counter_checker(Load& l) { l.out.icp.max_iterations = l.truncated("maxIterationCount", 40); l.counter = true; }
 void differential_checker(Load& l) {
@@ -239,6 +249,7 @@ const Row kRows[] = {
     {"outlierFilters", "SurfaceNormalOutlierFilter", "maxAngle", true, surface_normal_outlier},
     {"errorMinimizer", "PointToPlaneErrorMinimizer", nullptr, false, error_minimizer},
     {"errorMinimizer", "PointToPointErrorMinimizer", nullptr, false, error_minimizer},
+    {"errorMinimizer", "PointToPlaneWithCovErrorMinimizer", "sensorStdDev", false, error_minimizer_with_cov},
     {"transformationCheckers", "CounterTransformationChecker", "maxIterationCount", true, counter_checker},
     {"transformationCheckers", "DifferentialTransformationChecker", "minDiffRotErr minDiffTransErr smoothLength", true, differential_checker},
 };
@@ -251,7 +262,7 @@ void finish(Load& l) {
   lsgpu_loaded_chain& o = l.out;
   const int have_normals = l.stage[1] != 0;
   if (!l.matcher) refuse("matcher: KDTreeMatcher is required");
-  if (!l.minimizer) refuse("errorMinimizer: PointToPlaneErrorMinimizer or PointToPointErrorMinimizer is required");
+  if (!l.minimizer) refuse("errorMinimizer: PointToPlaneErrorMinimizer, PointToPlaneWithCovErrorMinimizer or PointToPointErrorMinimizer is required");
   if (!have_normals && o.icp.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
     refuse("referenceDataPointsFilters: SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter is required (it "
            "provides the normals of PointToPlaneErrorMinimizer)");
@@ -262,6 +273,11 @@ void finish(Load& l) {
       refuse(std::string(s == 0 ? "readingDataPointsFilters" : "referenceDataPointsFilters") + ": ObservationDirectionDataPointsFilter" + kPair);
   if (lsgpu::normal_angle::check(&o.normals, o.icp.error_minimizer, have_normals, &why) != LSGPU_OK) refuse(why);
   if (!l.counter) refuse("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
+  if (l.with_cov) {   // what the covariance pass does not cover (lsgpu_icp_set_covariance refuses the same handles)
+    const char* with = o.icp.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2" : l.robust ? "RobustOutlierFilter"
+                     : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
+    if (with) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + with + " (the covariance is implemented for knn 1 and binary distance filters)");
+  }
   o.has_robust = l.robust ? 1 : 0;
   o.has_normals = o.normals.max_angle >= 0.f || o.normals.reading_sn_knn != 0 || o.normals.reading_orient != 0 || o.normals.reference_orient != 0;
 }
@@ -318,6 +334,12 @@ int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
   } catch (const std::exception&) {   // (no exception crosses the ABI)
     return LSGPU_BAD_ARG;
   }
+}
+
+int lsgpu_loaded_chain_covariance(const lsgpu_loaded_chain* c, float* sensor_std_dev) {
+  if (!c || c->reserved[0] != 1) return 0;
+  if (sensor_std_dev) std::memcpy(sensor_std_dev, &c->reserved[1], sizeof(float));
+  return 1;
 }
 
 }  // extern "C"

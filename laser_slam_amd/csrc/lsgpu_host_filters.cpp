@@ -25,6 +25,7 @@
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
 #include "lsgpu_voxel_filter.h"
+#include "lsgpu_cov.h"
 
 namespace {
 
@@ -294,6 +295,20 @@ int lsgpu_point_to_plane_solve(const double sums[27], float dT[16]) {
   }
   lsgpu::hostmath::delta_from_x(x, dT);
   return LSGPU_OK;
+}
+
+// ---- PointToPlaneWithCovErrorMinimizer: the 6x6 work on the sums of k_cov (csrc/lsgpu_cov.h)
+void lsgpu_covariance_config_default(lsgpu_covariance_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->sensor_std_dev = 0.01f;
+}
+
+int lsgpu_point_to_plane_cov_solve(const double sums[44], float sensor_std_dev, double cov[36]) {
+  if (!sums || !cov) return LSGPU_BAD_ARG;
+  if (!(sensor_std_dev >= 0.f) || std::isinf(sensor_std_dev)) return LSGPU_BAD_CONFIG;
+  if (!(sums[42] > 0.0)) return LSGPU_NO_CONVERGENCE;   // "no point to minimize" (a NaN count included)
+  return lsgpu::cov::solve(sums, (double)sensor_std_dev, cov) ? LSGPU_OK : LSGPU_NO_CONVERGENCE;
 }
 
 // ---- RobustOutlierFilter: the host twins of the device loop's scale and weights (csrc/lsgpu_robust.h)

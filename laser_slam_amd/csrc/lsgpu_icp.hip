@@ -30,6 +30,8 @@
 #include "lsgpu_snf.hip.h"
 #include "lsgpu_cone.hip.h"
 #include "lsgpu_solve.hip.h"
+#include "lsgpu_cov.hip.h"
+#include "lsgpu_cov.h"
 #include "lsgpu_host_math.h"
 #include "lsgpu_ssn.hip.h"
 #include "lsgpu_voxel_filter.hip.h"
@@ -165,6 +167,8 @@ struct Staging {
   alignas(64) IcpState state;               // the loop state of the running align, as of the host's last look
   alignas(64) uint32_t totals[2][4];        // scan_totals, [lane.totals_row]: {last input, last scanned} of two scans
   alignas(64) uint32_t bounds[6];           // cloud_bounds: ordered keys of the minimum and the maximum
+  alignas(64) double cov[kCovStride];       // PointToPlaneWithCovErrorMinimizer: the 44 sums of k_cov ...
+  alignas(64) lsgpu_iter_trace cov_trace;   // ... and the last iteration's trace record (its normal equations give the step)
 };
 
 struct lsgpu_icp {
@@ -320,6 +324,13 @@ struct lsgpu_icp {
   DevBuf<float> nrm_io;       // staging of lsgpu_icp_get_reference_normals
   DevBuf<lsgpu_normal_angle_trace> na_trace_dev;
   size_t na_trace_n = 0;      // records of the last alignment in na_trace_dev
+  // PointToPlaneWithCovErrorMinimizer (lsgpu_icp_set_covariance): the pass after the loop and the record it leaves
+  bool cov_on = false;
+  lsgpu_covariance_config cov_cfg{};
+  int quality_state = 0;      // of the last alignment: 0 none / it did not return LSGPU_OK, 1 `quality` holds it, 2 singular H
+  lsgpu_icp_quality quality{};
+  DevBuf<float4> cov_pts;     // the moved reading in the caller's order
+  DevBuf<double> cov_partials, cov_out;   // kNeBlocksMax x kCovStride, kCovStride
   DevBuf<double> ne_partials; // kNeBlocks * 32
   DevBuf<double> ne_gpartials;  // (kNeBlocksMax / kNeGroup) * 32: first-level sums of k_normal_eq_loop
   DevBuf<uint32_t> ne_tickets;  // 1 + kNeBlocksMax / kNeGroup
@@ -461,6 +472,7 @@ int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg) {
   // (whether the reference has normals is known to align / the stand-alone sums, which check point2plane again)
   if (robust::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
   if (h->comm) { h->err = "RobustOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
+  if (h->cov_on) { h->err = "RobustOutlierFilter: not together with PointToPlaneWithCovErrorMinimizer (its covariance takes binary weights)"; return LSGPU_BAD_CONFIG; }
   h->robust = *cfg;
   h->robust_on = true;
   return LSGPU_OK;
@@ -478,8 +490,37 @@ int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
   // (whether the reference has normals is known to align, for which a filter without them is inert)
   if (normal_angle::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
   if (h->comm) { h->err = "SurfaceNormalOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
+  if (h->cov_on && cfg->max_angle >= 0.f) { h->err = "SurfaceNormalOutlierFilter: not together with PointToPlaneWithCovErrorMinimizer (its covariance pass does not apply the angle test)"; return LSGPU_BAD_CONFIG; }
   h->normals = *cfg;
   h->normals_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->cov_on = false; h->quality_state = 0; return LSGPU_OK; }
+  const char* const mod = "PointToPlaneWithCovErrorMinimizer: ";
+  if (!(cfg->sensor_std_dev >= 0.f) || std::isinf(cfg->sensor_std_dev)) { h->err = std::string(mod) + "sensorStdDev must be finite and >= 0"; return LSGPU_BAD_CONFIG; }
+  const char* with = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT ? "PointToPointErrorMinimizer (the handle's minimizer)"
+                   : h->cfg.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2"
+                   : h->robust_on ? "RobustOutlierFilter"
+                   : (h->normals_on && h->normals.max_angle >= 0.f) ? "SurfaceNormalOutlierFilter"
+                   : h->comm ? "the split-scan mode (lsgpu_icp_comm_init)" : nullptr;
+  if (with) { h->err = std::string(mod) + "not together with " + with; return LSGPU_BAD_CONFIG; }
+  if (!h->cov_on) h->quality_state = 0;
+  h->cov_cfg = *cfg;
+  h->cov_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_get_quality(lsgpu_icp* h, lsgpu_icp_quality* out) {
+  if (!h || !out) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!h->cov_on) { h->err = "get_quality: the covariance is not switched on (lsgpu_icp_set_covariance / PointToPlaneWithCovErrorMinimizer)"; return LSGPU_BAD_CONFIG; }
+  if (h->quality_state == 0) { h->err = "get_quality: no alignment of this handle has returned LSGPU_OK since the covariance was switched on"; return LSGPU_NO_CONVERGENCE; }
+  if (h->quality_state == 2) { h->err = "get_quality: H is singular (the pairs of the last iteration do not determine the pose)"; return LSGPU_NO_CONVERGENCE; }
+  *out = h->quality;
   return LSGPU_OK;
 }
 
@@ -555,6 +596,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
   h->rd_nrm.release(); h->rd_nrm0.release(); h->nrm_io.release(); h->na_trace_dev.release();
+  h->cov_pts.release(); h->cov_partials.release(); h->cov_out.release();
   h->sel.release(); h->ne_partials.release(); h->ne_gpartials.release(); h->ne_tickets.release(); h->ne_out.release(); h->limit_dev.release();
   for (auto& e : h->comm_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : h->knn_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); (void)hipEventDestroy(e.d); (void)hipEventDestroy(e.e); }
@@ -1214,6 +1256,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
     h->err = "comm_init: the split-scan mode runs knn 1 only (matcher_knn >= 2 is not supported there)";
     return LSGPU_BAD_CONFIG;
   }
+  if (h->cov_on) {
+    h->err = "comm_init: the split-scan mode does not run PointToPlaneWithCovErrorMinimizer";
+    return LSGPU_BAD_CONFIG;
+  }
   if (chain_on(h)) {
     h->err = (h->normals_on && h->normals.max_angle >= 0.f) ? "comm_init: the split-scan mode does not run SurfaceNormalOutlierFilter"
            : h->robust_on ? "comm_init: the split-scan mode does not run RobustOutlierFilter"
@@ -1411,6 +1457,50 @@ int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const flo
 int lsgpu_point_to_point(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
                          const int32_t* ids, const float* d2, float limit, double out[29]) {
   return stand_alone_sums<kPointToPoint>(h, "point_to_point", query_xyz1, nq, T, ids, d2, limit, out);
+}
+
+// The covariance sums of the pairs (q, ids, d2: device pointers, the caller's order, ids indexing the reference as given)
+// into h->pin->cov, on return.  lsgpu_point_to_plane_cov and the pass after the loop both end here: same grid, same order.
+static int cov_sums(lsgpu_icp* h, const float4* q, int64_t nq, const Mat34& Tm, const int* ids, const float* d2,
+                                 float limit, const float dT[16]) {
+  HIPC(h->cov_partials.reserve((size_t)kNeBlocksMax * kCovStride));
+  HIPC(h->cov_out.reserve(kCovStride));
+  float wt[6];
+  cov::step_params(dT, wt);
+  CovStep step;
+  for (int d = 0; d < 3; ++d) { step.w[d] = wt[d]; step.t[d] = wt[3 + d]; }
+  const int nb = std::min(kNeBlocks, nblk(nq));
+  const float lo2 = h->cfg.outlier_min_dist * h->cfg.outlier_min_dist;   // MinDistOutlierFilter (0: none), as the loop's ChainArgs
+  hipLaunchKernelGGL((k_cov<true>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm, ids, d2, h->pts.p, h->nrm.p,
+                     h->ref_inv.p, (uint32_t)h->nr, limit, lo2, step, h->cov_partials.p);
+  hipLaunchKernelGGL(k_cov_final, dim3(1), dim3(1024), 0, h->stream, h->cov_partials.p, nb, h->cov_out.p);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h->pin->cov, h->cov_out.p, kCov * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  return LSGPU_OK;
+}
+
+int lsgpu_point_to_plane_cov(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16], const int32_t* ids,
+                             const float* d2, float limit, const float dT[16], double out[44]) {
+  if (!h || !out) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (h->nr <= 0) { h->err = "point_to_plane_cov: no reference set"; return LSGPU_BAD_ARG; }
+  if (!h->have_normals) { h->err = "point_to_plane_cov: the reference has no normals"; return LSGPU_BAD_ARG; }
+  if (nq <= 0 || !query_xyz1 || !ids || !d2 || nq > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
+  HIPC(hipSetDevice(h->device));
+  int rc = ensure_loop_buffers(h, nq);
+  if (rc) return rc;
+  const float4* q = nullptr;
+  rc = stage_points(h, query_xyz1, nq, h->q_in, &q);
+  if (rc) return rc;
+  const int* idp = nullptr; const float* dp = nullptr;
+  if ((rc = stage_in(h, ids, (size_t)nq, h->ids_io, &idp))) return rc;
+  if ((rc = stage_in(h, d2, (size_t)nq, h->d2_io, &dp))) return rc;
+  const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  rc = cov_sums(h, q, nq, to_mat34(T ? T : I), idp, dp, limit, dT ? dT : I);
+  if (rc) return rc;
+  std::memcpy(out, h->pin->cov, kCov * sizeof(double));
+  return LSGPU_OK;
 }
 
 int lsgpu_transform_points(lsgpu_icp* h, const float T[16], const float* xyz1, int64_t n,
@@ -3226,6 +3316,66 @@ struct AlignRun {
   }
 };
 
+// PointToPlaneWithCovErrorMinimizer: the pass after a loop that returned LSGPU_OK.  The covariance a caller can observe is that
+// of the last executed iteration: its pairs at the pose it matched at.  That pose is the loop state's T_rows_prev (the update
+// keeps the transform it replaces; the identity after one iteration), its step comes from the normal equations of its trace
+// record (lsgpu_point_to_plane_solve, as a caller would take it), its limit is the state's last_limit.  The pairs are searched
+// once more, exactly, with the search of lsgpu_knn -- the loop's own ids / d2 are exact only inside the radius cap and the
+// kept lanes of the direction index -- and brought into the caller's order, so that the sums are those of
+// lsgpu_point_to_plane_cov on the same inputs, bit for bit.
+static int covariance_pass(AlignRun& run, lsgpu_icp_stats& st) {
+  lsgpu_icp* h = run.h;
+  const IcpState* hst = run.hst;
+  const int64_t nq = run.nq;
+  const int it = hst->iter;
+  if (it < 1 || it > run.max_it) return LSGPU_OK;   // (no executed iteration: the record stays "none")
+  Mat34 Tm;
+  for (int i = 0; i < 12; ++i) Tm.m[i] = hst->T_rows_prev[i];
+  HIPC(hipMemcpyAsync(&h->pin->cov_trace, h->trace_dev.p + (it - 1), sizeof(lsgpu_iter_trace), hipMemcpyDeviceToHost, h->stream));
+  HIPC(h->cov_pts.reserve((size_t)nq)); HIPC(h->ids_io.reserve((size_t)nq)); HIPC(h->d2_io.reserve((size_t)nq));
+  int rc = LSGPU_OK;
+  if (matcher_max_d2(h) < INFINITY) {   // KDTreeMatcher maxDist: the bounded k-best search with k = 1 (as lsgpu_knn)
+    rc = run_knn_k(h, 1, Tm, nullptr, true, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_knnk_unpermute, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rdq.p, (int)nq, 1, h->kmatch.p,
+                       h->kd2.p, h->pts.p, h->ids_io.p, h->d2_io.p);
+  } else {
+    policy::Iteration probe;   // a seeded, uncapped, wide search outside any loop
+    probe.seed = true; probe.capped = false; probe.wide = true;
+    h->pol.begin_align(false, false, false, 0.f);
+    rc = run_knn(h, Tm, nullptr, probe, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_knn_unpermute, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rdq.p, (int)nq,
+                       h->ids.p, h->d2.p, h->pts.p, h->ids_io.p, h->d2_io.p);
+  }
+  hipLaunchKernelGGL(k_cov_unpermute_points, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rdq.p, (int)nq, h->cov_pts.p);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(h->stream));
+  const lsgpu_iter_trace& tr = h->pin->cov_trace;
+  double sums[27];
+  {
+    int k = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int c = a; c < 6; ++c) sums[k++] = tr.A[a * 6 + c];
+    for (int a = 0; a < 6; ++a) sums[21 + a] = tr.b[a];
+  }
+  float dT[16];
+  if (lsgpu_point_to_plane_solve(sums, dT) != LSGPU_OK) { h->quality_state = 2; return LSGPU_OK; }   // (the loop solved it: not reached)
+  rc = cov_sums(h, h->cov_pts.p, nq, Tm, h->ids_io.p, h->d2_io.p, hst->last_limit, dT);
+  if (rc) return rc;
+  const double* s = h->pin->cov;
+  lsgpu_icp_quality q;
+  std::memset(&q, 0, sizeof(q));
+  q.residual = s[43];
+  q.n_pairs = (int64_t)s[42];
+  q.used_ratio = (float)((double)q.n_pairs / (double)nq);
+  const int rs = lsgpu_point_to_plane_cov_solve(s, h->cov_cfg.sensor_std_dev, q.covariance);
+  h->quality = q;
+  h->quality_state = rs == LSGPU_OK ? 1 : 2;
+  st.t_total_ms = wall_ms() - run.t0;
+  return LSGPU_OK;
+}
+
 extern "C" {
 
 static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float T_init[16], float T_out[16],
@@ -3236,6 +3386,7 @@ static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const 
   lsgpu_icp_stats st;
   std::memset(&st, 0, sizeof(st));
   if (stats) *stats = st;
+  h->quality_state = 0;
   AlignRun run{h, reading_xyz1, nq, T_init, extras};
   int rc = run.start();
   if (!rc) rc = run.init_loop_state();
@@ -3243,6 +3394,10 @@ static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const 
   if (!rc) rc = run.feed();
   if (rc) return rc;
   rc = run.harvest(T_out, st);
+  if (rc == LSGPU_OK && h->cov_on) {
+    const int rq = covariance_pass(run, st);
+    if (rq) { std::memcpy(T_out, T_init, 16 * sizeof(float)); return rq; }
+  }
   if (stats) *stats = st;
   return rc;
 }

@@ -81,7 +81,7 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None, normals=None):
+                 robust=None, normals=None, covariance=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
@@ -89,7 +89,8 @@ class IcpHandle:
         (None: cfg's; 0: no such module; see lsgpu_icp_config).  robust: None, or RobustOutlierFilter's parameters (a
         RobustConfig, a dict of its fields, or an _lib.RobustCfg) -- lsgpu_icp_set_robust_filter.  normals: None, or a
         NormalsConfig / dict of its fields / _lib.NormalsCfg (SurfaceNormalOutlierFilter, reading normals, oriented
-        normals) -- lsgpu_icp_set_normals."""
+        normals) -- lsgpu_icp_set_normals.  covariance: None, or PointToPlaneWithCovErrorMinimizer's sensorStdDev --
+        lsgpu_icp_set_covariance (given last: it refuses a handle with modules its pass does not cover)."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -129,6 +130,46 @@ class IcpHandle:
         self.normals = None
         if nc is not None:
             self.set_normals(nc)
+        self.covariance = None
+        if covariance is not None:
+            self.set_covariance(covariance)
+
+    def set_covariance(self, sensor_std_dev=0.01):
+        """lsgpu_icp_set_covariance: PointToPlaneWithCovErrorMinimizer's covariance after every alignment (None: off)."""
+        cc = None
+        if sensor_std_dev is not None:
+            cc = _lib.CovarianceCfg()
+            _lib.lib().lsgpu_covariance_config_default(C.byref(cc))
+            cc.sensor_std_dev = float(sensor_std_dev)
+        rc = _lib.lib().lsgpu_icp_set_covariance(self._h, C.byref(cc) if cc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_covariance", self._h)
+        self.covariance = None if cc is None else float(cc.sensor_std_dev)
+
+    def quality(self):
+        """lsgpu_icp_get_quality of the last alignment -> dict(covariance 6x6 float64, residual, n_pairs, used_ratio).
+        Raises LsgpuError (BAD_CONFIG: covariance off) / ConvergenceError (no OK alignment yet, singular H)."""
+        q = _lib.IcpQuality()
+        rc = _lib.lib().lsgpu_icp_get_quality(self._h, C.byref(q))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_get_quality", self._h)
+        return dict(covariance=np.array(q.covariance[:], np.float64).reshape(6, 6), residual=float(q.residual),
+                    n_pairs=int(q.n_pairs), used_ratio=float(q.used_ratio))
+
+    def point_to_plane_cov(self, query_xyz1, T, ids, d2, limit: float, dT=None) -> np.ndarray:
+        """lsgpu_point_to_plane_cov: the 44 covariance sums (21 of H, 21 of M, count, sum (n . (p - q))^2) of the pairs
+        with d2 <= limit under the step dT (4x4; None: identity), double."""
+        p, _k, n = _as_f32(query_xyz1, 4)
+        ids = np.ascontiguousarray(ids, np.int32)
+        d2 = np.ascontiguousarray(d2, np.float32)
+        out = np.zeros(44)
+        tp = _fp(_t16(T)) if T is not None else None
+        dp = _fp(_t16(dT)) if dT is not None else None
+        rc = _lib.lib().lsgpu_point_to_plane_cov(self._h, p, n, tp, ids.ctypes.data, d2.ctypes.data, limit, dp,
+                                                 out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_point_to_plane_cov", self._h)
+        return out
 
     def set_normals(self, normals):
         """lsgpu_icp_set_normals: SurfaceNormalOutlierFilter / reading normals / oriented normals (None removes them)."""
@@ -698,6 +739,21 @@ def point_to_plane_solve(sums) -> np.ndarray:
     return out.reshape(4, 4).T.copy()
 
 
+def point_to_plane_cov_solve(sums, sensor_std_dev: float = 0.01) -> np.ndarray:
+    """lsgpu_point_to_plane_cov_solve: cov = sensorStdDev^2 H^-1 M H^-1 (6x6 float64) from the 44 sums of
+    IcpHandle.point_to_plane_cov -- host only, the function the library calls after the loop.  Raises ConvergenceError for
+    a pair count of 0, a non-finite sum or a singular H."""
+    s = np.ascontiguousarray(sums, np.float64)
+    if s.shape != (44,):
+        raise ValueError("expected 44 sums")
+    out = np.empty(36, np.float64)
+    rc = _lib.lib().lsgpu_point_to_plane_cov_solve(s.ctypes.data_as(C.POINTER(C.c_double)), float(sensor_std_dev),
+                                                   out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_point_to_plane_cov_solve")
+    return out.reshape(6, 6)
+
+
 @dataclass
 class RobustConfig:
     """RobustOutlierFilter's parameters, with the module's defaults."""
@@ -856,6 +912,19 @@ class ChainConfig:
             self.extra["normals"] = value
 
     @property
+    def covariance(self) -> Optional[float]:
+        """PointToPlaneWithCovErrorMinimizer's sensorStdDev; None: the covariance is not asked for.  The step is
+        PointToPlaneErrorMinimizer's: `error_minimizer` names that module.  Kept in `extra`, like `robust`."""
+        return self.extra.get("covariance")
+
+    @covariance.setter
+    def covariance(self, value):
+        if value is None:
+            self.extra.pop("covariance", None)
+        else:
+            self.extra["covariance"] = float(value)
+
+    @property
     def robust(self) -> Optional["RobustConfig"]:
         """RobustOutlierFilter's parameters (a RobustConfig); None: no such module.  Kept in `extra`, so that the fields of
         a chain without the module are what they were."""
@@ -916,6 +985,9 @@ def _chain_config(lc) -> "ChainConfig":
         n = lc.normals
         ch.normals = NormalsConfig(_f32(n.max_angle), n.reading_sn_knn, n.reading_orient, n.reference_orient,
                                    tuple(_f32(v) for v in n.reading_sensor), tuple(_f32(v) for v in n.reference_sensor))
+    sd = C.c_float()
+    if _lib.lib().lsgpu_loaded_chain_covariance(C.byref(lc), C.byref(sd)):
+        ch.covariance = _f32(sd.value)
     return ch
 
 
@@ -971,8 +1043,24 @@ class ICP:
             self._handle = IcpHandle(cfg, self.device, self.chain.error_minimizer, self.chain.matcher_knn,
                                      self.chain.matcher_max_dist, self.chain.outlier_max_dist,
                                      self.chain.outlier_min_dist, self.chain.outlier_median_factor,
-                                     robust=self.chain.robust, normals=self.chain.normals)
+                                     robust=self.chain.robust, normals=self.chain.normals,
+                                     covariance=self.chain.covariance)
         return self._handle
+
+    @property
+    def handle(self) -> IcpHandle:
+        """The IcpHandle the chain runs on (created on first use)."""
+        return self._ensure_handle()
+
+    def quality(self):
+        """IcpHandle.quality() of the last compute (a chain with PointToPlaneWithCovErrorMinimizer)."""
+        return self._ensure_handle().quality()
+
+    @property
+    def covariance(self) -> np.ndarray:
+        """errorMinimizer->getCovariance(): the 6x6 float64 covariance of the last compute.  Raises LsgpuError with the
+        library's code before a compute, after a singular H, or on a chain without PointToPlaneWithCovErrorMinimizer."""
+        return self.quality()["covariance"]
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
     def compute(self, reading_xyz1, reference_xyz1, T_init) -> np.ndarray:
