@@ -642,7 +642,8 @@ typedef struct lsgpu_loaded_chain {
   int has_normals;                  /* 0: none of these modules (normals holds lsgpu_normals_config_default)       */
   int reserved[6];                  /* [0] = 1: errorMinimizer PointToPlaneWithCovErrorMinimizer (icp.error_minimizer stays
                                      * LSGPU_MINIMIZER_POINT_TO_PLANE), [1] = the IEEE-754 bits of (float)sensorStdDev then, else 0;
-                                     * read them with lsgpu_loaded_chain_covariance.  [2..5] 0 */
+                                     * read them with lsgpu_loaded_chain_covariance.  [2], [3] = the number of cut modules in
+                                     * the reading / reference section (the modules: lsgpu_chain_load_cuts).  [4], [5] 0 */
 } lsgpu_loaded_chain;
 /* LSGPU_OK and *out (every byte of it, padding 0), or LSGPU_BAD_CONFIG with the reason -- the module's name in it, or the
  * section's for an unknown section -- written to why[0 .. why_cap), truncated if need be and always NUL-terminated; *out is
@@ -708,6 +709,50 @@ int lsgpu_point_to_plane_cov_solve(const double sums[44], float sensor_std_dev, 
  * PointToPlaneWithCovErrorMinimizer, else 0 and *sensor_std_dev untouched.  Host only.  (An exported function, not an inline one:
  * every function this header names is a symbol of the library, which is what the FFI front ends bind.) */
 int lsgpu_loaded_chain_covariance(const lsgpu_loaded_chain* c, float* sensor_std_dev);
+
+/* ---- cut modules in the ICP chain (DESIGN.md §3 "Cut modules in the ICP chain") ----------------------------------------
+ * A cut module is one of the four stateless per-point predicates of the input filter chain above: MaxDist- (type 1), MinDist-
+ * (2), BoundingBox- (3) and RemoveNaNDataPointsFilter (6), as lsgpu_point_filter records with the semantics stated there
+ * (`state` and `pad_` are not read).  In readingDataPointsFilters / referenceDataPointsFilters of an ICP chain they run INSIDE
+ * lsgpu_icp_compute / _compute_clouds / _compute_clouds_upload:
+ *   Reference section: up to LSGPU_CHAIN_CUT_MAX modules, any order, in front of the normals module (ssn_knn / sn_knn; none on a
+ *     point-to-point chain).  Applied to the reference as handed to compute (the assembled sub-map of _compute_clouds), before
+ *     the sampling filter and before centring.  sn_knn larger than the surviving count: LSGPU_BAD_ARG.
+ *   Reading section: up to LSGPU_CHAIN_CUT_MAX modules, any order, reading[0 .. reading_sampling_at) in front of
+ *     RandomSamplingDataPointsFilter (chain.reading_prob >= 0) and the rest behind it; all of them in front of the reading's
+ *     normals.  Applied to the reading in its own frame, before T_init; an uploaded slot is never modified.
+ *   Order of the surviving points is preserved; a cut module consumes no draw; RandomSampling draws once per point that reaches
+ *     it -- once per survivor of the modules in front of it, the draw's index the point's rank among them.  After the call the
+ *     library's draw stream stands where the sequential chain (lsgpu_apply_point_filters per section, reference first) leaves it.
+ *   A section that leaves no point: LSGPU_NO_CONVERGENCE ("... filter left no point").
+ * Each section is ONE fused pass whatever it holds (csrc/lsgpu_chain_cut.hip.h); a handle without cut modules enqueues what it
+ * always did.  The split-scan mode (lsgpu_icp_comm_init) refuses a handle with cut modules, and the other way round. */
+#define LSGPU_CHAIN_CUT_MAX 8
+typedef struct lsgpu_chain_cuts {
+  int n_reading, n_reference;   /* 0 .. LSGPU_CHAIN_CUT_MAX each                                                                 */
+  int reading_sampling_at;      /* reading modules in front of RandomSampling, 0 .. n_reading; ignored without RandomSampling   */
+  int reserved;                 /* 0 */
+  lsgpu_point_filter reading[LSGPU_CHAIN_CUT_MAX], reference[LSGPU_CHAIN_CUT_MAX];
+} lsgpu_chain_cuts;
+/* Gives the handle the cut modules (copied); NULL or two zero counts switch them off.  LSGPU_BAD_CONFIG, the module named in
+ * lsgpu_last_error and the handle left as it was: a type other than 1, 2, 3, 6, a dim outside -1..2 (Max- / MinDist), a count out of
+ * range, a handle with a communicator.  reading_sampling_at is clamped to 0 .. n_reading. */
+int lsgpu_icp_set_chain_cuts(lsgpu_icp* h, const lsgpu_chain_cuts* cuts);
+/* The fused pass of one section alone (kernel-level entry).  side 0: cuts->reading with RandomSampling of probability prob at
+ * position cuts->reading_sampling_at (prob < 0: no RandomSampling); side 1: cuts->reference, prob ignored.  The handle's own
+ * cut modules are not read.  seed as lsgpu_apply_point_filters; xyz1 / out_xyz1 host or device pointers, out_xyz1 with room
+ * for n points.  CONTRACT: the output points and the draws consumed equal lsgpu_apply_point_filters with the same modules in
+ * the same order (RandomSampling as a type 5 module at its position), except that a section emptied by a module that is not
+ * its last returns LSGPU_OK with *n_out = 0 where the sequential chain reports LSGPU_NO_CONVERGENCE.  n == 0 with a module:
+ * LSGPU_NO_CONVERGENCE, as there. */
+int lsgpu_icp_filter_section(lsgpu_icp* h, const lsgpu_chain_cuts* cuts, int side, float prob, const float* xyz1, int64_t n,
+                             int64_t seed, float* out_xyz1, int64_t* n_out);
+/* The cut modules of a YAML document: the rules, the refusals and the texts of lsgpu_chain_load (which writes their counts to
+ * lsgpu_loaded_chain.reserved[2], [3]: reading, reference), the modules themselves in *out (every byte, padding 0).
+ * Parameters and defaults: MaxDist {dim -1, maxDist 1}, MinDist {dim -1, minDist 1}, BoundingBox {xMin -1, xMax 1, yMin -1,
+ * yMax 1, zMin -1, zMax 1, removeInside 1}, RemoveNaN {} -- those of the input filter chain's front ends.  dim an integer in
+ * -1..2, removeInside 0 or 1, the limits numbers (inf allowed).  Host only. */
+int lsgpu_chain_load_cuts(const lsgpu_yaml_module* mods, int n_mods, lsgpu_chain_cuts* out, char* why, int why_cap);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

@@ -134,6 +134,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_covariance: " + why);
       }
+      if (has_cuts_ && lsgpu_icp_set_chain_cuts(h_, &cuts_) != LSGPU_OK) {   // MaxDist- / MinDist- / BoundingBox- / RemoveNaN of the filter sections
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_chain_cuts: " + why);
+      }
     }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
@@ -168,6 +173,8 @@ class LsgpuICP {
     if (has_normals_) normals_ = *parsed.normalsConfig();
     lsgpu_covariance_config_default(&cov_);
     has_cov_ = parsed.covarianceConfig(&cov_.sensor_std_dev);
+    has_cuts_ = parsed.chainCuts() != nullptr;
+    if (has_cuts_) cuts_ = *parsed.chainCuts();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -184,6 +191,8 @@ class LsgpuICP {
   bool has_normals_ = false;                            // ... if the chain holds any of them
   lsgpu_covariance_config cov_{};                       // PointToPlaneWithCovErrorMinimizer's sensorStdDev ...
   bool has_cov_ = false;                                // ... if the chain names the module
+  lsgpu_chain_cuts cuts_{};                             // the cut modules of the two filter sections ...
+  bool has_cuts_ = false;                               // ... if the chain holds any
   int64_t seed_ = -1;
 };
 

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "lsgpu_filter_voxel_grid_points",
     "lsgpu_covariance_config_default", "lsgpu_icp_set_covariance", "lsgpu_icp_get_quality", "lsgpu_point_to_plane_cov",
     "lsgpu_point_to_plane_cov_solve", "lsgpu_loaded_chain_covariance",
+    "lsgpu_icp_set_chain_cuts", "lsgpu_icp_filter_section", "lsgpu_chain_load_cuts",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -202,6 +203,16 @@ class PointFilter(C.Structure):
                 ("state", C.c_double)]
 
 
+# the cut modules of an ICP chain's filter sections (LSGPU_CHAIN_CUT_MAX, lsgpu_chain_cuts)
+CHAIN_CUT_MAX = 8
+
+
+class ChainCuts(C.Structure):
+    """lsgpu_chain_cuts: MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter of the two filter sections."""
+    _fields_ = [("n_reading", C.c_int), ("n_reference", C.c_int), ("reading_sampling_at", C.c_int), ("reserved", C.c_int),
+                ("reading", PointFilter * CHAIN_CUT_MAX), ("reference", PointFilter * CHAIN_CUT_MAX)]
+
+
 FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_FIX_STEP_SAMPLING, FILTER_RANDOM_SAMPLING, FILTER_REMOVE_NAN = 1, 2, 3, 4, 5, 6
 FILTER_VOXEL_GRID = 7   # VoxelGridDataPointsFilter: v[0..2] = vSizeX/Y/Z, flag = useCentroid, dim = averageExistingDescriptors
 
@@ -334,6 +345,9 @@ def lib() -> C.CDLL:
                                            C.POINTER(C.c_double)]
     L.lsgpu_point_to_plane_cov_solve.argtypes = [C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_double)]
     L.lsgpu_loaded_chain_covariance.argtypes = [C.POINTER(LoadedChain), C.POINTER(C.c_float)]
+    L.lsgpu_icp_set_chain_cuts.argtypes = [vp, C.POINTER(ChainCuts)]
+    L.lsgpu_icp_filter_section.argtypes = [vp, C.POINTER(ChainCuts), C.c_int, C.c_float, fp, i64, i64, fp, C.POINTER(i64)]
+    L.lsgpu_chain_load_cuts.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(ChainCuts), C.c_char_p, C.c_int]
     _lib = L
     return L
 

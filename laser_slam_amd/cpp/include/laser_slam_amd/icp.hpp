@@ -261,6 +261,7 @@ class ICP {
     std::memset(&loaded_, 0, sizeof(loaded_));
     lsgpu_icp_config_default(&loaded_.icp);
     lsgpu_chain_config_default(&loaded_.chain);
+    std::memset(&cuts_, 0, sizeof(cuts_));
     release();
   }
 
@@ -278,7 +279,13 @@ class ICP {
     lsgpu_loaded_chain loaded;
     char why[512];
     if (lsgpu_chain_load(list.data(), (int)list.size(), &loaded, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
+    // the cut modules of the filter sections (MaxDist-, MinDist-, BoundingBox-, RemoveNaNDataPointsFilter): same rules, the modules
+    lsgpu_chain_cuts cuts;
+    std::memset(&cuts, 0, sizeof(cuts));
+    if ((loaded.reserved[2] || loaded.reserved[3]) &&
+        lsgpu_chain_load_cuts(list.data(), (int)list.size(), &cuts, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
     loaded_ = loaded;
+    cuts_ = cuts;
     release();
   }
 
@@ -453,6 +460,9 @@ class ICP {
   const lsgpu_robust_config* robustFilter() const { return loaded_.has_robust ? &loaded_.robust : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
   // SurfaceNormalOutlierFilter / reading normals / the orientation pairs (nullptr: none of these modules)
   const lsgpu_normals_config* normalsConfig() const { return loaded_.has_normals ? &loaded_.normals : nullptr; }
+  // the cut modules of the two filter sections (nullptr: none)
+  const lsgpu_chain_cuts* chainCuts() const { return cuts_.n_reading || cuts_.n_reference ? &cuts_ : nullptr; }
+  const lsgpu_loaded_chain& loadedChain() const { return loaded_; }
 
  private:
   using Module = detail::YamlModule;
@@ -519,6 +529,11 @@ class ICP {
       release();
       throw ConfigError(msg);
     }
+    if (chainCuts() && lsgpu_icp_set_chain_cuts(h_, &cuts_) != LSGPU_OK) {
+      const std::string msg = std::string("lsgpu_icp_set_chain_cuts: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
   }
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
   void check(int rc, const char* what) {
@@ -531,6 +546,7 @@ class ICP {
 
   int device_ = 0;
   lsgpu_loaded_chain loaded_{};   // what loadFromYaml / setDefault left: the handle's config, the filters of compute()
+  lsgpu_chain_cuts cuts_{};       // ... and the cut modules of its filter sections (lsgpu_chain_load_cuts)
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;

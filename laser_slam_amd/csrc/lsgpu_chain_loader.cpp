@@ -32,6 +32,8 @@ const char* const kOneReference = "referenceDataPointsFilters: one module at mos
 const char* const kSurfaceNormalParams = "knn epsilon maxDist keepNormals keepDensities keepEigenValues keepEigenVectors "
                                          "keepMatchedIds keepMeanDist sortEigen smoothNormals";
 
+const char* const kBoundingBoxParams = "xMin xMax yMin yMax zMin zMax removeInside";
+
 bool listed(const char* list, const char* word) {   // is `word` one of the space-separated words of `list`?
   const size_t n = std::strlen(word);
   for (const char* p = list; *p;) {
@@ -45,6 +47,7 @@ bool listed(const char* list, const char* word) {   // is `word` one of the spac
 
 struct Load {
   lsgpu_loaded_chain out;
+  lsgpu_chain_cuts cuts;                  // the cut modules of the two filter sections (lsgpu_chain_load_cuts)
   const lsgpu_yaml_module* m = nullptr;   // the module being read
   // where a filter section has got to: 1 RandomSampling (reading) / the module that gives the normals (reference),
   // 2 SurfaceNormal on the reading, 3 ObservationDirection, 4 OrientNormals
@@ -110,8 +113,51 @@ void random_sampling(Load& l) {
     refuse("readingDataPointsFilters: SurfaceNormalDataPointsFilter before RandomSamplingDataPointsFilter is not "
            "implemented (the normals would have to be gathered through the sampling)");
   l.out.chain.reading_prob = (float)l.finite("prob", 0.75);
+  l.cuts.reading_sampling_at = l.cuts.n_reading;   // the cut modules so far stand in front of it
   l.stage[0] = 1;
 }
+// The cut modules (MaxDist-, MinDist-, BoundingBox-, RemoveNaNDataPointsFilter) of a filter section: any number up to
+// LSGPU_CHAIN_CUT_MAX, any order, around RandomSampling on the reading, and in front of whatever produces or reads normals
+lsgpu_point_filter& cut_slot(Load& l) {
+  const int s = l.side();
+  if (l.stage[s] >= (s == 0 ? 2 : 1))
+    refuse(std::string(l.m->section) + ": " + l.name() + " behind the module that produces the normals is not implemented: the "
+           "normals would have to be gathered through the cut");
+  int& n = s == 0 ? l.cuts.n_reading : l.cuts.n_reference;
+  if (n == LSGPU_CHAIN_CUT_MAX)
+    refuse(std::string(l.m->section) + ": " + l.name() + " is a ninth cut module (at most " + std::to_string(LSGPU_CHAIN_CUT_MAX) +
+           " of MaxDist-, MinDist-, BoundingBox- and RemoveNaNDataPointsFilter in a section)");
+  return (s == 0 ? l.cuts.reading : l.cuts.reference)[n++];   // (zero-filled by load())
+}
+int cut_dim(const Load& l) {
+  const double d = l.num("dim", -1);
+  if (!l.whole(d) || d < -1.0 || d > 2.0) refuse(l.name() + ": dim must be an integer in [-1, 2]");
+  return (int)d;
+}
+void cut_max_dist(Load& l) {
+  const int dim = cut_dim(l);
+  const float v = (float)l.num("maxDist", 1.0);
+  lsgpu_point_filter& f = cut_slot(l);
+  f.type = LSGPU_FILTER_MAX_DIST; f.dim = dim; f.v[0] = v;
+}
+void cut_min_dist(Load& l) {
+  const int dim = cut_dim(l);
+  const float v = (float)l.num("minDist", 1.0);
+  lsgpu_point_filter& f = cut_slot(l);
+  f.type = LSGPU_FILTER_MIN_DIST; f.dim = dim; f.v[0] = v;
+}
+void cut_bounding_box(Load& l) {
+  const char* keys[6] = {"xMin", "xMax", "yMin", "yMax", "zMin", "zMax"};
+  float v[6];
+  for (int i = 0; i < 6; ++i) v[i] = (float)l.num(keys[i], (i & 1) ? 1.0 : -1.0);
+  const double ri = l.num("removeInside", 1);
+  if (ri != 0.0 && ri != 1.0) refuse(l.name() + ": removeInside must be 0 or 1");
+  lsgpu_point_filter& f = cut_slot(l);
+  f.type = LSGPU_FILTER_BOUNDING_BOX; f.flag = (int)ri;
+  for (int i = 0; i < 6; ++i) f.v[i] = v[i];
+}
+void cut_remove_nan(Load& l) { cut_slot(l).type = LSGPU_FILTER_REMOVE_NAN; }
+
 void reading_normals(Load& l) { l.out.normals.reading_sn_knn = surface_normal_knn(l); l.stage[0] = 2; }
 void sampling_surface_normal(Load& l) {
   if (l.stage[1]) refuse(kOneReference);
@@ -240,6 +286,14 @@ const Row kRows[] = {
     {"referenceDataPointsFilters", "SurfaceNormalDataPointsFilter", kSurfaceNormalParams, false, reference_normals},
     {"referenceDataPointsFilters", "ObservationDirectionDataPointsFilter", "x y z", true, observation_direction},
     {"referenceDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
+    {"readingDataPointsFilters", "MaxDistDataPointsFilter", "dim maxDist", false, cut_max_dist},
+    {"readingDataPointsFilters", "MinDistDataPointsFilter", "dim minDist", false, cut_min_dist},
+    {"readingDataPointsFilters", "BoundingBoxDataPointsFilter", kBoundingBoxParams, false, cut_bounding_box},
+    {"readingDataPointsFilters", "RemoveNaNDataPointsFilter", "", false, cut_remove_nan},
+    {"referenceDataPointsFilters", "MaxDistDataPointsFilter", "dim maxDist", false, cut_max_dist},
+    {"referenceDataPointsFilters", "MinDistDataPointsFilter", "dim minDist", false, cut_min_dist},
+    {"referenceDataPointsFilters", "BoundingBoxDataPointsFilter", kBoundingBoxParams, false, cut_bounding_box},
+    {"referenceDataPointsFilters", "RemoveNaNDataPointsFilter", "", false, cut_remove_nan},
     {"matcher", "KDTreeMatcher", "knn epsilon searchType maxDist", false, kd_tree_matcher},
     {"outlierFilters", "TrimmedDistOutlierFilter", "ratio", true, trimmed_dist},
     {"outlierFilters", "MaxDistOutlierFilter", "maxDist", true, max_dist},
@@ -278,6 +332,8 @@ void finish(Load& l) {
                      : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
     if (with) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + with + " (the covariance is implemented for knn 1 and binary distance filters)");
   }
+  if (o.chain.reading_prob < 0.f) l.cuts.reading_sampling_at = l.cuts.n_reading;   // (no RandomSampling: not read)
+  o.reserved[2] = l.cuts.n_reading; o.reserved[3] = l.cuts.n_reference;
   o.has_robust = l.robust ? 1 : 0;
   o.has_normals = o.normals.max_angle >= 0.f || o.normals.reading_sn_knn != 0 || o.normals.reading_orient != 0 || o.normals.reference_orient != 0;
 }
@@ -286,6 +342,7 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
   // libpointmatcher's loadFromYaml starts from EMPTY chains: a section the file does not mention means "no such module",
   // not "the default module"
   std::memset(&l.out, 0, sizeof(l.out));
+  std::memset(&l.cuts, 0, sizeof(l.cuts));
   lsgpu_icp_config_default(&l.out.icp);
   l.out.icp.trim_ratio = 1.0f;
   l.out.icp.min_diff_rot = -1.f; l.out.icp.min_diff_trans = -1.f; l.out.icp.smooth_length = 1;   // never satisfied
@@ -315,9 +372,10 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
 
 extern "C" {
 
-int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* out, char* why, int why_cap) {
+// both entry points: the one walk over the modules, then what the caller asked for (`chain` or `cuts`, the other NULL)
+static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
-  if (!out || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
+  if ((!chain && !cuts) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
   for (int i = 0; i < n_mods; ++i) {
     if (!mods[i].section || !mods[i].name || mods[i].n_params < 0 || (mods[i].n_params > 0 && !mods[i].params)) return LSGPU_BAD_ARG;
     for (int p = 0; p < mods[i].n_params; ++p)
@@ -326,7 +384,8 @@ int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
   try {
     Load l;
     load(mods, n_mods, l);
-    *out = l.out;
+    if (chain) *chain = l.out;
+    if (cuts) *cuts = l.cuts;
     return LSGPU_OK;
   } catch (const Refusal& r) {
     if (why && why_cap > 0) std::snprintf(why, (size_t)why_cap, "%s", r.why.c_str());
@@ -334,6 +393,16 @@ int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
   } catch (const std::exception&) {   // (no exception crosses the ABI)
     return LSGPU_BAD_ARG;
   }
+}
+
+int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  return out ? load_into(mods, n_mods, out, nullptr, why, why_cap) : LSGPU_BAD_ARG;
+}
+
+int lsgpu_chain_load_cuts(const lsgpu_yaml_module* mods, int n_mods, lsgpu_chain_cuts* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  return out ? load_into(mods, n_mods, nullptr, out, why, why_cap) : LSGPU_BAD_ARG;
 }
 
 int lsgpu_loaded_chain_covariance(const lsgpu_loaded_chain* c, float* sensor_std_dev) {

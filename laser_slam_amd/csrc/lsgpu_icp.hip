@@ -290,6 +290,11 @@ struct lsgpu_icp {
   DevBuf<float4> flt_in, flt_in2, flt_ref, flt_rd;
   DevBuf<float4> vgf_out;   // VoxelGridDataPointsFilter (lsgpu_voxel_filter.hip.h): the voxels' points at their first points' positions
   DevBuf<float> flt_nrm;
+  // cut modules of the ICP chain's filter sections (lsgpu_icp_set_chain_cuts; lsgpu_chain_cut.hip.h)
+  bool cuts_on = false;
+  lsgpu_chain_cuts cuts{};
+  DevBuf<uint32_t> cut_blk;   // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
+  DevBuf<float4> cut_ref;     // the reference behind its cut modules
   float* draws_pinned = nullptr;  // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
@@ -404,6 +409,26 @@ static void order_after_tail(lsgpu_icp* h, hipStream_t s) {
   if (h->tail_pending && s && h->ev_tail && hipStreamWaitEvent(s, h->ev_tail, 0) != hipSuccess) (void)hipGetLastError();
 }
 
+// what lsgpu_icp_set_chain_cuts / lsgpu_icp_filter_section refuse in a lsgpu_chain_cuts, the module named; empty: nothing
+static std::string chain_cuts_why(const lsgpu_chain_cuts* c) {
+  const char* const names[7] = {nullptr, "MaxDistDataPointsFilter", "MinDistDataPointsFilter", "BoundingBoxDataPointsFilter", nullptr, nullptr,
+                                "RemoveNaNDataPointsFilter"};
+  const char* const all = "MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter";
+  for (int s = 0; s < 2; ++s) {
+    const int n = s == 0 ? c->n_reading : c->n_reference;
+    const std::string sec = s == 0 ? "readingDataPointsFilters: " : "referenceDataPointsFilters: ";
+    if (n < 0 || n > LSGPU_CHAIN_CUT_MAX) return sec + "0 to " + std::to_string(LSGPU_CHAIN_CUT_MAX) + " cut modules (" + all + "), not " + std::to_string(n);
+    for (int k = 0; k < n; ++k) {
+      const lsgpu_point_filter& f = (s == 0 ? c->reading : c->reference)[k];
+      const char* name = f.type >= 1 && f.type <= 6 ? names[f.type] : nullptr;
+      if (!name) return sec + "module " + std::to_string(k) + " has type " + std::to_string(f.type) + ", which is no cut module (" + all + ": 1, 2, 3, 6)";
+      if ((f.type == LSGPU_FILTER_MAX_DIST || f.type == LSGPU_FILTER_MIN_DIST) && (f.dim < -1 || f.dim > 2))
+        return sec + name + ": dim must be in [-1, 2]";
+    }
+  }
+  return std::string();   // (reading_sampling_at is clamped to 0 .. n_reading where it is read: without RandomSampling it means nothing)
+}
+
 static constexpr int kNeBlocksMax = 2048;
 static const int kNeBlocks = tuning().ne_blocks;   // 64 .. kNeBlocksMax (lsgpu_tuning.h)
 static constexpr int kStatBlocks = 512;
@@ -514,6 +539,18 @@ int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
   return LSGPU_OK;
 }
 
+int lsgpu_icp_set_chain_cuts(lsgpu_icp* h, const lsgpu_chain_cuts* cuts) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cuts || (cuts->n_reading == 0 && cuts->n_reference == 0)) { h->cuts_on = false; return LSGPU_OK; }
+  const std::string why = chain_cuts_why(cuts);
+  if (!why.empty()) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (h->comm) { h->err = "MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the ICP chain: the split-scan mode does not run them"; return LSGPU_BAD_CONFIG; }
+  h->cuts = *cuts;
+  h->cuts_on = true;
+  return LSGPU_OK;
+}
+
 int lsgpu_icp_get_quality(lsgpu_icp* h, lsgpu_icp_quality* out) {
   if (!h || !out) return LSGPU_BAD_ARG;
   h->err.clear();
@@ -591,7 +628,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->ref_in.release(); h->nrm_in.release(); h->scr_main.release(); h->scr_side.release();
   h->pts.release();
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
-  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
+  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->cut_blk.release(); h->cut_ref.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
@@ -1258,6 +1295,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
   }
   if (h->cov_on) {
     h->err = "comm_init: the split-scan mode does not run PointToPlaneWithCovErrorMinimizer";
+    return LSGPU_BAD_CONFIG;
+  }
+  if (h->cuts_on) {
+    h->err = "comm_init: the split-scan mode does not run MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the ICP chain";
     return LSGPU_BAD_CONFIG;
   }
   if (chain_on(h)) {
@@ -2058,6 +2099,59 @@ static int random_sampling_device(lsgpu_icp* h, const float4* src, int64_t n, fl
   return compact_kept_wait(h, n_out);
 }
 
+// The cut modules of one filter section as the pass takes them (rs: RandomSampling stands among the reading's)
+static CutSectionDev cut_section_of(const lsgpu_chain_cuts& c, int side, bool rs) {
+  CutSectionDev d;
+  std::memset(&d, 0, sizeof(d));
+  const lsgpu_point_filter* m = side == 0 ? c.reading : c.reference;
+  d.n = std::max(0, std::min(side == 0 ? c.n_reading : c.n_reference, kCutMax));
+  d.n_pre = side == 0 && rs ? std::max(0, std::min(c.reading_sampling_at, d.n)) : d.n;
+  for (int k = 0; k < d.n; ++k) {
+    d.m[k].type = m[k].type; d.m[k].dim = m[k].dim; d.m[k].flag = m[k].flag;
+    for (int i = 0; i < 6; ++i) d.m[k].v[i] = m[k].v[i];
+  }
+  return d;
+}
+// A filter section in one pass on the current lane (lsgpu_chain_cut.hip.h): src (n points, device) -> the kept points at the
+// front of dst (device, room for n, not src), order preserved; rs: keep = pre && draws[rank of pre] < prob && post, `draws`
+// (device) holding at least n.  The launches are the same whatever cs holds; the totals are on their way to the host ...
+static int cut_section_enqueue(lsgpu_icp* h, const CutSectionDev& cs, bool rs, float prob, const float* draws, const float4* src,
+                               int64_t n, float4* dst) {
+  const int nb = nblk(n);
+  const size_t row = ((size_t)nb + 3) & ~(size_t)3;
+  HIPC(h->cut_blk.reserve(4 * row));
+  uint32_t *cnt_a = h->cut_blk.p, *off_a = cnt_a + row, *cnt_b = off_a + row, *off_b = cnt_b + row;
+  hipStream_t st = h->lane.stream;
+  hipLaunchKernelGGL((k_cut_pass<0, false>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, (const float*)nullptr, 0.f,
+                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, cnt_a, (float4*)nullptr);
+  int rc = scan_u32(h, cnt_a, off_a, (size_t)nb);
+  if (rc) return rc;
+  if (!rs) {
+    hipLaunchKernelGGL((k_cut_pass<2, false>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, (const float*)nullptr, 0.f,
+                       (const uint32_t*)nullptr, (const uint32_t*)off_a, (uint32_t*)nullptr, dst);
+    HIPC(hipGetLastError());
+    return scan_totals_enqueue(h, nullptr, nullptr, 0, cnt_a, off_a, (size_t)nb);
+  }
+  hipLaunchKernelGGL((k_cut_pass<1, true>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, draws, prob, (const uint32_t*)off_a,
+                     (const uint32_t*)nullptr, cnt_b, (float4*)nullptr);
+  rc = scan_u32(h, cnt_b, off_b, (size_t)nb);
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_cut_pass<2, true>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, draws, prob, (const uint32_t*)off_a,
+                     (const uint32_t*)off_b, (uint32_t*)nullptr, dst);
+  HIPC(hipGetLastError());
+  return scan_totals_enqueue(h, cnt_a, off_a, (size_t)nb, cnt_b, off_b, (size_t)nb);
+}
+// ... and the host's wait for them: the points kept, and `pre` -- the points that reached RandomSampling, one draw each
+// (without it: the points kept)
+static int cut_section_wait(lsgpu_icp* h, bool rs, int64_t* pre, int64_t* kept) {
+  uint32_t a = 0, b = 0;
+  const int rc = scan_totals_wait(h, &a, &b);
+  if (rc) return rc;
+  *kept = b;
+  *pre = rs ? a : b;
+  return LSGPU_OK;
+}
+
 // SurfaceNormalDataPointsFilter on the reference the handle holds (set_reference has just been enqueued on h->stream):
 // normals of the sorted points into h->nrm; ids / d2 (device, nullable) in the order the cloud was given.
 template <int K>
@@ -2155,6 +2249,46 @@ int lsgpu_icp_filter_reading(lsgpu_icp* h, const float* xyz1, int64_t n, float p
   return LSGPU_OK;
 }
 
+int lsgpu_icp_filter_section(lsgpu_icp* h, const lsgpu_chain_cuts* cuts, int side, float prob, const float* xyz1, int64_t n,
+                             int64_t seed, float* out_xyz1, int64_t* n_out) {
+  if (!h || !cuts || !n_out || (side != 0 && side != 1) || n < 0 || (n > 0 && (!xyz1 || !out_xyz1))) return LSGPU_BAD_ARG;
+  h->err.clear();
+  *n_out = 0;
+  if (n > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
+  const std::string why = chain_cuts_why(cuts);
+  if (!why.empty()) { h->err = why; return LSGPU_BAD_CONFIG; }
+  const bool rs = side == 0 && prob >= 0.f;
+  if (rs && !(prob <= 1.f)) { h->err = "filter_section: RandomSamplingDataPointsFilter: prob must be in [0, 1]"; return LSGPU_BAD_CONFIG; }
+  if (seed >= 0) DrawStream::global().take(seed, 0, nullptr);
+  const CutSectionDev cs = cut_section_of(*cuts, side, rs);
+  if (n == 0) {   // as lsgpu_apply_point_filters: an empty chain is a no-op, a module handed an empty cloud is an error
+    if (cs.n == 0 && !rs) return LSGPU_OK;
+    h->err = "filter_section: no points to filter";
+    return LSGPU_NO_CONVERGENCE;
+  }
+  HIPC(hipSetDevice(h->device));
+  const float4* src = nullptr;
+  int rc = stage_points(h, xyz1, n, h->flt_in, &src);
+  if (rc) return rc;
+  OutStage<float4> ox;
+  // (the pass must not write where it reads: a caller's device buffer that is the input goes through the handle's)
+  if (static_cast<const void*>(out_xyz1) == static_cast<const void*>(xyz1)) { ox.user = out_xyz1; ox.staged = false; HIPC(h->flt_rd.reserve(n)); ox.p = h->flt_rd.p; }
+  else if ((rc = ox.open(h, out_xyz1, h->flt_rd, n))) return rc;
+  if (rs) {
+    rc = upload_draws_begin(h, -1, (size_t)n);   // at most one draw per point; the stream stays locked until the commit
+    if (rc) return rc;
+  }
+  int64_t reached = 0, kept = 0;
+  rc = cut_section_enqueue(h, cs, rs, prob, h->ssn_draws.p, src, n, ox.p);
+  if (!rc) rc = cut_section_wait(h, rs, &reached, &kept);
+  if (rs) DrawStream::global().commit(rc ? 0 : (size_t)reached);   // one draw per point that reached the module
+  if (rc) return rc;
+  *n_out = kept;
+  if (ox.p != static_cast<float4*>(ox.user)) { if ((rc = ox.send(h, ox.p, (size_t)kept))) return rc; }
+  HIPC(hipStreamSynchronize(h->stream));
+  return LSGPU_OK;
+}
+
 int lsgpu_icp_reading_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, int orient, const float sensor[3],
                               float* out_normals) {
   if (!h || !out_normals || orient < 0 || orient > 2 || (orient && !sensor)) return LSGPU_BAD_ARG;
@@ -2240,6 +2374,10 @@ struct ComputeRun {
   const float4 *src = nullptr, *ref_pts = nullptr; const float* ref_nrm = nullptr;   // the reference on the device: as given, as the grid gets it
   const float4 *rd_src = nullptr, *rd_dev = nullptr; int64_t nrf = 0, nqf = 0;       // the reading: as given, as the loop gets it; points kept
   AlignExtras extras{};   // what finish() tells the align
+  // lsgpu_icp_set_chain_cuts: the sections' cut modules.  rd_pre_cuts: some stand in front of RandomSampling, so the number of
+  // draws the reading consumes is the number of points that reach it -- known when the pass's totals are on the host
+  const lsgpu_chain_cuts* cuts = nullptr; bool rd_cuts = false, ref_cuts = false, rd_rs = false, rd_pre_cuts = false;
+  int64_t nrc = 0; size_t rd_first_draw = 0;   // the reference's points behind its cut modules; the reading's first draw
   // every return path drains the side stream, joins the uploader and drains its stream: a pinned host reading is read by DMA,
   // and the caller may free or reuse it as soon as this call has returned, error or not (after a completed alignment the
   // copy is long over and the wait returns at once)
@@ -2279,6 +2417,10 @@ struct ComputeRun {
     // Both are chains of short launches that leave most of the chip idle; side by side the shorter one disappears
     // (LSGPU_NO_SIDE_STREAM: one after the other).
     side = tuning().side_stream && !h->comm && !rd_normals;
+    cuts = h->cuts_on ? &h->cuts : nullptr;
+    rd_rs = chain->reading_prob >= 0.f;
+    rd_cuts = cuts && cuts->n_reading > 0; ref_cuts = cuts && cuts->n_reference > 0;
+    rd_pre_cuts = rd_cuts && rd_rs && cut_section_of(*cuts, 0, true).n_pre > 0;
     return LSGPU_OK;
   }
 
@@ -2318,16 +2460,28 @@ struct ComputeRun {
   }
 
   int filter_reference() {   // step 1: reference filter (yaml:5-7)
-    ref_pts = src; nrf = nr;   // (no reference filter module: the reference as given, no normals, no draw)
+    nrc = nr;
+    if (ref_cuts) {   // the cut modules stand in front of the normals module: the reference as handed over, before anything else
+      HIPC(h->cut_ref.reserve(nr));
+      int64_t reached = 0;
+      int rc = cut_section_enqueue(h, cut_section_of(*cuts, 1, false), false, 0.f, nullptr, src, nr, h->cut_ref.p);
+      if (!rc) rc = cut_section_wait(h, false, &reached, &nrc);   // (ssn_device and ref_build_front take the count on the host)
+      if (rc) return rc;
+      if (nrc <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+      if (nrc < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
+      src = h->cut_ref.p;
+    }
+    ref_pts = src; nrf = nrc;   // (no reference filter module: the reference as given, no normals, no draw)
     if (ref_filter) {
-      HIPC(h->flt_ref.reserve(nr)); HIPC(h->flt_nrm.reserve(3 * nr));
-      const int rc = ssn_device(h, src, nr, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
+      HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
+      const int rc = ssn_device(h, src, nrc, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
       if (rc) return rc;
       if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
       ref_pts = h->flt_ref.p; ref_nrm = h->flt_nrm.p;
     }
     // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
-    draws.commit_now(draws.used + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq));
+    // (not with cut modules in front of RandomSampling: reading_count_wait commits then)
+    if (!rd_pre_cuts) draws.commit_now(draws.used + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq));
     return LSGPU_OK;
   }
 
@@ -2339,6 +2493,20 @@ struct ComputeRun {
       HIPC(hipStreamWaitEvent(h->lane.stream, h->copy_done, 0));
     }
     rd_dev = rd_src;
+    if (rd_cuts) {   // the section in one pass, RandomSampling (if any) inside it; the slot / the caller's cloud is only read
+      HIPC(h->flt_rd.reserve(nq));
+      rd_dev = h->flt_rd.p;
+      const float* dr = nullptr;
+      if (rd_rs) {
+        rd_first_draw = draws.used;
+        if (!rd_pre_cuts) draws.used = rd_first_draw + (size_t)nq;   // one draw per point; else: per point that reaches the module
+        const int rcd = draws.ready();
+        if (rcd) return rcd;
+        dr = h->ssn_draws.p + rd_first_draw;
+      }
+      const int rc = cut_section_enqueue(h, cut_section_of(*cuts, 0, rd_rs), rd_rs, chain->reading_prob, dr, rd_src, nq, h->flt_rd.p);
+      return rc || defer_wait ? rc : reading_count_wait();
+    }
     if (chain->reading_prob < 0.f) {
       // no readingDataPointsFilters section: upstream runs no module at all -- every point, NO rand() call (a
       // RandomSampling module with prob 1 would consume nq draws and drop the points whose draw rounds to 1.0f)
@@ -2348,6 +2516,16 @@ struct ComputeRun {
     HIPC(h->flt_rd.reserve(nq));
     rd_dev = h->flt_rd.p;
     return random_sampling_device(h, rd_src, nq, chain->reading_prob, -1, h->flt_rd.p, &nqf, &draws, defer_wait);
+  }
+
+  // the host's wait for the number of reading points kept (current lane); with cut modules in front of RandomSampling also
+  // for the number that reached it: the draws the call consumes are known, the stream can go
+  int reading_count_wait() {
+    if (!rd_cuts) return compact_kept_wait(h, &nqf);
+    int64_t reached = 0;
+    const int rc = cut_section_wait(h, rd_rs, &reached, &nqf);
+    if (!rc && rd_pre_cuts) { draws.used = rd_first_draw + (size_t)reached; draws.commit_now(draws.used); }
+    return rc;
   }
 
   // The reading's side with the side stream on.  Order of the host's work (round 5, from rocprofv3's timeline of a step).
@@ -2373,7 +2551,7 @@ struct ComputeRun {
   }
   int order_queries_on_side_lane() {
     LaneScope on_side(h, h->side_lane());
-    const int rc = chain->reading_prob >= 0.f ? compact_kept_wait(h, &nqf) : LSGPU_OK;   // (the number of points kept)
+    const int rc = (chain->reading_prob >= 0.f || rd_cuts) ? reading_count_wait() : LSGPU_OK;   // (the number of points kept)
     return rc || nqf <= 0 ? rc : prepare_queries(h, reinterpret_cast<const float*>(rd_dev), nqf, Mat34{}, /*gather*/ false);
   }
   int move_queries() {   // the mean is known and the main stream is busy -- now the queries' side

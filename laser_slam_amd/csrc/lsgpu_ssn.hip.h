@@ -14,6 +14,7 @@
 #include "lsgpu_common.hip.h"
 #include "lsgpu_box_normal.h"
 #include "lsgpu_segsort.hip.h"
+#include "lsgpu_chain_cut.hip.h"
 
 namespace lsgpu {
 
@@ -424,7 +425,8 @@ __global__ __launch_bounds__(256) void k_voxel_centroids(const float4* __restric
 
 // ---------------------------------------------------------------- input filter chain (include/lsgpu_icp.h)
 // One predicate per launch: keep[i] = 1 if point i survives filter f.  laser_slam/src/laser_track.cpp:146
-// (input_filters_.apply(scan.scan)); semantics restated in the header.
+// (input_filters_.apply(scan.scan)); semantics restated in the header.  Max- / MinDist, BoundingBox and RemoveNaN are
+// the predicates of lsgpu_chain_cut.hip.h, shared with the ICP chain's cut pass.
 struct PointFilterDev {
   int type, dim, flag;
   float v[6];
@@ -439,25 +441,15 @@ __global__ __launch_bounds__(256) void k_point_filter_select(const float4* __res
   const float4 p = src[i];
   bool k = true;
   if (f.type == 1 || f.type == 2) {  // Max / MinDist
-    // upstream asymmetry (libpointmatcher MaxDist.cpp / MinDist.cpp, from knowledge): the radial branch of both compares
-    // the norm with |limit|; on ONE axis MaxDist compares the SIGNED coordinate (x < maxDist keeps every negative x),
-    // MinDist the absolute one
-    const float c = f.dim == 0 ? p.x : f.dim == 1 ? p.y : p.z;
-    if (f.dim < 0) {
-      const float val = sqrtf(__fmaf_rn(p.z, p.z, __fmaf_rn(p.y, p.y, p.x * p.x)));
-      k = f.type == 1 ? val < fabsf(f.v[0]) : val > fabsf(f.v[0]);
-    } else {
-      k = f.type == 1 ? c < f.v[0] : fabsf(c) > f.v[0];
-    }
+    k = cut_keep_dist(p, f);
   } else if (f.type == 3) {          // BoundingBox
-    const bool in = p.x > f.v[0] && p.x < f.v[1] && p.y > f.v[2] && p.y < f.v[3] && p.z > f.v[4] && p.z < f.v[5];
-    k = f.flag ? !in : in;
+    k = cut_keep_box(p, f);
   } else if (f.type == 4) {          // FixStepSampling
     k = (uint32_t)i >= f.phase && ((uint32_t)i - f.phase) % f.step == 0u;
   } else if (f.type == 5) {          // RandomSampling
     k = draws[i] < f.v[0];
-  } else if (f.type == 6) {          // RemoveNaN: a column with a NaN in any feature row goes (colArray == colArray).all()
-    k = p.x == p.x && p.y == p.y && p.z == p.z && p.w == p.w;
+  } else if (f.type == 6) {          // RemoveNaN
+    k = cut_keep_nan(p);
   }
   keep[i] = k ? 1u : 0u;
 }

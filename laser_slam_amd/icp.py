@@ -81,7 +81,7 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None, normals=None, covariance=None):
+                 robust=None, normals=None, covariance=None, cuts=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
@@ -90,7 +90,9 @@ class IcpHandle:
         RobustConfig, a dict of its fields, or an _lib.RobustCfg) -- lsgpu_icp_set_robust_filter.  normals: None, or a
         NormalsConfig / dict of its fields / _lib.NormalsCfg (SurfaceNormalOutlierFilter, reading normals, oriented
         normals) -- lsgpu_icp_set_normals.  covariance: None, or PointToPlaneWithCovErrorMinimizer's sensorStdDev --
-        lsgpu_icp_set_covariance (given last: it refuses a handle with modules its pass does not cover)."""
+        lsgpu_icp_set_covariance (given last: it refuses a handle with modules its pass does not cover).  cuts: None, or the
+        cut modules of the two filter sections (a ChainCuts, a dict of its fields, or an _lib.ChainCuts) --
+        lsgpu_icp_set_chain_cuts."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -133,6 +135,30 @@ class IcpHandle:
         self.covariance = None
         if covariance is not None:
             self.set_covariance(covariance)
+        self.cuts = None
+        if cuts is not None:
+            self.set_chain_cuts(cuts)
+
+    def set_chain_cuts(self, cuts):
+        """lsgpu_icp_set_chain_cuts: MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the filter sections of
+        this handle's compute calls (None, or no module at all, switches them off)."""
+        cc = chain_cuts_cfg(cuts) if cuts is not None else None
+        rc = _lib.lib().lsgpu_icp_set_chain_cuts(self._h, C.byref(cc) if cc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_chain_cuts", self._h)
+        self.cuts = cc if cc is not None and (cc.n_reading or cc.n_reference) else None
+
+    def filter_section(self, cuts, side: int, xyz1, prob: float = -1.0, seed: int = -1):
+        """lsgpu_icp_filter_section: the fused pass of one filter section alone -> xyz1'.  side 0: the reading's cut modules
+        with RandomSampling of probability `prob` at cuts.reading_sampling_at (prob < 0: none); side 1: the reference's."""
+        cc = chain_cuts_cfg(cuts)
+        p, _k, n = _as_f32(xyz1, 4)
+        o, po = self._filter_out(xyz1, n)
+        m = C.c_int64(0)
+        rc = _lib.lib().lsgpu_icp_filter_section(self._h, C.byref(cc), int(side), float(prob), p, n, seed, po, C.byref(m))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_filter_section", self._h)
+        return o[:m.value]
 
     def set_covariance(self, sensor_std_dev=0.01):
         """lsgpu_icp_set_covariance: PointToPlaneWithCovErrorMinimizer's covariance after every alignment (None: off)."""
@@ -896,7 +922,20 @@ class ChainConfig:
     outlier_max_dist: float = 0.0           # MaxDistOutlierFilter maxDist [m]; 0: no such module
     outlier_min_dist: float = 0.0           # MinDistOutlierFilter minDist [m]; 0: no such module (or minDist 0: keeps all)
     outlier_median_factor: float = 0.0      # MedianDistOutlierFilter factor; 0: no such module
-    extra: dict = field(default_factory=dict)   # "robust": RobustOutlierFilter's parameters (see `robust`); "normals": see `normals`
+    extra: dict = field(default_factory=dict)   # "robust": RobustOutlierFilter's parameters (see `robust`); "normals": see `normals`; "cuts": see `cuts`
+
+    @property
+    def cuts(self) -> Optional["ChainCuts"]:
+        """The cut modules of the two filter sections (a ChainCuts); None: none.  Kept in `extra`, like `robust`, so that a
+        chain without them compares equal to what it was."""
+        return self.extra.get("cuts")
+
+    @cuts.setter
+    def cuts(self, value):
+        if value is None:
+            self.extra.pop("cuts", None)
+        else:
+            self.extra["cuts"] = value
 
     @property
     def normals(self) -> Optional["NormalsConfig"]:
@@ -938,9 +977,40 @@ class ChainConfig:
             self.extra["robust"] = value
 
 
-def chain_load(doc):
-    """lsgpu_chain_load on a YAML chain document read with yaml.BaseLoader (every scalar stays text): its modules, section by
-    section in the document's order -> (return code, reason of a refusal, _lib.LoadedChain).  The rules are the library's."""
+@dataclass(frozen=True)
+class ChainCuts:
+    """lsgpu_chain_cuts: the cut modules of an ICP chain's filter sections, each `(type, dim, flag, (v, ...))` with type one
+    of _lib.FILTER_MAX_DIST / _MIN_DIST / _BOUNDING_BOX / _REMOVE_NAN, in the document's order.  `reading_sampling_at`: how
+    many of the reading's stand in front of RandomSampling (not read on a chain without it)."""
+    reading: tuple = ()
+    reference: tuple = ()
+    reading_sampling_at: int = 0
+
+
+def chain_cuts_cfg(c) -> "_lib.ChainCuts":
+    """ChainCuts / dict of its fields / _lib.ChainCuts -> _lib.ChainCuts (the counts are checked by the library)."""
+    if isinstance(c, _lib.ChainCuts):
+        return c
+    if isinstance(c, dict):
+        c = ChainCuts(tuple(c.get("reading", ())), tuple(c.get("reference", ())), int(c.get("reading_sampling_at", 0)))
+    out = _lib.ChainCuts()
+    out.n_reading, out.n_reference, out.reading_sampling_at = len(c.reading), len(c.reference), int(c.reading_sampling_at)
+    for dst, mods in ((out.reading, c.reading), (out.reference, c.reference)):
+        for f, (typ, dim, flag, v) in zip(dst, mods):     # (more than CHAIN_CUT_MAX: the count says so, the library refuses it)
+            f.type, f.dim, f.flag = int(typ), int(dim), int(flag)
+            for i, x in enumerate(tuple(v)[:6]):
+                f.v[i] = float(x)
+    return out
+
+
+def _chain_cuts(cc) -> "ChainCuts":
+    """_lib.ChainCuts -> ChainCuts"""
+    mods = lambda arr, n: tuple((f.type, f.dim, f.flag, tuple(_f32(x) for x in f.v)) for f in arr[:n])
+    return ChainCuts(mods(cc.reading, cc.n_reading), mods(cc.reference, cc.n_reference), cc.reading_sampling_at)
+
+
+def _yaml_modules(doc):
+    """A YAML chain document read with yaml.BaseLoader -> (lsgpu_yaml_module array, count, what keeps its strings alive)."""
     mods = []
     for section, v in doc.items():
         for it in (v if isinstance(v, list) else [v]):
@@ -955,9 +1025,26 @@ def chain_load(doc):
         ps = (_lib.YamlParam * max(len(kv), 1))(*[_lib.YamlParam(k, v) for k, v in kv])
         keep.append(ps)
         a.section, a.name, a.params, a.n_params = str(section).encode(), str(name).encode(), ps, len(kv)
+    return arr, len(mods), keep
+
+
+def chain_load(doc):
+    """lsgpu_chain_load on a YAML chain document read with yaml.BaseLoader (every scalar stays text): its modules, section by
+    section in the document's order -> (return code, reason of a refusal, _lib.LoadedChain).  The rules are the library's."""
+    arr, n, _keep = _yaml_modules(doc)
     out = _lib.LoadedChain()
     why = C.create_string_buffer(512)
-    rc = _lib.lib().lsgpu_chain_load(arr, len(mods), C.byref(out), why, len(why))
+    rc = _lib.lib().lsgpu_chain_load(arr, n, C.byref(out), why, len(why))
+    return rc, why.value.decode(), out
+
+
+def chain_load_cuts(doc):
+    """lsgpu_chain_load_cuts on the same document: the cut modules of its two filter sections -> (return code, reason of a
+    refusal, _lib.ChainCuts).  Same rules, same verdict and same text as chain_load."""
+    arr, n, _keep = _yaml_modules(doc)
+    out = _lib.ChainCuts()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load_cuts(arr, n, C.byref(out), why, len(why))
     return rc, why.value.decode(), out
 
 
@@ -966,8 +1053,8 @@ def _f32(x) -> float:
     return float(str(np.float32(x)))
 
 
-def _chain_config(lc) -> "ChainConfig":
-    """_lib.LoadedChain -> ChainConfig"""
+def _chain_config(lc, cuts=None) -> "ChainConfig":
+    """_lib.LoadedChain (and the _lib.ChainCuts of the same document, if it has cut modules) -> ChainConfig"""
     i, c = lc.icp, lc.chain
     name = {v: k for k, v in _MINIMIZERS.items()}[i.error_minimizer]
     ch = ChainConfig(reading_sampling_prob=_f32(c.reading_prob), surface_normal_knn=c.ssn_knn,
@@ -988,6 +1075,8 @@ def _chain_config(lc) -> "ChainConfig":
     sd = C.c_float()
     if _lib.lib().lsgpu_loaded_chain_covariance(C.byref(lc), C.byref(sd)):
         ch.covariance = _f32(sd.value)
+    if cuts is not None and (cuts.n_reading or cuts.n_reference):
+        ch.cuts = _chain_cuts(cuts)
     return ch
 
 
@@ -1028,7 +1117,12 @@ class ICP:
         rc, why, loaded = chain_load(doc)
         if rc != _lib.OK:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        self.chain = _chain_config(loaded)
+        cuts = None
+        if loaded.reserved[2] or loaded.reserved[3]:            # the document has cut modules: the modules themselves
+            rc, why, cuts = chain_load_cuts(doc)
+            if rc != _lib.OK:
+                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+        self.chain = _chain_config(loaded, cuts)
         self._handle = None
 
     def _ensure_handle(self) -> IcpHandle:
@@ -1044,7 +1138,7 @@ class ICP:
                                      self.chain.matcher_max_dist, self.chain.outlier_max_dist,
                                      self.chain.outlier_min_dist, self.chain.outlier_median_factor,
                                      robust=self.chain.robust, normals=self.chain.normals,
-                                     covariance=self.chain.covariance)
+                                     covariance=self.chain.covariance, cuts=self.chain.cuts)
         return self._handle
 
     @property
