@@ -271,7 +271,8 @@ int lsgpu_knn_k(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T
  * <= 0 asks for rank 0, the smallest input, whatever the count (rank from the host, as before). */
 int lsgpu_trim_limit(lsgpu_icp* h, const float* d2, int64_t n, float ratio, float* limit);
 /* PointToPlaneErrorMinimizer accumulation (yaml:18-19): out = 21 upper-tri of sum J J^T (row major
- * order a<=c), 6 of -sum J r, sum w, sum w r^2  -> double[29]. */
+ * order a<=c), 6 of -sum J r, sum w, sum w r^2  -> double[29].  w = 1 for the pairs with ids >= 0 and a finite
+ * d2 <= limit (+inf and NaN = an invalid match, as in lsgpu_trim_limit: a limit of +inf keeps every valid pair). */
 int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
                     const int32_t* ids, const float* d2, float limit, double out[29]);
 /* PointToPointErrorMinimizer accumulation, same inputs as lsgpu_normal_eq: out[0..2] = sum p, [3..5] = sum q,

@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
   for (int j = blockIdx.x * 256 + threadIdx.x; j < nq; j += gridDim.x * 256) {
     const float d = d2[j];
     int id = ids[j];
-    if (!(d <= limit) || id < 0) continue;
+    if (!(d <= limit) || !(d < INFINITY) || id < 0) continue;   // (+inf = an invalid match, whatever its id: not even a limit of +inf keeps it)
     if (IDS_ORIG) id = (int)inv[id];
     const float4 r = rdq[j];
     const float3 p = xform(T, r.x, r.y, r.z);
