@@ -7,14 +7,15 @@ keep their registers, scratch and LDS -- DESIGN.md §3, "RobustOutlierFilter").
         -Rpass-analysis=kernel-resource-usage -o /dev/null laser_slam_amd/csrc/lsgpu_icp.hip 2> remarks.txt    # in each tree
     devtools/compare_kernel_resources.py parent/remarks.txt remarks.txt
 
-Kernels are matched by demangled name; template arguments only the newer tree has (HistPlain, the trailing RB = false) and
-the argument lists are dropped first.  Exit status 1 if a kernel both trees have differs in VGPRs, AGPRs, scratch, LDS or
+Kernels are matched by demangled name; template arguments only the newer tree has (HistPlain, the trailing RB = false, the
+trailing DENS = false of k_snf_tile / k_snf_fallback) and
+the argument lists are dropped first.  Exit status 1 if a kernel both trees have differs in SGPRs, VGPRs, AGPRs, scratch, LDS or
 occupancy; kernels only the second tree has are listed with their figures."""
 import re
 import subprocess
 import sys
 
-KEYS = {"VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "LDS Size [bytes/block]": "lds",
+KEYS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [bytes/lane]": "scratch", "LDS Size [bytes/block]": "lds",
         "Occupancy [waves/SIMD]": "occ"}
 
 
@@ -39,6 +40,7 @@ def report(path):
         d = re.sub(r"(k_normal_eq_loop<[^,>]+, [^,>]+, [^,>]+), false>", r"\1>", d)
         d = re.sub(r"(k_normal_eq<[^,>]+, [^,>]+, [^,>]+), false>", r"\1>", d)
         d = re.sub(r"(icp_update_lane<[^,>]+), false>", r"\1>", d)
+        d = re.sub(r"(k_snf_(?:tile|fallback)<[^,>]+), false>", r"\1>", d)         # DENS = false: the kernels as they were
         res[d] = out[n]
     return res
 

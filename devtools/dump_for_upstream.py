@@ -10,6 +10,11 @@ For a synthetic HDL-64E pair (default: the 4 k-point pair of the parity tests, `
                                              PointMatcher::ICP::loadFromYaml; checked here with this repo's own loader)
   T_init.txt                                 4 x 4, row major, "%.9g"
   reference_filtered.csv                     what SamplingSurfaceNormalDataPointsFilter leaves (x,y,z,nx,ny,nz): choices 1, 2, 8, 10, 11
+                                             (a chain with SurfaceNormalDataPointsFilter keepDensities 1 + MaxDensityDataPointsFilter:
+                                             what those leave, and reference_densities.csv with every reference point's density:
+                                             choices 36-40; such a chain's draws, the reading's included, come from the
+                                             library's own stream, so --submap, whose input filters draw from the oracle's,
+                                             refuses it)
   reading_filtered.csv                       what RandomSamplingDataPointsFilter leaves: choice 8 (the draws continue the
                                              reference filter's; the process starts at srand(1) like an unseeded one)
   input_filtered.csv                         reading.csv through tests/golden/input_filters.yaml (srand(1) again): choice 9
@@ -67,6 +72,12 @@ VOXEL_CHOICES = """30 VoxelGrid: float bounds, numDiv = (uint)((1 + maxB) - minB
 32 VoxelGrid: centroid = first point + the others in input order, / count   input_filtered.csv: last digits of x, y, z
 33 VoxelGrid: output in the order of the voxels' first points    input_filtered.csv: row order
 34 VoxelGrid: the pad row and descriptors are the first point's  input_filtered.csv: nothing (pad is 1)
+"""
+DENSITY_CHOICES = """36 density: knn / ((4/3) pi r^3), r = the largest distance from the neighbourhood's mean, float   reference_densities.csv: last digits
+37 density of knn identical points: +inf (dropped by MaxDensity)   reference_densities.csv: inf rows; reference_filtered.csv: rows
+38 MaxDensity: one draw per point with density > maxDensity, kept iff draw < maxDensity / density   reference_filtered.csv: WHICH rows
+39 MaxDensity: the densest points' acceptance times (1 - nbSaturated / n) as an integer division   reference_filtered.csv: rows of the densest points
+40 the reading's draws continue behind the dense points' draws   reading_filtered.csv: WHICH rows
 """
 
 
@@ -193,6 +204,11 @@ def submap_inputs(out_dir, n_az, voxel_grid=None):
 def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
     os.makedirs(out_dir, exist_ok=True)
     ch = parse_chain(chain_path)
+    if submap and ch.max_density is not None:
+        # the input filters of the four scans draw from the oracle's rand(), MaxDensityDataPointsFilter's host twin from the
+        # library's own stream: the two cannot continue one another, and a dump with two streams would not be one process's
+        raise SystemExit("--submap with MaxDensityDataPointsFilter in the chain is not supported: the input filters' draws (the "
+                         "oracle's rand()) and the reference section's (the library's stream) would not be one sequence")
     shutil.copyfile(chain_path, os.path.join(out_dir, "icp.yaml"))
     if submap:
         rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az, voxel_grid)
@@ -207,11 +223,20 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
     write_mat(os.path.join(out_dir, "T_init.txt"), T16.reshape(4, 4).T)
     # ICP::compute, steps 1 and 4 with ONE draw stream that starts where an unseeded process starts (srand(1)) -- or, in the
     # sub-map dump, where the input filters of the four scans left it
-    rf, rn = O.sampling_surface_normal(ref, ch.surface_normal_knn, ch.surface_normal_ratio, icp_seed)
-    if ch.reading_sampling_prob >= 0:
-        rdf = rd[O.random_sampling(rd.shape[0], ch.reading_sampling_prob, -1)]
+    if ch.max_density is not None:
+        # SurfaceNormalDataPointsFilter keepDensities 1 + MaxDensityDataPointsFilter [+ the orientation pair]: not in the oracle,
+        # the library's host twins (no GPU): choices 36-40; reference_densities.csv has the density of every reference point
+        from laser_slam_amd import icp
+        # The twins draw from the LIBRARY's stream (csrc/lsgpu_rand.h: glibc's sequence, never libc's state), so the reading's
+        # mask is taken from that stream as well: draws n_dense + 1 .. n_dense + nq of srand(icp_seed), choice 40
+        rf, rn, _n_dense, dens = icp.max_density(ref, ch.reference_normal_knn, ch.max_density, icp_seed)
+        if ch.normals is not None and ch.normals.reference_orient:
+            rn = icp.orient_normals(rf, rn, ch.normals.reference_sensor, ch.normals.reference_orient == 1)
+        np.savetxt(os.path.join(out_dir, "reference_densities.csv"), dens, fmt="%.9g")
+        rdf = rd[icp.random_sampling(rd.shape[0], ch.reading_sampling_prob, -1)] if ch.reading_sampling_prob >= 0 else rd
     else:
-        rdf = rd
+        rf, rn = O.sampling_surface_normal(ref, ch.surface_normal_knn, ch.surface_normal_ratio, icp_seed)
+        rdf = rd[O.random_sampling(rd.shape[0], ch.reading_sampling_prob, -1)] if ch.reading_sampling_prob >= 0 else rd
     cloud_io.save_csv(os.path.join(out_dir, "reference_filtered.csv"), rf, rn)
     cloud_io.save_csv(os.path.join(out_dir, "reading_filtered.csv"), rdf)
     if not submap:
@@ -239,7 +264,8 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
                 "Replay on libpointmatcher: INTEGRATION.md, \"Diffing against a real libpointmatcher\".\n\n%s"
                 % (n_az, rd.shape[0], ref.shape[0], os.path.relpath(chain_path, ROOT), g(ch.reading_sampling_prob),
                    ch.surface_normal_knn, g(ch.surface_normal_ratio), g(ch.trim_ratio), ch.max_iterations,
-                   g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length, CHOICES + (VOXEL_CHOICES if voxel_grid else "")))
+                   g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length,
+                   CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "")))
     return rc, st.iterations
 
 

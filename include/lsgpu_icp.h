@@ -31,7 +31,8 @@
  * (lsgpu_chain_config.sn_knn), and RobustOutlierFilter (lsgpu_icp_set_robust_filter), and SurfaceNormalOutlierFilter with
  * SurfaceNormalDataPointsFilter on the reading and ObservationDirection- + OrientNormalsDataPointsFilter on either cloud
  * (lsgpu_icp_set_normals), and PointToPlaneWithCovErrorMinimizer: the point-to-plane step plus the 6x6 covariance of the result
- * (lsgpu_icp_set_covariance, lsgpu_icp_get_quality).
+ * (lsgpu_icp_set_covariance, lsgpu_icp_get_quality), and MaxDensityDataPointsFilter behind the reference's
+ * SurfaceNormalDataPointsFilter with keepDensities 1 (lsgpu_icp_set_max_density).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -644,7 +645,9 @@ typedef struct lsgpu_loaded_chain {
   int reserved[6];                  /* [0] = 1: errorMinimizer PointToPlaneWithCovErrorMinimizer (icp.error_minimizer stays
                                      * LSGPU_MINIMIZER_POINT_TO_PLANE), [1] = the IEEE-754 bits of (float)sensorStdDev then, else 0;
                                      * read them with lsgpu_loaded_chain_covariance.  [2], [3] = the number of cut modules in
-                                     * the reading / reference section (the modules: lsgpu_chain_load_cuts).  [4], [5] 0 */
+                                     * the reading / reference section (the modules: lsgpu_chain_load_cuts).  [4] = 1: MaxDensityDataPointsFilter
+                                     * behind the reference's SurfaceNormalDataPointsFilter, [5] = the IEEE-754 bits of (float)maxDensity
+                                     * then, else 0; read them with lsgpu_loaded_chain_max_density */
 } lsgpu_loaded_chain;
 /* LSGPU_OK and *out (every byte of it, padding 0), or LSGPU_BAD_CONFIG with the reason -- the module's name in it, or the
  * section's for an unknown section -- written to why[0 .. why_cap), truncated if need be and always NUL-terminated; *out is
@@ -754,6 +757,66 @@ int lsgpu_icp_filter_section(lsgpu_icp* h, const lsgpu_chain_cuts* cuts, int sid
  * yMax 1, zMin -1, zMax 1, removeInside 1}, RemoveNaN {} -- those of the input filter chain's front ends.  dim an integer in
  * -1..2, removeInside 0 or 1, the limits numbers (inf allowed).  Host only. */
 int lsgpu_chain_load_cuts(const lsgpu_yaml_module* mods, int n_mods, lsgpu_chain_cuts* out, char* why, int why_cap);
+
+/* ---- MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 (DESIGN.md §3 "Thinning the dense near
+ * range", §5 choices 36-40) ----------------------------------------------------------------------------------------------
+ * The reference section  SurfaceNormalDataPointsFilter {knn, keepDensities 1}, MaxDensityDataPointsFilter {maxDensity}  [,
+ * ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter]: normals and densities on the whole cloud, then the dense
+ * near range is thinned.  Restated from knowledge of upstream, parity unpinned.
+ *   Density of point i: the knn neighbourhood of lsgpu_icp_filter_reference_normals, in its order, on the centred cloud;
+ *     mean = box_normal's mean, bit for bit; e_j = p_j - mean; r = sqrtf(max_j ((ex ex + ey ey) + ez ez));
+ *     volume = (float)(4/3 pi) * ((r r) r); density = (float)knn / volume.  Float, one rounding per operation, no pow
+ *     (csrc/lsgpu_density.h, shared by host and device).  r == 0 (knn identical points): +inf.
+ *   MaxDensityDataPointsFilter {maxDensity: default 10, in (0, inf]}, over the cloud in the order given: last = the largest
+ *     non-NaN density; sat = 0 if every point's density equals last, else 1 (upstream's integer division 1 - nbSaturated / n).
+ *     A point with density > maxDensity takes ONE draw, (float)rand() / (float)RAND_MAX, and is kept iff draw < accept,
+ *     accept = maxDensity / density (a float division), multiplied by (float)sat if density == last.  Every other point -- a
+ *     NaN density included -- is kept and takes no draw.  Order preserved.  A +inf density: accept 0, dropped, its draw
+ *     consumed.  The draw of a dense point is indexed by its rank among the dense points; afterwards the library's draw stream
+ *     stands n_dense draws further on, and the reading section's draws start there.
+ *   In lsgpu_icp_compute (a handle with lsgpu_icp_set_max_density, chain->sn_knn > 0): the reference's cut modules, the grid of
+ *     the whole surviving cloud, normals + densities on it, the thinning pass; the thinned cloud and its normals then go on as
+ *     SamplingSurfaceNormalDataPointsFilter's output does (orientation, centring on the THINNED cloud's mean, grid, loop).  The
+ *     reading's filter runs behind the count of dense points, on one stream.  Nothing kept: LSGPU_NO_CONVERGENCE ("compute: the
+ *     reference filter left no point").  A point-to-point handle runs the densities and the thinning too.  chain->sn_knn == 0
+ *     on such a handle: LSGPU_BAD_CONFIG.  A handle without the module enqueues what it always did.
+ *   Not together with the split-scan mode (lsgpu_icp_comm_init) or PointToPlaneWithCovErrorMinimizer (lsgpu_icp_set_covariance):
+ *     LSGPU_BAD_CONFIG, the module named in lsgpu_last_error, whichever of the two calls comes second.
+ *   Loader: the module may stand only in referenceDataPointsFilters, directly behind SurfaceNormalDataPointsFilter with
+ *     keepDensities 1 and in front of the orientation pair, once.  keepDensities 1 with no MaxDensityDataPointsFilter behind it
+ *     stays refused (nothing would read the densities), as it is on the reading side. */
+typedef struct lsgpu_max_density_config {
+  float max_density;   /* maxDensity [points / m^3] (10): > 0, +inf allowed, not NaN */
+  int   reserved[3];   /* 0 */
+} lsgpu_max_density_config;
+void lsgpu_max_density_config_default(lsgpu_max_density_config* c);
+/* Without a handle or a device: LSGPU_OK / NULL, or LSGPU_BAD_CONFIG / the reason (a static string, the module's name in it)
+ * for a maxDensity that is not > 0, or sn_knn <= 0: no SurfaceNormalDataPointsFilter in front of the module. */
+int lsgpu_max_density_config_check(const lsgpu_max_density_config* c, int sn_knn);
+const char* lsgpu_max_density_config_why(const lsgpu_max_density_config* c, int sn_knn);
+/* Gives the handle the module (cfg is copied), NULL removes it.  A bad maxDensity and the refused combinations above:
+ * LSGPU_BAD_CONFIG before the device is touched (the handle keeps what it had). */
+int lsgpu_icp_set_max_density(lsgpu_icp* h, const lsgpu_max_density_config* cfg);
+/* lsgpu_icp_filter_reference_normals with the densities: out_densities (nullable) one float per point, in the cloud's order.
+ * Without out_densities it is that function: the same launches, the same outputs. */
+int lsgpu_icp_filter_reference_normals_densities(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals,
+                                                 int32_t* out_ids, float* out_d2, float* out_densities);
+/* The two modules on a cloud (kernel-level entry): out_xyz1 (4 floats / point) and out_normals (3 floats / point) need room for n
+ * points, out_xyz1 must not be xyz1; out_densities (nullable): one float per INPUT point; *n_out points kept, *n_dense draws
+ * consumed.  seed as lsgpu_icp_filter_reading.  Host or device pointers.  LSGPU_NO_CONVERGENCE if nothing is kept (the draws are
+ * consumed).  The call leaves the WHOLE cloud as the handle's reference, as lsgpu_icp_filter_reference_normals does. */
+int lsgpu_icp_filter_reference_max_density(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float max_density, int64_t seed,
+                                           float* out_xyz1, float* out_normals, float* out_densities, int64_t* n_out,
+                                           int64_t* n_dense);
+/* Host twins (no GPU, no handle), bit-identical with the device: lsgpu_filter_surface_normal with the densities beside the
+ * normals, and the two modules with the outputs of lsgpu_icp_filter_reference_max_density (host pointers). */
+int lsgpu_filter_surface_normal_densities(const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
+                                          float* out_d2, float* out_densities);
+int lsgpu_filter_max_density(const float* xyz1, int64_t n, int knn, float max_density, int64_t seed, float* out_xyz1,
+                             float* out_normals, float* out_densities, int64_t* n_out, int64_t* n_dense);
+/* The module's slots of a loaded chain: 1 and *max_density (nullable) if the document names MaxDensityDataPointsFilter, else 0
+ * and *max_density untouched.  Host only. */
+int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

@@ -139,6 +139,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_chain_cuts: " + why);
       }
+      if (has_md_ && lsgpu_icp_set_max_density(h_, &md_) != LSGPU_OK) {   // MaxDensityDataPointsFilter behind the reference's SurfaceNormal
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_max_density: " + why);
+      }
     }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
@@ -175,6 +180,8 @@ class LsgpuICP {
     has_cov_ = parsed.covarianceConfig(&cov_.sensor_std_dev);
     has_cuts_ = parsed.chainCuts() != nullptr;
     if (has_cuts_) cuts_ = *parsed.chainCuts();
+    lsgpu_max_density_config_default(&md_);
+    has_md_ = parsed.maxDensityConfig(&md_.max_density);
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -193,6 +200,8 @@ class LsgpuICP {
   bool has_cov_ = false;                                // ... if the chain names the module
   lsgpu_chain_cuts cuts_{};                             // the cut modules of the two filter sections ...
   bool has_cuts_ = false;                               // ... if the chain holds any
+  lsgpu_max_density_config md_{};                       // MaxDensityDataPointsFilter's maxDensity ...
+  bool has_md_ = false;                                 // ... if the chain names the module
   int64_t seed_ = -1;
 };
 

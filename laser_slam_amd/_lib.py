@@ -44,6 +44,9 @@ ABI_SYMBOLS = [
     "lsgpu_covariance_config_default", "lsgpu_icp_set_covariance", "lsgpu_icp_get_quality", "lsgpu_point_to_plane_cov",
     "lsgpu_point_to_plane_cov_solve", "lsgpu_loaded_chain_covariance",
     "lsgpu_icp_set_chain_cuts", "lsgpu_icp_filter_section", "lsgpu_chain_load_cuts",
+    "lsgpu_max_density_config_default", "lsgpu_max_density_config_check", "lsgpu_max_density_config_why",
+    "lsgpu_icp_set_max_density", "lsgpu_icp_filter_reference_normals_densities", "lsgpu_icp_filter_reference_max_density",
+    "lsgpu_filter_surface_normal_densities", "lsgpu_filter_max_density", "lsgpu_loaded_chain_max_density",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -81,6 +84,11 @@ class RobustTrace(C.Structure):
 class CovarianceCfg(C.Structure):
     """lsgpu_covariance_config: PointToPlaneWithCovErrorMinimizer's parameter."""
     _fields_ = [("sensor_std_dev", C.c_float), ("reserved", C.c_int * 3)]
+
+
+class MaxDensityCfg(C.Structure):
+    """lsgpu_max_density_config: MaxDensityDataPointsFilter's parameter."""
+    _fields_ = [("max_density", C.c_float), ("reserved", C.c_int * 3)]
 
 
 class IcpQuality(C.Structure):
@@ -348,6 +356,18 @@ def lib() -> C.CDLL:
     L.lsgpu_icp_set_chain_cuts.argtypes = [vp, C.POINTER(ChainCuts)]
     L.lsgpu_icp_filter_section.argtypes = [vp, C.POINTER(ChainCuts), C.c_int, C.c_float, fp, i64, i64, fp, C.POINTER(i64)]
     L.lsgpu_chain_load_cuts.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(ChainCuts), C.c_char_p, C.c_int]
+    L.lsgpu_max_density_config_default.argtypes = [C.POINTER(MaxDensityCfg)]
+    L.lsgpu_max_density_config_default.restype = None
+    L.lsgpu_max_density_config_check.argtypes = [C.POINTER(MaxDensityCfg), C.c_int]
+    L.lsgpu_max_density_config_why.argtypes = [C.POINTER(MaxDensityCfg), C.c_int]
+    L.lsgpu_max_density_config_why.restype = C.c_char_p
+    L.lsgpu_icp_set_max_density.argtypes = [vp, C.POINTER(MaxDensityCfg)]
+    L.lsgpu_icp_filter_reference_normals_densities.argtypes = [vp, fp, i64, C.c_int, fp, fp, fp, fp]
+    L.lsgpu_icp_filter_reference_max_density.argtypes = [vp, fp, i64, C.c_int, C.c_float, i64, fp, fp, fp, C.POINTER(i64),
+                                                         C.POINTER(i64)]
+    L.lsgpu_filter_surface_normal_densities.argtypes = [fp, i64, C.c_int, fp, fp, fp, fp]
+    L.lsgpu_filter_max_density.argtypes = [fp, i64, C.c_int, C.c_float, i64, fp, fp, fp, C.POINTER(i64), C.POINTER(i64)]
+    L.lsgpu_loaded_chain_max_density.argtypes = [C.POINTER(LoadedChain), C.POINTER(C.c_float)]
     _lib = L
     return L
 

@@ -450,6 +450,10 @@ class ICP {
   // sensorStdDev of the loaded chain's PointToPlaneWithCovErrorMinimizer; false: the chain does not name the module
   bool covarianceConfig(float* sensor_std_dev) const { return lsgpu_loaded_chain_covariance(&loaded_, sensor_std_dev) != 0; }
 
+  // maxDensity of the loaded chain's MaxDensityDataPointsFilter (behind SurfaceNormalDataPointsFilter keepDensities 1 in the
+  // reference section); false: the chain does not name the module
+  bool maxDensityConfig(float* max_density) const { return lsgpu_loaded_chain_max_density(&loaded_, max_density) != 0; }
+
   const lsgpu_icp_stats& lastStats() const { return stats_; }
   const lsgpu_icp_config& config() const { return loaded_.icp; }
   lsgpu_icp* handle() { ensureHandle(); return h_; }  // the C-ABI handle (device conversions of ros_msgs.hpp)
@@ -531,6 +535,13 @@ class ICP {
     }
     if (chainCuts() && lsgpu_icp_set_chain_cuts(h_, &cuts_) != LSGPU_OK) {
       const std::string msg = std::string("lsgpu_icp_set_chain_cuts: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
+    lsgpu_max_density_config mc;
+    lsgpu_max_density_config_default(&mc);
+    if (lsgpu_loaded_chain_max_density(&loaded_, &mc.max_density) && lsgpu_icp_set_max_density(h_, &mc) != LSGPU_OK) {
+      const std::string msg = std::string("lsgpu_icp_set_max_density: ") + lsgpu_last_error(h_);
       release();
       throw ConfigError(msg);
     }

@@ -32,6 +32,9 @@ const char* const kOneReference = "referenceDataPointsFilters: one module at mos
 const char* const kSurfaceNormalParams = "knn epsilon maxDist keepNormals keepDensities keepEigenValues keepEigenVectors "
                                          "keepMatchedIds keepMeanDist sortEigen smoothNormals";
 
+const char* const kDensitiesAlone = "referenceDataPointsFilters: SurfaceNormalDataPointsFilter: keepDensities 1 is implemented only with "
+                                    "MaxDensityDataPointsFilter directly behind it (no other module reads the densities)";
+
 const char* const kBoundingBoxParams = "xMin xMax yMin yMax zMin zMax removeInside";
 
 bool listed(const char* list, const char* word) {   // is `word` one of the space-separated words of `list`?
@@ -53,6 +56,7 @@ struct Load {
   // 2 SurfaceNormal on the reading, 3 ObservationDirection, 4 OrientNormals
   int stage[2] = {0, 0};
   bool matcher = false, minimizer = false, counter = false, robust = false, with_cov = false;
+  bool ref_densities = false, max_density = false;   // the reference's SurfaceNormal has keepDensities 1; MaxDensity stands behind it
 
   std::string name() const { return m->name; }
   int side() const { return std::strcmp(m->section, "readingDataPointsFilters") == 0 ? 0 : 1; }
@@ -93,8 +97,9 @@ struct Load {
   bool whole(double x) const { return std::fabs(x) < 2147483648.0 && x == (double)(int)x; }
 };
 
-// SurfaceNormalDataPointsFilter's parameters (either side): keepNormals 1 alone, exact (epsilon 0), no maxDist -> knn
-int surface_normal_knn(const Load& l) {
+// SurfaceNormalDataPointsFilter's parameters (either side): keepNormals 1, exact (epsilon 0), no maxDist -> knn.
+// keep_densities: where keepDensities (0 or 1) goes -- the reference's module; nullptr (the reading's): 1 is refused
+int surface_normal_knn(const Load& l, bool* keep_densities) {
   const std::string n = l.name();
   const double k = l.num("knn", 5);
   if (!(k >= 3 && k <= 32) || !l.whole(k)) refuse(n + ": knn must be an integer in [3, 32]");
@@ -102,7 +107,11 @@ int surface_normal_knn(const Load& l) {
   const double md = l.num("maxDist", INFINITY);
   if (!(std::isinf(md) && md > 0.0)) refuse(n + ": maxDist must be absent or inf");
   if (l.num("keepNormals", 1) != 1.0) refuse(n + ": keepNormals must be 1 (the module is there for the normals)");
-  for (const char* key : {"keepDensities", "keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
+  const double kd = l.num("keepDensities", 0);
+  if (kd != 0.0 && kd != 1.0) refuse(n + ": keepDensities must be 0 or 1");
+  if (kd == 1.0 && !keep_densities) refuse(std::string(l.m->section) + ": " + n + ": keepDensities 1: reading densities are not computed");
+  if (keep_densities) *keep_densities = kd == 1.0;
+  for (const char* key : {"keepEigenValues", "keepEigenVectors", "keepMatchedIds", "keepMeanDist",
                           "sortEigen", "smoothNormals"})
     if (l.num(key, 0) != 0.0) refuse(n + ": " + key + " must be 0 or absent");
   return (int)k;
@@ -158,7 +167,7 @@ void cut_bounding_box(Load& l) {
 }
 void cut_remove_nan(Load& l) { cut_slot(l).type = LSGPU_FILTER_REMOVE_NAN; }
 
-void reading_normals(Load& l) { l.out.normals.reading_sn_knn = surface_normal_knn(l); l.stage[0] = 2; }
+void reading_normals(Load& l) { l.out.normals.reading_sn_knn = surface_normal_knn(l, nullptr); l.stage[0] = 2; }
 void sampling_surface_normal(Load& l) {
   if (l.stage[1]) refuse(kOneReference);
   l.out.chain.ssn_knn = l.truncated("knn", 7);
@@ -168,8 +177,25 @@ void sampling_surface_normal(Load& l) {
 }
 void reference_normals(Load& l) {
   if (l.stage[1]) refuse(kOneReference);
-  l.out.chain.sn_knn = surface_normal_knn(l);
+  l.out.chain.sn_knn = surface_normal_knn(l, &l.ref_densities);
   l.stage[1] = 1;
+}
+// MaxDensityDataPointsFilter: directly behind the reference's SurfaceNormalDataPointsFilter with keepDensities 1, in front of the
+// orientation pair, once.  The two slots of lsgpu_loaded_chain.reserved
+void max_density_filter(Load& l) {
+  const std::string n = l.name();
+  const char* const where = " may stand only in referenceDataPointsFilters, directly behind SurfaceNormalDataPointsFilter with "
+                            "keepDensities 1 and in front of ObservationDirectionDataPointsFilter / OrientNormalsDataPointsFilter";
+  if (l.side() == 0) refuse("readingDataPointsFilters: " + n + ": reading densities are not computed (the module" + where + ")");
+  if (l.stage[1] == 1 && l.out.chain.ssn_knn > 0)
+    refuse("referenceDataPointsFilters: " + n + " behind SamplingSurfaceNormalDataPointsFilter: no densities (the module" + where + ")");
+  if (l.stage[1] != 1 || !l.ref_densities || l.max_density) refuse("referenceDataPointsFilters: " + n + where);
+  const double md = l.num("maxDensity", 10.0);
+  const float f = (float)md;
+  if (!(md > 0.0) || !(f > 0.f)) refuse(n + ": maxDensity must be > 0");
+  l.out.reserved[4] = 1;
+  std::memcpy(&l.out.reserved[5], &f, sizeof(f));
+  l.max_density = true;
 }
 void observation_direction(Load& l) {
   const int s = l.side();
@@ -284,6 +310,8 @@ const Row kRows[] = {
     {"readingDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
     {"referenceDataPointsFilters", "SamplingSurfaceNormalDataPointsFilter", "knn ratio samplingMethod", false, sampling_surface_normal},
     {"referenceDataPointsFilters", "SurfaceNormalDataPointsFilter", kSurfaceNormalParams, false, reference_normals},
+    {"referenceDataPointsFilters", "MaxDensityDataPointsFilter", "maxDensity", false, max_density_filter},
+    {"readingDataPointsFilters", "MaxDensityDataPointsFilter", "maxDensity", false, max_density_filter},
     {"referenceDataPointsFilters", "ObservationDirectionDataPointsFilter", "x y z", true, observation_direction},
     {"referenceDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
     {"readingDataPointsFilters", "MaxDistDataPointsFilter", "dim maxDist", false, cut_max_dist},
@@ -314,6 +342,7 @@ constexpr int kNumRows = (int)(sizeof(kRows) / sizeof(kRows[0]));
 // reads no normals: the reference as given; absent differential checker: the counter stops the loop.)
 void finish(Load& l) {
   lsgpu_loaded_chain& o = l.out;
+  if (l.ref_densities && !l.max_density) refuse(kDensitiesAlone);
   const int have_normals = l.stage[1] != 0;
   if (!l.matcher) refuse("matcher: KDTreeMatcher is required");
   if (!l.minimizer) refuse("errorMinimizer: PointToPlaneErrorMinimizer, PointToPlaneWithCovErrorMinimizer or PointToPointErrorMinimizer is required");
@@ -331,6 +360,7 @@ void finish(Load& l) {
     const char* with = o.icp.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2" : l.robust ? "RobustOutlierFilter"
                      : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
     if (with) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + with + " (the covariance is implemented for knn 1 and binary distance filters)");
+    if (l.max_density) refuse("PointToPlaneWithCovErrorMinimizer: not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)");
   }
   if (o.chain.reading_prob < 0.f) l.cuts.reading_sampling_at = l.cuts.n_reading;   // (no RandomSampling: not read)
   o.reserved[2] = l.cuts.n_reading; o.reserved[3] = l.cuts.n_reference;
@@ -363,6 +393,7 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
     for (int p = 0; kRows[r].params && p < m.n_params; ++p)
       if (!listed(kRows[r].params, m.params[p].key)) refuse(std::string(m.name) + ": unknown parameter " + m.params[p].key);
     l.m = &m;
+    if (l.ref_densities && !l.max_density && kRows[r].load != max_density_filter) refuse(kDensitiesAlone);
     kRows[r].load(l);
   }
   finish(l);
@@ -403,6 +434,12 @@ int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
 int lsgpu_chain_load_cuts(const lsgpu_yaml_module* mods, int n_mods, lsgpu_chain_cuts* out, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
   return out ? load_into(mods, n_mods, nullptr, out, why, why_cap) : LSGPU_BAD_ARG;
+}
+
+int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density) {
+  if (!c || c->reserved[4] != 1) return 0;
+  if (max_density) std::memcpy(max_density, &c->reserved[5], sizeof(float));
+  return 1;
 }
 
 int lsgpu_loaded_chain_covariance(const lsgpu_loaded_chain* c, float* sensor_std_dev) {

@@ -21,6 +21,7 @@
 
 #include "../../include/lsgpu_icp.h"
 #include "lsgpu_box_normal.h"
+#include "lsgpu_density.h"
 #include "lsgpu_robust.h"
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
@@ -95,6 +96,15 @@ struct SurfaceNormalBuilder {
     build(first + left, last, rmin, maxb);
   }
 };
+
+// MaxDensityDataPointsFilter's parameter and its place behind SurfaceNormalDataPointsFilter (sn_knn: that module's knn, 0: absent)
+const char* max_density_why(const lsgpu_max_density_config* c, int sn_knn) {
+  if (!c) return "MaxDensityDataPointsFilter: no configuration";
+  if (!(c->max_density > 0.f)) return "MaxDensityDataPointsFilter: maxDensity must be > 0 (inf allowed)";
+  if (c->reserved[0] || c->reserved[1] || c->reserved[2]) return "MaxDensityDataPointsFilter: reserved fields must be 0";
+  if (sn_knn <= 0) return "MaxDensityDataPointsFilter: needs the densities of SurfaceNormalDataPointsFilter with keepDensities 1 as the reference filter (sn_knn > 0)";
+  return nullptr;
+}
 
 float det3(const float* T) {
   auto m = [&](int r, int c) { return T[c * 4 + r]; };
@@ -199,6 +209,11 @@ int64_t lsgpu_filter_voxel_grid_points(const float* xyz1, int64_t n, const float
 // in float as well: adding a non-negative term never rounds below the other operand).
 int lsgpu_filter_surface_normal(const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
                                 float* out_d2) {
+  return lsgpu_filter_surface_normal_densities(xyz1, n, knn, out_normals, out_ids, out_d2, nullptr);
+}
+
+int lsgpu_filter_surface_normal_densities(const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
+                                          float* out_d2, float* out_densities) {
   if (!xyz1 || !out_normals || knn < 3 || knn > 32 || n < knn || n > 0x7FFFFFF0ll / knn || (out_d2 && !out_ids))
     return LSGPU_BAD_ARG;
   // centred as lsgpu_icp_set_reference centres the reference: float mean from double sums, one float subtraction
@@ -253,8 +268,58 @@ int lsgpu_filter_surface_normal(const float* xyz1, int64_t n, int knn, float* ou
       nv[0] = 0.f; nv[1] = 1.f; nv[2] = 0.f;   // upstream leaves the eigenvectors at identity: column 1
     }
     std::memcpy(out_normals + 3 * i, nv, 12);
+    if (out_densities) out_densities[i] = lsgpu::density::of_neighbourhood(knn, [&](int k, int d) { return c[3 * (size_t)I[k] + d]; });
   }
   return LSGPU_OK;
+}
+
+// ---- MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1: upstream's sequential loop (csrc/lsgpu_density.h)
+void lsgpu_max_density_config_default(lsgpu_max_density_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->max_density = 10.f;
+}
+int lsgpu_max_density_config_check(const lsgpu_max_density_config* c, int sn_knn) { return max_density_why(c, sn_knn) ? LSGPU_BAD_CONFIG : LSGPU_OK; }
+const char* lsgpu_max_density_config_why(const lsgpu_max_density_config* c, int sn_knn) { return max_density_why(c, sn_knn); }
+
+int lsgpu_filter_max_density(const float* xyz1, int64_t n, int knn, float max_density, int64_t seed, float* out_xyz1,
+                             float* out_normals, float* out_densities, int64_t* n_out, int64_t* n_dense) {
+  if (!out_xyz1 || !out_normals || !n_out || !n_dense) return LSGPU_BAD_ARG;
+  *n_out = 0; *n_dense = 0;
+  lsgpu_max_density_config mc;
+  lsgpu_max_density_config_default(&mc);
+  mc.max_density = max_density;
+  if (max_density_why(&mc, knn)) return LSGPU_BAD_CONFIG;
+  std::vector<float> nrm(3 * (size_t)std::max<int64_t>(n, 0)), dens((size_t)std::max<int64_t>(n, 0));
+  const int rc = lsgpu_filter_surface_normal_densities(xyz1, n, knn, nrm.data(), nullptr, nullptr, dens.data());
+  if (rc) return rc;
+  if (seed >= 0) lsgpu::DrawStream::global().take(seed, 0, nullptr);
+  // last: the largest non-NaN density; sat: 0 iff every point's density equals it
+  float last = 0.f;
+  bool any = false, all_equal = true;
+  for (int64_t i = 0; i < n; ++i)
+    if (dens[(size_t)i] == dens[(size_t)i] && (!any || dens[(size_t)i] > last)) { last = dens[(size_t)i]; any = true; }
+  for (int64_t i = 0; i < n; ++i) all_equal = all_equal && dens[(size_t)i] == last;
+  const int sat = all_equal ? 0 : 1;
+  int64_t kept = 0, dense = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const float d = dens[(size_t)i];
+    bool keep = true;
+    if (lsgpu::density::is_dense(d, max_density)) {
+      float draw;
+      lsgpu::DrawStream::global().take(-1, 1, &draw);
+      ++dense;
+      keep = lsgpu::density::keeps(d, max_density, last, sat, draw);
+    }
+    if (keep) {
+      std::memcpy(out_xyz1 + 4 * kept, xyz1 + 4 * i, 16);
+      std::memcpy(out_normals + 3 * kept, nrm.data() + 3 * i, 12);
+      ++kept;
+    }
+  }
+  if (out_densities) std::memcpy(out_densities, dens.data(), (size_t)n * sizeof(float));
+  *n_out = kept; *n_dense = dense;
+  return kept > 0 ? LSGPU_OK : LSGPU_NO_CONVERGENCE;
 }
 
 int lsgpu_check_rigid(const float T[16]) { return std::fabs(1.0f - det3(T)) <= 0.001f; }

@@ -28,6 +28,7 @@
 #include "lsgpu_knn.hip.h"
 #include "lsgpu_knn_k.hip.h"
 #include "lsgpu_snf.hip.h"
+#include "lsgpu_max_density.hip.h"
 #include "lsgpu_cone.hip.h"
 #include "lsgpu_solve.hip.h"
 #include "lsgpu_cov.hip.h"
@@ -295,6 +296,12 @@ struct lsgpu_icp {
   lsgpu_chain_cuts cuts{};
   DevBuf<uint32_t> cut_blk;   // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
   DevBuf<float4> cut_ref;     // the reference behind its cut modules
+  // MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 (lsgpu_icp_set_max_density; lsgpu_max_density.hip.h)
+  bool md_on = false;
+  lsgpu_max_density_config md_cfg{};
+  DevBuf<float> dens, dens_io;   // the density of every point of the cloud as given; its staging for a host caller
+  DevBuf<MdStat> md_stat;        // minimum / maximum of the densities, NaN count
+  DevBuf<uint32_t> md_blk;       // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
   float* draws_pinned = nullptr;  // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
@@ -533,9 +540,23 @@ int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
                    : (h->normals_on && h->normals.max_angle >= 0.f) ? "SurfaceNormalOutlierFilter"
                    : h->comm ? "the split-scan mode (lsgpu_icp_comm_init)" : nullptr;
   if (with) { h->err = std::string(mod) + "not together with " + with; return LSGPU_BAD_CONFIG; }
+  if (h->md_on) { h->err = std::string(mod) + "not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
   if (!h->cov_on) h->quality_state = 0;
   h->cov_cfg = *cfg;
   h->cov_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_set_max_density(lsgpu_icp* h, const lsgpu_max_density_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->md_on = false; return LSGPU_OK; }
+  // (SurfaceNormalDataPointsFilter's knn comes with the chain: lsgpu_icp_compute checks that it is there)
+  if (const char* why = lsgpu_max_density_config_why(cfg, kSnfMinKnn)) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (h->comm) { h->err = "MaxDensityDataPointsFilter: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
+  if (h->cov_on) { h->err = "MaxDensityDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
+  h->md_cfg = *cfg;
+  h->md_on = true;
   return LSGPU_OK;
 }
 
@@ -628,7 +649,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->ref_in.release(); h->nrm_in.release(); h->scr_main.release(); h->scr_side.release();
   h->pts.release();
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
-  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->cut_blk.release(); h->cut_ref.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
+  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->cut_blk.release(); h->cut_ref.release(); h->dens.release(); h->dens_io.release(); h->md_stat.release(); h->md_blk.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
@@ -1295,6 +1316,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
   }
   if (h->cov_on) {
     h->err = "comm_init: the split-scan mode does not run PointToPlaneWithCovErrorMinimizer";
+    return LSGPU_BAD_CONFIG;
+  }
+  if (h->md_on) {
+    h->err = "comm_init: the split-scan mode does not run MaxDensityDataPointsFilter";
     return LSGPU_BAD_CONFIG;
   }
   if (h->cuts_on) {
@@ -2154,20 +2179,28 @@ static int cut_section_wait(lsgpu_icp* h, bool rs, int64_t* pre, int64_t* kept) 
 
 // SurfaceNormalDataPointsFilter on the reference the handle holds (set_reference has just been enqueued on h->stream):
 // normals of the sorted points into h->nrm; ids / d2 (device, nullable) in the order the cloud was given.
+// dens (device, nullable): keepDensities 1 -- the density of every point, in the order the cloud was given (the DENS kernels)
+template <int K, bool DENS>
+static void launch_snf_(lsgpu_icp* h, const SnfArgs& a) {
+  hipLaunchKernelGGL((k_snf_tile<K, DENS>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, h->stream, a);
+  hipLaunchKernelGGL((k_snf_fallback<K, DENS>), dim3((unsigned)std::min((a.n + 63) / 64, 4096)), dim3(64), 0, h->stream, a);   // (strides over the list: usually short)
+}
 template <int K>
 static void launch_snf(lsgpu_icp* h, const SnfArgs& a) {
-  hipLaunchKernelGGL((k_snf_tile<K>), dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, h->stream, a);
-  hipLaunchKernelGGL((k_snf_fallback<K>), dim3((unsigned)std::min((a.n + 63) / 64, 4096)), dim3(64), 0, h->stream, a);   // (strides over the list: usually short)
+  if (a.dens) launch_snf_<K, true>(h, a); else launch_snf_<K, false>(h, a);
 }
-static int snf_device(lsgpu_icp* h, int knn, int* ids, float* d2) {
+static int snf_device(lsgpu_icp* h, int knn, int* ids, float* d2, float* dens = nullptr) {
   const int64_t n = h->nr;
-  if (knn < kSnfMinKnn || knn > kSnfMaxKnn || n < knn) return LSGPU_BAD_ARG;
+  if (knn < kSnfMinKnn || knn > kSnfMaxKnn || n < knn) {
+    h->err = "SurfaceNormalDataPointsFilter: knn must be in [3, 32] and the cloud must hold at least knn points";
+    return LSGPU_BAD_ARG;
+  }
   HIPC(h->snf_strag.reserve(n)); HIPC(h->snf_count.reserve(1));
   HIPC(hipMemsetAsync(h->snf_count.p, 0, sizeof(uint32_t), h->stream));
   SnfArgs a;
   a.n = (int)n; a.knn = knn; a.g = h->grid; a.pts = h->pts.p; a.inv = h->ref_inv.p; a.chunks = h->chunks.p;
   a.nrm = h->nrm.p; a.ids = ids; a.d2 = ids ? d2 : nullptr;
-  a.strag = h->snf_strag.p; a.strag_count = h->snf_count.p; a.r_cap = kSnfRCap;
+  a.strag = h->snf_strag.p; a.strag_count = h->snf_count.p; a.r_cap = kSnfRCap; a.dens = dens;
   // list lengths: the first knn entries of the next larger list are exact (lsgpu_snf.hip.h)
   if (knn <= 4) launch_snf<4>(h, a);
   else if (knn <= 8) launch_snf<8>(h, a);
@@ -2177,10 +2210,107 @@ static int snf_device(lsgpu_icp* h, int knn, int* ids, float* d2) {
   return LSGPU_OK;
 }
 
+// MaxDensityDataPointsFilter on the current lane (lsgpu_max_density.hip.h): src (n points, device, as given) with the densities
+// dens (device, the cloud's order) -> the kept points at the front of out_pts, their normals -- gathered from the handle's
+// sorted normals through h->ref_inv (normals false: none are read or written) -- in out_nrm; draws (device): at least n.  The
+// totals are on their way to the host ...
+static int max_density_enqueue(lsgpu_icp* h, const float4* src, int64_t n, const float* dens, float max_density,
+                               const float* draws, bool normals, float4* out_pts, float* out_nrm) {
+  const int nb = nblk(n);
+  const size_t row = ((size_t)nb + 3) & ~(size_t)3;
+  HIPC(h->md_blk.reserve(4 * row)); HIPC(h->md_stat.reserve(1));
+  uint32_t *cnt_a = h->md_blk.p, *off_a = cnt_a + row, *cnt_b = off_a + row, *off_b = cnt_b + row;
+  hipStream_t st = h->lane.stream;
+  HIPC(hipMemsetAsync(h->md_stat.p, 0, sizeof(MdStat), st));
+  HIPC(hipMemsetAsync(&h->md_stat.p->lo, 0xFF, sizeof(uint32_t), st));
+  const uint32_t* inv = h->ref_inv.p;
+  const float4* nrm = normals ? h->nrm.p : nullptr;
+  hipLaunchKernelGGL((k_md_pass<0>), dim3(nb), dim3(256), 0, st, src, dens, (int)n, max_density, (const float*)nullptr, h->md_stat.p,
+                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, cnt_a, inv, nrm, (float4*)nullptr, (float*)nullptr);
+  int rc = scan_u32(h, cnt_a, off_a, (size_t)nb);
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_md_pass<1>), dim3(nb), dim3(256), 0, st, src, dens, (int)n, max_density, draws, h->md_stat.p,
+                     (const uint32_t*)off_a, (const uint32_t*)nullptr, cnt_b, inv, nrm, (float4*)nullptr, (float*)nullptr);
+  rc = scan_u32(h, cnt_b, off_b, (size_t)nb);
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_md_pass<2>), dim3(nb), dim3(256), 0, st, src, dens, (int)n, max_density, draws, h->md_stat.p,
+                     (const uint32_t*)off_a, (const uint32_t*)off_b, (uint32_t*)nullptr, inv, nrm, out_pts, out_nrm);
+  HIPC(hipGetLastError());
+  return scan_totals_enqueue(h, cnt_a, off_a, (size_t)nb, cnt_b, off_b, (size_t)nb);
+}
+// ... and the host's wait for them: the dense points (one draw each) and the points kept
+static int max_density_wait(lsgpu_icp* h, int64_t* n_dense, int64_t* kept) {
+  uint32_t a = 0, b = 0;
+  const int rc = scan_totals_wait(h, &a, &b);
+  if (rc) return rc;
+  *n_dense = a; *kept = b;
+  return LSGPU_OK;
+}
+
+// lsgpu_icp_filter_reference_normals, with the densities of keepDensities 1 if the caller asks for them
+static int filter_reference_normals_run(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
+                                        float* out_d2, float* out_densities);
+
 extern "C" {
 
 int lsgpu_icp_filter_reference_normals(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals,
                                        int32_t* out_ids, float* out_d2) {
+  return filter_reference_normals_run(h, xyz1, n, knn, out_normals, out_ids, out_d2, nullptr);
+}
+
+int lsgpu_icp_filter_reference_normals_densities(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals,
+                                                 int32_t* out_ids, float* out_d2, float* out_densities) {
+  return filter_reference_normals_run(h, xyz1, n, knn, out_normals, out_ids, out_d2, out_densities);
+}
+
+int lsgpu_icp_filter_reference_max_density(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float max_density, int64_t seed,
+                                           float* out_xyz1, float* out_normals, float* out_densities, int64_t* n_out,
+                                           int64_t* n_dense) {
+  if (!h || !out_xyz1 || !out_normals || !n_out || !n_dense) return LSGPU_BAD_ARG;
+  h->err.clear();
+  *n_out = 0; *n_dense = 0;
+  lsgpu_max_density_config mc{};
+  mc.max_density = max_density;
+  if (const char* why = lsgpu_max_density_config_why(&mc, kSnfMinKnn)) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (knn < kSnfMinKnn || knn > kSnfMaxKnn) { h->err = "filter_reference_max_density: knn must be in [3, 32]"; return LSGPU_BAD_ARG; }
+  if (!xyz1 || n < knn) { h->err = "filter_reference_max_density: the cloud has fewer points than knn"; return LSGPU_BAD_ARG; }
+  if (n > 0x7FFFFFF0ll / knn) { h->err = "filter_reference_max_density: knn x n exceeds the 32-bit pair count"; return LSGPU_BAD_ARG; }
+  if (static_cast<const void*>(out_xyz1) == static_cast<const void*>(xyz1)) { h->err = "filter_reference_max_density: out_xyz1 must not be the input"; return LSGPU_BAD_ARG; }
+  if (seed >= 0) DrawStream::global().take(seed, 0, nullptr);
+  HIPC(hipSetDevice(h->device));
+  const float4* src = nullptr;
+  int rc = stage_points(h, xyz1, n, h->flt_in, &src);
+  if (!rc) rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(src), nullptr, n);
+  if (rc) return rc;
+  OutStage<float4> ox; OutStage<float> on;
+  if ((rc = ox.open(h, out_xyz1, h->flt_ref, n))) return rc;
+  if ((rc = on.open(h, out_normals, h->flt_nrm, 3 * n))) return rc;
+  HIPC(h->dens.reserve(n));
+  rc = snf_device(h, knn, nullptr, nullptr, h->dens.p);
+  if (rc) return rc;
+  h->have_normals = true;
+  rc = upload_draws_begin(h, -1, (size_t)n);   // at most one draw per point; the stream stays locked until the commit
+  if (rc) return rc;
+  int64_t dense = 0, kept = 0;
+  rc = max_density_enqueue(h, src, n, h->dens.p, max_density, h->ssn_draws.p, true, ox.p, on.p);
+  if (!rc) rc = max_density_wait(h, &dense, &kept);
+  DrawStream::global().commit(rc ? 0 : (size_t)dense);   // one draw per dense point
+  if (rc) return rc;
+  *n_out = kept; *n_dense = dense;
+  if ((rc = ox.copy_back(h, (size_t)kept))) return rc;
+  if ((rc = on.copy_back(h, 3 * (size_t)kept))) return rc;
+  if (out_densities)
+    HIPC(hipMemcpyAsync(out_densities, h->dens.p, (size_t)n * sizeof(float),
+                        is_device_ptr(out_densities) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  if (kept <= 0) { h->err = "filter_reference_max_density: the filter left no point"; return LSGPU_NO_CONVERGENCE; }
+  return LSGPU_OK;
+}
+
+}  // extern "C"
+
+static int filter_reference_normals_run(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
+                                        float* out_d2, float* out_densities) {
   if (!h || !out_normals || (out_d2 && !out_ids)) return LSGPU_BAD_ARG;
   h->err.clear();
   if (knn < kSnfMinKnn || knn > kSnfMaxKnn) { h->err = "filter_reference_normals: knn must be in [3, 32]"; return LSGPU_BAD_ARG; }
@@ -2193,16 +2323,21 @@ int lsgpu_icp_filter_reference_normals(lsgpu_icp* h, const float* xyz1, int64_t 
   if ((rc = on.open(h, out_normals, h->flt_nrm, 3 * n))) return rc;
   if (out_ids && (rc = oi.open(h, out_ids, h->ids_io, np))) return rc;
   if (out_ids && (rc = od.open(h, out_d2, h->d2_io, np))) return rc;   // (the kernels write both or neither: no out_d2, the handle's buffer)
-  rc = snf_device(h, knn, oi.p, od.p);
+  OutStage<float> odn;
+  if (out_densities && (rc = odn.open(h, out_densities, h->dens_io, n))) return rc;   // (the kernels store at the original index: the caller's order)
+  rc = snf_device(h, knn, oi.p, od.p, odn.p);
   if (rc) return rc;
   hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(n)), dim3(256), 0, h->stream, h->pts.p, (int)n, h->nrm.p, on.p);
   HIPC(hipGetLastError());
   if ((rc = on.copy_back(h, 3 * n))) return rc;
   if ((rc = oi.copy_back(h, np))) return rc;
   if (out_d2 && (rc = od.copy_back(h, np))) return rc;
+  if (out_densities && (rc = odn.copy_back(h, n))) return rc;
   HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
+
+extern "C" {
 
 int lsgpu_icp_filter_reference(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float ratio,
                                int64_t seed, float* out_xyz1, float* out_normals, int64_t* n_out) {
@@ -2368,6 +2503,9 @@ struct ComputeRun {
   // learns whether it went out (it reads the flag after the return: the uploader is joined by then)
   float4* const upload_into; bool* const upload_enqueued;
   bool ref_filter = false, ref_normals = false, rd_normals = false, side = false;   // what the chain and the handle ask for
+  // lsgpu_icp_set_max_density: SurfaceNormalDataPointsFilter with densities on the whole reference, then the thinning pass; the
+  // thinned cloud and its normals go on as the sampling filter's do (md_normals: somebody reads the normals)
+  bool md = false, md_normals = false;
   const lsgpu_normals_config* nc = nullptr; double t0 = 0.0;
   DrawAhead draws; std::thread uploader; hipError_t upload_err = hipSuccess;
   bool overlap_upload = false, side_used = false;   // the copy stream / the side stream has work of this call
@@ -2406,6 +2544,11 @@ struct ComputeRun {
       return LSGPU_BAD_CONFIG;
     }
     ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter);
+    if (h->md_on) {
+      if (const char* why = lsgpu_max_density_config_why(&h->md_cfg, chain->sn_knn)) { h->err = std::string("compute: ") + why; return LSGPU_BAD_CONFIG; }
+      // the normals travel with the thinned cloud (flt_nrm), as the sampling filter's: nothing is computed on the second grid
+      md = true; md_normals = ref_normals; ref_normals = false;
+    }
     if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
     if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
     if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
@@ -2416,7 +2559,8 @@ struct ComputeRun {
     // (the first part of step 5) -- do not depend on each other: the latter goes to a second stream with its own sort scratch.
     // Both are chains of short launches that leave most of the chip idle; side by side the shorter one disappears
     // (LSGPU_NO_SIDE_STREAM: one after the other).
-    side = tuning().side_stream && !h->comm && !rd_normals;
+    // (md: the reading's first draw is known only after the thinning pass has counted the dense points -- one stream)
+    side = tuning().side_stream && !h->comm && !rd_normals && !md;
     cuts = h->cuts_on ? &h->cuts : nullptr;
     rd_rs = chain->reading_prob >= 0.f;
     rd_cuts = cuts && cuts->n_reading > 0; ref_cuts = cuts && cuts->n_reference > 0;
@@ -2426,7 +2570,7 @@ struct ComputeRun {
 
   int start_uploads() {
     // the draws of both filters, produced on a helper thread from now on: at most one per reference point, then one per reading point
-    const size_t ref_draws = ref_filter ? (size_t)nr : (size_t)0;
+    const size_t ref_draws = ref_filter || md ? (size_t)nr : (size_t)0;   // (md: one per dense point)
     int rc = draws.begin(h, -1, ref_draws + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq), ref_draws);   // (the reference filter's share first)
     if (!rc) rc = stage_points(h, reference_xyz1, nr, h->flt_in, &src);   // (step 1 starts here)
     if (rc) return rc;
@@ -2478,6 +2622,23 @@ struct ComputeRun {
       if (rc) return rc;
       if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
       ref_pts = h->flt_ref.p; ref_nrm = h->flt_nrm.p;
+    }
+    if (md) {
+      // the whole reference's grid (no direction index of it), normals and densities on it, then the thinning: the draws of
+      // the dense points are the section's, the reading's start behind them
+      int rc = ref_build_front(h, reinterpret_cast<const float*>(src), nullptr, nrc);
+      if (!rc) rc = ref_build_back(h, nrc);
+      if (rc) return rc;
+      HIPC(h->dens.reserve(nrc)); HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
+      rc = snf_device(h, chain->sn_knn, nullptr, nullptr, h->dens.p);
+      if (!rc) rc = draws.ready((size_t)nr);
+      int64_t n_dense = 0;
+      if (!rc) rc = max_density_enqueue(h, src, nrc, h->dens.p, h->md_cfg.max_density, h->ssn_draws.p + draws.used, md_normals, h->flt_ref.p, h->flt_nrm.p);
+      if (!rc) rc = max_density_wait(h, &n_dense, &nrf);
+      if (rc) return rc;
+      draws.used += (size_t)n_dense;
+      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+      ref_pts = h->flt_ref.p; ref_nrm = md_normals ? h->flt_nrm.p : nullptr;
     }
     // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
     // (not with cut modules in front of RandomSampling: reading_count_wait commits then)

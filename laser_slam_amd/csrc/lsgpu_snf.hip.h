@@ -26,6 +26,7 @@
 #pragma once
 #include "lsgpu_common.hip.h"
 #include "lsgpu_box_normal.h"
+#include "lsgpu_density.h"
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_knn_k.hip.h"
 
@@ -46,6 +47,7 @@ struct SnfArgs {
   uint2* strag;               // points handed to k_snf_fallback {sorted position, bound bits} ...
   uint32_t* strag_count;      // ... and their number
   float r_cap;
+  float* dens;                // out (the DENS instantiations only): density of the point, at its ORIGINAL index
 };
 
 // the knn-th entry of a list of compile-time length, picked with masks: a runtime index -- and a chain of selects, which
@@ -59,7 +61,9 @@ __device__ __forceinline__ float snf_kth(const float (&D)[K], int knn) {
 }
 
 // the finished list of sorted point j -> optional ids / d2, normal.  col = this lane's LDS column (stride 64).
-template <int K>
+// DENS (keepDensities 1): the density of the same neighbourhood (lsgpu_density.h), read from the same column, stored at the
+// point's original index as the ids are.
+template <int K, bool DENS = false>
 __device__ __forceinline__ void snf_finish(const SnfArgs& a, int j, uint32_t orig, const float (&D)[K],
                                            const int (&I)[K], int* col) {
 #pragma unroll
@@ -76,13 +80,14 @@ __device__ __forceinline__ void snf_finish(const SnfArgs& a, int j, uint32_t ori
   float nv[3];
   const bool ok = boxnormal::box_normal(a.knn, [&](int i, int d) { return xyz[4 * (size_t)col[i * 64] + d]; }, nv);
   a.nrm[j] = ok ? make_float4(nv[0], nv[1], nv[2], 0.f) : make_float4(0.f, 1.f, 0.f, 0.f);
+  if (DENS) a.dens[orig] = density::of_neighbourhood(a.knn, [&](int i, int d) { return xyz[4 * (size_t)col[i * 64] + d]; });
 }
 
 // amdgpu_waves_per_eu on both kernels: with the default occupancy target the compiler keeps rank3's 3 x 3 work matrix
 // (rows and columns swapped by runtime index) in 48 B of scratch per lane; with it the matrix is promoted to LDS.  That is
 // a compiler heuristic: devtools/check_snf_resources.sh recompiles the kernels and fails if any of them uses scratch.
 // ---------------------------------------------------------------- tile search + normal, 64 points per wave
-template <int K>
+template <int K, bool DENS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, K > 16 ? 2 : 4))) void k_snf_tile(SnfArgs a) {
   __shared__ float4 stage[kChunkMax];
   __shared__ int nb[K * 64];
@@ -168,11 +173,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, K > 16 ? 
       }
     }
   }
-  if (search) snf_finish<K>(a, j, __float_as_uint(self.w), D, I, nb + lane);
+  if (search) snf_finish<K, DENS>(a, j, __float_as_uint(self.w), D, I, nb + lane);
 }
 
 // ---------------------------------------------------------------- exact fallback, one wave per point
-template <int K>
+template <int K, bool DENS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, K > 16 ? 2 : 4))) void k_snf_fallback(SnfArgs a) {
   __shared__ int nb[K * 64];
   const int lane = (int)threadIdx.x;
@@ -253,7 +258,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, K > 16 ? 
         D[K - 1] = INFINITY; I[K - 1] = kKnnNoIndex;
       }
     }
-    if (lane == 0) snf_finish<K>(a, j, __float_as_uint(q.w), RD, RI, nb);
+    if (lane == 0) snf_finish<K, DENS>(a, j, __float_as_uint(q.w), RD, RI, nb);
   }
 }
 

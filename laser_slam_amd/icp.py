@@ -81,7 +81,7 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None, normals=None, covariance=None, cuts=None):
+                 robust=None, normals=None, covariance=None, cuts=None, max_density=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
@@ -92,7 +92,8 @@ class IcpHandle:
         normals) -- lsgpu_icp_set_normals.  covariance: None, or PointToPlaneWithCovErrorMinimizer's sensorStdDev --
         lsgpu_icp_set_covariance (given last: it refuses a handle with modules its pass does not cover).  cuts: None, or the
         cut modules of the two filter sections (a ChainCuts, a dict of its fields, or an _lib.ChainCuts) --
-        lsgpu_icp_set_chain_cuts."""
+        lsgpu_icp_set_chain_cuts.  max_density: None, or MaxDensityDataPointsFilter's maxDensity behind the reference's
+        SurfaceNormalDataPointsFilter (compute's sn_knn) -- lsgpu_icp_set_max_density."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -138,6 +139,49 @@ class IcpHandle:
         self.cuts = None
         if cuts is not None:
             self.set_chain_cuts(cuts)
+        self.max_density = None
+        if max_density is not None:
+            self.set_max_density(max_density)
+
+    def set_max_density(self, max_density=10.0):
+        """lsgpu_icp_set_max_density: MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 in the
+        reference section of this handle's compute calls (None: off)."""
+        mc = None
+        if max_density is not None:
+            mc = _lib.MaxDensityCfg()
+            _lib.lib().lsgpu_max_density_config_default(C.byref(mc))
+            mc.max_density = float(max_density)
+        rc = _lib.lib().lsgpu_icp_set_max_density(self._h, C.byref(mc) if mc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_max_density", self._h)
+        self.max_density = None if mc is None else float(mc.max_density)
+
+    def filter_reference_max_density(self, xyz1, knn: int = 10, max_density: float = 10.0, seed: int = -1,
+                                     with_densities: bool = False):
+        """SurfaceNormalDataPointsFilter keepDensities 1 + MaxDensityDataPointsFilter on the GPU
+        (lsgpu_icp_filter_reference_max_density) -> (xyz1', normals, n_dense), or (xyz1', normals, n_dense, densities of the
+        INPUT points) with `with_densities`.  torch CUDA input gives torch CUDA output, anything else numpy."""
+        p, _k, n = _as_f32(xyz1, 4)
+        knn = int(knn)
+        if not 3 <= knn <= 32:
+            raise LsgpuError(_lib.BAD_ARG, "lsgpu_icp_filter_reference_max_density", "knn must be in [3, 32]")
+        if _is_torch(xyz1) and xyz1.is_cuda:
+            o = torch.empty((max(n, 1), 4), dtype=torch.float32, device=xyz1.device)
+            nr = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xyz1.device)
+            dn = torch.empty((max(n, 1),), dtype=torch.float32, device=xyz1.device) if with_densities else None
+            torch.cuda.synchronize()
+            po, pn, pd = o.data_ptr(), nr.data_ptr(), (dn.data_ptr() if with_densities else None)
+        else:
+            o = np.empty((max(n, 1), 4), np.float32)
+            nr = np.empty((max(n, 1), 3), np.float32)
+            dn = np.empty((max(n, 1),), np.float32) if with_densities else None
+            po, pn, pd = o.ctypes.data, nr.ctypes.data, (dn.ctypes.data if with_densities else None)
+        m, nd = C.c_int64(0), C.c_int64(0)
+        rc = _lib.lib().lsgpu_icp_filter_reference_max_density(self._h, p, n, knn, float(max_density), seed, po, pn, pd,
+                                                               C.byref(m), C.byref(nd))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_filter_reference_max_density", self._h)
+        return (o[:m.value], nr[:m.value], nd.value, dn[:n]) if with_densities else (o[:m.value], nr[:m.value], nd.value)
 
     def set_chain_cuts(self, cuts):
         """lsgpu_icp_set_chain_cuts: MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the filter sections of
@@ -346,11 +390,12 @@ class IcpHandle:
             _raise(rc, "lsgpu_icp_filter_reference", self._h)
         return o[:m.value], nr[:m.value]
 
-    def filter_reference_normals(self, xyz1, knn: int = 5, with_neighbours: bool = False):
+    def filter_reference_normals(self, xyz1, knn: int = 5, with_neighbours: bool = False, with_densities: bool = False):
         """SurfaceNormalDataPointsFilter on the GPU: every point keeps its place and gets the PCA normal of its knn
         nearest neighbours, itself included (include/lsgpu_icp.h has the contract) -> normals (n, 3), or
         (normals, ids (n, knn) int32, d2 (n, knn)) with `with_neighbours`.  torch CUDA input gives torch CUDA output,
-        anything else numpy.  The cloud becomes the handle's reference, with these normals."""
+        anything else numpy.  The cloud becomes the handle's reference, with these normals.  with_densities (keepDensities
+        1): the density of every point, (n,), is appended to the result."""
         p, _k, n = _as_f32(xyz1, 4)
         knn = int(knn)
         if not 3 <= knn <= 32:                                   # (before any output is sized with it)
@@ -361,16 +406,26 @@ class IcpHandle:
             ids = torch.empty((max(n, 1), knn), dtype=torch.int32, device=xyz1.device) if with_neighbours else None
             d2 = torch.empty((max(n, 1), knn), dtype=torch.float32, device=xyz1.device) if with_neighbours else None
             torch.cuda.synchronize()
+            dn = torch.empty((max(n, 1),), dtype=torch.float32, device=xyz1.device) if with_densities else None
             pn, pi, pd = nr.data_ptr(), (ids.data_ptr() if with_neighbours else None), (d2.data_ptr() if with_neighbours else None)
+            pdn = dn.data_ptr() if with_densities else None
         else:
             nr = np.empty((max(n, 1), 3), np.float32)
             ids = np.empty((max(n, 1), knn), np.int32) if with_neighbours else None
             d2 = np.empty((max(n, 1), knn), np.float32) if with_neighbours else None
+            dn = np.empty((max(n, 1),), np.float32) if with_densities else None
             pn, pi, pd = nr.ctypes.data, (ids.ctypes.data if with_neighbours else None), (d2.ctypes.data if with_neighbours else None)
-        rc = _lib.lib().lsgpu_icp_filter_reference_normals(self._h, p, n, int(knn), pn, pi, pd)
+            pdn = dn.ctypes.data if with_densities else None
+        if with_densities:
+            rc = _lib.lib().lsgpu_icp_filter_reference_normals_densities(self._h, p, n, int(knn), pn, pi, pd, pdn)
+        else:
+            rc = _lib.lib().lsgpu_icp_filter_reference_normals(self._h, p, n, int(knn), pn, pi, pd)
         if rc != _lib.OK:
             _raise(rc, "lsgpu_icp_filter_reference_normals", self._h)
-        return (nr[:n], ids[:n], d2[:n]) if with_neighbours else nr[:n]
+        out = (nr[:n], ids[:n], d2[:n]) if with_neighbours else (nr[:n],)
+        if with_densities:
+            out += (dn[:n],)
+        return out if len(out) > 1 else out[0]
 
     def filter_reading(self, xyz1, prob: float = 0.5, seed: int = -1):
         """RandomSamplingDataPointsFilter (icp_default.yaml:1-3) on the GPU -> xyz1'."""
@@ -702,9 +757,10 @@ def sampling_surface_normal(xyz1, knn: int = 10, ratio: float = 0.5, seed: int =
     return o[:m].copy(), nr[:m].copy()
 
 
-def surface_normal(xyz1, knn: int = 5, with_neighbours: bool = False):
+def surface_normal(xyz1, knn: int = 5, with_neighbours: bool = False, with_densities: bool = False):
     """SurfaceNormalDataPointsFilter on the host (lsgpu_filter_surface_normal; the device filter's checker, bit for bit)
-    -> normals (n, 3), or (normals, ids (n, knn), d2 (n, knn)) with `with_neighbours`."""
+    -> normals (n, 3), or (normals, ids (n, knn), d2 (n, knn)) with `with_neighbours`; with_densities (keepDensities 1)
+    appends the densities (n,)."""
     a = np.ascontiguousarray(xyz1, np.float32)
     if a.ndim != 2 or a.shape[1] != 4:
         raise ValueError(f"expected (N,4) array, got {a.shape}")
@@ -715,12 +771,36 @@ def surface_normal(xyz1, knn: int = 5, with_neighbours: bool = False):
     nr = np.empty((max(n, 1), 3), np.float32)
     ids = np.empty((max(n, 1), max(knn, 1)), np.int32) if with_neighbours else None
     d2 = np.empty((max(n, 1), max(knn, 1)), np.float32) if with_neighbours else None
-    rc = _lib.lib().lsgpu_filter_surface_normal(a.ctypes.data if n else None, n, int(knn), nr.ctypes.data,
-                                                ids.ctypes.data if with_neighbours else None,
-                                                d2.ctypes.data if with_neighbours else None)
+    dn = np.empty((max(n, 1),), np.float32) if with_densities else None
+    rc = _lib.lib().lsgpu_filter_surface_normal_densities(a.ctypes.data if n else None, n, int(knn), nr.ctypes.data,
+                                                          ids.ctypes.data if with_neighbours else None,
+                                                          d2.ctypes.data if with_neighbours else None,
+                                                          dn.ctypes.data if with_densities else None)
     if rc != _lib.OK:
         _raise(rc, "lsgpu_filter_surface_normal")
-    return (nr[:n], ids[:n], d2[:n]) if with_neighbours else nr[:n]
+    out = (nr[:n], ids[:n], d2[:n]) if with_neighbours else (nr[:n],)
+    if with_densities:
+        out += (dn[:n],)
+    return out if len(out) > 1 else out[0]
+
+
+def max_density(xyz1, knn: int = 10, max_density: float = 10.0, seed: int = -1):
+    """SurfaceNormalDataPointsFilter keepDensities 1 + MaxDensityDataPointsFilter on the host (lsgpu_filter_max_density; the
+    device pass's checker, bit for bit) -> (xyz1', normals, n_dense, densities of the input points).  Raises ConvergenceError
+    if nothing is kept (the draws are consumed all the same)."""
+    a = np.ascontiguousarray(xyz1, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"expected (N,4) array, got {a.shape}")
+    n = a.shape[0]
+    o = np.empty((max(n, 1), 4), np.float32)
+    nr = np.empty((max(n, 1), 3), np.float32)
+    dn = np.empty((max(n, 1),), np.float32)
+    m, nd = C.c_int64(0), C.c_int64(0)
+    rc = _lib.lib().lsgpu_filter_max_density(a.ctypes.data if n else None, n, int(knn), float(max_density), seed, o.ctypes.data,
+                                             nr.ctypes.data, dn.ctypes.data, C.byref(m), C.byref(nd))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_filter_max_density")
+    return o[:m.value].copy(), nr[:m.value].copy(), nd.value, dn[:n]
 
 
 def voxel_grid_points(xyz1, vsize=(1.0, 1.0, 1.0), use_centroid: bool = True) -> np.ndarray:
@@ -964,6 +1044,19 @@ class ChainConfig:
             self.extra["covariance"] = float(value)
 
     @property
+    def max_density(self) -> Optional[float]:
+        """MaxDensityDataPointsFilter's maxDensity behind the reference's SurfaceNormalDataPointsFilter with keepDensities 1
+        (`reference_normal_knn`); None: no such module.  Kept in `extra`, like `robust`."""
+        return self.extra.get("max_density")
+
+    @max_density.setter
+    def max_density(self, value):
+        if value is None:
+            self.extra.pop("max_density", None)
+        else:
+            self.extra["max_density"] = float(value)
+
+    @property
     def robust(self) -> Optional["RobustConfig"]:
         """RobustOutlierFilter's parameters (a RobustConfig); None: no such module.  Kept in `extra`, so that the fields of
         a chain without the module are what they were."""
@@ -1075,6 +1168,9 @@ def _chain_config(lc, cuts=None) -> "ChainConfig":
     sd = C.c_float()
     if _lib.lib().lsgpu_loaded_chain_covariance(C.byref(lc), C.byref(sd)):
         ch.covariance = _f32(sd.value)
+    md = C.c_float()
+    if _lib.lib().lsgpu_loaded_chain_max_density(C.byref(lc), C.byref(md)):
+        ch.max_density = float(md.value) if np.isinf(md.value) else _f32(md.value)
     if cuts is not None and (cuts.n_reading or cuts.n_reference):
         ch.cuts = _chain_cuts(cuts)
     return ch
@@ -1138,7 +1234,8 @@ class ICP:
                                      self.chain.matcher_max_dist, self.chain.outlier_max_dist,
                                      self.chain.outlier_min_dist, self.chain.outlier_median_factor,
                                      robust=self.chain.robust, normals=self.chain.normals,
-                                     covariance=self.chain.covariance, cuts=self.chain.cuts)
+                                     covariance=self.chain.covariance, cuts=self.chain.cuts,
+                                     max_density=self.chain.max_density)
         return self._handle
 
     @property
