@@ -14,7 +14,10 @@ For a synthetic HDL-64E pair (default: the 4 k-point pair of the parity tests, `
                                              what those leave, and reference_densities.csv with every reference point's density:
                                              choices 36-40; such a chain's draws, the reading's included, come from the
                                              library's own stream, so --submap, whose input filters draw from the oracle's,
-                                             refuses it)
+                                             refuses it; a chain with ShadowDataPointsFilter in the reference section:
+                                             what is left behind that module too -- the library's host twin, no draw:
+                                             choices 41-44; the module on the reading is refused, the oracle's loop reads no
+                                             reading normals)
   reading_filtered.csv                       what RandomSamplingDataPointsFilter leaves: choice 8 (the draws continue the
                                              reference filter's; the process starts at srand(1) like an unseeded one)
   input_filtered.csv                         reading.csv through tests/golden/input_filters.yaml (srand(1) again): choice 9
@@ -78,6 +81,11 @@ DENSITY_CHOICES = """36 density: knn / ((4/3) pi r^3), r = the largest distance 
 38 MaxDensity: one draw per point with density > maxDensity, kept iff draw < maxDensity / density   reference_filtered.csv: WHICH rows
 39 MaxDensity: the densest points' acceptance times (1 - nbSaturated / n) as an integer division   reference_filtered.csv: rows of the densest points
 40 the reading's draws continue behind the dense points' draws   reading_filtered.csv: WHICH rows
+"""
+SHADOW_CHOICES = """41 Shadow: value = |n/|n| . p/|p||, float, three divisions per vector, sums left to right   reference_filtered.csv: WHICH rows (points near eps)
+42 Shadow: kept iff value > eps (a tie is dropped)                  reference_filtered.csv: rows whose value equals eps
+43 Shadow: a zero normal, a point at the origin, a NaN: dropped    reference_filtered.csv: those rows
+44 Shadow: p is the point as given to the section, the sensor at the frame's origin   reference_filtered.csv: WHICH rows
 """
 
 
@@ -209,6 +217,10 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
         # library's own stream: the two cannot continue one another, and a dump with two streams would not be one process's
         raise SystemExit("--submap with MaxDensityDataPointsFilter in the chain is not supported: the input filters' draws (the "
                          "oracle's rand()) and the reference section's (the library's stream) would not be one sequence")
+    if ch.shadow is not None and ch.shadow[0] is not None:
+        # the reading's module stands behind the reading's normals, which only SurfaceNormalOutlierFilter reads: not in the oracle's loop
+        raise SystemExit("ShadowDataPointsFilter in readingDataPointsFilters is not supported: the oracle's loop runs no "
+                         "SurfaceNormalOutlierFilter and reads no reading normals")
     shutil.copyfile(chain_path, os.path.join(out_dir, "icp.yaml"))
     if submap:
         rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az, voxel_grid)
@@ -237,6 +249,11 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
     else:
         rf, rn = O.sampling_surface_normal(ref, ch.surface_normal_knn, ch.surface_normal_ratio, icp_seed)
         rdf = rd[O.random_sampling(rd.shape[0], ch.reading_sampling_prob, -1)] if ch.reading_sampling_prob >= 0 else rd
+    if ch.shadow is not None:
+        # ShadowDataPointsFilter behind the reference's normals (in front of or behind the orientation pair: |dot| is the same):
+        # not in the oracle, the library's host twin; no draw: choices 41-44
+        from laser_slam_amd import icp
+        rf, rn = icp.shadow(rf, rn, ch.shadow[1])
     cloud_io.save_csv(os.path.join(out_dir, "reference_filtered.csv"), rf, rn)
     cloud_io.save_csv(os.path.join(out_dir, "reading_filtered.csv"), rdf)
     if not submap:
@@ -265,7 +282,8 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
                 % (n_az, rd.shape[0], ref.shape[0], os.path.relpath(chain_path, ROOT), g(ch.reading_sampling_prob),
                    ch.surface_normal_knn, g(ch.surface_normal_ratio), g(ch.trim_ratio), ch.max_iterations,
                    g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length,
-                   CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "")))
+                   CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "") +
+                   (SHADOW_CHOICES if ch.shadow is not None else "")))
     return rc, st.iterations
 
 

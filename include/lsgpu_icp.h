@@ -32,7 +32,8 @@
  * SurfaceNormalDataPointsFilter on the reading and ObservationDirection- + OrientNormalsDataPointsFilter on either cloud
  * (lsgpu_icp_set_normals), and PointToPlaneWithCovErrorMinimizer: the point-to-plane step plus the 6x6 covariance of the result
  * (lsgpu_icp_set_covariance, lsgpu_icp_get_quality), and MaxDensityDataPointsFilter behind the reference's
- * SurfaceNormalDataPointsFilter with keepDensities 1 (lsgpu_icp_set_max_density).
+ * SurfaceNormalDataPointsFilter with keepDensities 1 (lsgpu_icp_set_max_density), and ShadowDataPointsFilter behind the normals
+ * of either filter section (lsgpu_icp_set_shadow).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -817,6 +818,60 @@ int lsgpu_filter_max_density(const float* xyz1, int64_t n, int knn, float max_de
 /* The module's slots of a loaded chain: 1 and *max_density (nullable) if the document names MaxDensityDataPointsFilter, else 0
  * and *max_density untouched.  Host only. */
 int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density);
+
+/* ---- ShadowDataPointsFilter behind the module that produces the normals, either section (DESIGN.md §3
+ * "ShadowDataPointsFilter", §5 choices 41-44) -----------------------------------------------------------------------------
+ * Drops the points whose normal is nearly perpendicular to the ray that observed them: grazing returns and the mixed pixels at
+ * depth edges.  Restated from knowledge of upstream's ShadowDataPointsFilter::inPlaceFilter, parity unpinned.
+ *   Per point p (as given to the section -- not centred, the 4th component not read) with normal n, in float, one rounding per
+ *     operation, no fma, sums of three terms left to right:  ln = sqrtf((nx nx + ny ny) + nz nz), lp = sqrtf((px px + py py) + pz pz),
+ *     u = n / ln, v = p / lp (three divisions each), value = fabsf((ux vx + uy vy) + uz vz); kept iff value > eps
+ *     (csrc/lsgpu_shadow.h, shared by host and device).  A zero normal, a point at the origin or a NaN anywhere: value 0 or NaN,
+ *     dropped.  eps: default 0.1, finite, in [0, 3.1416].  Order of the survivors preserved, no draw consumed.
+ *   In lsgpu_icp_compute / _compute_clouds / _compute_clouds_upload (a handle with lsgpu_icp_set_shadow):
+ *     reference, chain->ssn_knn > 0: the pass runs on the sampling filter's points and normals;
+ *     reference, chain->sn_knn > 0: the grid of the whole (cut) reference, the normals on it, the pass -- the kept cloud and its
+ *       normals then go on as the sampling filter's output does (orientation, centring on the KEPT cloud's mean, grid, loop); a
+ *       point-to-point handle computes the normals for the module too;
+ *     reference, with lsgpu_icp_set_max_density: the pass runs on the thinning's output, the thinning's draws are untouched;
+ *     reference, neither ssn_knn nor sn_knn: LSGPU_BAD_CONFIG (no normals);
+ *     reading: behind its SurfaceNormalDataPointsFilter (lsgpu_normals_config.reading_sn_knn) and its orientation; the
+ *       loop and SurfaceNormalOutlierFilter see the kept points and their normals.
+ *     A section left with no point: LSGPU_NO_CONVERGENCE ("compute: the reference / reading filter left no point").  A handle
+ *     without the module enqueues what it always did.
+ *   Not together with the split-scan mode (lsgpu_icp_comm_init) or PointToPlaneWithCovErrorMinimizer (lsgpu_icp_set_covariance: its
+ *     first version does not cover a reference thinned behind the normals): LSGPU_BAD_CONFIG, the module named in
+ *     lsgpu_last_error, whichever of the two calls comes second.  reading_eps >= 0 on a handle whose lsgpu_normals_config has no
+ *     reading_sn_knn, and lsgpu_icp_set_normals taking the reading's normals away while reading_eps >= 0: refused likewise.
+ *   Loader: ShadowDataPointsFilter {eps}, once per section, anywhere behind the section's normals module (and behind
+ *     MaxDensityDataPointsFilter where there is one) but not between ObservationDirection- and OrientNormalsDataPointsFilter.
+ *     On the reading only with SurfaceNormalOutlierFilter in the chain (reading normals that no outlier filter reads stay
+ *     refused).  lsgpu_loaded_chain has no free slot left, so the module travels by its own entry, lsgpu_chain_load_shadow: a
+ *     front end that loads a document MUST call it beside lsgpu_chain_load and give the result to lsgpu_icp_set_shadow (both
+ *     facades of this repository and the shim do), or a chain with the module runs without it. */
+typedef struct lsgpu_shadow_config {
+  float reading_eps, reference_eps;   /* eps of the section's module; < 0: no module on that side */
+  int   reserved[2];                  /* 0 */
+} lsgpu_shadow_config;
+void lsgpu_shadow_config_default(lsgpu_shadow_config* c);   /* both -1: no module */
+/* Without a handle or a device: LSGPU_OK / NULL, or LSGPU_BAD_CONFIG / the reason (a static string, the module's name in it) for
+ * an eps that is NaN, infinite or above 3.1416, or a reserved field that is not 0. */
+int lsgpu_shadow_config_check(const lsgpu_shadow_config* c);
+const char* lsgpu_shadow_config_why(const lsgpu_shadow_config* c);
+/* Gives the handle the module (cfg is copied); NULL, or both eps < 0, removes it.  A bad eps and the refused combinations above:
+ * LSGPU_BAD_CONFIG before the device is touched (the handle keeps what it had). */
+int lsgpu_icp_set_shadow(lsgpu_icp* h, const lsgpu_shadow_config* cfg);
+/* The pass on a cloud with its normals (kernel-level entry): xyz1 4 floats / point, normals 3 floats / point, host or device
+ * pointers; out_xyz1 / out_normals need room for n points and must not be the inputs.  *n_out points kept.  The handle's own
+ * module is not read.  LSGPU_NO_CONVERGENCE if nothing is kept ("... the filter left no point"). */
+int lsgpu_icp_filter_shadow(lsgpu_icp* h, const float* xyz1, const float* normals, int64_t n, float eps, float* out_xyz1,
+                            float* out_normals, int64_t* n_out);
+/* Host twin (no GPU, no handle), bit-identical with the device pass; host pointers. */
+int lsgpu_filter_shadow(const float* xyz1, const float* normals, int64_t n, float eps, float* out_xyz1, float* out_normals,
+                        int64_t* n_out);
+/* The ShadowDataPointsFilter modules of a YAML document: the walk, the rules, the refusals and the texts of lsgpu_chain_load,
+ * the two eps in *out (every byte; -1 for a section without the module).  Host only. */
+int lsgpu_chain_load_shadow(const lsgpu_yaml_module* mods, int n_mods, lsgpu_shadow_config* out, char* why, int why_cap);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

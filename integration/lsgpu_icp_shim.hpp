@@ -144,6 +144,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_max_density: " + why);
       }
+      if (has_shadow_ && lsgpu_icp_set_shadow(h_, &shadow_) != LSGPU_OK) {   // ShadowDataPointsFilter behind the normals of either section
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_shadow: " + why);
+      }
     }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
@@ -182,6 +187,8 @@ class LsgpuICP {
     if (has_cuts_) cuts_ = *parsed.chainCuts();
     lsgpu_max_density_config_default(&md_);
     has_md_ = parsed.maxDensityConfig(&md_.max_density);
+    has_shadow_ = parsed.shadowConfig() != nullptr;
+    if (has_shadow_) shadow_ = *parsed.shadowConfig();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -202,6 +209,8 @@ class LsgpuICP {
   bool has_cuts_ = false;                               // ... if the chain holds any
   lsgpu_max_density_config md_{};                       // MaxDensityDataPointsFilter's maxDensity ...
   bool has_md_ = false;                                 // ... if the chain names the module
+  lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};      // ShadowDataPointsFilter's eps of the two filter sections ...
+  bool has_shadow_ = false;                             // ... if the chain names the module
   int64_t seed_ = -1;
 };
 

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "lsgpu_max_density_config_default", "lsgpu_max_density_config_check", "lsgpu_max_density_config_why",
     "lsgpu_icp_set_max_density", "lsgpu_icp_filter_reference_normals_densities", "lsgpu_icp_filter_reference_max_density",
     "lsgpu_filter_surface_normal_densities", "lsgpu_filter_max_density", "lsgpu_loaded_chain_max_density",
+    "lsgpu_shadow_config_default", "lsgpu_shadow_config_check", "lsgpu_shadow_config_why", "lsgpu_icp_set_shadow",
+    "lsgpu_icp_filter_shadow", "lsgpu_filter_shadow", "lsgpu_chain_load_shadow",
 ]
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
@@ -89,6 +91,11 @@ class CovarianceCfg(C.Structure):
 class MaxDensityCfg(C.Structure):
     """lsgpu_max_density_config: MaxDensityDataPointsFilter's parameter."""
     _fields_ = [("max_density", C.c_float), ("reserved", C.c_int * 3)]
+
+
+class ShadowCfg(C.Structure):
+    """lsgpu_shadow_config: ShadowDataPointsFilter's eps of the two filter sections (< 0: no module on that side)."""
+    _fields_ = [("reading_eps", C.c_float), ("reference_eps", C.c_float), ("reserved", C.c_int * 2)]
 
 
 class IcpQuality(C.Structure):
@@ -368,6 +375,15 @@ def lib() -> C.CDLL:
     L.lsgpu_filter_surface_normal_densities.argtypes = [fp, i64, C.c_int, fp, fp, fp, fp]
     L.lsgpu_filter_max_density.argtypes = [fp, i64, C.c_int, C.c_float, i64, fp, fp, fp, C.POINTER(i64), C.POINTER(i64)]
     L.lsgpu_loaded_chain_max_density.argtypes = [C.POINTER(LoadedChain), C.POINTER(C.c_float)]
+    L.lsgpu_shadow_config_default.argtypes = [C.POINTER(ShadowCfg)]
+    L.lsgpu_shadow_config_default.restype = None
+    L.lsgpu_shadow_config_check.argtypes = [C.POINTER(ShadowCfg)]
+    L.lsgpu_shadow_config_why.argtypes = [C.POINTER(ShadowCfg)]
+    L.lsgpu_shadow_config_why.restype = C.c_char_p
+    L.lsgpu_icp_set_shadow.argtypes = [vp, C.POINTER(ShadowCfg)]
+    L.lsgpu_icp_filter_shadow.argtypes = [vp, fp, fp, i64, C.c_float, fp, fp, C.POINTER(i64)]
+    L.lsgpu_filter_shadow.argtypes = [fp, fp, i64, C.c_float, fp, fp, C.POINTER(i64)]
+    L.lsgpu_chain_load_shadow.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(ShadowCfg), C.c_char_p, C.c_int]
     _lib = L
     return L
 

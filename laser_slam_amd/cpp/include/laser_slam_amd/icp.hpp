@@ -262,6 +262,7 @@ class ICP {
     lsgpu_icp_config_default(&loaded_.icp);
     lsgpu_chain_config_default(&loaded_.chain);
     std::memset(&cuts_, 0, sizeof(cuts_));
+    lsgpu_shadow_config_default(&shadow_);
     release();
   }
 
@@ -284,8 +285,12 @@ class ICP {
     std::memset(&cuts, 0, sizeof(cuts));
     if ((loaded.reserved[2] || loaded.reserved[3]) &&
         lsgpu_chain_load_cuts(list.data(), (int)list.size(), &cuts, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
+    // ShadowDataPointsFilter of the two sections: lsgpu_loaded_chain has no slot for it, the module travels by its own entry
+    lsgpu_shadow_config shadow;
+    if (lsgpu_chain_load_shadow(list.data(), (int)list.size(), &shadow, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
     loaded_ = loaded;
     cuts_ = cuts;
+    shadow_ = shadow;
     release();
   }
 
@@ -466,6 +471,8 @@ class ICP {
   const lsgpu_normals_config* normalsConfig() const { return loaded_.has_normals ? &loaded_.normals : nullptr; }
   // the cut modules of the two filter sections (nullptr: none)
   const lsgpu_chain_cuts* chainCuts() const { return cuts_.n_reading || cuts_.n_reference ? &cuts_ : nullptr; }
+  // ShadowDataPointsFilter's eps of the two filter sections (nullptr: no such module; an eps < 0: none on that side)
+  const lsgpu_shadow_config* shadowConfig() const { return shadow_.reading_eps >= 0.f || shadow_.reference_eps >= 0.f ? &shadow_ : nullptr; }
   const lsgpu_loaded_chain& loadedChain() const { return loaded_; }
 
  private:
@@ -545,6 +552,11 @@ class ICP {
       release();
       throw ConfigError(msg);
     }
+    if (shadowConfig() && lsgpu_icp_set_shadow(h_, &shadow_) != LSGPU_OK) {   // (behind lsgpu_icp_set_normals: the reading's needs its normals)
+      const std::string msg = std::string("lsgpu_icp_set_shadow: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
   }
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
   void check(int rc, const char* what) {
@@ -558,6 +570,7 @@ class ICP {
   int device_ = 0;
   lsgpu_loaded_chain loaded_{};   // what loadFromYaml / setDefault left: the handle's config, the filters of compute()
   lsgpu_chain_cuts cuts_{};       // ... and the cut modules of its filter sections (lsgpu_chain_load_cuts)
+  lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};   // ... and ShadowDataPointsFilter's eps of the two (lsgpu_chain_load_shadow)
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;

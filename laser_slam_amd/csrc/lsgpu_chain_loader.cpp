@@ -19,6 +19,7 @@
 #include "../../include/lsgpu_icp.h"
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_robust.h"
+#include "lsgpu_shadow.h"
 
 namespace {
 
@@ -57,6 +58,7 @@ struct Load {
   int stage[2] = {0, 0};
   bool matcher = false, minimizer = false, counter = false, robust = false, with_cov = false;
   bool ref_densities = false, max_density = false;   // the reference's SurfaceNormal has keepDensities 1; MaxDensity stands behind it
+  lsgpu_shadow_config shadow;             // ShadowDataPointsFilter of the two sections (lsgpu_chain_load_shadow): beside stage[], not in it
 
   std::string name() const { return m->name; }
   int side() const { return std::strcmp(m->section, "readingDataPointsFilters") == 0 ? 0 : 1; }
@@ -197,6 +199,23 @@ void max_density_filter(Load& l) {
   std::memcpy(&l.out.reserved[5], &f, sizeof(f));
   l.max_density = true;
 }
+// ShadowDataPointsFilter {eps}: behind the section's normals module (and behind MaxDensityDataPointsFilter, which load() sees to),
+// not inside the orientation pair, once (the row).  stage[] stays as it is: the pair may still follow
+void shadow_filter(Load& l) {
+  const std::string n = l.name();
+  const int s = l.side();
+  const std::string sec = std::string(l.m->section) + ": ";
+  if (l.stage[s] < (s == 0 ? 2 : 1))
+    refuse(sec + n + " needs the normals: it may stand only behind " +
+           (s == 0 ? "the reading's SurfaceNormalDataPointsFilter" : "SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter") +
+           " (a chain with no such module in the section cannot run it)");
+  if (l.stage[s] == 3)
+    refuse(sec + n + " may not stand between ObservationDirectionDataPointsFilter and OrientNormalsDataPointsFilter (the pair is implemented as one step)");
+  const double e = l.finite("eps", 0.1);
+  const float f = (float)e;
+  if (!(e >= 0.0 && e <= 3.1416) || !lsgpu::shadow::eps_ok(f)) refuse(n + ": eps must be in [0, 3.1416]");
+  (s == 0 ? l.shadow.reading_eps : l.shadow.reference_eps) = f;
+}
 void observation_direction(Load& l) {
   const int s = l.side();
   if (l.stage[s] != (s == 0 ? 2 : 1)) refuse(std::string(l.m->section) + ": " + l.name() + kPair);
@@ -312,6 +331,8 @@ const Row kRows[] = {
     {"referenceDataPointsFilters", "SurfaceNormalDataPointsFilter", kSurfaceNormalParams, false, reference_normals},
     {"referenceDataPointsFilters", "MaxDensityDataPointsFilter", "maxDensity", false, max_density_filter},
     {"readingDataPointsFilters", "MaxDensityDataPointsFilter", "maxDensity", false, max_density_filter},
+    {"referenceDataPointsFilters", "ShadowDataPointsFilter", "eps", true, shadow_filter},
+    {"readingDataPointsFilters", "ShadowDataPointsFilter", "eps", true, shadow_filter},
     {"referenceDataPointsFilters", "ObservationDirectionDataPointsFilter", "x y z", true, observation_direction},
     {"referenceDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
     {"readingDataPointsFilters", "MaxDistDataPointsFilter", "dim maxDist", false, cut_max_dist},
@@ -354,6 +375,10 @@ void finish(Load& l) {
   for (int s = 0; s < 2; ++s)
     if (l.stage[s] == 3)
       refuse(std::string(s == 0 ? "readingDataPointsFilters" : "referenceDataPointsFilters") + ": ObservationDirectionDataPointsFilter" + kPair);
+  const bool shadow = l.shadow.reading_eps >= 0.f || l.shadow.reference_eps >= 0.f;
+  if (l.shadow.reading_eps >= 0.f && !(o.normals.max_angle >= 0.f))   // (in front of the rule below, whose text does not name the module)
+    refuse("readingDataPointsFilters: ShadowDataPointsFilter without SurfaceNormalOutlierFilter is not implemented (reading normals that "
+           "no outlier filter reads are refused, and the module alone does not change that)");
   if (lsgpu::normal_angle::check(&o.normals, o.icp.error_minimizer, have_normals, &why) != LSGPU_OK) refuse(why);
   if (!l.counter) refuse("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
   if (l.with_cov) {   // what the covariance pass does not cover (lsgpu_icp_set_covariance refuses the same handles)
@@ -361,6 +386,7 @@ void finish(Load& l) {
                      : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
     if (with) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + with + " (the covariance is implemented for knn 1 and binary distance filters)");
     if (l.max_density) refuse("PointToPlaneWithCovErrorMinimizer: not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)");
+    if (shadow) refuse("PointToPlaneWithCovErrorMinimizer: not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)");
   }
   if (o.chain.reading_prob < 0.f) l.cuts.reading_sampling_at = l.cuts.n_reading;   // (no RandomSampling: not read)
   o.reserved[2] = l.cuts.n_reading; o.reserved[3] = l.cuts.n_reference;
@@ -373,6 +399,8 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
   // not "the default module"
   std::memset(&l.out, 0, sizeof(l.out));
   std::memset(&l.cuts, 0, sizeof(l.cuts));
+  std::memset(&l.shadow, 0, sizeof(l.shadow));
+  l.shadow.reading_eps = -1.f; l.shadow.reference_eps = -1.f;
   lsgpu_icp_config_default(&l.out.icp);
   l.out.icp.trim_ratio = 1.0f;
   l.out.icp.min_diff_rot = -1.f; l.out.icp.min_diff_trans = -1.f; l.out.icp.smooth_length = 1;   // never satisfied
@@ -403,10 +431,11 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
 
 extern "C" {
 
-// both entry points: the one walk over the modules, then what the caller asked for (`chain` or `cuts`, the other NULL)
-static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, char* why, int why_cap) {
+// the three entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts` or `shadow`, the others NULL)
+static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, lsgpu_shadow_config* shadow,
+                     char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
-  if ((!chain && !cuts) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
+  if ((!chain && !cuts && !shadow) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
   for (int i = 0; i < n_mods; ++i) {
     if (!mods[i].section || !mods[i].name || mods[i].n_params < 0 || (mods[i].n_params > 0 && !mods[i].params)) return LSGPU_BAD_ARG;
     for (int p = 0; p < mods[i].n_params; ++p)
@@ -417,6 +446,7 @@ static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
     load(mods, n_mods, l);
     if (chain) *chain = l.out;
     if (cuts) *cuts = l.cuts;
+    if (shadow) *shadow = l.shadow;
     return LSGPU_OK;
   } catch (const Refusal& r) {
     if (why && why_cap > 0) std::snprintf(why, (size_t)why_cap, "%s", r.why.c_str());
@@ -428,12 +458,17 @@ static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
 
 int lsgpu_chain_load(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* out, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
-  return out ? load_into(mods, n_mods, out, nullptr, why, why_cap) : LSGPU_BAD_ARG;
+  return out ? load_into(mods, n_mods, out, nullptr, nullptr, why, why_cap) : LSGPU_BAD_ARG;
 }
 
 int lsgpu_chain_load_cuts(const lsgpu_yaml_module* mods, int n_mods, lsgpu_chain_cuts* out, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
-  return out ? load_into(mods, n_mods, nullptr, out, why, why_cap) : LSGPU_BAD_ARG;
+  return out ? load_into(mods, n_mods, nullptr, out, nullptr, why, why_cap) : LSGPU_BAD_ARG;
+}
+
+int lsgpu_chain_load_shadow(const lsgpu_yaml_module* mods, int n_mods, lsgpu_shadow_config* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  return out ? load_into(mods, n_mods, nullptr, nullptr, out, why, why_cap) : LSGPU_BAD_ARG;
 }
 
 int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density) {

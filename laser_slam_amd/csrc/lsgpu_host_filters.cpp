@@ -23,6 +23,7 @@
 #include "lsgpu_box_normal.h"
 #include "lsgpu_density.h"
 #include "lsgpu_robust.h"
+#include "lsgpu_shadow.h"
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
 #include "lsgpu_voxel_filter.h"
@@ -319,6 +320,41 @@ int lsgpu_filter_max_density(const float* xyz1, int64_t n, int knn, float max_de
   }
   if (out_densities) std::memcpy(out_densities, dens.data(), (size_t)n * sizeof(float));
   *n_out = kept; *n_dense = dense;
+  return kept > 0 ? LSGPU_OK : LSGPU_NO_CONVERGENCE;
+}
+
+// ---- ShadowDataPointsFilter: the predicate of csrc/lsgpu_shadow.h over the cloud in its order
+void lsgpu_shadow_config_default(lsgpu_shadow_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->reading_eps = -1.f; c->reference_eps = -1.f;
+}
+const char* lsgpu_shadow_config_why(const lsgpu_shadow_config* c) {
+  if (!c) return "ShadowDataPointsFilter: no configuration";
+  // (eps < 0: no module on that side; a NaN is neither)
+  if (!(c->reading_eps < 0.f) && !lsgpu::shadow::eps_ok(c->reading_eps)) return "ShadowDataPointsFilter: the reading's eps must be in [0, 3.1416] (or < 0: no module)";
+  if (!(c->reference_eps < 0.f) && !lsgpu::shadow::eps_ok(c->reference_eps)) return "ShadowDataPointsFilter: the reference's eps must be in [0, 3.1416] (or < 0: no module)";
+  if (c->reserved[0] || c->reserved[1]) return "ShadowDataPointsFilter: reserved fields must be 0";
+  return nullptr;
+}
+int lsgpu_shadow_config_check(const lsgpu_shadow_config* c) { return lsgpu_shadow_config_why(c) ? LSGPU_BAD_CONFIG : LSGPU_OK; }
+
+int lsgpu_filter_shadow(const float* xyz1, const float* normals, int64_t n, float eps, float* out_xyz1, float* out_normals,
+                        int64_t* n_out) {
+  if (!n_out) return LSGPU_BAD_ARG;
+  *n_out = 0;
+  if (n < 0 || (n > 0 && (!xyz1 || !normals || !out_xyz1 || !out_normals)) || out_xyz1 == xyz1 || out_normals == normals) return LSGPU_BAD_ARG;
+  if (!lsgpu::shadow::eps_ok(eps)) return LSGPU_BAD_CONFIG;
+  int64_t kept = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const float* p = xyz1 + 4 * i;
+    const float* v = normals + 3 * i;
+    if (!lsgpu::shadow::keeps(p[0], p[1], p[2], v[0], v[1], v[2], eps)) continue;
+    std::memcpy(out_xyz1 + 4 * kept, p, 16);
+    std::memcpy(out_normals + 3 * kept, v, 12);
+    ++kept;
+  }
+  *n_out = kept;
   return kept > 0 ? LSGPU_OK : LSGPU_NO_CONVERGENCE;
 }
 

@@ -29,6 +29,7 @@
 #include "lsgpu_knn_k.hip.h"
 #include "lsgpu_snf.hip.h"
 #include "lsgpu_max_density.hip.h"
+#include "lsgpu_shadow.hip.h"
 #include "lsgpu_cone.hip.h"
 #include "lsgpu_solve.hip.h"
 #include "lsgpu_cov.hip.h"
@@ -302,6 +303,13 @@ struct lsgpu_icp {
   DevBuf<float> dens, dens_io;   // the density of every point of the cloud as given; its staging for a host caller
   DevBuf<MdStat> md_stat;        // minimum / maximum of the densities, NaN count
   DevBuf<uint32_t> md_blk;       // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
+  // ShadowDataPointsFilter behind the normals of either section (lsgpu_icp_set_shadow; lsgpu_shadow.hip.h)
+  bool sh_on = false;
+  lsgpu_shadow_config sh_cfg{};
+  DevBuf<uint32_t> sh_blk;           // the pass's block counts and their scan: 2 rows of ceil(n / 256) words
+  DevBuf<float4> sh_ref, sh_rd;      // the kept points of the reference (behind the sampling filter or the thinning) / the reading
+  DevBuf<float> sh_nrm, sh_rd_nrm;   // the kept reference normals; the reading's normals in front of the pass
+  DevBuf<float> sh_nrm_in;           // staging of a host caller's normals (lsgpu_icp_filter_shadow)
   float* draws_pinned = nullptr;  // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
@@ -517,6 +525,10 @@ int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap) {
 int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
   if (!h) return LSGPU_BAD_ARG;
   h->err.clear();
+  if (h->sh_on && h->sh_cfg.reading_eps >= 0.f && (!cfg || cfg->reading_sn_knn <= 0)) {
+    h->err = "ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn): remove the module first (lsgpu_icp_set_shadow)";
+    return LSGPU_BAD_CONFIG;
+  }
   if (!cfg) { h->normals_on = false; return LSGPU_OK; }
   const char* why = nullptr;
   // (whether the reference has normals is known to align, for which a filter without them is inert)
@@ -541,6 +553,7 @@ int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
                    : h->comm ? "the split-scan mode (lsgpu_icp_comm_init)" : nullptr;
   if (with) { h->err = std::string(mod) + "not together with " + with; return LSGPU_BAD_CONFIG; }
   if (h->md_on) { h->err = std::string(mod) + "not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
+  if (h->sh_on) { h->err = std::string(mod) + "not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
   if (!h->cov_on) h->quality_state = 0;
   h->cov_cfg = *cfg;
   h->cov_on = true;
@@ -557,6 +570,23 @@ int lsgpu_icp_set_max_density(lsgpu_icp* h, const lsgpu_max_density_config* cfg)
   if (h->cov_on) { h->err = "MaxDensityDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
   h->md_cfg = *cfg;
   h->md_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_set_shadow(lsgpu_icp* h, const lsgpu_shadow_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->sh_on = false; return LSGPU_OK; }
+  if (const char* why = lsgpu_shadow_config_why(cfg)) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (cfg->reading_eps < 0.f && cfg->reference_eps < 0.f) { h->sh_on = false; return LSGPU_OK; }
+  if (h->comm) { h->err = "ShadowDataPointsFilter: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
+  if (h->cov_on) { h->err = "ShadowDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
+  if (cfg->reading_eps >= 0.f && !(h->normals_on && h->normals.reading_sn_knn > 0)) {
+    h->err = "ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (lsgpu_icp_set_normals with reading_sn_knn) first";
+    return LSGPU_BAD_CONFIG;
+  }
+  h->sh_cfg = *cfg;
+  h->sh_on = true;
   return LSGPU_OK;
 }
 
@@ -649,7 +679,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->ref_in.release(); h->nrm_in.release(); h->scr_main.release(); h->scr_side.release();
   h->pts.release();
   h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
-  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->cut_blk.release(); h->cut_ref.release(); h->dens.release(); h->dens_io.release(); h->md_stat.release(); h->md_blk.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
+  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->cut_blk.release(); h->cut_ref.release(); h->dens.release(); h->dens_io.release(); h->md_stat.release(); h->md_blk.release(); h->sh_blk.release(); h->sh_ref.release(); h->sh_rd.release(); h->sh_nrm.release(); h->sh_rd_nrm.release(); h->sh_nrm_in.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
   h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
   h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
   h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
@@ -1320,6 +1350,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
   }
   if (h->md_on) {
     h->err = "comm_init: the split-scan mode does not run MaxDensityDataPointsFilter";
+    return LSGPU_BAD_CONFIG;
+  }
+  if (h->sh_on) {
+    h->err = "comm_init: the split-scan mode does not run ShadowDataPointsFilter";
     return LSGPU_BAD_CONFIG;
   }
   if (h->cuts_on) {
@@ -2247,6 +2281,80 @@ static int max_density_wait(lsgpu_icp* h, int64_t* n_dense, int64_t* kept) {
   return LSGPU_OK;
 }
 
+// ShadowDataPointsFilter on the current lane (lsgpu_shadow.hip.h): src (n points, device, as given to the section) with the
+// normals nrm3 (device, 3 floats per point in the cloud's order) -- or, nrm3 == nullptr, with the handle's sorted normals
+// gathered through h->ref_inv (the snf kernels have just written them for this cloud) -> the kept points at the front of
+// out_pts, their normals in out_nrm (device, room for n points each, not the inputs).  The total is on its way to the host ...
+static int shadow_enqueue(lsgpu_icp* h, const float4* src, const float* nrm3, int64_t n, float eps, float4* out_pts, float* out_nrm) {
+  const int nb = nblk(n);
+  const size_t row = ((size_t)nb + 3) & ~(size_t)3;
+  HIPC(h->sh_blk.reserve(2 * row));
+  uint32_t *cnt = h->sh_blk.p, *off = cnt + row;
+  hipStream_t st = h->lane.stream;
+  const uint32_t* inv = h->ref_inv.p;
+  const float4* nrm4 = h->nrm.p;
+  if (nrm3)
+    hipLaunchKernelGGL((k_shadow_pass<0, false>), dim3(nb), dim3(256), 0, st, src, nrm3, (const uint32_t*)nullptr, (const float4*)nullptr,
+                       (int)n, eps, (const uint32_t*)nullptr, cnt, (float4*)nullptr, (float*)nullptr);
+  else
+    hipLaunchKernelGGL((k_shadow_pass<0, true>), dim3(nb), dim3(256), 0, st, src, (const float*)nullptr, inv, nrm4,
+                       (int)n, eps, (const uint32_t*)nullptr, cnt, (float4*)nullptr, (float*)nullptr);
+  const int rc = scan_u32(h, cnt, off, (size_t)nb);
+  if (rc) return rc;
+  if (nrm3)
+    hipLaunchKernelGGL((k_shadow_pass<2, false>), dim3(nb), dim3(256), 0, st, src, nrm3, (const uint32_t*)nullptr, (const float4*)nullptr,
+                       (int)n, eps, (const uint32_t*)off, (uint32_t*)nullptr, out_pts, out_nrm);
+  else
+    hipLaunchKernelGGL((k_shadow_pass<2, true>), dim3(nb), dim3(256), 0, st, src, (const float*)nullptr, inv, nrm4,
+                       (int)n, eps, (const uint32_t*)off, (uint32_t*)nullptr, out_pts, out_nrm);
+  HIPC(hipGetLastError());
+  return scan_totals_enqueue(h, nullptr, nullptr, 0, cnt, off, (size_t)nb);
+}
+// ... and the host's wait for it: the points kept
+static int shadow_wait(lsgpu_icp* h, int64_t* kept) {
+  uint32_t unused = 0, k = 0;
+  const int rc = scan_totals_wait(h, &unused, &k);
+  if (rc) return rc;
+  *kept = k;
+  return LSGPU_OK;
+}
+
+extern "C" {
+
+int lsgpu_icp_filter_shadow(lsgpu_icp* h, const float* xyz1, const float* normals, int64_t n, float eps, float* out_xyz1,
+                            float* out_normals, int64_t* n_out) {
+  if (!h || !n_out) return LSGPU_BAD_ARG;
+  h->err.clear();
+  *n_out = 0;
+  if (n < 0 || n > 0x7FFFFFF0ll / 3 || (n > 0 && (!xyz1 || !normals || !out_xyz1 || !out_normals))) return LSGPU_BAD_ARG;
+  if (n > 0 && (static_cast<const void*>(out_xyz1) == static_cast<const void*>(xyz1) || static_cast<const void*>(out_normals) == static_cast<const void*>(normals))) {
+    h->err = "filter_shadow: the outputs must not be the inputs";
+    return LSGPU_BAD_ARG;
+  }
+  if (!shadow::eps_ok(eps)) { h->err = "ShadowDataPointsFilter: eps must be in [0, 3.1416]"; return LSGPU_BAD_CONFIG; }
+  if (n == 0) { h->err = "filter_shadow: no points to filter"; return LSGPU_NO_CONVERGENCE; }
+  HIPC(hipSetDevice(h->device));
+  const float4* src = nullptr; const float* nsrc = nullptr;
+  int rc = stage_points(h, xyz1, n, h->flt_in, &src);
+  if (!rc) rc = stage_in(h, normals, (size_t)3 * n, h->sh_nrm_in, &nsrc);
+  if (rc) return rc;
+  OutStage<float4> ox; OutStage<float> on;
+  if ((rc = ox.open(h, out_xyz1, h->sh_ref, n))) return rc;
+  if ((rc = on.open(h, out_normals, h->sh_nrm, 3 * n))) return rc;
+  int64_t kept = 0;
+  rc = shadow_enqueue(h, src, nsrc, n, eps, ox.p, on.p);
+  if (!rc) rc = shadow_wait(h, &kept);
+  if (rc) return rc;
+  *n_out = kept;
+  if ((rc = ox.copy_back(h, (size_t)kept))) return rc;
+  if ((rc = on.copy_back(h, 3 * (size_t)kept))) return rc;
+  HIPC(hipStreamSynchronize(h->stream));
+  if (kept <= 0) { h->err = "filter_shadow: the filter left no point"; return LSGPU_NO_CONVERGENCE; }
+  return LSGPU_OK;
+}
+
+}  // extern "C"
+
 // lsgpu_icp_filter_reference_normals, with the densities of keepDensities 1 if the caller asks for them
 static int filter_reference_normals_run(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
                                         float* out_d2, float* out_densities);
@@ -2506,10 +2614,13 @@ struct ComputeRun {
   // lsgpu_icp_set_max_density: SurfaceNormalDataPointsFilter with densities on the whole reference, then the thinning pass; the
   // thinned cloud and its normals go on as the sampling filter's do (md_normals: somebody reads the normals)
   bool md = false, md_normals = false;
+  // lsgpu_icp_set_shadow: ShadowDataPointsFilter on the reference (sh_ref; sh_sn: behind SurfaceNormalDataPointsFilter without
+  // the thinning -- the md route without it; sh_ref_normals: somebody behind the module reads the normals) / on the reading
+  bool sh_ref = false, sh_sn = false, sh_ref_normals = false, sh_rd = false;
   const lsgpu_normals_config* nc = nullptr; double t0 = 0.0;
   DrawAhead draws; std::thread uploader; hipError_t upload_err = hipSuccess;
   bool overlap_upload = false, side_used = false;   // the copy stream / the side stream has work of this call
-  const float4 *src = nullptr, *ref_pts = nullptr; const float* ref_nrm = nullptr;   // the reference on the device: as given, as the grid gets it
+  const float4 *src = nullptr, *ref_pts = nullptr; float* ref_nrm = nullptr;   // the reference on the device: as given, as the grid gets it
   const float4 *rd_src = nullptr, *rd_dev = nullptr; int64_t nrf = 0, nqf = 0;       // the reading: as given, as the loop gets it; points kept
   AlignExtras extras{};   // what finish() tells the align
   // lsgpu_icp_set_chain_cuts: the sections' cut modules.  rd_pre_cuts: some stand in front of RandomSampling, so the number of
@@ -2548,6 +2659,15 @@ struct ComputeRun {
       if (const char* why = lsgpu_max_density_config_why(&h->md_cfg, chain->sn_knn)) { h->err = std::string("compute: ") + why; return LSGPU_BAD_CONFIG; }
       // the normals travel with the thinned cloud (flt_nrm), as the sampling filter's: nothing is computed on the second grid
       md = true; md_normals = ref_normals; ref_normals = false;
+    }
+    if (h->sh_on) {
+      sh_rd = h->sh_cfg.reading_eps >= 0.f; sh_ref = h->sh_cfg.reference_eps >= 0.f;
+      if (sh_rd && !rd_normals) { h->err = "compute: ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn)"; return LSGPU_BAD_CONFIG; }
+      if (sh_ref && chain->ssn_knn == 0 && chain->sn_knn == 0) { h->err = "compute: ShadowDataPointsFilter on the reference needs the normals of a reference filter (ssn_knn or sn_knn)"; return LSGPU_BAD_CONFIG; }
+      if (sh_ref && md) { sh_ref_normals = md_normals; md_normals = true; }   // (the thinning gathers the normals for the module)
+      // behind SurfaceNormalDataPointsFilter: the normals on the whole reference's grid, whoever reads them afterwards; the kept
+      // cloud carries them (flt_nrm), nothing is computed on the second grid
+      if (sh_ref && !md && chain->sn_knn != 0) { sh_sn = true; sh_ref_normals = ref_normals; ref_normals = false; }
     }
     if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
     if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
@@ -2639,6 +2759,28 @@ struct ComputeRun {
       draws.used += (size_t)n_dense;
       if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
       ref_pts = h->flt_ref.p; ref_nrm = md_normals ? h->flt_nrm.p : nullptr;
+    }
+    if (sh_sn) {
+      // the md route without the thinning: the whole reference's grid (no direction index of it), the normals on it, the pass
+      // with the gather through the sort's inverse
+      int rc = ref_build_front(h, reinterpret_cast<const float*>(src), nullptr, nrc);
+      if (!rc) rc = ref_build_back(h, nrc);
+      if (rc) return rc;
+      HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
+      rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
+      if (!rc) rc = shadow_enqueue(h, src, nullptr, nrc, h->sh_cfg.reference_eps, h->flt_ref.p, h->flt_nrm.p);
+      if (!rc) rc = shadow_wait(h, &nrf);
+      if (rc) return rc;
+      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+      ref_pts = h->flt_ref.p; ref_nrm = sh_ref_normals ? h->flt_nrm.p : nullptr;
+    } else if (sh_ref) {
+      // behind the sampling filter or the thinning: their points and normals (flt_ref / flt_nrm), compacted together
+      HIPC(h->sh_ref.reserve(nrf)); HIPC(h->sh_nrm.reserve(3 * nrf));
+      int rc = shadow_enqueue(h, ref_pts, ref_nrm, nrf, h->sh_cfg.reference_eps, h->sh_ref.p, h->sh_nrm.p);
+      if (!rc) rc = shadow_wait(h, &nrf);
+      if (rc) return rc;
+      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
+      ref_pts = h->sh_ref.p; ref_nrm = (md && !sh_ref_normals) ? nullptr : h->sh_nrm.p;
     }
     // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
     // (not with cut modules in front of RandomSampling: reading_count_wait commits then)
@@ -2741,11 +2883,21 @@ struct ComputeRun {
     if (!rc) rc = snf_device(h, nc->reading_sn_knn, nullptr, nullptr);
     if (rc) return rc;
     HIPC(h->rd_nrm.reserve((size_t)3 * nqf));
-    hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nqf)), dim3(256), 0, h->stream, h->pts.p, (int)nqf, h->nrm.p, h->rd_nrm.p);
+    float* rn = h->rd_nrm.p;   // (ShadowDataPointsFilter behind them: a buffer in front of the pass, which writes h->rd_nrm)
+    if (sh_rd) { HIPC(h->sh_rd_nrm.reserve((size_t)3 * nqf)); rn = h->sh_rd_nrm.p; }
+    hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nqf)), dim3(256), 0, h->stream, h->pts.p, (int)nqf, h->nrm.p, rn);
     if (nc->reading_orient)
       hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nqf)), dim3(256), 0, h->stream, rd_dev, (const float4*)nullptr, (int)nqf,
-                         nc->reading_sensor[0], nc->reading_sensor[1], nc->reading_sensor[2], nc->reading_orient, h->rd_nrm.p, (float4*)nullptr);
+                         nc->reading_sensor[0], nc->reading_sensor[1], nc->reading_sensor[2], nc->reading_orient, rn, (float4*)nullptr);
     HIPC(hipGetLastError());
+    if (sh_rd) {   // the loop and the angle filter see the kept points and their normals from here on
+      HIPC(h->sh_rd.reserve(nqf));
+      rc = shadow_enqueue(h, rd_dev, rn, nqf, h->sh_cfg.reading_eps, h->sh_rd.p, h->rd_nrm.p);
+      if (!rc) rc = shadow_wait(h, &nqf);
+      if (rc) return rc;
+      if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
+      rd_dev = h->sh_rd.p;
+    }
     extras.reading_normals = true;
     return LSGPU_OK;
   }
@@ -2754,7 +2906,7 @@ struct ComputeRun {
   int build_reference() {
     if (nc && nc->reference_orient && ref_nrm)   // the sampling filter's normals, beside its points
       hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, (const float4*)nullptr, (int)nrf,
-                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, h->flt_nrm.p, (float4*)nullptr);
+                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, ref_nrm, (float4*)nullptr);
     int rc = ref_build_front(h, reinterpret_cast<const float*>(ref_pts), ref_nrm, nrf);
     if (!rc && side) rc = order_queries_on_side_lane();
     if (!rc) rc = ref_build_back(h, nrf);

@@ -81,7 +81,7 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None, normals=None, covariance=None, cuts=None, max_density=None):
+                 robust=None, normals=None, covariance=None, cuts=None, max_density=None, shadow=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
@@ -93,7 +93,10 @@ class IcpHandle:
         lsgpu_icp_set_covariance (given last: it refuses a handle with modules its pass does not cover).  cuts: None, or the
         cut modules of the two filter sections (a ChainCuts, a dict of its fields, or an _lib.ChainCuts) --
         lsgpu_icp_set_chain_cuts.  max_density: None, or MaxDensityDataPointsFilter's maxDensity behind the reference's
-        SurfaceNormalDataPointsFilter (compute's sn_knn) -- lsgpu_icp_set_max_density."""
+        SurfaceNormalDataPointsFilter (compute's sn_knn) -- lsgpu_icp_set_max_density.  shadow: None, or
+        ShadowDataPointsFilter's eps as (reading_eps, reference_eps), None or a negative value for a side without the module
+        (a dict with those keys or an _lib.ShadowCfg too) -- lsgpu_icp_set_shadow (the reading's needs `normals` with
+        reading_sn_knn)."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -142,6 +145,42 @@ class IcpHandle:
         self.max_density = None
         if max_density is not None:
             self.set_max_density(max_density)
+        self.shadow = None
+        if shadow is not None:
+            self.set_shadow(shadow)
+
+    def set_shadow(self, shadow):
+        """lsgpu_icp_set_shadow: ShadowDataPointsFilter behind the normals of the reading's / the reference's section of this
+        handle's compute calls.  shadow: (reading_eps, reference_eps), a dict with those keys or an _lib.ShadowCfg; None or a
+        negative eps: no module on that side; None: off."""
+        sc = shadow_cfg(shadow) if shadow is not None else None
+        rc = _lib.lib().lsgpu_icp_set_shadow(self._h, C.byref(sc) if sc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_shadow", self._h)
+        on = sc is not None and (sc.reading_eps >= 0 or sc.reference_eps >= 0)
+        self.shadow = (float(sc.reading_eps), float(sc.reference_eps)) if on else None
+
+    def filter_shadow(self, xyz1, normals, eps: float = 0.1):
+        """ShadowDataPointsFilter on the GPU (lsgpu_icp_filter_shadow) -> (xyz1', normals').  torch CUDA inputs give torch CUDA
+        outputs, anything else numpy.  Raises ConvergenceError if nothing is kept."""
+        p, _k, n = _as_f32(xyz1, 4)
+        q, _k3, m = _as_f32(normals, 3)
+        if m != n:
+            raise ValueError(f"{n} points, {m} normals")
+        if _is_torch(xyz1) and xyz1.is_cuda and _is_torch(normals) and normals.is_cuda:
+            o = torch.empty((max(n, 1), 4), dtype=torch.float32, device=xyz1.device)
+            nr = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xyz1.device)
+            torch.cuda.synchronize()
+            po, pn = o.data_ptr(), nr.data_ptr()
+        else:
+            o = np.empty((max(n, 1), 4), np.float32)
+            nr = np.empty((max(n, 1), 3), np.float32)
+            po, pn = o.ctypes.data, nr.ctypes.data
+        k = C.c_int64(0)
+        rc = _lib.lib().lsgpu_icp_filter_shadow(self._h, p, q, n, float(eps), po, pn, C.byref(k))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_filter_shadow", self._h)
+        return o[:k.value], nr[:k.value]
 
     def set_max_density(self, max_density=10.0):
         """lsgpu_icp_set_max_density: MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 in the
@@ -803,6 +842,40 @@ def max_density(xyz1, knn: int = 10, max_density: float = 10.0, seed: int = -1):
     return o[:m.value].copy(), nr[:m.value].copy(), nd.value, dn[:n]
 
 
+def shadow(xyz1, normals, eps: float = 0.1):
+    """ShadowDataPointsFilter on the host (lsgpu_filter_shadow; the device pass's checker, bit for bit) -> (xyz1', normals').
+    Raises ConvergenceError if nothing is kept."""
+    a = np.ascontiguousarray(xyz1, np.float32)
+    b = np.ascontiguousarray(normals, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4 or b.ndim != 2 or b.shape[1] != 3 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"expected (N,4) points and (N,3) normals, got {a.shape} and {b.shape}")
+    n = a.shape[0]
+    o = np.empty((max(n, 1), 4), np.float32)
+    nr = np.empty((max(n, 1), 3), np.float32)
+    k = C.c_int64(0)
+    rc = _lib.lib().lsgpu_filter_shadow(a.ctypes.data if n else None, b.ctypes.data if n else None, n, float(eps), o.ctypes.data,
+                                        nr.ctypes.data, C.byref(k))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_filter_shadow")
+    return o[:k.value].copy(), nr[:k.value].copy()
+
+
+def shadow_cfg(s) -> "_lib.ShadowCfg":
+    """(reading_eps, reference_eps) / a dict with those keys / an _lib.ShadowCfg -> _lib.ShadowCfg (None or a negative eps: -1)."""
+    if isinstance(s, _lib.ShadowCfg):
+        return s
+    if isinstance(s, dict):
+        s = (s.get("reading_eps"), s.get("reference_eps"))
+    rd, ref = s
+    c = _lib.ShadowCfg()
+    _lib.lib().lsgpu_shadow_config_default(C.byref(c))
+    if rd is not None and not rd < 0:
+        c.reading_eps = float(rd)
+    if ref is not None and not ref < 0:
+        c.reference_eps = float(ref)
+    return c
+
+
 def voxel_grid_points(xyz1, vsize=(1.0, 1.0, 1.0), use_centroid: bool = True) -> np.ndarray:
     """VoxelGridDataPointsFilter of the input filter chain on the host (lsgpu_filter_voxel_grid_points; bit for bit what
     IcpHandle.apply_point_filters gives with this one module) -> one point per occupied voxel, in first-point order."""
@@ -1057,6 +1130,19 @@ class ChainConfig:
             self.extra["max_density"] = float(value)
 
     @property
+    def shadow(self):
+        """ShadowDataPointsFilter's eps of the two filter sections, (reading_eps or None, reference_eps or None); None: no
+        such module.  Kept in `extra`, like `robust`."""
+        return self.extra.get("shadow")
+
+    @shadow.setter
+    def shadow(self, value):
+        if value is None or (value[0] is None and value[1] is None):
+            self.extra.pop("shadow", None)
+        else:
+            self.extra["shadow"] = (None if value[0] is None else float(value[0]), None if value[1] is None else float(value[1]))
+
+    @property
     def robust(self) -> Optional["RobustConfig"]:
         """RobustOutlierFilter's parameters (a RobustConfig); None: no such module.  Kept in `extra`, so that the fields of
         a chain without the module are what they were."""
@@ -1141,12 +1227,22 @@ def chain_load_cuts(doc):
     return rc, why.value.decode(), out
 
 
+def chain_load_shadow(doc):
+    """lsgpu_chain_load_shadow on the same document: ShadowDataPointsFilter's eps of its two filter sections -> (return code,
+    reason of a refusal, _lib.ShadowCfg).  Same rules, same verdict and same text as chain_load."""
+    arr, n, _keep = _yaml_modules(doc)
+    out = _lib.ShadowCfg()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load_shadow(arr, n, C.byref(out), why, len(why))
+    return rc, why.value.decode(), out
+
+
 def _f32(x) -> float:
     """The shortest decimal that is this float32 (0.75, not 0.75000000000000011...): what the document said."""
     return float(str(np.float32(x)))
 
 
-def _chain_config(lc, cuts=None) -> "ChainConfig":
+def _chain_config(lc, cuts=None, shadow=None) -> "ChainConfig":
     """_lib.LoadedChain (and the _lib.ChainCuts of the same document, if it has cut modules) -> ChainConfig"""
     i, c = lc.icp, lc.chain
     name = {v: k for k, v in _MINIMIZERS.items()}[i.error_minimizer]
@@ -1173,6 +1269,8 @@ def _chain_config(lc, cuts=None) -> "ChainConfig":
         ch.max_density = float(md.value) if np.isinf(md.value) else _f32(md.value)
     if cuts is not None and (cuts.n_reading or cuts.n_reference):
         ch.cuts = _chain_cuts(cuts)
+    if shadow is not None and (shadow.reading_eps >= 0 or shadow.reference_eps >= 0):
+        ch.shadow = tuple(_f32(e) if e >= 0 else None for e in (shadow.reading_eps, shadow.reference_eps))
     return ch
 
 
@@ -1218,7 +1316,10 @@ class ICP:
             rc, why, cuts = chain_load_cuts(doc)
             if rc != _lib.OK:
                 raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        self.chain = _chain_config(loaded, cuts)
+        rc, why, shadow = chain_load_shadow(doc)                # (lsgpu_loaded_chain has no slot for the module: its own entry)
+        if rc != _lib.OK:
+            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+        self.chain = _chain_config(loaded, cuts, shadow)
         self._handle = None
 
     def _ensure_handle(self) -> IcpHandle:
@@ -1235,7 +1336,7 @@ class ICP:
                                      self.chain.outlier_min_dist, self.chain.outlier_median_factor,
                                      robust=self.chain.robust, normals=self.chain.normals,
                                      covariance=self.chain.covariance, cuts=self.chain.cuts,
-                                     max_density=self.chain.max_density)
+                                     max_density=self.chain.max_density, shadow=self.chain.shadow)
         return self._handle
 
     @property
