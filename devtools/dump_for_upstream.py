@@ -87,6 +87,13 @@ SHADOW_CHOICES = """41 Shadow: value = |n/|n| . p/|p||, float, three divisions p
 43 Shadow: a zero normal, a point at the origin, a NaN: dropped    reference_filtered.csv: those rows
 44 Shadow: p is the point as given to the section, the sensor at the frame's origin   reference_filtered.csv: WHICH rows
 """
+MOTION_CHOICES = """45 force2D / force4DOF: rows and columns {2,3,4} / {2,3,4,5} of the 6x6 system, float LLT   T of every iteration
+46 force2D: b with the planar residual n.x dx + n.y dy, normals not renormalised; matching and filters stay 3-D   T of every iteration
+47 constrained dT: third row and column exactly 0 0 1, sine / cosine of |yaw| in double   T of every iteration (last bits)
+48 BoundTransformationChecker: against the loop's first T_iter (identity, reference-mean frame), compared with >   WHETHER compute throws
+(oracle_trace.csv / oracle_result.txt are the oracle's FREE 6-DOF loop without the bound -- the oracle restates neither module;
+ the library's own records of this chain: ICP.compute, then IcpHandle.trace())
+"""
 
 
 def g(v) -> str:
@@ -283,7 +290,7 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
                    ch.surface_normal_knn, g(ch.surface_normal_ratio), g(ch.trim_ratio), ch.max_iterations,
                    g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length,
                    CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "") +
-                   (SHADOW_CHOICES if ch.shadow is not None else "")))
+                   (SHADOW_CHOICES if ch.shadow is not None else "") + (MOTION_CHOICES if ch.motion is not None else "")))
     return rc, st.iterations
 
 

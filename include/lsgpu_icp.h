@@ -873,6 +873,70 @@ int lsgpu_filter_shadow(const float* xyz1, const float* normals, int64_t n, floa
  * the two eps in *out (every byte; -1 for a section without the module).  Host only. */
 int lsgpu_chain_load_shadow(const lsgpu_yaml_module* mods, int n_mods, lsgpu_shadow_config* out, char* why, int why_cap);
 
+/* ---- PointToPlaneErrorMinimizer force4DOF / force2D and BoundTransformationChecker (DESIGN.md §3 "Constrained steps and the
+ * bound checker") ------------------------------------------------------------------------------------------------------------
+ * What a ground vehicle's ICP file adds to icp_.compute (laser_slam/src/laser_track.cpp:496-499 catches the ConvergenceError
+ * the checker throws and falls back to the odometry).  Restated from knowledge of upstream's
+ * PointToPlaneErrorMinimizer::compute_in_place and BoundTransformationChecker::check, parity unpinned.
+ *   The constrained steps (dof): per kept pair, in the loop's reference-mean frame, f = [p x n; n] and e = n . (p - q) as in the
+ *     6-DOF step; the 6x6 sums A = sum w f f^T, b = -sum w f e are formed as always.
+ *     LSGPU_MOTION_DOF_4 (force4DOF; unknowns yaw, tx, ty, tz): rows and columns {2, 3, 4, 5} of A and b are solved.
+ *     LSGPU_MOTION_DOF_3 (force2D; unknowns yaw, tx, ty): rows and columns {2, 3, 4}; b is formed with the planar residual
+ *       e2 = n.x (p.x - q.x) + n.y (p.y - q.y) (the z row of both clouds and of the normals dropped, the normals not
+ *       renormalised).  A and slot 28 (sum e^2) keep the three-dimensional terms; matching, distances, the trim limit and every
+ *       outlier filter stay three-dimensional.
+ *     Solve: the float LLT of the 6-DOF step on the sub-system; a failed pivot is LSGPU_NO_CONVERGENCE ("normal matrix not
+ *       positive definite").  dT: the rotation by yaw about the z axis through the reference mean -- sine and cosine of |yaw|
+ *       evaluated in double and rounded, third row and column exactly 0, 0, 1 -- and the translation (tz = 0 under force2D);
+ *       T_iter <- dT T_iter.  Checkers, trace layout and caps unchanged: lsgpu_iter_trace.A / .b hold the full sums (b with e2
+ *       under force2D), .x = {0, 0, yaw, tx, ty, tz} with the fixed unknowns exactly 0.  lsgpu_normal_eq on such a handle
+ *       returns the sums of its mode.
+ *     First version: KDTreeMatcher knn 1 (with or without maxDist) and any of Trimmed-, Max-, Min-, MedianDistOutlierFilter.
+ *       Not together with knn >= 2, RobustOutlierFilter, SurfaceNormalOutlierFilter, PointToPlaneWithCovErrorMinimizer,
+ *       PointToPointErrorMinimizer or the split-scan mode: LSGPU_BAD_CONFIG before the device is touched, the module named in
+ *       lsgpu_last_error, whichever call comes second.
+ *   BoundTransformationChecker (bound 1; max_rotation_norm, max_translation_norm finite and >= 0): the checker is initialised
+ *     with the loop's first T_iter; an iteration whose T_iter has angularDistance(q_iter, q_0) > max_rotation_norm or
+ *     |t_iter - t_0| > max_translation_norm is a ConvergenceError.  The bound is evaluated on the host AFTER the loop, from the
+ *     history the loop's checkers keep (one quaternion and translation per iteration, copied with the loop state): the first
+ *     entry out of bounds makes the call return LSGPU_NO_CONVERGENCE with T_out = T_init and lsgpu_last_error
+ *     "BoundTransformationChecker: limit out of bounds: rot <value>/<limit> tr <value>/<limit>".  A loop that failed by itself
+ *     in a later iteration: the bound's message wins; in an earlier one: the loop's stands.  When
+ *     CounterTransformationChecker ends the loop its last T_iter is in no history; bound_before_counter 1 (the document lists
+ *     the bound in front of the counter) checks it too, 0 does not (upstream's MaxNumIterationsReached leaves the checker
+ *     loop).  Works with either minimizer; not in the split-scan mode.  A handle without it enqueues and copies what it did. */
+#define LSGPU_MOTION_DOF_6 0   /* the free step */
+#define LSGPU_MOTION_DOF_3 3   /* force2D  */
+#define LSGPU_MOTION_DOF_4 4   /* force4DOF */
+typedef struct lsgpu_motion_config {
+  int   dof;                    /* LSGPU_MOTION_DOF_* */
+  int   bound;                  /* 1: BoundTransformationChecker */
+  float max_rotation_norm, max_translation_norm;   /* rad, m; read if bound */
+  int   bound_before_counter;   /* 1: listed in front of CounterTransformationChecker */
+  int   reserved[3];            /* 0 */
+} lsgpu_motion_config;
+void lsgpu_motion_config_default(lsgpu_motion_config* c);   /* dof 0, no bound, both limits 1 (the module's defaults), behind the counter */
+/* Without a handle or a device: LSGPU_OK / NULL, or LSGPU_BAD_CONFIG / the reason (a static string, the module's name in it). */
+int lsgpu_motion_config_check(const lsgpu_motion_config* c);
+const char* lsgpu_motion_config_why(const lsgpu_motion_config* c);
+/* Gives the handle the two modules (cfg is copied); NULL, or dof 0 without bound, removes them.  Bad values and the refused
+ * combinations above: LSGPU_BAD_CONFIG before the device is touched (the handle keeps what it had). */
+int lsgpu_icp_set_motion(lsgpu_icp* h, const lsgpu_motion_config* cfg);
+/* The step of a handle's mode from the 27 sums of lsgpu_normal_eq: dof LSGPU_MOTION_DOF_6 is lsgpu_point_to_plane_solve, _4 and
+ * _3 the constrained steps above (dof 3 expects b formed with e2, as a force2D handle's lsgpu_normal_eq returns it).  Host only,
+ * bit for bit what the device lane computes.  LSGPU_NO_CONVERGENCE (dT the identity) if the system solved is not positive
+ * definite; any other dof: LSGPU_BAD_ARG. */
+int lsgpu_point_to_plane_solve_dof(const double sums[27], int dof, float dT[16]);
+/* T_iters: n column-major 4x4 transforms, entry 0 the one the checker was initialised with.  The first index >= 1 whose
+ * rotation (angularDistance of the Eigen quaternions) or translation differs from entry 0 by MORE than its limit, -1 if there
+ * is none (or n < 2, or a NULL T_iters).  Host only; the arithmetic the library applies to the loop's history. */
+int lsgpu_bound_first_violation(const float* T_iters, int n, float max_rot, float max_trans);
+/* The force2D / force4DOF parameters and the BoundTransformationChecker of a YAML document: the walk, the rules, the refusals and
+ * the texts of lsgpu_chain_load, the result in *out (every byte; lsgpu_motion_config_default for a document with neither).  Host
+ * only.  As with lsgpu_chain_load_shadow, a front end that loads a document MUST call it beside lsgpu_chain_load and give the
+ * result to lsgpu_icp_set_motion. */
+int lsgpu_chain_load_motion(const lsgpu_yaml_module* mods, int n_mods, lsgpu_motion_config* out, char* why, int why_cap);
+
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */
 int         lsgpu_abi_version(void);

@@ -149,6 +149,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_shadow: " + why);
       }
+      if (has_motion_ && lsgpu_icp_set_motion(h_, &motion_) != LSGPU_OK) {   // force2D / force4DOF, BoundTransformationChecker
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_motion: " + why);
+      }
     }
     lsgpu_chain_config chain;
     lsgpu_chain_config_default(&chain);
@@ -189,6 +194,8 @@ class LsgpuICP {
     has_md_ = parsed.maxDensityConfig(&md_.max_density);
     has_shadow_ = parsed.shadowConfig() != nullptr;
     if (has_shadow_) shadow_ = *parsed.shadowConfig();
+    has_motion_ = parsed.motionConfig() != nullptr;
+    if (has_motion_) motion_ = *parsed.motionConfig();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
@@ -211,6 +218,8 @@ class LsgpuICP {
   bool has_md_ = false;                                 // ... if the chain names the module
   lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};      // ShadowDataPointsFilter's eps of the two filter sections ...
   bool has_shadow_ = false;                             // ... if the chain names the module
+  lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // PointToPlaneErrorMinimizer force2D / force4DOF, BoundTransformationChecker ...
+  bool has_motion_ = false;                             // ... if the chain names either
   int64_t seed_ = -1;
 };
 

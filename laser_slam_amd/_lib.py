@@ -49,7 +49,12 @@ ABI_SYMBOLS = [
     "lsgpu_filter_surface_normal_densities", "lsgpu_filter_max_density", "lsgpu_loaded_chain_max_density",
     "lsgpu_shadow_config_default", "lsgpu_shadow_config_check", "lsgpu_shadow_config_why", "lsgpu_icp_set_shadow",
     "lsgpu_icp_filter_shadow", "lsgpu_filter_shadow", "lsgpu_chain_load_shadow",
+    "lsgpu_motion_config_default", "lsgpu_motion_config_check", "lsgpu_motion_config_why", "lsgpu_icp_set_motion",
+    "lsgpu_point_to_plane_solve_dof", "lsgpu_bound_first_violation", "lsgpu_chain_load_motion",
 ]
+
+# lsgpu_motion_config.dof (LSGPU_MOTION_DOF_*): the free step, force2D, force4DOF
+MOTION_DOF_6, MOTION_DOF_3, MOTION_DOF_4 = 0, 3, 4
 
 # lsgpu_robust_config: RobustOutlierFilter's robustFct / scaleEstimator / distanceType names -> LSGPU_ROBUST_*
 ROBUST_FCT = {"cauchy": 0, "huber": 1, "tukey": 2, "gm": 3, "sc": 4, "L1": 5, "welsch": 6, "student": 7}
@@ -96,6 +101,12 @@ class MaxDensityCfg(C.Structure):
 class ShadowCfg(C.Structure):
     """lsgpu_shadow_config: ShadowDataPointsFilter's eps of the two filter sections (< 0: no module on that side)."""
     _fields_ = [("reading_eps", C.c_float), ("reference_eps", C.c_float), ("reserved", C.c_int * 2)]
+
+
+class MotionCfg(C.Structure):
+    """lsgpu_motion_config: PointToPlaneErrorMinimizer's force2D / force4DOF (dof) and BoundTransformationChecker."""
+    _fields_ = [("dof", C.c_int), ("bound", C.c_int), ("max_rotation_norm", C.c_float), ("max_translation_norm", C.c_float),
+                ("bound_before_counter", C.c_int), ("reserved", C.c_int * 3)]
 
 
 class IcpQuality(C.Structure):
@@ -384,6 +395,15 @@ def lib() -> C.CDLL:
     L.lsgpu_icp_filter_shadow.argtypes = [vp, fp, fp, i64, C.c_float, fp, fp, C.POINTER(i64)]
     L.lsgpu_filter_shadow.argtypes = [fp, fp, i64, C.c_float, fp, fp, C.POINTER(i64)]
     L.lsgpu_chain_load_shadow.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(ShadowCfg), C.c_char_p, C.c_int]
+    L.lsgpu_motion_config_default.argtypes = [C.POINTER(MotionCfg)]
+    L.lsgpu_motion_config_default.restype = None
+    L.lsgpu_motion_config_check.argtypes = [C.POINTER(MotionCfg)]
+    L.lsgpu_motion_config_why.argtypes = [C.POINTER(MotionCfg)]
+    L.lsgpu_motion_config_why.restype = C.c_char_p
+    L.lsgpu_icp_set_motion.argtypes = [vp, C.POINTER(MotionCfg)]
+    L.lsgpu_point_to_plane_solve_dof.argtypes = [C.POINTER(C.c_double), C.c_int, fp]
+    L.lsgpu_bound_first_violation.argtypes = [fp, C.c_int, C.c_float, C.c_float]
+    L.lsgpu_chain_load_motion.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(MotionCfg), C.c_char_p, C.c_int]
     _lib = L
     return L
 

@@ -263,6 +263,7 @@ class ICP {
     lsgpu_chain_config_default(&loaded_.chain);
     std::memset(&cuts_, 0, sizeof(cuts_));
     lsgpu_shadow_config_default(&shadow_);
+    lsgpu_motion_config_default(&motion_);
     release();
   }
 
@@ -288,9 +289,13 @@ class ICP {
     // ShadowDataPointsFilter of the two sections: lsgpu_loaded_chain has no slot for it, the module travels by its own entry
     lsgpu_shadow_config shadow;
     if (lsgpu_chain_load_shadow(list.data(), (int)list.size(), &shadow, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
+    // force2D / force4DOF of PointToPlaneErrorMinimizer and BoundTransformationChecker: likewise by their own entry
+    lsgpu_motion_config motion;
+    if (lsgpu_chain_load_motion(list.data(), (int)list.size(), &motion, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
     loaded_ = loaded;
     cuts_ = cuts;
     shadow_ = shadow;
+    motion_ = motion;
     release();
   }
 
@@ -473,6 +478,8 @@ class ICP {
   const lsgpu_chain_cuts* chainCuts() const { return cuts_.n_reading || cuts_.n_reference ? &cuts_ : nullptr; }
   // ShadowDataPointsFilter's eps of the two filter sections (nullptr: no such module; an eps < 0: none on that side)
   const lsgpu_shadow_config* shadowConfig() const { return shadow_.reading_eps >= 0.f || shadow_.reference_eps >= 0.f ? &shadow_ : nullptr; }
+  // PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (nullptr: neither)
+  const lsgpu_motion_config* motionConfig() const { return motion_.dof || motion_.bound ? &motion_ : nullptr; }
   const lsgpu_loaded_chain& loadedChain() const { return loaded_; }
 
  private:
@@ -557,6 +564,11 @@ class ICP {
       release();
       throw ConfigError(msg);
     }
+    if (motionConfig() && lsgpu_icp_set_motion(h_, &motion_) != LSGPU_OK) {   // (last: it refuses what the constrained steps do not cover)
+      const std::string msg = std::string("lsgpu_icp_set_motion: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
   }
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
   void check(int rc, const char* what) {
@@ -571,6 +583,7 @@ class ICP {
   lsgpu_loaded_chain loaded_{};   // what loadFromYaml / setDefault left: the handle's config, the filters of compute()
   lsgpu_chain_cuts cuts_{};       // ... and the cut modules of its filter sections (lsgpu_chain_load_cuts)
   lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};   // ... and ShadowDataPointsFilter's eps of the two (lsgpu_chain_load_shadow)
+  lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // ... and force2D / force4DOF, BoundTransformationChecker (lsgpu_chain_load_motion)
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;

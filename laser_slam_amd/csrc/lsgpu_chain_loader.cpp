@@ -59,6 +59,7 @@ struct Load {
   bool matcher = false, minimizer = false, counter = false, robust = false, with_cov = false;
   bool ref_densities = false, max_density = false;   // the reference's SurfaceNormal has keepDensities 1; MaxDensity stands behind it
   lsgpu_shadow_config shadow;             // ShadowDataPointsFilter of the two sections (lsgpu_chain_load_shadow): beside stage[], not in it
+  lsgpu_motion_config motion;             // force2D / force4DOF of PointToPlaneErrorMinimizer, BoundTransformationChecker (lsgpu_chain_load_motion)
 
   std::string name() const { return m->name; }
   int side() const { return std::strcmp(m->section, "readingDataPointsFilters") == 0 ? 0 : 1; }
@@ -293,10 +294,27 @@ void surface_normal_outlier(Load& l) {
   if (!(a >= 0.0 && a <= 3.1416)) refuse(l.name() + ": maxAngle must be in [0, 3.1416]");
   l.out.normals.max_angle = (float)a;
 }
+// force2D / force4DOF: 0 or 1 each, read on PointToPlaneErrorMinimizer; PointToPointErrorMinimizer is refused either one by
+// name.  Every other parameter of the two modules stays not looked at (the row)
+int flag01(const Load& l, const char* key) {
+  const double v = l.num(key, 0);
+  if (v != 0.0 && v != 1.0) refuse(l.name() + ": " + key + " must be 0 or 1");
+  return (int)v;
+}
 void error_minimizer(Load& l) {
   if (l.minimizer) refuse("errorMinimizer: one module at most (" + l.name() + " is a second one)");
-  l.out.icp.error_minimizer = l.name() == "PointToPointErrorMinimizer" ? LSGPU_MINIMIZER_POINT_TO_POINT : LSGPU_MINIMIZER_POINT_TO_PLANE;
+  const bool p2p = l.name() == "PointToPointErrorMinimizer";
+  l.out.icp.error_minimizer = p2p ? LSGPU_MINIMIZER_POINT_TO_POINT : LSGPU_MINIMIZER_POINT_TO_PLANE;
   l.minimizer = true;
+  if (l.name() == "PointToPlaneWithCovErrorMinimizer") return;   // (its row refuses the two parameters as unknown)
+  if (p2p) {
+    for (const char* key : {"force2D", "force4DOF"})
+      if (l.text(key)) refuse(l.name() + ": " + key + " is not implemented on the HIP path (the constrained steps are those of PointToPlaneErrorMinimizer)");
+    return;
+  }
+  const int f2 = flag01(l, "force2D"), f4 = flag01(l, "force4DOF");
+  if (f2 && f4) refuse(l.name() + ": force2D 1 together with force4DOF 1 is not implemented (what upstream does with both is not restated)");
+  l.motion.dof = f2 ? LSGPU_MOTION_DOF_3 : f4 ? LSGPU_MOTION_DOF_4 : LSGPU_MOTION_DOF_6;
 }
 // the step of PointToPlaneErrorMinimizer plus the covariance of the result: the two slots of lsgpu_loaded_chain.reserved
 void error_minimizer_with_cov(Load& l) {
@@ -313,6 +331,17 @@ void differential_checker(Load& l) {
   l.out.icp.min_diff_rot = (float)l.finite("minDiffRotErr", 0.001);
   l.out.icp.min_diff_trans = (float)l.finite("minDiffTransErr", 0.001);
   l.out.icp.smooth_length = l.truncated("smoothLength", 3);
+}
+
+// BoundTransformationChecker {maxRotationNorm, maxTranslationNorm}: once (the row); where it stands relative to the counter
+// decides whether the counter's last iteration is checked
+void bound_checker(Load& l) {
+  const double r = l.num("maxRotationNorm", 1.0), t = l.num("maxTranslationNorm", 1.0);
+  if (!(r >= 0.0) || std::isinf(r) || std::isinf((float)r)) refuse(l.name() + ": maxRotationNorm must be finite and >= 0");
+  if (!(t >= 0.0) || std::isinf(t) || std::isinf((float)t)) refuse(l.name() + ": maxTranslationNorm must be finite and >= 0");
+  l.motion.bound = 1;
+  l.motion.max_rotation_norm = (float)r; l.motion.max_translation_norm = (float)t;
+  l.motion.bound_before_counter = l.counter ? 0 : 1;
 }
 
 struct Row {
@@ -355,6 +384,7 @@ const Row kRows[] = {
     {"errorMinimizer", "PointToPlaneWithCovErrorMinimizer", "sensorStdDev", false, error_minimizer_with_cov},
     {"transformationCheckers", "CounterTransformationChecker", "maxIterationCount", true, counter_checker},
     {"transformationCheckers", "DifferentialTransformationChecker", "minDiffRotErr minDiffTransErr smoothLength", true, differential_checker},
+    {"transformationCheckers", "BoundTransformationChecker", "maxRotationNorm maxTranslationNorm", true, bound_checker},
 };
 constexpr int kNumRows = (int)(sizeof(kRows) / sizeof(kRows[0]));
 
@@ -388,6 +418,13 @@ void finish(Load& l) {
     if (l.max_density) refuse("PointToPlaneWithCovErrorMinimizer: not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)");
     if (shadow) refuse("PointToPlaneWithCovErrorMinimizer: not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)");
   }
+  if (l.motion.dof != LSGPU_MOTION_DOF_6) {   // what the constrained steps' first version does not cover (lsgpu_icp_set_motion refuses the same handles)
+    const char* with = o.icp.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2" : l.robust ? "RobustOutlierFilter"
+                     : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
+    if (with)
+      refuse(std::string("PointToPlaneErrorMinimizer: ") + (l.motion.dof == LSGPU_MOTION_DOF_3 ? "force2D" : "force4DOF") + " not together with " + with +
+             " (the constrained steps are implemented for knn 1 and binary distance filters)");
+  }
   if (o.chain.reading_prob < 0.f) l.cuts.reading_sampling_at = l.cuts.n_reading;   // (no RandomSampling: not read)
   o.reserved[2] = l.cuts.n_reading; o.reserved[3] = l.cuts.n_reference;
   o.has_robust = l.robust ? 1 : 0;
@@ -401,6 +438,8 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
   std::memset(&l.cuts, 0, sizeof(l.cuts));
   std::memset(&l.shadow, 0, sizeof(l.shadow));
   l.shadow.reading_eps = -1.f; l.shadow.reference_eps = -1.f;
+  std::memset(&l.motion, 0, sizeof(l.motion));   // (= lsgpu_motion_config_default: this file stands alone in one of the tests)
+  l.motion.max_rotation_norm = 1.f; l.motion.max_translation_norm = 1.f;
   lsgpu_icp_config_default(&l.out.icp);
   l.out.icp.trim_ratio = 1.0f;
   l.out.icp.min_diff_rot = -1.f; l.out.icp.min_diff_trans = -1.f; l.out.icp.smooth_length = 1;   // never satisfied
@@ -431,11 +470,11 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
 
 extern "C" {
 
-// the three entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts` or `shadow`, the others NULL)
+// the four entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts`, `shadow` or `motion`, the others NULL)
 static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, lsgpu_shadow_config* shadow,
-                     char* why, int why_cap) {
+                     char* why, int why_cap, lsgpu_motion_config* motion = nullptr) {
   if (why && why_cap > 0) why[0] = '\0';
-  if ((!chain && !cuts && !shadow) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
+  if ((!chain && !cuts && !shadow && !motion) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
   for (int i = 0; i < n_mods; ++i) {
     if (!mods[i].section || !mods[i].name || mods[i].n_params < 0 || (mods[i].n_params > 0 && !mods[i].params)) return LSGPU_BAD_ARG;
     for (int p = 0; p < mods[i].n_params; ++p)
@@ -447,6 +486,7 @@ static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
     if (chain) *chain = l.out;
     if (cuts) *cuts = l.cuts;
     if (shadow) *shadow = l.shadow;
+    if (motion) *motion = l.motion;
     return LSGPU_OK;
   } catch (const Refusal& r) {
     if (why && why_cap > 0) std::snprintf(why, (size_t)why_cap, "%s", r.why.c_str());
@@ -469,6 +509,11 @@ int lsgpu_chain_load_cuts(const lsgpu_yaml_module* mods, int n_mods, lsgpu_chain
 int lsgpu_chain_load_shadow(const lsgpu_yaml_module* mods, int n_mods, lsgpu_shadow_config* out, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
   return out ? load_into(mods, n_mods, nullptr, nullptr, out, why, why_cap) : LSGPU_BAD_ARG;
+}
+
+int lsgpu_chain_load_motion(const lsgpu_yaml_module* mods, int n_mods, lsgpu_motion_config* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  return out ? load_into(mods, n_mods, nullptr, nullptr, nullptr, why, why_cap, out) : LSGPU_BAD_ARG;
 }
 
 int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density) {

@@ -139,6 +139,10 @@ struct IcpState {
 // the errorMinimizer a kernel is instantiated for (= LSGPU_MINIMIZER_*, include/lsgpu_icp.h)
 constexpr int kPointToPlane = 0;
 constexpr int kPointToPoint = 1;
+// PointToPlaneErrorMinimizer force4DOF / force2D (lsgpu_icp_set_motion): the point-to-plane kernels with the sub-system solve
+// and the planar update; force2D forms b with the planar residual.  Kernel-side values only, no LSGPU_MINIMIZER_* has them
+constexpr int kPointToPlane4Dof = 2;
+constexpr int kPointToPlane2D = 3;
 constexpr int kSelBelowSlots = 64;   // counters of "distance below the predicted bin", hashed by tile ...
 constexpr int kSelBelowStride = 32;  // ... one per 128-byte line (atomics on one line serialise in L2)
 constexpr int kSelFailFlag = kSelBelowSlots * kSelBelowStride;  // word index of the failure flag

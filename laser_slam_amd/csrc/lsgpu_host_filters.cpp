@@ -398,6 +398,47 @@ int lsgpu_point_to_plane_solve(const double sums[27], float dT[16]) {
   return LSGPU_OK;
 }
 
+// ---- PointToPlaneErrorMinimizer force4DOF / force2D and BoundTransformationChecker (lsgpu_icp_set_motion)
+void lsgpu_motion_config_default(lsgpu_motion_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->max_rotation_norm = 1.f; c->max_translation_norm = 1.f;
+}
+const char* lsgpu_motion_config_why(const lsgpu_motion_config* c) {
+  if (!c) return "PointToPlaneErrorMinimizer / BoundTransformationChecker: no configuration";
+  if (c->dof != LSGPU_MOTION_DOF_6 && c->dof != LSGPU_MOTION_DOF_3 && c->dof != LSGPU_MOTION_DOF_4)
+    return "PointToPlaneErrorMinimizer: dof must be 0 (free), 3 (force2D) or 4 (force4DOF)";
+  if (c->bound != 0 && c->bound != 1) return "BoundTransformationChecker: bound must be 0 or 1";
+  if (c->bound_before_counter != 0 && c->bound_before_counter != 1) return "BoundTransformationChecker: bound_before_counter must be 0 or 1";
+  if (c->bound) {
+    if (!(c->max_rotation_norm >= 0.f) || std::isinf(c->max_rotation_norm)) return "BoundTransformationChecker: maxRotationNorm must be finite and >= 0";
+    if (!(c->max_translation_norm >= 0.f) || std::isinf(c->max_translation_norm)) return "BoundTransformationChecker: maxTranslationNorm must be finite and >= 0";
+  }
+  if (c->reserved[0] || c->reserved[1] || c->reserved[2]) return "PointToPlaneErrorMinimizer / BoundTransformationChecker: reserved fields must be 0";
+  return nullptr;
+}
+int lsgpu_motion_config_check(const lsgpu_motion_config* c) { return lsgpu_motion_config_why(c) ? LSGPU_BAD_CONFIG : LSGPU_OK; }
+
+int lsgpu_point_to_plane_solve_dof(const double sums[27], int dof, float dT[16]) {
+  if (dof == LSGPU_MOTION_DOF_6) return lsgpu_point_to_plane_solve(sums, dT);
+  if (!sums || !dT || (dof != LSGPU_MOTION_DOF_3 && dof != LSGPU_MOTION_DOF_4)) return LSGPU_BAD_ARG;
+  double A[36], b[6];
+  float x[6];
+  lsgpu::hostmath::unpack_normal_eq(sums, A, b);
+  lsgpu::hostmath::identity4(dT);
+  const bool ok = dof == LSGPU_MOTION_DOF_3 ? lsgpu::hostmath::point_to_plane_step_yaw<3>(A, b, x, dT)
+                                            : lsgpu::hostmath::point_to_plane_step_yaw<4>(A, b, x, dT);
+  return ok ? LSGPU_OK : LSGPU_NO_CONVERGENCE;
+}
+
+int lsgpu_bound_first_violation(const float* T_iters, int n, float max_rot, float max_trans) {
+  if (!T_iters || n < 2) return -1;
+  std::vector<float> hist((size_t)8 * n);
+  lsgpu::hostmath::CheckerState cs{0, 0};
+  for (int i = 0; i < n; ++i) lsgpu::hostmath::checker_push(&cs, hist.data(), T_iters + 16 * i);
+  return lsgpu::hostmath::bound_first_violation(hist.data(), n, max_rot, max_trans, nullptr, nullptr);
+}
+
 // ---- PointToPlaneWithCovErrorMinimizer: the 6x6 work on the sums of k_cov (csrc/lsgpu_cov.h)
 void lsgpu_covariance_config_default(lsgpu_covariance_config* c) {
   if (!c) return;

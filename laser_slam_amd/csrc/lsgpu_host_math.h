@@ -4,7 +4,11 @@
 //
 // libpointmatcher pieces restated here (selected by laser_slam/configurations/icp_default.yaml):
 //   PointToPlaneErrorMinimizer solve + AngleAxis update ............ yaml:18-19
+//   PointToPlaneErrorMinimizer force2D / force4DOF: the sub-system solve and the planar update (a ground vehicle's chain;
+//     not in icp_default.yaml)
 //   CounterTransformationChecker / DifferentialTransformationChecker  yaml:21-27
+//   BoundTransformationChecker: its ConvergenceError is what laser_slam/src/laser_track.cpp:496-499 catches around
+//     icp_.compute to fall back to the odometry (evaluated on the host after the loop, bound_first_violation)
 //   final composition T_refIn_refMean * T_iter * T_refMean_dataIn
 // All float, column-major 4x4 (PointMatcher<float>::TransformationParameters,
 // laser_slam/include/laser_slam/common.hpp:14).  Compiled with -ffp-contract=off; only IEEE
@@ -207,6 +211,74 @@ LSGPU_HD void delta_from_x(const float x[6], float* dT) {
   set(dT, 0, 3, x[3]); set(dT, 1, 3, x[4]); set(dT, 2, 3, x[5]);
 }
 
+// ---- PointToPlaneErrorMinimizer force4DOF / force2D: the step with roll and pitch (and, force2D, z) held fixed.
+// The unknowns are rows and columns 2 .. 2 + N - 1 of the 6x6 system: N = 4 {yaw, tx, ty, tz}, N = 3 {yaw, tx, ty}.
+// The float LLT of llt_solve6 on that sub-system; x = {0, 0, yaw, tx, ty, tz}, the fixed unknowns exactly 0.
+template <int N>
+LSGPU_HD bool llt_solve_yaw(const double A[36], const double b[6], float x[6]) {
+  static_assert(N == 3 || N == 4, "force2D: 3 unknowns, force4DOF: 4");
+  constexpr int F = 2;
+  float L[N][N];
+  float y[N], z[N];
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) L[i][j] = 0.f;
+  for (int j = 0; j < N; ++j) {
+    float s = (float)A[(F + j) * 6 + F + j];
+    for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
+    if (!(s > 0.f)) return false;
+    L[j][j] = sqrtf(s);
+    for (int i = j + 1; i < N; ++i) {
+      float t = (float)A[(F + i) * 6 + F + j];
+      for (int k = 0; k < j; ++k) t = t - L[i][k] * L[j][k];
+      L[i][j] = t / L[j][j];
+    }
+  }
+  for (int i = 0; i < N; ++i) {
+    float t = (float)b[F + i];
+    for (int k = 0; k < i; ++k) t = t - L[i][k] * y[k];
+    y[i] = t / L[i][i];
+  }
+  for (int i = N - 1; i >= 0; --i) {
+    float t = y[i];
+    for (int k = i + 1; k < N; ++k) t = t - L[k][i] * z[k];
+    z[i] = t / L[i][i];
+  }
+  for (int i = 0; i < N; ++i)
+    if (z[i] != z[i]) return false;
+  for (int i = 0; i < 6; ++i) x[i] = 0.f;
+  for (int i = 0; i < N; ++i) x[F + i] = z[i];
+  return true;
+}
+
+// dT = [rotation by x[2] about z, t = x[3..5]]: the sine and cosine of |yaw| as delta_from_x takes them (its axis is
+// (0, 0, +-1), so s * az is +-s exactly), the third row and column of the rotation written as 0, 0, 1 -- Rodrigues'
+// (1 - c) + c is not 1 in float for every c.  A yaw of 0 (or a non-finite one) gives the identity rotation.
+LSGPU_HD void delta_from_yaw(const float x[6], float* dT) {
+  identity4(dT);
+  const float ang = fabsf(x[2]);
+  if (ang > 0.f && ang <= 3.4e38f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    double sd, cd;
+    sincos((double)ang, &sd, &cd);
+    const float s = (float)sd, c = (float)cd;
+#else
+    const float s = sin_f32(ang), c = cos_f32(ang);
+#endif
+    const float sz = x[2] < 0.f ? -s : s;
+    set(dT, 0, 0, c); set(dT, 0, 1, -sz);
+    set(dT, 1, 0, sz); set(dT, 1, 1, c);
+  }
+  set(dT, 0, 3, x[3]); set(dT, 1, 3, x[4]); set(dT, 2, 3, x[5]);
+}
+
+// the constrained step from the unpacked sums: N as above.  false: a failed pivot or a NaN (dT untouched)
+template <int N>
+LSGPU_HD bool point_to_plane_step_yaw(const double A[36], const double b[6], float x[6], float dT[16]) {
+  if (!llt_solve_yaw<N>(A, b, x)) return false;
+  delta_from_yaw(x, dT);
+  return true;
+}
+
 // Eigen Quaternion(Matrix3): q = {w, x, y, z}
 LSGPU_HD void quat_from_rotation(const float* T, float q[4]) {
   float t = at(T, 0, 0) + at(T, 1, 1) + at(T, 2, 2);
@@ -282,6 +354,25 @@ LSGPU_HD bool checker_check(CheckerState* s, float* hist, int max_iter, int smoo
     if (rot < lim_rot && trans < lim_trans) { *iterate = false; *by_diff = true; }
   }
   return !(rot != rot || trans != trans);
+}
+
+// BoundTransformationChecker over a checker history (entries as checker_push writes them, entry 0 the state the checkers
+// were initialised with): the first index >= 1 whose rotation or translation differs from entry 0 by MORE than its limit,
+// -1 if there is none.  rot / trans (nullable): the two values of that entry.  Host side only: the loop's kernels do not
+// evaluate the bound, the library does after the loop.
+inline int bound_first_violation(const float* hist, int n, float max_rot, float max_trans, float* rot, float* trans) {
+  for (int i = 1; i < n; ++i) {
+    const float* e = hist + 8 * i;
+    const float r = angular_distance(e, hist);
+    const float dx = e[4] - hist[4], dy = e[5] - hist[5], dz = e[6] - hist[6];
+    const float t = sqrtf(dx * dx + dy * dy + dz * dz);
+    if (r > max_rot || t > max_trans) {
+      if (rot) *rot = r;
+      if (trans) *trans = t;
+      return i;
+    }
+  }
+  return -1;
 }
 
 }  // namespace hostmath

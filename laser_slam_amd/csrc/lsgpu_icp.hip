@@ -310,6 +310,13 @@ struct lsgpu_icp {
   DevBuf<float4> sh_ref, sh_rd;      // the kept points of the reference (behind the sampling filter or the thinning) / the reading
   DevBuf<float> sh_nrm, sh_rd_nrm;   // the kept reference normals; the reading's normals in front of the pass
   DevBuf<float> sh_nrm_in;           // staging of a host caller's normals (lsgpu_icp_filter_shadow)
+  // PointToPlaneErrorMinimizer force4DOF / force2D and BoundTransformationChecker (lsgpu_icp_set_motion)
+  bool mo_on = false;
+  lsgpu_motion_config mo_cfg{};
+  float* h_chk = nullptr;            // the bound's copy of the checker history (pinned; travels with the loop state's read-back)
+  size_t h_chk_cap = 0;              // ... floats
+  int dof() const { return mo_on ? mo_cfg.dof : LSGPU_MOTION_DOF_6; }
+  bool bound() const { return mo_on && mo_cfg.bound != 0; }
   float* draws_pinned = nullptr;  // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
@@ -513,6 +520,7 @@ int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg) {
   if (robust::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
   if (h->comm) { h->err = "RobustOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
   if (h->cov_on) { h->err = "RobustOutlierFilter: not together with PointToPlaneWithCovErrorMinimizer (its covariance takes binary weights)"; return LSGPU_BAD_CONFIG; }
+  if (h->dof()) { h->err = "RobustOutlierFilter: not together with PointToPlaneErrorMinimizer force2D / force4DOF (the constrained steps' first version takes binary distance filters)"; return LSGPU_BAD_CONFIG; }
   h->robust = *cfg;
   h->robust_on = true;
   return LSGPU_OK;
@@ -535,6 +543,7 @@ int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
   if (normal_angle::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
   if (h->comm) { h->err = "SurfaceNormalOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
   if (h->cov_on && cfg->max_angle >= 0.f) { h->err = "SurfaceNormalOutlierFilter: not together with PointToPlaneWithCovErrorMinimizer (its covariance pass does not apply the angle test)"; return LSGPU_BAD_CONFIG; }
+  if (h->dof() && cfg->max_angle >= 0.f) { h->err = "SurfaceNormalOutlierFilter: not together with PointToPlaneErrorMinimizer force2D / force4DOF (the constrained steps' first version takes binary distance filters)"; return LSGPU_BAD_CONFIG; }
   h->normals = *cfg;
   h->normals_on = true;
   return LSGPU_OK;
@@ -554,6 +563,7 @@ int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
   if (with) { h->err = std::string(mod) + "not together with " + with; return LSGPU_BAD_CONFIG; }
   if (h->md_on) { h->err = std::string(mod) + "not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
   if (h->sh_on) { h->err = std::string(mod) + "not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
+  if (h->dof()) { h->err = std::string(mod) + "not together with PointToPlaneErrorMinimizer force2D / force4DOF (the covariance is that of the free 6-DOF step)"; return LSGPU_BAD_CONFIG; }
   if (!h->cov_on) h->quality_state = 0;
   h->cov_cfg = *cfg;
   h->cov_on = true;
@@ -587,6 +597,28 @@ int lsgpu_icp_set_shadow(lsgpu_icp* h, const lsgpu_shadow_config* cfg) {
   }
   h->sh_cfg = *cfg;
   h->sh_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_set_motion(lsgpu_icp* h, const lsgpu_motion_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->mo_on = false; return LSGPU_OK; }
+  if (const char* why = lsgpu_motion_config_why(cfg)) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (cfg->dof == LSGPU_MOTION_DOF_6 && !cfg->bound) { h->mo_on = false; return LSGPU_OK; }
+  if (cfg->dof != LSGPU_MOTION_DOF_6) {
+    const char* const mod = cfg->dof == LSGPU_MOTION_DOF_3 ? "PointToPlaneErrorMinimizer force2D: " : "PointToPlaneErrorMinimizer force4DOF: ";
+    const char* with = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT ? "PointToPointErrorMinimizer (the handle's minimizer)"
+                     : h->cfg.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2"
+                     : h->robust_on ? "RobustOutlierFilter"
+                     : (h->normals_on && h->normals.max_angle >= 0.f) ? "SurfaceNormalOutlierFilter"
+                     : h->cov_on ? "PointToPlaneWithCovErrorMinimizer"
+                     : h->comm ? "the split-scan mode (lsgpu_icp_comm_init)" : nullptr;
+    if (with) { h->err = std::string(mod) + "not together with " + with + " (the constrained steps are implemented for knn 1 and binary distance filters)"; return LSGPU_BAD_CONFIG; }
+  }
+  if (cfg->bound && h->comm) { h->err = "BoundTransformationChecker: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
+  h->mo_cfg = *cfg;
+  h->mo_on = true;
   return LSGPU_OK;
 }
 
@@ -704,6 +736,7 @@ void lsgpu_icp_destroy(lsgpu_icp* h) {
   h->gs_tab.release(); h->gs_sblk.release(); h->gs_hist.release(); h->gs_cand.release(); h->gs_median.release();
   h->gs_cand_blk.release(); h->gs_cand_n.release(); h->gs_cl.release(); h->gs_err.release(); h->gs_rng.release();
   if (h->draws_pinned) (void)hipHostFree(h->draws_pinned);
+  if (h->h_chk) (void)hipHostFree(h->h_chk);
   if (h->copy_done) (void)hipEventDestroy(h->copy_done);
   if (h->ref_up_done) (void)hipEventDestroy(h->ref_up_done);
   if (h->draws_done) (void)hipEventDestroy(h->draws_done);
@@ -1360,6 +1393,11 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
     h->err = "comm_init: the split-scan mode does not run MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the ICP chain";
     return LSGPU_BAD_CONFIG;
   }
+  if (h->dof() || h->bound()) {
+    h->err = h->dof() ? "comm_init: the split-scan mode does not run PointToPlaneErrorMinimizer force2D / force4DOF"
+                      : "comm_init: the split-scan mode does not run BoundTransformationChecker";
+    return LSGPU_BAD_CONFIG;
+  }
   if (chain_on(h)) {
     h->err = (h->normals_on && h->normals.max_angle >= 0.f) ? "comm_init: the split-scan mode does not run SurfaceNormalOutlierFilter"
            : h->robust_on ? "comm_init: the split-scan mode does not run RobustOutlierFilter"
@@ -1518,7 +1556,12 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
   float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   const Mat34 Tm = to_mat34(T ? T : I);
   const int nb = std::min(kNeBlocks, nblk(nq));
-  if (h->robust_on) {
+  if constexpr (MIN == kPointToPlane4Dof || MIN == kPointToPlane2D) {   // (lsgpu_icp_set_motion refuses such a handle the weighted filter)
+    hipLaunchKernelGGL((k_normal_eq<true, false, MIN>), dim3(nb), dim3(256), 0, h->stream, q, (int)nq, Tm,
+                       idp, dp, h->pts.p, h->nrm.p, h->ref_inv.p,
+                       (const uint32_t*)nullptr, (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p,
+                       robust::Params{}, 1.f);
+  } else if (h->robust_on) {
     // RobustOutlierFilter: the pairs' weights go into the sums; the scale is the MAD of the distances given (host twin)
     const robust::Params rp = robust::params(h->robust);
     if (rp.plane && !h->have_normals) { h->err = std::string(what) + ": RobustOutlierFilter distanceType point2plane needs reference normals"; return LSGPU_BAD_CONFIG; }
@@ -1551,6 +1594,9 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
 
 int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
                     const int32_t* ids, const float* d2, float limit, double out[29]) {
+  // (a force2D / force4DOF handle: the sums of its mode -- force2D forms b with the planar residual)
+  if (h && h->dof() == LSGPU_MOTION_DOF_3) return stand_alone_sums<kPointToPlane2D>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
+  if (h && h->dof() == LSGPU_MOTION_DOF_4) return stand_alone_sums<kPointToPlane4Dof>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
   return stand_alone_sums<kPointToPlane>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
 }
 
@@ -3370,6 +3416,13 @@ static NeLoopFn ne_loop_of(bool p2p, int k) {
   using Ks = std::make_index_sequence<kKnnKMax>;
   return p2p ? ne_loop_of_k<kPointToPoint, CHAIN, RB>(k, Ks{}) : ne_loop_of_k<kPointToPlane, CHAIN, RB>(k, Ks{});
 }
+// force4DOF / force2D (lsgpu_icp_set_motion: knn 1, binary filters): the plain loop and the chain plan's k = 1 instantiation
+template <int MIN>
+static void constrained_kernels(bool chain, NeLoopFn* ne_loop, NeLoopFn* ne_loop_k, UpdateFn* update) {
+  *ne_loop = k_normal_eq_loop<MIN>;
+  *ne_loop_k = chain ? k_normal_eq_loop<MIN, 1, true, false> : nullptr;
+  *update = k_icp_update<MIN>;
+}
 static NeLoopFn ne_loop_fn(bool p2p, int k, bool chain, bool robust) {
   if (robust) return ne_loop_of<true, true>(p2p, k);
   if (chain) return ne_loop_of<true, false>(p2p, k);
@@ -3535,6 +3588,16 @@ struct AlignRun {
     ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
     update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
     ne_loop_k = ne_loop_fn(p2p, kk, chain, robust);
+    if (h->dof() == LSGPU_MOTION_DOF_4) constrained_kernels<kPointToPlane4Dof>(chain, &ne_loop, &ne_loop_k, &update);
+    if (h->dof() == LSGPU_MOTION_DOF_3) constrained_kernels<kPointToPlane2D>(chain, &ne_loop, &ne_loop_k, &update);
+    if (h->bound()) {   // the bound's host copy of the checker history
+      const size_t need = (size_t)8 * (max_it + 2);
+      if (need > h->h_chk_cap) {
+        if (h->h_chk) { (void)hipHostFree(h->h_chk); h->h_chk = nullptr; h->h_chk_cap = 0; }
+        HIPC(hipHostMalloc((void**)&h->h_chk, need * sizeof(float), hipHostMallocDefault));
+        h->h_chk_cap = need;
+      }
+    }
     ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
     return LSGPU_OK;
   }
@@ -3651,6 +3714,8 @@ struct AlignRun {
   // and exits at once if the state it finds says `done`.
   int fetch_state(int* enqueued_ahead) {
     *enqueued_ahead = 0;
+    if (h->bound())   // BoundTransformationChecker: the history travels with the state (evaluated after the loop, check_bound)
+      HIPC(hipMemcpyAsync(h->h_chk, h->chk_hist.p, (size_t)8 * (max_it + 2) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipMemcpyAsync(hst, h->state.p, sizeof(IcpState), hipMemcpyDeviceToHost, h->stream));
     policy::Iteration ahead_it;
     if (h->pol.lookahead_iteration(h->pol_cfg, &ahead_it)) {
@@ -3731,6 +3796,28 @@ struct AlignRun {
         return LSGPU_HIP_ERROR;
       }
     }
+  }
+
+  // BoundTransformationChecker, after the loop: the first entry of the checker history (entry 0: the state the checkers were
+  // initialised with) out of bounds.  When the counter ended the loop its last T_iter is in no history: a checker listed in
+  // front of the counter has seen it.  true: violated, h->err holds the text.  A loop that failed by itself did so behind
+  // every entry of its history, so a violation found here came first.
+  bool check_bound() {
+    const lsgpu_motion_config& mc = h->mo_cfg;
+    int n = std::min(hst->n_hist, max_it + 2);
+    float* hist = h->h_chk;
+    if (mc.bound_before_counter && hst->status == LSGPU_OK && hst->done && !hst->converged && hst->iter > 0 && n <= max_it + 1) {
+      hostmath::CheckerState cs{0, n};
+      hostmath::checker_push(&cs, hist, hst->T_iter);
+      n = cs.n_hist;
+    }
+    float rot = 0.f, tr = 0.f;
+    if (hostmath::bound_first_violation(hist, n, mc.max_rotation_norm, mc.max_translation_norm, &rot, &tr) < 0) return false;
+    char buf[192];
+    std::snprintf(buf, sizeof(buf), "BoundTransformationChecker: limit out of bounds: rot %g/%g tr %g/%g", (double)rot,
+                  (double)mc.max_rotation_norm, (double)tr, (double)mc.max_translation_norm);
+    h->err = buf;
+    return true;
   }
 
   // The harvest: the index's pay-off judgement, status text, T_out (step 7), statistics and timings.  Returns the loop's status.
@@ -3885,6 +3972,10 @@ static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const 
   if (!rc) rc = run.feed();
   if (rc) return rc;
   rc = run.harvest(T_out, st);
+  if ((rc == LSGPU_OK || rc == LSGPU_NO_CONVERGENCE) && h->bound() && run.check_bound()) {
+    std::memcpy(T_out, T_init, 16 * sizeof(float));
+    rc = LSGPU_NO_CONVERGENCE;
+  }
   if (rc == LSGPU_OK && h->cov_on) {
     const int rq = covariance_pass(run, st);
     if (rq) { std::memcpy(T_out, T_init, 16 * sizeof(float)); return rq; }

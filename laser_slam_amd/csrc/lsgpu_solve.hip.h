@@ -403,6 +403,8 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
     J[2] = p.x * n.y - p.y * n.x;
     J[3] = n.x; J[4] = n.y; J[5] = n.z;
     const float res = (p.x - q.x) * n.x + (p.y - q.y) * n.y + (p.z - q.z) * n.z;
+    float resb = res;   // the residual b is formed with: force2D drops the z row of both clouds and of the normal
+    if constexpr (MIN == kPointToPlane2D) resb = (p.x - q.x) * n.x + (p.y - q.y) * n.y;
     if constexpr (RB) {
       const float wf = robust::weight(rb.fct, rb.plane ? res * res : d, rb_scale, rb.k, rb.approx2);
       if (!(wf > 0.f)) continue;
@@ -426,7 +428,7 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
       for (int c = a; c < 6; ++c) acc[k++] += (double)J[a] * (double)J[c];
     }
 #pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] -= (double)J[a] * (double)res;
+    for (int a = 0; a < 6; ++a) acc[21 + a] -= (double)J[a] * (double)resb;
     acc[27] += 1.0;
     acc[28] += (double)res * (double)res;
   }
@@ -502,12 +504,16 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
     if (!hostmath::point_to_point_delta(ne_out, dT, A, b, xd)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 4; st->done = 1; return; }
   } else {
   hostmath::unpack_normal_eq(ne_out, A, b);
+  if constexpr (MIN == kPointToPlane4Dof || MIN == kPointToPlane2D) {   // force4DOF / force2D: the sub-system and the planar dT
+    if (!hostmath::point_to_plane_step_yaw<MIN == kPointToPlane2D ? 3 : 4>(A, b, x, dT)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 2; st->done = 1; return; }
+  } else {
   if (!hostmath::llt_solve6(A, b, x)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 2; st->done = 1; return; }
+  }
   }
 #ifdef LSGPU_KNN_STATS
   const long long u1 = clock64();
 #endif
-  if constexpr (MIN != kPointToPoint) hostmath::delta_from_x(x, dT);
+  if constexpr (MIN == kPointToPlane) hostmath::delta_from_x(x, dT);
   hostmath::mul4(dT, st->T_iter, Tn);
   for (int i = 0; i < 16; ++i) st->T_iter[i] = Tn[i];
   for (int i = 0; i < 12; ++i) st->T_rows_prev[i] = st->T_rows[i];
@@ -894,6 +900,8 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
     J[2] = p.x * n.y - p.y * n.x;
     J[3] = n.x; J[4] = n.y; J[5] = n.z;
     const float res = (p.x - q.x) * n.x + (p.y - q.y) * n.y + (p.z - q.z) * n.z;
+    float resb = res;   // the residual b is formed with: force2D drops the z row of both clouds and of the normal
+    if constexpr (MIN == kPointToPlane2D) resb = (p.x - q.x) * n.x + (p.y - q.y) * n.y;
     if (amb[u]) {   // its contribution waits for the exact limit (the last block adds it, or not)
       const uint32_t slot = __hip_atomic_fetch_add(amb_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (slot < (uint32_t)kSelAmbCap) {
@@ -901,7 +909,7 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
         int kk = 0;
         for (int a = 0; a < 6; ++a)
           for (int c = a; c < 6; ++c) __hip_atomic_store(&v[kk++], (double)J[a] * (double)J[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int a = 0; a < 6; ++a) __hip_atomic_store(&v[21 + a], -((double)J[a] * (double)res), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int a = 0; a < 6; ++a) __hip_atomic_store(&v[21 + a], -((double)J[a] * (double)resb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&v[27], 1.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(&v[28], (double)res * (double)res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(reinterpret_cast<unsigned long long*>(&amb_key[slot]),
@@ -935,7 +943,7 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
       for (int c = a; c < 6; ++c) acc[k++] += (double)J[a] * (double)J[c];
     }
 #pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] -= (double)J[a] * (double)res;
+    for (int a = 0; a < 6; ++a) acc[21 + a] -= (double)J[a] * (double)resb;
     acc[27] += 1.0;
     acc[28] += (double)res * (double)res;
     }

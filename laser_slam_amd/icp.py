@@ -81,7 +81,7 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None, normals=None, covariance=None, cuts=None, max_density=None, shadow=None):
+                 robust=None, normals=None, covariance=None, cuts=None, max_density=None, shadow=None, motion=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
@@ -96,7 +96,9 @@ class IcpHandle:
         SurfaceNormalDataPointsFilter (compute's sn_knn) -- lsgpu_icp_set_max_density.  shadow: None, or
         ShadowDataPointsFilter's eps as (reading_eps, reference_eps), None or a negative value for a side without the module
         (a dict with those keys or an _lib.ShadowCfg too) -- lsgpu_icp_set_shadow (the reading's needs `normals` with
-        reading_sn_knn)."""
+        reading_sn_knn).  motion: None, or PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (a
+        MotionConfig, a dict of its fields, or an _lib.MotionCfg) -- lsgpu_icp_set_motion (given last: it refuses a handle with
+        modules the constrained steps do not cover)."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -148,6 +150,18 @@ class IcpHandle:
         self.shadow = None
         if shadow is not None:
             self.set_shadow(shadow)
+        self.motion = None
+        if motion is not None:
+            self.set_motion(motion)
+
+    def set_motion(self, motion):
+        """lsgpu_icp_set_motion: PointToPlaneErrorMinimizer's force2D / force4DOF step and BoundTransformationChecker of this
+        handle's alignments.  motion: a MotionConfig, a dict of its fields or an _lib.MotionCfg; None: off."""
+        mc = motion_cfg(motion) if motion is not None else None
+        rc = _lib.lib().lsgpu_icp_set_motion(self._h, C.byref(mc) if mc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_motion", self._h)
+        self.motion = _motion_config(mc) if mc is not None and (mc.dof or mc.bound) else None
 
     def set_shadow(self, shadow):
         """lsgpu_icp_set_shadow: ShadowDataPointsFilter behind the normals of the reading's / the reference's section of this
@@ -918,6 +932,28 @@ def point_to_plane_solve(sums) -> np.ndarray:
     return out.reshape(4, 4).T.copy()
 
 
+def point_to_plane_solve_dof(sums, dof: int) -> np.ndarray:
+    """lsgpu_point_to_plane_solve_dof: the step dT (4x4 float32) of a handle's mode from the first 27 sums of lsgpu_normal_eq --
+    dof _lib.MOTION_DOF_6 (the free step), _lib.MOTION_DOF_4 (force4DOF) or _lib.MOTION_DOF_3 (force2D; b formed with the planar
+    residual).  Host only, the function the device loop runs.  Raises ConvergenceError if the system is not positive definite."""
+    s = np.ascontiguousarray(sums, np.float64).ravel()
+    if s.size < 27:
+        raise ValueError("expected at least 27 sums")
+    out = np.empty(16, np.float32)
+    rc = _lib.lib().lsgpu_point_to_plane_solve_dof(s.ctypes.data_as(C.POINTER(C.c_double)), int(dof), _fp(out))
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_point_to_plane_solve_dof")
+    return out.reshape(4, 4).T.copy()
+
+
+def bound_first_violation(T_iters, max_rot: float, max_trans: float) -> int:
+    """lsgpu_bound_first_violation: BoundTransformationChecker over a sequence of 4x4 transforms (entry 0: the one the checker
+    was initialised with) -> the first index >= 1 out of bounds, -1 if there is none.  Host only."""
+    Ts = [np.asarray(T, np.float32).reshape(4, 4).T.ravel() for T in T_iters]          # column major
+    a = np.ascontiguousarray(np.concatenate(Ts) if Ts else np.zeros(0), np.float32)
+    return int(_lib.lib().lsgpu_bound_first_violation(a.ctypes.data if len(Ts) else None, len(Ts), float(max_rot), float(max_trans)))
+
+
 def point_to_plane_cov_solve(sums, sensor_std_dev: float = 0.01) -> np.ndarray:
     """lsgpu_point_to_plane_cov_solve: cov = sensorStdDev^2 H^-1 M H^-1 (6x6 float64) from the 44 sums of
     IcpHandle.point_to_plane_cov -- host only, the function the library calls after the loop.  Raises ConvergenceError for
@@ -1143,6 +1179,19 @@ class ChainConfig:
             self.extra["shadow"] = (None if value[0] is None else float(value[0]), None if value[1] is None else float(value[1]))
 
     @property
+    def motion(self) -> Optional["MotionConfig"]:
+        """PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (a MotionConfig); None: neither.
+        Kept in `extra`, like `robust`."""
+        return self.extra.get("motion")
+
+    @motion.setter
+    def motion(self, value):
+        if value is None:
+            self.extra.pop("motion", None)
+        else:
+            self.extra["motion"] = value
+
+    @property
     def robust(self) -> Optional["RobustConfig"]:
         """RobustOutlierFilter's parameters (a RobustConfig); None: no such module.  Kept in `extra`, so that the fields of
         a chain without the module are what they were."""
@@ -1154,6 +1203,37 @@ class ChainConfig:
             self.extra.pop("robust", None)
         else:
             self.extra["robust"] = value
+
+
+@dataclass(frozen=True)
+class MotionConfig:
+    """lsgpu_motion_config: `dof` _lib.MOTION_DOF_6 (the free step), _lib.MOTION_DOF_3 (PointToPlaneErrorMinimizer force2D) or
+    _lib.MOTION_DOF_4 (force4DOF); `bound`: BoundTransformationChecker with its two limits (rad, m), `bound_before_counter`:
+    the document lists it in front of CounterTransformationChecker (the counter's last iteration is checked too)."""
+    dof: int = 0
+    bound: bool = False
+    max_rotation_norm: float = 1.0
+    max_translation_norm: float = 1.0
+    bound_before_counter: bool = False
+
+
+def motion_cfg(m) -> "_lib.MotionCfg":
+    """MotionConfig / dict of its fields / _lib.MotionCfg -> _lib.MotionCfg (the values are checked by the library)."""
+    if isinstance(m, _lib.MotionCfg):
+        return m
+    if isinstance(m, dict):
+        m = MotionConfig(**m)
+    c = _lib.MotionCfg()
+    _lib.lib().lsgpu_motion_config_default(C.byref(c))
+    c.dof, c.bound, c.bound_before_counter = int(m.dof), int(m.bound), int(m.bound_before_counter)
+    c.max_rotation_norm, c.max_translation_norm = float(m.max_rotation_norm), float(m.max_translation_norm)
+    return c
+
+
+def _motion_config(mc) -> "MotionConfig":
+    """_lib.MotionCfg -> MotionConfig"""
+    return MotionConfig(int(mc.dof), bool(mc.bound), _f32(mc.max_rotation_norm), _f32(mc.max_translation_norm),
+                        bool(mc.bound_before_counter))
 
 
 @dataclass(frozen=True)
@@ -1237,12 +1317,22 @@ def chain_load_shadow(doc):
     return rc, why.value.decode(), out
 
 
+def chain_load_motion(doc):
+    """lsgpu_chain_load_motion on the same document: force2D / force4DOF of PointToPlaneErrorMinimizer and
+    BoundTransformationChecker -> (return code, reason of a refusal, _lib.MotionCfg).  Same rules, verdict and text as chain_load."""
+    arr, n, _keep = _yaml_modules(doc)
+    out = _lib.MotionCfg()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load_motion(arr, n, C.byref(out), why, len(why))
+    return rc, why.value.decode(), out
+
+
 def _f32(x) -> float:
     """The shortest decimal that is this float32 (0.75, not 0.75000000000000011...): what the document said."""
     return float(str(np.float32(x)))
 
 
-def _chain_config(lc, cuts=None, shadow=None) -> "ChainConfig":
+def _chain_config(lc, cuts=None, shadow=None, motion=None) -> "ChainConfig":
     """_lib.LoadedChain (and the _lib.ChainCuts of the same document, if it has cut modules) -> ChainConfig"""
     i, c = lc.icp, lc.chain
     name = {v: k for k, v in _MINIMIZERS.items()}[i.error_minimizer]
@@ -1271,6 +1361,8 @@ def _chain_config(lc, cuts=None, shadow=None) -> "ChainConfig":
         ch.cuts = _chain_cuts(cuts)
     if shadow is not None and (shadow.reading_eps >= 0 or shadow.reference_eps >= 0):
         ch.shadow = tuple(_f32(e) if e >= 0 else None for e in (shadow.reading_eps, shadow.reference_eps))
+    if motion is not None and (motion.dof or motion.bound):
+        ch.motion = _motion_config(motion)
     return ch
 
 
@@ -1319,7 +1411,10 @@ class ICP:
         rc, why, shadow = chain_load_shadow(doc)                # (lsgpu_loaded_chain has no slot for the module: its own entry)
         if rc != _lib.OK:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        self.chain = _chain_config(loaded, cuts, shadow)
+        rc, why, motion = chain_load_motion(doc)                # (likewise: force2D / force4DOF, BoundTransformationChecker)
+        if rc != _lib.OK:
+            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+        self.chain = _chain_config(loaded, cuts, shadow, motion)
         self._handle = None
 
     def _ensure_handle(self) -> IcpHandle:
@@ -1336,7 +1431,8 @@ class ICP:
                                      self.chain.outlier_min_dist, self.chain.outlier_median_factor,
                                      robust=self.chain.robust, normals=self.chain.normals,
                                      covariance=self.chain.covariance, cuts=self.chain.cuts,
-                                     max_density=self.chain.max_density, shadow=self.chain.shadow)
+                                     max_density=self.chain.max_density, shadow=self.chain.shadow,
+                                     motion=self.chain.motion)
         return self._handle
 
     @property
