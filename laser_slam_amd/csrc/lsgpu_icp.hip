@@ -5,6 +5,7 @@
 //   set_reference : steps 2-3 (centre on mean, matcher init)
 //   align         : steps 5-7 (move reading by T_refMean_dataIn, iterate, compose)
 // Kernels: lsgpu_grid.hip.h, lsgpu_knn.hip.h, lsgpu_solve.hip.h.  No CPU fallback exists: every failure is returned to the caller.
+#include <atomic>
 #include <cstring>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include <chrono>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <utility>
 
 #include <dlfcn.h>
@@ -97,21 +99,80 @@ RcclApi* rccl_api() {
   return api.lib ? &api : nullptr;
 }
 
+// The four owners of what a handle takes from the runtime: device memory, pinned host memory, events, streams.  Each
+// frees what it holds when it goes, none can be copied, and g_live counts what they hold between them
+// (lsgpu_dev_live_resources: a create / destroy cycle must give back everything it took).
+std::atomic<long> g_live{0};
+inline hipError_t counted(hipError_t made) { if (made == hipSuccess) ++g_live; return made; }
+
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t n) {
     if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
+    release();
     const size_t want = n + n / 8 + 256;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
+    hipError_t e = counted(hipMalloc((void**)&p, want * sizeof(T)));
+    if (e == hipSuccess) cap = want; else p = nullptr;
     return e;
   }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  void release() { if (p) { (void)hipFree(p); --g_live; } p = nullptr; cap = 0; }
 };
+
+// pinned (host-coherent, device-mapped) host memory: reserve() grows by freeing and allocating anew -- the contents go
+template <class T>
+struct PinBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
+  hipError_t reserve(size_t n) {
+    if (n <= cap) return hipSuccess;
+    release();
+    hipError_t e = counted(hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault));
+    if (e == hipSuccess) cap = n; else p = nullptr;
+    return e;
+  }
+  void release() { if (p) { (void)hipHostFree(p); --g_live; } p = nullptr; cap = 0; }
+  T* operator->() const { return p; }
+};
+
+// created on first use: ensure(hipEventDefault) for an event that times, ensure(hipEventDisableTiming) for one that orders
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : ev(o.ev) { o.ev = nullptr; }   // (the pools are vectors; no copy, no assignment)
+  ~Event() { if (ev) { (void)hipEventDestroy(ev); --g_live; } }
+  hipError_t ensure(unsigned flags) { return ev ? hipSuccess : counted(hipEventCreateWithFlags(&ev, flags)); }
+  operator hipEvent_t() const { return ev; }
+};
+
+// non-blocking, created on first use, waited for before it goes
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); --g_live; } }
+  hipError_t ensure() { return s ? hipSuccess : counted(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  operator hipStream_t() const { return s; }
+};
+
+static_assert(!std::is_copy_constructible<DevBuf<float>>::value && !std::is_copy_constructible<PinBuf<float>>::value &&
+              !std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Stream>::value,
+              "an owner that could be copied would free twice");
 
 bool is_device_ptr(const void* p) {
   hipPointerAttribute_t a;
@@ -171,15 +232,18 @@ struct Staging {
   alignas(64) uint32_t bounds[6];           // cloud_bounds: ordered keys of the minimum and the maximum
   alignas(64) double cov[kCovStride];       // PointToPlaneWithCovErrorMinimizer: the 44 sums of k_cov ...
   alignas(64) lsgpu_iter_trace cov_trace;   // ... and the last iteration's trace record (its normal equations give the step)
+  alignas(64) uint32_t price[kPriceSlots * kPriceStride];   // run_knn: the price check's counters (price_cnt) behind the priced search
+  alignas(64) uint32_t cone_occ;            // build_cone: occupied bins of the direction index, behind the build
+  alignas(64) uint32_t gs_err[8];           // ssn_device: the error record of the sort-free levels (gs_err), with the totals
 };
 
 struct lsgpu_icp {
   lsgpu_icp_config cfg;
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t copy_stream = nullptr;   // lsgpu_icp_compute: the reading's H2D, overlapped with the reference filter
-  hipEvent_t copy_done = nullptr;
-  hipEvent_t ref_up_done = nullptr;    // the reference's H2D on `stream`: the reading's copy queues behind it
+  Stream stream;
+  Stream copy_stream;      // lsgpu_icp_compute: the reading's H2D, overlapped with the reference filter
+  Event copy_done;
+  Event ref_up_done;       // the reference's H2D on `stream`: the reading's copy queues behind it
   std::string err;
 
   // reference (steps 2-3)
@@ -197,16 +261,15 @@ struct lsgpu_icp {
     DevBuf<uint32_t> vals, vals_alt;
     DevBuf<char> sort_tmp;
     DevBuf<uint32_t> sort_hist;  // radix sort: 256 x blocks digit histograms + 256 digit totals
-    void release() { keys.release(); keys_alt.release(); vals.release(); vals_alt.release(); sort_tmp.release(); sort_hist.release(); }
   };
   SortScratch scr_main, scr_side;
   struct Lane { hipStream_t stream; SortScratch* scratch; int totals_row; } lane{nullptr, &scr_main, 0};
   Lane main_lane() { return Lane{stream, &scr_main, 0}; }
   Lane side_lane() { return Lane{side_stream, &scr_side, 1}; }   // (lsgpu_icp_compute's side work, its align's deferred index build)
-  hipStream_t draw_stream = nullptr;   // H2D of the filters' draws, issued by the helper thread that produces them
-  hipEvent_t draws_done = nullptr, draws_first_done = nullptr;
-  hipStream_t side_stream = nullptr;   // lsgpu_icp_compute: reading filter + query order, beside the grid build
-  hipEvent_t side_done = nullptr;
+  Stream draw_stream;      // H2D of the filters' draws, issued by the helper thread that produces them
+  Event draws_done, draws_first_done;
+  Stream side_stream;      // lsgpu_icp_compute: reading filter + query order, beside the grid build
+  Event side_done;
   DevBuf<float4> pts, nrm;
   DevBuf<uint32_t> ref_inv;
   DevBuf<HashEntry> tables;
@@ -222,23 +285,21 @@ struct lsgpu_icp {
   ConeDev cone;
   bool cone_ok = false;       // built (or being built on the side stream: cone_pending) for the current reference
   bool cone_pending = false;  // the loop's stream has not yet waited for cone_done
-  hipEvent_t cone_done = nullptr;
+  Event cone_done;
   DevBuf<uint32_t> cone_occ;          // occupied (row, column) bins of the index
-  hipEvent_t cone_occ_ready = nullptr;
+  Event cone_occ_ready;               // ... are on the host (pin->cone_occ)
   bool cone_decided = false;          // ... looked at (per reference): cone_dense says whether the reference is too dense in direction
   bool cone_dense = false;
   float cone_occupancy = 0.f;         // points per occupied bin
   float cone_zeta_lo = 0.f, cone_zeta_hi = 0.f;
   bool cone_origin_inside = false;
-  uint32_t* h_cone_occ = nullptr;     // pinned word the build's occupancy count travels to
-  hipEvent_t price_ready = nullptr;   // the price check's two counters are on the host
+  Event price_ready;                  // the price check's two counters are on the host (pin->price)
   DevBuf<uint32_t> price_cnt;         // kPriceSlots x kPriceStride words (lsgpu_knn.hip.h: ConePrice::count)
-  uint32_t* h_price = nullptr;        // ... and their pinned copy
   // launch policy of the running align (lsgpu_policy.h): every decision about what is enqueued next lives there
   policy::Config pol_cfg;
   policy::State pol;
   // is the index paying on this handle's clouds?  (policy::index_not_paying; two event pairs per alignment)
-  hipEvent_t ev_pay[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev_pay[4];
   bool pay_voxel_timed = false, pay_index_timed = false;
   int index_rest = 0;         // alignments that still leave the index alone
   int64_t index_rest_nr = 0;  // ... decided on a reference of this size (another size: the judgement starts over)
@@ -285,7 +346,6 @@ struct lsgpu_icp {
   DevBuf<GsMedian> gs_cand, gs_median;
   DevBuf<uint32_t> gs_cand_blk, gs_cand_n, gs_cl, gs_err;
   DevBuf<uint2> gs_rng;                       // per segment: the key range of its points on its cut axis (two levels)
-  uint32_t* h_gs_err = nullptr;               // pinned
   int64_t gs_plan_n = -1;                     // the cloud size / level count the tables on the device were made for
   int gs_plan_levels = -1;
   std::vector<uint32_t> gs_lvl_first, gs_lvl_blocks;
@@ -313,15 +373,13 @@ struct lsgpu_icp {
   // PointToPlaneErrorMinimizer force4DOF / force2D and BoundTransformationChecker (lsgpu_icp_set_motion)
   bool mo_on = false;
   lsgpu_motion_config mo_cfg{};
-  float* h_chk = nullptr;            // the bound's copy of the checker history (pinned; travels with the loop state's read-back)
-  size_t h_chk_cap = 0;              // ... floats
+  PinBuf<float> h_chk;               // the bound's copy of the checker history (travels with the loop state's read-back)
   int dof() const { return mo_on ? mo_cfg.dof : LSGPU_MOTION_DOF_6; }
   bool bound() const { return mo_on && mo_cfg.bound != 0; }
-  float* draws_pinned = nullptr;  // host staging of the filter draws (pinned: async H2D)
+  PinBuf<float> draws_pinned;     // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
   DevBuf<float4> submap;               // assembled reference of lsgpu_icp_compute_clouds
-  size_t draws_pinned_cap = 0;
 
   // reading
   int64_t nq = 0;
@@ -363,18 +421,18 @@ struct lsgpu_icp {
   DevBuf<uint32_t> ne_tickets;  // 1 + kNeBlocksMax / kNeGroup
   DevBuf<double> ne_out;      // 32 (29 + limit slot)
   DevBuf<float> limit_dev;
-  Staging* pin = nullptr;     // pinned host staging, one member per use
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t ev_state = nullptr;   // lsgpu_icp_align: completion of a loop-state copy (the stream goes on behind it)
+  PinBuf<Staging> pin;        // pinned host staging, one member per use
+  Event ev0, ev1;
+  Event ev_state;   // lsgpu_icp_align: completion of a loop-state copy (the stream goes on behind it)
   // lsgpu_icp_align may return with ONE more iteration queued on `stream` behind its last look at the loop state (it
   // exits at once: the state says `done`).  Work the next call starts on the handle's OTHER streams is ordered behind
   // it through this event, so that nothing ever depends on what that launch does not touch.
-  hipEvent_t ev_tail = nullptr;
+  Event ev_tail;
   bool tail_pending = false;
-  struct KnnEv { hipEvent_t a, b, c, d, e; bool second; };  // before kNN, after the main pass, after the wave-per-query pass (recorded only if one was launched: `second`), after the select, after the normal equations
+  struct KnnEv { Event a, b, c, d, e; bool second = false; };  // before kNN, after the main pass, after the wave-per-query pass (recorded only if one was launched: `second`), after the select, after the normal equations
   std::vector<KnnEv> knn_events;   // pool, reused across aligns
   // split-scan mode with profile_kernels: an event pair around every RCCL call of the loop (stats.t_comm_ms)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> comm_events;
+  std::vector<std::pair<Event, Event>> comm_events;
   size_t comm_events_used = 0;
   bool time_comm = false;
   size_t knn_events_used = 0;
@@ -417,9 +475,9 @@ static void comm_mark(lsgpu_icp* h, bool begin) {
   if (!h->time_comm) return;
   if (begin) {
     if (h->comm_events_used == h->comm_events.size()) {
-      hipEvent_t a = nullptr, b = nullptr;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { (void)hipGetLastError(); h->time_comm = false; return; }
-      h->comm_events.emplace_back(a, b);
+      std::pair<Event, Event> p;
+      if (p.first.ensure(hipEventDefault) != hipSuccess || p.second.ensure(hipEventDefault) != hipSuccess) { (void)hipGetLastError(); h->time_comm = false; return; }
+      h->comm_events.push_back(std::move(p));
     }
     (void)hipEventRecord(h->comm_events[h->comm_events_used].first, h->stream);
   } else {
@@ -688,11 +746,10 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
   h->device = device;
   std::memset(&h->grid, 0, sizeof(h->grid));
   if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&h->pin, sizeof(Staging), hipHostMallocDefault) != hipSuccess ||
-      hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
+      h->stream.ensure() != hipSuccess || h->pin.reserve(1) != hipSuccess ||
+      h->ev0.ensure(hipEventDefault) != hipSuccess || h->ev1.ensure(hipEventDefault) != hipSuccess) {
     (void)hipGetLastError();
-    delete h;
+    delete h;   // (gives back what was made)
     return LSGPU_HIP_ERROR;
   }
   h->lane = h->main_lane();
@@ -703,49 +760,10 @@ int lsgpu_icp_create(const lsgpu_icp_config* cfg, int device, lsgpu_icp** out) {
 void lsgpu_icp_destroy(lsgpu_icp* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  // (waited for here, not only where the members go: nothing depends on the order they are declared in)
+  for (const Stream* s : {&h->stream, &h->copy_stream, &h->draw_stream, &h->side_stream})
+    if (*s) (void)hipStreamSynchronize(*s);
   if (h->comm && rccl_api()) (void)rccl_api()->CommDestroy(h->comm);
-  h->comm_tmp.release();
-  for (auto& c : h->clouds) c.release();
-  h->submap.release();
-  h->ref_in.release(); h->nrm_in.release(); h->scr_main.release(); h->scr_side.release();
-  h->pts.release();
-  h->cone_soa.release(); h->cone_occ.release(); h->cone_tab.release(); h->cone_map.release(); h->cone_rowz.release();
-  h->nrm.release(); h->ref_inv.release(); h->tables.release(); h->flags.release(); h->cidx.release(); h->bounds.release(); h->chunks.release(); h->chunk_groups.release(); h->soa.release(); h->soa_base.release(); h->soa_cnt4.release(); h->soa_first.release(); h->prev.release(); h->state.release(); h->lb.release(); h->cell_cache.release(); h->cell_tags.release(); h->ssn_seg_a.release(); h->ssn_seg_b.release(); h->ssn_axis_a.release(); h->ssn_axis_b.release(); h->ssn_seg_fb.release(); h->ssn_blocktab.release(); h->ssn_seg_of.release(); h->ssn_box_pts.release(); h->ssn_box_base.release(); h->ssn_keep.release(); h->ssn_out_pos.release(); h->ssn_bb.release(); h->ssn_bounds_ws.release(); h->ssn_box_normal.release(); h->ssn_draws.release(); h->flt_in.release(); h->flt_in2.release(); h->flt_ref.release(); h->flt_rd.release(); h->vgf_out.release(); h->flt_nrm.release(); h->cut_blk.release(); h->cut_ref.release(); h->dens.release(); h->dens_io.release(); h->md_stat.release(); h->md_blk.release(); h->sh_blk.release(); h->sh_ref.release(); h->sh_rd.release(); h->sh_nrm.release(); h->sh_rd_nrm.release(); h->sh_nrm_in.release(); h->chk_hist.release(); h->trace_dev.release(); h->knn_dbg.release(); h->knn_dbg_wave.release(); h->stat_partials.release(); h->geom.release();
-  h->counters.release(); h->price_cnt.release(); h->ang_cells.release(); h->sel_aux.release(); h->sel_win.release(); h->amb_key.release(); h->amb_val.release(); h->spread_flag.release(); h->spread_list.release(); h->spread_cnt.release(); h->q_in.release(); h->rdq.release(); h->ids.release(); h->d2.release();
-  h->ids_io.release(); h->d2_io.release(); h->strag.release(); h->snf_strag.release(); h->snf_count.release(); h->hist.release(); h->kmatch.release(); h->kd2.release();
-  h->rb_hist.release(); h->rb_sel.release(); h->rb_state.release(); h->rb_trace_dev.release();
-  h->rd_nrm.release(); h->rd_nrm0.release(); h->nrm_io.release(); h->na_trace_dev.release();
-  h->cov_pts.release(); h->cov_partials.release(); h->cov_out.release();
-  h->sel.release(); h->ne_partials.release(); h->ne_gpartials.release(); h->ne_tickets.release(); h->ne_out.release(); h->limit_dev.release();
-  for (auto& e : h->comm_events) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (auto& e : h->knn_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); (void)hipEventDestroy(e.c); (void)hipEventDestroy(e.d); (void)hipEventDestroy(e.e); }
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->ev_state) (void)hipEventDestroy(h->ev_state);
-  if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-  if (h->cone_done) (void)hipEventDestroy(h->cone_done);
-  if (h->cone_occ_ready) (void)hipEventDestroy(h->cone_occ_ready);
-  for (auto& e : h->ev_pay) if (e) (void)hipEventDestroy(e);
-  if (h->pin) (void)hipHostFree(h->pin);
-  if (h->h_price) (void)hipHostFree(h->h_price);
-  if (h->h_cone_occ) (void)hipHostFree(h->h_cone_occ);
-  if (h->h_gs_err) (void)hipHostFree(h->h_gs_err);
-  for (auto& bf : h->gs_e) bf.release();
-  for (auto& bf : h->gs_k) bf.release();
-  h->gs_tab.release(); h->gs_sblk.release(); h->gs_hist.release(); h->gs_cand.release(); h->gs_median.release();
-  h->gs_cand_blk.release(); h->gs_cand_n.release(); h->gs_cl.release(); h->gs_err.release(); h->gs_rng.release();
-  if (h->draws_pinned) (void)hipHostFree(h->draws_pinned);
-  if (h->h_chk) (void)hipHostFree(h->h_chk);
-  if (h->copy_done) (void)hipEventDestroy(h->copy_done);
-  if (h->ref_up_done) (void)hipEventDestroy(h->ref_up_done);
-  if (h->draws_done) (void)hipEventDestroy(h->draws_done);
-  if (h->draws_first_done) (void)hipEventDestroy(h->draws_first_done);
-  if (h->draw_stream) { (void)hipStreamSynchronize(h->draw_stream); (void)hipStreamDestroy(h->draw_stream); }
-  if (h->side_done) (void)hipEventDestroy(h->side_done);
-  if (h->side_stream) { (void)hipStreamSynchronize(h->side_stream); (void)hipStreamDestroy(h->side_stream); }
-  if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
 
@@ -879,17 +897,16 @@ static bool chain_on(const lsgpu_icp* h) {
 
 static float price_share(const lsgpu_icp* h) {   // heavy lanes / searching lanes of the priced launch (its counters are on the host)
   uint64_t heavy = 0, searching = 0;
-  for (int i = 0; i < kPriceSlots; ++i) { heavy += h->h_price[i * kPriceStride]; searching += h->h_price[i * kPriceStride + 1]; }
+  for (int i = 0; i < kPriceSlots; ++i) { heavy += h->pin->price[i * kPriceStride]; searching += h->pin->price[i * kPriceStride + 1]; }
   return searching ? (float)((double)heavy / (double)searching) : 0.f;
 }
 
 // the next event record of a profiled align (a pool, reused across aligns), its first event on the stream
 static int knn_event_begin(lsgpu_icp* h, lsgpu_icp::KnnEv** ev) {
   if (h->knn_events_used == h->knn_events.size()) {
-    lsgpu_icp::KnnEv n{};
-    HIPC(hipEventCreate(&n.a)); HIPC(hipEventCreate(&n.b)); HIPC(hipEventCreate(&n.c));
-    HIPC(hipEventCreate(&n.d)); HIPC(hipEventCreate(&n.e));
-    h->knn_events.push_back(n);
+    lsgpu_icp::KnnEv n;   // (a failure part-way: `n` takes what it has with it)
+    for (Event* e : {&n.a, &n.b, &n.c, &n.d, &n.e}) HIPC(e->ensure(hipEventDefault));
+    h->knn_events.push_back(std::move(n));
   }
   *ev = &h->knn_events[h->knn_events_used++];
   (*ev)->second = false;
@@ -965,7 +982,6 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
   if (pricing) {
     constexpr size_t kPriceBytes = (size_t)kPriceSlots * kPriceStride * sizeof(uint32_t);
     HIPC(h->price_cnt.reserve((size_t)kPriceSlots * kPriceStride));
-    if (!h->h_price) HIPC(hipHostMalloc((void**)&h->h_price, kPriceBytes, hipHostMallocDefault));
     HIPC(hipMemsetAsync(h->price_cnt.p, 0, kPriceBytes, h->stream));
     a.price.ox = h->cone.ox; a.price.oy = h->cone.oy; a.price.oz = h->cone.oz; a.price.rs = h->cone.rs; a.price.cs = h->cone.cs;
     a.price.dens4 = (float)(0.25 * (double)h->nr / ((double)h->cone.rows * (double)h->cone.cols));
@@ -991,7 +1007,7 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
     // per settled launch: K = 1: 48 us against 82 with the voxel grid, K = 3: 69 / 107, K = 8: 423 / 186.  Points per
     // occupied bin: 2, 3, 8.  (The wait is for a copy queued behind the build; the device is in the first iterations.)
     HIPC(hipEventSynchronize(h->cone_occ_ready));
-    const uint32_t occ = *h->h_cone_occ;
+    const uint32_t occ = h->pin->cone_occ;
     pol.set_occupancy(pc, occ ? (float)((double)h->nr / (double)occ) : 1e9f);
     h->cone_occupancy = pol.cone_occupancy; h->cone_dense = pol.cone_dense; h->cone_decided = true;   // (per reference: a reused reference keeps the verdict)
   }
@@ -1037,8 +1053,8 @@ static int run_knn(lsgpu_icp* h, const Mat34& T, const IcpState* st, const polic
   if (timed && second) { ev->second = true; HIPC(hipEventRecord(ev->c, h->stream)); }   // (an event pair around nothing still reads ~5 us)
   if (pay_voxel) { HIPC(hipEventRecord(h->ev_pay[1], h->stream)); h->pay_voxel_timed = true; }
   if (pricing) {
-    if (!h->price_ready) HIPC(hipEventCreateWithFlags(&h->price_ready, hipEventDisableTiming));
-    HIPC(hipMemcpyAsync(h->h_price, h->price_cnt.p, (size_t)kPriceSlots * kPriceStride * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h->price_ready.ensure(hipEventDisableTiming));
+    HIPC(hipMemcpyAsync(h->pin->price, h->price_cnt.p, (size_t)kPriceSlots * kPriceStride * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipEventRecord(h->price_ready, h->stream));
     pol.priced();
   }
@@ -1190,12 +1206,11 @@ static int build_cone_index(lsgpu_icp* h) {
   HIPC(hipGetLastError());
   // the number of occupied bins travels to the host behind the build; lsgpu_icp_align looks at it before its first
   // search through the index (the device is busy with the first two iterations by then)
-  if (!h->cone_occ_ready) HIPC(hipEventCreateWithFlags(&h->cone_occ_ready, hipEventDisableTiming));
-  // (its own pinned word, not a member of the staging block: an earlier build's copy may still be in flight on the side
-  // stream when the next one starts -- wait for it before the word is reset)
-  if (!h->h_cone_occ) HIPC(hipHostMalloc((void**)&h->h_cone_occ, 64, hipHostMallocDefault));
+  // (an earlier build's copy may still be in flight on the side stream when the next one starts -- wait for it before the
+  // word is reset)
+  if (!h->cone_occ_ready) HIPC(h->cone_occ_ready.ensure(hipEventDisableTiming));
   else if (hipEventSynchronize(h->cone_occ_ready) != hipSuccess) (void)hipGetLastError();
-  uint32_t* ho = h->h_cone_occ;
+  uint32_t* ho = &h->pin->cone_occ;
   *ho = 0u;
   HIPC(hipMemcpyAsync(ho, h->cone_occ.p, sizeof(uint32_t), hipMemcpyDeviceToHost, h->lane.stream));
   HIPC(hipEventRecord(h->cone_occ_ready, h->lane.stream));
@@ -1713,16 +1728,11 @@ static int scan_u32(lsgpu_icp* h, const uint32_t* in, uint32_t* out, size_t n, b
 // Up to `kmax` draws of the library stream -> h->ssn_draws, speculatively: the stream stays locked until
 // the caller commits the number the sequential filter would have consumed (DrawStream::commit).
 static int upload_draws_begin(lsgpu_icp* h, int64_t seed, size_t kmax) {
-  if (kmax + 1 > h->draws_pinned_cap) {
-    if (h->draws_pinned) (void)hipHostFree(h->draws_pinned);
-    h->draws_pinned = nullptr; h->draws_pinned_cap = 0;
-    HIPC(hipHostMalloc((void**)&h->draws_pinned, (kmax + 1) * sizeof(float), hipHostMallocDefault));
-    h->draws_pinned_cap = kmax + 1;
-  }
+  HIPC(h->draws_pinned.reserve(kmax + 1));
   HIPC(h->ssn_draws.reserve(kmax + 1));
-  DrawStream::global().begin(seed, kmax, h->draws_pinned);
+  DrawStream::global().begin(seed, kmax, h->draws_pinned.p);
   if (kmax) {
-    const hipError_t e = hipMemcpyAsync(h->ssn_draws.p, h->draws_pinned, kmax * sizeof(float), hipMemcpyHostToDevice, h->stream);
+    const hipError_t e = hipMemcpyAsync(h->ssn_draws.p, h->draws_pinned.p, kmax * sizeof(float), hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) { DrawStream::global().commit(0); HIPC(e); }
   }
   return LSGPU_OK;
@@ -1749,16 +1759,11 @@ struct DrawAhead {
   int begin(lsgpu_icp* hh, int64_t seed, size_t k, size_t k_first = 0) {
     h = hh; kmax = k; kfirst = (k_first && k_first < k) ? k_first : 0;
     first_sent.store(0, std::memory_order_relaxed);
-    if (kmax + 1 > h->draws_pinned_cap) {
-      if (h->draws_pinned) (void)hipHostFree(h->draws_pinned);
-      h->draws_pinned = nullptr; h->draws_pinned_cap = 0;
-      HIPC(hipHostMalloc((void**)&h->draws_pinned, (kmax + 1) * sizeof(float), hipHostMallocDefault));
-      h->draws_pinned_cap = kmax + 1;
-    }
+    HIPC(h->draws_pinned.reserve(kmax + 1));
     HIPC(h->ssn_draws.reserve(kmax + 1));
-    if (!h->draw_stream) HIPC(hipStreamCreateWithFlags(&h->draw_stream, hipStreamNonBlocking));
-    if (!h->draws_done) HIPC(hipEventCreateWithFlags(&h->draws_done, hipEventDisableTiming));
-    if (!h->draws_first_done) HIPC(hipEventCreateWithFlags(&h->draws_first_done, hipEventDisableTiming));
+    HIPC(h->draw_stream.ensure());
+    HIPC(h->draws_done.ensure(hipEventDisableTiming));
+    HIPC(h->draws_first_done.ensure(hipEventDisableTiming));
     order_after_tail(h, h->draw_stream);
     DrawStream::global().lock(seed);
     open = true;
@@ -1771,16 +1776,16 @@ struct DrawAhead {
         const size_t kf = kfirst;
         if (kf) {
           // the first filter's share leaves as soon as it exists; the rest is still being produced
-          DrawStream::global().generate(k, hh2->draws_pinned, kf, [&] {
-            if (e == hipSuccess) e = hipMemcpyAsync(hh2->ssn_draws.p, hh2->draws_pinned, kf * sizeof(float), hipMemcpyHostToDevice, hh2->draw_stream);
+          DrawStream::global().generate(k, hh2->draws_pinned.p, kf, [&] {
+            if (e == hipSuccess) e = hipMemcpyAsync(hh2->ssn_draws.p, hh2->draws_pinned.p, kf * sizeof(float), hipMemcpyHostToDevice, hh2->draw_stream);
             if (e == hipSuccess) e = hipEventRecord(hh2->draws_first_done, hh2->draw_stream);
             upload_err = e;
             first_sent.store(1, std::memory_order_release);
           });
-          if (e == hipSuccess) e = hipMemcpyAsync(hh2->ssn_draws.p + kf, hh2->draws_pinned + kf, (k - kf) * sizeof(float), hipMemcpyHostToDevice, hh2->draw_stream);
+          if (e == hipSuccess) e = hipMemcpyAsync(hh2->ssn_draws.p + kf, hh2->draws_pinned.p + kf, (k - kf) * sizeof(float), hipMemcpyHostToDevice, hh2->draw_stream);
         } else {
-          DrawStream::global().generate(k, hh2->draws_pinned);
-          if (e == hipSuccess) e = hipMemcpyAsync(hh2->ssn_draws.p, hh2->draws_pinned, k * sizeof(float), hipMemcpyHostToDevice, hh2->draw_stream);
+          DrawStream::global().generate(k, hh2->draws_pinned.p);
+          if (e == hipSuccess) e = hipMemcpyAsync(hh2->ssn_draws.p, hh2->draws_pinned.p, k * sizeof(float), hipMemcpyHostToDevice, hh2->draw_stream);
         }
         if (e == hipSuccess) e = hipEventRecord(hh2->draws_done, hh2->draw_stream);
         upload_err = e;
@@ -2042,7 +2047,6 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
     HIPC(h->gs_cand.reserve(cand_room)); HIPC(h->gs_cand_blk.reserve(cand_room));
     HIPC(h->gs_cl.reserve((size_t)2 * cap)); HIPC(h->gs_err.reserve(8)); HIPC(h->gs_rng.reserve(2 * nseg_g + 2));
     HIPC(h->ssn_axis_a.reserve(nseg_g)); HIPC(h->ssn_axis_b.reserve(nseg_g));
-    if (!h->h_gs_err) HIPC(hipHostMalloc((void**)&h->h_gs_err, 64, hipHostMallocDefault));
     uint32_t* cand_n[2] = {h->gs_cand_n.p, h->gs_cand_n.p + nseg_g + 1};
     uint32_t* sig_cur = reinterpret_cast<uint32_t*>(h->ssn_axis_a.p);
     uint32_t* sig_nxt = reinterpret_cast<uint32_t*>(h->ssn_axis_b.p);
@@ -2163,11 +2167,11 @@ static int ssn_device(lsgpu_icp* h, const float4* src, int64_t n, int knn, float
   if (rc == LSGPU_OK)
     // (the sort-free levels' error words travel with the totals)
     rc = scan_totals(h, h->ssn_box_pts.p, h->ssn_box_base.p, nseg, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)n, &n_draws, &kept,
-                     select_levels ? h->gs_err.p : nullptr, h->h_gs_err, 8 * sizeof(uint32_t), /*b_flags*/ true);
+                     select_levels ? h->gs_err.p : nullptr, h->pin->gs_err, sizeof h->pin->gs_err, /*b_flags*/ true);
   if (rc) return rc;
-  if (select_levels && *h->h_gs_err) {
+  if (select_levels && h->pin->gs_err[0]) {
     if (getenv("LSGPU_GS_DEBUG")) fprintf(stderr, "lsgpu: sort-free levels gave up (n %lld): code %u seg %u a %u b %u | part %u seg %u dst %u\n", (long long)n,
-                                          h->h_gs_err[1], h->h_gs_err[2], h->h_gs_err[3], h->h_gs_err[4], h->h_gs_err[5], h->h_gs_err[6], h->h_gs_err[7]);
+                                          h->pin->gs_err[1], h->pin->gs_err[2], h->pin->gs_err[3], h->pin->gs_err[4], h->pin->gs_err[5], h->pin->gs_err[6], h->pin->gs_err[7]);
     // thousands of equal coordinates around a median (more candidates than a workgroup selects among): the segmented
     // sorts do not care -- the same filter again with them (same draws: nothing has been consumed yet).  Counted:
     // lsgpu_icp_get_policy_info shows a handle that pays the filter twice on every call.
@@ -2744,8 +2748,8 @@ struct ComputeRun {
     // A reading handed over in HOST memory crosses PCIe while the reference is being filtered: its own stream, and its own
     // host thread, because a copy from pageable memory keeps the calling thread until the last chunk is staged
     // (SURVEY.md §8d counts H2D in scans/s).  The loop's stream waits for it right before the reading filter.
-    if (!h->copy_stream) HIPC(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    if (!h->copy_done) HIPC(hipEventCreateWithFlags(&h->copy_done, hipEventDisableTiming));
+    HIPC(h->copy_stream.ensure());
+    HIPC(h->copy_done.ensure(hipEventDisableTiming));
     float4* up_dst = upload_into;
     if (!up_dst) { HIPC(h->flt_in2.reserve(nq)); up_dst = h->flt_in2.p; }
     overlap_upload = true; rd_src = up_dst;
@@ -2753,7 +2757,7 @@ struct ComputeRun {
     // the reference's own upload goes first: it is in front of everything, the reading is not needed before the reading
     // filter, and two copies at once share the link (from pinned buffers they did: the pinned path was the slower one)
     if (src != reinterpret_cast<const float4*>(reference_xyz1)) {
-      if (!h->ref_up_done) HIPC(hipEventCreateWithFlags(&h->ref_up_done, hipEventDisableTiming));
+      HIPC(h->ref_up_done.ensure(hipEventDisableTiming));
       HIPC(hipEventRecord(h->ref_up_done, h->stream));
       HIPC(hipStreamWaitEvent(h->copy_stream, h->ref_up_done, 0));
     }
@@ -2892,8 +2896,8 @@ struct ComputeRun {
     // (Tried: this stream at the lowest stream priority, so that the loop's short kernels never wait for a compute unit behind
     // the direction index's build.  Measured slower, 5.27 -> 5.41..5.60 ms per compute from host buffers, level from resident
     // ones: the reading's filter and query order run here too and ARE on the critical path.)
-    if (!h->side_stream) HIPC(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-    if (!h->side_done) HIPC(hipEventCreateWithFlags(&h->side_done, hipEventDisableTiming));
+    HIPC(h->side_stream.ensure());
+    HIPC(h->side_done.ensure(hipEventDisableTiming));
     order_after_tail(h, h->side_stream); side_used = true;
     LaneScope on_side(h, h->side_lane());
     return reading_filter(/*defer_wait*/ true);
@@ -2973,7 +2977,7 @@ struct ComputeRun {
       // build on the side stream (behind the queries' order, with that stream's sort scratch) once the loop's first
       // iteration is out -- beside the first two iterations instead of in front of the loop (0.16 ms per 1 M-point
       // compute), and without holding the host back from starting the loop (round 5)
-      if (!h->cone_done) HIPC(hipEventCreateWithFlags(&h->cone_done, hipEventDisableTiming));
+      HIPC(h->cone_done.ensure(hipEventDisableTiming));
       extras.build_index_on_side = true;
     }
     return LSGPU_OK;
@@ -3590,14 +3594,7 @@ struct AlignRun {
     ne_loop_k = ne_loop_fn(p2p, kk, chain, robust);
     if (h->dof() == LSGPU_MOTION_DOF_4) constrained_kernels<kPointToPlane4Dof>(chain, &ne_loop, &ne_loop_k, &update);
     if (h->dof() == LSGPU_MOTION_DOF_3) constrained_kernels<kPointToPlane2D>(chain, &ne_loop, &ne_loop_k, &update);
-    if (h->bound()) {   // the bound's host copy of the checker history
-      const size_t need = (size_t)8 * (max_it + 2);
-      if (need > h->h_chk_cap) {
-        if (h->h_chk) { (void)hipHostFree(h->h_chk); h->h_chk = nullptr; h->h_chk_cap = 0; }
-        HIPC(hipHostMalloc((void**)&h->h_chk, need * sizeof(float), hipHostMallocDefault));
-        h->h_chk_cap = need;
-      }
-    }
+    if (h->bound()) HIPC(h->h_chk.reserve((size_t)8 * (max_it + 2)));   // the bound's host copy of the checker history
     ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
     return LSGPU_OK;
   }
@@ -3626,8 +3623,8 @@ struct AlignRun {
     if (index_rests) { --h->index_rest; x.build_index_on_side = false; }
     h->pol.begin_align(index && !index_rests, h->cone_decided, h->cone_dense, h->cone_occupancy);
     h->pay_voxel_timed = h->pay_index_timed = false;
-    if (!h->ev_pay[0]) for (auto& e : h->ev_pay) HIPC(hipEventCreate(&e));
-    if (pc.lookahead && !pc.comm && !h->ev_state) HIPC(hipEventCreateWithFlags(&h->ev_state, hipEventDisableTiming));   // (fetch_state's look-ahead)
+    for (Event& e : h->ev_pay) HIPC(e.ensure(hipEventDefault));
+    if (pc.lookahead && !pc.comm) HIPC(h->ev_state.ensure(hipEventDisableTiming));   // (fetch_state's look-ahead)
     return LSGPU_OK;
   }
 
@@ -3715,7 +3712,7 @@ struct AlignRun {
   int fetch_state(int* enqueued_ahead) {
     *enqueued_ahead = 0;
     if (h->bound())   // BoundTransformationChecker: the history travels with the state (evaluated after the loop, check_bound)
-      HIPC(hipMemcpyAsync(h->h_chk, h->chk_hist.p, (size_t)8 * (max_it + 2) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+      HIPC(hipMemcpyAsync(h->h_chk.p, h->chk_hist.p, (size_t)8 * (max_it + 2) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipMemcpyAsync(hst, h->state.p, sizeof(IcpState), hipMemcpyDeviceToHost, h->stream));
     policy::Iteration ahead_it;
     if (h->pol.lookahead_iteration(h->pol_cfg, &ahead_it)) {
@@ -3785,7 +3782,7 @@ struct AlignRun {
       }
       if (verdict == policy::LookVerdict::Done) {
         if (ahead) {   // one launch is still queued behind the look that saw `done`
-          if (!h->ev_tail) HIPC(hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming));
+          HIPC(h->ev_tail.ensure(hipEventDisableTiming));
           HIPC(hipEventRecord(h->ev_tail, h->stream));
           h->tail_pending = true;
         }
@@ -3805,7 +3802,7 @@ struct AlignRun {
   bool check_bound() {
     const lsgpu_motion_config& mc = h->mo_cfg;
     int n = std::min(hst->n_hist, max_it + 2);
-    float* hist = h->h_chk;
+    float* hist = h->h_chk.p;
     if (mc.bound_before_counter && hst->status == LSGPU_OK && hst->done && !hst->converged && hst->iter > 0 && n <= max_it + 1) {
       hostmath::CheckerState cs{0, n};
       hostmath::checker_push(&cs, hist, hst->T_iter);
@@ -4042,6 +4039,8 @@ int lsgpu_icp_align_batch(lsgpu_icp* const* handles, int n_handles, int64_t n_pa
   return ret;
 }
 
+// dev only: device allocations, pinned allocations, events and streams the library holds at the moment (all handles of the process)
+long lsgpu_dev_live_resources(void) { return g_live.load(); }
 // dev only (LSGPU_KNN_STATS build): per-wave records of the last k_knn_tile launch / global counters
 int lsgpu_dev_knn_wave_stats(lsgpu_icp* h, unsigned int* out, int nwaves) {
   if (!h) return LSGPU_BAD_ARG;

@@ -824,6 +824,13 @@ def test_compute_clouds_assembles_the_submap_on_the_device(icp_mod):
         with pytest.raises(LsgpuError):
             bad = np.eye(4); bad[0, 0] = 2.0
             h.compute_clouds(3, [2], [bad], T_init)
+    # the vector of slots grows while lower slots hold clouds: they stay what they were
+    with icp_mod.IcpHandle() as h:
+        h.cloud_upload(0, scans[2])
+        T_f, _ = h.compute_clouds_upload(1, scans[3], [0], None, T_init, 0.5, 10, 0.5, seed=6)
+        h.cloud_upload(5, scans[0])
+        T_g, _ = h.compute_clouds(1, [0], None, T_init, 0.5, 10, 0.5, seed=6)
+        assert np.array_equal(T_f, T_a) and np.array_equal(T_g, T_f)
 
 
 def test_align_degenerate_and_badly_initialised_cases_match_oracle(icp_mod, oracle, pair4k):
