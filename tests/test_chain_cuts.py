@@ -239,6 +239,8 @@ SECTION_LISTS = {
     "keeps_nothing": [(6, 0, 0, []), (1, -1, 0, [0.0])],
     "keeps_nothing_sampled": [RS, (2, -1, 0, [5.0]), (1, -1, 0, [0.0])],
 }
+# wave and block edges, a partial last block, more than one scan element -- at most 17 block counts: one launch and one sub-tile
+# of the scan; the multi-tile scan of the block counts (from 1 048 577 points on) is covered in tests/test_primitive_sizes.py
 SIZES = (1, 63, 64, 65, 255, 256, 257, 4099)
 
 

@@ -303,8 +303,10 @@ def handle():
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", SIZES)
 def test_device_pass_equals_the_host_twin(n, handle):
-    """Wave and block edges, a partial last block, more than one scan element; all kept, only the last point kept, about
-    half kept, nothing kept; host pointers and device pointers."""
+    """Wave and block edges, a partial last block, more than one scan element (at most 17 block counts: one launch, one
+    sub-tile of the scan -- the multi-tile scan of the block counts, from 1 048 577 points on, is covered in
+    tests/test_primitive_sizes.py); all kept, only the last point kept, about half kept, nothing kept; host pointers and
+    device pointers."""
     import torch
     for pattern in ("all", "last", "half", "none"):
         p, v, keep = pattern_cloud(n, pattern)
