@@ -34,7 +34,8 @@
 //   LSGPU_SORT_ITEMS         0  keys per thread of the radix passes (0: by size; 4, 8, 16)
 //   LSGPU_SSN_SORT_LEVELS       the upper levels of the reference filter with a segmented sort per level (round 4, lsgpu_segsort.hip.h) instead of
 //                               the sort-free levels of lsgpu_ssn_select.hip.h (exact median by selection + one stable partition)
-//   LSGPU_SSN_ROOT        8192  points per workgroup of k_ssn_tree (2048, 4096, 8192)
+//   LSGPU_SSN_ROOT           0  points per workgroup of k_ssn_tree (0: by size -- 2048 below 819 200 points, 4096 below
+//                               1 638 400, 8192 from there; 2048, 4096, 8192)
 //   LSGPU_NE_BLOCKS        256  blocks of k_normal_eq_loop (64 .. 2048)
 //   LSGPU_SPLIT_UPDATE          the per-iteration update as its own launch (profiling)
 //   LSGPU_COMM_TIMEOUT_MS 30000 bound on every stream wait of the split-scan mode
