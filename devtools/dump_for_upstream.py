@@ -23,7 +23,11 @@ For a synthetic HDL-64E pair (default: the 4 k-point pair of the parity tests, `
   input_filtered.csv                         reading.csv through tests/golden/input_filters.yaml (srand(1) again): choice 9
   input_filters.yaml                         only with --voxel-grid VX,VY,VZ[,useCentroid]: the golden input chain with a
                                              VoxelGridDataPointsFilter appended -- the chain input_filtered.csv (and, with
-                                             --submap, scan*_input_filtered.csv) then went through: choices 30-34
+                                             --submap, scan*_input_filtered.csv) then went through: choices 30-34;
+                                             likewise with --octree-grid MAX_SIZE,MAX_POINT[,SAMPLING_METHOD]: an
+                                             OctreeGridDataPointsFilter appended (behind the voxel grid if both are asked
+                                             for): choices 49-54 (samplingMethod 1, RandomPts, is refused: its draws would
+                                             come from the library's stream, the chain's other modules draw from the oracle's)
   oracle_trace.csv                           per iteration: iter, limit (squared metres), n_used, T_iter (16, column major)
   oracle_result.txt                          rc, iterations, converged, final T (4 x 4 row major)
   README.txt                                 what is what, and which file / column each restatement choice would change
@@ -43,6 +47,7 @@ float relative pose + concatenate, :474-486), the guess is T_a^-1 T_b of the odo
 The files regenerate byte for byte (tests/test_oracle.py::test_upstream_dump_regenerates).  INTEGRATION.md has the
 C++ program that replays them on a real PointMatcher<float>::ICP and prints a trace in the same format.
 usage: dump_for_upstream.py OUT_DIR [--n-az 64] [--chain tests/golden/icp_chain_tight.yaml] [--submap] [--voxel-grid 0.5,0.5,0.5]
+                            [--octree-grid 0.5,7,3]
 """
 import argparse
 import ctypes as C
@@ -75,6 +80,13 @@ VOXEL_CHOICES = """30 VoxelGrid: float bounds, numDiv = (uint)((1 + maxB) - minB
 32 VoxelGrid: centroid = first point + the others in input order, / count   input_filtered.csv: last digits of x, y, z
 33 VoxelGrid: output in the order of the voxels' first points    input_filtered.csv: row order
 34 VoxelGrid: the pad row and descriptors are the first point's  input_filtered.csv: nothing (pad is 1)
+"""
+OCTREE_CHOICES = """49 OctreeGrid: root centre min + ext 0.5, radius = the largest extent 0.5; octant by x > cx, y > cy, z > cz   input_filtered.csv: WHICH rows / number of rows
+50 OctreeGrid: a leaf at 2 radius <= maxSizeByNode, at <= maxPointByNode points, or at depth 21 (the cap is a DEVIATION)   input_filtered.csv: number of rows
+51 OctreeGrid: output point k comes from the k-th non-empty leaf, depth first, octants 0..7             input_filtered.csv: row order
+52 OctreeGrid: FirstPts = smallest input index; RandomPts = point (uint)((count - 1) draw), one draw per leaf   input_filtered.csv: WHICH rows
+53 OctreeGrid: centroid = first point + the others in input order, / count; medoid = nearest to it, the earliest of a tie   input_filtered.csv: last digits / WHICH rows
+54 OctreeGrid: the pad row and descriptors are the chosen point's (Centroid: the first point's pad)   input_filtered.csv: nothing (pad is 1)
 """
 DENSITY_CHOICES = """36 density: knn / ((4/3) pi r^3), r = the largest distance from the neighbourhood's mean, float   reference_densities.csv: last digits
 37 density of knn identical points: +inf (dropped by MaxDensity)   reference_densities.csv: inf rows; reference_filtered.csv: rows
@@ -115,9 +127,16 @@ def voxel_grid_yaml(vsize=(1.0, 1.0, 1.0), use_centroid=1, average_existing_desc
                                                        int(use_centroid), int(average_existing_descriptors)))
 
 
+def octree_grid_yaml(max_size_by_node=0.0, max_point_by_node=1, sampling_method=0, build_parallel=1) -> str:
+    """OctreeGridDataPointsFilter as one item of a libpointmatcher DataPointsFilters file."""
+    return ("- OctreeGridDataPointsFilter:\n    buildParallel: %d\n    maxPointByNode: %d\n    maxSizeByNode: %s\n    samplingMethod: %d\n"
+            % (int(build_parallel), int(max_point_by_node), g(np.float32(max_size_by_node)), int(sampling_method)))
+
+
 def input_filter_chain(path, text=None):
     """tests/golden/input_filters.yaml (or the text of such a file) -> oracle PointFilter array.  VoxelGridDataPointsFilter
-    (type 7) is not in the oracle: run_input_filters hands it to the library's host twin."""
+    (type 7) and OctreeGridDataPointsFilter (type 8) are not in the oracle: run_input_filters hands them to the library's
+    host twins."""
     import yaml
     doc = yaml.safe_load(open(path).read() if text is None else text) or []
     arr = (O.PointFilter * len(doc))()
@@ -143,6 +162,9 @@ def input_filter_chain(path, text=None):
             a.type, a.flag, a.dim = 7, int(p.get("useCentroid", 1)), int(p.get("averageExistingDescriptors", 1))
             for i, k in enumerate(("vSizeX", "vSizeY", "vSizeZ")):
                 a.v[i] = float(p.get(k, 1.0))
+        elif name == "OctreeGridDataPointsFilter":
+            a.type, a.dim, a.flag = 8, int(p.get("samplingMethod", 0)), int(p.get("buildParallel", 1))
+            a.v[0] = float(p.get("maxSizeByNode", 0.0)); a.v[1] = float(p.get("maxPointByNode", 1))
         else:
             raise SystemExit("input filter %s is not in the restatement" % name)
     return arr
@@ -150,7 +172,8 @@ def input_filter_chain(path, text=None):
 
 def run_input_filters(flt, cloud, seed):
     """The chain on one cloud: the oracle for every run of its own modules (one draw stream, `seed` before the first), the
-    host twin of the library (lsgpu_filter_voxel_grid_points, no GPU) for VoxelGridDataPointsFilter, which draws nothing.
+    host twins of the library (lsgpu_filter_voxel_grid_points, lsgpu_filter_octree_grid_points, no GPU) for
+    VoxelGridDataPointsFilter and OctreeGridDataPointsFilter, which draw nothing (RandomPts is refused when the chain is made).
     None if a module is handed an empty cloud."""
     from laser_slam_amd import icp
     i, n = 0, len(flt)
@@ -161,8 +184,12 @@ def run_input_filters(flt, cloud, seed):
             cloud = icp.voxel_grid_points(cloud, [flt[i].v[k] for k in range(3)], flt[i].flag)
             i += 1
             continue
+        if flt[i].type == 8:
+            cloud = icp.octree_grid_points(cloud, flt[i].v[0], int(flt[i].v[1]), flt[i].dim)
+            i += 1
+            continue
         j = i
-        while j < n and flt[j].type != 7:
+        while j < n and flt[j].type not in (7, 8):
             j += 1
         part = (O.PointFilter * (j - i)).from_address(C.addressof(flt) + i * C.sizeof(O.PointFilter))   # (FixStep's state stays in flt)
         cloud = O.apply_point_filters(part, cloud, seed=seed)
@@ -176,25 +203,35 @@ def write_mat(path, T):
             f.write(" ".join(g(T[r, c]) for c in range(4)) + "\n")
 
 
-def input_chain_for_dump(out_dir, voxel_grid):
-    """The golden input chain; with `voxel_grid` (vSizeX, vSizeY, vSizeZ[, useCentroid]) the module is appended and the
-    chain's text written to OUT_DIR/input_filters.yaml."""
+def input_chain_for_dump(out_dir, voxel_grid, octree_grid=None):
+    """The golden input chain; with `voxel_grid` (vSizeX, vSizeY, vSizeZ[, useCentroid]) and / or `octree_grid` (maxSizeByNode,
+    maxPointByNode[, samplingMethod]) the modules are appended and the chain's text written to OUT_DIR/input_filters.yaml."""
     path = os.path.join(ROOT, "tests", "golden", "input_filters.yaml")
-    if not voxel_grid:
+    if not voxel_grid and not octree_grid:
         return input_filter_chain(path)
-    text = open(path).read().rstrip("\n") + "\n" + voxel_grid_yaml(voxel_grid[:3], int(voxel_grid[3]) if len(voxel_grid) > 3 else 1, 0)
+    text = open(path).read().rstrip("\n") + "\n"
+    if voxel_grid:
+        text += voxel_grid_yaml(voxel_grid[:3], int(voxel_grid[3]) if len(voxel_grid) > 3 else 1, 0)
+    if octree_grid:
+        method = int(octree_grid[2]) if len(octree_grid) > 2 else 0
+        if method == 1:
+            # the chain's other modules draw from the oracle's rand(), the host twin from the library's own stream: the two
+            # cannot continue one another (the rule of --submap with MaxDensityDataPointsFilter)
+            raise SystemExit("--octree-grid with samplingMethod 1 (RandomPts) is not supported: its draws (the library's stream) and "
+                             "the other input filters' (the oracle's rand()) would not be one sequence")
+        text += octree_grid_yaml(octree_grid[0], int(octree_grid[1]), method)
     with open(os.path.join(out_dir, "input_filters.yaml"), "w") as f:
         f.write(text)
     return input_filter_chain(None, text)
 
 
-def submap_inputs(out_dir, n_az, voxel_grid=None):
+def submap_inputs(out_dir, n_az, voxel_grid=None, octree_grid=None):
     """laser_track.cpp:146, 466-496 on four synthetic scans: input filters, sub-map of three in the frame of scan 2, the
     odometry guess.  Returns (reading, reference, T_init 4x4 float64, seed for the ICP's first draw)."""
     scene = synth.Scene(1234)
     truth = [synth.se3(0.8 * i, 0.05 * i, synth.SENSOR_HEIGHT, yaw=np.deg2rad(2.0 * i)) for i in range(4)]
     odom = [T @ synth.se3(0.1, -0.05, 0.0, yaw=np.deg2rad(0.5)) for T in truth]     # (the drive of bench.py's value_track)
-    flt = input_chain_for_dump(out_dir, voxel_grid)
+    flt = input_chain_for_dump(out_dir, voxel_grid, octree_grid)
     filtered = []
     with open(os.path.join(out_dir, "poses.txt"), "w") as f:
         for i in range(4):
@@ -216,7 +253,7 @@ def submap_inputs(out_dir, n_az, voxel_grid=None):
     return filtered[3], np.ascontiguousarray(np.concatenate(parts, 0)), np.linalg.inv(odom[a]) @ odom[3], -1
 
 
-def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
+def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None, octree_grid=None):
     os.makedirs(out_dir, exist_ok=True)
     ch = parse_chain(chain_path)
     if submap and ch.max_density is not None:
@@ -230,7 +267,7 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
                          "SurfaceNormalOutlierFilter and reads no reading normals")
     shutil.copyfile(chain_path, os.path.join(out_dir, "icp.yaml"))
     if submap:
-        rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az, voxel_grid)
+        rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az, voxel_grid, octree_grid)
     else:
         ref, rd, T_true, T_init = synth.scan_pair(n_az)
         icp_seed = 1
@@ -264,7 +301,7 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
     cloud_io.save_csv(os.path.join(out_dir, "reference_filtered.csv"), rf, rn)
     cloud_io.save_csv(os.path.join(out_dir, "reading_filtered.csv"), rdf)
     if not submap:
-        flt = input_chain_for_dump(out_dir, voxel_grid)
+        flt = input_chain_for_dump(out_dir, voxel_grid, octree_grid)
         kept = run_input_filters(flt, rd, 1)
         cloud_io.save_csv(os.path.join(out_dir, "input_filtered.csv"), kept if kept is not None else rd[:0])
     cfg = O.config_yaml(accum_double=0, trim_ratio=ch.trim_ratio, max_iterations=ch.max_iterations,
@@ -289,7 +326,7 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None):
                 % (n_az, rd.shape[0], ref.shape[0], os.path.relpath(chain_path, ROOT), g(ch.reading_sampling_prob),
                    ch.surface_normal_knn, g(ch.surface_normal_ratio), g(ch.trim_ratio), ch.max_iterations,
                    g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length,
-                   CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "") +
+                   CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (OCTREE_CHOICES if octree_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "") +
                    (SHADOW_CHOICES if ch.shadow is not None else "") + (MOTION_CHOICES if ch.motion is not None else "")))
     return rc, st.iterations
 
@@ -302,9 +339,14 @@ if __name__ == "__main__":
     ap.add_argument("--submap", action="store_true", help="the call shape of LaserTrack::localScanToSubMap (four scans, input filters, three-scan sub-map)")
     ap.add_argument("--voxel-grid", default=None, metavar="VX,VY,VZ[,USE_CENTROID]",
                     help="append VoxelGridDataPointsFilter to the input filter chain and write the chain to OUT_DIR/input_filters.yaml")
+    ap.add_argument("--octree-grid", default=None, metavar="MAX_SIZE,MAX_POINT[,SAMPLING_METHOD]",
+                    help="append OctreeGridDataPointsFilter to the input filter chain and write the chain to OUT_DIR/input_filters.yaml")
     a = ap.parse_args()
+    og = [float(x) for x in a.octree_grid.split(",")] if a.octree_grid else None
+    if og is not None and len(og) not in (2, 3):
+        ap.error("--octree-grid takes MAX_SIZE,MAX_POINT or MAX_SIZE,MAX_POINT,SAMPLING_METHOD")
     vg = [float(x) for x in a.voxel_grid.split(",")] if a.voxel_grid else None
     if vg is not None and len(vg) not in (3, 4):
         ap.error("--voxel-grid takes VX,VY,VZ or VX,VY,VZ,USE_CENTROID")
-    rc, it = dump(a.out_dir, a.n_az, a.chain, a.submap, vg)
+    rc, it = dump(a.out_dir, a.n_az, a.chain, a.submap, vg, og)
     print("wrote %s: oracle rc %d, %d iterations" % (a.out_dir, rc, it))

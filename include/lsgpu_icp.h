@@ -405,6 +405,7 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
  *   RandomSamplingDataPointsFilter   keeps point i iff draw_i < prob
  *   RemoveNaNDataPointsFilter        drops the points with a NaN among their four feature rows x, y, z, pad (Inf stays)
  *   VoxelGridDataPointsFilter        one point per occupied voxel of a grid anchored at the cloud's own minimum (below)
+ *   OctreeGridDataPointsFilter       one point per leaf of an octree over the cloud, in depth-first leaf order (below)
  * (MaxPointCountDataPointsFilter is NOT offered: which points it keeps depends on the libpointmatcher version --
  *  std::random_shuffle in the 1.2 line, sequential selection sampling later -- and on the C++ library's shuffle; it
  *  cannot be restated from the reference, which configures none.  Unknown module names are configuration errors.)
@@ -435,7 +436,40 @@ int lsgpu_filter_voxel_grid(lsgpu_icp* h, const float* xyz1, int64_t n, const fl
  *   Descriptors: the library sees none.  The C++ facade picks the first point's normal through the tag
  *     (averageExistingDescriptors 0); with averageExistingDescriptors 1 on a cloud that carries normals its apply() throws
  *     ConfigError -- averaging descriptors is not implemented.  Without descriptors both values are accepted.
- *   lsgpu_filter_voxel_grid_points is the host twin, bit for bit. */
+ *   lsgpu_filter_voxel_grid_points is the host twin, bit for bit.
+ *
+ * OctreeGridDataPointsFilter (libpointmatcher's module, the 3-D case): one point per leaf of an octree over the cloud whose
+ * leaves stop at maxPointByNode points or maxSizeByNode metres.  Restated from knowledge of upstream's
+ * OctreeGridDataPointsFilter::inPlaceFilter and Octree_::build, parity unpinned (DESIGN.md §5 choices 49-54).
+ * lsgpu_point_filter: v[0] = maxSizeByNode (default 0; finite, >= 0), v[1] = maxPointByNode (default 1; an integer in
+ * [1, 2^24], carried as a float), dim = samplingMethod (default 0; 0 FirstPts, 1 RandomPts, 2 Centroid, 3 Medoid), flag =
+ * buildParallel (default 1; 0 or 1, accepted and without effect).  Anything else is LSGPU_BAD_CONFIG, with the module and
+ * the parameter named, before anything runs.
+ *   Arithmetic: float throughout, one rounding per operation, as above.
+ *   Root box, per axis a: ext_a = max_a - min_a over the cloud handed to the module, center_a = min_a + ext_a 0.5f;
+ *     radius = max_a(ext_a) 0.5f.
+ *   A node is a leaf if 2 radius <= maxSizeByNode, or it holds at most maxPointByNode points, or it is at depth 21 (the
+ *     root is at depth 0).  DEVIATION: the depth cap -- upstream goes on halving until the radius underflows.  The cap
+ *     matters only when more than maxPointByNode points lie within 2^-21 of the root's extent of each other (exact
+ *     duplicates, say): they then share one leaf instead of a chain of ~130 more levels.
+ *   Splitting: otherwise the node's points go to octant (x > cx) | (y > cy) << 1 | (z > cz) << 2.  Child o has radius' =
+ *     radius 0.5f and center'_a = center_a + radius' if bit a of o is set, center_a - radius' if not.  Inside a node the
+ *     points stay in ascending input index.
+ *   Leaf order: the non-empty leaves are visited depth first, octants 0..7.  Output point k comes from the k-th visited leaf
+ *     (what upstream's swap-and-lookup bookkeeping intends):
+ *       FirstPts   the leaf's point with the smallest input index
+ *       RandomPts  its point number (uint)((float)(count - 1) draw) in that order; ONE draw of the library's stream per
+ *                  non-empty leaf, in visiting order -- no other method draws
+ *       Centroid   per coordinate, s starts as the first point's, every further point is added in ascending input index,
+ *                  the result is s / (float)count; the 4th component is the first point's
+ *       Medoid     the point with the smallest sqrtf(dx dx + dy dy + dz dz) to that centroid, the sum left to right, strict
+ *                  <: the earliest wins a tie
+ *     The methods that return an input point return all four components of it (the facades' tag travels in the 4th).
+ *   A NaN or +-inf coordinate in the cloud handed to the module: LSGPU_BAD_ARG (put RemoveNaNDataPointsFilter in front).
+ *   Descriptors: the library sees none.  The C++ facade picks the chosen point's normal through the tag; Centroid on a cloud
+ *     that carries normals makes its apply() throw ConfigError -- averaging descriptors is not implemented.
+ *   The 2-D quadtree is not offered; the module stands in the input filter chain only, not in the filter sections of the ICP
+ *   chain.  lsgpu_filter_octree_grid_points is the host twin, bit for bit. */
 enum {
   LSGPU_FILTER_MAX_DIST = 1,
   LSGPU_FILTER_MIN_DIST = 2,
@@ -443,16 +477,19 @@ enum {
   LSGPU_FILTER_FIX_STEP_SAMPLING = 4,
   LSGPU_FILTER_RANDOM_SAMPLING = 5,
   LSGPU_FILTER_REMOVE_NAN = 6,
-  LSGPU_FILTER_VOXEL_GRID = 7
+  LSGPU_FILTER_VOXEL_GRID = 7,
+  LSGPU_FILTER_OCTREE_GRID = 8
 };
 typedef struct lsgpu_point_filter {
   int    type;     /* LSGPU_FILTER_*                                                                          */
   int    dim;      /* Max/MinDist: -1 radial, 0..2 one axis   VoxelGrid: averageExistingDescriptors           */
+                   /* OctreeGrid: samplingMethod                                                               */
   int    flag;     /* BoundingBox: removeInside               VoxelGrid: useCentroid                          */
+                   /* OctreeGrid: buildParallel                                                                */
   int    pad_;
   float  v[6];     /* MaxDist {maxDist}  MinDist {minDist}  BoundingBox {xMin,xMax,yMin,yMax,zMin,zMax}        */
                    /* FixStepSampling {startStep,endStep,stepMult}  RandomSampling {prob}                      */
-                   /* VoxelGrid {vSizeX,vSizeY,vSizeZ}                                                         */
+                   /* VoxelGrid {vSizeX,vSizeY,vSizeZ}  OctreeGrid {maxSizeByNode,maxPointByNode}              */
   double state;    /* FixStepSampling: current step (0: start at startStep); updated by every apply            */
 } lsgpu_point_filter;
 int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
@@ -491,6 +528,14 @@ int lsgpu_filter_surface_normal(const float* xyz1, int64_t n, int knn, float* ou
  * too many voxels), -LSGPU_BAD_ARG (a NULL pointer, a NaN or infinite coordinate), -LSGPU_NO_CONVERGENCE (n <= 0). */
 int64_t lsgpu_filter_voxel_grid_points(const float* xyz1, int64_t n, const float vsize[3], int use_centroid,
                                        float* out_xyz1);
+/* OctreeGridDataPointsFilter of the input filter chain on the host (no GPU, no handle): the sequential recursion itself, with
+ * the contract and the float arithmetic above, bit for bit the output of lsgpu_apply_point_filters with this one module.
+ * seed >= 0 reseeds the library's draw stream first; RandomPts (sampling_method 1) then takes one draw per non-empty leaf.
+ * out_xyz1 needs room for n points.  Returns the number of output points, or -LSGPU_BAD_CONFIG (a bad max_size_by_node /
+ * max_point_by_node / sampling_method), -LSGPU_BAD_ARG (a NULL pointer, a NaN or infinite coordinate),
+ * -LSGPU_NO_CONVERGENCE (n <= 0). */
+int64_t lsgpu_filter_octree_grid_points(const float* xyz1, int64_t n, float max_size_by_node, int max_point_by_node,
+                                        int sampling_method, int64_t seed, float* out_xyz1);
 /* RigidTransformation::checkParameters / correctParameters (common.hpp:136-149). */
 int  lsgpu_check_rigid(const float T[16]);
 void lsgpu_correct_rigid(const float T[16], float out[16]);

@@ -258,7 +258,12 @@ class LsgpuDataPointsFilters {
     // VoxelGridDataPointsFilter writes new points (below); of the descriptors it can only hand on the first point's
     bool writes_points = false;
     for (const auto& f : filters_) {
-      writes_points = writes_points || f.type == LSGPU_FILTER_VOXEL_GRID;
+      // (OctreeGridDataPointsFilter: Centroid writes a new point as well; its other methods return the tagged point itself,
+      //  for which the copy below changes nothing)
+      writes_points = writes_points || f.type == LSGPU_FILTER_VOXEL_GRID || f.type == LSGPU_FILTER_OCTREE_GRID;
+      if (f.type == LSGPU_FILTER_OCTREE_GRID && f.dim == 2 && Traits::hasDescriptors(cloud))
+        throw std::runtime_error("LsgpuDataPointsFilters: OctreeGridDataPointsFilter: samplingMethod 2 (Centroid) on a cloud with "
+                                 "descriptors is not implemented (averaging descriptors; samplingMethod 0, 1 and 3 keep the chosen point's)");
       if (f.type == LSGPU_FILTER_VOXEL_GRID && f.dim != 0 && Traits::hasDescriptors(cloud))
         throw std::runtime_error("LsgpuDataPointsFilters: VoxelGridDataPointsFilter: averageExistingDescriptors 1 on a cloud with "
                                  "descriptors is not implemented (set averageExistingDescriptors: 0 to keep the first point's)");

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "lsgpu_icp_align_normals", "lsgpu_icp_get_reference_normals", "lsgpu_orient_normals", "lsgpu_normal_angle_weights",
     "lsgpu_icp_get_normal_angle_trace",
     "lsgpu_chain_load", "lsgpu_robust_config_why", "lsgpu_normals_config_why",
-    "lsgpu_filter_voxel_grid_points",
+    "lsgpu_filter_voxel_grid_points", "lsgpu_filter_octree_grid_points",
     "lsgpu_covariance_config_default", "lsgpu_icp_set_covariance", "lsgpu_icp_get_quality", "lsgpu_point_to_plane_cov",
     "lsgpu_point_to_plane_cov_solve", "lsgpu_loaded_chain_covariance",
     "lsgpu_icp_set_chain_cuts", "lsgpu_icp_filter_section", "lsgpu_chain_load_cuts",
@@ -241,6 +241,9 @@ class ChainCuts(C.Structure):
 
 FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_FIX_STEP_SAMPLING, FILTER_RANDOM_SAMPLING, FILTER_REMOVE_NAN = 1, 2, 3, 4, 5, 6
 FILTER_VOXEL_GRID = 7   # VoxelGridDataPointsFilter: v[0..2] = vSizeX/Y/Z, flag = useCentroid, dim = averageExistingDescriptors
+# OctreeGridDataPointsFilter: v[0] = maxSizeByNode, v[1] = maxPointByNode, dim = samplingMethod (OCTREE_*), flag = buildParallel
+FILTER_OCTREE_GRID = 8
+OCTREE_FIRST_PTS, OCTREE_RANDOM_PTS, OCTREE_CENTROID, OCTREE_MEDOID = 0, 1, 2, 3
 
 
 class LsgpuError(RuntimeError):
@@ -330,6 +333,8 @@ def lib() -> C.CDLL:
     L.lsgpu_filter_sampling_surface_normal.restype = i64
     L.lsgpu_filter_voxel_grid_points.argtypes = [fp, i64, C.POINTER(C.c_float), C.c_int, fp]
     L.lsgpu_filter_voxel_grid_points.restype = i64
+    L.lsgpu_filter_octree_grid_points.argtypes = [fp, i64, C.c_float, C.c_int, C.c_int, i64, fp]
+    L.lsgpu_filter_octree_grid_points.restype = i64
     L.lsgpu_check_rigid.argtypes = [C.POINTER(C.c_float)]
     L.lsgpu_rotation_distance.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.lsgpu_rotation_distance.restype = C.c_float

@@ -214,6 +214,18 @@ class DataPointsFilters {
           if (!(f.v[a] > 0.f) || !std::isfinite(f.v[a])) throw ConfigError(m.name + ": vSizeX / vSizeY / vSizeZ must be finite and > 0");
         if ((uc != 0 && uc != 1) || (avg != 0 && avg != 1)) throw ConfigError(m.name + ": useCentroid and averageExistingDescriptors take 0 or 1");
         f.flag = (int)uc; f.dim = (int)avg;
+      } else if (m.name == "OctreeGridDataPointsFilter") {
+        // libpointmatcher's octree (include/lsgpu_icp.h, "the input filter chain"): v[0] = maxSizeByNode, v[1] =
+        // maxPointByNode, dim = samplingMethod, flag = buildParallel; judged here as lsgpu_apply_point_filters judges them
+        only({"buildParallel", "maxPointByNode", "maxSizeByNode", "samplingMethod"});
+        f.type = LSGPU_FILTER_OCTREE_GRID;
+        const double bp = num("buildParallel", 1), mp = num("maxPointByNode", 1), ms = num("maxSizeByNode", 0), sm = num("samplingMethod", 0);
+        f.v[0] = (float)ms;
+        if (!(f.v[0] >= 0.f) || !std::isfinite(f.v[0])) throw ConfigError(m.name + ": maxSizeByNode must be finite and >= 0");
+        if (!(mp >= 1 && mp <= 16777216.0) || mp != std::floor(mp)) throw ConfigError(m.name + ": maxPointByNode must be an integer in [1, 2^24]");
+        if (sm != 0 && sm != 1 && sm != 2 && sm != 3) throw ConfigError(m.name + ": samplingMethod must be 0 (FirstPts), 1 (RandomPts), 2 (Centroid) or 3 (Medoid)");
+        if (bp != 0 && bp != 1) throw ConfigError(m.name + ": buildParallel must be 0 or 1");
+        f.v[1] = (float)mp; f.dim = (int)sm; f.flag = (int)bp;
       } else {
         throw ConfigError("input filters: module " + m.name + " is not implemented on the HIP path");
       }
@@ -603,6 +615,13 @@ inline void DataPointsFilters::apply(DataPoints& cloud) {
       if (f.type == LSGPU_FILTER_VOXEL_GRID && f.dim != 0)
         throw ConfigError("VoxelGridDataPointsFilter: averageExistingDescriptors 1 on a cloud with descriptors is not implemented "
                           "(set averageExistingDescriptors: 0 to keep the first point's)");
+  // OctreeGridDataPointsFilter likewise: FirstPts, RandomPts and Medoid return an input point, whose tag picks its normal;
+  // Centroid would have to average the leaf's descriptors.
+  if (!cloud.normals.empty())
+    for (const auto& f : filters_)
+      if (f.type == LSGPU_FILTER_OCTREE_GRID && f.dim == 2)
+        throw ConfigError("OctreeGridDataPointsFilter: samplingMethod 2 (Centroid) on a cloud with descriptors is not implemented "
+                          "(averaging descriptors; samplingMethod 0, 1 and 3 keep the chosen point's)");
   if (!h_) {
     lsgpu_icp_config c;
     lsgpu_icp_config_default(&c);

@@ -27,6 +27,7 @@
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
 #include "lsgpu_voxel_filter.h"
+#include "lsgpu_octree_filter.h"
 #include "lsgpu_cov.h"
 
 namespace {
@@ -203,6 +204,71 @@ int64_t lsgpu_filter_voxel_grid_points(const float* xyz1, int64_t n, const float
     std::memcpy(q + 3, &v.w, 4);
   }
   return (int64_t)voxels.size();
+}
+
+}  // extern "C"
+
+namespace {
+
+// OctreeGridDataPointsFilter: the recursion.  A node is its points' input indices in ascending order; a leaf emits its point
+// when it is reached, so the output is in depth-first leaf order and RandomPts draws once per non-empty leaf in that order.
+struct OctreeSampler {
+  const float* xyz1;
+  float max_size;
+  size_t max_point;
+  int method;
+  float* out;
+  int64_t n_out = 0;
+
+  void leaf(const std::vector<uint32_t>& idx) {
+    float draw = 0.f;
+    if (method == lsgpu::octreef::kRandomPts) lsgpu::DrawStream::global().take(-1, 1, &draw);
+    const lsgpu::octreef::Pt r = lsgpu::octreef::leaf_point(
+        [&](uint32_t j) { lsgpu::octreef::Pt v; std::memcpy(&v, xyz1 + 4 * (size_t)idx[j], 16); return v; }, (uint32_t)idx.size(), method, draw);
+    std::memcpy(out + 4 * n_out++, &r, 16);
+  }
+  void node(const std::vector<uint32_t>& idx, const float c[3], float radius, int depth) {
+    if (lsgpu::octreef::small_enough(radius, max_size) || idx.size() <= max_point || depth == lsgpu::octreef::kMaxDepth) { leaf(idx); return; }
+    std::vector<uint32_t> child[8];
+    for (const uint32_t i : idx) {
+      const float* p = xyz1 + 4 * (size_t)i;
+      child[lsgpu::octreef::octant(p[0], p[1], p[2], c)].push_back(i);
+    }
+    for (uint32_t o = 0; o < 8; ++o) {
+      if (child[o].empty()) continue;
+      float cc[3] = {c[0], c[1], c[2]}, r = radius;
+      lsgpu::octreef::descend(cc, &r, o);
+      node(child[o], cc, r, depth + 1);
+    }
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int64_t lsgpu_filter_octree_grid_points(const float* xyz1, int64_t n, float max_size_by_node, int max_point_by_node,
+                                        int sampling_method, int64_t seed, float* out_xyz1) {
+  if (max_point_by_node > (1 << 24) ||   // (the float the descriptor carries would round the next integers to 2^24)
+      lsgpu::octreef::why_bad_params(max_size_by_node, (float)max_point_by_node, sampling_method, 1)) return -LSGPU_BAD_CONFIG;
+  if (seed >= 0) lsgpu::DrawStream::global().take(seed, 0, nullptr);
+  if (n <= 0) return -LSGPU_NO_CONVERGENCE;
+  if (!xyz1 || !out_xyz1 || n > 0x7FFFFFF0ll) return -LSGPU_BAD_ARG;
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) lo[a] = hi[a] = xyz1[a];
+  for (int64_t i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const float c = xyz1[4 * i + a];
+      if (!std::isfinite(c)) return -LSGPU_BAD_ARG;
+      lo[a] = std::min(lo[a], c); hi[a] = std::max(hi[a], c);
+    }
+  lsgpu::octreef::Root g;
+  lsgpu::octreef::make_root(lo, hi, max_size_by_node, &g);
+  OctreeSampler s{xyz1, max_size_by_node, (size_t)max_point_by_node, sampling_method, out_xyz1};
+  std::vector<uint32_t> all((size_t)n);
+  std::iota(all.begin(), all.end(), 0u);
+  s.node(all, g.c, g.radius, 0);
+  return s.n_out;
 }
 
 // SurfaceNormalDataPointsFilter.  A checker: the exact search sweeps outwards from the point along the x-sorted cloud

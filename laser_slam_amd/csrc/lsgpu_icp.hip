@@ -39,6 +39,7 @@
 #include "lsgpu_host_math.h"
 #include "lsgpu_ssn.hip.h"
 #include "lsgpu_voxel_filter.hip.h"
+#include "lsgpu_octree_filter.hip.h"
 #include "lsgpu_ssn_tree.hip.h"
 #include "lsgpu_ssn_select.hip.h"
 #include "lsgpu_sort.hip.h"
@@ -3127,6 +3128,64 @@ static int voxel_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m, 
   return compact_kept(h, h->vgf_out.p, m, dst, m_out);
 }
 
+// ... the launches of OctreeGridDataPointsFilter behind the root box: path keys, their sort, leaves, ranks, the sort by leaf
+// rank from input order, one point per leaf at the front of dst, the number of leaves on its way to the host
+static int octree_grid_enqueue(lsgpu_icp* h, const float4* src, int64_t m, const octreef::Root& g, uint32_t max_point, int method,
+                               float4* dst) {
+  hipLaunchKernelGGL(k_ogf_keys, dim3(nblk(m)), dim3(256), 0, h->stream, src, (int)m, g, h->lane.scratch->keys.p, h->lane.scratch->vals.p);
+  int rc = sort_pairs(h, m, 3 * g.depth);  // the nodes of every depth in depth-first order (equal paths keep input order)
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ogf_leaves, dim3(nblk(m)), dim3(256), 0, h->stream, h->lane.scratch->keys_alt.p, (int)m, g.depth, max_point, h->ssn_keep.p);
+  rc = scan_u32(h, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m, false, true);   // (the heads' words are not 1: they count as 1)
+  if (rc) return rc;
+  // (the path sort's result is in keys_alt / vals_alt: the other pair is free, and it is the next sort's input)
+  hipLaunchKernelGGL(k_ogf_regroup, dim3(nblk(m)), dim3(256), 0, h->stream, h->lane.scratch->vals_alt.p, h->ssn_keep.p, h->ssn_out_pos.p, (int)m,
+                     h->lane.scratch->keys.p, h->lane.scratch->vals.p);
+  int rank_bits = 0;   // a leaf's rank is < m
+  while (rank_bits < 31 && ((uint64_t)(m - 1) >> rank_bits)) ++rank_bits;
+  rc = sort_pairs(h, m, rank_bits);  // stable, from input order: a leaf's points in ascending input index
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_ogf_sample, dim3(nblk(m)), dim3(256), 0, h->stream, src, h->lane.scratch->keys_alt.p, h->lane.scratch->vals_alt.p, (int)m,
+                     h->ssn_keep.p, method, h->ssn_draws.p, dst);
+  HIPC(hipGetLastError());
+  return scan_totals_enqueue(h, nullptr, nullptr, 0, h->ssn_keep.p, h->ssn_out_pos.p, (size_t)m);
+}
+
+// OctreeGridDataPointsFilter (include/lsgpu_icp.h, "the input filter chain"): src (m points, device) -> dst (device, room for
+// m, not src), one point per non-empty leaf in depth-first order.  RandomPts: one draw per leaf -- their number is known on
+// the device only, so up to m draws are uploaded and the stream is committed with the count once it is on the host (the rule
+// of the pass behind MaxDensityDataPointsFilter).
+static int octree_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m, const lsgpu_point_filter& f, float4* dst,
+                                     int64_t* m_out) {
+  float lo[3], hi[3];
+  int rc = cloud_bounds(h, src, m, lo, hi);
+  if (rc) return rc;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) {
+      h->err = "apply_point_filters: OctreeGridDataPointsFilter was handed a NaN or infinite coordinate; put RemoveNaNDataPointsFilter "
+               "(and a MaxDist / BoundingBox filter against infinities) in front of it";
+      return LSGPU_BAD_ARG;
+    }
+  }
+  octreef::Root g;
+  octreef::make_root(lo, hi, f.v[0], &g);
+  const bool draws = f.dim == octreef::kRandomPts;
+  HIPC(h->lane.scratch->keys.reserve(m));
+  HIPC(h->lane.scratch->vals.reserve(m));
+  HIPC(h->ssn_draws.reserve((size_t)m + 1));
+  if (draws) {
+    rc = upload_draws_begin(h, -1, (size_t)m);   // at most one draw per point; the stream stays locked until the commit
+    if (rc) return rc;
+  }
+  rc = octree_grid_enqueue(h, src, m, g, (uint32_t)f.v[1], f.dim, dst);
+  uint32_t unused = 0, n_leaves = 0;
+  if (!rc) rc = scan_totals_wait(h, &unused, &n_leaves, true);
+  if (draws) DrawStream::global().commit(rc ? 0 : (size_t)n_leaves);   // one draw per non-empty leaf
+  if (rc) return rc;
+  *m_out = n_leaves;
+  return LSGPU_OK;
+}
+
 int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
                               int64_t n, int64_t seed, float* out_xyz1, int64_t* n_out) {
   if (!h || !n_out || n_filters < 0 || (n_filters > 0 && !filters) || n < 0 || (n > 0 && (!xyz1 || !out_xyz1))) return LSGPU_BAD_ARG;
@@ -3140,7 +3199,11 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
                     : f.type == LSGPU_FILTER_FIX_STEP_SAMPLING ? (f.v[0] >= 1.f && f.v[1] >= 1.f && f.v[2] > 0.f)
                     : f.type == LSGPU_FILTER_RANDOM_SAMPLING ? (f.v[0] >= 0.f && f.v[0] <= 1.f)
                     : f.type == LSGPU_FILTER_REMOVE_NAN ? true
-                    : f.type == LSGPU_FILTER_VOXEL_GRID ? true : false;
+                    : f.type == LSGPU_FILTER_VOXEL_GRID ? true
+                    : f.type == LSGPU_FILTER_OCTREE_GRID ? true : false;
+    if (ok && f.type == LSGPU_FILTER_OCTREE_GRID) {
+      if (const char* why = octreef::why_bad_params(f.v[0], f.v[1], f.dim, f.flag)) { h->err = std::string("apply_point_filters: ") + why; return LSGPU_BAD_CONFIG; }
+    }
     if (ok && f.type == LSGPU_FILTER_VOXEL_GRID) {
       if (const char* why = voxelf::why_bad_params(f.v, f.flag, f.dim)) { h->err = std::string("apply_point_filters: ") + why; return LSGPU_BAD_CONFIG; }
     }
@@ -3168,8 +3231,8 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
   for (int k = 0; k < n_filters; ++k) {
     lsgpu_point_filter& f = filters[k];
     if (m == 0) { h->err = "apply_point_filters: no points to filter"; return LSGPU_NO_CONVERGENCE; }
-    if (f.type == LSGPU_FILTER_VOXEL_GRID) {
-      rc = voxel_grid_filter_device(h, cur, m, f, ping, &m);
+    if (f.type == LSGPU_FILTER_VOXEL_GRID || f.type == LSGPU_FILTER_OCTREE_GRID) {
+      rc = f.type == LSGPU_FILTER_VOXEL_GRID ? voxel_grid_filter_device(h, cur, m, f, ping, &m) : octree_grid_filter_device(h, cur, m, f, ping, &m);
       if (rc) return rc;
       cur = ping;
       std::swap(ping, pong);

@@ -905,6 +905,27 @@ def voxel_grid_points(xyz1, vsize=(1.0, 1.0, 1.0), use_centroid: bool = True) ->
     return o[:m].copy()
 
 
+def octree_grid_points(xyz1, max_size_by_node: float = 0.0, max_point_by_node: int = 1, sampling_method: int = 0,
+                       seed: int = -1) -> np.ndarray:
+    """OctreeGridDataPointsFilter of the input filter chain on the host (lsgpu_filter_octree_grid_points; bit for bit what
+    IcpHandle.apply_point_filters gives with this one module) -> one point per non-empty leaf, in depth-first leaf order.
+    sampling_method: 0 FirstPts, 1 RandomPts (one draw of the library's stream per leaf; seed >= 0 reseeds it first),
+    2 Centroid, 3 Medoid."""
+    a = np.ascontiguousarray(xyz1, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"expected (N,4) array, got {a.shape}")
+    if int(max_point_by_node) != max_point_by_node:
+        raise ValueError("max_point_by_node must be an integer")
+    n = a.shape[0]
+    o = np.empty((max(n, 1), 4), np.float32)
+    m = _lib.lib().lsgpu_filter_octree_grid_points(a.ctypes.data if n else None, n, float(max_size_by_node),
+                                                   min(max(int(max_point_by_node), -1), 2 ** 31 - 1),   # (a C int; refused all the same)
+                                                   int(sampling_method), int(seed), o.ctypes.data)
+    if m < 0:
+        _raise(int(-m), "lsgpu_filter_octree_grid_points")
+    return o[:m].copy()
+
+
 def point_to_point_solve(sums) -> np.ndarray:
     """lsgpu_point_to_point_solve: the point-to-point step dT (4x4 float32) from the 29 sums of
     IcpHandle.point_to_point -- host only, the same function the device loop runs.  Raises ConvergenceError for
