@@ -17,7 +17,9 @@ For a synthetic HDL-64E pair (default: the 4 k-point pair of the parity tests, `
                                              refuses it; a chain with ShadowDataPointsFilter in the reference section:
                                              what is left behind that module too -- the library's host twin, no draw:
                                              choices 41-44; the module on the reading is refused, the oracle's loop reads no
-                                             reading normals)
+                                             reading normals; a chain with CovarianceSamplingDataPointsFilter in the reference
+                                             section: what that module picks, in pick order -- the library's host twin, no
+                                             draw: choices 55-62; on the reading it is refused for the same reason)
   reading_filtered.csv                       what RandomSamplingDataPointsFilter leaves: choice 8 (the draws continue the
                                              reference filter's; the process starts at srand(1) like an unseeded one)
   input_filtered.csv                         reading.csv through tests/golden/input_filters.yaml (srand(1) again): choice 9
@@ -98,6 +100,15 @@ SHADOW_CHOICES = """41 Shadow: value = |n/|n| . p/|p||, float, three divisions p
 42 Shadow: kept iff value > eps (a tie is dropped)                  reference_filtered.csv: rows whose value equals eps
 43 Shadow: a zero normal, a point at the origin, a NaN: dropped    reference_filtered.csv: those rows
 44 Shadow: p is the point as given to the section, the sensor at the frame's origin   reference_filtered.csv: WHICH rows
+"""
+COV_SAMPLING_CHOICES = """55 CovarianceSampling: c = (float)(sum p / n) in double, v = (invL (p - c) x n, n) in float      reference_filtered.csv: WHICH rows
+56 CovarianceSampling: Lnorm 1 / mean |p - c| / half the largest extent (torqueNorm 0 / 1 / 2)     reference_filtered.csv: WHICH rows
+57 CovarianceSampling: C = sum v v^T in double; cyclic Jacobi in double, vectors rounded to float      reference_filtered.csv: WHICH rows (near-tied magnitudes)
+58 CovarianceSampling: eigen-directions in ASCENDING order of the eigenvalue (upstream: unspecified)   reference_filtered.csv: WHICH rows and their order
+59 CovarianceSampling: lists by decreasing |v . X_k|, ties by ascending index (stable sort)          reference_filtered.csv: rows with tied magnitudes
+60 CovarianceSampling: the walk takes the FIRST index of the smallest t; t_j += mag_j^2 in float      reference_filtered.csv: WHICH rows and their order
+61 CovarianceSampling: output in pick order, every component of point and normal                     reference_filtered.csv: row order
+62 CovarianceSampling: nbSample >= n passes the cloud unchanged; Lnorm 0 / a value not finite is an error   reference_filtered.csv: all rows / no dump
 """
 MOTION_CHOICES = """45 force2D / force4DOF: rows and columns {2,3,4} / {2,3,4,5} of the 6x6 system, float LLT   T of every iteration
 46 force2D: b with the planar residual n.x dx + n.y dy, normals not renormalised; matching and filters stay 3-D   T of every iteration
@@ -265,6 +276,9 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None, octree_grid=N
         # the reading's module stands behind the reading's normals, which only SurfaceNormalOutlierFilter reads: not in the oracle's loop
         raise SystemExit("ShadowDataPointsFilter in readingDataPointsFilters is not supported: the oracle's loop runs no "
                          "SurfaceNormalOutlierFilter and reads no reading normals")
+    if ch.cov_sampling is not None and ch.cov_sampling[0] is not None:
+        raise SystemExit("CovarianceSamplingDataPointsFilter in readingDataPointsFilters is not supported: the oracle's loop runs no "
+                         "SurfaceNormalOutlierFilter and reads no reading normals")
     shutil.copyfile(chain_path, os.path.join(out_dir, "icp.yaml"))
     if submap:
         rd, ref, T_init, icp_seed = submap_inputs(out_dir, n_az, voxel_grid, octree_grid)
@@ -298,6 +312,11 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None, octree_grid=N
         # not in the oracle, the library's host twin; no draw: choices 41-44
         from laser_slam_amd import icp
         rf, rn = icp.shadow(rf, rn, ch.shadow[1])
+    if ch.cov_sampling is not None:
+        # CovarianceSamplingDataPointsFilter, the section's last thinning step (in front of or behind the orientation pair: the
+        # module does not read the normals' signs): not in the oracle, the library's host twin; no draw: choices 55-62
+        from laser_slam_amd import icp
+        rf, rn, _ids = icp.cov_sampling(rf, rn, ch.cov_sampling[1][0], ch.cov_sampling[1][1])
     cloud_io.save_csv(os.path.join(out_dir, "reference_filtered.csv"), rf, rn)
     cloud_io.save_csv(os.path.join(out_dir, "reading_filtered.csv"), rdf)
     if not submap:
@@ -327,7 +346,7 @@ def dump(out_dir, n_az, chain_path, submap=False, voxel_grid=None, octree_grid=N
                    ch.surface_normal_knn, g(ch.surface_normal_ratio), g(ch.trim_ratio), ch.max_iterations,
                    g(ch.min_diff_rot), g(ch.min_diff_trans), ch.smooth_length,
                    CHOICES + (VOXEL_CHOICES if voxel_grid else "") + (OCTREE_CHOICES if octree_grid else "") + (DENSITY_CHOICES if ch.max_density is not None else "") +
-                   (SHADOW_CHOICES if ch.shadow is not None else "") + (MOTION_CHOICES if ch.motion is not None else "")))
+                   (SHADOW_CHOICES if ch.shadow is not None else "") + (COV_SAMPLING_CHOICES if ch.cov_sampling is not None else "") + (MOTION_CHOICES if ch.motion is not None else "")))
     return rc, st.iterations
 
 

@@ -33,7 +33,8 @@
  * (lsgpu_icp_set_normals), and PointToPlaneWithCovErrorMinimizer: the point-to-plane step plus the 6x6 covariance of the result
  * (lsgpu_icp_set_covariance, lsgpu_icp_get_quality), and MaxDensityDataPointsFilter behind the reference's
  * SurfaceNormalDataPointsFilter with keepDensities 1 (lsgpu_icp_set_max_density), and ShadowDataPointsFilter behind the normals
- * of either filter section (lsgpu_icp_set_shadow).
+ * of either filter section (lsgpu_icp_set_shadow), and CovarianceSamplingDataPointsFilter as the last thinning step of either
+ * (lsgpu_icp_set_cov_sampling).
  */
 #ifndef LSGPU_ICP_H_
 #define LSGPU_ICP_H_
@@ -981,6 +982,113 @@ int lsgpu_bound_first_violation(const float* T_iters, int n, float max_rot, floa
  * only.  As with lsgpu_chain_load_shadow, a front end that loads a document MUST call it beside lsgpu_chain_load and give the
  * result to lsgpu_icp_set_motion. */
 int lsgpu_chain_load_motion(const lsgpu_yaml_module* mods, int n_mods, lsgpu_motion_config* out, char* why, int why_cap);
+
+/* ---- CovarianceSamplingDataPointsFilter: geometrically stable sampling of a cloud with normals (DESIGN.md §3
+ * "CovarianceSamplingDataPointsFilter", §5 choices 55-62) ---------------------------------------------------------------------
+ * Gelfand's sampling: of the point-to-plane constraints [(p - c) x n ; n] of a cloud it keeps the nbSample points that constrain
+ * the six eigen-directions of their 6x6 covariance equally -- in a corridor the few points that stop the scan sliding along
+ * it, where RandomSampling keeps what is plentiful.  Restated from knowledge of upstream's
+ * CovarianceSamplingDataPointsFilter::inPlaceFilter, parity unpinned.
+ *   Parameters: nbSample (default 5000, an integer in [1, 2^31 - 16]); torqueNorm (default 1; 0: L = 1, 1: L = Lavg, 2: L = Lmax).
+ *     Anything else: LSGPU_BAD_CONFIG, the module and the parameter named.
+ *   Input: n points xyz1 with normals (3 floats each), as given -- not centred, the 4th component carried and not read.
+ *   nbSample >= n: the cloud passes unchanged (ids 0 .. n - 1), nothing is computed (sums_out: zeros, n in its last slot).
+ *   Otherwise, in float, one rounding per operation, no fma, sums left to right, unless marked double:
+ *   1. S_a = sum p_a in double, c_a = (float)(S_a / (double)n); min_a, max_a per axis; d = p - c.
+ *   2. Lnorm.  torqueNorm 0: 1.  1: (float)(sum (double)sqrtf((dx dx + dy dy) + dz dz) / (double)n).  2: e * 0.5f with e the
+ *      largest of the three float differences max_a - min_a.  An Lnorm that is 0 or not finite: LSGPU_BAD_ARG (upstream
+ *      divides by it).
+ *   3. invL = 1.f / Lnorm; m = d x n, each component two products and one subtraction (mx = dy nz - dz ny, my = dz nx - dx nz,
+ *      mz = dx ny - dy nx); v = (invL mx, invL my, invL mz, nx, ny, nz).
+ *   4. C_ab = sum (double)v_a (double)v_b for a <= b: 21 sums, the products exact in double.  A sum of step 1, 2 or 4 that is
+ *      not finite -- a NaN or an infinite point or normal -- is LSGPU_BAD_ARG, the outputs untouched.
+ *   5. Eigenvectors: cyclic Jacobi on the symmetric C in double (lsgpu_cov_sampling_eigen; one host function, which the
+ *      device path and the host twin both call).  A = C, V = I.  A sweep starts with off = the sum, row major, of a_pq^2 over
+ *      p < q: off == 0 ends the iteration, as do 30 sweeps.  The sweep visits (p, q), p < q, row major, and skips a pair with
+ *      a_pq == 0; else theta = (a_qq - a_pp) / (2 a_pq), t = s / (|theta| + sqrt(theta theta + 1)) with s = -1 if theta < 0
+ *      and +1 otherwise, cs = 1 / sqrt(t t + 1), sn = t cs; then for every row k (a_kp, a_kq) <- (cs a_kp - sn a_kq,
+ *      sn a_kp + cs a_kq), then for every column k (a_pk, a_qk) <- (cs a_pk - sn a_qk, sn a_pk + cs a_qk), then a_pq = a_qp = 0,
+ *      then for every row k (v_kp, v_kq) <- (cs v_kp - sn v_kq, sn v_kp + cs v_kq).  Eigenpairs (a_jj, column j of V) in
+ *      ascending order of the eigenvalue, ties by the original column; X_k = the k-th vector rounded to float.  Signs do not
+ *      matter below.  (Upstream's general EigenSolver leaves the order unspecified; ascending -- the least constrained
+ *      direction served first -- is this library's choice.)
+ *   6. s_k = ((((v0 X0k + v1 X1k) + v2 X2k) + v3 X3k) + v4 X4k) + v5 X5k, mag_k(i) = fabsf(s_k).
+ *   7. List k: the point indices by decreasing mag_k, ties by ascending index (upstream's std::list::sort is stable).  The
+ *      order is that of the magnitudes' bit patterns as unsigned integers, which for the non-negative floats is their order.
+ *   8. Walk: t[0..5] = 0 in float; nbSample times: k = 0, for i = 0..5: if (t[k] > t[i]) k = i (the first index of the
+ *      minimum); pop list k from the front while its head is already chosen; the head is chosen and popped;
+ *      t[j] += mag_j(id) * mag_j(id) for j = 0..5.
+ *   9. Output: the chosen points and normals, all four and three components, in the order they were chosen (what upstream's
+ *      swap-and-lookup bookkeeping intends).  No draw is consumed.
+ *   Heads of nbSample entries suffice: every entry popped from list k is a chosen point and chosen points are distinct, so at
+ *   most nbSample entries of a list are ever popped and the last head is read at position nbSample - 1 at most.  The device
+ *   path therefore sends the first nbSample entries of each sorted list -- index and the six magnitudes, 28 bytes -- to the
+ *   host in one download; the walk runs there, the picks go back, one kernel gathers.  Device path: three passes of double
+ *   sums without atomics (reproducible run to run), six full stable radix sorts of n pairs (a top-nbSample selection in front of a
+ *   small sort is the follow-up).
+ *   sums[32], in order: S (3), min (3), max (3), sum of lengths (1; 0 unless torqueNorm 1), C upper triangle row major (21), n.
+ *   In lsgpu_icp_compute / _compute_clouds / _compute_clouds_upload (a handle with lsgpu_icp_set_cov_sampling) the module is
+ *   the section's last thinning step behind the normals:
+ *     reference, chain->ssn_knn > 0: on the sampling filter's points and normals;
+ *     reference, chain->sn_knn > 0: the grid of the whole (cut) reference, the normals on it, copied out in the cloud's order, the
+ *       module -- by the route ShadowDataPointsFilter takes; a point-to-point handle computes the normals for the module too;
+ *     reference, behind MaxDensityDataPointsFilter and ShadowDataPointsFilter where the handle has them: on their output;
+ *     the kept cloud and its normals go on as the sampling filter's output does (orientation, centring on the KEPT cloud's
+ *       mean, grid, loop);
+ *     reference, neither ssn_knn nor sn_knn: LSGPU_BAD_CONFIG (no normals);
+ *     reading: behind its SurfaceNormalDataPointsFilter (lsgpu_normals_config.reading_sn_knn), its orientation and its Shadow
+ *       pass; the loop and SurfaceNormalOutlierFilter see the kept points and their normals.
+ *     A section with no more than nbSample points passes unchanged (behind SurfaceNormalDataPointsFilter alone the handle then
+ *     does what one without the module does).  A degenerate section (Lnorm 0, a value that is not finite) or one of more than
+ *     (2^31 - 16) / 6 points: LSGPU_BAD_ARG, the handle holds no reference and stays usable.  No draw is consumed, the draw stream of a compute is untouched; the side stream
+ *     stays on (the module runs on the main stream, in front of the reading's side).  A handle without the module enqueues
+ *     what it always did.
+ *   Not together with the split-scan mode (lsgpu_icp_comm_init) or PointToPlaneWithCovErrorMinimizer (lsgpu_icp_set_covariance):
+ *     LSGPU_BAD_CONFIG, the module named in lsgpu_last_error, whichever of the two calls comes second.  reading_nb_sample > 0 on
+ *     a handle whose lsgpu_normals_config has no reading_sn_knn, and lsgpu_icp_set_normals taking the reading's normals away
+ *     while reading_nb_sample > 0: refused likewise.
+ *   Loader: CovarianceSamplingDataPointsFilter {nbSample, torqueNorm}, once per section, behind the section's normals module
+ *     and behind its MaxDensity- and ShadowDataPointsFilter (either of them behind the module is refused), not between
+ *     ObservationDirection- and OrientNormalsDataPointsFilter (the pair may follow: the module does not read the normals'
+ *     signs).  On the reading only with SurfaceNormalOutlierFilter in the chain.  Not with PointToPlaneWithCovErrorMinimizer.
+ *     The module travels by its own entry, lsgpu_chain_load_cov_sampling: a front end that loads a document MUST call it beside
+ *     lsgpu_chain_load and give the result to lsgpu_icp_set_cov_sampling (both facades of this repository and the shim do), or
+ *     a chain with the module runs without it.  In the input filter chain (lsgpu_apply_point_filters) the name stays unknown. */
+typedef struct lsgpu_cov_sampling_config {
+  int reading_nb_sample, reference_nb_sample;       /* nbSample of the section's module; 0: no module on that side */
+  int reading_torque_norm, reference_torque_norm;   /* torqueNorm: 0, 1 or 2 */
+  int reserved[4];                                  /* 0 */
+} lsgpu_cov_sampling_config;
+void lsgpu_cov_sampling_config_default(lsgpu_cov_sampling_config* c);   /* no module on either side, torqueNorm 1 */
+/* Without a handle or a device: LSGPU_OK / NULL, or LSGPU_BAD_CONFIG / the reason (a static string, the module's and the
+ * parameter's name in it). */
+int lsgpu_cov_sampling_config_check(const lsgpu_cov_sampling_config* c);
+const char* lsgpu_cov_sampling_config_why(const lsgpu_cov_sampling_config* c);
+/* Gives the handle the module (cfg is copied); NULL, or both nb_sample 0, removes it.  Bad values and the refused combinations
+ * above: LSGPU_BAD_CONFIG before the device is touched (the handle keeps what it had). */
+int lsgpu_icp_set_cov_sampling(lsgpu_icp* h, const lsgpu_cov_sampling_config* cfg);
+/* The CovarianceSamplingDataPointsFilter modules of a YAML document: the walk, the rules, the refusals and the texts of
+ * lsgpu_chain_load, the parameters in *out (every byte; lsgpu_cov_sampling_config_default for a document without the module).
+ * Host only. */
+int lsgpu_chain_load_cov_sampling(const lsgpu_yaml_module* mods, int n_mods, lsgpu_cov_sampling_config* out, char* why, int why_cap);
+/* The module on a cloud with its normals (kernel-level entry): xyz1 4 floats / point, normals 3 floats / point, host or device
+ * pointers; out_xyz1 / out_normals / out_ids (nullable) need room for min(nb_sample, n) points and must not be the inputs.
+ * n <= (2^31 - 16) / 6.  *n_out = min(nb_sample, n); sums_out (nullable, host): the sums the device formed.
+ * LSGPU_NO_CONVERGENCE for n == 0. */
+int lsgpu_icp_filter_cov_sampling(lsgpu_icp* h, const float* xyz1, const float* normals, int64_t n, int nb_sample, int torque_norm,
+                                  float* out_xyz1, float* out_normals, int32_t* out_ids, int64_t* n_out, double sums_out[32]);
+/* Wall time in ms of the phases of the handle's last lsgpu_icp_filter_cov_sampling that got past the early exit: sums (three
+ * waits and the Jacobi), projections + sorts + heads download, the host walk, picks upload + gather (enqueue). */
+int lsgpu_icp_cov_sampling_phase_ms(lsgpu_icp* h, double ms[4]);
+/* Host twin (no GPU, no handle); host pointers.  sums_in == NULL: the sums are added sequentially in double, in index order.
+ * sums_in given (32 doubles in sums_out's layout): those are used and no sum is formed -- a tree-shaped device sum and a
+ * sequential one differ in the last bits of a double; fed the device's sums_out the twin is bit-identical with the device
+ * path in everything behind the sums. */
+int lsgpu_filter_cov_sampling(const float* xyz1, const float* normals, int64_t n, int nb_sample, int torque_norm, const double* sums_in,
+                              float* out_xyz1, float* out_normals, int32_t* out_ids, int64_t* n_out, double sums_out[32]);
+/* Step 5 on the upper triangle C21 (row major) of a symmetric 6x6 matrix: X[6 a + k] = component a of the k-th eigenvector as
+ * float, values (nullable) the eigenvalues, ascending.  Host only.  LSGPU_BAD_ARG for a NULL or an entry that is not finite. */
+int lsgpu_cov_sampling_eigen(const double C21[21], float X[36], double values[6]);
 
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */

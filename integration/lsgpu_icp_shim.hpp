@@ -149,6 +149,11 @@ class LsgpuICP {
         reset();
         throw std::runtime_error("LsgpuICP: lsgpu_icp_set_shadow: " + why);
       }
+      if (has_cov_sampling_ && lsgpu_icp_set_cov_sampling(h_, &cov_sampling_) != LSGPU_OK) {   // CovarianceSamplingDataPointsFilter, the last thinning step of either section
+        const std::string why = lsgpu_last_error(h_);
+        reset();
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_cov_sampling: " + why);
+      }
       if (has_motion_ && lsgpu_icp_set_motion(h_, &motion_) != LSGPU_OK) {   // force2D / force4DOF, BoundTransformationChecker
         const std::string why = lsgpu_last_error(h_);
         reset();
@@ -194,6 +199,8 @@ class LsgpuICP {
     has_md_ = parsed.maxDensityConfig(&md_.max_density);
     has_shadow_ = parsed.shadowConfig() != nullptr;
     if (has_shadow_) shadow_ = *parsed.shadowConfig();
+    has_cov_sampling_ = parsed.covSamplingConfig() != nullptr;
+    if (has_cov_sampling_) cov_sampling_ = *parsed.covSamplingConfig();
     has_motion_ = parsed.motionConfig() != nullptr;
     if (has_motion_) motion_ = *parsed.motionConfig();
     reset();
@@ -218,6 +225,8 @@ class LsgpuICP {
   bool has_md_ = false;                                 // ... if the chain names the module
   lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};      // ShadowDataPointsFilter's eps of the two filter sections ...
   bool has_shadow_ = false;                             // ... if the chain names the module
+  lsgpu_cov_sampling_config cov_sampling_{0, 0, 1, 1, {0, 0, 0, 0}};   // CovarianceSamplingDataPointsFilter's nbSample / torqueNorm of the two filter sections ...
+  bool has_cov_sampling_ = false;                       // ... if the chain names the module
   lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // PointToPlaneErrorMinimizer force2D / force4DOF, BoundTransformationChecker ...
   bool has_motion_ = false;                             // ... if the chain names either
   int64_t seed_ = -1;

@@ -51,6 +51,9 @@ ABI_SYMBOLS = [
     "lsgpu_icp_filter_shadow", "lsgpu_filter_shadow", "lsgpu_chain_load_shadow",
     "lsgpu_motion_config_default", "lsgpu_motion_config_check", "lsgpu_motion_config_why", "lsgpu_icp_set_motion",
     "lsgpu_point_to_plane_solve_dof", "lsgpu_bound_first_violation", "lsgpu_chain_load_motion",
+    "lsgpu_icp_filter_cov_sampling", "lsgpu_icp_cov_sampling_phase_ms", "lsgpu_filter_cov_sampling", "lsgpu_cov_sampling_eigen",
+    "lsgpu_cov_sampling_config_default", "lsgpu_cov_sampling_config_check", "lsgpu_cov_sampling_config_why",
+    "lsgpu_icp_set_cov_sampling", "lsgpu_chain_load_cov_sampling",
 ]
 
 # lsgpu_motion_config.dof (LSGPU_MOTION_DOF_*): the free step, force2D, force4DOF
@@ -96,6 +99,13 @@ class CovarianceCfg(C.Structure):
 class MaxDensityCfg(C.Structure):
     """lsgpu_max_density_config: MaxDensityDataPointsFilter's parameter."""
     _fields_ = [("max_density", C.c_float), ("reserved", C.c_int * 3)]
+
+
+class CovSamplingCfg(C.Structure):
+    """lsgpu_cov_sampling_config: CovarianceSamplingDataPointsFilter's nbSample (0: no module on that side) and torqueNorm of the
+    two filter sections."""
+    _fields_ = [("reading_nb_sample", C.c_int), ("reference_nb_sample", C.c_int), ("reading_torque_norm", C.c_int),
+                ("reference_torque_norm", C.c_int), ("reserved", C.c_int * 4)]
 
 
 class ShadowCfg(C.Structure):
@@ -400,6 +410,17 @@ def lib() -> C.CDLL:
     L.lsgpu_icp_filter_shadow.argtypes = [vp, fp, fp, i64, C.c_float, fp, fp, C.POINTER(i64)]
     L.lsgpu_filter_shadow.argtypes = [fp, fp, i64, C.c_float, fp, fp, C.POINTER(i64)]
     L.lsgpu_chain_load_shadow.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(ShadowCfg), C.c_char_p, C.c_int]
+    L.lsgpu_icp_filter_cov_sampling.argtypes = [vp, fp, fp, i64, C.c_int, C.c_int, fp, fp, vp, C.POINTER(i64), vp]
+    L.lsgpu_icp_cov_sampling_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.lsgpu_filter_cov_sampling.argtypes = [fp, fp, i64, C.c_int, C.c_int, vp, fp, fp, vp, C.POINTER(i64), vp]
+    L.lsgpu_cov_sampling_eigen.argtypes = [vp, vp, vp]
+    L.lsgpu_cov_sampling_config_default.argtypes = [C.POINTER(CovSamplingCfg)]
+    L.lsgpu_cov_sampling_config_default.restype = None
+    L.lsgpu_cov_sampling_config_check.argtypes = [C.POINTER(CovSamplingCfg)]
+    L.lsgpu_cov_sampling_config_why.argtypes = [C.POINTER(CovSamplingCfg)]
+    L.lsgpu_cov_sampling_config_why.restype = C.c_char_p
+    L.lsgpu_icp_set_cov_sampling.argtypes = [vp, C.POINTER(CovSamplingCfg)]
+    L.lsgpu_chain_load_cov_sampling.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(CovSamplingCfg), C.c_char_p, C.c_int]
     L.lsgpu_motion_config_default.argtypes = [C.POINTER(MotionCfg)]
     L.lsgpu_motion_config_default.restype = None
     L.lsgpu_motion_config_check.argtypes = [C.POINTER(MotionCfg)]

@@ -276,6 +276,7 @@ class ICP {
     std::memset(&cuts_, 0, sizeof(cuts_));
     lsgpu_shadow_config_default(&shadow_);
     lsgpu_motion_config_default(&motion_);
+    lsgpu_cov_sampling_config_default(&cov_sampling_);
     release();
   }
 
@@ -304,10 +305,14 @@ class ICP {
     // force2D / force4DOF of PointToPlaneErrorMinimizer and BoundTransformationChecker: likewise by their own entry
     lsgpu_motion_config motion;
     if (lsgpu_chain_load_motion(list.data(), (int)list.size(), &motion, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
+    // CovarianceSamplingDataPointsFilter of the two sections: likewise
+    lsgpu_cov_sampling_config cov_sampling;
+    if (lsgpu_chain_load_cov_sampling(list.data(), (int)list.size(), &cov_sampling, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
     loaded_ = loaded;
     cuts_ = cuts;
     shadow_ = shadow;
     motion_ = motion;
+    cov_sampling_ = cov_sampling;
     release();
   }
 
@@ -490,6 +495,8 @@ class ICP {
   const lsgpu_chain_cuts* chainCuts() const { return cuts_.n_reading || cuts_.n_reference ? &cuts_ : nullptr; }
   // ShadowDataPointsFilter's eps of the two filter sections (nullptr: no such module; an eps < 0: none on that side)
   const lsgpu_shadow_config* shadowConfig() const { return shadow_.reading_eps >= 0.f || shadow_.reference_eps >= 0.f ? &shadow_ : nullptr; }
+  // CovarianceSamplingDataPointsFilter's nbSample / torqueNorm of the two filter sections (nullptr: no such module; nbSample 0: none on that side)
+  const lsgpu_cov_sampling_config* covSamplingConfig() const { return cov_sampling_.reading_nb_sample > 0 || cov_sampling_.reference_nb_sample > 0 ? &cov_sampling_ : nullptr; }
   // PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (nullptr: neither)
   const lsgpu_motion_config* motionConfig() const { return motion_.dof || motion_.bound ? &motion_ : nullptr; }
   const lsgpu_loaded_chain& loadedChain() const { return loaded_; }
@@ -576,6 +583,11 @@ class ICP {
       release();
       throw ConfigError(msg);
     }
+    if (covSamplingConfig() && lsgpu_icp_set_cov_sampling(h_, &cov_sampling_) != LSGPU_OK) {   // (behind lsgpu_icp_set_normals: the reading's needs its normals)
+      const std::string msg = std::string("lsgpu_icp_set_cov_sampling: ") + lsgpu_last_error(h_);
+      release();
+      throw ConfigError(msg);
+    }
     if (motionConfig() && lsgpu_icp_set_motion(h_, &motion_) != LSGPU_OK) {   // (last: it refuses what the constrained steps do not cover)
       const std::string msg = std::string("lsgpu_icp_set_motion: ") + lsgpu_last_error(h_);
       release();
@@ -596,6 +608,7 @@ class ICP {
   lsgpu_chain_cuts cuts_{};       // ... and the cut modules of its filter sections (lsgpu_chain_load_cuts)
   lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};   // ... and ShadowDataPointsFilter's eps of the two (lsgpu_chain_load_shadow)
   lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // ... and force2D / force4DOF, BoundTransformationChecker (lsgpu_chain_load_motion)
+  lsgpu_cov_sampling_config cov_sampling_{0, 0, 1, 1, {0, 0, 0, 0}};   // ... and CovarianceSamplingDataPointsFilter of the two (lsgpu_chain_load_cov_sampling)
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;

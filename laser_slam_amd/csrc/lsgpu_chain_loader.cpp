@@ -20,6 +20,7 @@
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_robust.h"
 #include "lsgpu_shadow.h"
+#include "lsgpu_cov_sampling.h"
 
 namespace {
 
@@ -59,6 +60,7 @@ struct Load {
   bool matcher = false, minimizer = false, counter = false, robust = false, with_cov = false;
   bool ref_densities = false, max_density = false;   // the reference's SurfaceNormal has keepDensities 1; MaxDensity stands behind it
   lsgpu_shadow_config shadow;             // ShadowDataPointsFilter of the two sections (lsgpu_chain_load_shadow): beside stage[], not in it
+  lsgpu_cov_sampling_config cov_sampling; // CovarianceSamplingDataPointsFilter of the two sections (lsgpu_chain_load_cov_sampling): likewise
   lsgpu_motion_config motion;             // force2D / force4DOF of PointToPlaneErrorMinimizer, BoundTransformationChecker (lsgpu_chain_load_motion)
 
   std::string name() const { return m->name; }
@@ -99,6 +101,15 @@ struct Load {
   }
   bool whole(double x) const { return std::fabs(x) < 2147483648.0 && x == (double)(int)x; }
 };
+
+// CovarianceSamplingDataPointsFilter runs as its section's last thinning step: the section's MaxDensity- or
+// ShadowDataPointsFilter behind it is refused
+const char* const kCovSampling = "CovarianceSamplingDataPointsFilter";
+void not_behind_cov_sampling(const Load& l) {
+  const int s = l.side();
+  if ((s == 0 ? l.cov_sampling.reading_nb_sample : l.cov_sampling.reference_nb_sample) > 0)
+    refuse(std::string(l.m->section) + ": " + kCovSampling + " in front of " + l.name() + " is not implemented (the module runs as the section's last thinning step)");
+}
 
 // SurfaceNormalDataPointsFilter's parameters (either side): keepNormals 1, exact (epsilon 0), no maxDist -> knn.
 // keep_densities: where keepDensities (0 or 1) goes -- the reference's module; nullptr (the reading's): 1 is refused
@@ -186,6 +197,7 @@ void reference_normals(Load& l) {
 // MaxDensityDataPointsFilter: directly behind the reference's SurfaceNormalDataPointsFilter with keepDensities 1, in front of the
 // orientation pair, once.  The two slots of lsgpu_loaded_chain.reserved
 void max_density_filter(Load& l) {
+  not_behind_cov_sampling(l);
   const std::string n = l.name();
   const char* const where = " may stand only in referenceDataPointsFilters, directly behind SurfaceNormalDataPointsFilter with "
                             "keepDensities 1 and in front of ObservationDirectionDataPointsFilter / OrientNormalsDataPointsFilter";
@@ -203,6 +215,7 @@ void max_density_filter(Load& l) {
 // ShadowDataPointsFilter {eps}: behind the section's normals module (and behind MaxDensityDataPointsFilter, which load() sees to),
 // not inside the orientation pair, once (the row).  stage[] stays as it is: the pair may still follow
 void shadow_filter(Load& l) {
+  not_behind_cov_sampling(l);
   const std::string n = l.name();
   const int s = l.side();
   const std::string sec = std::string(l.m->section) + ": ";
@@ -216,6 +229,26 @@ void shadow_filter(Load& l) {
   const float f = (float)e;
   if (!(e >= 0.0 && e <= 3.1416) || !lsgpu::shadow::eps_ok(f)) refuse(n + ": eps must be in [0, 3.1416]");
   (s == 0 ? l.shadow.reading_eps : l.shadow.reference_eps) = f;
+}
+// CovarianceSamplingDataPointsFilter {nbSample, torqueNorm}: behind the section's normals module, behind its MaxDensity- and
+// ShadowDataPointsFilter (their handlers see to that), not inside the orientation pair, once (the row).  stage[] stays as it
+// is: the pair may still follow (the module does not read the normals' signs)
+void cov_sampling_filter(Load& l) {
+  const std::string n = l.name();
+  const int s = l.side();
+  const std::string sec = std::string(l.m->section) + ": ";
+  if (l.stage[s] < (s == 0 ? 2 : 1))
+    refuse(sec + n + " needs the normals: it may stand only behind " +
+           (s == 0 ? "the reading's SurfaceNormalDataPointsFilter" : "SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter") +
+           " (a chain with no such module in the section cannot run it)");
+  if (l.stage[s] == 3)
+    refuse(sec + n + " may not stand between ObservationDirectionDataPointsFilter and OrientNormalsDataPointsFilter (the pair is implemented as one step)");
+  const double nb = l.num("nbSample", 5000);
+  if (!l.whole(nb) || !lsgpu::covs::nb_sample_ok((long long)nb)) refuse(n + ": nbSample must be an integer in [1, 2147483632]");
+  const double tn = l.num("torqueNorm", 1);
+  if (tn != 0.0 && tn != 1.0 && tn != 2.0) refuse(n + ": torqueNorm must be 0, 1 or 2");
+  (s == 0 ? l.cov_sampling.reading_nb_sample : l.cov_sampling.reference_nb_sample) = (int)nb;
+  (s == 0 ? l.cov_sampling.reading_torque_norm : l.cov_sampling.reference_torque_norm) = (int)tn;
 }
 void observation_direction(Load& l) {
   const int s = l.side();
@@ -362,6 +395,8 @@ const Row kRows[] = {
     {"readingDataPointsFilters", "MaxDensityDataPointsFilter", "maxDensity", false, max_density_filter},
     {"referenceDataPointsFilters", "ShadowDataPointsFilter", "eps", true, shadow_filter},
     {"readingDataPointsFilters", "ShadowDataPointsFilter", "eps", true, shadow_filter},
+    {"referenceDataPointsFilters", "CovarianceSamplingDataPointsFilter", "nbSample torqueNorm", true, cov_sampling_filter},
+    {"readingDataPointsFilters", "CovarianceSamplingDataPointsFilter", "nbSample torqueNorm", true, cov_sampling_filter},
     {"referenceDataPointsFilters", "ObservationDirectionDataPointsFilter", "x y z", true, observation_direction},
     {"referenceDataPointsFilters", "OrientNormalsDataPointsFilter", "towardCenter", true, orient_normals},
     {"readingDataPointsFilters", "MaxDistDataPointsFilter", "dim maxDist", false, cut_max_dist},
@@ -409,6 +444,10 @@ void finish(Load& l) {
   if (l.shadow.reading_eps >= 0.f && !(o.normals.max_angle >= 0.f))   // (in front of the rule below, whose text does not name the module)
     refuse("readingDataPointsFilters: ShadowDataPointsFilter without SurfaceNormalOutlierFilter is not implemented (reading normals that "
            "no outlier filter reads are refused, and the module alone does not change that)");
+  const bool cov_sampling = l.cov_sampling.reading_nb_sample > 0 || l.cov_sampling.reference_nb_sample > 0;
+  if (l.cov_sampling.reading_nb_sample > 0 && !(o.normals.max_angle >= 0.f))   // (likewise)
+    refuse(std::string("readingDataPointsFilters: ") + kCovSampling + " without SurfaceNormalOutlierFilter is not implemented (reading normals that "
+           "no outlier filter reads are refused, and the module alone does not change that)");
   if (lsgpu::normal_angle::check(&o.normals, o.icp.error_minimizer, have_normals, &why) != LSGPU_OK) refuse(why);
   if (!l.counter) refuse("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
   if (l.with_cov) {   // what the covariance pass does not cover (lsgpu_icp_set_covariance refuses the same handles)
@@ -417,6 +456,7 @@ void finish(Load& l) {
     if (with) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + with + " (the covariance is implemented for knn 1 and binary distance filters)");
     if (l.max_density) refuse("PointToPlaneWithCovErrorMinimizer: not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)");
     if (shadow) refuse("PointToPlaneWithCovErrorMinimizer: not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)");
+    if (cov_sampling) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + kCovSampling + " (the covariance's first version does not cover a reference thinned behind the normals)");
   }
   if (l.motion.dof != LSGPU_MOTION_DOF_6) {   // what the constrained steps' first version does not cover (lsgpu_icp_set_motion refuses the same handles)
     const char* with = o.icp.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2" : l.robust ? "RobustOutlierFilter"
@@ -438,6 +478,8 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
   std::memset(&l.cuts, 0, sizeof(l.cuts));
   std::memset(&l.shadow, 0, sizeof(l.shadow));
   l.shadow.reading_eps = -1.f; l.shadow.reference_eps = -1.f;
+  std::memset(&l.cov_sampling, 0, sizeof(l.cov_sampling));   // (= lsgpu_cov_sampling_config_default)
+  l.cov_sampling.reading_torque_norm = 1; l.cov_sampling.reference_torque_norm = 1;
   std::memset(&l.motion, 0, sizeof(l.motion));   // (= lsgpu_motion_config_default: this file stands alone in one of the tests)
   l.motion.max_rotation_norm = 1.f; l.motion.max_translation_norm = 1.f;
   lsgpu_icp_config_default(&l.out.icp);
@@ -460,6 +502,9 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
     for (int p = 0; kRows[r].params && p < m.n_params; ++p)
       if (!listed(kRows[r].params, m.params[p].key)) refuse(std::string(m.name) + ": unknown parameter " + m.params[p].key);
     l.m = &m;
+    if (l.ref_densities && !l.max_density && kRows[r].load == cov_sampling_filter && l.side() == 1)   // (the reference's own module; in front of the rule below, whose text does not name the module)
+      refuse(std::string(m.section) + ": " + kCovSampling + " in front of MaxDensityDataPointsFilter is not implemented (keepDensities 1 needs "
+             "MaxDensityDataPointsFilter directly behind SurfaceNormalDataPointsFilter; the module runs as the section's last thinning step)");
     if (l.ref_densities && !l.max_density && kRows[r].load != max_density_filter) refuse(kDensitiesAlone);
     kRows[r].load(l);
   }
@@ -470,11 +515,12 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
 
 extern "C" {
 
-// the four entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts`, `shadow` or `motion`, the others NULL)
+// the five entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts`, `shadow`, `motion` or
+// `cov_sampling`, the others NULL)
 static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, lsgpu_shadow_config* shadow,
-                     char* why, int why_cap, lsgpu_motion_config* motion = nullptr) {
+                     char* why, int why_cap, lsgpu_motion_config* motion = nullptr, lsgpu_cov_sampling_config* cov_sampling = nullptr) {
   if (why && why_cap > 0) why[0] = '\0';
-  if ((!chain && !cuts && !shadow && !motion) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
+  if ((!chain && !cuts && !shadow && !motion && !cov_sampling) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
   for (int i = 0; i < n_mods; ++i) {
     if (!mods[i].section || !mods[i].name || mods[i].n_params < 0 || (mods[i].n_params > 0 && !mods[i].params)) return LSGPU_BAD_ARG;
     for (int p = 0; p < mods[i].n_params; ++p)
@@ -487,6 +533,7 @@ static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
     if (cuts) *cuts = l.cuts;
     if (shadow) *shadow = l.shadow;
     if (motion) *motion = l.motion;
+    if (cov_sampling) *cov_sampling = l.cov_sampling;
     return LSGPU_OK;
   } catch (const Refusal& r) {
     if (why && why_cap > 0) std::snprintf(why, (size_t)why_cap, "%s", r.why.c_str());
@@ -514,6 +561,11 @@ int lsgpu_chain_load_shadow(const lsgpu_yaml_module* mods, int n_mods, lsgpu_sha
 int lsgpu_chain_load_motion(const lsgpu_yaml_module* mods, int n_mods, lsgpu_motion_config* out, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
   return out ? load_into(mods, n_mods, nullptr, nullptr, nullptr, why, why_cap, out) : LSGPU_BAD_ARG;
+}
+
+int lsgpu_chain_load_cov_sampling(const lsgpu_yaml_module* mods, int n_mods, lsgpu_cov_sampling_config* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  return out ? load_into(mods, n_mods, nullptr, nullptr, nullptr, why, why_cap, nullptr, out) : LSGPU_BAD_ARG;
 }
 
 int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density) {

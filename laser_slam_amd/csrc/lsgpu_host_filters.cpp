@@ -24,6 +24,7 @@
 #include "lsgpu_density.h"
 #include "lsgpu_robust.h"
 #include "lsgpu_shadow.h"
+#include "lsgpu_cov_sampling.h"
 #include "lsgpu_normal_angle.h"
 #include "lsgpu_rand.h"
 #include "lsgpu_voxel_filter.h"
@@ -422,6 +423,116 @@ int lsgpu_filter_shadow(const float* xyz1, const float* normals, int64_t n, floa
   }
   *n_out = kept;
   return kept > 0 ? LSGPU_OK : LSGPU_NO_CONVERGENCE;
+}
+
+// ---- CovarianceSamplingDataPointsFilter: the steps of include/lsgpu_icp.h in their order, the arithmetic of
+// csrc/lsgpu_cov_sampling.h; with sums_in the sums are the caller's (the device's), everything behind them is computed here
+void lsgpu_cov_sampling_config_default(lsgpu_cov_sampling_config* c) {
+  if (!c) return;
+  std::memset(c, 0, sizeof(*c));
+  c->reading_torque_norm = 1; c->reference_torque_norm = 1;
+}
+const char* lsgpu_cov_sampling_config_why(const lsgpu_cov_sampling_config* c) {
+  if (!c) return "CovarianceSamplingDataPointsFilter: no configuration";
+  // (nbSample 0: no module on that side)
+  if (c->reading_nb_sample != 0 && !lsgpu::covs::nb_sample_ok(c->reading_nb_sample)) return "CovarianceSamplingDataPointsFilter: the reading's nbSample must be in [1, 2147483632] (or 0: no module)";
+  if (c->reference_nb_sample != 0 && !lsgpu::covs::nb_sample_ok(c->reference_nb_sample)) return "CovarianceSamplingDataPointsFilter: the reference's nbSample must be in [1, 2147483632] (or 0: no module)";
+  if (!lsgpu::covs::torque_norm_ok(c->reading_torque_norm)) return "CovarianceSamplingDataPointsFilter: the reading's torqueNorm must be 0, 1 or 2";
+  if (!lsgpu::covs::torque_norm_ok(c->reference_torque_norm)) return "CovarianceSamplingDataPointsFilter: the reference's torqueNorm must be 0, 1 or 2";
+  for (int r : c->reserved)
+    if (r) return "CovarianceSamplingDataPointsFilter: reserved fields must be 0";
+  return nullptr;
+}
+int lsgpu_cov_sampling_config_check(const lsgpu_cov_sampling_config* c) { return lsgpu_cov_sampling_config_why(c) ? LSGPU_BAD_CONFIG : LSGPU_OK; }
+
+int lsgpu_cov_sampling_eigen(const double C21[21], float X[36], double values[6]) {
+  if (!C21 || !X) return LSGPU_BAD_ARG;
+  for (int k = 0; k < 21; ++k)
+    if (!std::isfinite(C21[k])) return LSGPU_BAD_ARG;
+  lsgpu::covs::eigen(C21, X, values);
+  return LSGPU_OK;
+}
+
+int lsgpu_filter_cov_sampling(const float* xyz1, const float* normals, int64_t n, int nb_sample, int torque_norm, const double* sums_in,
+                              float* out_xyz1, float* out_normals, int32_t* out_ids, int64_t* n_out, double sums_out[32]) {
+  namespace cs = lsgpu::covs;
+  if (!n_out) return LSGPU_BAD_ARG;
+  *n_out = 0;
+  if (n < 0 || n > cs::kPointsMax || (n > 0 && (!xyz1 || !normals || !out_xyz1 || !out_normals)) || (n > 0 && (out_xyz1 == xyz1 || out_normals == normals)))
+    return LSGPU_BAD_ARG;
+  if (!cs::nb_sample_ok(nb_sample) || !cs::torque_norm_ok(torque_norm)) return LSGPU_BAD_CONFIG;
+  if (n == 0) return LSGPU_NO_CONVERGENCE;
+  if ((int64_t)nb_sample >= n) {   // the cloud passes unchanged, nothing is computed
+    std::memcpy(out_xyz1, xyz1, (size_t)n * 16);
+    std::memcpy(out_normals, normals, (size_t)n * 12);
+    if (out_ids) std::iota(out_ids, out_ids + n, 0);
+    if (sums_out) { std::fill(sums_out, sums_out + cs::kSums, 0.0); sums_out[cs::kSumN] = (double)n; }
+    *n_out = n;
+    return LSGPU_OK;
+  }
+  double sums[cs::kSums];
+  std::fill(sums, sums + cs::kSums, 0.0);
+  if (sums_in) std::memcpy(sums, sums_in, sizeof sums);
+  sums[cs::kSumN] = (double)n;
+  if (!sums_in) {
+    for (int a = 0; a < 3; ++a) { sums[cs::kSumMin + a] = (double)INFINITY; sums[cs::kSumMax + a] = -(double)INFINITY; }
+    for (int64_t i = 0; i < n; ++i)
+      for (int a = 0; a < 3; ++a) {
+        const double v = (double)xyz1[4 * i + a];
+        sums[cs::kSumS + a] += v;
+        if (v < sums[cs::kSumMin + a]) sums[cs::kSumMin + a] = v;
+        if (v > sums[cs::kSumMax + a]) sums[cs::kSumMax + a] = v;
+      }
+  }
+  if (!cs::finite_sums(sums)) return LSGPU_BAD_ARG;
+  float c[3];
+  cs::centre(sums, n, c);
+  if (!sums_in && torque_norm == 1)
+    for (int64_t i = 0; i < n; ++i)
+      sums[cs::kSumLen] += (double)cs::length(xyz1[4 * i] - c[0], xyz1[4 * i + 1] - c[1], xyz1[4 * i + 2] - c[2]);
+  const float L = cs::lnorm(torque_norm, sums, n);
+  if (!(L != 0.f) || !std::isfinite(L)) return LSGPU_BAD_ARG;
+  const float invL = 1.f / L;
+  std::vector<float> v6(6 * (size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    cs::vec6(xyz1[4 * i], xyz1[4 * i + 1], xyz1[4 * i + 2], normals[3 * i], normals[3 * i + 1], normals[3 * i + 2], c, invL, &v6[6 * (size_t)i]);
+  if (!sums_in)
+    for (int64_t i = 0; i < n; ++i) {
+      const float* v = &v6[6 * (size_t)i];
+      for (int a = 0, k = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b, ++k) sums[cs::kSumC + k] += (double)v[a] * (double)v[b];
+    }
+  if (!cs::finite_sums(sums)) return LSGPU_BAD_ARG;
+  cs::Eig e;
+  cs::eigen(sums + cs::kSumC, e.X, nullptr);
+  std::vector<float> mag(6 * (size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    for (int k = 0; k < 6; ++k) mag[6 * (size_t)i + k] = cs::magnitude(&v6[6 * (size_t)i], e.X, k);
+  const int64_t m = nb_sample;   // (< n)
+  std::vector<cs::Head> heads(6 * (size_t)m);
+  std::vector<uint32_t> order((size_t)n);
+  for (int k = 0; k < 6; ++k) {
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+      return cs::sort_key(mag[6 * (size_t)x + k]) < cs::sort_key(mag[6 * (size_t)y + k]);
+    });
+    for (int64_t j = 0; j < m; ++j) {
+      cs::Head& hd = heads[(size_t)k * (size_t)m + (size_t)j];
+      hd.id = order[(size_t)j];
+      std::memcpy(hd.mag, &mag[6 * (size_t)hd.id], 24);
+    }
+  }
+  std::vector<uint32_t> ids((size_t)m);
+  std::vector<uint64_t> chosen;
+  if (cs::walk(heads.data(), m, n, m, ids.data(), chosen) != m) return LSGPU_BAD_ARG;
+  for (int64_t j = 0; j < m; ++j) {
+    std::memcpy(out_xyz1 + 4 * j, xyz1 + 4 * (size_t)ids[(size_t)j], 16);
+    std::memcpy(out_normals + 3 * j, normals + 3 * (size_t)ids[(size_t)j], 12);
+    if (out_ids) out_ids[j] = (int32_t)ids[(size_t)j];
+  }
+  if (sums_out) std::memcpy(sums_out, sums, sizeof sums);
+  *n_out = m;
+  return LSGPU_OK;
 }
 
 int lsgpu_check_rigid(const float T[16]) { return std::fabs(1.0f - det3(T)) <= 0.001f; }

@@ -32,6 +32,7 @@
 #include "lsgpu_snf.hip.h"
 #include "lsgpu_max_density.hip.h"
 #include "lsgpu_shadow.hip.h"
+#include "lsgpu_cov_sampling.hip.h"
 #include "lsgpu_cone.hip.h"
 #include "lsgpu_solve.hip.h"
 #include "lsgpu_cov.hip.h"
@@ -236,6 +237,7 @@ struct Staging {
   alignas(64) uint32_t price[kPriceSlots * kPriceStride];   // run_knn: the price check's counters (price_cnt) behind the priced search
   alignas(64) uint32_t cone_occ;            // build_cone: occupied bins of the direction index, behind the build
   alignas(64) uint32_t gs_err[8];           // ssn_device: the error record of the sort-free levels (gs_err), with the totals
+  alignas(64) double cs[kCsStride];         // CovarianceSamplingDataPointsFilter: the columns of one sums pass (k_cs_final)
 };
 
 struct lsgpu_icp {
@@ -371,6 +373,23 @@ struct lsgpu_icp {
   DevBuf<float4> sh_ref, sh_rd;      // the kept points of the reference (behind the sampling filter or the thinning) / the reading
   DevBuf<float> sh_nrm, sh_rd_nrm;   // the kept reference normals; the reading's normals in front of the pass
   DevBuf<float> sh_nrm_in;           // staging of a host caller's normals (lsgpu_icp_filter_shadow)
+  // CovarianceSamplingDataPointsFilter (lsgpu_icp_filter_cov_sampling; lsgpu_cov_sampling.hip.h)
+  bool cs_on = false;                   // lsgpu_icp_set_cov_sampling: the module in the sections of a compute
+  lsgpu_cov_sampling_config cs_cfg{};
+  DevBuf<float4> cs_ref, cs_rd;         // the chosen points of the reference / the reading ...
+  DevBuf<float> cs_ref_nrm, cs_rd_nrm;  // ... and their normals
+  DevBuf<float> cs_sn_nrm;              // behind SurfaceNormalDataPointsFilter alone: the whole reference's normals in its order
+  DevBuf<int32_t> cs_pick;              // the picks of a section (not read behind the gather)
+  DevBuf<double> cs_partials, cs_out;   // kCsBlocksMax x kCsStride, kCsStride
+  DevBuf<float> cs_mag;                 // the six magnitudes of every point
+  DevBuf<covs::Head> cs_heads;          // the first min(nbSample, n) entries of the six sorted lists ...
+  PinBuf<covs::Head> cs_heads_pin;      // ... on the host, for the walk
+  PinBuf<uint32_t> cs_ids_pin;          // the walk's picks on their way back ...
+  DevBuf<uint32_t> cs_ids;              // ... and on the device
+  std::vector<uint64_t> cs_chosen;      // the walk's bitmap, one bit per point
+  double cs_ms[4] = {0, 0, 0, 0};       // wall time of the last call's phases (lsgpu_icp_cov_sampling_phase_ms)
+  DevBuf<float> cs_nrm_in;              // staging of a host caller's normals ...
+  DevBuf<float4> cs_pts_out; DevBuf<float> cs_nrm_out; DevBuf<int32_t> cs_ids_out;   // ... and of its results
   // PointToPlaneErrorMinimizer force4DOF / force2D and BoundTransformationChecker (lsgpu_icp_set_motion)
   bool mo_on = false;
   lsgpu_motion_config mo_cfg{};
@@ -596,6 +615,10 @@ int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
     h->err = "ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn): remove the module first (lsgpu_icp_set_shadow)";
     return LSGPU_BAD_CONFIG;
   }
+  if (h->cs_on && h->cs_cfg.reading_nb_sample > 0 && (!cfg || cfg->reading_sn_knn <= 0)) {
+    h->err = "CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn): remove the module first (lsgpu_icp_set_cov_sampling)";
+    return LSGPU_BAD_CONFIG;
+  }
   if (!cfg) { h->normals_on = false; return LSGPU_OK; }
   const char* why = nullptr;
   // (whether the reference has normals is known to align, for which a filter without them is inert)
@@ -622,6 +645,7 @@ int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
   if (with) { h->err = std::string(mod) + "not together with " + with; return LSGPU_BAD_CONFIG; }
   if (h->md_on) { h->err = std::string(mod) + "not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
   if (h->sh_on) { h->err = std::string(mod) + "not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
+  if (h->cs_on) { h->err = std::string(mod) + "not together with CovarianceSamplingDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
   if (h->dof()) { h->err = std::string(mod) + "not together with PointToPlaneErrorMinimizer force2D / force4DOF (the covariance is that of the free 6-DOF step)"; return LSGPU_BAD_CONFIG; }
   if (!h->cov_on) h->quality_state = 0;
   h->cov_cfg = *cfg;
@@ -656,6 +680,23 @@ int lsgpu_icp_set_shadow(lsgpu_icp* h, const lsgpu_shadow_config* cfg) {
   }
   h->sh_cfg = *cfg;
   h->sh_on = true;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_set_cov_sampling(lsgpu_icp* h, const lsgpu_cov_sampling_config* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (!cfg) { h->cs_on = false; return LSGPU_OK; }
+  if (const char* why = lsgpu_cov_sampling_config_why(cfg)) { h->err = why; return LSGPU_BAD_CONFIG; }
+  if (cfg->reading_nb_sample == 0 && cfg->reference_nb_sample == 0) { h->cs_on = false; return LSGPU_OK; }
+  if (h->comm) { h->err = "CovarianceSamplingDataPointsFilter: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
+  if (h->cov_on) { h->err = "CovarianceSamplingDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
+  if (cfg->reading_nb_sample > 0 && !(h->normals_on && h->normals.reading_sn_knn > 0)) {
+    h->err = "CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (lsgpu_icp_set_normals with reading_sn_knn) first";
+    return LSGPU_BAD_CONFIG;
+  }
+  h->cs_cfg = *cfg;
+  h->cs_on = true;
   return LSGPU_OK;
 }
 
@@ -1403,6 +1444,10 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
   }
   if (h->sh_on) {
     h->err = "comm_init: the split-scan mode does not run ShadowDataPointsFilter";
+    return LSGPU_BAD_CONFIG;
+  }
+  if (h->cs_on) {
+    h->err = "comm_init: the split-scan mode does not run CovarianceSamplingDataPointsFilter";
     return LSGPU_BAD_CONFIG;
   }
   if (h->cuts_on) {
@@ -2406,6 +2451,146 @@ int lsgpu_icp_filter_shadow(lsgpu_icp* h, const float* xyz1, const float* normal
 
 }  // extern "C"
 
+// One sums pass of CovarianceSamplingDataPointsFilter on the current lane (lsgpu_cov_sampling.hip.h): its columns are in
+// h->pin->cs on return -- the host needs them to parametrise the next pass.
+template <int PASS>
+static int cov_sampling_sums(lsgpu_icp* h, const float4* src, const float* nrm3, int64_t n, const CsParams& q) {
+  const int nb = std::min(nblk(n), kCsBlocksMax);
+  hipStream_t st = h->lane.stream;
+  hipLaunchKernelGGL((k_cs_pass<PASS>), dim3(nb), dim3(256), 0, st, src, nrm3, (int)n, q, h->cs_partials.p);
+  hipLaunchKernelGGL(k_cs_final, dim3(1), dim3(1024), 0, st, (const double*)h->cs_partials.p, nb, PASS, h->cs_out.p);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h->pin->cs, h->cs_out.p, (size_t)cs_cols(PASS) * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  return LSGPU_OK;
+}
+
+// CovarianceSamplingDataPointsFilter on the current lane: src (n points, device, as given to the section) with the normals nrm3
+// (device, 3 floats per point) -> the nb chosen points, normals and indices in pick order at the front of out_pts / out_nrm /
+// out_ids (device, room for nb, not the inputs); 1 <= nb < n.  sums: the 32 doubles of lsgpu_icp_filter_cov_sampling.  Three
+// short waits for sums, one for the heads of the sorted lists; the gather is enqueued, not waited for.  ms (nullable): wall
+// time of the four phases -- sums, projections and sorts, heads download and walk, upload and gather (enqueue only).
+static int cov_sampling_run(lsgpu_icp* h, const float4* src, const float* nrm3, int64_t n, int64_t nb, int torque_norm,
+                            float4* out_pts, float* out_nrm, int32_t* out_ids, double sums[covs::kSums], double ms[4]) {
+  const double t0 = wall_ms();
+  hipStream_t st = h->lane.stream;
+  // (the kernels hold a point's index in an int: the entry's limit holds for a section of a compute too)
+  if (n > covs::kPointsMax) { h->err = "CovarianceSamplingDataPointsFilter: more than (2^31 - 16) / 6 points"; return LSGPU_BAD_ARG; }
+  HIPC(h->cs_partials.reserve((size_t)kCsBlocksMax * kCsStride));
+  HIPC(h->cs_out.reserve(kCsStride));
+  std::fill(sums, sums + covs::kSums, 0.0);
+  sums[covs::kSumN] = (double)n;
+  CsParams q{};
+  int rc = cov_sampling_sums<0>(h, src, nrm3, n, q);
+  if (rc) return rc;
+  std::memcpy(sums, h->pin->cs, 9 * sizeof(double));
+  if (!covs::finite_sums(sums)) { h->err = "CovarianceSamplingDataPointsFilter: a coordinate that is not finite"; return LSGPU_BAD_ARG; }
+  covs::centre(sums, n, q.c);
+  if (torque_norm == 1) {
+    if ((rc = cov_sampling_sums<1>(h, src, nrm3, n, q))) return rc;
+    sums[covs::kSumLen] = h->pin->cs[0];
+  }
+  const float L = covs::lnorm(torque_norm, sums, n);
+  if (!(L != 0.f) || !std::isfinite(L)) { h->err = "CovarianceSamplingDataPointsFilter: Lnorm is 0 or not finite (torqueNorm " + std::to_string(torque_norm) + ")"; return LSGPU_BAD_ARG; }
+  q.invL = 1.f / L;
+  if ((rc = cov_sampling_sums<2>(h, src, nrm3, n, q))) return rc;
+  std::memcpy(sums + covs::kSumC, h->pin->cs, 21 * sizeof(double));
+  if (!covs::finite_sums(sums)) { h->err = "CovarianceSamplingDataPointsFilter: a point or normal that is not finite"; return LSGPU_BAD_ARG; }
+  covs::Eig e;
+  covs::eigen(sums + covs::kSumC, e.X, nullptr);
+  const double t1 = wall_ms();
+
+  const int64_t m = nb;   // (< n)
+  HIPC(h->cs_mag.reserve(6 * (size_t)n));
+  HIPC(h->cs_heads.reserve(6 * (size_t)m));
+  HIPC(h->cs_heads_pin.reserve(6 * (size_t)m));
+  HIPC(h->cs_ids_pin.reserve((size_t)m));
+  HIPC(h->cs_ids.reserve((size_t)m));
+  HIPC(h->lane.scratch->keys.reserve(n));
+  HIPC(h->lane.scratch->vals.reserve(n));
+  hipLaunchKernelGGL(k_cs_project, dim3(nblk(n)), dim3(256), 0, st, src, nrm3, (int)n, q, e, h->cs_mag.p);
+  for (int k = 0; k < 6; ++k) {   // (sort_pairs may exchange the scratch's buffer pairs: the members are read anew every time)
+    hipLaunchKernelGGL(k_cs_keys, dim3(nblk(n)), dim3(256), 0, st, (const float*)h->cs_mag.p, (int)n, k, h->lane.scratch->keys.p,
+                       h->lane.scratch->vals.p);
+    if ((rc = sort_pairs(h, n, 32))) return rc;
+    hipLaunchKernelGGL(k_cs_heads, dim3(nblk(m)), dim3(256), 0, st, (const uint32_t*)h->lane.scratch->vals_alt.p, (int)m, (int)n,
+                       (const float*)h->cs_mag.p, h->cs_heads.p + (size_t)k * (size_t)m);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h->cs_heads_pin.p, h->cs_heads.p, 6 * (size_t)m * sizeof(covs::Head), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  const double t2 = wall_ms();
+  if (covs::walk(h->cs_heads_pin.p, m, n, nb, h->cs_ids_pin.p, h->cs_chosen) != nb) {
+    h->err = "CovarianceSamplingDataPointsFilter: a sorted list ran out before nbSample points were chosen";
+    return LSGPU_HIP_ERROR;
+  }
+  const double t3 = wall_ms();
+  HIPC(hipMemcpyAsync(h->cs_ids.p, h->cs_ids_pin.p, (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_cs_gather, dim3(nblk(nb)), dim3(256), 0, st, src, nrm3, (const uint32_t*)h->cs_ids.p, (int)nb, (int)n, out_pts,
+                     out_nrm, out_ids);
+  HIPC(hipGetLastError());
+  if (ms) { ms[0] = t1 - t0; ms[1] = t2 - t1; ms[2] = t3 - t2; ms[3] = wall_ms() - t3; }
+  return LSGPU_OK;
+}
+
+extern "C" {
+
+int lsgpu_icp_filter_cov_sampling(lsgpu_icp* h, const float* xyz1, const float* normals, int64_t n, int nb_sample, int torque_norm,
+                                  float* out_xyz1, float* out_normals, int32_t* out_ids, int64_t* n_out, double sums_out[32]) {
+  if (!h || !n_out) return LSGPU_BAD_ARG;
+  h->err.clear();
+  *n_out = 0;
+  if (n < 0 || n > covs::kPointsMax || (n > 0 && (!xyz1 || !normals || !out_xyz1 || !out_normals))) return LSGPU_BAD_ARG;
+  if (n > 0 && (static_cast<const void*>(out_xyz1) == static_cast<const void*>(xyz1) || static_cast<const void*>(out_normals) == static_cast<const void*>(normals))) {
+    h->err = "filter_cov_sampling: the outputs must not be the inputs";
+    return LSGPU_BAD_ARG;
+  }
+  if (!covs::nb_sample_ok(nb_sample)) { h->err = "CovarianceSamplingDataPointsFilter: nbSample must be in [1, 2147483632]"; return LSGPU_BAD_CONFIG; }
+  if (!covs::torque_norm_ok(torque_norm)) { h->err = "CovarianceSamplingDataPointsFilter: torqueNorm must be 0, 1 or 2"; return LSGPU_BAD_CONFIG; }
+  if (n == 0) { h->err = "filter_cov_sampling: no points to filter"; return LSGPU_NO_CONVERGENCE; }
+  HIPC(hipSetDevice(h->device));
+  if ((int64_t)nb_sample >= n) {   // the cloud passes unchanged, nothing is computed
+    HIPC(hipMemcpyAsync(out_xyz1, xyz1, (size_t)n * 16, hipMemcpyDefault, h->stream));
+    HIPC(hipMemcpyAsync(out_normals, normals, (size_t)n * 12, hipMemcpyDefault, h->stream));
+    if (out_ids) {
+      HIPC(h->cs_ids_pin.reserve((size_t)n));
+      for (int64_t i = 0; i < n; ++i) h->cs_ids_pin.p[i] = (uint32_t)i;
+      HIPC(hipMemcpyAsync(out_ids, h->cs_ids_pin.p, (size_t)n * 4, hipMemcpyDefault, h->stream));
+    }
+    HIPC(hipStreamSynchronize(h->stream));
+    if (sums_out) { std::fill(sums_out, sums_out + covs::kSums, 0.0); sums_out[covs::kSumN] = (double)n; }
+    *n_out = n;
+    return LSGPU_OK;
+  }
+  const float4* src = nullptr; const float* nsrc = nullptr;
+  int rc = stage_points(h, xyz1, n, h->flt_in, &src);
+  if (!rc) rc = stage_in(h, normals, (size_t)3 * n, h->cs_nrm_in, &nsrc);
+  if (rc) return rc;
+  const size_t nb = (size_t)nb_sample;
+  OutStage<float4> ox; OutStage<float> on; OutStage<int32_t> oi;
+  if ((rc = ox.open(h, out_xyz1, h->cs_pts_out, nb))) return rc;
+  if ((rc = on.open(h, out_normals, h->cs_nrm_out, 3 * nb))) return rc;
+  if (out_ids) { if ((rc = oi.open(h, out_ids, h->cs_ids_out, nb))) return rc; }
+  else { HIPC(h->cs_ids_out.reserve(nb)); oi.p = h->cs_ids_out.p; }
+  double sums[covs::kSums];
+  if ((rc = cov_sampling_run(h, src, nsrc, n, (int64_t)nb, torque_norm, ox.p, on.p, oi.p, sums, h->cs_ms))) return rc;
+  if ((rc = ox.copy_back(h, nb))) return rc;
+  if ((rc = on.copy_back(h, 3 * nb))) return rc;
+  if (out_ids && (rc = oi.copy_back(h, nb))) return rc;
+  HIPC(hipStreamSynchronize(h->stream));
+  if (sums_out) std::memcpy(sums_out, sums, sizeof sums);
+  *n_out = (int64_t)nb;
+  return LSGPU_OK;
+}
+
+int lsgpu_icp_cov_sampling_phase_ms(lsgpu_icp* h, double ms[4]) {
+  if (!h || !ms) return LSGPU_BAD_ARG;
+  std::memcpy(ms, h->cs_ms, sizeof h->cs_ms);
+  return LSGPU_OK;
+}
+
+}  // extern "C"
+
 // lsgpu_icp_filter_reference_normals, with the densities of keepDensities 1 if the caller asks for them
 static int filter_reference_normals_run(lsgpu_icp* h, const float* xyz1, int64_t n, int knn, float* out_normals, int32_t* out_ids,
                                         float* out_d2, float* out_densities);
@@ -2668,6 +2853,10 @@ struct ComputeRun {
   // lsgpu_icp_set_shadow: ShadowDataPointsFilter on the reference (sh_ref; sh_sn: behind SurfaceNormalDataPointsFilter without
   // the thinning -- the md route without it; sh_ref_normals: somebody behind the module reads the normals) / on the reading
   bool sh_ref = false, sh_sn = false, sh_ref_normals = false, sh_rd = false;
+  // lsgpu_icp_set_cov_sampling: CovarianceSamplingDataPointsFilter as the last thinning step of the reference (cs_ref; cs_sn:
+  // behind SurfaceNormalDataPointsFilter alone -- the sh_sn route with the normals copied out in the cloud's order;
+  // cs_ref_normals: somebody behind the module reads the normals) / of the reading
+  bool cs_ref = false, cs_sn = false, cs_ref_normals = false, cs_rd = false;
   const lsgpu_normals_config* nc = nullptr; double t0 = 0.0;
   DrawAhead draws; std::thread uploader; hipError_t upload_err = hipSuccess;
   bool overlap_upload = false, side_used = false;   // the copy stream / the side stream has work of this call
@@ -2719,6 +2908,16 @@ struct ComputeRun {
       // behind SurfaceNormalDataPointsFilter: the normals on the whole reference's grid, whoever reads them afterwards; the kept
       // cloud carries them (flt_nrm), nothing is computed on the second grid
       if (sh_ref && !md && chain->sn_knn != 0) { sh_sn = true; sh_ref_normals = ref_normals; ref_normals = false; }
+    }
+    if (h->cs_on) {
+      cs_rd = h->cs_cfg.reading_nb_sample > 0; cs_ref = h->cs_cfg.reference_nb_sample > 0;
+      if (cs_rd && !rd_normals) { h->err = "compute: CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn)"; return LSGPU_BAD_CONFIG; }
+      if (cs_ref && chain->ssn_knn == 0 && chain->sn_knn == 0) { h->err = "compute: CovarianceSamplingDataPointsFilter on the reference needs the normals of a reference filter (ssn_knn or sn_knn)"; return LSGPU_BAD_CONFIG; }
+      // the module reads the normals of whatever stands in front of it; who reads them behind it decides whether they go on
+      if (cs_ref && sh_ref && (md || sh_sn)) { cs_ref_normals = sh_ref_normals; sh_ref_normals = true; }
+      else if (cs_ref && md) { cs_ref_normals = md_normals; md_normals = true; }
+      else if (cs_ref && chain->sn_knn != 0) { cs_sn = true; cs_ref_normals = ref_normals; ref_normals = false; }
+      else if (cs_ref) cs_ref_normals = true;   // (the sampling filter's normals always travel with its points)
     }
     if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
     if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
@@ -2832,6 +3031,33 @@ struct ComputeRun {
       if (rc) return rc;
       if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
       ref_pts = h->sh_ref.p; ref_nrm = (md && !sh_ref_normals) ? nullptr : h->sh_nrm.p;
+    }
+    if (cs_sn && h->cs_cfg.reference_nb_sample >= nrc) {
+      // the section passes unchanged: what a handle without the module does -- one grid, the normals computed on it
+      cs_sn = false; cs_ref = false; ref_normals = cs_ref_normals;
+    }
+    if (cs_sn) {
+      // the sh_sn route: the whole reference's grid (no direction index of it), the normals on it, copied out in the cloud's order
+      int rc = ref_build_front(h, reinterpret_cast<const float*>(src), nullptr, nrc);
+      if (!rc) rc = ref_build_back(h, nrc);
+      if (rc) return rc;
+      HIPC(h->cs_sn_nrm.reserve(3 * nrc));
+      rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
+      if (rc) return rc;
+      hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nrc)), dim3(256), 0, h->stream, h->pts.p, (int)nrc, h->nrm.p, h->cs_sn_nrm.p);
+      HIPC(hipGetLastError());
+      ref_pts = src; ref_nrm = h->cs_sn_nrm.p; nrf = nrc;
+    }
+    if (cs_ref) {   // the section's last thinning step: fewer points than nbSample pass unchanged
+      const int64_t nb = h->cs_cfg.reference_nb_sample;
+      if (nb < nrf) {
+        HIPC(h->cs_ref.reserve(nb)); HIPC(h->cs_ref_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
+        double sums[covs::kSums];
+        const int rc = cov_sampling_run(h, ref_pts, ref_nrm, nrf, nb, h->cs_cfg.reference_torque_norm, h->cs_ref.p, h->cs_ref_nrm.p, h->cs_pick.p, sums, nullptr);
+        if (rc) { h->nr = 0; return rc; }
+        ref_pts = h->cs_ref.p; ref_nrm = h->cs_ref_nrm.p; nrf = nb;
+      }
+      if (!cs_ref_normals) ref_nrm = nullptr;
     }
     // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
     // (not with cut modules in front of RandomSampling: reading_count_wait commits then)
@@ -2948,6 +3174,15 @@ struct ComputeRun {
       if (rc) return rc;
       if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
       rd_dev = h->sh_rd.p;
+    }
+    if (cs_rd && h->cs_cfg.reading_nb_sample < nqf) {   // behind the normals, their orientation and the Shadow pass
+      const int64_t nb = h->cs_cfg.reading_nb_sample;
+      HIPC(h->cs_rd.reserve(nb)); HIPC(h->cs_rd_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
+      double sums[covs::kSums];
+      rc = cov_sampling_run(h, rd_dev, h->rd_nrm.p, nqf, nb, h->cs_cfg.reading_torque_norm, h->cs_rd.p, h->cs_rd_nrm.p, h->cs_pick.p, sums, nullptr);
+      if (rc) { h->nr = 0; return rc; }   // (the grid the handle holds is the reading's: no reference to align against)
+      HIPC(hipMemcpyAsync(h->rd_nrm.p, h->cs_rd_nrm.p, (size_t)nb * 12, hipMemcpyDeviceToDevice, h->stream));   // (where the loop reads them)
+      rd_dev = h->cs_rd.p; nqf = nb;
     }
     extras.reading_normals = true;
     return LSGPU_OK;

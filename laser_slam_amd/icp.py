@@ -81,7 +81,8 @@ class IcpHandle:
 
     def __init__(self, cfg: Optional[IcpConfig] = None, device: int = 0, error_minimizer=None, matcher_knn=None,
                  matcher_max_dist=None, outlier_max_dist=None, outlier_min_dist=None, outlier_median_factor=None,
-                 robust=None, normals=None, covariance=None, cuts=None, max_density=None, shadow=None, motion=None):
+                 robust=None, normals=None, covariance=None, cuts=None, max_density=None, shadow=None, motion=None,
+                 cov_sampling=None):
         """error_minimizer: None (cfg's), a module name ("PointToPlaneErrorMinimizer" / "PointToPointErrorMinimizer")
         or an _lib.MINIMIZER_* value.  matcher_knn: None (cfg's) or KDTreeMatcher's knn, 1.._lib.MATCHER_KNN_MAX (k >= 2:
         every reading point is paired with its k nearest reference points).  matcher_max_dist: KDTreeMatcher's maxDist;
@@ -98,7 +99,10 @@ class IcpHandle:
         (a dict with those keys or an _lib.ShadowCfg too) -- lsgpu_icp_set_shadow (the reading's needs `normals` with
         reading_sn_knn).  motion: None, or PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (a
         MotionConfig, a dict of its fields, or an _lib.MotionCfg) -- lsgpu_icp_set_motion (given last: it refuses a handle with
-        modules the constrained steps do not cover)."""
+        modules the constrained steps do not cover).  cov_sampling: None, or CovarianceSamplingDataPointsFilter's
+        ((reading_nb_sample, reading_torque_norm), (reference_nb_sample, reference_torque_norm)), None for a side without the
+        module (a dict of lsgpu_cov_sampling_config's fields or an _lib.CovSamplingCfg too) -- lsgpu_icp_set_cov_sampling (the
+        reading's needs `normals` with reading_sn_knn)."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -150,6 +154,9 @@ class IcpHandle:
         self.shadow = None
         if shadow is not None:
             self.set_shadow(shadow)
+        self.cov_sampling = None
+        if cov_sampling is not None:
+            self.set_cov_sampling(cov_sampling)
         self.motion = None
         if motion is not None:
             self.set_motion(motion)
@@ -162,6 +169,17 @@ class IcpHandle:
         if rc != _lib.OK:
             _raise(rc, "lsgpu_icp_set_motion", self._h)
         self.motion = _motion_config(mc) if mc is not None and (mc.dof or mc.bound) else None
+
+    def set_cov_sampling(self, cov_sampling):
+        """lsgpu_icp_set_cov_sampling: CovarianceSamplingDataPointsFilter as the last thinning step of the reading's / the
+        reference's section of this handle's compute calls.  cov_sampling: ((reading_nb_sample, reading_torque_norm),
+        (reference_nb_sample, reference_torque_norm)) with None for a side without the module, a dict of
+        lsgpu_cov_sampling_config's fields or an _lib.CovSamplingCfg; None: off."""
+        cc = cov_sampling_cfg(cov_sampling) if cov_sampling is not None else None
+        rc = _lib.lib().lsgpu_icp_set_cov_sampling(self._h, C.byref(cc) if cc is not None else None)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_cov_sampling", self._h)
+        self.cov_sampling = _cov_sampling_pairs(cc) if cc is not None else None
 
     def set_shadow(self, shadow):
         """lsgpu_icp_set_shadow: ShadowDataPointsFilter behind the normals of the reading's / the reference's section of this
@@ -195,6 +213,45 @@ class IcpHandle:
         if rc != _lib.OK:
             _raise(rc, "lsgpu_icp_filter_shadow", self._h)
         return o[:k.value], nr[:k.value]
+
+    def filter_cov_sampling(self, xyz1, normals, nb_sample: int = 5000, torque_norm: int = 1, return_sums: bool = False):
+        """CovarianceSamplingDataPointsFilter on the GPU (lsgpu_icp_filter_cov_sampling) -> (xyz1', normals', ids) in pick
+        order, with return_sums also the 32 sums the device formed (numpy float64).  torch CUDA inputs give torch CUDA outputs
+        (ids int32), anything else numpy."""
+        p, _k, n = _as_f32(xyz1, 4)
+        q, _k3, m = _as_f32(normals, 3)
+        if m != n:
+            raise ValueError(f"{n} points, {m} normals")
+        nb = _c_int(nb_sample)
+        room = max(min(nb, n), 1)
+        if _is_torch(xyz1) and xyz1.is_cuda and _is_torch(normals) and normals.is_cuda:
+            o = torch.empty((room, 4), dtype=torch.float32, device=xyz1.device)
+            nr = torch.empty((room, 3), dtype=torch.float32, device=xyz1.device)
+            ids = torch.empty((room,), dtype=torch.int32, device=xyz1.device)
+            torch.cuda.synchronize()
+            po, pn, pi = o.data_ptr(), nr.data_ptr(), ids.data_ptr()
+        else:
+            o = np.empty((room, 4), np.float32)
+            nr = np.empty((room, 3), np.float32)
+            ids = np.empty((room,), np.int32)
+            po, pn, pi = o.ctypes.data, nr.ctypes.data, ids.ctypes.data
+        sums = np.zeros(32, np.float64)
+        k = C.c_int64(0)
+        rc = _lib.lib().lsgpu_icp_filter_cov_sampling(self._h, p, q, n, nb, _c_int(torque_norm), po, pn, pi, C.byref(k),
+                                                      sums.ctypes.data)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_filter_cov_sampling", self._h)
+        out = (o[:k.value], nr[:k.value], ids[:k.value])
+        return out + (sums,) if return_sums else out
+
+    def cov_sampling_phase_ms(self):
+        """Wall time in ms of the four phases of this handle's last filter_cov_sampling (lsgpu_icp_cov_sampling_phase_ms):
+        sums, projections + sorts + heads download, host walk, picks upload + gather (enqueue)."""
+        ms = (C.c_double * 4)()
+        rc = _lib.lib().lsgpu_icp_cov_sampling_phase_ms(self._h, ms)
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_cov_sampling_phase_ms", self._h)
+        return [float(x) for x in ms]
 
     def set_max_density(self, max_density=10.0):
         """lsgpu_icp_set_max_density: MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 in the
@@ -874,6 +931,86 @@ def shadow(xyz1, normals, eps: float = 0.1):
     return o[:k.value].copy(), nr[:k.value].copy()
 
 
+def _c_int(v) -> int:
+    """An integer parameter on its way into a C int: a value that is no integer is refused here, one out of an int's range is
+    clamped to a value the library refuses all the same."""
+    if int(v) != v:
+        raise ValueError(f"expected an integer, got {v!r}")
+    return min(max(int(v), -(2 ** 31)), 2 ** 31 - 1)
+
+
+def cov_sampling(xyz1, normals, nb_sample: int = 5000, torque_norm: int = 1, sums=None, return_sums: bool = False):
+    """CovarianceSamplingDataPointsFilter on the host (lsgpu_filter_cov_sampling) -> (xyz1', normals', ids) in pick order, with
+    return_sums also the 32 sums used.  sums: None -- the twin adds its own, sequentially -- or the 32 doubles of
+    IcpHandle.filter_cov_sampling(return_sums=True): fed those, the twin is the device path's checker, bit for bit."""
+    a = np.ascontiguousarray(xyz1, np.float32)
+    b = np.ascontiguousarray(normals, np.float32)
+    if a.ndim != 2 or a.shape[1] != 4 or b.ndim != 2 or b.shape[1] != 3 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"expected (N,4) points and (N,3) normals, got {a.shape} and {b.shape}")
+    n = a.shape[0]
+    nb = _c_int(nb_sample)
+    room = max(min(nb, n), 1)
+    o = np.empty((room, 4), np.float32)
+    nr = np.empty((room, 3), np.float32)
+    ids = np.empty((room,), np.int32)
+    s_in = None
+    if sums is not None:
+        s_in = np.ascontiguousarray(sums, np.float64)
+        if s_in.shape != (32,):
+            raise ValueError(f"expected 32 sums, got {s_in.shape}")
+    s_out = np.zeros(32, np.float64)
+    k = C.c_int64(0)
+    rc = _lib.lib().lsgpu_filter_cov_sampling(a.ctypes.data if n else None, b.ctypes.data if n else None, n, nb, _c_int(torque_norm),
+                                              s_in.ctypes.data if s_in is not None else None, o.ctypes.data, nr.ctypes.data,
+                                              ids.ctypes.data, C.byref(k), s_out.ctypes.data)
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_filter_cov_sampling")
+    out = (o[:k.value].copy(), nr[:k.value].copy(), ids[:k.value].copy())
+    return out + (s_out,) if return_sums else out
+
+
+def cov_sampling_eigen(C21):
+    """lsgpu_cov_sampling_eigen: the cyclic Jacobi of CovarianceSamplingDataPointsFilter on the upper triangle (21 doubles, row
+    major) of a symmetric 6x6 matrix -> (X, values): X (6, 6) float32 with the k-th eigenvector in column k, values ascending."""
+    c = np.ascontiguousarray(C21, np.float64)
+    if c.shape != (21,):
+        raise ValueError(f"expected 21 values, got {c.shape}")
+    X = np.empty((6, 6), np.float32)
+    w = np.empty(6, np.float64)
+    rc = _lib.lib().lsgpu_cov_sampling_eigen(c.ctypes.data, X.ctypes.data, w.ctypes.data)
+    if rc != _lib.OK:
+        _raise(rc, "lsgpu_cov_sampling_eigen")
+    return X, w
+
+
+def cov_sampling_cfg(c) -> "_lib.CovSamplingCfg":
+    """((reading_nb_sample, reading_torque_norm) or None, (reference_nb_sample, reference_torque_norm) or None) / a dict of
+    lsgpu_cov_sampling_config's fields / an _lib.CovSamplingCfg -> _lib.CovSamplingCfg (the values are checked by the library)."""
+    if isinstance(c, _lib.CovSamplingCfg):
+        return c
+    out = _lib.CovSamplingCfg()
+    _lib.lib().lsgpu_cov_sampling_config_default(C.byref(out))
+    if isinstance(c, dict):
+        for k, v in c.items():
+            if k not in ("reading_nb_sample", "reference_nb_sample", "reading_torque_norm", "reference_torque_norm"):
+                raise ValueError(f"lsgpu_cov_sampling_config has no field {k}")
+            setattr(out, k, _c_int(v))
+        return out
+    rd, ref = c
+    if rd is not None:
+        out.reading_nb_sample, out.reading_torque_norm = _c_int(rd[0]), _c_int(rd[1])
+    if ref is not None:
+        out.reference_nb_sample, out.reference_torque_norm = _c_int(ref[0]), _c_int(ref[1])
+    return out
+
+
+def _cov_sampling_pairs(cc):
+    """_lib.CovSamplingCfg -> ((nbSample, torqueNorm) or None of the reading, the same of the reference), None: no module."""
+    rd = (int(cc.reading_nb_sample), int(cc.reading_torque_norm)) if cc.reading_nb_sample > 0 else None
+    ref = (int(cc.reference_nb_sample), int(cc.reference_torque_norm)) if cc.reference_nb_sample > 0 else None
+    return (rd, ref) if rd or ref else None
+
+
 def shadow_cfg(s) -> "_lib.ShadowCfg":
     """(reading_eps, reference_eps) / a dict with those keys / an _lib.ShadowCfg -> _lib.ShadowCfg (None or a negative eps: -1)."""
     if isinstance(s, _lib.ShadowCfg):
@@ -1200,6 +1337,19 @@ class ChainConfig:
             self.extra["shadow"] = (None if value[0] is None else float(value[0]), None if value[1] is None else float(value[1]))
 
     @property
+    def cov_sampling(self):
+        """CovarianceSamplingDataPointsFilter of the two filter sections, ((nbSample, torqueNorm) or None of the reading, the
+        same of the reference); None: no such module.  Kept in `extra`, like `robust`."""
+        return self.extra.get("cov_sampling")
+
+    @cov_sampling.setter
+    def cov_sampling(self, value):
+        if value is None:
+            self.extra.pop("cov_sampling", None)
+        else:
+            self.extra["cov_sampling"] = tuple(None if v is None else (int(v[0]), int(v[1])) for v in value)
+
+    @property
     def motion(self) -> Optional["MotionConfig"]:
         """PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (a MotionConfig); None: neither.
         Kept in `extra`, like `robust`."""
@@ -1338,6 +1488,16 @@ def chain_load_shadow(doc):
     return rc, why.value.decode(), out
 
 
+def chain_load_cov_sampling(doc):
+    """lsgpu_chain_load_cov_sampling on the same document: CovarianceSamplingDataPointsFilter's parameters of its two filter
+    sections -> (return code, reason of a refusal, _lib.CovSamplingCfg).  Same rules, same verdict and same text as chain_load."""
+    arr, n, _keep = _yaml_modules(doc)
+    out = _lib.CovSamplingCfg()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load_cov_sampling(arr, n, C.byref(out), why, len(why))
+    return rc, why.value.decode(), out
+
+
 def chain_load_motion(doc):
     """lsgpu_chain_load_motion on the same document: force2D / force4DOF of PointToPlaneErrorMinimizer and
     BoundTransformationChecker -> (return code, reason of a refusal, _lib.MotionCfg).  Same rules, verdict and text as chain_load."""
@@ -1353,7 +1513,7 @@ def _f32(x) -> float:
     return float(str(np.float32(x)))
 
 
-def _chain_config(lc, cuts=None, shadow=None, motion=None) -> "ChainConfig":
+def _chain_config(lc, cuts=None, shadow=None, motion=None, cov_sampling=None) -> "ChainConfig":
     """_lib.LoadedChain (and the _lib.ChainCuts of the same document, if it has cut modules) -> ChainConfig"""
     i, c = lc.icp, lc.chain
     name = {v: k for k, v in _MINIMIZERS.items()}[i.error_minimizer]
@@ -1384,6 +1544,8 @@ def _chain_config(lc, cuts=None, shadow=None, motion=None) -> "ChainConfig":
         ch.shadow = tuple(_f32(e) if e >= 0 else None for e in (shadow.reading_eps, shadow.reference_eps))
     if motion is not None and (motion.dof or motion.bound):
         ch.motion = _motion_config(motion)
+    if cov_sampling is not None and _cov_sampling_pairs(cov_sampling):
+        ch.cov_sampling = _cov_sampling_pairs(cov_sampling)
     return ch
 
 
@@ -1435,7 +1597,10 @@ class ICP:
         rc, why, motion = chain_load_motion(doc)                # (likewise: force2D / force4DOF, BoundTransformationChecker)
         if rc != _lib.OK:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        self.chain = _chain_config(loaded, cuts, shadow, motion)
+        rc, why, cov_sampling = chain_load_cov_sampling(doc)    # (likewise: CovarianceSamplingDataPointsFilter)
+        if rc != _lib.OK:
+            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+        self.chain = _chain_config(loaded, cuts, shadow, motion, cov_sampling)
         self._handle = None
 
     def _ensure_handle(self) -> IcpHandle:
@@ -1453,7 +1618,7 @@ class ICP:
                                      robust=self.chain.robust, normals=self.chain.normals,
                                      covariance=self.chain.covariance, cuts=self.chain.cuts,
                                      max_density=self.chain.max_density, shadow=self.chain.shadow,
-                                     motion=self.chain.motion)
+                                     motion=self.chain.motion, cov_sampling=self.chain.cov_sampling)
         return self._handle
 
     @property
