@@ -27,6 +27,7 @@
 #include "lsgpu_grid.hip.h"
 #include "lsgpu_tuning.h"
 #include "lsgpu_policy.h"
+#include "lsgpu_section_plan.h"
 #include "lsgpu_knn.hip.h"
 #include "lsgpu_knn_k.hip.h"
 #include "lsgpu_snf.hip.h"
@@ -378,7 +379,7 @@ struct lsgpu_icp {
   lsgpu_cov_sampling_config cs_cfg{};
   DevBuf<float4> cs_ref, cs_rd;         // the chosen points of the reference / the reading ...
   DevBuf<float> cs_ref_nrm, cs_rd_nrm;  // ... and their normals
-  DevBuf<float> cs_sn_nrm;              // behind SurfaceNormalDataPointsFilter alone: the whole reference's normals in its order
+  DevBuf<float> cs_whole_nrm;           // behind SurfaceNormalDataPointsFilter alone: the whole reference's normals in its order
   DevBuf<int32_t> cs_pick;              // the picks of a section (not read behind the gather)
   DevBuf<double> cs_partials, cs_out;   // kCsBlocksMax x kCsStride, kCsStride
   DevBuf<float> cs_mag;                 // the six magnitudes of every point
@@ -2846,22 +2847,13 @@ struct ComputeRun {
   // lsgpu_icp_compute_clouds_upload: the reading's H2D goes into its slot instead of the staging buffer, and the caller
   // learns whether it went out (it reads the flag after the return: the uploader is joined by then)
   float4* const upload_into; bool* const upload_enqueued;
-  bool ref_filter = false, ref_normals = false, rd_normals = false, side = false;   // what the chain and the handle ask for
-  // lsgpu_icp_set_max_density: SurfaceNormalDataPointsFilter with densities on the whole reference, then the thinning pass; the
-  // thinned cloud and its normals go on as the sampling filter's do (md_normals: somebody reads the normals)
-  bool md = false, md_normals = false;
-  // lsgpu_icp_set_shadow: ShadowDataPointsFilter on the reference (sh_ref; sh_sn: behind SurfaceNormalDataPointsFilter without
-  // the thinning -- the md route without it; sh_ref_normals: somebody behind the module reads the normals) / on the reading
-  bool sh_ref = false, sh_sn = false, sh_ref_normals = false, sh_rd = false;
-  // lsgpu_icp_set_cov_sampling: CovarianceSamplingDataPointsFilter as the last thinning step of the reference (cs_ref; cs_sn:
-  // behind SurfaceNormalDataPointsFilter alone -- the sh_sn route with the normals copied out in the cloud's order;
-  // cs_ref_normals: somebody behind the module reads the normals) / of the reading
-  bool cs_ref = false, cs_sn = false, cs_ref_normals = false, cs_rd = false;
+  section::Plan plan;   // what the sections are made of (lsgpu_section_plan.h): check() asks, filter_reference() settles it
   const lsgpu_normals_config* nc = nullptr; double t0 = 0.0;
   DrawAhead draws; std::thread uploader; hipError_t upload_err = hipSuccess;
   bool overlap_upload = false, side_used = false;   // the copy stream / the side stream has work of this call
-  const float4 *src = nullptr, *ref_pts = nullptr; float* ref_nrm = nullptr;   // the reference on the device: as given, as the grid gets it
-  const float4 *rd_src = nullptr, *rd_dev = nullptr; int64_t nrf = 0, nqf = 0;       // the reading: as given, as the loop gets it; points kept
+  struct Cloud { const float4* pts; float* nrm; int64_t n; };   // points, their normals beside them (or nullptr), how many
+  const float4* src = nullptr; Cloud ref{};   // the reference on the device: as given, as the grid gets it
+  const float4 *rd_src = nullptr, *rd_dev = nullptr; int64_t nqf = 0;   // the reading: as given, as the loop gets it; points kept
   AlignExtras extras{};   // what finish() tells the align
   // lsgpu_icp_set_chain_cuts: the sections' cut modules.  rd_pre_cuts: some stand in front of RandomSampling, so the number of
   // draws the reading consumes is the number of points that reach it -- known when the pass's totals are on the host
@@ -2881,56 +2873,30 @@ struct ComputeRun {
       h->err = "compute: one reference filter, ssn_knn or sn_knn in [3, 32] (none only with the point-to-point minimizer)";
       return LSGPU_BAD_CONFIG;
     }
-    ref_filter = chain->ssn_knn != 0;
-    // SurfaceNormalDataPointsFilter keeps every point and draws nothing: the reference goes to the grid build as given and
-    // the normals are computed on the grid it builds (a point-to-point handle reads none: skipped)
-    const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;   // (its residuals need the normals)
-    // lsgpu_icp_set_normals: the angle filter reads the reference normals whatever the minimizer; the reading's normals are
-    // computed on the handle's grid BEFORE the reference takes it (rd_normals), which rules the side stream out
     nc = h->normals_on ? &h->normals : nullptr;
+    // who reads the reference normals behind the section: the minimizer, the robust filter's residuals, the angle filter
+    const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
     const bool na_filter = nc && nc->max_angle >= 0.f;
-    rd_normals = nc && nc->reading_sn_knn > 0;
     if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0) {
       h->err = "compute: SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter need the normals of a reference filter";
       return LSGPU_BAD_CONFIG;
     }
-    ref_normals = chain->sn_knn != 0 && (h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter);
-    if (h->md_on) {
-      if (const char* why = lsgpu_max_density_config_why(&h->md_cfg, chain->sn_knn)) { h->err = std::string("compute: ") + why; return LSGPU_BAD_CONFIG; }
-      // the normals travel with the thinned cloud (flt_nrm), as the sampling filter's: nothing is computed on the second grid
-      md = true; md_normals = ref_normals; ref_normals = false;
-    }
-    if (h->sh_on) {
-      sh_rd = h->sh_cfg.reading_eps >= 0.f; sh_ref = h->sh_cfg.reference_eps >= 0.f;
-      if (sh_rd && !rd_normals) { h->err = "compute: ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn)"; return LSGPU_BAD_CONFIG; }
-      if (sh_ref && chain->ssn_knn == 0 && chain->sn_knn == 0) { h->err = "compute: ShadowDataPointsFilter on the reference needs the normals of a reference filter (ssn_knn or sn_knn)"; return LSGPU_BAD_CONFIG; }
-      if (sh_ref && md) { sh_ref_normals = md_normals; md_normals = true; }   // (the thinning gathers the normals for the module)
-      // behind SurfaceNormalDataPointsFilter: the normals on the whole reference's grid, whoever reads them afterwards; the kept
-      // cloud carries them (flt_nrm), nothing is computed on the second grid
-      if (sh_ref && !md && chain->sn_knn != 0) { sh_sn = true; sh_ref_normals = ref_normals; ref_normals = false; }
-    }
-    if (h->cs_on) {
-      cs_rd = h->cs_cfg.reading_nb_sample > 0; cs_ref = h->cs_cfg.reference_nb_sample > 0;
-      if (cs_rd && !rd_normals) { h->err = "compute: CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn)"; return LSGPU_BAD_CONFIG; }
-      if (cs_ref && chain->ssn_knn == 0 && chain->sn_knn == 0) { h->err = "compute: CovarianceSamplingDataPointsFilter on the reference needs the normals of a reference filter (ssn_knn or sn_knn)"; return LSGPU_BAD_CONFIG; }
-      // the module reads the normals of whatever stands in front of it; who reads them behind it decides whether they go on
-      if (cs_ref && sh_ref && (md || sh_sn)) { cs_ref_normals = sh_ref_normals; sh_ref_normals = true; }
-      else if (cs_ref && md) { cs_ref_normals = md_normals; md_normals = true; }
-      else if (cs_ref && chain->sn_knn != 0) { cs_sn = true; cs_ref_normals = ref_normals; ref_normals = false; }
-      else if (cs_ref) cs_ref_normals = true;   // (the sampling filter's normals always travel with its points)
-    }
+    section::Inputs in;
+    in.module = chain->ssn_knn != 0 ? section::Module::Sampling : chain->sn_knn != 0 ? section::Module::SurfaceNormal : section::Module::None;
+    in.normals_read = h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter;
+    in.max_density = h->md_on;
+    in.ref_shadow = h->sh_on && h->sh_cfg.reference_eps >= 0.f; in.ref_cov_sampling = h->cs_on && h->cs_cfg.reference_nb_sample > 0;
+    in.rd_normals = nc && nc->reading_sn_knn > 0;
+    in.rd_shadow = h->sh_on && h->sh_cfg.reading_eps >= 0.f; in.rd_cov_sampling = h->cs_on && h->cs_cfg.reading_nb_sample > 0;
+    in.comm = h->comm != nullptr; in.side_switch = tuning().side_stream;
+    plan = section::plan(in);
+    if (plan.refusal) { h->err = plan.refusal; return LSGPU_BAD_CONFIG; }
     if (chain->seed >= 0) DrawStream::global().take(chain->seed, 0, nullptr);
     if (nq <= 0 || nr <= 0 || !reading_xyz1 || !reference_xyz1) { h->err = "compute: empty cloud"; return LSGPU_NO_CONVERGENCE; }
     if (nq > 0x7FFFFFF0ll || nr > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
     if (nr < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
     HIPC(hipSetDevice(h->device));
     t0 = wall_ms();
-    // steps 2-4.  The grid build (steps 2-3, h->stream) and the reading's side -- its filter (step 4) and the queries' order
-    // (the first part of step 5) -- do not depend on each other: the latter goes to a second stream with its own sort scratch.
-    // Both are chains of short launches that leave most of the chip idle; side by side the shorter one disappears
-    // (LSGPU_NO_SIDE_STREAM: one after the other).
-    // (md: the reading's first draw is known only after the thinning pass has counted the dense points -- one stream)
-    side = tuning().side_stream && !h->comm && !rd_normals && !md;
     cuts = h->cuts_on ? &h->cuts : nullptr;
     rd_rs = chain->reading_prob >= 0.f;
     rd_cuts = cuts && cuts->n_reading > 0; ref_cuts = cuts && cuts->n_reference > 0;
@@ -2940,7 +2906,7 @@ struct ComputeRun {
 
   int start_uploads() {
     // the draws of both filters, produced on a helper thread from now on: at most one per reference point, then one per reading point
-    const size_t ref_draws = ref_filter || md ? (size_t)nr : (size_t)0;   // (md: one per dense point)
+    const size_t ref_draws = plan.draws_per_reference_point() ? (size_t)nr : (size_t)0;   // (MaxDensity: one per dense point)
     int rc = draws.begin(h, -1, ref_draws + (chain->reading_prob < 0.f ? (size_t)0 : (size_t)nq), ref_draws);   // (the reference filter's share first)
     if (!rc) rc = stage_points(h, reference_xyz1, nr, h->flt_in, &src);   // (step 1 starts here)
     if (rc) return rc;
@@ -2973,6 +2939,60 @@ struct ComputeRun {
     return LSGPU_OK;
   }
 
+  // the section emptied its cloud: no reference to align against
+  int left_points(int64_t n) {
+    if (n > 0) return LSGPU_OK;
+    h->err = "compute: the reference filter left no point"; h->nr = 0;
+    return LSGPU_NO_CONVERGENCE;
+  }
+
+  // SurfaceNormalDataPointsFilter on a whole cloud: its grid (no direction index of it) and the normals on it, in the grid's
+  // order (h->nrm); `dens`: the densities of keepDensities 1 beside them
+  int normals_on_whole_cloud(const float4* pts, int64_t n, int knn, DevBuf<float>* dens) {
+    int rc = ref_build_front(h, reinterpret_cast<const float*>(pts), nullptr, n);
+    if (!rc) rc = ref_build_back(h, n);
+    if (rc) return rc;
+    if (dens) HIPC(dens->reserve(n));
+    return snf_device(h, knn, nullptr, nullptr, dens ? dens->p : nullptr);
+  }
+
+  // A thinning stage takes the section's cloud and leaves what it kept; the normals are those of the stage in front of it
+  // (nullptr behind a whole cloud's grid: read in the grid's order) and go on if the plan says that somebody reads them.
+  // MaxDensity: the draws of the dense points are the section's, the reading's start behind them
+  int max_density_stage(Cloud& c, bool emits) {
+    HIPC(h->flt_ref.reserve(c.n)); HIPC(h->flt_nrm.reserve(3 * c.n));
+    int rc = draws.ready((size_t)nr);
+    int64_t n_dense = 0;
+    if (!rc) rc = max_density_enqueue(h, c.pts, c.n, h->dens.p, h->md_cfg.max_density, h->ssn_draws.p + draws.used, emits, h->flt_ref.p, h->flt_nrm.p);
+    if (!rc) rc = max_density_wait(h, &n_dense, &c.n);
+    if (rc) return rc;
+    draws.used += (size_t)n_dense;
+    c.pts = h->flt_ref.p; c.nrm = h->flt_nrm.p;
+    return left_points(c.n);
+  }
+  // Shadow: points and normals compacted together; behind a whole cloud's grid the gather goes through the sort's inverse
+  int shadow_stage(Cloud& c) {
+    const bool gathered = plan.shadow_normals == section::ShadowNormals::Gathered;
+    DevBuf<float4>& pts = gathered ? h->flt_ref : h->sh_ref; DevBuf<float>& nrm = gathered ? h->flt_nrm : h->sh_nrm;
+    HIPC(pts.reserve(c.n)); HIPC(nrm.reserve(3 * c.n));
+    int rc = shadow_enqueue(h, c.pts, c.nrm, c.n, h->sh_cfg.reference_eps, pts.p, nrm.p);
+    if (!rc) rc = shadow_wait(h, &c.n);
+    if (rc) return rc;
+    c.pts = pts.p; c.nrm = nrm.p;
+    return left_points(c.n);
+  }
+  // CovarianceSampling, the section's last stage: fewer points than nbSample pass unchanged
+  int cov_sampling_stage(Cloud& c) {
+    const int64_t nb = h->cs_cfg.reference_nb_sample;
+    if (nb >= c.n) return LSGPU_OK;
+    HIPC(h->cs_ref.reserve(nb)); HIPC(h->cs_ref_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
+    double sums[covs::kSums];
+    const int rc = cov_sampling_run(h, c.pts, c.nrm, c.n, nb, h->cs_cfg.reference_torque_norm, h->cs_ref.p, h->cs_ref_nrm.p, h->cs_pick.p, sums, nullptr);
+    if (rc) { h->nr = 0; return rc; }
+    c = {h->cs_ref.p, h->cs_ref_nrm.p, nb};
+    return LSGPU_OK;
+  }
+
   int filter_reference() {   // step 1: reference filter (yaml:5-7)
     nrc = nr;
     if (ref_cuts) {   // the cut modules stand in front of the normals module: the reference as handed over, before anything else
@@ -2980,84 +3000,36 @@ struct ComputeRun {
       int64_t reached = 0;
       int rc = cut_section_enqueue(h, cut_section_of(*cuts, 1, false), false, 0.f, nullptr, src, nr, h->cut_ref.p);
       if (!rc) rc = cut_section_wait(h, false, &reached, &nrc);   // (ssn_device and ref_build_front take the count on the host)
+      if (!rc) rc = left_points(nrc);
       if (rc) return rc;
-      if (nrc <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
       if (nrc < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
       src = h->cut_ref.p;
     }
-    ref_pts = src; nrf = nrc;   // (no reference filter module: the reference as given, no normals, no draw)
-    if (ref_filter) {
+    plan = section::settle(plan, h->cs_cfg.reference_nb_sample, nrc);   // (the count is on the host: the plan is final from here on)
+    ref = {src, nullptr, nrc};   // (no normals module, or normals on the final grid: the reference as given, no draw)
+    if (plan.source == section::Source::Sampling) {
       HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
-      const int rc = ssn_device(h, src, nrc, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &nrf, &draws);
+      int rc = ssn_device(h, src, nrc, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &ref.n, &draws);
+      if (!rc) rc = left_points(ref.n);
       if (rc) return rc;
-      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
-      ref_pts = h->flt_ref.p; ref_nrm = h->flt_nrm.p;
-    }
-    if (md) {
-      // the whole reference's grid (no direction index of it), normals and densities on it, then the thinning: the draws of
-      // the dense points are the section's, the reading's start behind them
-      int rc = ref_build_front(h, reinterpret_cast<const float*>(src), nullptr, nrc);
-      if (!rc) rc = ref_build_back(h, nrc);
+      ref.pts = h->flt_ref.p; ref.nrm = h->flt_nrm.p;
+    } else if (plan.whole_cloud()) {
+      const int rc = normals_on_whole_cloud(src, nrc, chain->sn_knn, plan.source == section::Source::WholeCloudDensities ? &h->dens : nullptr);
       if (rc) return rc;
-      HIPC(h->dens.reserve(nrc)); HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
-      rc = snf_device(h, chain->sn_knn, nullptr, nullptr, h->dens.p);
-      if (!rc) rc = draws.ready((size_t)nr);
-      int64_t n_dense = 0;
-      if (!rc) rc = max_density_enqueue(h, src, nrc, h->dens.p, h->md_cfg.max_density, h->ssn_draws.p + draws.used, md_normals, h->flt_ref.p, h->flt_nrm.p);
-      if (!rc) rc = max_density_wait(h, &n_dense, &nrf);
-      if (rc) return rc;
-      draws.used += (size_t)n_dense;
-      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
-      ref_pts = h->flt_ref.p; ref_nrm = md_normals ? h->flt_nrm.p : nullptr;
-    }
-    if (sh_sn) {
-      // the md route without the thinning: the whole reference's grid (no direction index of it), the normals on it, the pass
-      // with the gather through the sort's inverse
-      int rc = ref_build_front(h, reinterpret_cast<const float*>(src), nullptr, nrc);
-      if (!rc) rc = ref_build_back(h, nrc);
-      if (rc) return rc;
-      HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
-      rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
-      if (!rc) rc = shadow_enqueue(h, src, nullptr, nrc, h->sh_cfg.reference_eps, h->flt_ref.p, h->flt_nrm.p);
-      if (!rc) rc = shadow_wait(h, &nrf);
-      if (rc) return rc;
-      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
-      ref_pts = h->flt_ref.p; ref_nrm = sh_ref_normals ? h->flt_nrm.p : nullptr;
-    } else if (sh_ref) {
-      // behind the sampling filter or the thinning: their points and normals (flt_ref / flt_nrm), compacted together
-      HIPC(h->sh_ref.reserve(nrf)); HIPC(h->sh_nrm.reserve(3 * nrf));
-      int rc = shadow_enqueue(h, ref_pts, ref_nrm, nrf, h->sh_cfg.reference_eps, h->sh_ref.p, h->sh_nrm.p);
-      if (!rc) rc = shadow_wait(h, &nrf);
-      if (rc) return rc;
-      if (nrf <= 0) { h->err = "compute: the reference filter left no point"; h->nr = 0; return LSGPU_NO_CONVERGENCE; }
-      ref_pts = h->sh_ref.p; ref_nrm = (md && !sh_ref_normals) ? nullptr : h->sh_nrm.p;
-    }
-    if (cs_sn && h->cs_cfg.reference_nb_sample >= nrc) {
-      // the section passes unchanged: what a handle without the module does -- one grid, the normals computed on it
-      cs_sn = false; cs_ref = false; ref_normals = cs_ref_normals;
-    }
-    if (cs_sn) {
-      // the sh_sn route: the whole reference's grid (no direction index of it), the normals on it, copied out in the cloud's order
-      int rc = ref_build_front(h, reinterpret_cast<const float*>(src), nullptr, nrc);
-      if (!rc) rc = ref_build_back(h, nrc);
-      if (rc) return rc;
-      HIPC(h->cs_sn_nrm.reserve(3 * nrc));
-      rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nrc)), dim3(256), 0, h->stream, h->pts.p, (int)nrc, h->nrm.p, h->cs_sn_nrm.p);
-      HIPC(hipGetLastError());
-      ref_pts = src; ref_nrm = h->cs_sn_nrm.p; nrf = nrc;
-    }
-    if (cs_ref) {   // the section's last thinning step: fewer points than nbSample pass unchanged
-      const int64_t nb = h->cs_cfg.reference_nb_sample;
-      if (nb < nrf) {
-        HIPC(h->cs_ref.reserve(nb)); HIPC(h->cs_ref_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
-        double sums[covs::kSums];
-        const int rc = cov_sampling_run(h, ref_pts, ref_nrm, nrf, nb, h->cs_cfg.reference_torque_norm, h->cs_ref.p, h->cs_ref_nrm.p, h->cs_pick.p, sums, nullptr);
-        if (rc) { h->nr = 0; return rc; }
-        ref_pts = h->cs_ref.p; ref_nrm = h->cs_ref_nrm.p; nrf = nb;
+      if (plan.normals_copied_out()) {   // in the cloud's order
+        HIPC(h->cs_whole_nrm.reserve(3 * nrc));
+        hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nrc)), dim3(256), 0, h->stream, h->pts.p, (int)nrc, h->nrm.p, h->cs_whole_nrm.p);
+        HIPC(hipGetLastError());
+        ref.nrm = h->cs_whole_nrm.p;
       }
-      if (!cs_ref_normals) ref_nrm = nullptr;
+    }
+    for (int i = 0; i < plan.n_stages; ++i) {
+      const section::Stage s = plan.stages[i];
+      const int rc = s == section::Stage::MaxDensity ? max_density_stage(ref, plan.emits[i])
+                   : s == section::Stage::Shadow     ? shadow_stage(ref)
+                                                     : cov_sampling_stage(ref);
+      if (rc) return rc;
+      if (!plan.emits[i]) ref.nrm = nullptr;
     }
     // the reading filter draws once per reading point, whatever it keeps: the total is known, the stream can go
     // (not with cut modules in front of RandomSampling: reading_count_wait commits then)
@@ -3155,19 +3127,17 @@ struct ComputeRun {
     if (rc) return rc;
     if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
     if (nqf < nc->reading_sn_knn) { h->err = "compute: the kept reading has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
-    rc = ref_build_front(h, reinterpret_cast<const float*>(rd_dev), nullptr, nqf);
-    if (!rc) rc = ref_build_back(h, nqf);
-    if (!rc) rc = snf_device(h, nc->reading_sn_knn, nullptr, nullptr);
+    rc = normals_on_whole_cloud(rd_dev, nqf, nc->reading_sn_knn, nullptr);
     if (rc) return rc;
     HIPC(h->rd_nrm.reserve((size_t)3 * nqf));
     float* rn = h->rd_nrm.p;   // (ShadowDataPointsFilter behind them: a buffer in front of the pass, which writes h->rd_nrm)
-    if (sh_rd) { HIPC(h->sh_rd_nrm.reserve((size_t)3 * nqf)); rn = h->sh_rd_nrm.p; }
+    if (plan.rd_shadow) { HIPC(h->sh_rd_nrm.reserve((size_t)3 * nqf)); rn = h->sh_rd_nrm.p; }
     hipLaunchKernelGGL(k_snf_unpermute, dim3(nblk(nqf)), dim3(256), 0, h->stream, h->pts.p, (int)nqf, h->nrm.p, rn);
     if (nc->reading_orient)
       hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nqf)), dim3(256), 0, h->stream, rd_dev, (const float4*)nullptr, (int)nqf,
                          nc->reading_sensor[0], nc->reading_sensor[1], nc->reading_sensor[2], nc->reading_orient, rn, (float4*)nullptr);
     HIPC(hipGetLastError());
-    if (sh_rd) {   // the loop and the angle filter see the kept points and their normals from here on
+    if (plan.rd_shadow) {   // the loop and the angle filter see the kept points and their normals from here on
       HIPC(h->sh_rd.reserve(nqf));
       rc = shadow_enqueue(h, rd_dev, rn, nqf, h->sh_cfg.reading_eps, h->sh_rd.p, h->rd_nrm.p);
       if (!rc) rc = shadow_wait(h, &nqf);
@@ -3175,7 +3145,7 @@ struct ComputeRun {
       if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
       rd_dev = h->sh_rd.p;
     }
-    if (cs_rd && h->cs_cfg.reading_nb_sample < nqf) {   // behind the normals, their orientation and the Shadow pass
+    if (plan.rd_cov_sampling && h->cs_cfg.reading_nb_sample < nqf) {   // behind the normals, their orientation and the Shadow pass
       const int64_t nb = h->cs_cfg.reading_nb_sample;
       HIPC(h->cs_rd.reserve(nb)); HIPC(h->cs_rd_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
       double sums[covs::kSums];
@@ -3190,25 +3160,25 @@ struct ComputeRun {
 
   // steps 2-3: the reference's grid, the queries' side between and behind its halves, and the normals the chain computes on it
   int build_reference() {
-    if (nc && nc->reference_orient && ref_nrm)   // the sampling filter's normals, beside its points
-      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, (const float4*)nullptr, (int)nrf,
-                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, ref_nrm, (float4*)nullptr);
-    int rc = ref_build_front(h, reinterpret_cast<const float*>(ref_pts), ref_nrm, nrf);
-    if (!rc && side) rc = order_queries_on_side_lane();
-    if (!rc) rc = ref_build_back(h, nrf);
-    if (!rc && side) rc = move_queries();
-    if (!rc && !side) rc = build_cone_index(h);
-    if (!rc && ref_normals) rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
+    if (nc && nc->reference_orient && ref.nrm)   // the sampling filter's normals, beside its points
+      hipLaunchKernelGGL(k_orient_normals, dim3(nblk(ref.n)), dim3(256), 0, h->stream, ref.pts, (const float4*)nullptr, (int)ref.n,
+                         nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, ref.nrm, (float4*)nullptr);
+    int rc = ref_build_front(h, reinterpret_cast<const float*>(ref.pts), ref.nrm, ref.n);
+    if (!rc && plan.side) rc = order_queries_on_side_lane();
+    if (!rc) rc = ref_build_back(h, ref.n);
+    if (!rc && plan.side) rc = move_queries();
+    if (!rc && !plan.side) rc = build_cone_index(h);
+    if (!rc && plan.normals_on_final_grid) rc = snf_device(h, chain->sn_knn, nullptr, nullptr);
     if (rc) return rc;
-    if (ref_normals) {
+    if (plan.normals_on_final_grid) {
       h->have_normals = true;
-      if (nc && nc->reference_orient) {   // on the sorted normals; the position is the point as given (ref_pts, by the sorted point's index)
-        hipLaunchKernelGGL(k_orient_normals, dim3(nblk(nrf)), dim3(256), 0, h->stream, ref_pts, h->pts.p, (int)nrf,
+      if (nc && nc->reference_orient) {   // on the sorted normals; the position is the point as given (ref.pts, by the sorted point's index)
+        hipLaunchKernelGGL(k_orient_normals, dim3(nblk(ref.n)), dim3(256), 0, h->stream, ref.pts, h->pts.p, (int)ref.n,
                            nc->reference_sensor[0], nc->reference_sensor[1], nc->reference_sensor[2], nc->reference_orient, (float*)nullptr, h->nrm.p);
         HIPC(hipGetLastError());
       }
     }
-    if (side) {
+    if (plan.side) {
       // the direction index of the reference is not needed before the loop's third search: the align enqueues its
       // build on the side stream (behind the queries' order, with that stream's sort scratch) once the loop's first
       // iteration is out -- beside the first two iterations instead of in front of the loop (0.16 ms per 1 M-point
@@ -3241,10 +3211,10 @@ static int compute_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, cons
   int rc = run.check();
   if (!rc) rc = run.start_uploads();
   if (!rc) rc = run.filter_reference();
-  if (!rc && run.side) rc = run.reading_on_side_lane();
-  if (!rc && run.rd_normals) rc = run.reading_with_normals();
+  if (!rc && run.plan.side) rc = run.reading_on_side_lane();
+  if (!rc && run.plan.rd_normals) rc = run.reading_with_normals();
   if (!rc) rc = run.build_reference();
-  if (!rc && !run.side && !run.rd_normals) rc = run.reading_filter(false);   // (the reading's side after the grid build)
+  if (!rc && !run.plan.side && !run.plan.rd_normals) rc = run.reading_filter(false);   // (the reading's side after the grid build)
   return rc ? rc : run.finish(T_out, stats);
 }
 

@@ -37,18 +37,43 @@ def cov_sampling(nb=None, tq=None):
     return y
 
 
+MAX_DIST_10 = "  - MaxDistDataPointsFilter:\n      maxDist: 10\n"   # keeps 3226 of the pair's 4096 reference points
+
+P2P = "PointToPointErrorMinimizer"
+
+
 # The cases of the compute test on the 4 k-point pair (4096 reference points, 4080 reading points), seed 4; what the module is
-# handed is asserted to be more than nbSample in the test
+# handed is asserted to be more than nbSample in the test.  The chains of several thinning stages, counted with the host
+# twins (every stage is asserted to drop something in the test):
+#   sn_shadow, sn_shadow_point_to_point        Shadow keeps 2130 of 4096, the module 1000 of them
+#   sn_max_density_shadow                      MaxDensity keeps 3010 of 4096 (maxDensity = the median density), Shadow 1980 of
+#                                              them, the module 900 of them
+#   sn_max_density_point_to_point              MaxDensity keeps 3010 of 4096; no module, and nobody reads the normals
 def cases(md="26.893463"):
     return {
+        "sn_shadow": chain(reference=SN + shadow() + cov_sampling(1000, 1) + PAIR_REF),
+        "sn_max_density_shadow": chain(reference=SN_DENS + max_density(md) + shadow() + cov_sampling(900, 1) + PAIR_REF),
+        "sn_max_density_point_to_point": chain(reference=SN_DENS + max_density(md), minimizer=P2P),
+        "sn_shadow_point_to_point": chain(reference=SN + shadow() + cov_sampling(1000, 2), minimizer=P2P),
         "sampling": chain(reference=SSN + cov_sampling(600, 1)),
         "surface_normal": chain(reference=SN + PAIR_REF + cov_sampling(1500, 2)),
         "max_density": chain(reference=SN_DENS + max_density(md) + cov_sampling(1000, 1) + PAIR_REF),
         "shadow": chain(reference=SSN + shadow() + cov_sampling(500, 0)),
-        "point_to_point": chain(reference=SN + cov_sampling(1500, 1), minimizer="PointToPointErrorMinimizer"),
+        "point_to_point": chain(reference=SN + cov_sampling(1500, 1), minimizer=P2P),
         "reading": chain(reading=RS + SN_RD + PAIR_RD + cov_sampling(800, 1), reference=SSN + PAIR_REF, outliers=TRIM + SNO),
         "both": chain(reading=RS + SN_RD + cov_sampling(800, 2) + PAIR_RD, reference=SN + cov_sampling(1500, 0) + PAIR_REF,
                       outliers=TRIM + SNO),
+    }
+
+
+def fallback_cases(nb):
+    """SurfaceNormalDataPointsFilter with the module alone behind it and an nbSample that reaches what the module is handed: the
+    section passes unchanged.  -> {name: (the document, the same document without the module)}; "cut": a cut module in front
+    leaves 3226 points, which nbSample reaches although it is below 4096"""
+    return {
+        "plain": (chain(reference=SN + cov_sampling(nb, 1) + PAIR_REF), chain(reference=SN + PAIR_REF)),
+        "point_to_point": (chain(reference=SN + cov_sampling(nb, 1), minimizer=P2P), chain(reference=SN, minimizer=P2P)),
+        "cut": (chain(reference=MAX_DIST_10 + SN + cov_sampling(nb, 1) + PAIR_REF), chain(reference=MAX_DIST_10 + SN + PAIR_REF)),
     }
 
 
@@ -99,12 +124,13 @@ def route_a(doc, rd, ref, T_init, seed=SEED):
 
 
 def route_b(doc, rd, ref, T_init, seed=SEED):
-    """the same compute by hand -> (result, stream position, {side: (points handed to the module, points it kept)})"""
+    """the same compute by hand -> (result, stream position, {side: (points handed to the module, points it kept)}; the other
+    thinning stages of the reference as "reference MaxDensity" / "reference Shadow")"""
     from laser_slam_amd import icp, _lib
     o = icp.ICP()
     o.load_from_yaml(io.StringIO(doc))
     ch = o.chain
-    cs_rd, cs_ref = ch.cov_sampling
+    cs_rd, cs_ref = ch.cov_sampling if ch.cov_sampling is not None else (None, None)
     sh_rd, sh_ref = ch.shadow if ch.shadow is not None else (None, None)
     nc = ch.normals
     counts = {}
@@ -114,12 +140,15 @@ def route_b(doc, rd, ref, T_init, seed=SEED):
             rf, rn = hf.filter_reference(ref, ch.surface_normal_knn, ch.surface_normal_ratio, seed=-1)
         elif ch.max_density is not None:
             rf, rn, _n_dense = hf.filter_reference_max_density(ref, ch.reference_normal_knn, ch.max_density, seed=-1)
+            counts["reference MaxDensity"] = (len(ref), len(rf))
         else:
             rf, rn = np.ascontiguousarray(ref, np.float32), hf.filter_reference_normals(ref, ch.reference_normal_knn)
         rf, rn = np.ascontiguousarray(rf), np.ascontiguousarray(rn)
         if sh_ref is not None:
+            n_in = len(rf)
             rf, rn = hf.filter_shadow(rf, rn, sh_ref)
             rf, rn = np.ascontiguousarray(rf), np.ascontiguousarray(rn)
+            counts["reference Shadow"] = (n_in, len(rf))
         if cs_ref is not None:
             n_in = len(rf)
             rf, rn, _ids = hf.filter_cov_sampling(rf, rn, cs_ref[0], cs_ref[1])
@@ -153,7 +182,7 @@ def route_b(doc, rd, ref, T_init, seed=SEED):
         return result(T, st, h), pos, counts
 
 
-SIDE_CASES = ("sampling",)   # a chain whose reading runs on the side stream
+SIDE_CASES = ("sampling", "sn_shadow")   # chains whose reading runs on the side stream
 
 
 def main():

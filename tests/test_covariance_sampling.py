@@ -533,8 +533,11 @@ def route_a(name, pair):
     return _ROUTE_A[name]
 
 
-SIDES = {"sampling": ("reference",), "surface_normal": ("reference",), "max_density": ("reference",), "shadow": ("reference",),
-         "point_to_point": ("reference",), "reading": ("reading",), "both": ("reference", "reading")}
+SIDES = {"sampling": ("reference",), "surface_normal": ("reference",), "max_density": ("reference", "reference MaxDensity"),
+         "shadow": ("reference", "reference Shadow"), "point_to_point": ("reference",), "reading": ("reading",),
+         "both": ("reference", "reading"), "sn_shadow": ("reference", "reference Shadow"),
+         "sn_max_density_shadow": ("reference", "reference MaxDensity", "reference Shadow"),
+         "sn_max_density_point_to_point": ("reference MaxDensity",), "sn_shadow_point_to_point": ("reference", "reference Shadow")}
 
 
 @pytest.mark.gpu
@@ -569,6 +572,30 @@ def test_compute_without_the_side_stream(pair):
     assert set(res) == set(cases.SIDE_CASES)
     for name in cases.SIDE_CASES:
         assert res[name]["a"] == res[name]["b"] == cases.digest(*route_a(name, pair)), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ("plain", "point_to_point", "cut"))
+def test_an_nb_sample_that_reaches_the_section_equals_the_document_without_the_module(name, pair):
+    """SurfaceNormalDataPointsFilter with the module alone behind it, nbSample at and above what the module would be handed: the
+    section passes unchanged and the compute is the one of the document without the module -- T_out, the stats' result fields,
+    the trace, the reference the handle holds and the draw stream, bit for bit.  "cut": a MaxDist module in front leaves 3226 of
+    the 4096 points and nbSample lies between the two, so it is the count behind the cut that it reaches.  (Which grid the
+    normals are computed on is the plan's decision and changes no result: tests/cpp/section_plan_check.cpp pins it.)"""
+    rd, ref, T_init = pair["rd"], pair["ref"], pair["T_init"]
+    n_handed = 4096
+    if name == "cut":
+        n_handed = int((np.linalg.norm(ref[:, :3].astype(np.float64), axis=1) < 10).sum())
+        assert n_handed == 3226
+    without = None
+    for nb in ((3226, 3600) if name == "cut" else (4096, 6000)):
+        assert n_handed <= nb and (name != "cut" or nb < 4096)
+        doc, doc_without = cases.fallback_cases(nb)[name]
+        if without is None:
+            without = cases.route_a(doc_without, rd, ref, T_init)
+        a, pos_a = cases.route_a(doc, rd, ref, T_init)
+        assert a[1] >= 3 and len(a[5]) > 0 and a[6] == n_handed
+        assert (a, pos_a) == without, (name, nb)
 
 
 def _default_result(h, pair):

@@ -55,6 +55,43 @@ def test_launch_policy_state_machine(tmp_path):
     assert r.returncode == 0 and "policy_check ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_section_plan_equals_the_routing_it_replaced(tmp_path):
+    """csrc/lsgpu_section_plan.h decides what the filter sections of a compute are made of (no HIP in it).
+    tests/cpp/section_plan_check.cpp prints its plan for every input -- 3 reference modules x normals read x MaxDensity x
+    reference Shadow x reference CovarianceSampling x nbSample reaches the count, x the 8 reading combinations, x communicator x
+    side-stream switch -- and tests/golden/section_plan_parent.json holds what the flag routing before it did on the same
+    input (its header says how it was made): equal entry by entry, the refusal texts included."""
+    import itertools
+    import json
+    exe = str(tmp_path / "section_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "section_plan_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0 and lines and lines[-1].startswith("section_plan_check: ok"), r.stdout[-2000:] + r.stderr
+    got = [json.loads(ln) for ln in lines[:-1]]
+    with open(os.path.join(ROOT, "tests", "golden", "section_plan_parent.json")) as f:
+        fixture = json.load(f)
+    # one record per input: the outcome the fixture names for it, under the input's digits in enumeration order
+    digits = itertools.product(range(3), range(2), range(2), range(2), range(2), range(2), range(8), range(2), range(2))
+    keys = ["%d%d%d%d%d%d%d%d%d%d%d" % (m, read, md, sh, cs, reach, rd & 1, rd >> 1 & 1, rd >> 2, comm, sw)
+            for m, read, md, sh, cs, reach, rd, comm, sw in digits]
+    want = [dict(fixture["outcomes"][i], **{"in": k}) for i, k in zip(fixture["records"], keys)]
+    # the fixture is the whole input space, with plenty on either side of the verdict and every refusal of the routing in it
+    assert len(fixture["records"]) == len(keys) == 3 * 2 ** 5 * 8 * 2 * 2 == len(set(keys))
+    ok = [w for w in want if w["verdict"] == "ok"]
+    assert len(ok) > 200 and len(want) - len(ok) > 200
+    assert {w["verdict"] for w in want} - {"ok"} == {
+        "compute: MaxDensityDataPointsFilter: needs the densities of SurfaceNormalDataPointsFilter with keepDensities 1 as the reference filter (sn_knn > 0)",
+        "compute: ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn)",
+        "compute: ShadowDataPointsFilter on the reference needs the normals of a reference filter (ssn_knn or sn_knn)",
+        "compute: CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn)",
+        "compute: CovarianceSamplingDataPointsFilter on the reference needs the normals of a reference filter (ssn_knn or sn_knn)"}
+    assert {tuple(w["stages"]) for w in ok} >= {(), ("max_density", "shadow", "cov_sampling"), ("shadow", "cov_sampling"), ("cov_sampling",)}
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w, (g, w)
+
+
 def test_gtsam_overlay_parses_and_resolves_the_ros_worker_calls():
     """PARSE check of integration/gtsam/laser_slam_gtsam_overlay.hpp (the `namespace laser_slam` types laser_slam_ros
     compiles against): g++ -fsyntax-only against the declaration-only stand-ins of tests/cpp/mock/ (GTSAM, minkindr,
