@@ -1090,6 +1090,67 @@ int lsgpu_filter_cov_sampling(const float* xyz1, const float* normals, int64_t n
  * float, values (nullable) the eigenvalues, ascending.  Host only.  LSGPU_BAD_ARG for a NULL or an entry that is not finite. */
 int lsgpu_cov_sampling_eigen(const double C21[21], float X[36], double values[6]);
 
+/* ---- carried normals: a cloud brings its normals along (DESIGN.md §3 "Carried normals", §5 choices) --------------------------
+ * LaserTrack applies its input filters once to every scan, stores the result, rebuilds the sub-map with
+ * RigidTransformation::compute + concatenate and hands both clouds to ICP::compute.  With SurfaceNormalDataPointsFilter in the
+ * input filters the normals are computed once per scan and travel as a descriptor; the ICP chain then needs no normals
+ * module.  The rules:
+ *  1. A cloud may carry normals, 3 floats per point beside the points.  A sub-map concat_i(T_i cloud_i) carries normals iff
+ *     EVERY member does (concatenate keeps what both sides have).  Points move with the arithmetic of lsgpu_transform_points,
+ *     normals with that of lsgpu_rotate_descriptors; a member whose transform is exactly the identity is copied bit for bit
+ *     (Inf and NaN survive).
+ *  2. A normals module in a section overwrites what the section's cloud carries: with ssn_knn / sn_knn > 0 (reference) or
+ *     reading_sn_knn > 0 (reading) the carried normals of that side are never read, and every result is bit-identical to the
+ *     call on clouds without normals.
+ *  3. Carried normals nobody reads do not travel (no upload, no compaction, no sort).  The reference's are read iff the
+ *     minimizer is not point-to-point, or RobustOutlierFilter takes the point-to-plane distance, or SurfaceNormalOutlierFilter
+ *     is set; the reading's iff SurfaceNormalOutlierFilter is set (max_angle >= 0).
+ *  4. RandomSamplingDataPointsFilter and the cut modules (lsgpu_icp_set_chain_cuts) keep a point's normal with the point.
+ *     Order, predicates, draws and the number of draws consumed are those of the section on a cloud without normals;
+ *     RemoveNaN looks at the four feature rows only.
+ *  5. Readers.  Reference: the point-to-plane minimizers, RobustOutlierFilter point2plane, SurfaceNormalOutlierFilter and the
+ *     reference's ObservationDirection + OrientNormals pair (reference_orient).  Reading: SurfaceNormalOutlierFilter.  Behind
+ *     the sections the loop sees what lsgpu_icp_set_reference(ref, ref_normals) + lsgpu_icp_align_normals(reading,
+ *     reading_normals) on the sections' outputs see.
+ *  6. A reference without normals that somebody reads, in a chain without a reference module, is LSGPU_BAD_CONFIG as ever;
+ *     where some slots of a sub-map carry normals and one does not, the error names that slot.  SurfaceNormalOutlierFilter
+ *     with reading_normals_given 1 and a reading that carries none is inert (upstream skips it with a warning).
+ * Refused in this version: MaxDensity-, Shadow- and CovarianceSamplingDataPointsFilter on carried normals (they need the
+ * section's own normals module: the texts of lsgpu_icp_compute apply), the reading's orientation pair on carried normals
+ * (lsgpu_normals_config_check's text), and carried normals on a split-scan handle (lsgpu_icp_set_reference takes them there).
+ *
+ * lsgpu_cloud_upload_normals: lsgpu_cloud_upload plus the cloud's normals (host or device); normals NULL is lsgpu_cloud_upload,
+ * which drops what the slot carried.  lsgpu_cloud_release frees both. */
+int lsgpu_cloud_upload_normals(lsgpu_icp* h, int slot, const float* xyz1, const float* normals, int64_t n);
+int lsgpu_cloud_has_normals(lsgpu_icp* h, int slot, int* has);   /* 1: the slot holds a cloud that carries normals */
+/* lsgpu_icp_compute on clouds that carry normals; host or device pointers, either normals pointer may be NULL.  Both NULL:
+ * lsgpu_icp_compute, bit for bit.  The caller's normals are only read. */
+int lsgpu_icp_compute_normals(lsgpu_icp* h, const float* reading_xyz1, const float* reading_normals, int64_t nq,
+                              const float* reference_xyz1, const float* reference_normals, int64_t nr, const float T_init[16],
+                              const lsgpu_chain_config* chain, float T_out[16], lsgpu_icp_stats* stats);
+/* lsgpu_icp_compute_clouds and lsgpu_icp_compute_clouds_upload use what the slots carry (rule 1); the latter stores points only,
+ * so its reading slot carries none afterwards.  This entry stores the reading with its normals and computes.  In this version
+ * the upload and the compute run one after the other: no overlap of the copy with the sub-map's assembly. */
+int lsgpu_icp_compute_clouds_upload_normals(lsgpu_icp* h, int reading_slot, const float* reading_xyz1, const float* reading_normals,
+                                            int64_t nq, const int* ref_slots, const float* ref_T, int n_ref, const float T_init[16],
+                                            const lsgpu_chain_config* chain, float T_out[16], lsgpu_icp_stats* stats);
+/* lsgpu_chain_load for a caller whose clouds carry normals: `carried` is a set of the two bits below.  The same walk, rules
+ * and texts; a carried reference counts as normals for whoever reads the reference's (no reference module needed, and its
+ * ObservationDirection + OrientNormals pair may stand without one), and with a carried reading, SurfaceNormalOutlierFilter
+ * and no SurfaceNormalDataPointsFilter in the reading's section out->normals.reading_normals_given is 1.  carried 0 is
+ * lsgpu_chain_load in every byte and text.  lsgpu_chain_load_parts_carried: the other four loaders under the same
+ * declaration, each output nullable. */
+#define LSGPU_CARRIED_READING 1
+#define LSGPU_CARRIED_REFERENCE 2
+int lsgpu_chain_load_carried(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_loaded_chain* out, char* why, int why_cap);
+int lsgpu_chain_load_parts_carried(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_chain_cuts* cuts,
+                                   lsgpu_shadow_config* shadow, lsgpu_motion_config* motion, lsgpu_cov_sampling_config* cov_sampling,
+                                   char* why, int why_cap);
+/* SurfaceNormalDataPointsFilter's parameters as the loader judges the reading's module (knn 3..32, keepNormals 1, epsilon 0,
+ * no maxDist, nothing else kept): LSGPU_OK and *knn, or LSGPU_BAD_CONFIG and the loader's text.  For a chain outside the ICP
+ * file that runs the module (the input filters).  Host only. */
+int lsgpu_surface_normal_params_check(const lsgpu_yaml_param* params, int n_params, int* knn, char* why, int why_cap);
+
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */
 int         lsgpu_abi_version(void);

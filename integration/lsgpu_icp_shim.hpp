@@ -31,6 +31,18 @@ struct LsgpuCloudTraits {
   static const float* features(const DataPoints& d) { return d.features.data(); }      // 4 x N, column major
   static int64_t size(const DataPoints& d) { return (int64_t)d.features.cols(); }
   static bool hasDescriptors(const DataPoints& d) { return d.descriptors.cols() > 0; }
+  // The normals the cloud carries, 3 floats per point: the rows labelled `normals` of `descriptors` (any other descriptor
+  // stays where it is).  false, and *out empty: the cloud carries none
+  static bool normals(const DataPoints& d, std::vector<float>* out) {
+    out->clear();
+    if (d.descriptors.cols() == 0 || !d.descriptorExists("normals")) return false;
+    const auto rows = d.getDescriptorViewByName("normals");
+    if (rows.rows() != 3) return false;
+    out->resize((size_t)rows.cols() * 3);
+    for (Eigen_Index i = 0; i < (Eigen_Index)rows.cols(); ++i)
+      for (int r = 0; r < 3; ++r) (*out)[3 * (size_t)i + r] = rows(r, i);
+    return true;
+  }
   // keep the listed columns (ascending) of features and of every descriptor, drop the others
   static void keepColumns(DataPoints& d, const std::vector<int64_t>& cols) {
     for (size_t j = 0; j < cols.size(); ++j) {
@@ -65,6 +77,10 @@ struct LsgpuCloudTraits<LsgpuMirrorPM> {
   static const float* features(const DataPoints& d) { return d.features.data(); }
   static int64_t size(const DataPoints& d) { return d.getNbPoints(); }
   static bool hasDescriptors(const DataPoints& d) { return !d.normals.empty(); }
+  static bool normals(const DataPoints& d, std::vector<float>* out) {   // the vector itself
+    *out = d.normals;
+    return !out->empty();
+  }
   static void keepColumns(DataPoints& d, const std::vector<int64_t>& cols) {
     const bool nrm = !d.normals.empty();
     for (size_t j = 0; j < cols.size(); ++j) {
@@ -100,10 +116,12 @@ class LsgpuICP {
     laser_slam_amd::ICP parsed;                         // == ICP::setDefault() values
     take(parsed);
   }
-  void loadFromYaml(std::istream& in) {                 // laser_track.cpp:17
+  // carried: which of compute()'s clouds carry a `normals` descriptor that the chain may read without a module of its own
+  // (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE; include/lsgpu_icp.h, "carried normals"): the input filters computed them
+  void loadFromYaml(std::istream& in, unsigned carried = 0) {   // laser_track.cpp:17
     laser_slam_amd::ICP parsed;
     try {
-      parsed.loadFromYaml(in);                          // the module chain of icp_default.yaml; anything else throws
+      parsed.loadFromYaml(in, carried);                        // the module chain of icp_default.yaml; anything else throws
     } catch (const laser_slam_amd::ConfigError& e) {
       throw std::runtime_error(std::string("LsgpuICP::loadFromYaml: ") + e.what());   // PointMatcher: InvalidModuleType
     }
@@ -164,8 +182,14 @@ class LsgpuICP {
     lsgpu_chain_config_default(&chain);
     chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
     TransformationParameters T = T_init;
-    const int rc = lsgpu_icp_compute(h_, Traits::features(reading), Traits::size(reading), Traits::features(reference),
-                                     Traits::size(reference), T_init.data(), &chain, T.data(), &stats_);
+    // the normals of a side travel iff loadFromYaml declared that side
+    const bool rd_n = (carried_ & LSGPU_CARRIED_READING) && Traits::normals(reading, &rd_normals_) && (int64_t)rd_normals_.size() == 3 * Traits::size(reading);
+    const bool ref_n = (carried_ & LSGPU_CARRIED_REFERENCE) && Traits::normals(reference, &ref_normals_) && (int64_t)ref_normals_.size() == 3 * Traits::size(reference);
+    const int rc = carried_ ? lsgpu_icp_compute_normals(h_, Traits::features(reading), rd_n ? rd_normals_.data() : nullptr, Traits::size(reading),
+                                                        Traits::features(reference), ref_n ? ref_normals_.data() : nullptr, Traits::size(reference),
+                                                        T_init.data(), &chain, T.data(), &stats_)
+                            : lsgpu_icp_compute(h_, Traits::features(reading), Traits::size(reading), Traits::features(reference),
+                                                Traits::size(reference), T_init.data(), &chain, T.data(), &stats_);
     if (rc == LSGPU_NO_CONVERGENCE) throw typename PM::ConvergenceError(lsgpu_last_error(h_));
     if (rc != LSGPU_OK) throw std::runtime_error(std::string("LsgpuICP::compute: ") + lsgpu_strerror(rc) + " [" + lsgpu_last_error(h_) + "]");
     return T;
@@ -185,6 +209,7 @@ class LsgpuICP {
  private:
   void take(const laser_slam_amd::ICP& parsed) {
     cfg_ = parsed.config();
+    carried_ = parsed.carried();
     prob_ = parsed.readingSamplingProb(); knn_ = parsed.surfaceNormalKnn(); ratio_ = parsed.surfaceNormalRatio();
     sn_knn_ = parsed.referenceNormalKnn();
     has_robust_ = parsed.robustFilter() != nullptr;
@@ -230,6 +255,8 @@ class LsgpuICP {
   lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // PointToPlaneErrorMinimizer force2D / force4DOF, BoundTransformationChecker ...
   bool has_motion_ = false;                             // ... if the chain names either
   int64_t seed_ = -1;
+  unsigned carried_ = 0;                                // loadFromYaml's declaration: which clouds carry normals
+  std::vector<float> rd_normals_, ref_normals_;         // the normals handed to the last compute()
 };
 
 // ---- PointMatcher::DataPointsFilters stand-in (laser_track.cpp:24-30, :81, :146)

@@ -54,7 +54,13 @@ ABI_SYMBOLS = [
     "lsgpu_icp_filter_cov_sampling", "lsgpu_icp_cov_sampling_phase_ms", "lsgpu_filter_cov_sampling", "lsgpu_cov_sampling_eigen",
     "lsgpu_cov_sampling_config_default", "lsgpu_cov_sampling_config_check", "lsgpu_cov_sampling_config_why",
     "lsgpu_icp_set_cov_sampling", "lsgpu_chain_load_cov_sampling",
+    "lsgpu_cloud_upload_normals", "lsgpu_cloud_has_normals", "lsgpu_icp_compute_normals",
+    "lsgpu_icp_compute_clouds_upload_normals", "lsgpu_chain_load_carried", "lsgpu_chain_load_parts_carried",
+    "lsgpu_surface_normal_params_check",
 ]
+
+# lsgpu_chain_load_carried: which of a caller's clouds carry normals (LSGPU_CARRIED_*)
+CARRIED_READING, CARRIED_REFERENCE = 1, 2
 
 # lsgpu_motion_config.dof (LSGPU_MOTION_DOF_*): the free step, force2D, force4DOF
 MOTION_DOF_6, MOTION_DOF_3, MOTION_DOF_4 = 0, 3, 4
@@ -430,6 +436,17 @@ def lib() -> C.CDLL:
     L.lsgpu_point_to_plane_solve_dof.argtypes = [C.POINTER(C.c_double), C.c_int, fp]
     L.lsgpu_bound_first_violation.argtypes = [fp, C.c_int, C.c_float, C.c_float]
     L.lsgpu_chain_load_motion.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(MotionCfg), C.c_char_p, C.c_int]
+    L.lsgpu_cloud_upload_normals.argtypes = [vp, C.c_int, fp, fp, i64]
+    L.lsgpu_cloud_has_normals.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.lsgpu_icp_compute_normals.argtypes = [vp, fp, fp, i64, fp, fp, i64, C.POINTER(C.c_float), C.POINTER(ChainCfg),
+                                            C.POINTER(C.c_float), C.POINTER(IcpStats)]
+    L.lsgpu_icp_compute_clouds_upload_normals.argtypes = [vp, C.c_int, fp, fp, i64, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int,
+                                                          C.POINTER(C.c_float), C.POINTER(ChainCfg), C.POINTER(C.c_float),
+                                                          C.POINTER(IcpStats)]
+    L.lsgpu_chain_load_carried.argtypes = [C.POINTER(YamlModule), C.c_int, C.c_uint, C.POINTER(LoadedChain), C.c_char_p, C.c_int]
+    L.lsgpu_chain_load_parts_carried.argtypes = [C.POINTER(YamlModule), C.c_int, C.c_uint, C.POINTER(ChainCuts), C.POINTER(ShadowCfg),
+                                                 C.POINTER(MotionCfg), C.POINTER(CovSamplingCfg), C.c_char_p, C.c_int]
+    L.lsgpu_surface_normal_params_check.argtypes = [C.POINTER(YamlParam), C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
     _lib = L
     return L
 

@@ -162,10 +162,16 @@ inline std::vector<YamlModule> parseYamlList(std::istream& in) {
 // applied in place to every incoming scan (laser_track.cpp:81, :146).  The supported modules run on the device
 // (lsgpu_apply_point_filters); any other module is a configuration error, like an unknown name is for
 // PointMatcher's registrar.  FixStepSampling keeps its step between calls, as the upstream object does.
+// The chain may END with the modules that give a scan its normals -- SurfaceNormalDataPointsFilter, optionally followed
+// directly by ObservationDirectionDataPointsFilter + OrientNormalsDataPointsFilter: apply() runs them on what the point
+// modules kept (lsgpu_icp_reading_normals), the cloud's `normals` hold the result and travel with the scan from then on
+// (include/lsgpu_icp.h, "carried normals").  A point module behind that tail is a configuration error.  The tail is read only
+// where the caller asks for it (normals_tail; LaserTrack does): a caller that does not hand the normals on keeps the refusal.
 class DataPointsFilters {
  public:
   DataPointsFilters() = default;
-  explicit DataPointsFilters(std::istream& in, int device = 0) : device_(device) {
+  explicit DataPointsFilters(std::istream& in, int device = 0, bool normals_tail = false) : device_(device) {
+    int tail = 0;   // 1: SurfaceNormalDataPointsFilter seen, 2: ObservationDirection behind it, 3: OrientNormals behind that
     for (const auto& m : detail::parseYamlList(in)) {
       auto num = [&](const char* key, double def) {
         auto it = m.params.find(key);
@@ -178,6 +184,41 @@ class DataPointsFilters {
           if (!known) throw ConfigError(m.name + ": unknown parameter " + kv.first);
         }
       };
+      if (!normals_tail) {
+        // (the three modules of the tail fall through to the refusal of an unknown module below)
+      } else if (m.name == "SurfaceNormalDataPointsFilter") {
+        // the parameters are judged by the rule the ICP chain's loader applies to the reading's module
+        if (tail) throw ConfigError("input filters: SurfaceNormalDataPointsFilter given twice");
+        std::vector<lsgpu_yaml_param> ps;
+        for (const auto& kv : m.params) ps.push_back({kv.first.c_str(), kv.second.c_str()});
+        char why[512];
+        if (lsgpu_surface_normal_params_check(ps.data(), (int)ps.size(), &normals_knn_, why, (int)sizeof(why)) != LSGPU_OK)
+          throw ConfigError(std::string("input filters: ") + why);
+        tail = 1;
+        continue;
+      } else if (m.name == "ObservationDirectionDataPointsFilter") {
+        if (tail != 1) throw ConfigError("input filters: ObservationDirectionDataPointsFilter is implemented only as the pair "
+                                         "ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter directly behind SurfaceNormalDataPointsFilter");
+        only({"x", "y", "z"});
+        const char* keys[3] = {"x", "y", "z"};
+        for (int a = 0; a < 3; ++a) {
+          sensor_[a] = (float)num(keys[a], 0.0);
+          if (!std::isfinite(sensor_[a])) throw ConfigError(m.name + ": x, y, z must be finite");
+        }
+        tail = 2;
+        continue;
+      } else if (m.name == "OrientNormalsDataPointsFilter") {
+        if (tail != 2) throw ConfigError("input filters: OrientNormalsDataPointsFilter is implemented only as the pair "
+                                         "ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter directly behind SurfaceNormalDataPointsFilter");
+        only({"towardCenter"});
+        const double tc = num("towardCenter", 1);
+        if (tc != 0 && tc != 1) throw ConfigError(m.name + ": towardCenter must be 0 or 1");
+        orient_ = tc == 1 ? 1 : 2;
+        tail = 3;
+        continue;
+      }
+      if (tail) throw ConfigError("input filters: " + m.name + " behind SurfaceNormalDataPointsFilter is not implemented (the normals "
+                                  "modules are the chain's last: the normals would have to be gathered through the module)");
       lsgpu_point_filter f;
       std::memset(&f, 0, sizeof(f));
       if (m.name == "MaxDistDataPointsFilter") {
@@ -231,6 +272,8 @@ class DataPointsFilters {
       }
       filters_.push_back(f);
     }
+    if (tail == 2) throw ConfigError("input filters: ObservationDirectionDataPointsFilter is implemented only as the pair "
+                                     "ObservationDirectionDataPointsFilter, OrientNormalsDataPointsFilter directly behind SurfaceNormalDataPointsFilter");
   }
   ~DataPointsFilters() { if (h_) lsgpu_icp_destroy(h_); }
   DataPointsFilters(const DataPointsFilters&) = delete;
@@ -240,12 +283,18 @@ class DataPointsFilters {
     if (this != &o) {
       if (h_) lsgpu_icp_destroy(h_);
       filters_ = std::move(o.filters_); h_ = o.h_; o.h_ = nullptr; device_ = o.device_; seed_ = o.seed_;
+      normals_knn_ = o.normals_knn_; orient_ = o.orient_;
+      for (int a = 0; a < 3; ++a) sensor_[a] = o.sensor_[a];
     }
     return *this;
   }
 
   size_t size() const { return filters_.size(); }
-  bool empty() const { return filters_.empty(); }
+  bool empty() const { return filters_.empty() && !producesNormals(); }
+  // the chain ends with SurfaceNormalDataPointsFilter: every cloud apply() leaves carries normals
+  bool producesNormals() const { return normals_knn_ > 0; }
+  int normalsKnn() const { return normals_knn_; }
+  int normalsOrientation() const { return orient_; }   // 0: no pair, 1: towardCenter 1, 2: towardCenter 0
   const std::vector<lsgpu_point_filter>& modules() const { return filters_; }
   void setSeed(int64_t seed) { seed_ = seed; }  // >= 0: reseed the draw stream at every apply(); < 0: continue it
 
@@ -253,10 +302,13 @@ class DataPointsFilters {
   void apply(DataPoints& cloud);
 
  private:
+  void applyPointModules(DataPoints& cloud, int64_t n);
   std::vector<lsgpu_point_filter> filters_;
   lsgpu_icp* h_ = nullptr;
   int device_ = 0;
   int64_t seed_ = -1;
+  int normals_knn_ = 0, orient_ = 0;   // the tail: SurfaceNormalDataPointsFilter's knn (0: none), the pair's orientation
+  float sensor_[3] = {0.f, 0.f, 0.f};
 };
 
 class ICP {
@@ -273,6 +325,7 @@ class ICP {
     std::memset(&loaded_, 0, sizeof(loaded_));
     lsgpu_icp_config_default(&loaded_.icp);
     lsgpu_chain_config_default(&loaded_.chain);
+    carried_ = 0;
     std::memset(&cuts_, 0, sizeof(cuts_));
     lsgpu_shadow_config_default(&shadow_);
     lsgpu_motion_config_default(&motion_);
@@ -283,7 +336,9 @@ class ICP {
   // The syntax is read here (parseYaml), the modules are handed to lsgpu_chain_load as text: which modules the device path
   // has, their parameters, ranges and order are the library's rule set (csrc/lsgpu_chain_loader.cpp), shared with the Python
   // facade.  Any other module is a configuration error (PointMatcher's registrar throws on unknown names as well).
-  void loadFromYaml(std::istream& in) {
+  // carried: which of compute()'s clouds carry normals (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE): the chain may then
+  // read normals it has no module for, and compute(), uploadCloud() and the slot calls hand over the normals of a declared side.
+  void loadFromYaml(std::istream& in, unsigned carried = 0) {
     const auto mods = parseYaml(in);
     std::vector<std::vector<lsgpu_yaml_param>> params(mods.size());
     std::vector<lsgpu_yaml_module> list(mods.size());
@@ -293,6 +348,16 @@ class ICP {
     }
     lsgpu_loaded_chain loaded;
     char why[512];
+    if (carried) {   // one declaration, the same walk: every part under it
+      lsgpu_chain_cuts c_cuts; lsgpu_shadow_config c_shadow; lsgpu_motion_config c_motion; lsgpu_cov_sampling_config c_cs;
+      if (lsgpu_chain_load_carried(list.data(), (int)list.size(), carried, &loaded, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
+      if (lsgpu_chain_load_parts_carried(list.data(), (int)list.size(), carried, &c_cuts, &c_shadow, &c_motion, &c_cs, why, (int)sizeof(why)) != LSGPU_OK)
+        throw ConfigError(why);
+      loaded_ = loaded; cuts_ = c_cuts; shadow_ = c_shadow; motion_ = c_motion; cov_sampling_ = c_cs;
+      carried_ = carried;
+      release();
+      return;
+    }
     if (lsgpu_chain_load(list.data(), (int)list.size(), &loaded, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
     // the cut modules of the filter sections (MaxDist-, MinDist-, BoundingBox-, RemoveNaNDataPointsFilter): same rules, the modules
     lsgpu_chain_cuts cuts;
@@ -313,7 +378,15 @@ class ICP {
     shadow_ = shadow;
     motion_ = motion;
     cov_sampling_ = cov_sampling;
+    carried_ = 0;
     release();
+  }
+  unsigned carried() const { return carried_; }
+  // does a module behind the reference's section read its normals (include/lsgpu_icp.h, "carried normals", rule 3)?
+  bool readsReferenceNormals() const {
+    return loaded_.icp.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT ||
+           (loaded_.has_robust && loaded_.robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE) ||
+           (loaded_.has_normals && loaded_.normals.max_angle >= 0.f);
   }
 
   static void requireRigid(const TransformationParameters& T_init) {
@@ -347,10 +420,17 @@ class ICP {
     lsgpu_chain_config chain = loaded_.chain;
     chain.seed = seed_;
     TransformationParameters T = T_init;
-    const int rc = lsgpu_icp_compute(h_, reading.features.data(), nq, reference.features.data(), nr, T_init.data(),
-                                     &chain, T.data(), &stats_);
+    // the normals of a side travel iff loadFromYaml declared that side as carrying some
+    const float* rd_n = carriedNormals(reading, LSGPU_CARRIED_READING);
+    const float* ref_n = carriedNormals(reference, LSGPU_CARRIED_REFERENCE);
+    if ((carried_ & LSGPU_CARRIED_REFERENCE) && !ref_n && readsReferenceNormals() && loaded_.chain.ssn_knn == 0 && loaded_.chain.sn_knn == 0)
+      throw ConfigError("ICP::compute: the reference was declared to carry normals and carries none, and the chain reads them");
+    const int rc = carried_ ? lsgpu_icp_compute_normals(h_, reading.features.data(), rd_n, nq, reference.features.data(), ref_n, nr,
+                                                        T_init.data(), &chain, T.data(), &stats_)
+                            : lsgpu_icp_compute(h_, reading.features.data(), nq, reference.features.data(), nr, T_init.data(),
+                                                &chain, T.data(), &stats_);
     if (!rigid) requireRigid(T_init);          // (rc is LSGPU_BAD_ARG from step 5, the filters have run)
-    check(rc, "lsgpu_icp_compute");
+    check(rc, carried_ ? "lsgpu_icp_compute_normals" : "lsgpu_icp_compute");
 #ifdef LSGPU_TEST_SEAMS
     if (observer_) observer_(*this, reading, reference, T_init, T);
 #endif
@@ -361,7 +441,10 @@ class ICP {
   // Slots live in the handle; loadFromYaml / setDefault drop them (generation() changes).
   void uploadCloud(int slot, const DataPoints& cloud) {
     ensureHandle();
-    check(lsgpu_cloud_upload(h_, slot, cloud.features.data(), cloud.getNbPoints()), "lsgpu_cloud_upload");
+    // (a stored scan serves as the reading once and as a sub-map member afterwards: its normals travel if either side is declared)
+    const float* nrm = carriedNormals(cloud, LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE);
+    if (nrm) check(lsgpu_cloud_upload_normals(h_, slot, cloud.features.data(), nrm, cloud.getNbPoints()), "lsgpu_cloud_upload_normals");
+    else check(lsgpu_cloud_upload(h_, slot, cloud.features.data(), cloud.getNbPoints()), "lsgpu_cloud_upload");
   }
   void releaseCloud(int slot) { if (h_) lsgpu_cloud_release(h_, slot); }
   bool hasCloud(int slot) {
@@ -412,10 +495,13 @@ class ICP {
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
     TransformationParameters T = T_init;
-    const int rc = lsgpu_icp_compute_clouds_upload(h_, reading, cloud.features.data(), cloud.getNbPoints(), refs.data(),
-                                                   flat.data(), (int)refs.size(), T_init.data(), &chain, T.data(), &stats_);
+    const float* nrm = carriedNormals(cloud, LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE);
+    const int rc = nrm ? lsgpu_icp_compute_clouds_upload_normals(h_, reading, cloud.features.data(), nrm, cloud.getNbPoints(), refs.data(),
+                                                                 flat.data(), (int)refs.size(), T_init.data(), &chain, T.data(), &stats_)
+                       : lsgpu_icp_compute_clouds_upload(h_, reading, cloud.features.data(), cloud.getNbPoints(), refs.data(),
+                                                         flat.data(), (int)refs.size(), T_init.data(), &chain, T.data(), &stats_);
     if (!rigid) requireRigid(T_init);
-    check(rc, "lsgpu_icp_compute_clouds_upload");
+    check(rc, nrm ? "lsgpu_icp_compute_clouds_upload_normals" : "lsgpu_icp_compute_clouds_upload");
     return T;
   }
 
@@ -595,6 +681,11 @@ class ICP {
     }
   }
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
+  // the cloud's normals if one of `sides` was declared at load and the cloud carries one normal per point, else nullptr
+  const float* carriedNormals(const DataPoints& cloud, unsigned sides) const {
+    if (!(carried_ & sides) || cloud.normals.empty() || cloud.normals.size() != (size_t)cloud.getNbPoints() * 3) return nullptr;
+    return cloud.normals.data();
+  }
   void check(int rc, const char* what) {
     if (rc == LSGPU_OK) return;
     const std::string msg = std::string(what) + ": " + lsgpu_strerror(rc) + " [" + lsgpu_last_error(h_) + "]";
@@ -609,6 +700,7 @@ class ICP {
   lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};   // ... and ShadowDataPointsFilter's eps of the two (lsgpu_chain_load_shadow)
   lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // ... and force2D / force4DOF, BoundTransformationChecker (lsgpu_chain_load_motion)
   lsgpu_cov_sampling_config cov_sampling_{0, 0, 1, 1, {0, 0, 0, 0}};   // ... and CovarianceSamplingDataPointsFilter of the two (lsgpu_chain_load_cov_sampling)
+  unsigned carried_ = 0;          // ... and which of compute()'s clouds were declared as carrying normals (LSGPU_CARRIED_*)
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;
@@ -620,7 +712,8 @@ class ICP {
 };
 
 inline void DataPointsFilters::apply(DataPoints& cloud) {
-  if (filters_.empty()) return;
+  if (filters_.empty() && !producesNormals()) return;
+  if (producesNormals()) cloud.normals.clear();   // (a cloud that arrives with normals has them overwritten)
   // VoxelGridDataPointsFilter writes new points: the tag it hands on is the voxel's first point's, so the normal picked
   // further down is that point's (averageExistingDescriptors 0).  Averaging the descriptors of a voxel is not implemented.
   if (!cloud.normals.empty())
@@ -641,6 +734,20 @@ inline void DataPointsFilters::apply(DataPoints& cloud) {
     if (lsgpu_icp_create(&c, device_, &h_) != LSGPU_OK) throw DeviceError("lsgpu_icp_create failed (no ROCm GPU visible?)");
   }
   const int64_t n = cloud.getNbPoints();
+  if (!filters_.empty()) applyPointModules(cloud, n);
+  if (!producesNormals()) return;
+  // the tail, on what the point modules kept: SurfaceNormalDataPointsFilter and the orientation pair
+  const int64_t kept = cloud.getNbPoints();
+  if (kept <= 0) throw ConvergenceError("no points to filter");
+  cloud.normals.assign((size_t)kept * 3, 0.f);
+  const int rc = lsgpu_icp_reading_normals(h_, cloud.features.data(), kept, normals_knn_, orient_, sensor_, cloud.normals.data());
+  if (rc != LSGPU_OK) {
+    cloud.normals.clear();
+    throw DeviceError(std::string("lsgpu_icp_reading_normals: ") + lsgpu_strerror(rc) + " [" + lsgpu_last_error(h_) + "]");
+  }
+}
+
+inline void DataPointsFilters::applyPointModules(DataPoints& cloud, int64_t n) {
   std::vector<float> out((size_t)std::max<int64_t>(n, 1) * 4);
   int64_t m = 0;
   // A cloud with descriptors (normals): the device filters look at x, y, z only and carry the 4th component through, so

@@ -87,7 +87,10 @@ class IncrementalEstimator {
     first_association_sigmas_ = {0.05, 0.05, 0.05, 0.015, 0.015, 0.015};
     // incremental_estimator.cpp:49-59: the loop-closure ICP uses the lidar-odometry configuration
     std::ifstream ifs(params_.laser_track_params.icp_configuration_file.c_str());
-    if (!params_.laser_track_params.icp_configuration_file.empty() && ifs.good()) icp_.loadFromYaml(ifs);
+    // (sub-maps of scans whose input chain gave them normals carry those: the same declaration as the tracks')
+    const unsigned carried = !laser_tracks_.empty() && laser_tracks_[0]->inputFilters().producesNormals()
+                                 ? (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE) : 0u;
+    if (!params_.laser_track_params.icp_configuration_file.empty() && ifs.good()) icp_.loadFromYaml(ifs, carried);
     else icp_.setDefault();
   }
 

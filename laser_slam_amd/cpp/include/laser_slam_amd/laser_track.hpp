@@ -17,6 +17,7 @@
 #pragma once
 #include <algorithm>
 #include <chrono>
+#include <exception>
 #include <fstream>
 #include <map>
 #include <mutex>
@@ -118,13 +119,21 @@ class LaserTrack {
   explicit LaserTrack(const LaserTrackParams& parameters, unsigned int laser_track_id = 0u)
       : params_(parameters), laser_track_id_(laser_track_id), icp_(parameters.device) {
     // laser_track.cpp:14-21: YAML if readable, otherwise the default chain
+    // An input chain that ends with SurfaceNormalDataPointsFilter gives every stored scan its normals: both of compute()'s
+    // clouds carry them, and the ICP file is read under that declaration (it may then have no normals module).  So the
+    // input chain is read first; what it throws is kept until the ICP file has had its say, as in the order upstream reads them
+    std::exception_ptr filters_error;
+    try {
+      std::ifstream ifs_filters(params_.icp_input_filters_file.c_str());
+      if (!ifs_filters.good()) throw ConfigError("Could not open ICP input filters configuration file.");
+      input_filters_ = DataPointsFilters(ifs_filters, params_.device, /*normals_tail*/ true);
+    } catch (...) { filters_error = std::current_exception(); }
+    const unsigned carried = !filters_error && input_filters_.producesNormals() ? (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE) : 0u;
     std::ifstream ifs(params_.icp_configuration_file.c_str());
-    if (!params_.icp_configuration_file.empty() && ifs.good()) icp_.loadFromYaml(ifs);
+    if (!params_.icp_configuration_file.empty() && ifs.good()) icp_.loadFromYaml(ifs, carried);
     else icp_.setDefault();
     // laser_track.cpp:24-30: the input filter chain; LOG(FATAL) upstream if the file cannot be opened
-    std::ifstream ifs_filters(params_.icp_input_filters_file.c_str());
-    if (!ifs_filters.good()) throw ConfigError("Could not open ICP input filters configuration file.");
-    input_filters_ = DataPointsFilters(ifs_filters, params_.device);
+    if (filters_error) std::rethrow_exception(filters_error);
     trajectory_.setFirstKey((Key)laser_track_id_ << 40);  // per-track key range
   }
 

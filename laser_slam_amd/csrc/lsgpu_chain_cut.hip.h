@@ -13,6 +13,7 @@
 //                            k_cut_pass<1>  rank of `pre` -> the point's draw; keep = pre && draw < prob && post; counts keep
 //                            scan
 //                            k_cut_pass<2>  the same again, rank of keep, out[rank] = p
+//   a cloud with normals     k_cut_pass<2, RS, true> in place of k_cut_pass<2, RS>: the normal of a kept point goes with it
 // plus the one k_to_host launch that sends the totals.  There is no flag array and no per-point scan: the rank inside a block
 // is a wave64 ballot + popcount and four wave totals in LDS, the only arrays are the nb block counts and their offsets.  The
 // predicate is evaluated two or three times per point instead -- it is a handful of compares on a float4 the compaction
@@ -78,11 +79,15 @@ __device__ __forceinline__ uint32_t cut_block_rank(bool flag, uint32_t* ws, uint
 // the block's kept points.  STAGE 2: the kept points to out, order preserved.  RS: the section has RandomSampling -- off_pre
 // = exclusive scan of stage 0's counts, off_keep = of stage 1's; without it the kept points are `pre` and off_keep is the
 // scan of stage 0's counts.  draws: at least as many as `pre` can count (n).  out: room for n points; not src.
-template <int STAGE, bool RS>
+// NRM (stage 2 of a cloud that carries normals somebody reads; include/lsgpu_icp.h, "carried normals"): the point's normal goes
+// with it, out_nrm[3 rank ..] = nrm[3 i ..] -- nrm: 3 floats per point of src, out_nrm: room for 3 n floats, not nrm.  No other
+// stage reads a normal.
+template <int STAGE, bool RS, bool NRM = false>
 __global__ __launch_bounds__(256) void k_cut_pass(const float4* __restrict__ src, int n, CutSectionDev cs,
                                                   const float* __restrict__ draws, float prob,
                                                   const uint32_t* __restrict__ off_pre, const uint32_t* __restrict__ off_keep,
-                                                  uint32_t* __restrict__ cnt, float4* __restrict__ out) {
+                                                  uint32_t* __restrict__ cnt, float4* __restrict__ out,
+                                                  const float* __restrict__ nrm, float* __restrict__ out_nrm) {
   __shared__ uint32_t ws_pre[4], ws_keep[4];
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -113,7 +118,14 @@ __global__ __launch_bounds__(256) void k_cut_pass(const float4* __restrict__ src
     if (threadIdx.x == 0) cnt[blockIdx.x] = total;
     return;
   }
-  if (keep) out[off_keep[blockIdx.x] + rk] = p;
+  if (!keep) return;
+  const uint32_t at = off_keep[blockIdx.x] + rk;
+  out[at] = p;
+  if (NRM) {
+    const float* a = nrm + 3 * (size_t)i;
+    float* o = out_nrm + 3 * (size_t)at;
+    o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
+  }
 }
 
 }  // namespace lsgpu

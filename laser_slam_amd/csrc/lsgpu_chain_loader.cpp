@@ -62,6 +62,10 @@ struct Load {
   lsgpu_shadow_config shadow;             // ShadowDataPointsFilter of the two sections (lsgpu_chain_load_shadow): beside stage[], not in it
   lsgpu_cov_sampling_config cov_sampling; // CovarianceSamplingDataPointsFilter of the two sections (lsgpu_chain_load_cov_sampling): likewise
   lsgpu_motion_config motion;             // force2D / force4DOF of PointToPlaneErrorMinimizer, BoundTransformationChecker (lsgpu_chain_load_motion)
+  // lsgpu_chain_load_carried: the caller's clouds carry normals (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE).
+  // ref_module: the reference's section has a normals module of its own (stage[1] may also come from a carried pair)
+  unsigned carried = 0;
+  bool ref_module = false;
 
   std::string name() const { return m->name; }
   int side() const { return std::strcmp(m->section, "readingDataPointsFilters") == 0 ? 0 : 1; }
@@ -187,12 +191,12 @@ void sampling_surface_normal(Load& l) {
   l.out.chain.ssn_knn = l.truncated("knn", 7);
   l.out.chain.ssn_ratio = (float)l.finite("ratio", 0.5);
   if (l.truncated("samplingMethod", 0) != 0) refuse(l.name() + ": samplingMethod != 0 is not implemented");
-  l.stage[1] = 1;
+  l.stage[1] = 1; l.ref_module = true;
 }
 void reference_normals(Load& l) {
   if (l.stage[1]) refuse(kOneReference);
   l.out.chain.sn_knn = surface_normal_knn(l, &l.ref_densities);
-  l.stage[1] = 1;
+  l.stage[1] = 1; l.ref_module = true;
 }
 // MaxDensityDataPointsFilter: directly behind the reference's SurfaceNormalDataPointsFilter with keepDensities 1, in front of the
 // orientation pair, once.  The two slots of lsgpu_loaded_chain.reserved
@@ -219,7 +223,7 @@ void shadow_filter(Load& l) {
   const std::string n = l.name();
   const int s = l.side();
   const std::string sec = std::string(l.m->section) + ": ";
-  if (l.stage[s] < (s == 0 ? 2 : 1))
+  if (l.stage[s] < (s == 0 ? 2 : 1) || (s == 1 && !l.ref_module))   // (carried normals do not count: the module's own)
     refuse(sec + n + " needs the normals: it may stand only behind " +
            (s == 0 ? "the reading's SurfaceNormalDataPointsFilter" : "SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter") +
            " (a chain with no such module in the section cannot run it)");
@@ -237,7 +241,7 @@ void cov_sampling_filter(Load& l) {
   const std::string n = l.name();
   const int s = l.side();
   const std::string sec = std::string(l.m->section) + ": ";
-  if (l.stage[s] < (s == 0 ? 2 : 1))
+  if (l.stage[s] < (s == 0 ? 2 : 1) || (s == 1 && !l.ref_module))   // (carried normals do not count: the module's own)
     refuse(sec + n + " needs the normals: it may stand only behind " +
            (s == 0 ? "the reading's SurfaceNormalDataPointsFilter" : "SamplingSurfaceNormalDataPointsFilter or SurfaceNormalDataPointsFilter") +
            " (a chain with no such module in the section cannot run it)");
@@ -252,7 +256,9 @@ void cov_sampling_filter(Load& l) {
 }
 void observation_direction(Load& l) {
   const int s = l.side();
-  if (l.stage[s] != (s == 0 ? 2 : 1)) refuse(std::string(l.m->section) + ": " + l.name() + kPair);
+  // (a carried reference: the pair may stand without a module, on the normals the cloud brings along)
+  const bool on_carried = s == 1 && l.stage[1] == 0 && (l.carried & LSGPU_CARRIED_REFERENCE) != 0;
+  if (l.stage[s] != (s == 0 ? 2 : 1) && !on_carried) refuse(std::string(l.m->section) + ": " + l.name() + kPair);
   float* sensor = s == 0 ? l.out.normals.reading_sensor : l.out.normals.reference_sensor;
   const char* keys[3] = {"x", "y", "z"};
   for (int i = 0; i < 3; ++i) {
@@ -429,7 +435,8 @@ constexpr int kNumRows = (int)(sizeof(kRows) / sizeof(kRows[0]));
 void finish(Load& l) {
   lsgpu_loaded_chain& o = l.out;
   if (l.ref_densities && !l.max_density) refuse(kDensitiesAlone);
-  const int have_normals = l.stage[1] != 0;
+  const int have_normals = l.stage[1] != 0 || (l.carried & LSGPU_CARRIED_REFERENCE) != 0;
+  if ((l.carried & LSGPU_CARRIED_READING) && o.normals.max_angle >= 0.f && o.normals.reading_sn_knn == 0) o.normals.reading_normals_given = 1;
   if (!l.matcher) refuse("matcher: KDTreeMatcher is required");
   if (!l.minimizer) refuse("errorMinimizer: PointToPlaneErrorMinimizer, PointToPlaneWithCovErrorMinimizer or PointToPointErrorMinimizer is required");
   if (!have_normals && o.icp.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT)
@@ -471,7 +478,8 @@ void finish(Load& l) {
   o.has_normals = o.normals.max_angle >= 0.f || o.normals.reading_sn_knn != 0 || o.normals.reading_orient != 0 || o.normals.reference_orient != 0;
 }
 
-void load(const lsgpu_yaml_module* mods, int n_mods, Load& l) {
+void load(const lsgpu_yaml_module* mods, int n_mods, Load& l, unsigned carried) {
+  l.carried = carried;
   // libpointmatcher's loadFromYaml starts from EMPTY chains: a section the file does not mention means "no such module",
   // not "the default module"
   std::memset(&l.out, 0, sizeof(l.out));
@@ -518,7 +526,8 @@ extern "C" {
 // the five entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts`, `shadow`, `motion` or
 // `cov_sampling`, the others NULL)
 static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, lsgpu_shadow_config* shadow,
-                     char* why, int why_cap, lsgpu_motion_config* motion = nullptr, lsgpu_cov_sampling_config* cov_sampling = nullptr) {
+                     char* why, int why_cap, lsgpu_motion_config* motion = nullptr, lsgpu_cov_sampling_config* cov_sampling = nullptr,
+                     unsigned carried = 0) {
   if (why && why_cap > 0) why[0] = '\0';
   if ((!chain && !cuts && !shadow && !motion && !cov_sampling) || n_mods < 0 || (n_mods > 0 && !mods)) return LSGPU_BAD_ARG;
   for (int i = 0; i < n_mods; ++i) {
@@ -528,7 +537,7 @@ static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_cha
   }
   try {
     Load l;
-    load(mods, n_mods, l);
+    load(mods, n_mods, l, carried);
     if (chain) *chain = l.out;
     if (cuts) *cuts = l.cuts;
     if (shadow) *shadow = l.shadow;
@@ -566,6 +575,42 @@ int lsgpu_chain_load_motion(const lsgpu_yaml_module* mods, int n_mods, lsgpu_mot
 int lsgpu_chain_load_cov_sampling(const lsgpu_yaml_module* mods, int n_mods, lsgpu_cov_sampling_config* out, char* why, int why_cap) {
   if (why && why_cap > 0) why[0] = '\0';
   return out ? load_into(mods, n_mods, nullptr, nullptr, nullptr, why, why_cap, nullptr, out) : LSGPU_BAD_ARG;
+}
+
+int lsgpu_chain_load_carried(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_loaded_chain* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  if (!out || (carried & ~(unsigned)(LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE))) return LSGPU_BAD_ARG;
+  return load_into(mods, n_mods, out, nullptr, nullptr, why, why_cap, nullptr, nullptr, carried);
+}
+
+int lsgpu_chain_load_parts_carried(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_chain_cuts* cuts,
+                                   lsgpu_shadow_config* shadow, lsgpu_motion_config* motion, lsgpu_cov_sampling_config* cov_sampling,
+                                   char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  if (carried & ~(unsigned)(LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE)) return LSGPU_BAD_ARG;
+  return load_into(mods, n_mods, nullptr, cuts, shadow, why, why_cap, motion, cov_sampling, carried);
+}
+
+int lsgpu_surface_normal_params_check(const lsgpu_yaml_param* params, int n_params, int* knn, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  if (n_params < 0 || (n_params > 0 && !params)) return LSGPU_BAD_ARG;
+  for (int p = 0; p < n_params; ++p)
+    if (!params[p].key || !params[p].value) return LSGPU_BAD_ARG;
+  const lsgpu_yaml_module m = {"readingDataPointsFilters", "SurfaceNormalDataPointsFilter", params, n_params, 0};
+  try {
+    for (int p = 0; p < n_params; ++p)
+      if (!listed(kSurfaceNormalParams, params[p].key)) refuse(std::string(m.name) + ": unknown parameter " + params[p].key);
+    Load l;
+    l.m = &m;
+    const int k = surface_normal_knn(l, nullptr);
+    if (knn) *knn = k;
+    return LSGPU_OK;
+  } catch (const Refusal& r) {
+    if (why && why_cap > 0) std::snprintf(why, (size_t)why_cap, "%s", r.why.c_str());
+    return LSGPU_BAD_CONFIG;
+  } catch (const std::exception&) {
+    return LSGPU_BAD_ARG;
+  }
 }
 
 int lsgpu_loaded_chain_max_density(const lsgpu_loaded_chain* c, float* max_density) {

@@ -28,6 +28,7 @@
 #include "lsgpu_tuning.h"
 #include "lsgpu_policy.h"
 #include "lsgpu_section_plan.h"
+#include "lsgpu_submap.hip.h"
 #include "lsgpu_knn.hip.h"
 #include "lsgpu_knn_k.hip.h"
 #include "lsgpu_snf.hip.h"
@@ -361,6 +362,7 @@ struct lsgpu_icp {
   lsgpu_chain_cuts cuts{};
   DevBuf<uint32_t> cut_blk;   // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
   DevBuf<float4> cut_ref;     // the reference behind its cut modules
+  DevBuf<float> cut_ref_nrm;  // ... and its carried normals, when somebody reads them
   // MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 (lsgpu_icp_set_max_density; lsgpu_max_density.hip.h)
   bool md_on = false;
   lsgpu_max_density_config md_cfg{};
@@ -400,7 +402,11 @@ struct lsgpu_icp {
   PinBuf<float> draws_pinned;     // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
+  std::vector<DevBuf<float>> cloud_nrm;   // the normals a slot carries (lsgpu_cloud_upload_normals), 3 floats per point
+  std::vector<char> cloud_has_nrm;        // the slot carries normals
   DevBuf<float4> submap;               // assembled reference of lsgpu_icp_compute_clouds
+  DevBuf<float> submap_nrm;            // ... and its normals: every member carries some and somebody reads them
+  DevBuf<float> car_ref_nrm, car_rd_nrm;   // a compute's carried normals where the caller's cannot be used in place (host memory; the orientation writes)
 
   // reading
   int64_t nq = 0;
@@ -2271,29 +2277,39 @@ static CutSectionDev cut_section_of(const lsgpu_chain_cuts& c, int side, bool rs
 // A filter section in one pass on the current lane (lsgpu_chain_cut.hip.h): src (n points, device) -> the kept points at the
 // front of dst (device, room for n, not src), order preserved; rs: keep = pre && draws[rank of pre] < prob && post, `draws`
 // (device) holding at least n.  The launches are the same whatever cs holds; the totals are on their way to the host ...
+// nrm / dst_nrm (device, both or neither): the normals beside src, kept with their points (dst_nrm: room for 3 n, not nrm)
 static int cut_section_enqueue(lsgpu_icp* h, const CutSectionDev& cs, bool rs, float prob, const float* draws, const float4* src,
-                               int64_t n, float4* dst) {
+                               int64_t n, float4* dst, const float* nrm = nullptr, float* dst_nrm = nullptr) {
   const int nb = nblk(n);
   const size_t row = ((size_t)nb + 3) & ~(size_t)3;
   HIPC(h->cut_blk.reserve(4 * row));
   uint32_t *cnt_a = h->cut_blk.p, *off_a = cnt_a + row, *cnt_b = off_a + row, *off_b = cnt_b + row;
   hipStream_t st = h->lane.stream;
+  const float* const no_nrm = nullptr; float* const no_out_nrm = nullptr;
   hipLaunchKernelGGL((k_cut_pass<0, false>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, (const float*)nullptr, 0.f,
-                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, cnt_a, (float4*)nullptr);
+                     (const uint32_t*)nullptr, (const uint32_t*)nullptr, cnt_a, (float4*)nullptr, no_nrm, no_out_nrm);
   int rc = scan_u32(h, cnt_a, off_a, (size_t)nb);
   if (rc) return rc;
   if (!rs) {
+    if (nrm)
+      hipLaunchKernelGGL((k_cut_pass<2, false, true>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, (const float*)nullptr, 0.f,
+                         (const uint32_t*)nullptr, (const uint32_t*)off_a, (uint32_t*)nullptr, dst, nrm, dst_nrm);
+    else
     hipLaunchKernelGGL((k_cut_pass<2, false>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, (const float*)nullptr, 0.f,
-                       (const uint32_t*)nullptr, (const uint32_t*)off_a, (uint32_t*)nullptr, dst);
+                       (const uint32_t*)nullptr, (const uint32_t*)off_a, (uint32_t*)nullptr, dst, no_nrm, no_out_nrm);
     HIPC(hipGetLastError());
     return scan_totals_enqueue(h, nullptr, nullptr, 0, cnt_a, off_a, (size_t)nb);
   }
   hipLaunchKernelGGL((k_cut_pass<1, true>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, draws, prob, (const uint32_t*)off_a,
-                     (const uint32_t*)nullptr, cnt_b, (float4*)nullptr);
+                     (const uint32_t*)nullptr, cnt_b, (float4*)nullptr, no_nrm, no_out_nrm);
   rc = scan_u32(h, cnt_b, off_b, (size_t)nb);
   if (rc) return rc;
+  if (nrm)
+    hipLaunchKernelGGL((k_cut_pass<2, true, true>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, draws, prob, (const uint32_t*)off_a,
+                       (const uint32_t*)off_b, (uint32_t*)nullptr, dst, nrm, dst_nrm);
+  else
   hipLaunchKernelGGL((k_cut_pass<2, true>), dim3(nb), dim3(256), 0, st, src, (int)n, cs, draws, prob, (const uint32_t*)off_a,
-                     (const uint32_t*)off_b, (uint32_t*)nullptr, dst);
+                     (const uint32_t*)off_b, (uint32_t*)nullptr, dst, no_nrm, no_out_nrm);
   HIPC(hipGetLastError());
   return scan_totals_enqueue(h, cnt_a, off_a, (size_t)nb, cnt_b, off_b, (size_t)nb);
 }
@@ -2831,8 +2847,15 @@ int lsgpu_icp_get_reference_normals(lsgpu_icp* h, float* out_normals, int64_t ca
 }
 
 // one reference filter module, knn in [3, 32]; or none on a point-to-point handle, which needs no normals
-static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain) {
-  return lsgpu_chain_config_check(chain, h->cfg.error_minimizer) == LSGPU_OK;
+// (ref_carried: the reference carries normals of its own, which stand in for the module's)
+static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain, bool ref_carried = false) {
+  return lsgpu_chain_config_check(chain, ref_carried ? LSGPU_MINIMIZER_POINT_TO_POINT : h->cfg.error_minimizer) == LSGPU_OK;
+}
+// somebody behind the reference's section reads its normals: the minimizer, the robust filter's residuals, the angle filter
+static bool reference_normals_read(const lsgpu_icp* h) {
+  const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
+  const bool na_filter = h->normals_on && h->normals.max_angle >= 0.f;
+  return h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter;
 }
 
 }  // extern "C"
@@ -2847,6 +2870,9 @@ struct ComputeRun {
   // lsgpu_icp_compute_clouds_upload: the reading's H2D goes into its slot instead of the staging buffer, and the caller
   // learns whether it went out (it reads the flag after the return: the uploader is joined by then)
   float4* const upload_into; bool* const upload_enqueued;
+  // carried normals (include/lsgpu_icp.h): what the reading / the reference brings along, host or device, or nullptr; ref_nrm_owned:
+  // the reference's are a buffer of the handle's that this call may write (the assembled sub-map's)
+  const float* const rd_carried_nrm; const float* const ref_carried_nrm; const bool ref_nrm_owned;
   section::Plan plan;   // what the sections are made of (lsgpu_section_plan.h): check() asks, filter_reference() settles it
   const lsgpu_normals_config* nc = nullptr; double t0 = 0.0;
   DrawAhead draws; std::thread uploader; hipError_t upload_err = hipSuccess;
@@ -2857,7 +2883,8 @@ struct ComputeRun {
   AlignExtras extras{};   // what finish() tells the align
   // lsgpu_icp_set_chain_cuts: the sections' cut modules.  rd_pre_cuts: some stand in front of RandomSampling, so the number of
   // draws the reading consumes is the number of points that reach it -- known when the pass's totals are on the host
-  const lsgpu_chain_cuts* cuts = nullptr; bool rd_cuts = false, ref_cuts = false, rd_rs = false, rd_pre_cuts = false;
+  // rd_pass: the reading's section runs as one cut pass -- it has cut modules, or RandomSampling on a reading whose normals travel
+  const lsgpu_chain_cuts* cuts = nullptr; bool rd_cuts = false, ref_cuts = false, rd_rs = false, rd_pre_cuts = false, rd_pass = false;
   int64_t nrc = 0; size_t rd_first_draw = 0;   // the reference's points behind its cut modules; the reading's first draw
   // every return path drains the side stream, joins the uploader and drains its stream: a pinned host reading is read by DMA,
   // and the caller may free or reuse it as soon as this call has returned, error or not (after a completed alignment the
@@ -2869,7 +2896,12 @@ struct ComputeRun {
   }
 
   int check() {
-    if (!chain_ok(h, chain)) {
+    const bool ref_given = ref_carried_nrm != nullptr, rd_given = rd_carried_nrm != nullptr;
+    if ((ref_given || rd_given) && h->comm) {
+      h->err = "compute: carried normals are not implemented on a split-scan handle (lsgpu_icp_set_reference takes the reference's normals there)";
+      return LSGPU_BAD_CONFIG;
+    }
+    if (!chain_ok(h, chain, ref_given)) {
       h->err = "compute: one reference filter, ssn_knn or sn_knn in [3, 32] (none only with the point-to-point minimizer)";
       return LSGPU_BAD_CONFIG;
     }
@@ -2877,7 +2909,7 @@ struct ComputeRun {
     // who reads the reference normals behind the section: the minimizer, the robust filter's residuals, the angle filter
     const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
     const bool na_filter = nc && nc->max_angle >= 0.f;
-    if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0) {
+    if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0 && !ref_given) {
       h->err = "compute: SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter need the normals of a reference filter";
       return LSGPU_BAD_CONFIG;
     }
@@ -2888,6 +2920,7 @@ struct ComputeRun {
     in.ref_shadow = h->sh_on && h->sh_cfg.reference_eps >= 0.f; in.ref_cov_sampling = h->cs_on && h->cs_cfg.reference_nb_sample > 0;
     in.rd_normals = nc && nc->reading_sn_knn > 0;
     in.rd_shadow = h->sh_on && h->sh_cfg.reading_eps >= 0.f; in.rd_cov_sampling = h->cs_on && h->cs_cfg.reading_nb_sample > 0;
+    in.ref_carried = ref_given; in.rd_carried = rd_given && na_filter;   // (the reading's normals: the angle filter alone reads them)
     in.comm = h->comm != nullptr; in.side_switch = tuning().side_stream;
     plan = section::plan(in);
     if (plan.refusal) { h->err = plan.refusal; return LSGPU_BAD_CONFIG; }
@@ -2901,6 +2934,7 @@ struct ComputeRun {
     rd_rs = chain->reading_prob >= 0.f;
     rd_cuts = cuts && cuts->n_reading > 0; ref_cuts = cuts && cuts->n_reference > 0;
     rd_pre_cuts = rd_cuts && rd_rs && cut_section_of(*cuts, 0, true).n_pre > 0;
+    rd_pass = rd_cuts || (plan.rd_carried && rd_rs);
     return LSGPU_OK;
   }
 
@@ -2995,10 +3029,19 @@ struct ComputeRun {
 
   int filter_reference() {   // step 1: reference filter (yaml:5-7)
     nrc = nr;
+    // carried normals that somebody reads: on the device, and through the cut modules with their points
+    const bool carried = plan.source == section::Source::Carried;
+    const float* carried_nrm = nullptr;
+    if (carried) {
+      const int rc = stage_in(h, ref_carried_nrm, (size_t)3 * nr, h->car_ref_nrm, &carried_nrm);
+      if (rc) return rc;
+    }
     if (ref_cuts) {   // the cut modules stand in front of the normals module: the reference as handed over, before anything else
       HIPC(h->cut_ref.reserve(nr));
+      if (carried) HIPC(h->cut_ref_nrm.reserve((size_t)3 * nr));
       int64_t reached = 0;
-      int rc = cut_section_enqueue(h, cut_section_of(*cuts, 1, false), false, 0.f, nullptr, src, nr, h->cut_ref.p);
+      int rc = cut_section_enqueue(h, cut_section_of(*cuts, 1, false), false, 0.f, nullptr, src, nr, h->cut_ref.p,
+                                   carried_nrm, carried ? h->cut_ref_nrm.p : nullptr);
       if (!rc) rc = cut_section_wait(h, false, &reached, &nrc);   // (ssn_device and ref_build_front take the count on the host)
       if (!rc) rc = left_points(nrc);
       if (rc) return rc;
@@ -3007,7 +3050,17 @@ struct ComputeRun {
     }
     plan = section::settle(plan, h->cs_cfg.reference_nb_sample, nrc);   // (the count is on the host: the plan is final from here on)
     ref = {src, nullptr, nrc};   // (no normals module, or normals on the final grid: the reference as given, no draw)
-    if (plan.source == section::Source::Sampling) {
+    if (carried) {
+      // the reference's orientation pair flips normals where they stand: never in a buffer of the caller's
+      const bool in_place = ref_nrm_owned || carried_nrm == h->car_ref_nrm.p || !(nc && nc->reference_orient);
+      if (ref_cuts) ref.nrm = h->cut_ref_nrm.p;
+      else if (in_place) ref.nrm = const_cast<float*>(carried_nrm);
+      else {
+        HIPC(h->car_ref_nrm.reserve((size_t)3 * nr));
+        HIPC(hipMemcpyAsync(h->car_ref_nrm.p, carried_nrm, (size_t)nr * 12, hipMemcpyDeviceToDevice, h->stream));
+        ref.nrm = h->car_ref_nrm.p;
+      }
+    } else if (plan.source == section::Source::Sampling) {
       HIPC(h->flt_ref.reserve(nrc)); HIPC(h->flt_nrm.reserve(3 * nrc));
       int rc = ssn_device(h, src, nrc, chain->ssn_knn, chain->ssn_ratio, -1, h->flt_ref.p, h->flt_nrm.p, &ref.n, &draws);
       if (!rc) rc = left_points(ref.n);
@@ -3045,7 +3098,14 @@ struct ComputeRun {
       HIPC(hipStreamWaitEvent(h->lane.stream, h->copy_done, 0));
     }
     rd_dev = rd_src;
-    if (rd_cuts) {   // the section in one pass, RandomSampling (if any) inside it; the slot / the caller's cloud is only read
+    const float* rn = nullptr;   // the reading's carried normals on the device: kept with their points into h->rd_nrm
+    if (plan.rd_carried) {
+      const int rc = stage_in(h, rd_carried_nrm, (size_t)3 * nq, h->car_rd_nrm, &rn);
+      if (rc) return rc;
+      HIPC(h->rd_nrm.reserve((size_t)3 * nq));
+      extras.reading_normals = true;
+    }
+    if (rd_pass) {   // the section in one pass, RandomSampling (if any) inside it; the slot / the caller's cloud is only read
       HIPC(h->flt_rd.reserve(nq));
       rd_dev = h->flt_rd.p;
       const float* dr = nullptr;
@@ -3056,10 +3116,14 @@ struct ComputeRun {
         if (rcd) return rcd;
         dr = h->ssn_draws.p + rd_first_draw;
       }
-      const int rc = cut_section_enqueue(h, cut_section_of(*cuts, 0, rd_rs), rd_rs, chain->reading_prob, dr, rd_src, nq, h->flt_rd.p);
+      CutSectionDev cs;   // (RandomSampling alone: a section of no cut module)
+      std::memset(&cs, 0, sizeof(cs));
+      if (rd_cuts) cs = cut_section_of(*cuts, 0, rd_rs);
+      const int rc = cut_section_enqueue(h, cs, rd_rs, chain->reading_prob, dr, rd_src, nq, h->flt_rd.p, rn, rn ? h->rd_nrm.p : nullptr);
       return rc || defer_wait ? rc : reading_count_wait();
     }
     if (chain->reading_prob < 0.f) {
+      if (rn) HIPC(hipMemcpyAsync(h->rd_nrm.p, rn, (size_t)nq * 12, hipMemcpyDeviceToDevice, h->lane.stream));
       // no readingDataPointsFilters section: upstream runs no module at all -- every point, NO rand() call (a
       // RandomSampling module with prob 1 would consume nq draws and drop the points whose draw rounds to 1.0f)
       nqf = nq;
@@ -3073,7 +3137,7 @@ struct ComputeRun {
   // the host's wait for the number of reading points kept (current lane); with cut modules in front of RandomSampling also
   // for the number that reached it: the draws the call consumes are known, the stream can go
   int reading_count_wait() {
-    if (!rd_cuts) return compact_kept_wait(h, &nqf);
+    if (!rd_pass) return compact_kept_wait(h, &nqf);
     int64_t reached = 0;
     const int rc = cut_section_wait(h, rd_rs, &reached, &nqf);
     if (!rc && rd_pre_cuts) { draws.used = rd_first_draw + (size_t)reached; draws.commit_now(draws.used); }
@@ -3103,7 +3167,7 @@ struct ComputeRun {
   }
   int order_queries_on_side_lane() {
     LaneScope on_side(h, h->side_lane());
-    const int rc = (chain->reading_prob >= 0.f || rd_cuts) ? reading_count_wait() : LSGPU_OK;   // (the number of points kept)
+    const int rc = (chain->reading_prob >= 0.f || rd_pass) ? reading_count_wait() : LSGPU_OK;   // (the number of points kept)
     return rc || nqf <= 0 ? rc : prepare_queries(h, reinterpret_cast<const float*>(rd_dev), nqf, Mat34{}, /*gather*/ false);
   }
   int move_queries() {   // the mean is known and the main stream is busy -- now the queries' side
@@ -3202,12 +3266,13 @@ struct ComputeRun {
 // lsgpu_icp_compute, told by lsgpu_icp_compute_clouds_upload where the reading's upload goes (nullptr, nullptr otherwise)
 static int compute_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const float* reference_xyz1, int64_t nr,
                        const float T_init[16], const lsgpu_chain_config* chain, float T_out[16], lsgpu_icp_stats* stats,
-                       float4* upload_into, bool* upload_enqueued) {
+                       float4* upload_into, bool* upload_enqueued, const float* reading_normals = nullptr,
+                       const float* reference_normals = nullptr, bool ref_nrm_owned = false) {
   if (!h || !T_init || !T_out || !chain) return LSGPU_BAD_ARG;
   h->err.clear();
   std::memcpy(T_out, T_init, 16 * sizeof(float));
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  ComputeRun run{h, reading_xyz1, nq, reference_xyz1, nr, T_init, chain, upload_into, upload_enqueued};
+  ComputeRun run{h, reading_xyz1, nq, reference_xyz1, nr, T_init, chain, upload_into, upload_enqueued, reading_normals, reference_normals, ref_nrm_owned};
   int rc = run.check();
   if (!rc) rc = run.start_uploads();
   if (!rc) rc = run.filter_reference();
@@ -3224,6 +3289,12 @@ int lsgpu_icp_compute(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const
                       int64_t nr, const float T_init[16], const lsgpu_chain_config* chain,
                       float T_out[16], lsgpu_icp_stats* stats) {
   return compute_run(h, reading_xyz1, nq, reference_xyz1, nr, T_init, chain, T_out, stats, nullptr, nullptr);
+}
+
+int lsgpu_icp_compute_normals(lsgpu_icp* h, const float* reading_xyz1, const float* reading_normals, int64_t nq,
+                              const float* reference_xyz1, const float* reference_normals, int64_t nr, const float T_init[16],
+                              const lsgpu_chain_config* chain, float T_out[16], lsgpu_icp_stats* stats) {
+  return compute_run(h, reading_xyz1, nq, reference_xyz1, nr, T_init, chain, T_out, stats, nullptr, nullptr, reading_normals, reference_normals);
 }
 
 int lsgpu_filter_cylinder(lsgpu_icp* h, const float* xyz1, int64_t n, const float center[3], double radius_m,
@@ -3533,16 +3604,40 @@ int lsgpu_cloud_to_pointxyz(lsgpu_icp* h, const float* xyz1, int64_t n, unsigned
   return LSGPU_OK;
 }
 
-int lsgpu_cloud_upload(lsgpu_icp* h, int slot, const float* xyz1, int64_t n) {
+// the slot exists, holds nothing and carries no normals (whatever it held is gone from here on: a failed copy must not leave
+// a half-written cloud behind)
+static void cloud_slot_clear(lsgpu_icp* h, int slot) {
+  if ((size_t)slot >= h->clouds.size()) { h->clouds.resize((size_t)slot + 1); h->cloud_n.resize((size_t)slot + 1, -1); }
+  if (h->cloud_nrm.size() < h->clouds.size()) { h->cloud_nrm.resize(h->clouds.size()); h->cloud_has_nrm.resize(h->clouds.size(), 0); }
+  h->cloud_n[slot] = -1;
+  h->cloud_has_nrm[slot] = 0;
+}
+static bool cloud_has_normals(const lsgpu_icp* h, int slot) {
+  return slot >= 0 && (size_t)slot < h->cloud_has_nrm.size() && h->cloud_n[slot] >= 0 && h->cloud_has_nrm[slot] != 0;
+}
+
+int lsgpu_cloud_upload_normals(lsgpu_icp* h, int slot, const float* xyz1, const float* normals, int64_t n) {
   if (!h || slot < 0 || slot >= (1 << 20) || n < 0 || n > 0x7FFFFFF0ll || (n > 0 && !xyz1)) return LSGPU_BAD_ARG;
   h->err.clear();
   HIPC(hipSetDevice(h->device));
-  if ((size_t)slot >= h->clouds.size()) { h->clouds.resize((size_t)slot + 1); h->cloud_n.resize((size_t)slot + 1, -1); }
-  h->cloud_n[slot] = -1;   // (whatever the slot held is gone from here on: a failed copy must not leave a half-written cloud behind)
+  cloud_slot_clear(h, slot);
   HIPC(h->clouds[slot].reserve(n ? n : 1));
+  if (normals) HIPC(h->cloud_nrm[slot].reserve(n ? (size_t)3 * n : 1));
   if (n) HIPC(hipMemcpyAsync(h->clouds[slot].p, xyz1, (size_t)n * 16, hipMemcpyDefault, h->stream));
-  HIPC(hipStreamSynchronize(h->stream));  // the caller's buffer is free again on return
+  if (n && normals) HIPC(hipMemcpyAsync(h->cloud_nrm[slot].p, normals, (size_t)n * 12, hipMemcpyDefault, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));  // the caller's buffers are free again on return
   h->cloud_n[slot] = n;
+  h->cloud_has_nrm[slot] = normals ? 1 : 0;
+  return LSGPU_OK;
+}
+
+int lsgpu_cloud_upload(lsgpu_icp* h, int slot, const float* xyz1, int64_t n) {
+  return lsgpu_cloud_upload_normals(h, slot, xyz1, nullptr, n);
+}
+
+int lsgpu_cloud_has_normals(lsgpu_icp* h, int slot, int* has) {
+  if (!h || !has || slot < 0) return LSGPU_BAD_ARG;
+  *has = cloud_has_normals(h, slot) ? 1 : 0;
   return LSGPU_OK;
 }
 
@@ -3552,6 +3647,7 @@ int lsgpu_cloud_release(lsgpu_icp* h, int slot) {
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   h->clouds[slot].release();
+  if ((size_t)slot < h->cloud_nrm.size()) { h->cloud_nrm[slot].release(); h->cloud_has_nrm[slot] = 0; }
   h->cloud_n[slot] = -1;
   return LSGPU_OK;
 }
@@ -3588,6 +3684,68 @@ static int assemble_submap(lsgpu_icp* h, const int* ref_slots, const float* ref_
   return LSGPU_OK;
 }
 
+static bool is_identity16(const float* T) {
+  if (!T) return true;
+  bool identity = true;
+  for (int k = 0; k < 16; ++k) identity = identity && T[k] == ((k % 5 == 0) ? 1.f : 0.f);
+  return identity;
+}
+// ... of members that all carry normals somebody reads: points and normals in one launch (lsgpu_submap.hip.h); more members
+// than its table holds: one launch per member
+static int assemble_submap_normals(lsgpu_icp* h, const int* ref_slots, const float* ref_T, int n_ref, int64_t total) {
+  HIPC(h->submap.reserve(total)); HIPC(h->submap_nrm.reserve((size_t)3 * total));
+  SubmapTable tab;
+  std::memset(&tab, 0, sizeof(tab));
+  const bool one_launch = n_ref <= kSubmapMembers;
+  auto launch = [&]() {
+    const int64_t count = (int64_t)tab.first[tab.n] - (int64_t)tab.first[0];
+    if (count > 0) hipLaunchKernelGGL(k_assemble_submap, dim3(nblk(count)), dim3(256), 0, h->stream, tab, h->submap.p, h->submap_nrm.p);
+  };
+  int64_t off = 0;
+  for (int i = 0; i < n_ref; ++i) {
+    const int slot = ref_slots[i];
+    const int64_t n = h->cloud_n[slot];
+    if (!n && !one_launch) continue;
+    const float* T = ref_T ? ref_T + 16 * i : nullptr;
+    const bool identity = is_identity16(T);
+    if (n && !identity && !lsgpu_check_rigid(T)) { h->err = "compute_clouds: a sub-map transform is not rigid"; return LSGPU_BAD_ARG; }
+    if (!one_launch) { std::memset(&tab, 0, sizeof(tab)); }
+    const int m = tab.n++;
+    tab.first[m] = (uint32_t)off; tab.first[m + 1] = (uint32_t)(off + n);
+    tab.pts[m] = h->clouds[slot].p; tab.nrm[m] = h->cloud_nrm[slot].p;
+    tab.identity[m] = identity ? 1 : 0;
+    if (!identity) tab.T[m] = to_mat34(T);
+    off += n;
+    if (!one_launch) launch();
+  }
+  if (one_launch && tab.n > 0) launch();
+  HIPC(hipGetLastError());
+  return LSGPU_OK;
+}
+// Which of the two: the sub-map has normals iff every member carries some, and they are assembled iff the chain has no
+// reference module (a module overwrites them) and somebody reads the reference's normals.  *with_normals tells; a member
+// without normals among members with them, where they would be read, is refused by its slot
+static int assemble_reference(lsgpu_icp* h, const int* ref_slots, const float* ref_T, int n_ref, int64_t total,
+                              const lsgpu_chain_config* chain, bool* with_normals) {
+  *with_normals = false;
+  bool all = n_ref > 0, any = false;
+  int without = -1;
+  for (int i = 0; i < n_ref; ++i) {
+    const bool has = cloud_has_normals(h, ref_slots[i]);
+    all = all && has; any = any || has;
+    if (!has && without < 0) without = ref_slots[i];
+  }
+  const bool wanted = chain->ssn_knn == 0 && chain->sn_knn == 0 && reference_normals_read(h);
+  if (wanted && any && !all) {
+    h->err = "compute_clouds: reference slot " + std::to_string(without) + " carries no normals: the sub-map has none (every member must "
+             "carry some), and the chain reads the reference's normals without a reference filter (ssn_knn or sn_knn)";
+    return LSGPU_BAD_CONFIG;
+  }
+  if (!(wanted && all)) return assemble_submap(h, ref_slots, ref_T, n_ref, total);
+  *with_normals = true;
+  return assemble_submap_normals(h, ref_slots, ref_T, n_ref, total);
+}
+
 int lsgpu_icp_compute_clouds(lsgpu_icp* h, int reading_slot, const int* ref_slots, const float* ref_T,
                              int n_ref, const float T_init[16], const lsgpu_chain_config* chain,
                              float T_out[16], lsgpu_icp_stats* stats) {
@@ -3609,13 +3767,25 @@ int lsgpu_icp_compute_clouds(lsgpu_icp* h, int reading_slot, const int* ref_slot
     return LSGPU_NO_CONVERGENCE;
   }
   HIPC(hipSetDevice(h->device));
+  bool with_normals = false;
   {
-    const int rca = assemble_submap(h, ref_slots, ref_T, n_ref, total);
+    const int rca = assemble_reference(h, ref_slots, ref_T, n_ref, total, chain, &with_normals);
     if (rca) return rca;
   }
   // (the assembly is stream-ordered: its time is part of compute's filter time, stats->t_reserved[0])
   return compute_run(h, reinterpret_cast<const float*>(h->clouds[reading_slot].p), h->cloud_n[reading_slot],
-                     reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats, nullptr, nullptr);
+                     reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats, nullptr, nullptr,
+                     cloud_has_normals(h, reading_slot) ? h->cloud_nrm[reading_slot].p : nullptr,
+                     with_normals ? h->submap_nrm.p : nullptr, /*ref_nrm_owned*/ true);
+}
+
+int lsgpu_icp_compute_clouds_upload_normals(lsgpu_icp* h, int reading_slot, const float* reading_xyz1, const float* reading_normals,
+                                            int64_t nq, const int* ref_slots, const float* ref_T, int n_ref, const float T_init[16],
+                                            const lsgpu_chain_config* chain, float T_out[16], lsgpu_icp_stats* stats) {
+  if (!h || !T_init || !T_out || !chain || n_ref < 0 || (n_ref > 0 && !ref_slots)) return LSGPU_BAD_ARG;
+  const int rcu = lsgpu_cloud_upload_normals(h, reading_slot, reading_xyz1, reading_normals, nq);
+  if (rcu) return rcu;
+  return lsgpu_icp_compute_clouds(h, reading_slot, ref_slots, ref_T, n_ref, T_init, chain, T_out, stats);
 }
 
 // lsgpu_cloud_upload(reading_slot) + lsgpu_icp_compute_clouds in one call: the new scan crosses PCIe WHILE the sub-map --
@@ -3636,7 +3806,9 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
     fused = have(ref_slots[i]) && ref_slots[i] != reading_slot;
     if (fused) total += h->cloud_n[ref_slots[i]];
   }
-  fused = fused && total > 0 && total <= 0x7FFFFFF0ll && chain_ok(h, chain);   // (ssn_knn 0: point-to-point without a reference filter)
+  bool ref_all_nrm = n_ref > 0;
+  for (int i = 0; i < n_ref && fused; ++i) ref_all_nrm = ref_all_nrm && cloud_has_normals(h, ref_slots[i]);
+  fused = fused && total > 0 && total <= 0x7FFFFFF0ll && chain_ok(h, chain, ref_all_nrm);   // (ssn_knn 0: point-to-point without a reference filter)
   if (!fused) {   // nothing to overlap (or nothing to match against): the two calls, one after the other
     const int rcu = lsgpu_cloud_upload(h, reading_slot, reading_xyz1, nq);
     if (rcu) return rcu;
@@ -3646,11 +3818,11 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
   std::memcpy(T_out, T_init, 16 * sizeof(float));
   if (stats) std::memset(stats, 0, sizeof(*stats));
   HIPC(hipSetDevice(h->device));
-  if ((size_t)reading_slot >= h->clouds.size()) { h->clouds.resize((size_t)reading_slot + 1); h->cloud_n.resize((size_t)reading_slot + 1, -1); }
-  h->cloud_n[reading_slot] = -1;
+  cloud_slot_clear(h, reading_slot);   // (this entry stores points only: the slot's normals are dropped, as by lsgpu_cloud_upload)
   HIPC(h->clouds[reading_slot].reserve(nq));
+  bool with_normals = false;
   {
-    const int rca = assemble_submap(h, ref_slots, ref_T, n_ref, total);
+    const int rca = assemble_reference(h, ref_slots, ref_T, n_ref, total, chain, &with_normals);
     if (rca) {   // (a sub-map transform that is not rigid: the scan is stored all the same)
       const std::string why = h->err;
       const int rcu = lsgpu_cloud_upload(h, reading_slot, reading_xyz1, nq);
@@ -3660,7 +3832,7 @@ int lsgpu_icp_compute_clouds_upload(lsgpu_icp* h, int reading_slot, const float*
   }
   bool upload_enqueued = false;
   const int rc = compute_run(h, reading_xyz1, nq, reinterpret_cast<const float*>(h->submap.p), total, T_init, chain, T_out, stats,
-                             h->clouds[reading_slot].p, &upload_enqueued);
+                             h->clouds[reading_slot].p, &upload_enqueued, nullptr, with_normals ? h->submap_nrm.p : nullptr, /*ref_nrm_owned*/ true);
   if (!upload_enqueued) {   // the call returned before its upload went out: the plain copy, so that the slot holds the scan
     const std::string why = h->err;
     HIPC(hipMemcpyAsync(h->clouds[reading_slot].p, reading_xyz1, (size_t)nq * 16, hipMemcpyDefault, h->stream));

@@ -24,6 +24,9 @@ struct Inputs {
   bool normals_read = false;
   bool max_density = false, ref_shadow = false, ref_cov_sampling = false;
   bool rd_normals = false, rd_shadow = false, rd_cov_sampling = false;   // the reading's SurfaceNormalDataPointsFilter and what stands behind it
+  // the cloud handed over carries normals (include/lsgpu_icp.h, "carried normals"): read only where the section has no
+  // normals module of its own and somebody reads the side's normals -- the reading's: the angle filter alone
+  bool ref_carried = false, rd_carried = false;
   bool comm = false;          // split-scan mode
   bool side_switch = true;    // the tuning's side-stream switch
 };
@@ -33,7 +36,8 @@ enum class Source {
   Sampling,              // SamplingSurfaceNormalDataPointsFilter: its points and their normals, always together
   FinalGrid,             // SurfaceNormalDataPointsFilter on the grid the loop searches
   WholeCloud,            // ... on a grid of the whole cloud, built before the thinning
-  WholeCloudDensities    // ... with the densities MaxDensity reads
+  WholeCloudDensities,   // ... with the densities MaxDensity reads
+  Carried                // the cloud's own normals, beside its points like Sampling's: no module, no draws
 };
 
 enum class Stage { MaxDensity, Shadow, CovSampling };
@@ -48,6 +52,7 @@ struct Plan {
   ShadowNormals shadow_normals = ShadowNormals::NotRun;
   bool normals_on_final_grid = false;
   bool rd_normals = false, rd_shadow = false, rd_cov_sampling = false;
+  bool rd_carried = false;         // the reading's own normals go through its section with the points
   bool side = false;               // the reading's side may run on the side stream
 
   bool has(Stage s) const { for (int i = 0; i < n_stages; ++i) if (stages[i] == s) return true; return false; }
@@ -55,7 +60,7 @@ struct Plan {
   // the normals stand in the whole cloud's grid order and CovarianceSampling, which takes an array, is the first to read them
   bool normals_copied_out() const { return whole_cloud() && stages[0] == Stage::CovSampling; }
   // what the final grid build is handed beside the points
-  bool normals_to_build() const { return n_stages ? emits[n_stages - 1] : source == Source::Sampling; }
+  bool normals_to_build() const { return n_stages ? emits[n_stages - 1] : source == Source::Sampling || source == Source::Carried; }
   bool draws_per_reference_point() const { return source == Source::Sampling || has(Stage::MaxDensity); }
 };
 
@@ -79,9 +84,11 @@ inline Plan plan(const Inputs& in) {
   if (in.module == Module::Sampling) p.source = Source::Sampling;
   else if (in.module == Module::SurfaceNormal && p.n_stages) p.source = in.max_density ? Source::WholeCloudDensities : Source::WholeCloud;
   else if (read) p.source = Source::FinalGrid;
+  else if (no_normals && in.ref_carried && in.normals_read) p.source = Source::Carried;   // (no stage: each is refused above without a module)
   p.normals_on_final_grid = p.source == Source::FinalGrid;
   if (in.ref_shadow) p.shadow_normals = p.whole_cloud() && p.stages[0] == Stage::Shadow ? ShadowNormals::Gathered : ShadowNormals::Array;
   p.rd_normals = in.rd_normals; p.rd_shadow = in.rd_shadow; p.rd_cov_sampling = in.rd_cov_sampling;
+  p.rd_carried = in.rd_carried && !in.rd_normals;   // (a module overwrites what the cloud carries)
   // The reference's grid build and the reading's side (its filter, the queries' order) do not depend on each other: the latter
   // goes to a second stream.  Both are chains of short launches that leave most of the chip idle; side by side the shorter
   // one disappears (LSGPU_NO_SIDE_STREAM: one after the other).  Not with MaxDensity: the reading's first draw is known only

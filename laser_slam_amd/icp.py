@@ -359,6 +359,13 @@ class IcpHandle:
             _raise(rc, "lsgpu_icp_set_normals", self._h)
         self.normals = nc
 
+    def reads_reference_normals(self) -> bool:
+        """Does a module behind the reference's section read its normals: a minimizer other than point-to-point,
+        RobustOutlierFilter with the point-to-plane distance, or SurfaceNormalOutlierFilter."""
+        return (self.cfg.error_minimizer != _lib.MINIMIZER_POINT_TO_POINT
+                or (self.robust is not None and self.robust.distance_type == _lib.ROBUST_DIST["point2plane"])
+                or (self.normals is not None and self.normals.max_angle >= 0))
+
     def normal_angle_trace(self, cap: int = 64):
         """lsgpu_icp_get_normal_angle_trace: per iteration of the last align {rejected, eps}."""
         buf = (_lib.NormalAngleTrace * cap)()
@@ -554,20 +561,43 @@ class IcpHandle:
         return o[:m.value]
 
     def compute(self, reading_xyz1, reference_xyz1, T_init, reading_prob: float = 0.5, ssn_knn: int = 10,
-                ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0):
+                ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0, reading_normals=None, reference_normals=None):
         """``icp_.compute(reading, reference, T_init)`` entirely on the device: reference filter,
         set_reference, reading filter, align.  -> (T 4x4, IcpStats); raises ConvergenceError.
-        sn_knn > 0 (with ssn_knn 0): SurfaceNormalDataPointsFilter is the reference filter."""
+        sn_knn > 0 (with ssn_knn 0): SurfaceNormalDataPointsFilter is the reference filter.
+        reading_normals / reference_normals: the normals the clouds carry, (N, 3) beside the points
+        (lsgpu_icp_compute_normals; include/lsgpu_icp.h, "carried normals")."""
         q, _k1, nq = _as_f32(reading_xyz1, 4)
         r, _k2, nr = _as_f32(reference_xyz1, 4)
         ch = _lib.ChainCfg(reading_prob, ssn_knn, ssn_ratio, int(sn_knn), seed)
         ti = _t16(T_init)
         to = np.empty(16, np.float32)
         st = IcpStats()
-        rc = _lib.lib().lsgpu_icp_compute(self._h, q, nq, r, nr, _fp(ti), C.byref(ch), _fp(to), C.byref(st))
+        if reading_normals is None and reference_normals is None:
+            rc = _lib.lib().lsgpu_icp_compute(self._h, q, nq, r, nr, _fp(ti), C.byref(ch), _fp(to), C.byref(st))
+            if rc != _lib.OK:
+                _raise(rc, "lsgpu_icp_compute", self._h)
+            return to.reshape(4, 4).T.copy(), st
+        qn, _k3 = self._carried(reading_normals, nq, "reading_normals")
+        rn, _k4 = self._carried(reference_normals, nr, "reference_normals")
+        rc = _lib.lib().lsgpu_icp_compute_normals(self._h, q, qn, nq, r, rn, nr, _fp(ti), C.byref(ch), _fp(to), C.byref(st))
         if rc != _lib.OK:
-            _raise(rc, "lsgpu_icp_compute", self._h)
+            _raise(rc, "lsgpu_icp_compute_normals", self._h)
         return to.reshape(4, 4).T.copy(), st
+
+    @staticmethod
+    def _carried(normals, n: int, what: str):
+        """-> (address or None, keepalive) of the (n, 3) normals a cloud of n points carries.  An empty cloud's normals are
+        handed over by a valid address all the same: NULL means "carries none"."""
+        if normals is None:
+            return None, None
+        p, keep, m = _as_f32(normals, 3)
+        if m != n:
+            raise ValueError(f"{what}: {m} normals for {n} points")
+        if p is None:
+            keep = np.zeros((1, 3), np.float32)
+            p = keep.ctypes.data
+        return p, keep
 
     # ---- local-map maintenance (laser_slam_ros worker): cylinder crop, voxel grid
     def _filter_out(self, xyz1, n):
@@ -647,11 +677,23 @@ class IcpHandle:
         return o[:16 * n]
 
     # ---- clouds kept in HBM between calls; sub-map assembly on the device (laser_track.cpp:474-486)
-    def cloud_upload(self, slot: int, xyz1):
+    def cloud_upload(self, slot: int, xyz1, normals=None):
+        """normals: the (N, 3) normals the cloud carries (lsgpu_cloud_upload_normals); None: the slot carries none."""
         p, _k, n = _as_f32(xyz1, 4)
+        if normals is not None:
+            pn, _kn = self._carried(normals, n, "normals")
+            rc = _lib.lib().lsgpu_cloud_upload_normals(self._h, slot, p, pn, n)
+            if rc != _lib.OK:
+                _raise(rc, "lsgpu_cloud_upload_normals", self._h)
+            return
         rc = _lib.lib().lsgpu_cloud_upload(self._h, slot, p, n)
         if rc != _lib.OK:
             _raise(rc, "lsgpu_cloud_upload", self._h)
+
+    def cloud_has_normals(self, slot: int) -> bool:
+        has = C.c_int(0)
+        _lib.lib().lsgpu_cloud_has_normals(self._h, slot, C.byref(has))
+        return bool(has.value)
 
     def cloud_release(self, slot: int):
         _lib.lib().lsgpu_cloud_release(self._h, slot)
@@ -680,9 +722,10 @@ class IcpHandle:
         return to.reshape(4, 4).T.copy(), st
 
     def compute_clouds_upload(self, reading_slot: int, reading_xyz1, ref_slots, ref_T, T_init, reading_prob: float = 0.5,
-                              ssn_knn: int = 10, ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0):
+                              ssn_knn: int = 10, ssn_ratio: float = 0.5, seed: int = -1, sn_knn: int = 0, reading_normals=None):
         """upload_cloud(reading_slot, reading) + compute_clouds(reading_slot, ...) in one call: the host reading crosses
-        PCIe while the sub-map is assembled and filtered (the call shape of LaserTrack::localScanToSubMap)."""
+        PCIe while the sub-map is assembled and filtered (the call shape of LaserTrack::localScanToSubMap).
+        reading_normals: the scan is stored with its normals (lsgpu_icp_compute_clouds_upload_normals: upload, then compute)."""
         rd = np.ascontiguousarray(reading_xyz1, np.float32)
         k = len(ref_slots)
         slots = (C.c_int * max(k, 1))(*ref_slots)
@@ -693,6 +736,14 @@ class IcpHandle:
         ti = _t16(T_init)
         to = np.empty(16, np.float32)
         st = IcpStats()
+        if reading_normals is not None:
+            pn, _kn = self._carried(np.ascontiguousarray(reading_normals, np.float32), rd.shape[0], "reading_normals")
+            rc = _lib.lib().lsgpu_icp_compute_clouds_upload_normals(self._h, reading_slot, rd.ctypes.data if rd.size else None, pn,
+                                                                    rd.shape[0], slots, _fp(Ts) if Ts is not None else None, k,
+                                                                    _fp(ti), C.byref(ch), _fp(to), C.byref(st))
+            if rc != _lib.OK:
+                _raise(rc, "lsgpu_icp_compute_clouds_upload_normals", self._h)
+            return to.reshape(4, 4).T.copy(), st
         rc = _lib.lib().lsgpu_icp_compute_clouds_upload(self._h, reading_slot, _fp(rd), rd.shape[0], slots,
                                                         _fp(Ts) if Ts is not None else None, k, _fp(ti), C.byref(ch),
                                                         _fp(to), C.byref(st))
@@ -1458,14 +1509,29 @@ def _yaml_modules(doc):
     return arr, len(mods), keep
 
 
-def chain_load(doc):
+def chain_load(doc, carried: int = 0):
     """lsgpu_chain_load on a YAML chain document read with yaml.BaseLoader (every scalar stays text): its modules, section by
-    section in the document's order -> (return code, reason of a refusal, _lib.LoadedChain).  The rules are the library's."""
+    section in the document's order -> (return code, reason of a refusal, _lib.LoadedChain).  The rules are the library's.
+    carried != 0: lsgpu_chain_load_carried -- the caller's clouds carry normals (_lib.CARRIED_READING | _lib.CARRIED_REFERENCE)."""
     arr, n, _keep = _yaml_modules(doc)
     out = _lib.LoadedChain()
     why = C.create_string_buffer(512)
-    rc = _lib.lib().lsgpu_chain_load(arr, n, C.byref(out), why, len(why))
+    if carried:
+        rc = _lib.lib().lsgpu_chain_load_carried(arr, n, int(carried), C.byref(out), why, len(why))
+    else:
+        rc = _lib.lib().lsgpu_chain_load(arr, n, C.byref(out), why, len(why))
     return rc, why.value.decode(), out
+
+
+def chain_load_parts_carried(doc, carried: int):
+    """lsgpu_chain_load_parts_carried: what chain_load_cuts, _shadow, _motion and _cov_sampling give, for a caller whose clouds
+    carry normals -> (return code, reason of a refusal, _lib.ChainCuts, _lib.ShadowCfg, _lib.MotionCfg, _lib.CovSamplingCfg)."""
+    arr, n, _keep = _yaml_modules(doc)
+    cuts, shadow, motion, cs = _lib.ChainCuts(), _lib.ShadowCfg(), _lib.MotionCfg(), _lib.CovSamplingCfg()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load_parts_carried(arr, n, int(carried), C.byref(cuts), C.byref(shadow), C.byref(motion), C.byref(cs),
+                                                   why, len(why))
+    return rc, why.value.decode(), cuts, shadow, motion, cs
 
 
 def chain_load_cuts(doc):
@@ -1531,7 +1597,8 @@ def _chain_config(lc, cuts=None, shadow=None, motion=None, cov_sampling=None) ->
     if lc.has_normals:
         n = lc.normals
         ch.normals = NormalsConfig(_f32(n.max_angle), n.reading_sn_knn, n.reading_orient, n.reference_orient,
-                                   tuple(_f32(v) for v in n.reading_sensor), tuple(_f32(v) for v in n.reference_sensor))
+                                   tuple(_f32(v) for v in n.reading_sensor), tuple(_f32(v) for v in n.reference_sensor),
+                                   n.reading_normals_given)
     sd = C.c_float()
     if _lib.lib().lsgpu_loaded_chain_covariance(C.byref(lc), C.byref(sd)):
         ch.covariance = _f32(sd.value)
@@ -1557,6 +1624,7 @@ class ICP:
         self.chain = ChainConfig()
         self._handle: Optional[IcpHandle] = None
         self.last_stats: Optional[IcpStats] = None
+        self.carried = 0        # load_from_yaml's declaration: which clouds carry normals (_lib.CARRIED_*)
 
     # -- laser_track.cpp:20
     def set_default(self):
@@ -1566,9 +1634,11 @@ class ICP:
         self._handle = None
 
     # -- laser_track.cpp:17
-    def load_from_yaml(self, stream):
+    def load_from_yaml(self, stream, carried: int = 0):
         """stream: file object, path or YAML text.  Unsupported modules raise (bad config), as
-        PointMatcher's registrar does for unknown module names."""
+        PointMatcher's registrar does for unknown module names.
+        carried: which of compute's clouds carry normals (_lib.CARRIED_READING | _lib.CARRIED_REFERENCE): the chain may then
+        read normals without a module that computes them, and compute hands over the normals of the declared sides."""
         import yaml
         if hasattr(stream, "read"):
             text = stream.read()
@@ -1583,9 +1653,18 @@ class ICP:
             doc = {}
         if not isinstance(doc, dict):
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "not a YAML mapping")
-        rc, why, loaded = chain_load(doc)
+        rc, why, loaded = chain_load(doc, carried)
         if rc != _lib.OK:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+        if carried:
+            rc, why, cuts, shadow, motion, cov_sampling = chain_load_parts_carried(doc, carried)
+            if rc != _lib.OK:
+                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
+            self.chain = _chain_config(loaded, cuts, shadow, motion, cov_sampling)
+            self.carried = int(carried)
+            self._handle = None
+            return
+        self.carried = 0
         cuts = None
         if loaded.reserved[2] or loaded.reserved[3]:            # the document has cut modules: the modules themselves
             rc, why, cuts = chain_load_cuts(doc)
@@ -1637,11 +1716,20 @@ class ICP:
         return self.quality()["covariance"]
 
     # -- laser_track.cpp:496 / incremental_estimator.cpp:108
-    def compute(self, reading_xyz1, reference_xyz1, T_init) -> np.ndarray:
-        """T (4x4 float32) with p_reference = T p_reading.  Raises ConvergenceError."""
+    def compute(self, reading_xyz1, reference_xyz1, T_init, reading_normals=None, reference_normals=None) -> np.ndarray:
+        """T (4x4 float32) with p_reference = T p_reading.  Raises ConvergenceError.
+        reading_normals / reference_normals: handed over iff load_from_yaml declared that side as carrying normals."""
         h = self._ensure_handle()
         ch = self.chain
+        if not self.carried & _lib.CARRIED_READING:
+            reading_normals = None
+        if not self.carried & _lib.CARRIED_REFERENCE:
+            reference_normals = None
+        elif reference_normals is None and h.reads_reference_normals() and not (ch.surface_normal_knn or ch.reference_normal_knn):
+            raise LsgpuError(_lib.BAD_CONFIG, "compute", "the chain reads the reference's normals and the reference, declared as "
+                             "carrying normals, carries none")
         T, st = h.compute(reading_xyz1, reference_xyz1, T_init, ch.reading_sampling_prob,
-                          ch.surface_normal_knn, ch.surface_normal_ratio, ch.seed, ch.reference_normal_knn)
+                          ch.surface_normal_knn, ch.surface_normal_ratio, ch.seed, ch.reference_normal_knn,
+                          reading_normals=reading_normals, reference_normals=reference_normals)
         self.last_stats = st
         return T
