@@ -1,6 +1,6 @@
-"""The test-side ICP loop and the exact CPU k-NN it searches with -- shared by tests/test_knn_matcher.py and
-tests/test_reading_sizes.py (with its worker).  Test infrastructure only: numpy, the CPU oracle's primitives and the host
-twins of the solves, no device."""
+"""The test-side ICP loop and the exact CPU k-NN it searches with -- shared by tests/test_knn_matcher.py,
+tests/test_outlier_chain.py, tests/test_direction_index.py and tests/test_reading_sizes.py (with its worker).  Test
+infrastructure only: numpy, the CPU oracle's primitives and the host twins of the solves, no device."""
 import ctypes as C
 import os
 import subprocess
@@ -29,6 +29,14 @@ def build_brute(directory):
         assert L.knn_brute(r.ctypes.data, len(r), q.ctypes.data, len(q), k, 16, ids.ctypes.data, d2.ctypes.data) == 0
         return ids, d2
     return knn
+
+
+def d2_f32(q, p):
+    """fma(dz, dz, fma(dy, dy, dx * dx)) in float32, the definition of the device's distances (as _check_nn restates it)."""
+    dx, dy, dz = ((q[:, k] - p[:, k]).astype(np.float32) for k in range(3))
+    dd = np.float32(dx * dx)
+    dd = (dy.astype(np.float64) * dy + dd).astype(np.float32)
+    return (dz.astype(np.float64) * dz + dd).astype(np.float32)
 
 
 def _mul4(a, b):

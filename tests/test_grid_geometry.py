@@ -396,9 +396,9 @@ def test_knn_k_matches_the_brute_k_best(icp_mod, oracle, brute, name):
         for k in (3, 8):
             ids, d2 = h.knn_k(q, k, None)
             bids, bd2 = brute(ref_c, q, k)
-            _check_knn_k(ids, d2, bids, bd2)
+            _check_knn_k(ids, d2, bids, bd2, ref_c, q)
         ids, d2 = h.knn_k(rd, 3, T)                               # the transform applied by the search itself
-        _check_knn_k(ids, d2, *brute(ref_c, q[:len(rd)], 3))
+        _check_knn_k(ids, d2, *brute(ref_c, q[:len(rd)], 3), ref_c, q[:len(rd)])
 
 
 @pytest.mark.gpu

@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from host_loop import build_brute, host_kmatch_icp
+from host_loop import build_brute, d2_f32, host_kmatch_icp
 from laser_slam_amd import _lib, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,16 +131,24 @@ def icp_mod():
     return icp
 
 
-def _check_knn_k(ids, d2, bids, bd2):
-    """Device k-NN against the exact CPU k-NN: ascending, d2 bit for bit, ids equal up to exact ties."""
+def _check_knn_k(ids, d2, bids, bd2, ref_c, q):
+    """Device k-NN against the exact CPU k-NN of queries q in the centred reference ref_c: ascending, d2 bit for bit,
+    ids equal up to exact ties."""
     assert (np.diff(d2, axis=1) >= 0).all()
     assert np.array_equal(d2, bd2)
     # a different id only where the distance is tied: with another match of the query, or at the k-th distance (a point
     # outside the list may be at exactly that distance; the device keeps the smaller Morton index, the helper the smaller
-    # input index)
-    for j, s in zip(*np.nonzero(ids != bids)):
-        tied = (d2[j] == d2[j, s]).sum() >= 2 or d2[j, s] == d2[j, -1]
+    # input index) -- and the point the device names must lie at exactly the distance it reports, in every column
+    ref_c, q = np.ascontiguousarray(ref_c, np.float32), np.ascontiguousarray(q, np.float32)
+    jj, ss = np.nonzero(ids != bids)
+    for j, s in zip(jj, ss):
+        tied = (d2[j] == d2[j, s]).sum() >= 2 or s == d2.shape[1] - 1
         assert tied, (j, s, ids[j], bids[j], d2[j])
+    if jj.size:
+        assert (ids[jj, ss] >= 0).all() and (ids[jj, ss] < len(ref_c)).all()
+        at = d2_f32(q[jj, :3], ref_c[ids[jj, ss], :3])
+        bad = np.flatnonzero(at.view(np.uint32) != d2[jj, ss].view(np.uint32))
+        assert bad.size == 0, (jj[bad][:5], ss[bad][:5], ids[jj, ss][bad][:5], at[bad][:5], d2[jj, ss][bad][:5])
     # and no point twice in a query's list
     srt = np.sort(ids, axis=1)
     assert (srt[:, 1:] != srt[:, :-1]).all()
@@ -160,7 +168,7 @@ def test_knn_k_matches_exact_knn_4k(icp_mod, oracle, brute, pair4k):
         for k in (2, 3, 8):
             ids, d2 = h.knn_k(rd, k, T)
             bids, bd2 = brute(ref_c, q, k)
-            _check_knn_k(ids, d2, bids, bd2)
+            _check_knn_k(ids, d2, bids, bd2, ref_c, q)
         # k = 1 through the same entry point: the distances of lsgpu_knn
         _ids1, d21 = h.knn_k(rd, 1, T)
         _id0, d0 = h.knn(rd, T)
@@ -179,8 +187,9 @@ def test_knn_k_matches_exact_knn_full_size_sample(icp_mod, oracle, brute):
         T = synth.colmajor(T_init).copy()
         T[12:15] -= mean
         ids, d2 = h.knn_k(rd[sample], 3, T)
-    bids, bd2 = brute(ref_c, oracle.transform_points(T, rd[sample]), 3)
-    _check_knn_k(ids, d2, bids, bd2)
+    q = oracle.transform_points(T, rd[sample])
+    bids, bd2 = brute(ref_c, q, 3)
+    _check_knn_k(ids, d2, bids, bd2, ref_c, q)
 
 
 @pytest.mark.gpu

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from host_loop import d2_f32
 from laser_slam_amd import _lib, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -384,14 +385,23 @@ def icp_mod():
     return icp
 
 
-def _check_knn_k(ids, d2, bids, bd2):
-    """Device k-NN against the masked exact k-NN: ascending (invalid last), d2 bit for bit, ids equal up to exact ties."""
+def _check_knn_k(ids, d2, bids, bd2, ref_c, q):
+    """Device k-NN against the masked exact k-NN of queries q in the centred reference ref_c: ascending (invalid last),
+    d2 bit for bit, ids equal up to exact ties -- and a point the device names instead of the brute force's lies at exactly
+    the distance reported for it (invalid entries, -1 / +inf, are invalid on both sides and never differ)."""
     assert (np.diff(np.where(np.isinf(d2), np.float32(3e38), d2), axis=1) >= 0).all()
     assert np.array_equal(d2, bd2)
     assert np.array_equal(ids < 0, np.isinf(d2)) and np.array_equal(bids < 0, ids < 0)
-    for j, s in zip(*np.nonzero(ids != bids)):
+    ref_c, q = np.ascontiguousarray(ref_c, np.float32), np.ascontiguousarray(q, np.float32)
+    jj, ss = np.nonzero(ids != bids)
+    for j, s in zip(jj, ss):
         tied = (d2[j] == d2[j, s]).sum() >= 2 or d2[j, s] == d2[j][np.isfinite(d2[j])][-1] or d2[j, s] == d2[j, -1]
         assert tied, (j, s, ids[j], bids[j], d2[j])
+    if jj.size:
+        assert (ids[jj, ss] >= 0).all() and (ids[jj, ss] < len(ref_c)).all()
+        at = d2_f32(q[jj, :3], ref_c[ids[jj, ss], :3])
+        bad = np.flatnonzero(at.view(np.uint32) != d2[jj, ss].view(np.uint32))
+        assert bad.size == 0, (jj[bad][:5], ss[bad][:5], ids[jj, ss][bad][:5], at[bad][:5], d2[jj, ss][bad][:5])
     srt = np.sort(np.where(ids < 0, -1 - np.arange(ids.shape[1], dtype=np.int32), ids), axis=1)
     assert (srt[:, 1:] != srt[:, :-1]).all()
 
@@ -423,7 +433,7 @@ def test_knn_honours_matcher_max_dist(icp_mod, oracle, brute, pair4k):
         for k in (1, 3, 8):
             ids, d2 = h.knn_k(q, k, ident)
             bids, bd2 = mask_matches(*brute(ref_c, q, k), max_dist)
-            _check_knn_k(ids, d2, bids, bd2)
+            _check_knn_k(ids, d2, bids, bd2, ref_c, q)
             assert ids[-1].max() == -1 and np.isinf(d2[-1]).all()                 # nothing in range
             if dd[0, 0] == _sq(max_dist):                                         # (the construction landed exactly on the edge)
                 assert ids[-2, 0] == len(ref2) - 1 and d2[-2, 0] == _sq(max_dist)  # inclusive: valid
@@ -431,7 +441,7 @@ def test_knn_honours_matcher_max_dist(icp_mod, oracle, brute, pair4k):
             assert 0.02 < inv < 0.98, inv
         ids1, d21 = h.knn(q, ident)
         b1, bd1 = mask_matches(*brute(ref_c, q, 1), max_dist)
-        _check_knn_k(ids1[:, None], d21[:, None], b1, bd1)
+        _check_knn_k(ids1[:, None], d21[:, None], b1, bd1, ref_c, q)
         assert dd[0, 0] == _sq(max_dist), dd                                      # the edge case was really exercised
         # a handle without maxDist still returns every neighbour
         _i0, d0 = h0.knn(q, ident)
