@@ -1146,6 +1146,26 @@ int lsgpu_chain_load_carried(const lsgpu_yaml_module* mods, int n_mods, unsigned
 int lsgpu_chain_load_parts_carried(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_chain_cuts* cuts,
                                    lsgpu_shadow_config* shadow, lsgpu_motion_config* motion, lsgpu_cov_sampling_config* cov_sampling,
                                    char* why, int why_cap);
+/* A document's whole module set, and the two calls a front end needs: load it, apply it.
+ * lsgpu_chain_load_modules: the one walk of lsgpu_chain_load_carried and lsgpu_chain_load_parts_carried, every part into one
+ * record (byte for byte what those return; the same verdict and text; `carried` is kept in the record).
+ * lsgpu_icp_set_modules: the record's eight modules onto a handle in one call -- RobustOutlierFilter (chain.has_robust), the
+ * normals config (chain.has_normals), the covariance and MaxDensity (lsgpu_loaded_chain_covariance / _max_density), the cut
+ * modules, Shadow, CovarianceSampling and the motion config -- each through the code of its lsgpu_icp_set_* setter, in that
+ * order, a module the record does not hold being switched off.  All or nothing: where a step refuses, the call returns its
+ * code with its text in lsgpu_last_error and the handle is as it was.  A record not made by the loader starts from the
+ * *_config_default values.  Which modules run together is one rule set for all these entries (csrc/lsgpu_modules.h). */
+typedef struct lsgpu_chain_modules {
+  lsgpu_loaded_chain chain;
+  lsgpu_chain_cuts cuts;
+  lsgpu_shadow_config shadow;
+  lsgpu_motion_config motion;
+  lsgpu_cov_sampling_config cov_sampling;
+  unsigned carried;   /* LSGPU_CARRIED_*: what the document was loaded under */
+  int reserved[3];    /* 0 */
+} lsgpu_chain_modules;
+int lsgpu_chain_load_modules(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_chain_modules* out, char* why, int why_cap);
+int lsgpu_icp_set_modules(lsgpu_icp* h, const lsgpu_chain_modules* set);
 /* SurfaceNormalDataPointsFilter's parameters as the loader judges the reading's module (knn 3..32, keepNormals 1, epsilon 0,
  * no maxDist, nothing else kept): LSGPU_OK and *knn, or LSGPU_BAD_CONFIG and the loader's text.  For a chain outside the ICP
  * file that runs the module (the input filters).  Host only. */

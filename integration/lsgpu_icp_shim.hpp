@@ -135,57 +135,21 @@ class LsgpuICP {
   TransformationParameters compute(const DataPoints& reading, const DataPoints& reference,
                                    const TransformationParameters& T_init) {
     if (!h_) {
-      if (lsgpu_icp_create(&cfg_, device_, &h_) != LSGPU_OK)
+      if (lsgpu_icp_create(&mods_.chain.icp, device_, &h_) != LSGPU_OK)
         throw std::runtime_error("LsgpuICP: lsgpu_icp_create failed (no ROCm GPU visible?)");
-      if (has_robust_ && lsgpu_icp_set_robust_filter(h_, &robust_) != LSGPU_OK) {   // RobustOutlierFilter of the loaded chain
+      if (lsgpu_icp_set_modules(h_, &mods_) != LSGPU_OK) {   // every module of the loaded chain, or none and the refusal
         const std::string why = lsgpu_last_error(h_);
         reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_robust_filter: " + why);
-      }
-      if (has_normals_ && lsgpu_icp_set_normals(h_, &normals_) != LSGPU_OK) {   // SurfaceNormalOutlierFilter / normals of the loaded chain
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_normals: " + why);
-      }
-      if (has_cov_ && lsgpu_icp_set_covariance(h_, &cov_) != LSGPU_OK) {   // PointToPlaneWithCovErrorMinimizer of the loaded chain
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_covariance: " + why);
-      }
-      if (has_cuts_ && lsgpu_icp_set_chain_cuts(h_, &cuts_) != LSGPU_OK) {   // MaxDist- / MinDist- / BoundingBox- / RemoveNaN of the filter sections
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_chain_cuts: " + why);
-      }
-      if (has_md_ && lsgpu_icp_set_max_density(h_, &md_) != LSGPU_OK) {   // MaxDensityDataPointsFilter behind the reference's SurfaceNormal
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_max_density: " + why);
-      }
-      if (has_shadow_ && lsgpu_icp_set_shadow(h_, &shadow_) != LSGPU_OK) {   // ShadowDataPointsFilter behind the normals of either section
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_shadow: " + why);
-      }
-      if (has_cov_sampling_ && lsgpu_icp_set_cov_sampling(h_, &cov_sampling_) != LSGPU_OK) {   // CovarianceSamplingDataPointsFilter, the last thinning step of either section
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_cov_sampling: " + why);
-      }
-      if (has_motion_ && lsgpu_icp_set_motion(h_, &motion_) != LSGPU_OK) {   // force2D / force4DOF, BoundTransformationChecker
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_motion: " + why);
+        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_modules: " + why);
       }
     }
-    lsgpu_chain_config chain;
-    lsgpu_chain_config_default(&chain);
-    chain.reading_prob = prob_; chain.ssn_knn = knn_; chain.ssn_ratio = ratio_; chain.sn_knn = sn_knn_; chain.seed = seed_;
+    lsgpu_chain_config chain = mods_.chain.chain;
+    chain.seed = seed_;
     TransformationParameters T = T_init;
     // the normals of a side travel iff loadFromYaml declared that side
-    const bool rd_n = (carried_ & LSGPU_CARRIED_READING) && Traits::normals(reading, &rd_normals_) && (int64_t)rd_normals_.size() == 3 * Traits::size(reading);
-    const bool ref_n = (carried_ & LSGPU_CARRIED_REFERENCE) && Traits::normals(reference, &ref_normals_) && (int64_t)ref_normals_.size() == 3 * Traits::size(reference);
-    const int rc = carried_ ? lsgpu_icp_compute_normals(h_, Traits::features(reading), rd_n ? rd_normals_.data() : nullptr, Traits::size(reading),
+    const bool rd_n = (mods_.carried & LSGPU_CARRIED_READING) && Traits::normals(reading, &rd_normals_) && (int64_t)rd_normals_.size() == 3 * Traits::size(reading);
+    const bool ref_n = (mods_.carried & LSGPU_CARRIED_REFERENCE) && Traits::normals(reference, &ref_normals_) && (int64_t)ref_normals_.size() == 3 * Traits::size(reference);
+    const int rc = mods_.carried ? lsgpu_icp_compute_normals(h_, Traits::features(reading), rd_n ? rd_normals_.data() : nullptr, Traits::size(reading),
                                                         Traits::features(reference), ref_n ? ref_normals_.data() : nullptr, Traits::size(reference),
                                                         T_init.data(), &chain, T.data(), &stats_)
                             : lsgpu_icp_compute(h_, Traits::features(reading), Traits::size(reading), Traits::features(reference),
@@ -200,7 +164,7 @@ class LsgpuICP {
   // successful compute() and for a singular H, std::runtime_error if the chain does not name the module.
   typename Traits::Matrix getCovariance() {
     lsgpu_icp_quality q;
-    const int rc = h_ ? lsgpu_icp_get_quality(h_, &q) : (has_cov_ ? LSGPU_NO_CONVERGENCE : LSGPU_BAD_CONFIG);
+    const int rc = h_ ? lsgpu_icp_get_quality(h_, &q) : (lsgpu_loaded_chain_covariance(&mods_.chain, nullptr) ? LSGPU_NO_CONVERGENCE : LSGPU_BAD_CONFIG);
     if (rc == LSGPU_NO_CONVERGENCE) throw typename PM::ConvergenceError(h_ ? lsgpu_last_error(h_) : "getCovariance: no compute() yet");
     if (rc != LSGPU_OK) throw std::runtime_error(std::string("LsgpuICP::getCovariance: ") + lsgpu_strerror(rc) + (h_ ? std::string(" [") + lsgpu_last_error(h_) + "]" : std::string()));
     return Traits::matrix6(q.covariance);
@@ -208,54 +172,15 @@ class LsgpuICP {
 
  private:
   void take(const laser_slam_amd::ICP& parsed) {
-    cfg_ = parsed.config();
-    carried_ = parsed.carried();
-    prob_ = parsed.readingSamplingProb(); knn_ = parsed.surfaceNormalKnn(); ratio_ = parsed.surfaceNormalRatio();
-    sn_knn_ = parsed.referenceNormalKnn();
-    has_robust_ = parsed.robustFilter() != nullptr;
-    if (has_robust_) robust_ = *parsed.robustFilter();
-    has_normals_ = parsed.normalsConfig() != nullptr;
-    if (has_normals_) normals_ = *parsed.normalsConfig();
-    lsgpu_covariance_config_default(&cov_);
-    has_cov_ = parsed.covarianceConfig(&cov_.sensor_std_dev);
-    has_cuts_ = parsed.chainCuts() != nullptr;
-    if (has_cuts_) cuts_ = *parsed.chainCuts();
-    lsgpu_max_density_config_default(&md_);
-    has_md_ = parsed.maxDensityConfig(&md_.max_density);
-    has_shadow_ = parsed.shadowConfig() != nullptr;
-    if (has_shadow_) shadow_ = *parsed.shadowConfig();
-    has_cov_sampling_ = parsed.covSamplingConfig() != nullptr;
-    if (has_cov_sampling_) cov_sampling_ = *parsed.covSamplingConfig();
-    has_motion_ = parsed.motionConfig() != nullptr;
-    if (has_motion_) motion_ = *parsed.motionConfig();
+    mods_ = parsed.modules();
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
   int device_ = 0;
-  lsgpu_icp_config cfg_{};
+  lsgpu_chain_modules mods_{};                          // the loaded chain: its configs, every module, the declaration of carried normals
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
-  float prob_ = 0.75f, ratio_ = 0.5f;
-  int knn_ = 7;
-  int sn_knn_ = 0;                                      // SurfaceNormalDataPointsFilter as the reference filter (0: absent)
-  lsgpu_robust_config robust_{};                        // RobustOutlierFilter's parameters ...
-  bool has_robust_ = false;                             // ... if the chain holds one
-  lsgpu_normals_config normals_{};                      // SurfaceNormalOutlierFilter, reading normals, orientation pairs ...
-  bool has_normals_ = false;                            // ... if the chain holds any of them
-  lsgpu_covariance_config cov_{};                       // PointToPlaneWithCovErrorMinimizer's sensorStdDev ...
-  bool has_cov_ = false;                                // ... if the chain names the module
-  lsgpu_chain_cuts cuts_{};                             // the cut modules of the two filter sections ...
-  bool has_cuts_ = false;                               // ... if the chain holds any
-  lsgpu_max_density_config md_{};                       // MaxDensityDataPointsFilter's maxDensity ...
-  bool has_md_ = false;                                 // ... if the chain names the module
-  lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};      // ShadowDataPointsFilter's eps of the two filter sections ...
-  bool has_shadow_ = false;                             // ... if the chain names the module
-  lsgpu_cov_sampling_config cov_sampling_{0, 0, 1, 1, {0, 0, 0, 0}};   // CovarianceSamplingDataPointsFilter's nbSample / torqueNorm of the two filter sections ...
-  bool has_cov_sampling_ = false;                       // ... if the chain names the module
-  lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // PointToPlaneErrorMinimizer force2D / force4DOF, BoundTransformationChecker ...
-  bool has_motion_ = false;                             // ... if the chain names either
   int64_t seed_ = -1;
-  unsigned carried_ = 0;                                // loadFromYaml's declaration: which clouds carry normals
   std::vector<float> rd_normals_, ref_normals_;         // the normals handed to the last compute()
 };
 

@@ -56,7 +56,7 @@ ABI_SYMBOLS = [
     "lsgpu_icp_set_cov_sampling", "lsgpu_chain_load_cov_sampling",
     "lsgpu_cloud_upload_normals", "lsgpu_cloud_has_normals", "lsgpu_icp_compute_normals",
     "lsgpu_icp_compute_clouds_upload_normals", "lsgpu_chain_load_carried", "lsgpu_chain_load_parts_carried",
-    "lsgpu_surface_normal_params_check",
+    "lsgpu_surface_normal_params_check", "lsgpu_chain_load_modules", "lsgpu_icp_set_modules",
 ]
 
 # lsgpu_chain_load_carried: which of a caller's clouds carry normals (LSGPU_CARRIED_*)
@@ -255,6 +255,12 @@ class ChainCuts(C.Structure):
                 ("reading", PointFilter * CHAIN_CUT_MAX), ("reference", PointFilter * CHAIN_CUT_MAX)]
 
 
+class ChainModules(C.Structure):
+    """lsgpu_chain_modules: a document's whole module set (lsgpu_chain_load_modules), as lsgpu_icp_set_modules applies it."""
+    _fields_ = [("chain", LoadedChain), ("cuts", ChainCuts), ("shadow", ShadowCfg), ("motion", MotionCfg),
+                ("cov_sampling", CovSamplingCfg), ("carried", C.c_uint), ("reserved", C.c_int * 3)]
+
+
 FILTER_MAX_DIST, FILTER_MIN_DIST, FILTER_BOUNDING_BOX, FILTER_FIX_STEP_SAMPLING, FILTER_RANDOM_SAMPLING, FILTER_REMOVE_NAN = 1, 2, 3, 4, 5, 6
 FILTER_VOXEL_GRID = 7   # VoxelGridDataPointsFilter: v[0..2] = vSizeX/Y/Z, flag = useCentroid, dim = averageExistingDescriptors
 # OctreeGridDataPointsFilter: v[0] = maxSizeByNode, v[1] = maxPointByNode, dim = samplingMethod (OCTREE_*), flag = buildParallel
@@ -446,6 +452,8 @@ def lib() -> C.CDLL:
     L.lsgpu_chain_load_carried.argtypes = [C.POINTER(YamlModule), C.c_int, C.c_uint, C.POINTER(LoadedChain), C.c_char_p, C.c_int]
     L.lsgpu_chain_load_parts_carried.argtypes = [C.POINTER(YamlModule), C.c_int, C.c_uint, C.POINTER(ChainCuts), C.POINTER(ShadowCfg),
                                                  C.POINTER(MotionCfg), C.POINTER(CovSamplingCfg), C.c_char_p, C.c_int]
+    L.lsgpu_chain_load_modules.argtypes = [C.POINTER(YamlModule), C.c_int, C.c_uint, C.POINTER(ChainModules), C.c_char_p, C.c_int]
+    L.lsgpu_icp_set_modules.argtypes = [vp, C.POINTER(ChainModules)]
     L.lsgpu_surface_normal_params_check.argtypes = [C.POINTER(YamlParam), C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int]
     _lib = L
     return L

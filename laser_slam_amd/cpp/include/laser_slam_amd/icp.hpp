@@ -322,18 +322,16 @@ class ICP {
   // ICP::setDefault(): RandomSampling 0.75 / SamplingSurfaceNormal knn 7 / KDTree 1,0 / TrimmedDist 0.85 /
   // PointToPlane / Counter 40 + Differential 1e-3, 1e-3, 3
   void setDefault() {
-    std::memset(&loaded_, 0, sizeof(loaded_));
-    lsgpu_icp_config_default(&loaded_.icp);
-    lsgpu_chain_config_default(&loaded_.chain);
-    carried_ = 0;
-    std::memset(&cuts_, 0, sizeof(cuts_));
-    lsgpu_shadow_config_default(&shadow_);
-    lsgpu_motion_config_default(&motion_);
-    lsgpu_cov_sampling_config_default(&cov_sampling_);
+    std::memset(&mods_, 0, sizeof(mods_));
+    lsgpu_icp_config_default(&mods_.chain.icp);
+    lsgpu_chain_config_default(&mods_.chain.chain);
+    lsgpu_shadow_config_default(&mods_.shadow);
+    lsgpu_motion_config_default(&mods_.motion);
+    lsgpu_cov_sampling_config_default(&mods_.cov_sampling);
     release();
   }
 
-  // The syntax is read here (parseYaml), the modules are handed to lsgpu_chain_load as text: which modules the device path
+  // The syntax is read here (parseYaml), the modules are handed to lsgpu_chain_load_modules as text: which modules the device path
   // has, their parameters, ranges and order are the library's rule set (csrc/lsgpu_chain_loader.cpp), shared with the Python
   // facade.  Any other module is a configuration error (PointMatcher's registrar throws on unknown names as well).
   // carried: which of compute()'s clouds carry normals (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE): the chain may then
@@ -346,47 +344,16 @@ class ICP {
       for (const auto& kv : mods[i].params) params[i].push_back({kv.first.c_str(), kv.second.c_str()});
       list[i] = {mods[i].section.c_str(), mods[i].name.c_str(), params[i].data(), (int)params[i].size(), 0};
     }
-    lsgpu_loaded_chain loaded;
-    char why[512];
-    if (carried) {   // one declaration, the same walk: every part under it
-      lsgpu_chain_cuts c_cuts; lsgpu_shadow_config c_shadow; lsgpu_motion_config c_motion; lsgpu_cov_sampling_config c_cs;
-      if (lsgpu_chain_load_carried(list.data(), (int)list.size(), carried, &loaded, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
-      if (lsgpu_chain_load_parts_carried(list.data(), (int)list.size(), carried, &c_cuts, &c_shadow, &c_motion, &c_cs, why, (int)sizeof(why)) != LSGPU_OK)
-        throw ConfigError(why);
-      loaded_ = loaded; cuts_ = c_cuts; shadow_ = c_shadow; motion_ = c_motion; cov_sampling_ = c_cs;
-      carried_ = carried;
-      release();
-      return;
-    }
-    if (lsgpu_chain_load(list.data(), (int)list.size(), &loaded, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
-    // the cut modules of the filter sections (MaxDist-, MinDist-, BoundingBox-, RemoveNaNDataPointsFilter): same rules, the modules
-    lsgpu_chain_cuts cuts;
-    std::memset(&cuts, 0, sizeof(cuts));
-    if ((loaded.reserved[2] || loaded.reserved[3]) &&
-        lsgpu_chain_load_cuts(list.data(), (int)list.size(), &cuts, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
-    // ShadowDataPointsFilter of the two sections: lsgpu_loaded_chain has no slot for it, the module travels by its own entry
-    lsgpu_shadow_config shadow;
-    if (lsgpu_chain_load_shadow(list.data(), (int)list.size(), &shadow, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
-    // force2D / force4DOF of PointToPlaneErrorMinimizer and BoundTransformationChecker: likewise by their own entry
-    lsgpu_motion_config motion;
-    if (lsgpu_chain_load_motion(list.data(), (int)list.size(), &motion, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
-    // CovarianceSamplingDataPointsFilter of the two sections: likewise
-    lsgpu_cov_sampling_config cov_sampling;
-    if (lsgpu_chain_load_cov_sampling(list.data(), (int)list.size(), &cov_sampling, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
-    loaded_ = loaded;
-    cuts_ = cuts;
-    shadow_ = shadow;
-    motion_ = motion;
-    cov_sampling_ = cov_sampling;
-    carried_ = 0;
+    char why[512];   // the one walk: every part of the document, under the declaration (a refusal leaves mods_ as it was)
+    if (lsgpu_chain_load_modules(list.data(), (int)list.size(), carried, &mods_, why, (int)sizeof(why)) != LSGPU_OK) throw ConfigError(why);
     release();
   }
-  unsigned carried() const { return carried_; }
+  unsigned carried() const { return mods_.carried; }
   // does a module behind the reference's section read its normals (include/lsgpu_icp.h, "carried normals", rule 3)?
   bool readsReferenceNormals() const {
-    return loaded_.icp.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT ||
-           (loaded_.has_robust && loaded_.robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE) ||
-           (loaded_.has_normals && loaded_.normals.max_angle >= 0.f);
+    return mods_.chain.icp.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT ||
+           (mods_.chain.has_robust && mods_.chain.robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE) ||
+           (mods_.chain.has_normals && mods_.chain.normals.max_angle >= 0.f);
   }
 
   static void requireRigid(const TransformationParameters& T_init) {
@@ -417,20 +384,20 @@ class ICP {
     if (nr <= 0 || nq <= 0) { requireRigid(T_init); throw ConvergenceError("empty cloud"); }
     // ICP::compute steps 1-7 on the device: referenceDataPointsFilters, centring + grid,
     // readingDataPointsFilters, the loop (lsgpu_icp_compute)
-    lsgpu_chain_config chain = loaded_.chain;
+    lsgpu_chain_config chain = mods_.chain.chain;
     chain.seed = seed_;
     TransformationParameters T = T_init;
     // the normals of a side travel iff loadFromYaml declared that side as carrying some
     const float* rd_n = carriedNormals(reading, LSGPU_CARRIED_READING);
     const float* ref_n = carriedNormals(reference, LSGPU_CARRIED_REFERENCE);
-    if ((carried_ & LSGPU_CARRIED_REFERENCE) && !ref_n && readsReferenceNormals() && loaded_.chain.ssn_knn == 0 && loaded_.chain.sn_knn == 0)
+    if ((mods_.carried & LSGPU_CARRIED_REFERENCE) && !ref_n && readsReferenceNormals() && mods_.chain.chain.ssn_knn == 0 && mods_.chain.chain.sn_knn == 0)
       throw ConfigError("ICP::compute: the reference was declared to carry normals and carries none, and the chain reads them");
-    const int rc = carried_ ? lsgpu_icp_compute_normals(h_, reading.features.data(), rd_n, nq, reference.features.data(), ref_n, nr,
+    const int rc = mods_.carried ? lsgpu_icp_compute_normals(h_, reading.features.data(), rd_n, nq, reference.features.data(), ref_n, nr,
                                                         T_init.data(), &chain, T.data(), &stats_)
                             : lsgpu_icp_compute(h_, reading.features.data(), nq, reference.features.data(), nr, T_init.data(),
                                                 &chain, T.data(), &stats_);
     if (!rigid) requireRigid(T_init);          // (rc is LSGPU_BAD_ARG from step 5, the filters have run)
-    check(rc, carried_ ? "lsgpu_icp_compute_normals" : "lsgpu_icp_compute");
+    check(rc, mods_.carried ? "lsgpu_icp_compute_normals" : "lsgpu_icp_compute");
 #ifdef LSGPU_TEST_SEAMS
     if (observer_) observer_(*this, reading, reference, T_init, T);
 #endif
@@ -466,7 +433,7 @@ class ICP {
       ensureHandle();
     }
     if (refs.size() != ref_T.size()) throw std::logic_error("one transform per reference cloud");
-    lsgpu_chain_config chain = loaded_.chain;
+    lsgpu_chain_config chain = mods_.chain.chain;
     chain.seed = seed_;
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
@@ -490,7 +457,7 @@ class ICP {
       ensureHandle();
     }
     if (refs.size() != ref_T.size()) throw std::logic_error("one transform per reference cloud");
-    lsgpu_chain_config chain = loaded_.chain;
+    lsgpu_chain_config chain = mods_.chain.chain;
     chain.seed = seed_;
     std::vector<float> flat(16 * refs.size());
     for (size_t i = 0; i < refs.size(); ++i) std::memcpy(&flat[16 * i], ref_T[i].data(), 16 * sizeof(float));
@@ -561,31 +528,32 @@ class ICP {
     return c;
   }
   // sensorStdDev of the loaded chain's PointToPlaneWithCovErrorMinimizer; false: the chain does not name the module
-  bool covarianceConfig(float* sensor_std_dev) const { return lsgpu_loaded_chain_covariance(&loaded_, sensor_std_dev) != 0; }
+  bool covarianceConfig(float* sensor_std_dev) const { return lsgpu_loaded_chain_covariance(&mods_.chain, sensor_std_dev) != 0; }
 
   // maxDensity of the loaded chain's MaxDensityDataPointsFilter (behind SurfaceNormalDataPointsFilter keepDensities 1 in the
   // reference section); false: the chain does not name the module
-  bool maxDensityConfig(float* max_density) const { return lsgpu_loaded_chain_max_density(&loaded_, max_density) != 0; }
+  bool maxDensityConfig(float* max_density) const { return lsgpu_loaded_chain_max_density(&mods_.chain, max_density) != 0; }
 
   const lsgpu_icp_stats& lastStats() const { return stats_; }
-  const lsgpu_icp_config& config() const { return loaded_.icp; }
+  const lsgpu_icp_config& config() const { return mods_.chain.icp; }
   lsgpu_icp* handle() { ensureHandle(); return h_; }  // the C-ABI handle (device conversions of ros_msgs.hpp)
-  float readingSamplingProb() const { return loaded_.chain.reading_prob; }
-  int surfaceNormalKnn() const { return loaded_.chain.ssn_knn; }      // SamplingSurfaceNormalDataPointsFilter's knn (0: no such module)
-  int referenceNormalKnn() const { return loaded_.chain.sn_knn; }     // SurfaceNormalDataPointsFilter's knn (0: no such module)
-  float surfaceNormalRatio() const { return loaded_.chain.ssn_ratio; }
-  const lsgpu_robust_config* robustFilter() const { return loaded_.has_robust ? &loaded_.robust : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
+  float readingSamplingProb() const { return mods_.chain.chain.reading_prob; }
+  int surfaceNormalKnn() const { return mods_.chain.chain.ssn_knn; }      // SamplingSurfaceNormalDataPointsFilter's knn (0: no such module)
+  int referenceNormalKnn() const { return mods_.chain.chain.sn_knn; }     // SurfaceNormalDataPointsFilter's knn (0: no such module)
+  float surfaceNormalRatio() const { return mods_.chain.chain.ssn_ratio; }
+  const lsgpu_robust_config* robustFilter() const { return mods_.chain.has_robust ? &mods_.chain.robust : nullptr; }   // RobustOutlierFilter (nullptr: no such module)
   // SurfaceNormalOutlierFilter / reading normals / the orientation pairs (nullptr: none of these modules)
-  const lsgpu_normals_config* normalsConfig() const { return loaded_.has_normals ? &loaded_.normals : nullptr; }
+  const lsgpu_normals_config* normalsConfig() const { return mods_.chain.has_normals ? &mods_.chain.normals : nullptr; }
   // the cut modules of the two filter sections (nullptr: none)
-  const lsgpu_chain_cuts* chainCuts() const { return cuts_.n_reading || cuts_.n_reference ? &cuts_ : nullptr; }
+  const lsgpu_chain_cuts* chainCuts() const { return mods_.cuts.n_reading || mods_.cuts.n_reference ? &mods_.cuts : nullptr; }
   // ShadowDataPointsFilter's eps of the two filter sections (nullptr: no such module; an eps < 0: none on that side)
-  const lsgpu_shadow_config* shadowConfig() const { return shadow_.reading_eps >= 0.f || shadow_.reference_eps >= 0.f ? &shadow_ : nullptr; }
+  const lsgpu_shadow_config* shadowConfig() const { return mods_.shadow.reading_eps >= 0.f || mods_.shadow.reference_eps >= 0.f ? &mods_.shadow : nullptr; }
   // CovarianceSamplingDataPointsFilter's nbSample / torqueNorm of the two filter sections (nullptr: no such module; nbSample 0: none on that side)
-  const lsgpu_cov_sampling_config* covSamplingConfig() const { return cov_sampling_.reading_nb_sample > 0 || cov_sampling_.reference_nb_sample > 0 ? &cov_sampling_ : nullptr; }
+  const lsgpu_cov_sampling_config* covSamplingConfig() const { return mods_.cov_sampling.reading_nb_sample > 0 || mods_.cov_sampling.reference_nb_sample > 0 ? &mods_.cov_sampling : nullptr; }
   // PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (nullptr: neither)
-  const lsgpu_motion_config* motionConfig() const { return motion_.dof || motion_.bound ? &motion_ : nullptr; }
-  const lsgpu_loaded_chain& loadedChain() const { return loaded_; }
+  const lsgpu_motion_config* motionConfig() const { return mods_.motion.dof || mods_.motion.bound ? &mods_.motion : nullptr; }
+  const lsgpu_loaded_chain& loadedChain() const { return mods_.chain; }
+  const lsgpu_chain_modules& modules() const { return mods_; }   // the whole record, as lsgpu_icp_set_modules takes it
 
  private:
   using Module = detail::YamlModule;
@@ -632,50 +600,11 @@ class ICP {
 
   void ensureHandle() {
     if (h_) return;
-    const int rc = lsgpu_icp_create(&loaded_.icp, device_, &h_);
+    const int rc = lsgpu_icp_create(&mods_.chain.icp, device_, &h_);
     if (rc == LSGPU_BAD_CONFIG) throw ConfigError("lsgpu_icp_create: bad configuration");
     if (rc != LSGPU_OK) throw DeviceError("lsgpu_icp_create failed (no ROCm GPU visible?)");
-    if (loaded_.has_robust && lsgpu_icp_set_robust_filter(h_, &loaded_.robust) != LSGPU_OK) {
-      const std::string msg = std::string("lsgpu_icp_set_robust_filter: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    if (loaded_.has_normals && lsgpu_icp_set_normals(h_, &loaded_.normals) != LSGPU_OK) {
-      const std::string msg = std::string("lsgpu_icp_set_normals: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    lsgpu_covariance_config cc;
-    lsgpu_covariance_config_default(&cc);
-    if (lsgpu_loaded_chain_covariance(&loaded_, &cc.sensor_std_dev) && lsgpu_icp_set_covariance(h_, &cc) != LSGPU_OK) {
-      const std::string msg = std::string("lsgpu_icp_set_covariance: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    if (chainCuts() && lsgpu_icp_set_chain_cuts(h_, &cuts_) != LSGPU_OK) {
-      const std::string msg = std::string("lsgpu_icp_set_chain_cuts: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    lsgpu_max_density_config mc;
-    lsgpu_max_density_config_default(&mc);
-    if (lsgpu_loaded_chain_max_density(&loaded_, &mc.max_density) && lsgpu_icp_set_max_density(h_, &mc) != LSGPU_OK) {
-      const std::string msg = std::string("lsgpu_icp_set_max_density: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    if (shadowConfig() && lsgpu_icp_set_shadow(h_, &shadow_) != LSGPU_OK) {   // (behind lsgpu_icp_set_normals: the reading's needs its normals)
-      const std::string msg = std::string("lsgpu_icp_set_shadow: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    if (covSamplingConfig() && lsgpu_icp_set_cov_sampling(h_, &cov_sampling_) != LSGPU_OK) {   // (behind lsgpu_icp_set_normals: the reading's needs its normals)
-      const std::string msg = std::string("lsgpu_icp_set_cov_sampling: ") + lsgpu_last_error(h_);
-      release();
-      throw ConfigError(msg);
-    }
-    if (motionConfig() && lsgpu_icp_set_motion(h_, &motion_) != LSGPU_OK) {   // (last: it refuses what the constrained steps do not cover)
-      const std::string msg = std::string("lsgpu_icp_set_motion: ") + lsgpu_last_error(h_);
+    if (lsgpu_icp_set_modules(h_, &mods_) != LSGPU_OK) {   // all of the chain's modules, or none and the refusal
+      const std::string msg = std::string("lsgpu_icp_set_modules: ") + lsgpu_last_error(h_);
       release();
       throw ConfigError(msg);
     }
@@ -683,7 +612,7 @@ class ICP {
   void release() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; ++generation_; } }
   // the cloud's normals if one of `sides` was declared at load and the cloud carries one normal per point, else nullptr
   const float* carriedNormals(const DataPoints& cloud, unsigned sides) const {
-    if (!(carried_ & sides) || cloud.normals.empty() || cloud.normals.size() != (size_t)cloud.getNbPoints() * 3) return nullptr;
+    if (!(mods_.carried & sides) || cloud.normals.empty() || cloud.normals.size() != (size_t)cloud.getNbPoints() * 3) return nullptr;
     return cloud.normals.data();
   }
   void check(int rc, const char* what) {
@@ -695,12 +624,9 @@ class ICP {
   }
 
   int device_ = 0;
-  lsgpu_loaded_chain loaded_{};   // what loadFromYaml / setDefault left: the handle's config, the filters of compute()
-  lsgpu_chain_cuts cuts_{};       // ... and the cut modules of its filter sections (lsgpu_chain_load_cuts)
-  lsgpu_shadow_config shadow_{-1.f, -1.f, {0, 0}};   // ... and ShadowDataPointsFilter's eps of the two (lsgpu_chain_load_shadow)
-  lsgpu_motion_config motion_{0, 0, 1.f, 1.f, 0, {0, 0, 0}};   // ... and force2D / force4DOF, BoundTransformationChecker (lsgpu_chain_load_motion)
-  lsgpu_cov_sampling_config cov_sampling_{0, 0, 1, 1, {0, 0, 0, 0}};   // ... and CovarianceSamplingDataPointsFilter of the two (lsgpu_chain_load_cov_sampling)
-  unsigned carried_ = 0;          // ... and which of compute()'s clouds were declared as carrying normals (LSGPU_CARRIED_*)
+  // what loadFromYaml / setDefault left: the handle's config, the filters of compute(), every module of the chain and which of
+  // compute()'s clouds were declared as carrying normals (lsgpu_chain_load_modules)
+  lsgpu_chain_modules mods_{};
   lsgpu_icp* h_ = nullptr;
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;

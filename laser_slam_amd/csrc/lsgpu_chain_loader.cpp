@@ -21,6 +21,7 @@
 #include "lsgpu_robust.h"
 #include "lsgpu_shadow.h"
 #include "lsgpu_cov_sampling.h"
+#include "lsgpu_modules.h"
 
 namespace {
 
@@ -457,20 +458,14 @@ void finish(Load& l) {
            "no outlier filter reads are refused, and the module alone does not change that)");
   if (lsgpu::normal_angle::check(&o.normals, o.icp.error_minimizer, have_normals, &why) != LSGPU_OK) refuse(why);
   if (!l.counter) refuse("transformationCheckers: CounterTransformationChecker is required (the loop would not stop)");
-  if (l.with_cov) {   // what the covariance pass does not cover (lsgpu_icp_set_covariance refuses the same handles)
-    const char* with = o.icp.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2" : l.robust ? "RobustOutlierFilter"
-                     : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
-    if (with) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + with + " (the covariance is implemented for knn 1 and binary distance filters)");
-    if (l.max_density) refuse("PointToPlaneWithCovErrorMinimizer: not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)");
-    if (shadow) refuse("PointToPlaneWithCovErrorMinimizer: not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)");
-    if (cov_sampling) refuse(std::string("PointToPlaneWithCovErrorMinimizer: not together with ") + kCovSampling + " (the covariance's first version does not cover a reference thinned behind the normals)");
-  }
-  if (l.motion.dof != LSGPU_MOTION_DOF_6) {   // what the constrained steps' first version does not cover (lsgpu_icp_set_motion refuses the same handles)
-    const char* with = o.icp.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2" : l.robust ? "RobustOutlierFilter"
-                     : o.normals.max_angle >= 0.f ? "SurfaceNormalOutlierFilter" : nullptr;
-    if (with)
-      refuse(std::string("PointToPlaneErrorMinimizer: ") + (l.motion.dof == LSGPU_MOTION_DOF_3 ? "force2D" : "force4DOF") + " not together with " + with +
-             " (the constrained steps are implemented for knn 1 and binary distance filters)");
+  {   // what the covariance pass and the constrained steps do not cover: the rule set's verdict on what is loaded (lsgpu_modules.h)
+    lsgpu::modules::State s;
+    s.robust_on = l.robust; s.normals_on = true; s.normals = o.normals; s.cov_on = l.with_cov; s.md_on = l.max_density;
+    s.sh_on = shadow; s.cs_on = cov_sampling; s.mo_on = true; s.mo_cfg = l.motion;
+    lsgpu::modules::Facts f;
+    f.matcher_knn = o.icp.matcher_knn;
+    const std::string refused = lsgpu::modules::refusal(s, f, lsgpu::modules::kLoader);
+    if (!refused.empty()) refuse(refused);
   }
   if (o.chain.reading_prob < 0.f) l.cuts.reading_sampling_at = l.cuts.n_reading;   // (no RandomSampling: not read)
   o.reserved[2] = l.cuts.n_reading; o.reserved[3] = l.cuts.n_reference;
@@ -523,8 +518,8 @@ void load(const lsgpu_yaml_module* mods, int n_mods, Load& l, unsigned carried) 
 
 extern "C" {
 
-// the five entry points: the one walk over the modules, then what the caller asked for (`chain`, `cuts`, `shadow`, `motion` or
-// `cov_sampling`, the others NULL)
+// the entry points: the one walk over the modules, then what the caller asked for (all of it: lsgpu_chain_load_modules; `chain`,
+// `cuts`, `shadow`, `motion` or `cov_sampling`, the others NULL: the part loaders)
 static int load_into(const lsgpu_yaml_module* mods, int n_mods, lsgpu_loaded_chain* chain, lsgpu_chain_cuts* cuts, lsgpu_shadow_config* shadow,
                      char* why, int why_cap, lsgpu_motion_config* motion = nullptr, lsgpu_cov_sampling_config* cov_sampling = nullptr,
                      unsigned carried = 0) {
@@ -589,6 +584,17 @@ int lsgpu_chain_load_parts_carried(const lsgpu_yaml_module* mods, int n_mods, un
   if (why && why_cap > 0) why[0] = '\0';
   if (carried & ~(unsigned)(LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE)) return LSGPU_BAD_ARG;
   return load_into(mods, n_mods, nullptr, cuts, shadow, why, why_cap, motion, cov_sampling, carried);
+}
+
+int lsgpu_chain_load_modules(const lsgpu_yaml_module* mods, int n_mods, unsigned carried, lsgpu_chain_modules* out, char* why, int why_cap) {
+  if (why && why_cap > 0) why[0] = '\0';
+  if (!out || (carried & ~(unsigned)(LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE))) return LSGPU_BAD_ARG;
+  lsgpu_chain_modules m;
+  std::memset(&m, 0, sizeof(m));
+  m.carried = carried;
+  const int rc = load_into(mods, n_mods, &m.chain, &m.cuts, &m.shadow, why, why_cap, &m.motion, &m.cov_sampling, carried);
+  if (rc == LSGPU_OK) *out = m;
+  return rc;
 }
 
 int lsgpu_surface_normal_params_check(const lsgpu_yaml_param* params, int n_params, int* knn, char* why, int why_cap) {

@@ -28,6 +28,7 @@
 #include "lsgpu_tuning.h"
 #include "lsgpu_policy.h"
 #include "lsgpu_section_plan.h"
+#include "lsgpu_modules.h"
 #include "lsgpu_submap.hip.h"
 #include "lsgpu_knn.hip.h"
 #include "lsgpu_knn_k.hip.h"
@@ -357,28 +358,21 @@ struct lsgpu_icp {
   DevBuf<float4> flt_in, flt_in2, flt_ref, flt_rd;
   DevBuf<float4> vgf_out;   // VoxelGridDataPointsFilter (lsgpu_voxel_filter.hip.h): the voxels' points at their first points' positions
   DevBuf<float> flt_nrm;
+  modules::State mods;   // which of the eight optional modules run, and their configs (lsgpu_modules.h; lsgpu_icp_set_*, lsgpu_icp_set_modules)
   // cut modules of the ICP chain's filter sections (lsgpu_icp_set_chain_cuts; lsgpu_chain_cut.hip.h)
-  bool cuts_on = false;
-  lsgpu_chain_cuts cuts{};
   DevBuf<uint32_t> cut_blk;   // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
   DevBuf<float4> cut_ref;     // the reference behind its cut modules
   DevBuf<float> cut_ref_nrm;  // ... and its carried normals, when somebody reads them
   // MaxDensityDataPointsFilter behind SurfaceNormalDataPointsFilter keepDensities 1 (lsgpu_icp_set_max_density; lsgpu_max_density.hip.h)
-  bool md_on = false;
-  lsgpu_max_density_config md_cfg{};
   DevBuf<float> dens, dens_io;   // the density of every point of the cloud as given; its staging for a host caller
   DevBuf<MdStat> md_stat;        // minimum / maximum of the densities, NaN count
   DevBuf<uint32_t> md_blk;       // the pass's block counts and their scans: 4 rows of ceil(n / 256) words
   // ShadowDataPointsFilter behind the normals of either section (lsgpu_icp_set_shadow; lsgpu_shadow.hip.h)
-  bool sh_on = false;
-  lsgpu_shadow_config sh_cfg{};
   DevBuf<uint32_t> sh_blk;           // the pass's block counts and their scan: 2 rows of ceil(n / 256) words
   DevBuf<float4> sh_ref, sh_rd;      // the kept points of the reference (behind the sampling filter or the thinning) / the reading
   DevBuf<float> sh_nrm, sh_rd_nrm;   // the kept reference normals; the reading's normals in front of the pass
   DevBuf<float> sh_nrm_in;           // staging of a host caller's normals (lsgpu_icp_filter_shadow)
   // CovarianceSamplingDataPointsFilter (lsgpu_icp_filter_cov_sampling; lsgpu_cov_sampling.hip.h)
-  bool cs_on = false;                   // lsgpu_icp_set_cov_sampling: the module in the sections of a compute
-  lsgpu_cov_sampling_config cs_cfg{};
   DevBuf<float4> cs_ref, cs_rd;         // the chosen points of the reference / the reading ...
   DevBuf<float> cs_ref_nrm, cs_rd_nrm;  // ... and their normals
   DevBuf<float> cs_whole_nrm;           // behind SurfaceNormalDataPointsFilter alone: the whole reference's normals in its order
@@ -394,11 +388,7 @@ struct lsgpu_icp {
   DevBuf<float> cs_nrm_in;              // staging of a host caller's normals ...
   DevBuf<float4> cs_pts_out; DevBuf<float> cs_nrm_out; DevBuf<int32_t> cs_ids_out;   // ... and of its results
   // PointToPlaneErrorMinimizer force4DOF / force2D and BoundTransformationChecker (lsgpu_icp_set_motion)
-  bool mo_on = false;
-  lsgpu_motion_config mo_cfg{};
   PinBuf<float> h_chk;               // the bound's copy of the checker history (travels with the loop state's read-back)
-  int dof() const { return mo_on ? mo_cfg.dof : LSGPU_MOTION_DOF_6; }
-  bool bound() const { return mo_on && mo_cfg.bound != 0; }
   PinBuf<float> draws_pinned;     // host staging of the filter draws (pinned: async H2D)
   std::vector<DevBuf<float4>> clouds;  // lsgpu_cloud_upload slots
   std::vector<int64_t> cloud_n;        // -1: empty
@@ -423,22 +413,16 @@ struct lsgpu_icp {
   DevBuf<uint32_t> hist_med;  // MedianDistOutlierFilter: the second run of the select's refining passes (3 * kHistBins, [0] unused) ...
   DevBuf<SelState> sel_med;   // ... and its three states
   // RobustOutlierFilter (lsgpu_icp_set_robust_filter): the MAD's select over |d2 - median|, the loop's robust state, its trace
-  bool robust_on = false;
-  lsgpu_robust_config robust{};
   bool have_normals = false;  // the last set_reference was given normals (or a reference filter computed them)
   DevBuf<uint32_t> rb_hist; DevBuf<SelState> rb_sel; DevBuf<RobustState> rb_state; DevBuf<lsgpu_robust_trace> rb_trace_dev;
   size_t rb_trace_n = 0;      // records of the last alignment in rb_trace_dev
   // SurfaceNormalOutlierFilter / reading normals / orientation (lsgpu_icp_set_normals)
-  bool normals_on = false;
-  lsgpu_normals_config normals{};
   DevBuf<float> rd_nrm;       // the reading's normals, 3 floats per point in the reading's order (lsgpu_icp_compute's step, or the caller's) ...
   DevBuf<float> rd_nrm0;      // ... moved by R_init (step 5): what the loop's angle test reads
   DevBuf<float> nrm_io;       // staging of lsgpu_icp_get_reference_normals
   DevBuf<lsgpu_normal_angle_trace> na_trace_dev;
   size_t na_trace_n = 0;      // records of the last alignment in na_trace_dev
   // PointToPlaneWithCovErrorMinimizer (lsgpu_icp_set_covariance): the pass after the loop and the record it leaves
-  bool cov_on = false;
-  lsgpu_covariance_config cov_cfg{};
   int quality_state = 0;      // of the last alignment: 0 none / it did not return LSGPU_OK, 1 `quality` holds it, 2 singular H
   lsgpu_icp_quality quality{};
   DevBuf<float4> cov_pts;     // the moved reading in the caller's order
@@ -555,6 +539,91 @@ static int fetch_trace(lsgpu_icp* h, const T* dev, size_t have, T* out, int cap)
   return n;
 }
 
+// ---- the module set of a handle.  Which modules run together is lsgpu_modules.h's business; a step below validates one module's
+// values, puts it into the set in the making and asks.  lsgpu_icp_set_* is one step, lsgpu_icp_set_modules all eight: both work on
+// a copy of the handle's state and commit it only if every step passed.
+struct ModuleSet {
+  modules::State s;
+  modules::Facts f;
+  std::string err;   // of the step that returned LSGPU_BAD_CONFIG
+  int say(const std::string& why) { err = why; return LSGPU_BAD_CONFIG; }
+  int ask(modules::Asker who) { err = modules::refusal(s, f, who); return err.empty() ? LSGPU_OK : LSGPU_BAD_CONFIG; }
+
+  int robust(const lsgpu_robust_config* cfg) {
+    const char* why = nullptr;
+    // (whether the reference has normals is known to align / the stand-alone sums, which check point2plane again)
+    if (cfg && robust::check(cfg, f.error_minimizer, 1, &why) != LSGPU_OK) return say(why);
+    if ((s.robust_on = cfg != nullptr)) s.robust = *cfg;
+    return ask(modules::kSetRobust);
+  }
+  int normals(const lsgpu_normals_config* cfg) {
+    if ((s.normals_on = cfg != nullptr)) s.normals = *cfg;
+    if (ask(modules::kSetNormalsFirst) != LSGPU_OK) return LSGPU_BAD_CONFIG;   // (a module on the reading that needs its normals)
+    const char* why = nullptr;
+    // (whether the reference has normals is known to align, for which a filter without them is inert)
+    if (cfg && normal_angle::check(cfg, f.error_minimizer, 1, &why) != LSGPU_OK) return say(why);
+    return ask(modules::kSetNormals);
+  }
+  int covariance(const lsgpu_covariance_config* cfg) {
+    if (cfg && (!(cfg->sensor_std_dev >= 0.f) || std::isinf(cfg->sensor_std_dev))) return say("PointToPlaneWithCovErrorMinimizer: sensorStdDev must be finite and >= 0");
+    if ((s.cov_on = cfg != nullptr)) s.cov_cfg = *cfg;
+    return ask(modules::kSetCovariance);
+  }
+  int cuts(const lsgpu_chain_cuts* c) {
+    s.cuts_on = c && (c->n_reading != 0 || c->n_reference != 0);
+    const std::string why = s.cuts_on ? chain_cuts_why(c) : std::string();
+    if (!why.empty()) return say(why);
+    if (s.cuts_on) s.cuts = *c;
+    return ask(modules::kSetCuts);
+  }
+  int max_density(const lsgpu_max_density_config* cfg) {
+    // (SurfaceNormalDataPointsFilter's knn comes with the chain: lsgpu_icp_compute checks that it is there)
+    if (const char* why = cfg ? lsgpu_max_density_config_why(cfg, kSnfMinKnn) : nullptr) return say(why);
+    if ((s.md_on = cfg != nullptr)) s.md_cfg = *cfg;
+    return ask(modules::kSetMaxDensity);
+  }
+  int shadow(const lsgpu_shadow_config* cfg) {
+    if (const char* why = cfg ? lsgpu_shadow_config_why(cfg) : nullptr) return say(why);
+    if ((s.sh_on = cfg && (cfg->reading_eps >= 0.f || cfg->reference_eps >= 0.f))) s.sh_cfg = *cfg;
+    return ask(modules::kSetShadow);
+  }
+  int cov_sampling(const lsgpu_cov_sampling_config* cfg) {
+    if (const char* why = cfg ? lsgpu_cov_sampling_config_why(cfg) : nullptr) return say(why);
+    if ((s.cs_on = cfg && (cfg->reading_nb_sample != 0 || cfg->reference_nb_sample != 0))) s.cs_cfg = *cfg;
+    return ask(modules::kSetCovSampling);
+  }
+  int motion(const lsgpu_motion_config* cfg) {
+    if (const char* why = cfg ? lsgpu_motion_config_why(cfg) : nullptr) return say(why);
+    if ((s.mo_on = cfg && (cfg->dof != LSGPU_MOTION_DOF_6 || cfg->bound))) s.mo_cfg = *cfg;
+    return ask(modules::kSetMotion);
+  }
+};
+
+static ModuleSet module_set(const lsgpu_icp* h) {
+  ModuleSet m;
+  m.s = h->mods;
+  m.f.error_minimizer = h->cfg.error_minimizer; m.f.matcher_knn = h->cfg.matcher_knn;
+  m.f.chain = policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor);
+  m.f.comm = h->comm != nullptr;
+  return m;
+}
+
+// the end of a setter: the set's text, and its state if every step passed (else the handle stays as it was)
+static int commit_modules(lsgpu_icp* h, const ModuleSet& m, int rc) {
+  h->err = m.err;
+  if (rc != LSGPU_OK) return rc;
+  if (!(h->mods.cov_on && m.s.cov_on)) h->quality_state = 0;   // (the covariance removed, or switched on for the first time)
+  h->mods = m.s;
+  return LSGPU_OK;
+}
+
+template <class Cfg>
+static int set_module(lsgpu_icp* h, int (ModuleSet::*step)(const Cfg*), const Cfg* cfg) {
+  if (!h) return LSGPU_BAD_ARG;
+  ModuleSet m = module_set(h);
+  return commit_modules(h, m, (m.*step)(cfg));
+}
+
 extern "C" {
 
 void lsgpu_icp_config_yaml(lsgpu_icp_config* c) {  // icp_default.yaml:14-27
@@ -596,155 +665,43 @@ int lsgpu_chain_config_check(const lsgpu_chain_config* c, int error_minimizer) {
   return LSGPU_OK;
 }
 
-int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cfg) { h->robust_on = false; return LSGPU_OK; }
-  const char* why = nullptr;
-  // (whether the reference has normals is known to align / the stand-alone sums, which check point2plane again)
-  if (robust::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (h->comm) { h->err = "RobustOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
-  if (h->cov_on) { h->err = "RobustOutlierFilter: not together with PointToPlaneWithCovErrorMinimizer (its covariance takes binary weights)"; return LSGPU_BAD_CONFIG; }
-  if (h->dof()) { h->err = "RobustOutlierFilter: not together with PointToPlaneErrorMinimizer force2D / force4DOF (the constrained steps' first version takes binary distance filters)"; return LSGPU_BAD_CONFIG; }
-  h->robust = *cfg;
-  h->robust_on = true;
-  return LSGPU_OK;
+int lsgpu_icp_set_robust_filter(lsgpu_icp* h, const lsgpu_robust_config* cfg) { return set_module(h, &ModuleSet::robust, cfg); }
+int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) { return set_module(h, &ModuleSet::normals, cfg); }
+int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) { return set_module(h, &ModuleSet::covariance, cfg); }
+int lsgpu_icp_set_chain_cuts(lsgpu_icp* h, const lsgpu_chain_cuts* cuts) { return set_module(h, &ModuleSet::cuts, cuts); }
+int lsgpu_icp_set_max_density(lsgpu_icp* h, const lsgpu_max_density_config* cfg) { return set_module(h, &ModuleSet::max_density, cfg); }
+int lsgpu_icp_set_shadow(lsgpu_icp* h, const lsgpu_shadow_config* cfg) { return set_module(h, &ModuleSet::shadow, cfg); }
+int lsgpu_icp_set_cov_sampling(lsgpu_icp* h, const lsgpu_cov_sampling_config* cfg) { return set_module(h, &ModuleSet::cov_sampling, cfg); }
+int lsgpu_icp_set_motion(lsgpu_icp* h, const lsgpu_motion_config* cfg) { return set_module(h, &ModuleSet::motion, cfg); }
+
+int lsgpu_icp_set_modules(lsgpu_icp* h, const lsgpu_chain_modules* set) {
+  if (!h || !set) return LSGPU_BAD_ARG;
+  lsgpu_covariance_config cov;
+  lsgpu_covariance_config_default(&cov);
+  lsgpu_max_density_config md;
+  lsgpu_max_density_config_default(&md);
+  const bool has_cov = lsgpu_loaded_chain_covariance(&set->chain, &cov.sensor_std_dev) != 0;
+  const bool has_md = lsgpu_loaded_chain_max_density(&set->chain, &md.max_density) != 0;
+  ModuleSet m = module_set(h);
+  int rc = m.robust(set->chain.has_robust ? &set->chain.robust : nullptr);
+  if (!rc) rc = m.normals(set->chain.has_normals ? &set->chain.normals : nullptr);
+  if (!rc) rc = m.covariance(has_cov ? &cov : nullptr);
+  if (!rc) rc = m.cuts(&set->cuts);
+  if (!rc) rc = m.max_density(has_md ? &md : nullptr);
+  if (!rc) rc = m.shadow(&set->shadow);
+  if (!rc) rc = m.cov_sampling(&set->cov_sampling);
+  if (!rc) rc = m.motion(&set->motion);
+  return commit_modules(h, m, rc);
 }
 
 int lsgpu_icp_get_robust_trace(lsgpu_icp* h, lsgpu_robust_trace* out, int cap) {
   return h ? fetch_trace(h, h->rb_trace_dev.p, h->rb_trace_n, out, cap) : 0;
 }
 
-int lsgpu_icp_set_normals(lsgpu_icp* h, const lsgpu_normals_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (h->sh_on && h->sh_cfg.reading_eps >= 0.f && (!cfg || cfg->reading_sn_knn <= 0)) {
-    h->err = "ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn): remove the module first (lsgpu_icp_set_shadow)";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->cs_on && h->cs_cfg.reading_nb_sample > 0 && (!cfg || cfg->reading_sn_knn <= 0)) {
-    h->err = "CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (reading_sn_knn): remove the module first (lsgpu_icp_set_cov_sampling)";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (!cfg) { h->normals_on = false; return LSGPU_OK; }
-  const char* why = nullptr;
-  // (whether the reference has normals is known to align, for which a filter without them is inert)
-  if (normal_angle::check(cfg, h->cfg.error_minimizer, 1, &why) != LSGPU_OK) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (h->comm) { h->err = "SurfaceNormalOutlierFilter: the split-scan mode does not run it"; return LSGPU_BAD_CONFIG; }
-  if (h->cov_on && cfg->max_angle >= 0.f) { h->err = "SurfaceNormalOutlierFilter: not together with PointToPlaneWithCovErrorMinimizer (its covariance pass does not apply the angle test)"; return LSGPU_BAD_CONFIG; }
-  if (h->dof() && cfg->max_angle >= 0.f) { h->err = "SurfaceNormalOutlierFilter: not together with PointToPlaneErrorMinimizer force2D / force4DOF (the constrained steps' first version takes binary distance filters)"; return LSGPU_BAD_CONFIG; }
-  h->normals = *cfg;
-  h->normals_on = true;
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_covariance(lsgpu_icp* h, const lsgpu_covariance_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cfg) { h->cov_on = false; h->quality_state = 0; return LSGPU_OK; }
-  const char* const mod = "PointToPlaneWithCovErrorMinimizer: ";
-  if (!(cfg->sensor_std_dev >= 0.f) || std::isinf(cfg->sensor_std_dev)) { h->err = std::string(mod) + "sensorStdDev must be finite and >= 0"; return LSGPU_BAD_CONFIG; }
-  const char* with = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT ? "PointToPointErrorMinimizer (the handle's minimizer)"
-                   : h->cfg.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2"
-                   : h->robust_on ? "RobustOutlierFilter"
-                   : (h->normals_on && h->normals.max_angle >= 0.f) ? "SurfaceNormalOutlierFilter"
-                   : h->comm ? "the split-scan mode (lsgpu_icp_comm_init)" : nullptr;
-  if (with) { h->err = std::string(mod) + "not together with " + with; return LSGPU_BAD_CONFIG; }
-  if (h->md_on) { h->err = std::string(mod) + "not together with MaxDensityDataPointsFilter (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
-  if (h->sh_on) { h->err = std::string(mod) + "not together with ShadowDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
-  if (h->cs_on) { h->err = std::string(mod) + "not together with CovarianceSamplingDataPointsFilter (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
-  if (h->dof()) { h->err = std::string(mod) + "not together with PointToPlaneErrorMinimizer force2D / force4DOF (the covariance is that of the free 6-DOF step)"; return LSGPU_BAD_CONFIG; }
-  if (!h->cov_on) h->quality_state = 0;
-  h->cov_cfg = *cfg;
-  h->cov_on = true;
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_max_density(lsgpu_icp* h, const lsgpu_max_density_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cfg) { h->md_on = false; return LSGPU_OK; }
-  // (SurfaceNormalDataPointsFilter's knn comes with the chain: lsgpu_icp_compute checks that it is there)
-  if (const char* why = lsgpu_max_density_config_why(cfg, kSnfMinKnn)) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (h->comm) { h->err = "MaxDensityDataPointsFilter: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
-  if (h->cov_on) { h->err = "MaxDensityDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a thinned reference)"; return LSGPU_BAD_CONFIG; }
-  h->md_cfg = *cfg;
-  h->md_on = true;
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_shadow(lsgpu_icp* h, const lsgpu_shadow_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cfg) { h->sh_on = false; return LSGPU_OK; }
-  if (const char* why = lsgpu_shadow_config_why(cfg)) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (cfg->reading_eps < 0.f && cfg->reference_eps < 0.f) { h->sh_on = false; return LSGPU_OK; }
-  if (h->comm) { h->err = "ShadowDataPointsFilter: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
-  if (h->cov_on) { h->err = "ShadowDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
-  if (cfg->reading_eps >= 0.f && !(h->normals_on && h->normals.reading_sn_knn > 0)) {
-    h->err = "ShadowDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (lsgpu_icp_set_normals with reading_sn_knn) first";
-    return LSGPU_BAD_CONFIG;
-  }
-  h->sh_cfg = *cfg;
-  h->sh_on = true;
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_cov_sampling(lsgpu_icp* h, const lsgpu_cov_sampling_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cfg) { h->cs_on = false; return LSGPU_OK; }
-  if (const char* why = lsgpu_cov_sampling_config_why(cfg)) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (cfg->reading_nb_sample == 0 && cfg->reference_nb_sample == 0) { h->cs_on = false; return LSGPU_OK; }
-  if (h->comm) { h->err = "CovarianceSamplingDataPointsFilter: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
-  if (h->cov_on) { h->err = "CovarianceSamplingDataPointsFilter: not together with PointToPlaneWithCovErrorMinimizer (the covariance's first version does not cover a reference thinned behind the normals)"; return LSGPU_BAD_CONFIG; }
-  if (cfg->reading_nb_sample > 0 && !(h->normals_on && h->normals.reading_sn_knn > 0)) {
-    h->err = "CovarianceSamplingDataPointsFilter on the reading needs the reading's SurfaceNormalDataPointsFilter (lsgpu_icp_set_normals with reading_sn_knn) first";
-    return LSGPU_BAD_CONFIG;
-  }
-  h->cs_cfg = *cfg;
-  h->cs_on = true;
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_motion(lsgpu_icp* h, const lsgpu_motion_config* cfg) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cfg) { h->mo_on = false; return LSGPU_OK; }
-  if (const char* why = lsgpu_motion_config_why(cfg)) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (cfg->dof == LSGPU_MOTION_DOF_6 && !cfg->bound) { h->mo_on = false; return LSGPU_OK; }
-  if (cfg->dof != LSGPU_MOTION_DOF_6) {
-    const char* const mod = cfg->dof == LSGPU_MOTION_DOF_3 ? "PointToPlaneErrorMinimizer force2D: " : "PointToPlaneErrorMinimizer force4DOF: ";
-    const char* with = h->cfg.error_minimizer == LSGPU_MINIMIZER_POINT_TO_POINT ? "PointToPointErrorMinimizer (the handle's minimizer)"
-                     : h->cfg.matcher_knn >= 2 ? "KDTreeMatcher knn >= 2"
-                     : h->robust_on ? "RobustOutlierFilter"
-                     : (h->normals_on && h->normals.max_angle >= 0.f) ? "SurfaceNormalOutlierFilter"
-                     : h->cov_on ? "PointToPlaneWithCovErrorMinimizer"
-                     : h->comm ? "the split-scan mode (lsgpu_icp_comm_init)" : nullptr;
-    if (with) { h->err = std::string(mod) + "not together with " + with + " (the constrained steps are implemented for knn 1 and binary distance filters)"; return LSGPU_BAD_CONFIG; }
-  }
-  if (cfg->bound && h->comm) { h->err = "BoundTransformationChecker: the split-scan mode (lsgpu_icp_comm_init) does not run it"; return LSGPU_BAD_CONFIG; }
-  h->mo_cfg = *cfg;
-  h->mo_on = true;
-  return LSGPU_OK;
-}
-
-int lsgpu_icp_set_chain_cuts(lsgpu_icp* h, const lsgpu_chain_cuts* cuts) {
-  if (!h) return LSGPU_BAD_ARG;
-  h->err.clear();
-  if (!cuts || (cuts->n_reading == 0 && cuts->n_reference == 0)) { h->cuts_on = false; return LSGPU_OK; }
-  const std::string why = chain_cuts_why(cuts);
-  if (!why.empty()) { h->err = why; return LSGPU_BAD_CONFIG; }
-  if (h->comm) { h->err = "MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the ICP chain: the split-scan mode does not run them"; return LSGPU_BAD_CONFIG; }
-  h->cuts = *cuts;
-  h->cuts_on = true;
-  return LSGPU_OK;
-}
-
 int lsgpu_icp_get_quality(lsgpu_icp* h, lsgpu_icp_quality* out) {
   if (!h || !out) return LSGPU_BAD_ARG;
   h->err.clear();
-  if (!h->cov_on) { h->err = "get_quality: the covariance is not switched on (lsgpu_icp_set_covariance / PointToPlaneWithCovErrorMinimizer)"; return LSGPU_BAD_CONFIG; }
+  if (!h->mods.cov_on) { h->err = "get_quality: the covariance is not switched on (lsgpu_icp_set_covariance / PointToPlaneWithCovErrorMinimizer)"; return LSGPU_BAD_CONFIG; }
   if (h->quality_state == 0) { h->err = "get_quality: no alignment of this handle has returned LSGPU_OK since the covariance was switched on"; return LSGPU_NO_CONVERGENCE; }
   if (h->quality_state == 2) { h->err = "get_quality: H is singular (the pairs of the last iteration do not determine the pose)"; return LSGPU_NO_CONVERGENCE; }
   *out = h->quality;
@@ -941,7 +898,7 @@ static float matcher_max_d2(const lsgpu_icp* h) {
 // does the handle take the chain plan (lsgpu_policy.h)?
 static bool chain_on(const lsgpu_icp* h) {
   return policy::chain_fields(h->cfg.matcher_max_dist, h->cfg.outlier_max_dist, h->cfg.outlier_min_dist, h->cfg.outlier_median_factor,
-                              h->robust_on, h->normals_on && h->normals.max_angle >= 0.f);
+                              h->mods.robust_on, h->mods.normals_on && h->mods.normals.max_angle >= 0.f);
 }
 
 static float price_share(const lsgpu_icp* h) {   // heavy lanes / searching lanes of the priced launch (its counters are on the host)
@@ -1437,41 +1394,9 @@ int lsgpu_icp_comm_init(lsgpu_icp* h, int rank, int nranks, const void* id) {
   if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return LSGPU_BAD_ARG;
   h->err.clear();
   RcclApi* api = rccl_api();
-  if (h->cfg.matcher_knn >= 2) {
-    h->err = "comm_init: the split-scan mode runs knn 1 only (matcher_knn >= 2 is not supported there)";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->cov_on) {
-    h->err = "comm_init: the split-scan mode does not run PointToPlaneWithCovErrorMinimizer";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->md_on) {
-    h->err = "comm_init: the split-scan mode does not run MaxDensityDataPointsFilter";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->sh_on) {
-    h->err = "comm_init: the split-scan mode does not run ShadowDataPointsFilter";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->cs_on) {
-    h->err = "comm_init: the split-scan mode does not run CovarianceSamplingDataPointsFilter";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->cuts_on) {
-    h->err = "comm_init: the split-scan mode does not run MaxDist- / MinDist- / BoundingBox- / RemoveNaNDataPointsFilter in the ICP chain";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (h->dof() || h->bound()) {
-    h->err = h->dof() ? "comm_init: the split-scan mode does not run PointToPlaneErrorMinimizer force2D / force4DOF"
-                      : "comm_init: the split-scan mode does not run BoundTransformationChecker";
-    return LSGPU_BAD_CONFIG;
-  }
-  if (chain_on(h)) {
-    h->err = (h->normals_on && h->normals.max_angle >= 0.f) ? "comm_init: the split-scan mode does not run SurfaceNormalOutlierFilter"
-           : h->robust_on ? "comm_init: the split-scan mode does not run RobustOutlierFilter"
-                          : "comm_init: the split-scan mode runs neither KDTreeMatcher maxDist nor Max- / Min- / MedianDistOutlierFilter";
-    return LSGPU_BAD_CONFIG;
-  }
+  ModuleSet m = module_set(h);
+  m.f.comm = true;   // (the handle as it would be behind this call)
+  if (m.ask(modules::kCommInit) != LSGPU_OK) { h->err = m.err; return LSGPU_BAD_CONFIG; }
   if (!api) { h->err = "librccl.so.1 could not be loaded"; return LSGPU_HIP_ERROR; }
   HIPC(hipSetDevice(h->device));
   if (h->comm) { (void)api->CommDestroy(h->comm); h->comm = nullptr; }
@@ -1629,9 +1554,9 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
                        idp, dp, h->pts.p, h->nrm.p, h->ref_inv.p,
                        (const uint32_t*)nullptr, (const SelState*)nullptr, limit, (float*)nullptr, h->ne_partials.p,
                        robust::Params{}, 1.f);
-  } else if (h->robust_on) {
+  } else if (h->mods.robust_on) {
     // RobustOutlierFilter: the pairs' weights go into the sums; the scale is the MAD of the distances given (host twin)
-    const robust::Params rp = robust::params(h->robust);
+    const robust::Params rp = robust::params(h->mods.robust);
     if (rp.plane && !h->have_normals) { h->err = std::string(what) + ": RobustOutlierFilter distanceType point2plane needs reference normals"; return LSGPU_BAD_CONFIG; }
     float scale = 1.f, med = 0.f;
     if (rp.mad) {
@@ -1663,8 +1588,8 @@ static int stand_alone_sums(lsgpu_icp* h, const char* what, const float* query_x
 int lsgpu_normal_eq(lsgpu_icp* h, const float* query_xyz1, int64_t nq, const float T[16],
                     const int32_t* ids, const float* d2, float limit, double out[29]) {
   // (a force2D / force4DOF handle: the sums of its mode -- force2D forms b with the planar residual)
-  if (h && h->dof() == LSGPU_MOTION_DOF_3) return stand_alone_sums<kPointToPlane2D>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
-  if (h && h->dof() == LSGPU_MOTION_DOF_4) return stand_alone_sums<kPointToPlane4Dof>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
+  if (h && h->mods.dof() == LSGPU_MOTION_DOF_3) return stand_alone_sums<kPointToPlane2D>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
+  if (h && h->mods.dof() == LSGPU_MOTION_DOF_4) return stand_alone_sums<kPointToPlane4Dof>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
   return stand_alone_sums<kPointToPlane>(h, "normal_eq", query_xyz1, nq, T, ids, d2, limit, out);
 }
 
@@ -2853,8 +2778,8 @@ static bool chain_ok(const lsgpu_icp* h, const lsgpu_chain_config* chain, bool r
 }
 // somebody behind the reference's section reads its normals: the minimizer, the robust filter's residuals, the angle filter
 static bool reference_normals_read(const lsgpu_icp* h) {
-  const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
-  const bool na_filter = h->normals_on && h->normals.max_angle >= 0.f;
+  const bool rb_plane = h->mods.robust_on && h->mods.robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
+  const bool na_filter = h->mods.normals_on && h->mods.normals.max_angle >= 0.f;
   return h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter;
 }
 
@@ -2905,9 +2830,9 @@ struct ComputeRun {
       h->err = "compute: one reference filter, ssn_knn or sn_knn in [3, 32] (none only with the point-to-point minimizer)";
       return LSGPU_BAD_CONFIG;
     }
-    nc = h->normals_on ? &h->normals : nullptr;
+    nc = h->mods.normals_on ? &h->mods.normals : nullptr;
     // who reads the reference normals behind the section: the minimizer, the robust filter's residuals, the angle filter
-    const bool rb_plane = h->robust_on && h->robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
+    const bool rb_plane = h->mods.robust_on && h->mods.robust.distance_type == LSGPU_ROBUST_DIST_POINT2PLANE;
     const bool na_filter = nc && nc->max_angle >= 0.f;
     if (nc && (na_filter || nc->reference_orient) && chain->ssn_knn == 0 && chain->sn_knn == 0 && !ref_given) {
       h->err = "compute: SurfaceNormalOutlierFilter / OrientNormalsDataPointsFilter need the normals of a reference filter";
@@ -2916,10 +2841,10 @@ struct ComputeRun {
     section::Inputs in;
     in.module = chain->ssn_knn != 0 ? section::Module::Sampling : chain->sn_knn != 0 ? section::Module::SurfaceNormal : section::Module::None;
     in.normals_read = h->cfg.error_minimizer != LSGPU_MINIMIZER_POINT_TO_POINT || rb_plane || na_filter;
-    in.max_density = h->md_on;
-    in.ref_shadow = h->sh_on && h->sh_cfg.reference_eps >= 0.f; in.ref_cov_sampling = h->cs_on && h->cs_cfg.reference_nb_sample > 0;
+    in.max_density = h->mods.md_on;
+    in.ref_shadow = h->mods.sh_on && h->mods.sh_cfg.reference_eps >= 0.f; in.ref_cov_sampling = h->mods.cs_on && h->mods.cs_cfg.reference_nb_sample > 0;
     in.rd_normals = nc && nc->reading_sn_knn > 0;
-    in.rd_shadow = h->sh_on && h->sh_cfg.reading_eps >= 0.f; in.rd_cov_sampling = h->cs_on && h->cs_cfg.reading_nb_sample > 0;
+    in.rd_shadow = h->mods.sh_on && h->mods.sh_cfg.reading_eps >= 0.f; in.rd_cov_sampling = h->mods.cs_on && h->mods.cs_cfg.reading_nb_sample > 0;
     in.ref_carried = ref_given; in.rd_carried = rd_given && na_filter;   // (the reading's normals: the angle filter alone reads them)
     in.comm = h->comm != nullptr; in.side_switch = tuning().side_stream;
     plan = section::plan(in);
@@ -2930,7 +2855,7 @@ struct ComputeRun {
     if (nr < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
     HIPC(hipSetDevice(h->device));
     t0 = wall_ms();
-    cuts = h->cuts_on ? &h->cuts : nullptr;
+    cuts = h->mods.cuts_on ? &h->mods.cuts : nullptr;
     rd_rs = chain->reading_prob >= 0.f;
     rd_cuts = cuts && cuts->n_reading > 0; ref_cuts = cuts && cuts->n_reference > 0;
     rd_pre_cuts = rd_cuts && rd_rs && cut_section_of(*cuts, 0, true).n_pre > 0;
@@ -2997,7 +2922,7 @@ struct ComputeRun {
     HIPC(h->flt_ref.reserve(c.n)); HIPC(h->flt_nrm.reserve(3 * c.n));
     int rc = draws.ready((size_t)nr);
     int64_t n_dense = 0;
-    if (!rc) rc = max_density_enqueue(h, c.pts, c.n, h->dens.p, h->md_cfg.max_density, h->ssn_draws.p + draws.used, emits, h->flt_ref.p, h->flt_nrm.p);
+    if (!rc) rc = max_density_enqueue(h, c.pts, c.n, h->dens.p, h->mods.md_cfg.max_density, h->ssn_draws.p + draws.used, emits, h->flt_ref.p, h->flt_nrm.p);
     if (!rc) rc = max_density_wait(h, &n_dense, &c.n);
     if (rc) return rc;
     draws.used += (size_t)n_dense;
@@ -3009,7 +2934,7 @@ struct ComputeRun {
     const bool gathered = plan.shadow_normals == section::ShadowNormals::Gathered;
     DevBuf<float4>& pts = gathered ? h->flt_ref : h->sh_ref; DevBuf<float>& nrm = gathered ? h->flt_nrm : h->sh_nrm;
     HIPC(pts.reserve(c.n)); HIPC(nrm.reserve(3 * c.n));
-    int rc = shadow_enqueue(h, c.pts, c.nrm, c.n, h->sh_cfg.reference_eps, pts.p, nrm.p);
+    int rc = shadow_enqueue(h, c.pts, c.nrm, c.n, h->mods.sh_cfg.reference_eps, pts.p, nrm.p);
     if (!rc) rc = shadow_wait(h, &c.n);
     if (rc) return rc;
     c.pts = pts.p; c.nrm = nrm.p;
@@ -3017,11 +2942,11 @@ struct ComputeRun {
   }
   // CovarianceSampling, the section's last stage: fewer points than nbSample pass unchanged
   int cov_sampling_stage(Cloud& c) {
-    const int64_t nb = h->cs_cfg.reference_nb_sample;
+    const int64_t nb = h->mods.cs_cfg.reference_nb_sample;
     if (nb >= c.n) return LSGPU_OK;
     HIPC(h->cs_ref.reserve(nb)); HIPC(h->cs_ref_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
     double sums[covs::kSums];
-    const int rc = cov_sampling_run(h, c.pts, c.nrm, c.n, nb, h->cs_cfg.reference_torque_norm, h->cs_ref.p, h->cs_ref_nrm.p, h->cs_pick.p, sums, nullptr);
+    const int rc = cov_sampling_run(h, c.pts, c.nrm, c.n, nb, h->mods.cs_cfg.reference_torque_norm, h->cs_ref.p, h->cs_ref_nrm.p, h->cs_pick.p, sums, nullptr);
     if (rc) { h->nr = 0; return rc; }
     c = {h->cs_ref.p, h->cs_ref_nrm.p, nb};
     return LSGPU_OK;
@@ -3048,7 +2973,7 @@ struct ComputeRun {
       if (nrc < chain->sn_knn) { h->err = "compute: the reference has fewer points than SurfaceNormalDataPointsFilter's knn"; return LSGPU_BAD_ARG; }
       src = h->cut_ref.p;
     }
-    plan = section::settle(plan, h->cs_cfg.reference_nb_sample, nrc);   // (the count is on the host: the plan is final from here on)
+    plan = section::settle(plan, h->mods.cs_cfg.reference_nb_sample, nrc);   // (the count is on the host: the plan is final from here on)
     ref = {src, nullptr, nrc};   // (no normals module, or normals on the final grid: the reference as given, no draw)
     if (carried) {
       // the reference's orientation pair flips normals where they stand: never in a buffer of the caller's
@@ -3203,17 +3128,17 @@ struct ComputeRun {
     HIPC(hipGetLastError());
     if (plan.rd_shadow) {   // the loop and the angle filter see the kept points and their normals from here on
       HIPC(h->sh_rd.reserve(nqf));
-      rc = shadow_enqueue(h, rd_dev, rn, nqf, h->sh_cfg.reading_eps, h->sh_rd.p, h->rd_nrm.p);
+      rc = shadow_enqueue(h, rd_dev, rn, nqf, h->mods.sh_cfg.reading_eps, h->sh_rd.p, h->rd_nrm.p);
       if (!rc) rc = shadow_wait(h, &nqf);
       if (rc) return rc;
       if (nqf <= 0) { h->err = "compute: the reading filter left no point"; return LSGPU_NO_CONVERGENCE; }
       rd_dev = h->sh_rd.p;
     }
-    if (plan.rd_cov_sampling && h->cs_cfg.reading_nb_sample < nqf) {   // behind the normals, their orientation and the Shadow pass
-      const int64_t nb = h->cs_cfg.reading_nb_sample;
+    if (plan.rd_cov_sampling && h->mods.cs_cfg.reading_nb_sample < nqf) {   // behind the normals, their orientation and the Shadow pass
+      const int64_t nb = h->mods.cs_cfg.reading_nb_sample;
       HIPC(h->cs_rd.reserve(nb)); HIPC(h->cs_rd_nrm.reserve(3 * nb)); HIPC(h->cs_pick.reserve(nb));
       double sums[covs::kSums];
-      rc = cov_sampling_run(h, rd_dev, h->rd_nrm.p, nqf, nb, h->cs_cfg.reading_torque_norm, h->cs_rd.p, h->cs_rd_nrm.p, h->cs_pick.p, sums, nullptr);
+      rc = cov_sampling_run(h, rd_dev, h->rd_nrm.p, nqf, nb, h->mods.cs_cfg.reading_torque_norm, h->cs_rd.p, h->cs_rd_nrm.p, h->cs_pick.p, sums, nullptr);
       if (rc) { h->nr = 0; return rc; }   // (the grid the handle holds is the reading's: no reference to align against)
       HIPC(hipMemcpyAsync(h->rd_nrm.p, h->cs_rd_nrm.p, (size_t)nb * 12, hipMemcpyDeviceToDevice, h->stream));   // (where the loop reads them)
       rd_dev = h->cs_rd.p; nqf = nb;
@@ -3906,10 +3831,10 @@ struct AlignRun {
     ca.lo2 = h->cfg.outlier_min_dist * h->cfg.outlier_min_dist;
     ca.max2 = (h->cfg.outlier_max_dist > 0.f && !std::isinf(h->cfg.outlier_max_dist)) ? h->cfg.outlier_max_dist * h->cfg.outlier_max_dist : INFINITY;
     ca.med_factor = h->cfg.outlier_median_factor; ca.has_median = h->cfg.outlier_median_factor > 0.f ? 1 : 0;
-    robust = h->robust_on;
-    if (robust) { ca.rb = robust::params(h->robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
+    robust = h->mods.robust_on;
+    if (robust) { ca.rb = robust::params(h->mods.robust); ca.has_trim = h->cfg.trim_ratio < 1.f ? 1 : 0; }
     // SurfaceNormalOutlierFilter: inert without reading normals or without reference normals (as upstream)
-    angle = chain && h->normals_on && h->normals.max_angle >= 0.f && h->have_normals && reading_xyz1 && x.reading_normals;
+    angle = chain && h->mods.normals_on && h->mods.normals.max_angle >= 0.f && h->have_normals && reading_xyz1 && x.reading_normals;
     if (robust && ca.rb.plane && !h->have_normals) {
       h->err = "align: RobustOutlierFilter distanceType point2plane needs reference normals";
       return LSGPU_BAD_CONFIG;
@@ -3988,7 +3913,7 @@ struct AlignRun {
       HIPC(h->rd_nrm0.reserve((size_t)3 * nq)); HIPC(h->na_trace_dev.reserve((size_t)max_it));
       hipLaunchKernelGGL(k_rotate3, dim3(nblk(nq)), dim3(256), 0, h->stream, h->rd_nrm.p, nq, to_mat34(T_rm_in), h->rd_nrm0.p);
       HIPC(hipGetLastError());
-      ca.na_rn = h->rd_nrm0.p; ca.na_eps = normal_angle::eps_of(h->normals.max_angle); ca.na_trace = h->na_trace_dev.p;
+      ca.na_rn = h->rd_nrm0.p; ca.na_eps = normal_angle::eps_of(h->mods.normals.max_angle); ca.na_trace = h->na_trace_dev.p;
     }
     hst = &h->pin->state;
     std::memset(hst, 0, sizeof(IcpState));
@@ -4032,9 +3957,9 @@ struct AlignRun {
     ne_loop = p2p ? k_normal_eq_loop<kPointToPoint> : k_normal_eq_loop<kPointToPlane>;
     update = p2p ? k_icp_update<kPointToPoint> : k_icp_update<kPointToPlane>;
     ne_loop_k = ne_loop_fn(p2p, kk, chain, robust);
-    if (h->dof() == LSGPU_MOTION_DOF_4) constrained_kernels<kPointToPlane4Dof>(chain, &ne_loop, &ne_loop_k, &update);
-    if (h->dof() == LSGPU_MOTION_DOF_3) constrained_kernels<kPointToPlane2D>(chain, &ne_loop, &ne_loop_k, &update);
-    if (h->bound()) HIPC(h->h_chk.reserve((size_t)8 * (max_it + 2)));   // the bound's host copy of the checker history
+    if (h->mods.dof() == LSGPU_MOTION_DOF_4) constrained_kernels<kPointToPlane4Dof>(chain, &ne_loop, &ne_loop_k, &update);
+    if (h->mods.dof() == LSGPU_MOTION_DOF_3) constrained_kernels<kPointToPlane2D>(chain, &ne_loop, &ne_loop_k, &update);
+    if (h->mods.bound()) HIPC(h->h_chk.reserve((size_t)8 * (max_it + 2)));   // the bound's host copy of the checker history
     ca.hist_med = h->hist_med.p; ca.sel_med = h->sel_med.p;
     return LSGPU_OK;
   }
@@ -4052,7 +3977,7 @@ struct AlignRun {
     pc.two_pass_select = !h->comm && tuning().fused_select && tuning().two_pass_select;
     pc.cone_probe = tuning().cone_probe; pc.cone_heavy_share = tuning().cone_heavy_share; pc.cone_max_occupancy = tuning().cone_max_occupancy;
     pc.kmatch = kmatch; pc.chain = chain;
-    pc.robust_mad = robust && ca.rb.mad; pc.robust_scale_iters = robust ? h->robust.nb_iteration_for_scale : 0;
+    pc.robust_mad = robust && ca.rb.mad; pc.robust_scale_iters = robust ? h->mods.robust.nb_iteration_for_scale : 0;
     const bool index = x.build_index_on_side ? cone_wanted(h) : h->cone_ok;   // (built behind the first iteration, feed(): h->cone_ok is false until then)
     if (x.build_index_on_side) h->cone_decided = false;
     // a handle whose last alignments found the index slower than the voxel grid leaves it alone for a while (and spares
@@ -4151,7 +4076,7 @@ struct AlignRun {
   // and exits at once if the state it finds says `done`.
   int fetch_state(int* enqueued_ahead) {
     *enqueued_ahead = 0;
-    if (h->bound())   // BoundTransformationChecker: the history travels with the state (evaluated after the loop, check_bound)
+    if (h->mods.bound())   // BoundTransformationChecker: the history travels with the state (evaluated after the loop, check_bound)
       HIPC(hipMemcpyAsync(h->h_chk.p, h->chk_hist.p, (size_t)8 * (max_it + 2) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipMemcpyAsync(hst, h->state.p, sizeof(IcpState), hipMemcpyDeviceToHost, h->stream));
     policy::Iteration ahead_it;
@@ -4240,7 +4165,7 @@ struct AlignRun {
   // front of the counter has seen it.  true: violated, h->err holds the text.  A loop that failed by itself did so behind
   // every entry of its history, so a violation found here came first.
   bool check_bound() {
-    const lsgpu_motion_config& mc = h->mo_cfg;
+    const lsgpu_motion_config& mc = h->mods.mo_cfg;
     int n = std::min(hst->n_hist, max_it + 2);
     float* hist = h->h_chk.p;
     if (mc.bound_before_counter && hst->status == LSGPU_OK && hst->done && !hst->converged && hst->iter > 0 && n <= max_it + 1) {
@@ -4384,7 +4309,7 @@ static int covariance_pass(AlignRun& run, lsgpu_icp_stats& st) {
   q.residual = s[43];
   q.n_pairs = (int64_t)s[42];
   q.used_ratio = (float)((double)q.n_pairs / (double)nq);
-  const int rs = lsgpu_point_to_plane_cov_solve(s, h->cov_cfg.sensor_std_dev, q.covariance);
+  const int rs = lsgpu_point_to_plane_cov_solve(s, h->mods.cov_cfg.sensor_std_dev, q.covariance);
   h->quality = q;
   h->quality_state = rs == LSGPU_OK ? 1 : 2;
   st.t_total_ms = wall_ms() - run.t0;
@@ -4409,11 +4334,11 @@ static int align_run(lsgpu_icp* h, const float* reading_xyz1, int64_t nq, const 
   if (!rc) rc = run.feed();
   if (rc) return rc;
   rc = run.harvest(T_out, st);
-  if ((rc == LSGPU_OK || rc == LSGPU_NO_CONVERGENCE) && h->bound() && run.check_bound()) {
+  if ((rc == LSGPU_OK || rc == LSGPU_NO_CONVERGENCE) && h->mods.bound() && run.check_bound()) {
     std::memcpy(T_out, T_init, 16 * sizeof(float));
     rc = LSGPU_NO_CONVERGENCE;
   }
-  if (rc == LSGPU_OK && h->cov_on) {
+  if (rc == LSGPU_OK && h->mods.cov_on) {
     const int rq = covariance_pass(run, st);
     if (rq) { std::memcpy(T_out, T_init, 16 * sizeof(float)); return rq; }
   }

@@ -91,18 +91,18 @@ class IcpHandle:
         RobustConfig, a dict of its fields, or an _lib.RobustCfg) -- lsgpu_icp_set_robust_filter.  normals: None, or a
         NormalsConfig / dict of its fields / _lib.NormalsCfg (SurfaceNormalOutlierFilter, reading normals, oriented
         normals) -- lsgpu_icp_set_normals.  covariance: None, or PointToPlaneWithCovErrorMinimizer's sensorStdDev --
-        lsgpu_icp_set_covariance (given last: it refuses a handle with modules its pass does not cover).  cuts: None, or the
+        lsgpu_icp_set_covariance.  cuts: None, or the
         cut modules of the two filter sections (a ChainCuts, a dict of its fields, or an _lib.ChainCuts) --
         lsgpu_icp_set_chain_cuts.  max_density: None, or MaxDensityDataPointsFilter's maxDensity behind the reference's
         SurfaceNormalDataPointsFilter (compute's sn_knn) -- lsgpu_icp_set_max_density.  shadow: None, or
         ShadowDataPointsFilter's eps as (reading_eps, reference_eps), None or a negative value for a side without the module
         (a dict with those keys or an _lib.ShadowCfg too) -- lsgpu_icp_set_shadow (the reading's needs `normals` with
         reading_sn_knn).  motion: None, or PointToPlaneErrorMinimizer's force2D / force4DOF and BoundTransformationChecker (a
-        MotionConfig, a dict of its fields, or an _lib.MotionCfg) -- lsgpu_icp_set_motion (given last: it refuses a handle with
-        modules the constrained steps do not cover).  cov_sampling: None, or CovarianceSamplingDataPointsFilter's
+        MotionConfig, a dict of its fields, or an _lib.MotionCfg) -- lsgpu_icp_set_motion.  cov_sampling: None, or CovarianceSamplingDataPointsFilter's
         ((reading_nb_sample, reading_torque_norm), (reference_nb_sample, reference_torque_norm)), None for a side without the
         module (a dict of lsgpu_cov_sampling_config's fields or an _lib.CovSamplingCfg too) -- lsgpu_icp_set_cov_sampling (the
-        reading's needs `normals` with reading_sn_knn)."""
+        reading's needs `normals` with reading_sn_knn).  The modules are applied together (lsgpu_icp_set_modules): which of them
+        go together is the library's rule set, and a refusal leaves no handle behind."""
         L = _lib.lib()
         nc = normals_cfg(normals) if normals is not None else None
         if nc is not None:                                      # refused values: before the device is touched
@@ -136,30 +136,38 @@ class IcpHandle:
         if rc != _lib.OK:
             self._h = None
             _raise(rc, "lsgpu_icp_create (is a ROCm GPU visible?)")
-        self.robust = None
+        # the module set as one record (what lsgpu_chain_load_modules makes of a document), applied in one call: all or nothing
+        m = _lib.ChainModules()
+        for default, part in ((L.lsgpu_shadow_config_default, m.shadow), (L.lsgpu_motion_config_default, m.motion),
+                              (L.lsgpu_cov_sampling_config_default, m.cov_sampling)):
+            default(C.byref(part))
         if rb is not None:
-            self.set_robust_filter(rb)
-        self.normals = None
+            m.chain.robust, m.chain.has_robust = rb, 1
         if nc is not None:
-            self.set_normals(nc)
-        self.covariance = None
-        if covariance is not None:
-            self.set_covariance(covariance)
-        self.cuts = None
+            m.chain.normals, m.chain.has_normals = nc, 1
+        # (the two values lsgpu_loaded_chain carries in reserved[]: flag and float, as lsgpu_loaded_chain_covariance / _max_density read them)
+        for at, v in ((0, covariance), (4, max_density)):
+            if v is not None:
+                m.chain.reserved[at] = 1
+                m.chain.reserved[at + 1] = int(np.float32(v).view(np.int32))
         if cuts is not None:
-            self.set_chain_cuts(cuts)
-        self.max_density = None
-        if max_density is not None:
-            self.set_max_density(max_density)
-        self.shadow = None
+            m.cuts = chain_cuts_cfg(cuts)
         if shadow is not None:
-            self.set_shadow(shadow)
-        self.cov_sampling = None
+            m.shadow = shadow_cfg(shadow)
         if cov_sampling is not None:
-            self.set_cov_sampling(cov_sampling)
-        self.motion = None
+            m.cov_sampling = cov_sampling_cfg(cov_sampling)
         if motion is not None:
-            self.set_motion(motion)
+            m.motion = motion_cfg(motion)
+        rc = L.lsgpu_icp_set_modules(self._h, C.byref(m))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_icp_set_modules", self._h)
+        self.robust, self.normals = rb, nc
+        self.covariance = None if covariance is None else float(np.float32(covariance))
+        self.cuts = m.cuts if m.cuts.n_reading or m.cuts.n_reference else None
+        self.max_density = None if max_density is None else float(np.float32(max_density))
+        self.shadow = (float(m.shadow.reading_eps), float(m.shadow.reference_eps)) if m.shadow.reading_eps >= 0 or m.shadow.reference_eps >= 0 else None
+        self.cov_sampling = _cov_sampling_pairs(m.cov_sampling) if cov_sampling is not None else None
+        self.motion = _motion_config(m.motion) if m.motion.dof or m.motion.bound else None
 
     def set_motion(self, motion):
         """lsgpu_icp_set_motion: PointToPlaneErrorMinimizer's force2D / force4DOF step and BoundTransformationChecker of this
@@ -1574,13 +1582,23 @@ def chain_load_motion(doc):
     return rc, why.value.decode(), out
 
 
+def chain_load_modules(doc, carried: int = 0):
+    """lsgpu_chain_load_modules: the whole document in one walk -> (return code, reason of a refusal, _lib.ChainModules): what
+    chain_load and the part loaders give, in one record, under the declaration `carried`."""
+    arr, n, _keep = _yaml_modules(doc)
+    out = _lib.ChainModules()
+    why = C.create_string_buffer(512)
+    rc = _lib.lib().lsgpu_chain_load_modules(arr, n, int(carried), C.byref(out), why, len(why))
+    return rc, why.value.decode(), out
+
+
 def _f32(x) -> float:
     """The shortest decimal that is this float32 (0.75, not 0.75000000000000011...): what the document said."""
     return float(str(np.float32(x)))
 
 
 def _chain_config(lc, cuts=None, shadow=None, motion=None, cov_sampling=None) -> "ChainConfig":
-    """_lib.LoadedChain (and the _lib.ChainCuts of the same document, if it has cut modules) -> ChainConfig"""
+    """_lib.LoadedChain (and the other parts of the same document's _lib.ChainModules) -> ChainConfig"""
     i, c = lc.icp, lc.chain
     name = {v: k for k, v in _MINIMIZERS.items()}[i.error_minimizer]
     ch = ChainConfig(reading_sampling_prob=_f32(c.reading_prob), surface_normal_knn=c.ssn_knn,
@@ -1653,33 +1671,11 @@ class ICP:
             doc = {}
         if not isinstance(doc, dict):
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", "not a YAML mapping")
-        rc, why, loaded = chain_load(doc, carried)
+        rc, why, loaded = chain_load_modules(doc, carried)
         if rc != _lib.OK:
             raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        if carried:
-            rc, why, cuts, shadow, motion, cov_sampling = chain_load_parts_carried(doc, carried)
-            if rc != _lib.OK:
-                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-            self.chain = _chain_config(loaded, cuts, shadow, motion, cov_sampling)
-            self.carried = int(carried)
-            self._handle = None
-            return
-        self.carried = 0
-        cuts = None
-        if loaded.reserved[2] or loaded.reserved[3]:            # the document has cut modules: the modules themselves
-            rc, why, cuts = chain_load_cuts(doc)
-            if rc != _lib.OK:
-                raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        rc, why, shadow = chain_load_shadow(doc)                # (lsgpu_loaded_chain has no slot for the module: its own entry)
-        if rc != _lib.OK:
-            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        rc, why, motion = chain_load_motion(doc)                # (likewise: force2D / force4DOF, BoundTransformationChecker)
-        if rc != _lib.OK:
-            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        rc, why, cov_sampling = chain_load_cov_sampling(doc)    # (likewise: CovarianceSamplingDataPointsFilter)
-        if rc != _lib.OK:
-            raise LsgpuError(_lib.BAD_CONFIG, "load_from_yaml", why)
-        self.chain = _chain_config(loaded, cuts, shadow, motion, cov_sampling)
+        self.chain = _chain_config(loaded.chain, loaded.cuts, loaded.shadow, loaded.motion, loaded.cov_sampling)
+        self.carried = int(carried)
         self._handle = None
 
     def _ensure_handle(self) -> IcpHandle:
