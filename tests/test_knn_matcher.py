@@ -222,7 +222,7 @@ def _device_vs_host(icp_mod, oracle, brute, pair, k, p2p, seed=4):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("k,p2p", [(3, False), (3, True), (8, False)])
+@pytest.mark.parametrize("k,p2p", [(3, False), (3, True), (8, False), (2, False), (5, False), (6, True), (7, False)])
 def test_device_loop_matches_host_loop_4k(icp_mod, oracle, brute, pair4k, k, p2p):
     Tg, st, trg, Th, ith, convh, trh = _device_vs_host(icp_mod, oracle, brute, pair4k, k, p2p)
     assert (st.iterations, st.converged) == (ith, int(convh)), (st.iterations, st.converged, ith, convh)

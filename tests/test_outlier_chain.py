@@ -52,7 +52,11 @@ CHAINS = {
     "median": dict(median=1.5),
     "all": dict(trim=0.9, matcher=0.5, max=0.45, min=0.1, median=2.0),
     "all64k": dict(trim=0.9, matcher=0.25, max=0.2, min=0.05, median=2.0),     # (the denser pair)
+    # a maxDist above the k-best search's 1 m cap: a reading point with an invalid match searches the whole 3.25 m ball
+    # again through the fallback in every iteration, and its list may come back partly empty (tests/test_knn_k_edges.py)
+    "wide-matcher+trim": dict(trim=0.75, matcher=3.25),
 }
+WIDE = "wide-matcher+trim"
 
 
 def _fields(ch):
@@ -317,8 +321,8 @@ def test_reference_loop_without_new_fields_is_the_oracle_loop(oracle, brute, pai
 
 
 # (pair fixture, k, p2p, chain) of every device-loop case below
-LOOP_CASES = [("pair4k", k, p2p, name) for name in CHAINS if name != "all64k" for k in (1, 3) for p2p in (False, True)] + \
-             [("pair64k", 1, False, "all64k")]
+LOOP_CASES = [("pair4k", k, p2p, name) for name in CHAINS if name not in ("all64k", WIDE) for k in (1, 3) for p2p in (False, True)] + \
+             [("pair64k", 1, False, "all64k"), ("pair4k", 4, False, WIDE), ("pair4k", 2, True, WIDE)]
 
 _host_cache = {}
 
@@ -349,7 +353,9 @@ def _batch_pairs(oracle):
 def _check_not_vacuous(case, ch, r, t, binding):
     assert r is not None and t is not None, case
     _T, _it, _conv, trace, facts = r
-    if ch.get("matcher"):
+    if ch is CHAINS[WIDE]:                                       # (3.25 m leaves the pair few invalid matches: some, in every iteration)
+        assert all(0.0 < f["invalid"] <= 0.60 for f in facts), (case, [f["invalid"] for f in facts])
+    elif ch.get("matcher"):
         assert 0.05 <= facts[0]["invalid"] <= 0.60, (case, facts[0]["invalid"])
     if ch.get("min"):
         assert facts[-1]["min_removed"] >= 0.01 * facts[-1]["valid"], (case, facts[-1])
