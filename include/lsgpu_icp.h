@@ -1171,6 +1171,38 @@ int lsgpu_icp_set_modules(lsgpu_icp* h, const lsgpu_chain_modules* set);
  * file that runs the module (the input filters).  Host only. */
 int lsgpu_surface_normal_params_check(const lsgpu_yaml_param* params, int n_params, int* knn, char* why, int why_cap);
 
+/* ---- Ingest: a raw scan through the input filters, with its normals, into a cloud slot -- one call, on this handle
+ * lsgpu_cloud_ingest on a cloud in host or device memory does what these three calls do, bit for bit:
+ *   lsgpu_apply_point_filters(h, filters, n_filters, xyz1, n, seed, kept, &m);
+ *   if (normals_knn > 0) lsgpu_icp_reading_normals(h, kept, m, normals_knn, orient, sensor, normals);
+ *   lsgpu_cloud_upload_normals(h, slot, kept, normals_knn > 0 ? normals : NULL, m);
+ * with one upload of the raw scan and no second handle: the point modules, the grid, the normals search and one store kernel
+ * run on this handle's stream and buffers (which grow on demand; nothing is freed per call).  The same are: the slot's points
+ * (4th component included) and normals, the number and order of the draws consumed, seed's meaning, filters[k].state of
+ * FixStepSampling.  normals_knn 0 ingests without normals: no grid is built and the slot carries none afterwards.
+ * out_xyz1 (room for n points) and out_normals (3 n floats), each nullable, host or device, receive the kept cloud: one copy
+ * each on the handle's stream, one synchronise at the end.  *n_out (nullable): the kept count (on a failure of the normals'
+ * step what the point modules had kept, else 0 on failure).
+ *  - Argument and configuration errors return before the device or the slot is touched: the slot stays as it was, no draw is
+ *    consumed, seed is not taken.  These are what lsgpu_apply_point_filters refuses (LSGPU_BAD_ARG, LSGPU_BAD_CONFIG with its
+ *    texts), and LSGPU_BAD_ARG with a text for normals_knn not 0 and outside 3..32, orient outside 0..2, orient set without
+ *    sensor or with normals_knn 0, out_normals given with normals_knn 0.
+ *  - Once device work has begun any failure leaves the slot EMPTY (lsgpu_cloud_size: -1) and carries the composition's code
+ *    and text: LSGPU_NO_CONVERGENCE "no points to filter", LSGPU_BAD_ARG for fewer kept points than knn or for a NaN reaching
+ *    VoxelGrid, OctreeGrid or the normals' grid, a HIP error.
+ *  - A chain whose last module keeps nothing, with normals_knn 0, succeeds with an empty cloud (size 0), as the composition.
+ *  - With normals_knn > 0 the handle's reference is replaced, as by lsgpu_icp_filter_reference_normals (the search runs on
+ *    the handle's own grid).  lsgpu_icp_compute* rebuild the reference anyway; a caller of lsgpu_icp_align must call
+ *    lsgpu_icp_set_reference again.  With normals_knn 0 the reference is untouched.
+ *  - After lsgpu_icp_comm_init (split-scan handle) normals_knn > 0 is LSGPU_BAD_CONFIG by name, as carried normals are.
+ * lsgpu_cloud_download: a slot's points to out_xyz1 (room for cap_points), and its normals where out_normals is given; host
+ * or device.  LSGPU_BAD_ARG with a text for an empty slot, cap_points smaller than the cloud, out_normals on a slot that
+ * carries none. */
+int lsgpu_cloud_ingest(lsgpu_icp* h, int slot, lsgpu_point_filter* filters, int n_filters, const float* xyz1, int64_t n,
+                       int64_t seed, int normals_knn, int orient, const float sensor[3], float* out_xyz1, float* out_normals,
+                       int64_t* n_out);
+int lsgpu_cloud_download(lsgpu_icp* h, int slot, float* out_xyz1, float* out_normals, int64_t cap_points);
+
 const char* lsgpu_strerror(int code);
 const char* lsgpu_last_error(lsgpu_icp* h); /* detail of the last failure on this handle */
 int         lsgpu_abi_version(void);

@@ -53,6 +53,11 @@ struct LsgpuCloudTraits {
     d.features.conservativeResize(d.features.rows(), (Eigen_Index)cols.size());
     if (d.descriptors.cols() > 0) d.descriptors.conservativeResize(d.descriptors.rows(), (Eigen_Index)cols.size());
   }
+  // the cloud's features become these m points (x, y, z, pad per point); for a cloud without descriptors
+  static void setFeatures(DataPoints& d, const float* xyz1, int64_t m) {
+    d.features.conservativeResize(d.features.rows(), (Eigen_Index)m);
+    if (m) std::memcpy(d.features.data(), xyz1, (size_t)m * 16);
+  }
   // the 6 x 6 matrix errorMinimizer->getCovariance() returns (PointMatcher<float>::Matrix) from 36 doubles, row major
   using Matrix = typename PM::Matrix;
   static Matrix matrix6(const double* c) {
@@ -91,6 +96,7 @@ struct LsgpuCloudTraits<LsgpuMirrorPM> {
     d.features.resize(4 * cols.size());
     if (nrm) d.normals.resize(3 * cols.size());
   }
+  static void setFeatures(DataPoints& d, const float* xyz1, int64_t m) { d.features.assign(xyz1, xyz1 + 4 * (size_t)m); }
   using Matrix = std::array<float, 36>;   // row major
   static Matrix matrix6(const double* c) {
     Matrix m;
@@ -98,6 +104,8 @@ struct LsgpuCloudTraits<LsgpuMirrorPM> {
     return m;
   }
 };
+
+template <class PM> class LsgpuDataPointsFilters;
 
 // ---- PointMatcher::ICP stand-in
 template <class PM>
@@ -134,15 +142,7 @@ class LsgpuICP {
   // x,y,z,1 per point and TransformationParameters is a 4x4 column-major float matrix: both are passed as they are.
   TransformationParameters compute(const DataPoints& reading, const DataPoints& reference,
                                    const TransformationParameters& T_init) {
-    if (!h_) {
-      if (lsgpu_icp_create(&mods_.chain.icp, device_, &h_) != LSGPU_OK)
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_create failed (no ROCm GPU visible?)");
-      if (lsgpu_icp_set_modules(h_, &mods_) != LSGPU_OK) {   // every module of the loaded chain, or none and the refusal
-        const std::string why = lsgpu_last_error(h_);
-        reset();
-        throw std::runtime_error("LsgpuICP: lsgpu_icp_set_modules: " + why);
-      }
-    }
+    ensureHandle();
     lsgpu_chain_config chain = mods_.chain.chain;
     chain.seed = seed_;
     TransformationParameters T = T_init;
@@ -159,6 +159,43 @@ class LsgpuICP {
     return T;
   }
   const lsgpu_icp_stats& lastStats() const { return stats_; }
+
+  // ---- scans kept on the device (include/lsgpu_icp.h, lsgpu_cloud_*): not PointMatcher calls, for a LaserTrack that keeps
+  // its recent scans in slots of this handle (lsgpu_icp_compute_clouds through handle()).
+  // uploadCloud: the cloud's points into `slot`, with its `normals` descriptor if loadFromYaml declared a side as carrying some.
+  void uploadCloud(int slot, const DataPoints& cloud) {
+    ensureHandle();
+    const bool nrm = mods_.carried && Traits::normals(cloud, &rd_normals_) && (int64_t)rd_normals_.size() == 3 * Traits::size(cloud);
+    const int rc = lsgpu_cloud_upload_normals(h_, slot, Traits::features(cloud), nrm ? rd_normals_.data() : nullptr, Traits::size(cloud));
+    if (rc != LSGPU_OK) throw std::runtime_error(std::string("LsgpuICP::uploadCloud: ") + lsgpu_strerror(rc) + " [" + lsgpu_last_error(h_) + "]");
+  }
+  // filters.apply(cloud) + uploadCloud(slot, cloud) with one upload of the raw scan (lsgpu_cloud_ingest): the chain runs on
+  // this handle, the kept cloud stays in `slot` and its features come back into `cloud`; draws, seed and FixStepSampling's
+  // state move as apply() moves them.  A cloud with descriptors goes the old way (apply() thins their columns on the host
+  // through a tag in the pad row, which must not reach the slot), and so does an empty chain.
+  void ingestCloud(int slot, DataPoints& cloud, LsgpuDataPointsFilters<PM>& filters) {
+    if (filters.filters_.empty() || Traits::hasDescriptors(cloud)) {
+      filters.apply(cloud);
+      uploadCloud(slot, cloud);
+      return;
+    }
+    const int64_t n = Traits::size(cloud);
+    if (n == 0) throw typename PM::ConvergenceError("no points to filter");
+    ensureHandle();
+    std::vector<float> out((size_t)n * 4);
+    int64_t m = 0;
+    const int rc = lsgpu_cloud_ingest(h_, slot, filters.filters_.data(), (int)filters.filters_.size(), Traits::features(cloud), n,
+                                      filters.seed_, 0, 0, nullptr, out.data(), nullptr, &m);
+    if (rc == LSGPU_NO_CONVERGENCE) throw typename PM::ConvergenceError("no points to filter");
+    if (rc != LSGPU_OK) throw std::runtime_error(std::string("LsgpuDataPointsFilters::apply: ") + lsgpu_strerror(rc));
+    Traits::setFeatures(cloud, out.data(), m);
+  }
+  int64_t cloudSize(int slot) {   // -1: the slot holds nothing
+    int64_t n = -1;
+    if (h_) lsgpu_cloud_size(h_, slot, &n);
+    return n;
+  }
+  lsgpu_icp* handle() { ensureHandle(); return h_; }
   // icp.errorMinimizer->getCovariance() becomes icp.getCovariance(): the 6 x 6 covariance of the last compute() of a chain
   // with PointToPlaneWithCovErrorMinimizer, in the PointMatcher matrix type (float).  Throws ConvergenceError before a
   // successful compute() and for a singular H, std::runtime_error if the chain does not name the module.
@@ -176,6 +213,16 @@ class LsgpuICP {
     reset();
   }
   void reset() { if (h_) { lsgpu_icp_destroy(h_); h_ = nullptr; } }
+  void ensureHandle() {
+    if (h_) return;
+    if (lsgpu_icp_create(&mods_.chain.icp, device_, &h_) != LSGPU_OK)
+      throw std::runtime_error("LsgpuICP: lsgpu_icp_create failed (no ROCm GPU visible?)");
+    if (lsgpu_icp_set_modules(h_, &mods_) != LSGPU_OK) {   // every module of the loaded chain, or none and the refusal
+      const std::string why = lsgpu_last_error(h_);
+      reset();
+      throw std::runtime_error("LsgpuICP: lsgpu_icp_set_modules: " + why);
+    }
+  }
   int device_ = 0;
   lsgpu_chain_modules mods_{};                          // the loaded chain: its configs, every module, the declaration of carried normals
   lsgpu_icp* h_ = nullptr;
@@ -251,6 +298,7 @@ class LsgpuDataPointsFilters {
   }
 
  private:
+  template <class> friend class LsgpuICP;   // LsgpuICP::ingestCloud runs this chain on the ICP's handle
   std::vector<lsgpu_point_filter> filters_;
   lsgpu_icp* h_ = nullptr;
   int device_ = 0;

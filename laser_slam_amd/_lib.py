@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "lsgpu_cloud_upload_normals", "lsgpu_cloud_has_normals", "lsgpu_icp_compute_normals",
     "lsgpu_icp_compute_clouds_upload_normals", "lsgpu_chain_load_carried", "lsgpu_chain_load_parts_carried",
     "lsgpu_surface_normal_params_check", "lsgpu_chain_load_modules", "lsgpu_icp_set_modules",
+    "lsgpu_cloud_ingest", "lsgpu_cloud_download",
 ]
 
 # lsgpu_chain_load_carried: which of a caller's clouds carry normals (LSGPU_CARRIED_*)
@@ -444,6 +445,9 @@ def lib() -> C.CDLL:
     L.lsgpu_chain_load_motion.argtypes = [C.POINTER(YamlModule), C.c_int, C.POINTER(MotionCfg), C.c_char_p, C.c_int]
     L.lsgpu_cloud_upload_normals.argtypes = [vp, C.c_int, fp, fp, i64]
     L.lsgpu_cloud_has_normals.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.lsgpu_cloud_ingest.argtypes = [vp, C.c_int, C.POINTER(PointFilter), C.c_int, fp, i64, i64, C.c_int, C.c_int,
+                                     C.POINTER(C.c_float), fp, fp, C.POINTER(i64)]
+    L.lsgpu_cloud_download.argtypes = [vp, C.c_int, fp, fp, i64]
     L.lsgpu_icp_compute_normals.argtypes = [vp, fp, fp, i64, fp, fp, i64, C.POINTER(C.c_float), C.POINTER(ChainCfg),
                                             C.POINTER(C.c_float), C.POINTER(IcpStats)]
     L.lsgpu_icp_compute_clouds_upload_normals.argtypes = [vp, C.c_int, fp, fp, i64, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int,

@@ -167,6 +167,7 @@ inline std::vector<YamlModule> parseYamlList(std::istream& in) {
 // modules kept (lsgpu_icp_reading_normals), the cloud's `normals` hold the result and travel with the scan from then on
 // (include/lsgpu_icp.h, "carried normals").  A point module behind that tail is a configuration error.  The tail is read only
 // where the caller asks for it (normals_tail; LaserTrack does): a caller that does not hand the normals on keeps the refusal.
+class ICP;
 class DataPointsFilters {
  public:
   DataPointsFilters() = default;
@@ -302,6 +303,7 @@ class DataPointsFilters {
   void apply(DataPoints& cloud);
 
  private:
+  friend class ICP;   // ICP::ingestCloud runs this chain on the ICP's handle: the modules' state, the seed and the tail are these
   void applyPointModules(DataPoints& cloud, int64_t n);
   std::vector<lsgpu_point_filter> filters_;
   lsgpu_icp* h_ = nullptr;
@@ -412,7 +414,45 @@ class ICP {
     const float* nrm = carriedNormals(cloud, LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE);
     if (nrm) check(lsgpu_cloud_upload_normals(h_, slot, cloud.features.data(), nrm, cloud.getNbPoints()), "lsgpu_cloud_upload_normals");
     else check(lsgpu_cloud_upload(h_, slot, cloud.features.data(), cloud.getNbPoints()), "lsgpu_cloud_upload");
+    ++traffic_.uploads;
   }
+  // filters.apply(cloud) + uploadCloud(slot, cloud) with the raw scan crossing to the device once (lsgpu_cloud_ingest): the
+  // chain's point modules and its normals tail run on THIS handle, the kept cloud stays in `slot` with its normals and comes
+  // back into `cloud` -- features, normals, `filters`' sampling state, seed and draws as apply() leaves them, its exception
+  // classes and texts.  Three cases go the old way, apply() then uploadCloud(): an empty chain; a cloud that arrives with
+  // normals and a chain without a normals tail (the tagged path, with its VoxelGrid / Octree refusals); a chain with a tail
+  // under a loadFromYaml that declared no side as carrying normals (uploadCloud stores no normals then, an ingest would).
+  void ingestCloud(int slot, DataPoints& cloud, DataPointsFilters& filters) {
+    const bool tail = filters.producesNormals();
+    if (filters.empty() || (!tail && !cloud.normals.empty()) ||
+        (tail && !(mods_.carried & (LSGPU_CARRIED_READING | LSGPU_CARRIED_REFERENCE)))) {
+      filters.apply(cloud);
+      uploadCloud(slot, cloud);
+      return;
+    }
+    ensureHandle();
+    if (tail) cloud.normals.clear();   // (a cloud that arrives with normals has them overwritten)
+    const int64_t n = cloud.getNbPoints();
+    std::vector<float> out((size_t)std::max<int64_t>(n, 1) * 4), nrm(tail ? (size_t)std::max<int64_t>(n, 1) * 3 : 0);
+    int64_t m = 0;
+    const int rc = lsgpu_cloud_ingest(h_, slot, filters.filters_.data(), (int)filters.filters_.size(), cloud.features.data(), n,
+                                      filters.seed_, filters.normals_knn_, filters.orient_, filters.sensor_, out.data(),
+                                      tail ? nrm.data() : nullptr, &m);
+    if (rc != LSGPU_OK) {
+      const std::string why = lsgpu_last_error(h_);
+      const bool in_tail = why.compare(0, 17, "reading_normals: ") == 0;
+      if (rc == LSGPU_NO_CONVERGENCE || (in_tail && m <= 0)) throw ConvergenceError("no points to filter");
+      if (rc == LSGPU_BAD_CONFIG) throw ConfigError("input filters: " + why);
+      throw DeviceError(std::string(in_tail ? "lsgpu_icp_reading_normals: " : "lsgpu_apply_point_filters: ") + lsgpu_strerror(rc) + " [" + why + "]");
+    }
+    out.resize((size_t)m * 4);
+    cloud.features.swap(out);
+    if (tail) { nrm.resize((size_t)m * 3); cloud.normals.swap(nrm); }
+    ++traffic_.ingests;
+  }
+  // how scans reached the slots of this ICP so far:uploadCloud / computeCloudsUploading copies, ingestCloud runs on the device
+  struct SlotTraffic { uint64_t uploads = 0, ingests = 0; };
+  SlotTraffic slotTraffic() const { return traffic_; }
   void releaseCloud(int slot) { if (h_) lsgpu_cloud_release(h_, slot); }
   bool hasCloud(int slot) {
     if (!h_) return false;
@@ -468,6 +508,7 @@ class ICP {
                        : lsgpu_icp_compute_clouds_upload(h_, reading, cloud.features.data(), cloud.getNbPoints(), refs.data(),
                                                          flat.data(), (int)refs.size(), T_init.data(), &chain, T.data(), &stats_);
     if (!rigid) requireRigid(T_init);
+    ++traffic_.uploads;   // (the slot holds the scan whatever the registration's outcome)
     check(rc, nrm ? "lsgpu_icp_compute_clouds_upload_normals" : "lsgpu_icp_compute_clouds_upload");
     return T;
   }
@@ -631,6 +672,7 @@ class ICP {
   lsgpu_icp_stats stats_{};
   int64_t seed_ = -1;
   unsigned generation_ = 0;
+  SlotTraffic traffic_;
 #ifdef LSGPU_TEST_SEAMS
   ComputeOverride override_;
   ComputeObserver observer_;

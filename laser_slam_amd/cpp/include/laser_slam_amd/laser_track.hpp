@@ -73,6 +73,9 @@ struct LaserTrackParams {  // laser_slam/include/laser_slam/parameters.hpp:8-23
   int scans_on_device = 16;             // most recent scans kept in HBM for sub-map assembly (0: host assembly)
   bool overlap_scan_copy = true;        // processPoseAndLaserScan with an empty input chain: the host copy of the scan is made
                                         // beside the device's registration instead of in front of it (not a reference parameter)
+  bool ingest_on_device = false;        // the input chain (and its normals tail) runs on the ICP's handle, the kept scan stays in the
+                                        // slot it will own: one upload per scan, no second one for the registration
+                                        // (ICP::ingestCloud; same scans, same transformations; not a reference parameter)
 };
 
 // Factor / FactorList / Values: pose_graph.hpp
@@ -145,7 +148,10 @@ class LaserTrack {
   void processLaserScan(const LaserScan& in_scan) {  // laser_track.cpp:74-120
     std::lock_guard<std::recursive_mutex> lock(mutex_);
     LaserScan scan = in_scan;
-    input_filters_.apply(scan.scan);  // laser_track.cpp:81
+    // (the ICP below runs on the scans stored so far, the new one is stored behind it: one slot more must be free)
+    const size_t stored = laser_scans_.size();
+    if (!ingestScan(&scan, stored, params_.use_icp_factors && stored > 1u ? subMapMembers(stored) + 2 : 1))
+      input_filters_.apply(scan.scan);  // laser_track.cpp:81
     // (this entry point runs the ICP BEFORE it stores the new scan, laser_track.cpp:112-119: the transformation it
     // records matches the previously stored scan against its predecessors)
     registerScan(&scan, nullptr, /*icp_before_store=*/true);
@@ -187,9 +193,14 @@ class LaserTrack {
       copy.armed = true;   // (registerScan below stores the scan, points to follow, before it runs the ICP)
     } else {
       scan.scan = in_scan.scan;
-      input_filters_.apply(scan.scan);  // laser_track.cpp:146
+      // (registerScan stores the scan as number `stored`, then matches it against the sub-map of the scans before it)
+      const size_t stored = laser_scans_.size();
+      if (!ingestScan(&scan, stored, params_.use_icp_factors && stored > 0u ? subMapMembers(stored + 1) + 1 : 1))
+        input_filters_.apply(scan.scan);  // laser_track.cpp:146
     }
+    const double ingest_ms = stage_times_.ingest_ms;
     stage_times_ = StageTimes{};
+    stage_times_.ingest_ms = overlap ? 0.0 : ingest_ms;
     stage_times_.copy_ms = msSince(t0);
     pose_measurements_.push_back(pose);
     const bool first = trajectory_.isEmpty();
@@ -307,8 +318,9 @@ class LaserTrack {
   const std::vector<RelativePose>& getOdometryMeasurements() const { return odometry_measurements_; }
   const lsgpu_icp_stats& lastIcpStats() const { return icp_.lastStats(); }
   // where the wall time of the last processPoseAndLaserScan went (milliseconds; not a reference accessor): the working copy
-  // of the scan + the input filters, the scans that had to cross PCIe, icp_.compute on the resident clouds
-  struct StageTimes { double copy_ms = 0, upload_ms = 0, icp_ms = 0; };
+  // of the scan + the input filters, the scans that had to cross PCIe, icp_.compute on the resident clouds; ingest_ms: the
+  // part of copy_ms spent in ICP::ingestCloud (ingest_on_device; 0 where the scan went through apply())
+  struct StageTimes { double copy_ms = 0, upload_ms = 0, icp_ms = 0, ingest_ms = 0; };
   const StageTimes& lastStageTimes() const { return stage_times_; }
   ICP& icp() { return icp_; }  // configuration access (seed, test seam); the reference keeps icp_ private
   DataPointsFilters& inputFilters() { return input_filters_; }
@@ -481,6 +493,30 @@ class LaserTrack {
     icp.key_b = getPoseKey(icp.time_b_ns);
     icp.track_id_a = icp.track_id_b = laser_track_id_;
     icp_transformations_.push_back(icp);
+  }
+
+  // members of the sub-map localScanToSubMap builds when `n` scans are stored (n >= 2)
+  size_t subMapMembers(size_t n) const { return 1 + std::min(n - 2, size_t(std::max(params_.nscan_in_sub_map, 1) - 1)); }
+
+  // ingest_on_device: the new scan, which will be stored as number `index`, goes through the input chain on the ICP's handle
+  // and stays in the slot it will own; `resident` = the scans the coming registration needs in slots at once, this one
+  // included -- where they do not fit (localScanToSubMap's own condition) the slot may belong to a member, and where a seam
+  // wants the host's clouds or the chain is empty there is nothing to gain: false, and the caller runs apply().
+  // What apply() throws, this throws; the slot is nobody's then.
+  bool ingestScan(LaserScan* scan, size_t index, size_t resident) {
+    stage_times_.ingest_ms = 0;
+    bool on = params_.ingest_on_device && params_.scans_on_device > 0 && !icp_.hasComputeOverride() && !input_filters_.empty() &&
+              resident <= (size_t)params_.scans_on_device;
+#ifdef LSGPU_TEST_SEAMS
+    on = on && !icp_.hasComputeObserver();
+#endif
+    if (!on) return false;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int slot = claimSlot(index);
+    icp_.ingestCloud(slot, scan->scan, input_filters_);
+    confirmSlot(slot, index);
+    stage_times_.ingest_ms = msSince(t0);
+    return true;
   }
 
   // (is scan `index` in its slot already?  /  its slot, reserved for it: the fused call uploads (lsgpu_icp_compute_clouds_upload),

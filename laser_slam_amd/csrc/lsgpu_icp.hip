@@ -3387,12 +3387,8 @@ static int octree_grid_filter_device(lsgpu_icp* h, const float4* src, int64_t m,
   return LSGPU_OK;
 }
 
-int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
-                              int64_t n, int64_t seed, float* out_xyz1, int64_t* n_out) {
-  if (!h || !n_out || n_filters < 0 || (n_filters > 0 && !filters) || n < 0 || (n > 0 && (!xyz1 || !out_xyz1))) return LSGPU_BAD_ARG;
-  h->err.clear();
-  *n_out = 0;
-  if (n > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
+// the parameter checks of lsgpu_apply_point_filters (and of lsgpu_cloud_ingest): LSGPU_OK, or LSGPU_BAD_CONFIG with the text
+static int point_filters_check(lsgpu_icp* h, const lsgpu_point_filter* filters, int n_filters) {
   for (int k = 0; k < n_filters; ++k) {
     const lsgpu_point_filter& f = filters[k];
     const bool ok = (f.type == LSGPU_FILTER_MAX_DIST || f.type == LSGPU_FILTER_MIN_DIST) ? (f.dim >= -1 && f.dim <= 2)
@@ -3410,18 +3406,16 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
     }
     if (!ok) { h->err = "apply_point_filters: unknown filter type or parameter out of range"; return LSGPU_BAD_CONFIG; }
   }
-  if (seed >= 0) DrawStream::global().take(seed, 0, nullptr);
-  // DataPointsFilters::apply: an empty CHAIN is a no-op; otherwise the first filter that is handed an empty cloud throws
-  // ConvergenceError("no points to filter") -- also when the cloud came in empty
-  if (n == 0) {
-    if (n_filters == 0) return LSGPU_OK;
-    h->err = "apply_point_filters: no points to filter";
-    return LSGPU_NO_CONVERGENCE;
-  }
-  HIPC(hipSetDevice(h->device));
-  const float4* cur = nullptr;
-  int rc = stage_points(h, xyz1, n, h->flt_in, &cur);
-  if (rc) return rc;
+  return LSGPU_OK;
+}
+
+// The point modules of a chain on a staged cloud (`src`, n > 0 points on the device): the kept cloud is *out (src itself
+// for an empty chain, else one of the handle's two filter buffers), *m_out points, enqueued on the handle's stream.
+// Draws and FixStepSampling's `state` move as lsgpu_apply_point_filters documents; both of its callers are this function.
+static int point_filters_run(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float4* src, int64_t n,
+                             const float4** out, int64_t* m_out) {
+  const float4* cur = src;
+  int rc = LSGPU_OK;
   HIPC(h->flt_ref.reserve(n));
   HIPC(h->flt_rd.reserve(n));
   HIPC(h->ssn_keep.reserve(n));
@@ -3466,6 +3460,34 @@ int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_f
     cur = ping;
     std::swap(ping, pong);
   }
+  *out = cur;
+  *m_out = m;
+  return LSGPU_OK;
+}
+
+int lsgpu_apply_point_filters(lsgpu_icp* h, lsgpu_point_filter* filters, int n_filters, const float* xyz1,
+                              int64_t n, int64_t seed, float* out_xyz1, int64_t* n_out) {
+  if (!h || !n_out || n_filters < 0 || (n_filters > 0 && !filters) || n < 0 || (n > 0 && (!xyz1 || !out_xyz1))) return LSGPU_BAD_ARG;
+  h->err.clear();
+  *n_out = 0;
+  if (n > 0x7FFFFFF0ll) return LSGPU_BAD_ARG;
+  int rc = point_filters_check(h, filters, n_filters);
+  if (rc) return rc;
+  if (seed >= 0) DrawStream::global().take(seed, 0, nullptr);
+  // DataPointsFilters::apply: an empty CHAIN is a no-op; otherwise the first filter that is handed an empty cloud throws
+  // ConvergenceError("no points to filter") -- also when the cloud came in empty
+  if (n == 0) {
+    if (n_filters == 0) return LSGPU_OK;
+    h->err = "apply_point_filters: no points to filter";
+    return LSGPU_NO_CONVERGENCE;
+  }
+  HIPC(hipSetDevice(h->device));
+  const float4* cur = nullptr;
+  rc = stage_points(h, xyz1, n, h->flt_in, &cur);
+  if (rc) return rc;
+  int64_t m = 0;
+  rc = point_filters_run(h, filters, n_filters, cur, n, &cur, &m);
+  if (rc) return rc;
   *n_out = m;
   if (m) HIPC(hipMemcpyAsync(out_xyz1, cur, (size_t)m * 16, hipMemcpyDefault, h->stream));
   HIPC(hipStreamSynchronize(h->stream));
@@ -3580,6 +3602,87 @@ int lsgpu_cloud_release(lsgpu_icp* h, int slot) {
 int lsgpu_cloud_size(lsgpu_icp* h, int slot, int64_t* n) {
   if (!h || !n || slot < 0) return LSGPU_BAD_ARG;
   *n = (size_t)slot < h->clouds.size() ? h->cloud_n[slot] : -1;
+  return LSGPU_OK;
+}
+
+// the device half of lsgpu_cloud_ingest; the caller has cleared the slot and confirms it on LSGPU_OK
+static int cloud_ingest_run(lsgpu_icp* h, int slot, lsgpu_point_filter* filters, int n_filters, const float* xyz1, int64_t n,
+                            int normals_knn, int orient, const float sensor[3], int64_t* kept) {
+  const float4* cur = nullptr;
+  int64_t m = 0;
+  if (n == 0) {
+    if (n_filters) { h->err = "apply_point_filters: no points to filter"; return LSGPU_NO_CONVERGENCE; }
+  } else {
+    int rc = stage_points(h, xyz1, n, h->flt_in, &cur);
+    if (!rc) rc = point_filters_run(h, filters, n_filters, cur, n, &cur, &m);
+    if (rc) return rc;
+  }
+  *kept = m;
+  HIPC(h->clouds[slot].reserve(m ? m : 1));
+  if (!normals_knn) {
+    if (m) HIPC(hipMemcpyAsync(h->clouds[slot].p, cur, (size_t)m * 16, hipMemcpyDeviceToDevice, h->stream));
+    return LSGPU_OK;
+  }
+  // lsgpu_icp_reading_normals on the kept cloud where it lies: its texts, the grid on this handle
+  const char* why = m < normals_knn ? "filter_reference_normals: the cloud has fewer points than knn"
+                    : m > 0x7FFFFFF0ll / normals_knn ? "filter_reference_normals: knn x n exceeds the 32-bit pair count" : nullptr;
+  if (why) { h->err = std::string("reading_normals: ") + why; return LSGPU_BAD_ARG; }
+  int rc = lsgpu_icp_set_reference(h, reinterpret_cast<const float*>(cur), nullptr, m);
+  if (!rc) rc = snf_device(h, normals_knn, nullptr, nullptr);
+  if (rc) { h->err = std::string("reading_normals: ") + (h->err.empty() ? lsgpu_strerror(rc) : h->err); return rc; }
+  HIPC(h->cloud_nrm[slot].reserve((size_t)3 * m));
+  const float s3[3] = {orient ? sensor[0] : 0.f, orient ? sensor[1] : 0.f, orient ? sensor[2] : 0.f};
+  hipLaunchKernelGGL(k_ingest_store, dim3(nblk(m)), dim3(256), 0, h->stream, cur, (int)m, (const uint32_t*)h->ref_inv.p,
+                     (const float4*)h->nrm.p, s3[0], s3[1], s3[2], orient, h->clouds[slot].p, h->cloud_nrm[slot].p);
+  HIPC(hipGetLastError());
+  return LSGPU_OK;
+}
+
+int lsgpu_cloud_ingest(lsgpu_icp* h, int slot, lsgpu_point_filter* filters, int n_filters, const float* xyz1, int64_t n,
+                       int64_t seed, int normals_knn, int orient, const float sensor[3], float* out_xyz1, float* out_normals,
+                       int64_t* n_out) {
+  if (!h || slot < 0 || slot >= (1 << 20) || n_filters < 0 || (n_filters > 0 && !filters) || n < 0 || n > 0x7FFFFFF0ll ||
+      (n > 0 && !xyz1))
+    return LSGPU_BAD_ARG;
+  h->err.clear();
+  if (n_out) *n_out = 0;
+  int rc = point_filters_check(h, filters, n_filters);
+  if (rc) return rc;
+  if (normals_knn != 0 && (normals_knn < kSnfMinKnn || normals_knn > kSnfMaxKnn)) { h->err = "cloud_ingest: normals_knn must be 0 or in [3, 32]"; return LSGPU_BAD_ARG; }
+  if (orient < 0 || orient > 2) { h->err = "cloud_ingest: orient must be 0, 1 or 2"; return LSGPU_BAD_ARG; }
+  if (orient && !sensor) { h->err = "cloud_ingest: orient needs the sensor position"; return LSGPU_BAD_ARG; }
+  if (orient && !normals_knn) { h->err = "cloud_ingest: orient needs normals (normals_knn > 0)"; return LSGPU_BAD_ARG; }
+  if (out_normals && !normals_knn) { h->err = "cloud_ingest: out_normals needs normals (normals_knn > 0)"; return LSGPU_BAD_ARG; }
+  if (normals_knn && h->comm) {
+    h->err = "cloud_ingest: normals are not implemented on a split-scan handle (carried normals are refused there)";
+    return LSGPU_BAD_CONFIG;
+  }
+  if (seed >= 0) DrawStream::global().take(seed, 0, nullptr);
+  HIPC(hipSetDevice(h->device));
+  cloud_slot_clear(h, slot);
+  int64_t m = 0;
+  rc = cloud_ingest_run(h, slot, filters, n_filters, xyz1, n, normals_knn, orient, sensor, &m);
+  if (rc) { if (n_out) *n_out = m; return rc; }   // (what the point modules kept, where the normals' step refused it)
+  if (m && out_xyz1) HIPC(hipMemcpyAsync(out_xyz1, h->clouds[slot].p, (size_t)m * 16, hipMemcpyDefault, h->stream));
+  if (m && out_normals) HIPC(hipMemcpyAsync(out_normals, h->cloud_nrm[slot].p, (size_t)m * 12, hipMemcpyDefault, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  h->cloud_n[slot] = m;
+  h->cloud_has_nrm[slot] = normals_knn ? 1 : 0;
+  if (n_out) *n_out = m;
+  return LSGPU_OK;
+}
+
+int lsgpu_cloud_download(lsgpu_icp* h, int slot, float* out_xyz1, float* out_normals, int64_t cap_points) {
+  if (!h || slot < 0 || !out_xyz1) return LSGPU_BAD_ARG;
+  h->err.clear();
+  if ((size_t)slot >= h->clouds.size() || h->cloud_n[slot] < 0) { h->err = "cloud_download: empty slot"; return LSGPU_BAD_ARG; }
+  const int64_t n = h->cloud_n[slot];
+  if (cap_points < n) { h->err = "cloud_download: the buffer is smaller than the cloud"; return LSGPU_BAD_ARG; }
+  if (out_normals && !cloud_has_normals(h, slot)) { h->err = "cloud_download: the slot carries no normals"; return LSGPU_BAD_ARG; }
+  HIPC(hipSetDevice(h->device));
+  if (n) HIPC(hipMemcpyAsync(out_xyz1, h->clouds[slot].p, (size_t)n * 16, hipMemcpyDefault, h->stream));
+  if (n && out_normals) HIPC(hipMemcpyAsync(out_normals, h->cloud_nrm[slot].p, (size_t)n * 12, hipMemcpyDefault, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
   return LSGPU_OK;
 }
 

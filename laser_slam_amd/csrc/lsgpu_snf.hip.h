@@ -293,4 +293,22 @@ __global__ __launch_bounds__(256) void k_orient_normals(const float4* __restrict
   }
 }
 
+// lsgpu_cloud_ingest's last step: the kept cloud and its normals into a cloud slot, one thread per point of the cloud AS
+// STAGED (thread i = point i, so the 16-byte point load, the 16-byte point store and the 12-byte normal store of a wave are
+// contiguous; the one gather is the normal, through inv as k_md_pass reads it).  It stands for k_snf_unpermute,
+// k_orient_normals (its nrm3 layout) and the two copies into the slot: the point's bits are the staged ones, the normal's
+// are nrm[inv[i]]'s, negated where normal_angle::flips says so (mode 0: never) -- the very values those kernels leave.
+// No LDS, no atomics; out_pts / out_nrm are the slot's own buffers and never alias the inputs.
+__global__ __launch_bounds__(256) void k_ingest_store(const float4* __restrict__ staged, int n, const uint32_t* __restrict__ inv,
+                                                      const float4* __restrict__ nrm, float sx, float sy, float sz, int mode,
+                                                      float4* __restrict__ out_pts, float* __restrict__ out_nrm) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = staged[i];
+  float4 v = nrm[inv[i]];
+  if (normal_angle::flips(p.x, p.y, p.z, sx, sy, sz, v.x, v.y, v.z, mode)) { v.x = -v.x; v.y = -v.y; v.z = -v.z; }
+  out_pts[i] = p;
+  out_nrm[3 * (size_t)i + 0] = v.x; out_nrm[3 * (size_t)i + 1] = v.y; out_nrm[3 * (size_t)i + 2] = v.z;
+}
+
 }  // namespace lsgpu

@@ -698,6 +698,46 @@ class IcpHandle:
         if rc != _lib.OK:
             _raise(rc, "lsgpu_cloud_upload", self._h)
 
+    def cloud_ingest(self, slot: int, cloud, filters, seed: int = -1, normals_knn: int = 0, orient: int = 0,
+                     sensor=(0.0, 0.0, 0.0), download: bool = True):
+        """lsgpu_cloud_ingest: the raw scan through `filters` (ctypes array of _lib.PointFilter, as apply_point_filters takes
+        it) and, with normals_knn > 0, SurfaceNormalDataPointsFilter (+ the orientation pair) on this handle, into `slot`.
+        -> (points, normals | None) of the kept cloud, numpy for a host cloud and torch for a device one; download=False:
+        nothing comes back, (None, None) -- the cloud is in the slot (cloud_download)."""
+        p, _k, n = _as_f32(cloud, 4)
+        sv = np.ascontiguousarray(sensor, np.float32).reshape(3)
+        o = on = None
+        po = pn = None
+        if download:
+            o, po = self._filter_out(cloud, n)
+            if normals_knn:
+                if _is_torch(o):
+                    on = torch.empty((max(n, 1), 3), dtype=torch.float32, device=o.device)
+                    torch.cuda.synchronize()
+                    pn = on.data_ptr()
+                else:
+                    on = np.empty((max(n, 1), 3), np.float32)
+                    pn = on.ctypes.data
+        m = C.c_int64(0)
+        rc = _lib.lib().lsgpu_cloud_ingest(self._h, slot, filters, len(filters), p, n, seed, int(normals_knn), int(orient),
+                                           _fp(sv), po, pn, C.byref(m))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_cloud_ingest", self._h)
+        if not download:
+            return None, None
+        return o[:m.value], (on[:m.value] if on is not None else None)
+
+    def cloud_download(self, slot: int):
+        """lsgpu_cloud_download: -> (points (N, 4), normals (N, 3) | None) of what the slot holds, as numpy arrays."""
+        n = self.cloud_size(slot)
+        has = n >= 0 and self.cloud_has_normals(slot)
+        o = np.empty((max(n, 1), 4), np.float32)
+        on = np.empty((max(n, 1), 3), np.float32) if has else None
+        rc = _lib.lib().lsgpu_cloud_download(self._h, slot, o.ctypes.data, on.ctypes.data if has else None, max(n, 0))
+        if rc != _lib.OK:
+            _raise(rc, "lsgpu_cloud_download", self._h)
+        return o[:n], (on[:n] if has else None)
+
     def cloud_has_normals(self, slot: int) -> bool:
         has = C.c_int(0)
         _lib.lib().lsgpu_cloud_has_normals(self._h, slot, C.byref(has))
