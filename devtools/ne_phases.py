@@ -27,5 +27,8 @@ print("per block (shader cycles): prologue %.0f | main loop %.0f | wave+block re
 print("wall (us, 100 MHz clock): first start -> first loop start %.2f | first start -> last loop end %.2f | last loop end -> kernel end %.2f (update lane %.2f)"
       % (d[9] / n / 100, d[7] / n / 100, d[8] / n / 100, d[11] / n / 100))
 print("tail (us): last loop end -> last block knows it is last %.2f | partials + state + set-aside loads, first sums %.2f | set-aside ranking + sums %.2f | final sums, publish %.2f" % tuple(d[16:20] / n / 100))
-print("update lane (shader cycles per launch): unpack + LLT %.0f | delta, T update %.0f | trace record %.0f | checker %.0f" % tuple(d[12:16] / n))
+# (the staged update as lane 0 sees it; under LSGPU_SPLIT_UPDATE the serial lane of k_icp_update reports unpack + LLT |
+#  delta, T update | trace record | window + checker in slots 12 .. 15)
+print("staged update (shader cycles per launch, lane 0): stage 0 -- exits, solve, dT, Tn %.0f | barrier, stage 1 -- checker, verdict %.0f | "
+      "waiting for the trace's, the window's and the T rows' waves %.0f" % tuple(d[12:15] / n))
 print("distances set aside per iteration (stats build):", [t["searching"] for t in h.trace()])

@@ -16,7 +16,16 @@
 //   dist^2    : fma(dz,dz, fma(dy,dy, dx*dx))
 // The whole TU is compiled with -ffp-contract=off: every fused op is written out.
 #pragma once
+#if defined(LSGPU_UPDATE_HOST_CHECK)
+// tests/cpp/update_stages_check.cpp: a host compiler takes the loop state, the constants and the per-iteration update
+// (lsgpu_solve.hip.h) alone, to run the staged update against the serial one on the CPU
+#include <cmath>
+#include <cstring>
+#define __device__
+#define __forceinline__ inline
+#else
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 namespace lsgpu {
@@ -169,6 +178,7 @@ __device__ __forceinline__ bool iter_params(const IcpState* __restrict__ st, con
   return true;
 }
 
+#if !defined(LSGPU_UPDATE_HOST_CHECK)   // (device helpers from here to the end of the file)
 __device__ __forceinline__ float3 xform(const Mat34& T, float x, float y, float z) {
   float3 o;
   o.x = __fmaf_rn(T.m[2], z, __fmaf_rn(T.m[1], y, __fmaf_rn(T.m[0], x, T.m[3])));
@@ -307,5 +317,6 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   }
   return v;
 }
+#endif  // !LSGPU_UPDATE_HOST_CHECK
 
 }  // namespace lsgpu

@@ -4121,7 +4121,7 @@ struct AlignRun {
       hipLaunchKernelGGL(ne_loop_k, dim3(nb), dim3(256), 0, h->stream, h->rdq.p, np,
                          h->state.p, h->kmatch.p, h->kd2.p, (p2p && !(robust && ca.rb.plane) && !angle) ? (const float4*)nullptr : h->nrm.p, h->hist.p, h->sel.p + 2,
                          h->counters.p + 32, h->ne_tickets.p, h->ne_partials.p, h->ne_gpartials.p, h->ne_out.p,
-                         h->chk_hist.p, h->trace_dev.p, max_it, 0, (split_update && !robust && !angle) ? 0 : 1,
+                         h->chk_hist.p, h->trace_dev.p, max_it, 0, !split_update ? 1 : (robust || angle) ? 2 /* the serial update, in this launch */ : 0,
                          h->sel_aux.p, (uint32_t*)nullptr, 0, (uint32_t*)nullptr,
                          0, (uint32_t*)nullptr, (uint2*)nullptr, (double*)nullptr, 0, 0, ca_it);   // 6d (+6e)
       if (split_update && !robust && !angle)

@@ -17,6 +17,9 @@ struct SelState {
   uint32_t k;       // rank still to find inside the selected bin
 };
 
+// (LSGPU_UPDATE_HOST_CHECK, lsgpu_common.hip.h: the host check of the staged update compiles the structures and the
+// per-iteration update of this file, none of its kernels)
+#if !defined(LSGPU_UPDATE_HOST_CHECK)
 // Whole block (256 threads): find bin b with cum(b) <= k < cum(b)+hist[b] -- parallel: each thread
 // owns nbins/256 consecutive bins, block-wide inclusive scan of the per-thread sums, the one thread
 // whose range contains rank k walks its own bins.
@@ -210,6 +213,7 @@ __global__ __launch_bounds__(256) void k_chain_rank(const uint32_t* __restrict__
   if (sel_med0)
     for (int i = threadIdx.x; i < 2 * kHistBins; i += 256) hist_med[kHistBins + i] = 0u;
 }
+#endif  // !LSGPU_UPDATE_HOST_CHECK
 
 // RobustOutlierFilter's part of the loop state (its own two words: IcpState keeps its size, and with it the LDS copy every
 // instantiation of k_normal_eq_loop holds): written by k_mad_begin (median) and by the update lane (scale), read by the
@@ -248,6 +252,7 @@ struct ChainArgs {
   lsgpu_normal_angle_trace* na_trace;
 };
 
+#if !defined(LSGPU_UPDATE_HOST_CHECK)
 // Start of the MAD's select (one block, behind the median's select): the median goes to the loop's robust state, where the
 // three histogram passes over |d2 - median| read it (HistAbsDev); the rank m / 2 comes from the select's first table, which
 // has seen every distance of the iteration (k_chain_rank); the MAD's tables are cleared.
@@ -444,6 +449,9 @@ __global__ __launch_bounds__(256) void k_normal_eq(const float4* __restrict__ rd
     partials[(size_t)blockIdx.x * 32 + threadIdx.x] =
         ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
+#else
+inline uint32_t __float_as_uint(float f) { uint32_t u; std::memcpy(&u, &f, sizeof(u)); return u; }   // (the host check's stand-in)
+#endif  // !LSGPU_UPDATE_HOST_CHECK
 
 constexpr float kCapFactor = 1.1f;  // next search cap = this x the current trim limit (verified each iteration)
 
@@ -592,8 +600,175 @@ __device__ inline void icp_update_lane(IcpState* st, const double* ne_out, float
   if (!iterate) { st->converged = by_diff ? 1 : 0; st->done = 1; }
 }
 
+// ---------------------------------------------------------------- the staged update
+// icp_update_lane cut in two for the last block of k_normal_eq_loop: the same operations on the same operands in the same
+// order, value by value -- only the lane that executes them differs, so the loop state, the checker history and the trace
+// record get the bits the serial function gives them (k_icp_update keeps calling that one: under LSGPU_SPLIT_UPDATE it is
+// the reference the staged form is compared with, tests/test_update_stages.py; on the CPU
+// tests/cpp/update_stages_check.cpp runs both, stage by stage and thread by thread).
+// A stage is a function of (stage, thread, context); one barrier of the block separates the two, nothing else orders them.
+//   stage 0, lane 0: the early exits, the solve, the step dT and Tn = dT * T_iter, in registers as in the serial function
+//            (a failed solve ends the update here); what the consumers of (Tn, limit) need goes to the context
+//   stage 1, side by side -- none reads what another writes:
+//            lane 0: the checker, then status / converged / done from its verdict
+//            wave 1: the trace record, one value per lane and store (the sums straight from the last block's 32 doubles)
+//            wave 2, one lane: the select window's, the streak's and the cap's bookkeeping, iter
+//            wave 3: T_iter, T_rows_prev, T_rows
+// status, err_code, converged and done are written by lane 0 only.
+// (Measured and dropped: the LLT spread over the lanes of wave 0 with a barrier per column, and dT * T_iter on 16 lanes
+// behind one more -- a barrier and the trip through LDS cost as much as the divisions they take off lane 0; CHANGELOG.md.)
+struct UpdateArgs {   // icp_update_lane's arguments (sel_failed: 0 / 1, the flag already read)
+  IcpState* st; const double* ne_out; float* chk_hist; lsgpu_iter_trace* trace; int trace_cap, capped_launch, sel_failed;
+  const RobustIter* rb;   // RB only
+};
+struct UpdateCtx {    // what stage 0 hands stage 1 (the block's LDS)
+  double Mc[9], pq[6], xd[6];    // point-to-point: the trace's A[0..8], b and x
+  float x[6], Tn[16];
+  float limit;
+  int it;                        // IcpState::iter as the update found it
+  long long used;
+  unsigned long long nstrag;
+  int go;                        // stage 0 found no reason to leave
+};
+constexpr int kUpdateStages = 2;
+
+template <int MIN, bool RB = false>
+__device__ inline void icp_update_stage(int stage, int t, UpdateCtx& c, const UpdateArgs& a) {
+  IcpState* st = a.st;
+  const double* ne_out = a.ne_out;
+  if (stage == 0) {
+    if (t != 0) return;
+    c.go = 0;
+    if (st->done) return;
+    if (a.sel_failed) {
+      st->sel_mode = 0;
+      st->sel_fails += 1;
+      st->status = kStatusSelFailed;
+      st->done = 1;
+      return;
+    }
+    const float limit = (float)ne_out[29];
+    const unsigned long long nstrag = (unsigned long long)ne_out[30];
+    if (a.capped_launch && st->cap2 < INFINITY && !(limit <= st->cap2)) {
+      st->status = kStatusCapFailed;
+      st->done = 1;
+      return;
+    }
+    st->stragglers += nstrag;
+    long long used = (long long)ne_out[27];
+    if constexpr (RB) {
+      used = a.rb->used;
+      if (a.rb->mad && !(a.rb->scale > 0.f && a.rb->scale < INFINITY)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 5; st->done = 1; return; }
+      if (a.rb->bad > 0.0) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 6; st->done = 1; return; }
+    }
+    if (used <= 0) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 1; st->done = 1; return; }
+    double A[36], b[6];
+    float x[6], dT[16], Tn[16];
+    double xd[6];
+    if constexpr (MIN == kPointToPoint) {
+      for (int i = 0; i < 36; ++i) A[i] = 0.0;
+      if (!hostmath::point_to_point_delta(ne_out, dT, A, b, xd)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 4; st->done = 1; return; }
+      for (int i = 0; i < 9; ++i) c.Mc[i] = A[i];
+      for (int i = 0; i < 6; ++i) { c.pq[i] = b[i]; c.xd[i] = xd[i]; }
+    } else {
+      hostmath::unpack_normal_eq(ne_out, A, b);
+      if constexpr (MIN == kPointToPlane4Dof || MIN == kPointToPlane2D) {
+        if (!hostmath::point_to_plane_step_yaw<MIN == kPointToPlane2D ? 3 : 4>(A, b, x, dT)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 2; st->done = 1; return; }
+      } else {
+        if (!hostmath::llt_solve6(A, b, x)) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 2; st->done = 1; return; }
+        hostmath::delta_from_x(x, dT);
+      }
+      for (int i = 0; i < 6; ++i) c.x[i] = x[i];
+    }
+    hostmath::mul4(dT, st->T_iter, Tn);
+    for (int i = 0; i < 16; ++i) c.Tn[i] = Tn[i];
+    c.limit = limit; c.nstrag = nstrag; c.used = used; c.it = st->iter;
+    c.go = 1;
+    return;
+  }
+  if (!c.go) return;
+  const int it = c.it;
+  const float limit = c.limit;
+  if (t == 0) {
+    hostmath::CheckerState cs{st->counter, st->n_hist};
+    bool iterate = true, by_diff = false;
+    float chk2[2];
+    const bool ok = hostmath::checker_check(&cs, a.chk_hist, st->max_iter, st->smooth, st->lim_rot,
+                                            st->lim_trans, c.Tn, &iterate, &by_diff, chk2);
+    st->chk_rot_prev = st->chk_rot; st->chk_trans_prev = st->chk_trans;
+    st->chk_rot = chk2[0]; st->chk_trans = chk2[1];
+    st->counter = cs.counter; st->n_hist = cs.n_hist;
+    if (!ok) { st->status = LSGPU_NO_CONVERGENCE; st->err_code = 3; st->done = 1; return; }
+    if (!iterate) { st->converged = by_diff ? 1 : 0; st->done = 1; }
+  } else if (t >= 64 && t < 128) {
+    if (it < a.trace_cap) {
+      lsgpu_iter_trace& tr = a.trace[it];
+      for (int i = t - 64; i < (RB ? 75 : 70); i += 64) {
+        if (i < 16) tr.T_iter[i] = c.Tn[i];
+        else if (i < 52) {   // A: unpack_normal_eq's entry (r, cc) = the slot of (min, max) in the row-major upper triangle
+          const int e = i - 16, r = e / 6, cc = e % 6, lo = r < cc ? r : cc, hi = r < cc ? cc : r;
+          if constexpr (MIN == kPointToPoint) tr.A[e] = e < 9 ? c.Mc[e] : 0.0;
+          else tr.A[e] = ne_out[lo * 6 - lo * (lo - 1) / 2 + (hi - lo)];
+        }
+        else if (i < 58) { if constexpr (MIN == kPointToPoint) tr.b[i - 52] = c.pq[i - 52]; else tr.b[i - 52] = ne_out[21 + (i - 52)]; }
+        else if (i < 64) { if constexpr (MIN == kPointToPoint) tr.x[i - 58] = c.xd[i - 58]; else tr.x[i - 58] = c.x[i - 58]; }
+        else if (i == 64) tr.limit = limit;
+        else if (i == 65) tr.n_used = c.used;
+        else if (i == 66) tr.knn_main_us = 0.f;
+        else if (i == 67) tr.knn_fallback_us = 0.f;
+        else if (i == 68) tr.stragglers = (uint32_t)c.nstrag;
+        else if (i == 69) tr.reserved = (uint32_t)ne_out[31];
+        else if constexpr (RB) {
+          lsgpu_robust_trace& rt = a.rb->trace[it];
+          if (i == 70) rt.median = a.rb->median;
+          else if (i == 71) rt.scale = a.rb->scale;
+          else if (i == 72) rt.w_sum = ne_out[27];
+          else if (i == 73) rt.recomputed = a.rb->recomputed;
+          else rt.reserved = 0;
+        }
+      }
+    }
+    if constexpr (RB) { if (t == 127) a.rb->state->scale = a.rb->scale; }
+  } else if (t == 128) {
+    st->last_limit = limit; st->last_used = c.used;
+    const uint32_t lb = __float_as_uint(limit), b1 = lb >> 20, b2 = (lb >> 9) & 0x7FFu;
+    if (st->sel_wide) {
+      const float prev = st->prev_limit;
+      const bool armed = limit > 1e-30f && limit < 1e30f && prev < 1e30f && limit >= kSelArmLo * prev && limit <= kSelArmHi * prev && st->sel_fails < 2;
+      const float move = armed ? fabsf(limit - prev) / prev : 1.f;
+      const float f_lo = fmaxf(kSelWideLo, 1.f - 4.f * move - 0.01f), f_hi = fminf(2.f * kSelWideLo, 1.f + 4.f * move + 0.01f);
+      const uint32_t lo_s = __float_as_uint(limit * f_lo) >> kSelSliceShift, hi_s = (__float_as_uint(limit * f_hi) >> kSelSliceShift) + 1u;
+      st->sel_lo = lo_s << kSelSliceShift;
+      st->sel_span = (hi_s - lo_s < (uint32_t)kSelSlices ? hi_s - lo_s : (uint32_t)kSelSlices) << kSelSliceShift;
+      st->sel_shift = kSelSliceShift;
+      st->sel_streak = armed ? st->sel_streak + 1 : 0;
+      st->sel_mode = armed ? 1 : 0;
+    } else {
+      const uint32_t moved = b2 > st->sel_bin2 ? b2 - st->sel_bin2 : st->sel_bin2 - b2;
+      st->sel_streak = (b1 == st->sel_bin1 && moved <= (uint32_t)kSelStreakBins) ? st->sel_streak + 1 : 0;
+      st->sel_mode = (b1 == st->sel_bin1) ? 1 : 0;
+      st->sel_lo = b1 << 20; st->sel_span = 1u << 20; st->sel_shift = 9;
+    }
+    st->sel_bin1 = b1;
+    st->sel_bin2 = b2;
+    st->prev_limit = limit;
+    st->cap2 = st->cap_enabled ? limit * kCapFactor : INFINITY;
+    st->iter = it + 1;
+  } else if (t >= 192 && t < 192 + 16) {
+    const int i = t - 192;
+    st->T_iter[i] = c.Tn[i];
+    if (i < 12) {
+      st->T_rows_prev[i] = st->T_rows[i];
+      st->T_rows[i] = c.Tn[(i & 3) * 4 + (i >> 2)];   // rows of the column-major Tn
+    }
+  }
+}
+
+
+#if !defined(LSGPU_UPDATE_HOST_CHECK)   // (kernels from here to the end of the file)
 // stand-alone launch: used when something sits between the normal equations and the update (the RCCL
-// all-reduce of the split-scan mode); otherwise the last block of k_normal_eq_loop runs the update itself
+// all-reduce of the split-scan mode); otherwise the last block of k_normal_eq_loop runs the update itself,
+// in stages; this launch keeps the serial icp_update_lane
 template <int MIN>
 __global__ __launch_bounds__(64) void k_icp_update(IcpState* __restrict__ st,
                                                    const double* __restrict__ ne_out,
@@ -1196,23 +1371,29 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
   if (threadIdx.x == 0) w_pre = (unsigned long long)wall_clock64();
 #endif
   __syncthreads();
-  // wave 0's first lane advances the loop state; the other waves re-arm the iteration's scratch meanwhile (every
-  // block has read hist3 / the window table by now)
+  // the block advances the loop state in two stages (icp_update_stage); waves 1 to 3 first re-arm the iteration's scratch --
+  // stores only, on their way while lane 0 solves (every block has read hist3 / the window table by now).
+  // fuse_update: 0 the stand-alone k_icp_update follows; 1 the staged update; 2 (CHAIN instantiations, under
+  // LSGPU_SPLIT_UPDATE: the weighted launches and those with the angle test always run the update themselves) the serial
+  // icp_update_lane on lane 0 here -- the reference the staged form is compared with
+  const bool staged = fuse_update == 1;
   if (threadIdx.x == 0) {
     if constexpr (CHAIN) {   // (a launch with the angle test always runs the update itself: the record goes beside the iteration's)
       if (na_rn && chain.na_trace && !st_sh.done && st_sh.iter < trace_cap) {
         lsgpu_normal_angle_trace& nt = chain.na_trace[st_sh.iter];
         nt.rejected = (long long)red[2][32]; nt.eps = chain.na_eps; nt.reserved = 0;
       }
+      if (fuse_update == 2) {
+        RobustIter ri{};
+        if constexpr (RB) {
+          ri.used = (long long)red[0][32]; ri.bad = red[1][32]; ri.scale = rb_scale; ri.median = rb_med;
+          ri.recomputed = (chain.rb.mad && chain.rb_recompute) ? 1 : 0; ri.mad = chain.rb.mad;
+          ri.state = chain.rb_state; ri.trace = chain.rb_trace;
+        }
+        icp_update_lane<MIN, RB>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh, RB ? &ri : nullptr);
+      }
     }
-    if constexpr (RB) {   // (the weighted launches always run the update themselves)
-      RobustIter ri;
-      ri.used = (long long)red[0][32]; ri.bad = red[1][32]; ri.scale = rb_scale; ri.median = rb_med;
-      ri.recomputed = (chain.rb.mad && chain.rb_recompute) ? 1 : 0; ri.mad = chain.rb.mad;
-      ri.state = chain.rb_state; ri.trace = chain.rb_trace;
-      icp_update_lane<MIN, true>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh, &ri);
-    } else if (fuse_update) icp_update_lane<MIN>(&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, nullptr, (int)fail_sh);
-    else if (sel_aux && fail_sh) sel_aux[kSelFailFlag] = 1u;   // the stand-alone update kernel reads it there
+    if (!fuse_update && sel_aux && fail_sh) sel_aux[kSelFailFlag] = 1u;   // the stand-alone update kernel reads it there
   } else if (threadIdx.x >= 64) {
     const int t = (int)threadIdx.x - 64;
     for (int i = t; i < 3 * kHistBins; i += 192) hist[i] = 0u;
@@ -1222,6 +1403,37 @@ __global__ __launch_bounds__(256) void k_normal_eq_loop(const float4* __restrict
       uint4* w4 = reinterpret_cast<uint4*>(hist3w);
       for (int i = t; i < kSelWinRows * 512 / 4; i += 192) w4[i] = make_uint4(0u, 0u, 0u, 0u);
     }
+  }
+  if (staged) {
+    __shared__ UpdateCtx uctx;
+    RobustIter ri{};
+    if constexpr (RB) {
+      ri.used = (long long)red[0][32]; ri.bad = red[1][32]; ri.scale = rb_scale; ri.median = rb_med;
+      ri.recomputed = (chain.rb.mad && chain.rb_recompute) ? 1 : 0; ri.mad = chain.rb.mad;
+      ri.state = chain.rb_state; ri.trace = chain.rb_trace;
+    }
+    const UpdateArgs ua{&st_sh, fin, chk_hist, trace, trace_cap, capped_launch, (int)fail_sh, RB ? &ri : nullptr};
+#ifdef LSGPU_KNN_STATS
+    const long long u0 = clock64();
+#endif
+    icp_update_stage<MIN, RB>(0, (int)threadIdx.x, uctx, ua);
+#ifdef LSGPU_KNN_STATS
+    const long long u1 = clock64();
+#endif
+    __syncthreads();
+    icp_update_stage<MIN, RB>(1, (int)threadIdx.x, uctx, ua);
+    static_assert(kUpdateStages == 2, "two stages, one barrier");
+#ifdef LSGPU_KNN_STATS
+    {   // lane 0: stage 0 | the barrier | its part of stage 1 | until every wave is through stage 1 (a barrier the product does not need)
+      const long long u2 = clock64();
+      __syncthreads();
+      const long long u3 = clock64();
+      if (threadIdx.x == 0) {
+        g_ne_dbg[12] += (unsigned long long)(u1 - u0); g_ne_dbg[13] += (unsigned long long)(u2 - u1);
+        g_ne_dbg[14] += (unsigned long long)(u3 - u2);
+      }
+    }
+#endif
   }
   if (fuse_update) {
     __syncthreads();
@@ -1258,5 +1470,6 @@ __global__ __launch_bounds__(1024) void k_ne_final(const double* __restrict__ pa
     out[threadIdx.x] = t;
   }
 }
+#endif  // !LSGPU_UPDATE_HOST_CHECK
 
 }  // namespace lsgpu

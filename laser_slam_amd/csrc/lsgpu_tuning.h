@@ -37,7 +37,8 @@
 //   LSGPU_SSN_ROOT           0  points per workgroup of k_ssn_tree (0: by size -- 2048 below 819 200 points, 4096 below
 //                               1 638 400, 8192 from there; 2048, 4096, 8192)
 //   LSGPU_NE_BLOCKS        256  blocks of k_normal_eq_loop (64 .. 2048)
-//   LSGPU_SPLIT_UPDATE          the per-iteration update as its own launch (profiling)
+//   LSGPU_SPLIT_UPDATE          the per-iteration update as its own launch (profiling), and always the serial
+//                               icp_update_lane: the reference of the staged update of k_normal_eq_loop's last block
 //   LSGPU_COMM_TIMEOUT_MS 30000 bound on every stream wait of the split-scan mode
 //   LSGPU_CONE_HEAVY_STEPS / _SHARE  price check before the first search through the index: lanes whose windows would hold more
 //                               than STEPS (1024) evaluation steps are heavy; more than SHARE (0.07; 2 = never) of them: voxel grid
